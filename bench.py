@@ -10,6 +10,8 @@ trainers/single_window_trainer.py:68-147), all in the HIP kernels behind libvqwn
 Rank 0 prints ONE JSON line.  Extra fields: `roofline` for the dominant kernel family (timed with HIP
 events on the launch stream inside the timed region) and `cpu_baseline` (the CPU oracle timed on the
 host cores, rank 0, N=1 only, bounded sample).
+`--dump-outputs DIR` writes what the last timed step returned (losses, codebook ids, reconstructions, embeddings) as
+DIR/<name>.npy; the inputs and initial weights are seeded, so two builds run with the same arguments compare output for output.
 """
 import argparse
 import ctypes
@@ -109,6 +111,43 @@ def cpu_baseline(size):
                        "batch 4), 3 timed steps on %d threads" % (torch.__version__, size, size, cores, cores))
 
 
+DUMP_MAX_ELEMS = 1 << 21        # per array: larger outputs are written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """Write the arrays of one training step's result dict as <path>/<name>.npy: floating tensors as float32, integer tensors
+    (codebook ids) as float32 when exact there (float64 otherwise), scalars as float64.  A tensor of more than
+    DUMP_MAX_ELEMS elements is written as the 1-D sample of its flattened elements at sorted indices drawn from a
+    generator seeded with 0: the same indices for the same shape, so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name in sorted(out):
+        v = out[name]
+        if not torch.is_tensor(v):
+            a = np.asarray(float(v), dtype=np.float64)
+        else:
+            t = v.detach()
+            if t.numel() > DUMP_MAX_ELEMS:
+                g = torch.Generator().manual_seed(0)
+                idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+                t = t.reshape(-1)[idx.to(t.device)]
+            t = t.cpu()
+            if t.dim() == 0:
+                a = t.double().numpy()
+            elif t.is_floating_point():
+                a = t.float().numpy()
+            else:
+                a = t.double().numpy()
+                if np.abs(a).max(initial=0) < 2 ** 24:
+                    a = a.astype(np.float32)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, "--dump-outputs: more than %d MB" % (DUMP_MAX_BYTES >> 20)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -124,7 +163,11 @@ def main():
                          "remaining backward kernels), 0 = after the backward pass; default: VQW_DP_OVERLAP or 0")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (bench.dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.dp_overlap is not None:
         os.environ["VQW_DP_OVERLAP"] = str(args.dp_overlap)
@@ -215,6 +258,10 @@ def main():
     prof = (ctypes.c_double * 24)()
     if timing:
         _lib.check(L.vqw_profile_end(prof), "vqw_profile_end")
+    if args.dump_outputs and rank == 0:     # before the serialised pass below runs further steps
+        nbytes = dump_outputs(out, args.dump_outputs)
+        print("[bench] last timed step's outputs: %d arrays, %.1f MB in %s" % (len(out), nbytes / 2**20, args.dump_outputs),
+              file=sys.stderr, flush=True)
     # Second, untimed look at the same kernels WITHOUT concurrency: in the timed region the weight-gradient kernels run
     # on a side stream next to the chain kernels, which stretches every kernel's own duration.  Two extra steps with
     # the side stream off give the kernels' exclusive durations (reported as roofline.exclusive).

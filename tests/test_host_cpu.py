@@ -470,3 +470,27 @@ def test_winograd_kernels_hold_no_inline_asm_arithmetic_and_no_packed_adds(tmp_p
             for line in block.strip().splitlines():
                 line = line.strip()
                 assert line == "" or line.startswith(";") or line.startswith("v_mov_b32"), "%s: inline asm holds %r" % (f, line)
+
+
+def test_bench_dump_outputs_format(tmp_path):
+    """bench.py --dump-outputs: one float32 / float64 .npy per entry of the step's result dict, integer ids exact, tensors
+    beyond DUMP_MAX_ELEMS as the same seeded sample every time, the whole dump within DUMP_MAX_BYTES."""
+    import bench
+    g = torch.Generator().manual_seed(3)
+    big = torch.randn(3, 16, 256, 256, generator=g).to(memory_format=torch.channels_last)
+    assert big.numel() > bench.DUMP_MAX_ELEMS
+    out = dict(total=torch.tensor(2.5, requires_grad=True) * 1, dist=0.0, ids_2=torch.randint(0, 11, (4, 64, 64), generator=g).transpose(1, 2),
+               recon_1=torch.randn(4, 1, 64, 64, generator=g), embed_1=big)
+    n = bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in out)
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in out}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert n == sum(v.nbytes for v in a.values()) <= bench.DUMP_MAX_BYTES
+    assert a["total"].dtype == np.float64 and a["total"].shape == () and float(a["total"]) == 2.5 and float(a["dist"]) == 0.0
+    assert np.array_equal(a["ids_2"], out["ids_2"].numpy().astype(np.float32))
+    assert np.array_equal(a["recon_1"], out["recon_1"].numpy())
+    idx = torch.randint(0, big.numel(), (bench.DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(a["embed_1"], big.reshape(-1)[idx].numpy())
+    for k in out:
+        assert np.array_equal(a[k], np.load(tmp_path / "b" / (k + ".npy"))), k
