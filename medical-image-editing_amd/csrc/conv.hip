@@ -21,8 +21,6 @@ static double g_prof_flops[PROF_MAX];
 static double g_prof_bytes[PROF_MAX];
 static int g_prof_family[PROF_MAX];
 
-static const int g_pw_wgrad = []{ const char* e = getenv("VQW_PW_WGRAD"); return e ? atoi(e) : 1; }();      // 0: 1x1 weight gradients on the split-K GEMM kernel (A/B)
-
 extern "C" int vqw_profile_begin(void) {
     if (!g_prof_ev) {
         g_prof_ev = (hipEvent_t*)malloc(sizeof(hipEvent_t) * 2 * PROF_MAX);
@@ -267,7 +265,7 @@ extern "C" int vqw_conv2d_wgrad(const float* src0, int C0, int up0, const float*
         ProfScope ps(3, flops, st, bytes);
         return conv_head_wgrad(in, dy, dw_ohwi, dbias, wsf, (long)N * H * W, accumulate, st);
     }
-    if (g_conv_backend == 0 && g_pw_wgrad && conv_pw_wgrad_ok(in, Cout, ksize, (long)N * H * W)) {
+    if (g_conv_backend == 0 && conv_pw_wgrad_ok(in, Cout, ksize, (long)N * H * W)) {
         ProfScope ps(1, flops, st, bytes);
         if (dbias) {
             rc = bias_grad(dy, dbias, wsf, (long)N * H * W, Cout, st, accumulate);
@@ -417,9 +415,8 @@ extern "C" int vqw_conv3x3_wino_fwd_acc(const float* x, const void* ws, float* y
 // A 3x3 layer of DILATION 2 in Winograd form: the plain kernel on the four phase images of the tensors (rows / columns of one
 // parity: pixel pitch 2, row pitch 2 W), same transformed weights as the plain layer.  part: optional statistics partials
 // [N][parts][Cout][2] (forward, needs relu == 0); accumulate: y += result (a member of a gradient group).
-static const int g_wino_dil2_fwd = []{ const char* e = getenv("VQW_WINOGRAD_DIL2"); return e ? atoi(e) : 1; }();
 extern "C" int vqw_conv3x3_wino_dil2_supported(int Cin, int Cout, int N, int H, int W) {
-    if (!g_wino_dil2_fwd || g_conv_backend != 0 || N < 1 || H < 2 || W < 2) return 0;
+    if (g_conv_backend != 0 || N < 1 || H < 2 || W < 2) return 0;
     if (!conv_wino_ok(Cin, Cout, N, H / 2, W / 2) || !conv_wino64_dil2_ok(Cin, Cout, H, W)) return 0;
     return (long)N * H * W * (Cin > Cout ? Cin : Cout) * 4 <= 0xFFFFFFE0L ? 1 : 0;
 }

@@ -1,6 +1,19 @@
 // Internal declarations shared by the convolution translation units.
 #pragma once
 #include "common.h"
+#include <cstdlib>
+
+// Workgroups of the one-per-CU conv kernels (halo, dilated-row and Winograd kernels).  256 = every CU of an MI355X.  A smaller
+// VQW_CONV_MAX_BLOCKS (8..256) leaves CUs whose LDS is not taken for kernels of other streams that need LDS of their own (e.g.
+// RCCL collectives in data-parallel runs, which otherwise wait for one of these kernels to end).
+inline int conv_max_blocks() {
+    static const int v = [] {
+        const char* e = getenv("VQW_CONV_MAX_BLOCKS");
+        const int b = e ? atoi(e) : 256;
+        return b < 8 ? 8 : (b > 256 ? 256 : b);
+    }();
+    return v;
+}
 
 // Virtual conv input: channel-concat of src0 (C0 channels; up0=1 -> nearest x2 up-sampled from H/2 x W/2)
 // and src1 (C1 channels at full resolution; C1 == 0 -> absent).

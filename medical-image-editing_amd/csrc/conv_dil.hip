@@ -24,18 +24,10 @@
 #include "common.h"
 #include "conv_common.h"
 #include "mfma_util.h"
-#include <cstdlib>
 
 int g_dil_mode = 0;     // 0 auto, 1 off (A/B timing, tests of the implicit-GEMM kernel)
 
 namespace {
-
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static const int g_dil_env = env_int("VQW_DIL_ROWS", 1);
-static const int g_max_blocks = []{ int v = env_int("VQW_CONV_MAX_BLOCKS", 256); return v < 8 ? 8 : (v > 256 ? 256 : v); }();
 
 struct DilArgs {
     const float* x;
@@ -452,7 +444,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_conv_dilrow_wgrad(DilWgArgs a) {
 
 // 3x3, dilation 2..H, one 32-channel source, at most 32 couts, whole rows of at most 256 pixels
 bool conv_dil_fwd_ok(const ConvIn& in, int N, int H, int W, int Cout, int ks, int dil) {
-    if (g_dil_mode != 0 || !g_dil_env || ks != 3 || dil < 2 || dil > H) return false;
+    if (g_dil_mode != 0 || ks != 3 || dil < 2 || dil > H) return false;
     if (in.C0 != 32 || in.C1 != 0 || in.up0 || Cout < 1 || Cout > 32) return false;
     if (W % 32 != 0 || W > 256) return false;
     return (long)N * H * W * 32 * 4 <= 0xFFFFFFE0L;
@@ -477,7 +469,7 @@ int conv_dil_fwd(const ConvIn& in, const float* w, const float* bias, float* y, 
     a.x = in.src0; a.w = w; a.bias = bias; a.y = y;
     a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.dil = dil;
     a.total = N * (H + dil);
-    const int blocks = a.total < g_max_blocks ? a.total : g_max_blocks;
+    const int blocks = imin(a.total, conv_max_blocks());
     a.per = ceil_div(a.total, blocks);
     a.relu = relu;
     a.stats = stats;
@@ -512,7 +504,7 @@ int conv_dil_wgrad(const ConvIn& in, const float* dy, float* dw, float* ws, int 
     a.x = in.src0; a.dy = dy; a.part = ws;
     a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.dil = dil;
     a.total = N * H;
-    int blocks = a.total < g_max_blocks ? a.total : g_max_blocks;
+    int blocks = imin(a.total, conv_max_blocks());
     if (blocks > max_slabs) blocks = max_slabs;
     if (blocks < 1) blocks = 1;
     a.per = ceil_div(a.total, blocks);

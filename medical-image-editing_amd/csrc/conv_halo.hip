@@ -19,18 +19,6 @@
 #include "common.h"
 #include "conv_common.h"
 #include "mfma_util.h"
-#include <cstdlib>
-
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static const int g_halo16 = env_int("VQW_HALO16", 1);        // 0: 16-cout layers on the 32-wide tile (A/B)
-static const int g_halo_kt = env_int("VQW_HALO_KT", 0);     // tuning aid: spatial tiles per workgroup (0 = default)
-// Workgroups of the one-per-CU kernels in this file.  256 = every CU of an MI355X.  A smaller value leaves CUs whose
-// LDS is not taken for kernels of other streams that need LDS of their own (e.g. RCCL collectives in data-parallel
-// runs, which otherwise wait for one of these kernels to end).
-static const int g_max_blocks = []{ int v = env_int("VQW_CONV_MAX_BLOCKS", 256); return v < 8 ? 8 : (v > 256 ? 256 : v); }();
 
 namespace {
 
@@ -489,13 +477,11 @@ int launch_halo(const ConvIn& in, const float* w, const float* bias, float* y, i
     a.nbw = (unsigned)((long)Cout * NTAP * (in.C0 + in.C1) * 4);
     a.nby = (unsigned)((NTAP == 4 ? 4 : 1) * P * Cout * 4);
     // The LDS footprint allows one workgroup per CU: one workgroup per CU, each with an even share of the tiles, so the
-    // prologue (weights + first halo, not overlapped with MFMA work) is paid once.  Shorter runs per workgroup
-    // (VQW_HALO_KT) would let the dispatcher rebalance when other kernels hold CUs; measured 0.5-1 % slower in the step.
-    int groups = g_max_blocks / a.ntn;  // spatial groups: groups * ntn workgroups <= one per CU, never a second partial round
+    // prologue (weights + first halo, not overlapped with MFMA work) is paid once.  Shorter runs per workgroup would let
+    // the dispatcher rebalance when other kernels hold CUs; measured 0.5-1 % slower in the step.
+    int groups = conv_max_blocks() / a.ntn;  // spatial groups: groups * ntn workgroups <= one per CU, never a second partial round
     if (groups < 1) groups = 1;
-    const int even = ceil_div(a.nsp, groups);
-    int kt = g_halo_kt > 0 ? g_halo_kt : even;
-    if (kt > even) kt = even;
+    const int kt = ceil_div(a.nsp, groups);
     a.kt = kt < 1 ? 1 : kt;
     k_conv_halo<NW, TH, BN, KC, WPERSIST, TWO_SRC, NTAP><<<ceil_div(a.nsp, a.kt) * a.ntn, 64 * NW, lds, st>>>(a);
     VQW_LAUNCH_CHECK("conv_halo");
@@ -519,7 +505,7 @@ bool conv_halo_fwd_ok(const ConvIn& in, int N, int H, int W, int Cout, int ks, i
 // rows per tile of the variant conv_halo_fwd picks (the statistics partials are per tile)
 static int halo_tile_rows(const ConvIn& in, int Cout) {
     const int Cin = in.C0 + in.C1;
-    if (Cout <= 16 && g_halo16) return 16;
+    if (Cout <= 16) return 16;
     if (Cin == 32 && in.C1 == 0 && Cout > 32) return 4;
     return 8;
 }
@@ -531,7 +517,7 @@ int conv_halo_stat_tiles(const ConvIn& in, int H, int W, int Cout) {     // equa
 int conv_halo_fwd(const ConvIn& in, const float* w, const float* bias, float* y, int N, int H, int W, int Cout, int relu,
                   hipStream_t st, float* stats) {
     const int Cin = in.C0 + in.C1;
-    if (Cout <= 16 && g_halo16) {       // 16-cout layers: 16x16x4 MFMA, 16 x 32 pixel tiles
+    if (Cout <= 16) {       // 16-cout layers: 16x16x4 MFMA, 16 x 32 pixel tiles
         if (Cin == 16 && in.C1 == 0) return launch_halo<8, 16, 16, 16, true>(in, w, bias, y, N, H, W, Cout, relu, st, stats);
         if (in.C1 > 0) return launch_halo<8, 16, 16, 16, false, true>(in, w, bias, y, N, H, W, Cout, relu, st, stats);
         return launch_halo<8, 16, 16, 16, false>(in, w, bias, y, N, H, W, Cout, relu, st, stats);
@@ -555,9 +541,8 @@ int conv_halo_fwd(const ConvIn& in, const float* w, const float* bias, float* y,
 
 // Collapsed 3x3 over a nearest x2 up-sampled input, forward: four parity launches of the 4-tap form on the low-resolution
 // grid [N, h, w, Cin] -> [N, 2h, 2w, Cout]; wc = [4 parities][Cout][4][Cin] (k_collapse_up_weights).
-static const int g_halo_up2 = env_int("VQW_HALO_UP2", 1);
 bool conv_halo_up2_ok(int Cin, int Cout, int N, int h, int w) {
-    if (g_halo_mode != 0 || !g_halo_up2 || w % 32 != 0 || h < 2 || Cin % 16 != 0 || Cin < 32 || Cout < 32) return false;
+    if (g_halo_mode != 0 || w % 32 != 0 || h < 2 || Cin % 16 != 0 || Cin < 32 || Cout < 32) return false;
     return 4L * N * h * w * (Cin > Cout ? Cin : Cout) * 4 <= 0xFFFFFFE0L;
 }
 int conv_halo_up2_stat_tiles(int h, int w) { return h % 8 == 0 ? 4 * (h / 8) * (w / 32) : 0; }
@@ -859,7 +844,7 @@ bool conv_wgrad_tile_ok(int C0, int C1, int Cout, int ks, int W, int dil) {
 int conv_wgrad_tile_blocks(int Cin, int Cout, int N, int H, int W, int max_blocks, int* kt_out) {
     const int ntiles = ceil_div(Cout, 32) * ceil_div(Cin, 32);
     const int nsp = N * ceil_div(H, WT_TH) * (W / 32);
-    int nsb = g_max_blocks / ntiles;             // one workgroup per CU and never a second, nearly empty round
+    int nsb = conv_max_blocks() / ntiles;             // one workgroup per CU and never a second, nearly empty round
     if (nsb > max_blocks) nsb = max_blocks;
     if (nsb > nsp) nsb = nsp;
     if (nsb < 1) nsb = 1;
@@ -892,7 +877,7 @@ int conv_wgrad_tile(const ConvIn& in, const float* dy, float* ws, float* bpart, 
     a.nb0 = (unsigned)((in.up0 ? P / 4 : P) * in.C0 * 4);
     a.nb1 = (unsigned)(P * in.C1 * 4);
     a.nbd = (unsigned)(P * Cout * 4);
-    const bool m16 = g_halo16 && Cout <= 16, n16 = g_halo16 && Cin <= 16;
+    const bool m16 = Cout <= 16, n16 = Cin <= 16;
     if (m16 && n16) k_conv_wgrad_tile<1, 1><<<a.ntiles * nsb, 512, lds, st>>>(a);
     else if (m16) k_conv_wgrad_tile<1, 2><<<a.ntiles * nsb, 512, lds, st>>>(a);
     else if (n16) k_conv_wgrad_tile<2, 1><<<a.ntiles * nsb, 512, lds, st>>>(a);

@@ -513,9 +513,6 @@ int conv_k4s1_grid(const float* src, const float* w16, const float* bias, float*
     return dispatch_fwd(in, w16, bias, dst, N, H, W, Cdst, plain_geom(4, 1, tap0), 0, st);
 }
 
-// 0 = auto, 1 = per-tap kernel only, (testing / A-B timing)
-int g_wgrad_variant = 0;
-
 // =============================================================================================
 // wgrad, one tap per workgroup (1x1 convs, ragged widths)
 // =============================================================================================
@@ -852,7 +849,6 @@ k_conv_wgrad9(ConvIn in, const float* __restrict__ dy, float* __restrict__ part,
 }
 
 // shapes the wg9 kernel takes, and its split count (shared by the workspace query and the launcher)
-static const int g_wino_wgrad = []{ const char* e = getenv("VQW_WINOGRAD_WGRAD"); return e ? atoi(e) : 1; }();      // 0: direct-form weight gradients (A/B)
 static inline bool wg9_ok(int C0, int C1, int Cout, int ks, int W, int dil, long P) {
     return ks == 3 && (W % 32 == 0) && (C0 % 4 == 0) && (C1 % 4 == 0) && (Cout % 4 == 0) && dil <= 24 && P >= 32 &&
            (C1 == 0 || C0 % 32 == 0);
@@ -1156,18 +1152,17 @@ static int launch_wgrad(const ConvIn& in, const float* dy, float* dw, float* ws,
 
 // dbias != nullptr asks the kernel to produce the bias gradient too; returns 1 (not an error) in *bias_done when it did.
 // true when conv_mfma_wgrad takes the Winograd form for the layer (the profile scope prices it at the FLOPs it executes)
-// dilation 2 in Winograd form: the (32 x 32)-block kernel on the four phase images (VQW_WINOGRAD_DIL2=0: the row-chain kernels)
-static const int g_wino_dil2 = []{ const char* e = getenv("VQW_WINOGRAD_DIL2"); return e ? atoi(e) : 1; }();
+// dilation 2 in Winograd form: the (32 x 32)-block kernel on the four phase images
 extern int g_wino_mode;
 static bool wgrad_is_wino_dil2(const ConvIn& in, int N, int H, int W, int Cout, int ks, int dil) {
-    return g_wino_dil2 && g_wino_mode == 0 && g_wgrad_variant != 1 && g_wino_wgrad && ks == 3 && dil == 2 && in.C1 == 0 && !in.up0 &&
+    return g_wino_mode == 0 && ks == 3 && dil == 2 && in.C1 == 0 && !in.up0 &&
            fits_u32((long)N * H * W, in.C0, Cout) && conv_wino32_wgrad_dil2_ok(in.C0, Cout, H, W);
 }
 bool conv_mfma_wgrad_is_wino(const ConvIn& in, int N, int H, int W, int Cout, int ks, int dil) {
     if (wgrad_is_wino_dil2(in, N, H, W, Cout, ks, dil)) return true;
     if (in.C1 > 0 && (in.C0 % 16 != 0 || in.C1 % 16 != 0)) return false;      // a 16-channel ci block must not straddle the sources
     if (in.up0 && ((H | W) & 1)) return false;
-    return g_wgrad_variant != 1 && g_wino_wgrad && ks == 3 && dil == 1 && (long)N * H * W >= 32 &&
+    return ks == 3 && dil == 1 && (long)N * H * W >= 32 &&
            fits_u32((long)N * H * W, in.C0 + in.C1, Cout) && conv_wino_wgrad_ok(in.C0 + in.C1, Cout, N, H, W);
 }
 int conv_mfma_wgrad(const ConvIn& in, const float* dy, float* dw, float* dbias, int* bias_done, float* ws, int N, int H, int W,
@@ -1192,10 +1187,10 @@ int conv_mfma_wgrad(const ConvIn& in, const float* dy, float* dw, float* dbias, 
         }
         return reduce_rows(ws, dw, nout, nsbw, st, acc);
     }
-    if (g_wgrad_variant != 1 && wg9_ok(in.C0, in.C1, Cout, ks, W, dil, (long)N * H * W) &&
+    if (wg9_ok(in.C0, in.C1, Cout, ks, W, dil, (long)N * H * W) &&
         conv_dil_wgrad_ok(in, N, H, W, Cout, ks, dil))       // dilated 32-channel layers: rows walked along the residue chains
         return conv_dil_wgrad(in, dy, dw, ws, wg9_split_blocks(in.C0, Cout, (long)N * H * W), N, H, W, Cout, dil, acc, st);
-    if (g_wgrad_variant != 1 && wg9_ok(in.C0, in.C1, Cout, ks, W, dil, (long)N * H * W)) {
+    if (wg9_ok(in.C0, in.C1, Cout, ks, W, dil, (long)N * H * W)) {
         *bias_done = dbias != nullptr;
         const int Cin = in.C0 + in.C1;
         const long P = (long)N * H * W;

@@ -3,7 +3,6 @@
 #include "common.h"
 #include "conv_common.h"
 #include "mfma_util.h"
-#include <cstdlib>
 
 // ---------------------------------------------------------------------------------------------
 // stem forward: y[p][0..Cout) = b + sum_t x[p + shift(t)] * w[co][t]          (Cin == 1, Cout % 4 == 0, Cout <= 64)
@@ -238,8 +237,7 @@ int conv_stem_fwd(const ConvIn& in, const float* w, const float* bias, float* y,
         VQW_LAUNCH_CHECK("conv_stem_fwd(wide)");
         return VQW_OK;
     }
-    static const bool staged_env = []{ const char* e = getenv("VQW_STEM_STAGED"); return !e || atoi(e) != 0; }();
-    const bool staged = staged_env && ((long)N * H * W) % 64 == 0;      // whole waves of valid pixels
+    const bool staged = ((long)N * H * W) % 64 == 0;      // whole waves of valid pixels
     if (Cout == 16 && staged) k_stem_fwd<16, true><<<g, 256, 0, st>>>(in.src0, w, bias, y, N, H, W, ks, dil, relu);
     else if (Cout == 32 && staged) k_stem_fwd<32, true><<<g, 256, 0, st>>>(in.src0, w, bias, y, N, H, W, ks, dil, relu);
     else if (Cout == 16) k_stem_fwd<16><<<g, 256, 0, st>>>(in.src0, w, bias, y, N, H, W, ks, dil, relu);
@@ -512,11 +510,7 @@ __global__ void __launch_bounds__(256) k_pw_stream(const float4* __restrict__ x,
             // B's rows at q4 do not change from pixel to pixel: the compiler keeps them in registers (KIN float4: fine up to
             // KIN = 32, 422 registers at 64) - there an index it cannot see through keeps them in LDS
             int qo = q4;
-#ifdef PW_NOHOIST32
-            if (KIN >= 32) asm volatile("" : "+v"(qo));
-#else
             if (KIN > 32) asm volatile("" : "+v"(qo));
-#endif
 #pragma unroll
             for (int j = 0; j < K4; ++j) {
                 const float xv[4] = {xin[u][j].x, xin[u][j].y, xin[u][j].z, xin[u][j].w};
@@ -580,12 +574,11 @@ __global__ void __launch_bounds__(256) k_pw_stream(const float4* __restrict__ x,
     }
 }
 
-static const int g_pw_stream = []{ const char* e = getenv("VQW_PW_STREAM"); return e ? atoi(e) : 1; }();      // 0: implicit-GEMM kernel (A/B)
 static inline int pw_tile_px(int HW) { return HW % 1024 == 0 ? 1024 : (HW % 512 == 0 ? 512 : 0); }
 // K -> Nout channel mixing on a map of at least 128 x 128 pixels per image, both channel counts in {16, 32, 64}
 bool conv_pw_stream_ok(int K, int Nout, int N, int HW) {
     auto okc = [](int c) { return c == 16 || c == 32 || c == 64; };
-    return g_pw_stream && okc(K) && okc(Nout) && HW >= 16384 && pw_tile_px(HW) > 0 && (long)N * HW * (K > Nout ? K : Nout) * 4 < 0xffffff00L;
+    return okc(K) && okc(Nout) && HW >= 16384 && pw_tile_px(HW) > 0 && (long)N * HW * (K > Nout ? K : Nout) * 4 < 0xffffff00L;
 }
 int conv_pw_stream_stat_tiles(int HW) { const int tp = pw_tile_px(HW); return tp ? HW / tp : 0; }
 // Bm: the OHWI weights [Nout][K] of the 1 x 1 layer that maps K -> Nout channels (transposed while they are staged in LDS)

@@ -28,19 +28,11 @@
 #include "common.h"
 #include "conv_common.h"
 #include "mfma_util.h"
-#include <cstdlib>
 #include <type_traits>
 
 int g_wino_mode = 0;     // 0 auto, 1 off
 
 namespace {
-
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static const int g_wino_env = env_int("VQW_WINOGRAD", 1);
-static const int g_max_blocks = []{ int v = env_int("VQW_CONV_MAX_BLOCKS", 256); return v < 8 ? 8 : (v > 256 ? 256 : v); }();
 
 // U[xi = i*4 + j][co][ci] = sum_{ky,kx} G[i][ky] g[co][ky][kx][ci] G[j][kx],  G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]
 // chunked = 1: [ci / 8][xi][co][ci % 8] - what the kernels stream: the couts of a (chunk, xi) lie in a row, 32 bytes each
@@ -101,9 +93,7 @@ template <int RW> struct WinoGeo {
     static constexpr int HWS = RW == 32 ? 34 : 24;         // LDS row stride in pixels
     static constexpr int HBUF = HR * HWS * WN_KPH;         // floats per halo buffer
 };
-#ifndef WN_CP
-#define WN_CP 22                         // MFMA position of the first LDS commit of the prefetched item
-#endif
+constexpr int WN_CP = 22;                // MFMA position of the first LDS commit of the prefetched item
 
 template <int RW>
 __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
@@ -344,17 +334,12 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
         };
         auto slot = [&](int p) {       // p = 0..63: MFMA position (compile-time after unrolling)
             // loads (address arithmetic included) behind the first MFMAs: halo of item i+2, U chunk of item i+1
-#ifndef WN_EXP_NO_LOADS
             if (p == 0) issue_setup(n2, tx2, ty2, ch2);
             if (p >= 1 && p < 1 + LH) issue_h(p - 1);
             if (p == 1 + LH) i_cc4 = (unsigned)(ch1 * WN_KC) * 4u;
             if (p >= 2 + LH && p < 2 + LH + LW) issue_u(p - 2 - LH);
             if (p >= WN_CP && p < WN_CP + LH) commit_h(p - WN_CP, hC);
             if (p >= WN_CP + 4 && p < WN_CP + 4 + LW) commit_u(p - WN_CP - 4, ucur ^ 1);
-#endif
-#ifdef WN_EXP_NO_XFORM
-            if (true) return;
-#endif
             if (p == 29) read_col(hB, 0);
             if (p >= 32 && p < 48) {   // column pass: column c = (p - 32) / 4, two operations per position
                 const int c = (p - 32) >> 2, k = ((p - 32) & 3) * 2;
@@ -374,11 +359,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
 #pragma unroll
         for (int xi = 0; xi < 16; ++xi) {
             const int s = xi % 3;
-#ifndef WN_EXP_NO_BREAD
             if (xi + 2 < 16) ldb(xi + 2, (xi + 2) % 3);
-#else
-            if (xi == 0) ldb(2, 2);
-#endif
             acc[xi][0] = MFMA16(v[par][0][xi], bf[s][0].x, first ? zero4 : acc[xi][0]);
             slot(4 * xi); __builtin_amdgcn_sched_barrier(0);
             acc[xi][1] = MFMA16(v[par][0][xi], bf[s][1].x, first ? zero4 : acc[xi][1]);
@@ -389,11 +370,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
             slot(4 * xi + 3); __builtin_amdgcn_sched_barrier(0);
         }
 
-#ifdef WN_EXP_NO_EPI
-        if (ch == nch - 1 && acc[3][1][2] == 123.456f) {
-#else
         if (ch == nch - 1) {
-#endif
             // Y = A^T M A per (tile, cout) entry: lane-local over the 16 xi; then bias / ReLU, statistics, stores
             // C/D rows of a lane = tiles 4 q + r: RW = 32: tile row wv, columns 4 q + r; RW = 16: tile row 2 wv + (q >> 1),
             // columns 4 (q & 1) + r
@@ -428,11 +405,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
                     for (int r = 0; r < 4; ++r)
 #pragma unroll
                         for (int b = 0; b < 2; ++b)
-#ifndef WN_EXP_NO_STORE          // timing-only A/B builds (tools/wino_ab.sh): results are wrong by construction
                             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(yv[r * 4 + aa * 2 + b]), rsy, voff, (2 * r + b) * Cout * 4, 0);
-#else
-                            if (yv[r * 4 + aa * 2 + b] == 123.456f) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(yv[r * 4 + aa * 2 + b]), rsy, voff, (2 * r + b) * Cout * 4, 0);
-#endif
                 }
                 if (a.stats) {     // uniform: H % 16 == 0 whenever statistics are requested
                     float t1, t2;
@@ -451,9 +424,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
         cn = n1; ctx = tx1; cty = ty1; ch = ch1;
         n1 = n2; tx1 = tx2; ty1 = ty2; ch1 = ch2;
         advance(n2, tx2, ty2, ch2);
-#ifndef WN_EXP_NO_BARRIER
         __syncthreads();               // publishes the halo of item i+2 and the U chunk of item i+1
-#endif
         const int t = hA; hA = hB; hB = hC; hC = t;
         ucur ^= 1;
         fold_stats();
@@ -470,7 +441,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
 
 // 3x3, dilation 1, one source at full resolution, whole 32-pixel column strips, channels in chunks of 8
 bool conv_wino_ok(int Cin, int Cout, int N, int H, int W) {
-    if (g_wino_mode != 0 || !g_wino_env) return false;
+    if (g_wino_mode != 0) return false;
     if (Cin % 8 != 0 || Cin < 16 || Cout < 32 || Cout % 4 != 0 || W % 16 != 0 || H < 2 || N < 1) return false;
     // (a batch beyond the 32-bit descriptor range runs as image groups: one image must fit)
     return (long)H * W * (Cin > Cout ? Cin : Cout) * 4 <= 0xFFFFFFE0L && 16L * Cout * Cin * 4 <= 0xFFFFFFE0L;
@@ -534,7 +505,7 @@ int conv_wino_fwd(const float* x, const float* u, const float* bias, float* y, i
     a.nbx = (unsigned)(P * Cin * 4);
     a.nbu = (unsigned)(16L * Cout * Cin * 4);
     a.nby = (unsigned)(P * Cout * 4);
-    int groups = g_max_blocks / a.ntn;
+    int groups = conv_max_blocks() / a.ntn;
     if (groups < 1) groups = 1;
     const int even = ceil_div(a.nsp, groups);
     a.kt = even < 1 ? 1 : even;
@@ -808,7 +779,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad(WinoWgArgs a) {
 
 // (two sources: both channel counts multiples of 16, so that a 16-channel ci block never straddles them)
 bool conv_wino_wgrad_ok(int Cin, int Cout, int N, int H, int W) {
-    if (g_wino_mode != 0 || !g_wino_env) return false;
+    if (g_wino_mode != 0) return false;
     if (Cin % 16 != 0 || Cout % 32 != 0 || W % 16 != 0 || H < 2 || N < 1) return false;
     return (long)N * H * W * (Cin > Cout ? Cin : Cout) * 4 <= 0xFFFFFFE0L;
 }
@@ -820,7 +791,7 @@ int conv_wino_wgrad_blocks(const ConvIn& in, int Cout, int N, int H, int W, int 
     const int nblk = (Cout / 32) * (Cin / 16);
     const int rw = W % 32 == 0 ? 32 : 16;
     const int nsp = N * ceil_div(H, 256 / rw) * (W / rw);
-    int nsb = g_max_blocks / nblk;
+    int nsb = conv_max_blocks() / nblk;
     if (nsb > max_slabs) nsb = max_slabs;
     if (nsb > nsp) nsb = nsp;
     if (nsb < 1) nsb = 1;

@@ -27,21 +27,11 @@
 #include "common.h"
 #include "conv_common.h"
 #include "mfma_util.h"
-#include <cstdlib>
 #include <type_traits>
 
 extern int g_wino_mode;
 
 namespace {
-
-static int env_int64(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static const int g_w64_env = env_int64("VQW_WINOGRAD64", 1);
-static const int g_w64_max_blocks = []{ int v = env_int64("VQW_CONV_MAX_BLOCKS", 256); return v < 8 ? 8 : (v > 256 ? 256 : v); }();
-// weight-gradient kernels (they run on the side lanes beside the chain): VQW_WGRAD_MAX_BLOCKS leaves CUs to the chain's kernels (experiment)
-static const int g_w64_max_blocks_wg = []{ int v = env_int64("VQW_WGRAD_MAX_BLOCKS", g_w64_max_blocks); return v < 8 ? 8 : (v > 256 ? 256 : v); }();
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -109,19 +99,10 @@ template <int RW, int MBW, int NW = 8> struct W64Geo {
     static_assert(EXF >= UBUF, "U buffer 1 lives in the exchange area");
     static constexpr size_t LDS_FLOATS = 2 * HBUF + UBUF + EXF + 2 * NMB * NCO * 2;
 };
-#ifdef W6_EXP_NO_BARRIER
-#define W6_ITEM_BARRIER() do {} while (0)
-#else
-#define W6_ITEM_BARRIER() __syncthreads()
-#endif
-#ifndef W6_LS
-#define W6_LS 4                            // MFMA positions between two prefetch loads (a burst of 48 wave-loads stalls their issue;
+constexpr int W6_LS = 4;                   // MFMA positions between two prefetch loads (a burst of 48 wave-loads stalls their issue;
                                            // 2 -> 4: 32->64 @256 dgrad 0.447 -> 0.425 ms, 64->128 @128 0.318 -> 0.306, nothing slower)
-#endif
 constexpr int W6_CP = 26;                  // MFMA position of the first LDS commit of the prefetched data
-#ifndef W6_CP1
-#define W6_CP1 26                          // ... of the 64-cout shape (MBW = 1), which has registers to hold the loads longer
-#endif
+constexpr int W6_CP1 = 26;                 // ... of the 64-cout shape (MBW = 1), which has registers to hold the loads longer
 constexpr int W6_PB = 33, W6_CB = 58;      // second phase of U slots (four-wave workgroups): first issue, first commit
 
 template <int RW, int MBW, int EPI, int NW = 8>
@@ -372,21 +353,15 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
             bf[l & 1][nb] = *(const f32x2*)&Uc[(l < 4 ? b_0 : b_1) + ((l & 3) * NCO + nb * 16) * 8];
         };
         auto slot = [&](int p) {       // p = 0..63: MFMA position (compile-time after unrolling)
-#if !defined(W6_EXP_NO_LOADS) && !defined(W6_EXP_NO_HLOADS)      // timing-only A/B builds (tools/wino_ab.sh): wrong results
             if (p >= 1 && p < 1 + LH * W6_LS && (p - 1) % W6_LS == 0) issue_h((p - 1) / W6_LS, ch2);
             if (p >= CP && p < CP + LH) commit_h(p - CP, Hw);
-#endif
-#if !defined(W6_EXP_NO_LOADS) && !defined(W6_EXP_NO_ULOADS)
             if (p >= 1 + LH * W6_LS && p < 1 + (LH + LUA) * W6_LS && (p - 1) % W6_LS == 0) issue_u((p - 1) / W6_LS - LH, ch1);
             if (p >= CP + LH && p < CP + LH + LUA) commit_u(p - CP - LH, Uw);
             if (!ONE_PHASE) {
                 if (p >= W6_PB && p < W6_PB + LUA * W6_LS && (p - W6_PB) % W6_LS == 0) issue_u(LUA + (p - W6_PB) / W6_LS, ch1);
                 if (p >= W6_CB && p < W6_CB + LUA) commit_u(LUA + p - W6_CB, Uw);
             }
-#endif
-#ifndef W6_EXP_NO_XFORM
             xform_slot(Hn, par ^ 1, p);
-#endif
         };
         // The item's first B fragments are requested right behind the barrier; the eight MFMAs of the PREVIOUS item's last xi
         // (operands and fragments already in registers) run while they arrive - without them every wave of the workgroup
@@ -417,9 +392,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int w = j / (2 * NBW), k = (j / NBW) & 1, nb = j % NBW;
-#ifndef W6_EXP_NO_BREAD
                 if (j < NBW) ldb(l + 1, nb);             // (l = 6: the fragments of xi 7 stay in bf[1] for the next body)
-#endif
                 acc[l][w][nb] = MFMA16(v[par][w][k][l], k == 0 ? bf[l & 1][nb].x : bf[l & 1][nb].y, (first && k == 0) ? zero4 : acc[l][w][nb]);
                 slot(8 + l * 8 + j);
                 __builtin_amdgcn_sched_barrier(0);
@@ -619,31 +592,26 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
     // diamond's PHIs cost register copies and spills.)  Every branch is uniform per workgroup.
     for (int reg = 0; reg < my_tiles; ++reg) {
         body(P0{}, std::true_type{});
-        W6_ITEM_BARRIER();             // publishes the halo of item i+2 and the U chunk of item i+1
+        __syncthreads();             // publishes the halo of item i+2 and the U chunk of item i+1
         shift();
         body(P1{}, std::false_type{});
-        W6_ITEM_BARRIER();
+        __syncthreads();
         for (int c = 2; c < nch; c += 2) {
             shift();
             if (ch2 == 0) region_offsets(n2, tx2, ty2);   // item i+2 opens a region: its halo offsets
             body(P0{}, std::false_type{});
-            W6_ITEM_BARRIER();
+            __syncthreads();
             shift();
             body(P1{}, std::false_type{});
-            W6_ITEM_BARRIER();
+            __syncthreads();
         }
         // region (cn, ctx, cty) is complete
         flush();
-#ifdef W6_EXP_NO_EPI
-        if (acc[3][0][1][2] == 123.456f)
-#endif
-        {
         if (h == 0) epi_send(P0{}); else epi_send(P1{});
         __syncthreads();
         if (h == 0) epi_finish(P0{}); else epi_finish(P1{});
         __syncthreads();               // the exchange area is U buffer 1 again from the next item on
         fold_stats();
-        }
         shift();
         if (ch2 == 0) region_offsets(n2, tx2, ty2);       // item i+2 opens a region: its halo offsets
     }
@@ -654,14 +622,12 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
 // Which workgroup shape serves a layer (0: none - the 32-cout kernel of conv_wino.hip): 64 couts whenever Cout allows, else
 // two M blocks x 32 couts on maps whose width is a multiple of 32.  (Cin % 16: an even number of 8-channel chunks.)
 static int wino64_shape(int Cin, int Cout, int W) {
-    if (!g_w64_env || Cin % 16 != 0) return 0;
+    if (Cin % 16 != 0) return 0;
     if (Cout % 64 == 0) return 1;
     return (Cout % 32 == 0 && W % 32 == 0) ? 2 : 0;
 }
-// Waves per workgroup of a shape: the 32-cout shape (MBW = 2) runs as two four-wave workgroups per CU (VQW_WINO64_NW4=0: one
-// eight-wave workgroup, the round-3 form)
-static const int g_w64_nw4 = env_int64("VQW_WINO64_NW4", 1);
-static int wino64_waves(int shape) { return (shape == 2 && g_w64_nw4) ? 4 : 8; }
+// Waves per workgroup of a shape: the 32-cout shape (MBW = 2) runs as two four-wave workgroups per CU
+static int wino64_waves(int shape) { return shape == 2 ? 4 : 8; }
 bool conv_wino64_ok(int Cin, int Cout, int W) { return wino64_shape(Cin, Cout, W) != 0; }
 int conv_wino64_stat_tiles(int Cin, int Cout, int H, int W) {
     const int shape = wino64_shape(Cin, Cout, W);
@@ -684,7 +650,7 @@ static int launch_wino64(W64Args& a, hipStream_t st) {
     }
     a.tilesY = ceil_div(a.H, G::TR); a.tilesX = a.W / RW; a.nsp = a.N * a.tilesY * a.tilesX;
     a.ntn = a.Cout / G::NCO;
-    int groups = g_w64_max_blocks * (8 / NW) / a.ntn;
+    int groups = conv_max_blocks() * (8 / NW) / a.ntn;
     if (groups < 1) groups = 1;
     const int even = ceil_div(a.nsp, groups);
     a.kt = even < 1 ? 1 : even;
@@ -715,29 +681,23 @@ int conv_wino64_fwd(const float* x, const float* u, const float* bias, float* y,
     a.nbx = (unsigned)(P * Cin * 4);
     a.nbu = (unsigned)(16L * Cout * Cin * 4);
     a.nby = (unsigned)(P * Cout * 4);
-    const int shape = wino64_shape(Cin, Cout, W);
-    if (shape == 2 && wino64_waves(shape) == 4) {
-        if (in_mr) return launch_wino64<32, 2, 3, 4>(a, st);
-        if (mask) return launch_wino64<32, 2, 1, 4>(a, st);
-        if (accumulate) return launch_wino64<32, 2, 2, 4>(a, st);
-        return launch_wino64<32, 2, 0, 4>(a, st);
-    }
+    const int shape = wino64_shape(Cin, Cout, W);          // shape 2: four-wave workgroups (wino64_waves)
     if (in_mr) {               // (mask = the norm's raw input, stats = the backward sums)
-        if (shape == 2) return launch_wino64<32, 2, 3>(a, st);
+        if (shape == 2) return launch_wino64<32, 2, 3, 4>(a, st);
         if (W % 32 == 0) return launch_wino64<32, 1, 3>(a, st);
         return launch_wino64<16, 1, 3>(a, st);
     }
     if (mask) {
-        if (shape == 2) return launch_wino64<32, 2, 1>(a, st);
+        if (shape == 2) return launch_wino64<32, 2, 1, 4>(a, st);
         if (W % 32 == 0) return launch_wino64<32, 1, 1>(a, st);
         return launch_wino64<16, 1, 1>(a, st);
     }
     if (accumulate) {
-        if (shape == 2) return launch_wino64<32, 2, 2>(a, st);
+        if (shape == 2) return launch_wino64<32, 2, 2, 4>(a, st);
         if (W % 32 == 0) return launch_wino64<32, 1, 2>(a, st);
         return launch_wino64<16, 1, 2>(a, st);
     }
-    if (shape == 2) return launch_wino64<32, 2, 0>(a, st);
+    if (shape == 2) return launch_wino64<32, 2, 0, 4>(a, st);
     if (W % 32 == 0) return launch_wino64<32, 1, 0>(a, st);
     return launch_wino64<16, 1, 0>(a, st);
 }
@@ -770,7 +730,7 @@ int conv_wino64_fwd_split(const float* x, const float* u, const float* bias, flo
     a.nby = (unsigned)((pool0 ? P / 4 : P) * split * 4);
     a.nby2 = (unsigned)(P * c1 * 4);
     const int shape = wino64_shape(Cin, Cout, W);
-    if (shape == 2) return wino64_waves(shape) == 4 ? launch_wino64<32, 2, 4, 4>(a, st) : launch_wino64<32, 2, 4>(a, st);
+    if (shape == 2) return launch_wino64<32, 2, 4, 4>(a, st);
     if (W % 32 == 0) return launch_wino64<32, 1, 4>(a, st);
     return launch_wino64<16, 1, 4>(a, st);
 }
@@ -810,9 +770,7 @@ struct W64WgArgs {
     int n_sh, n_m;
 };
 
-#ifndef W6_WLS
-#define W6_WLS 2                           // MFMA positions between two prefetch loads of the weight-gradient kernel
-#endif
+constexpr int W6_WLS = 2;                  // MFMA positions between two prefetch loads of the weight-gradient kernel
 constexpr int WG_DP = 72, WG_XP = 40;     // floats per dY pixel (64 co + 8) / X pixel (32 ci + 8): adjacent tiles 16 banks apart
 template <int RW> struct WgGeo {
     static constexpr int TRP = RW == 32 ? 4 : 8;           // pixel rows per region: 32 tiles
@@ -820,13 +778,8 @@ template <int RW> struct WgGeo {
     static constexpr int DBUF = 128 * WG_DP, XBUF = XPIX * WG_XP;
 };
 
-#ifdef W6_WG_VGPR                            // experiment: cap the weight-gradient kernel's registers (room for other streams' waves)
-#define W6_WG_ATTR __attribute__((amdgpu_num_vgpr(W6_WG_VGPR)))
-#else
-#define W6_WG_ATTR
-#endif
 template <int RW>
-__global__ void __launch_bounds__(512, 1) W6_WG_ATTR k_conv_wino_wgrad64(W64WgArgs a) {
+__global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
     using G = WgGeo<RW>;
     constexpr int NT = 512, DBUF = G::DBUF, XBUF = G::XBUF, XW = G::XW;
     constexpr int XF = G::XPIX * 8;                        // float4 per X halo: 1632 / 1440
@@ -837,11 +790,6 @@ __global__ void __launch_bounds__(512, 1) W6_WG_ATTR k_conv_wino_wgrad64(W64WgAr
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = wv & 3, kh = wv >> 2;
-#if defined(W6_PRIO) && W6_PRIO == 1
-    if (wv >= 4) __builtin_amdgcn_s_setprio(1);
-#elif defined(W6_PRIO) && W6_PRIO == 2
-    if (wv < 4) __builtin_amdgcn_s_setprio(1);
-#endif
     const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
     // the (co, ci) blocks of one spatial split read the same dY / X regions: keep them on one XCD's L2
     const int lb = xcd_remap(blockIdx.x, gridDim.x);
@@ -1047,16 +995,12 @@ __global__ void __launch_bounds__(512, 1) W6_WG_ATTR k_conv_wino_wgrad64(W64WgAr
                 for (int nb = 0; nb < 2; ++nb) {
                     const int p = c * 8 + mb * 2 + nb;
                     acc[c][mb][nb] = MFMA16(dm[set][mb][c], vv[set][nb][c], acc[c][mb][nb]);
-#ifndef W6_EXP_NO_BUILD               // timing-only A/B builds (tools/wino_ab.sh): wrong results
                     build_slot(nbuf, sn, set ^ 1, p);
-#endif
                     // prefetch: a phase (1 us) between a load and its LDS commit (twice that changed nothing and costs registers)
-#ifndef W6_EXP_NO_WLOADS
                     if (loads == 0 && p >= 8 && p < 12) commit_d(p - 8, wbuf);
                     if (loads == 1 && p >= 2 && p < 2 + W6_WLS * LX && (p - 2) % W6_WLS == 0) issue_x((p - 2) / W6_WLS);
                     if (loads == 2 && p >= 8 && p < 8 + LX) commit_x(p - 8, wbuf);
                     if (loads == 3 && p >= 2 && p < 2 + W6_WLS * 4 && (p - 2) % W6_WLS == 0) issue_d((p - 2) / W6_WLS);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
     };
@@ -1071,9 +1015,7 @@ __global__ void __launch_bounds__(512, 1) W6_WG_ATTR k_conv_wino_wgrad64(W64WgAr
         phase(I0{}, I1{}, B{}, NB{}, I0{});        // k-step 0 (set 0), builds k-step 1; commits dY of the next region
         phase(I1{}, I2{}, B{}, NB{}, I1{});        // k-step 1, builds 2; issues X of the next region
         phase(I0{}, I3{}, B{}, NB{}, I2{});        // k-step 2, builds 3; commits X
-#ifndef W6_EXP_NO_WBARRIER
         __syncthreads();                           // the next region's buffers are complete; this region's are read once more
-#endif
         load_advance();
         phase(I1{}, I0{}, NB{}, B{}, I3{});        // k-step 3, builds k-step 0 of the next region; issues dY of the one after
     };
@@ -1100,9 +1042,6 @@ __global__ void __launch_bounds__(512, 1) W6_WG_ATTR k_conv_wino_wgrad64(W64WgAr
     // carries them, spilled, through the main loop)
     int fold_w = ((kh * 4 + r) * 4 * 16 + 4 * (lane >> 4)) * 32 + idx, fold_r = tid;
     asm volatile("" : "+v"(fold_w), "+v"(fold_r));
-#ifdef W6_EXP_NO_FOLD
-    if (acc[1][2][1][3] == 123.456f)
-#endif
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
         // C/D layout (16x16): col = lane & 15 (ci), row = 4 (lane >> 4) + q (co within the block)
@@ -1453,25 +1392,20 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad32(W64WgArgs a) {
 
 }  // namespace
 
-// one full-resolution source or two sources [up2x?(a) | b] with 32-channel-aligned widths (VQW_WGRAD_TWO_SRC=0: those on
-// k_conv_wino_wgrad, A/B timing); whole regions (4 x 32 or 8 x 16 pixels)
-static const int g_wg2src_env = env_int64("VQW_WGRAD_TWO_SRC", 1);
+// one full-resolution source or two sources [up2x?(a) | b] with 32-channel-aligned widths; whole regions (4 x 32 or 8 x 16 pixels)
 static bool wgrad_sources_ok(int C0, int C1, int up0, int H, int W) {
     if (C1 == 0) return !up0 && C0 % 32 == 0;          // (a single up-sampled source has the nine-product kernel)
-    return g_wg2src_env && C0 % 32 == 0 && C1 % 32 == 0 && (!up0 || (H % 2 == 0 && W % 2 == 0));
+    return C0 % 32 == 0 && C1 % 32 == 0 && (!up0 || (H % 2 == 0 && W % 2 == 0));
 }
-// VQW_WGRAD64=0 (experiment): the (64 co x 32 ci)-block kernel off; its 32-pixel-wide layers then take the (32 x 32)-block kernel
-static const int g_wg64_env = env_int64("VQW_WGRAD64", 1);
 bool conv_wino64_wgrad_ok(int C0, int C1, int up0, int Cout, int H, int W) {
-    if (!g_wg64_env && W % 32 == 0 && H % 4 == 0) return false;
-    if (!g_w64_env || !wgrad_sources_ok(C0, C1, up0, H, W) || Cout % 64 != 0 || W % 16 != 0) return false;
+    if (!wgrad_sources_ok(C0, C1, up0, H, W) || Cout % 64 != 0 || W % 16 != 0) return false;
     return H % (W % 32 == 0 ? 4 : 8) == 0;
 }
 int conv_wino64_wgrad_blocks(int Cin, int Cout, int N, int H, int W, int max_slabs, int* kt_out) {
     const int nblk = (Cout / 64) * (Cin / 32);
     const int rw = W % 32 == 0 ? 32 : 16;
     const int nsp = N * (H / (128 / rw)) * (W / rw);
-    int nsb = g_w64_max_blocks_wg / nblk;
+    int nsb = conv_max_blocks() / nblk;
     if (nsb > max_slabs) nsb = max_slabs;
     if (nsb > nsp) nsb = nsp;
     if (nsb < 1) nsb = 1;
@@ -1518,16 +1452,15 @@ int conv_wino64_wgrad(const ConvIn& in, const float* dy, float* ws, float* bpart
 }
 
 // (32 co x 32 ci) blocks: Cout a multiple of 32 but not of 64 (those take the 64-cout kernel), one full-resolution source,
-// 32-pixel-wide whole regions (4 x 32 pixels).  VQW_WINOGRAD32W=0: these layers on k_conv_wino_wgrad (A/B timing).
-static const int g_w32w_env = env_int64("VQW_WINOGRAD32W", 1);
+// 32-pixel-wide whole regions (4 x 32 pixels).
 bool conv_wino32_wgrad_ok(int C0, int C1, int up0, int Cout, int H, int W) {
-    if (!g_w64_env || !g_w32w_env || !wgrad_sources_ok(C0, C1, up0, H, W) || Cout % 32 != 0 || (Cout % 64 == 0 && g_wg64_env) || W % 32 != 0) return false;
+    if (!wgrad_sources_ok(C0, C1, up0, H, W) || Cout % 32 != 0 || Cout % 64 == 0 || W % 32 != 0) return false;
     return H % 4 == 0;
 }
 int conv_wino32_wgrad_blocks(int Cin, int Cout, int N, int H, int W, int max_slabs, int* kt_out) {
     const int nblk = (Cout / 32) * (Cin / 32);
     const int nsp = N * (H / 4) * (W / 32);
-    int nsb = g_w64_max_blocks_wg / nblk;
+    int nsb = conv_max_blocks() / nblk;
     if (nsb > max_slabs) nsb = max_slabs;
     if (nsb > nsp) nsb = nsp;
     if (nsb < 1) nsb = 1;

@@ -16,19 +16,9 @@
 #include "common.h"
 #include "conv_common.h"
 #include "mfma_util.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
-
-static int env_int_up(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static const int g_wup_env = env_int_up("VQW_WINOGRAD_UP", 1);
-static const int g_wup_max_blocks = []{ int v = env_int_up("VQW_CONV_MAX_BLOCKS", 256); return v < 8 ? 8 : (v > 256 ? 256 : v); }();
-// weight-gradient kernels (they run on the side lanes beside the chain): VQW_WGRAD_MAX_BLOCKS leaves CUs to the chain's kernels (experiment)
-static const int g_wup_max_blocks_wg = []{ int v = env_int_up("VQW_WGRAD_MAX_BLOCKS", g_wup_max_blocks); return v < 8 ? 8 : (v > 256 ? 256 : v); }();
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -990,7 +980,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_wgrad(WUpWgArgs a) {
 
 // Shapes served: full-resolution width a multiple of 32; Cout % 16 (an even number of 8-channel chunks); Cin % 64.
 bool conv_wino_up_dgrad_ok(int Cin, int Cout, int N, int h, int w) {
-    if (!g_wup_env || g_wino_mode != 0 || Cin % 64 != 0 || Cout % 16 != 0 || (2 * w) % 32 != 0 || h < 1 || N < 1) return false;
+    if (g_wino_mode != 0 || Cin % 64 != 0 || Cout % 16 != 0 || (2 * w) % 32 != 0 || h < 1 || N < 1) return false;
     const long P = (long)N * 4 * h * w;
     return P * (Cin > Cout ? Cin : Cout) * 4 <= 0xFFFFFFE0L;
 }
@@ -1016,7 +1006,7 @@ static int launch_up_dgrad(WUpDgArgs& a, hipStream_t st) {
         attr_set = true;
     }
     a.ntn = a.Cin / (16 * NBW);
-    int groups = g_wup_max_blocks / a.ntn;
+    int groups = conv_max_blocks() / a.ntn;
     if (groups < 1) groups = 1;
     const int even = ceil_div(a.nsp, groups);
     a.kt = even < 1 ? 1 : even;
@@ -1044,7 +1034,7 @@ int conv_wino_up_dgrad(const float* dy, const float* ws, float* g_low, int N, in
 
 // Forward: Cin % 16 (an even number of chunks), Cout % 64, full-resolution width a multiple of 32
 bool conv_wino_up_fwd_ok(int Cin, int Cout, int N, int h, int w) {
-    if (!g_wup_env || g_wino_mode != 0 || Cin % 16 != 0 || Cout % 64 != 0 || (2 * w) % 32 != 0 || h < 1 || N < 1) return false;
+    if (g_wino_mode != 0 || Cin % 16 != 0 || Cout % 64 != 0 || (2 * w) % 32 != 0 || h < 1 || N < 1) return false;
     const long P = (long)N * 4 * h * w;
     return P * (Cin > Cout ? Cin : Cout) * 4 <= 0xFFFFFFE0L;
 }
@@ -1064,7 +1054,7 @@ int conv_wino_up_fwd(const float* x_low, const float* ws, const float* bias, flo
     a.nbx = (unsigned)(Pl * Cin * 4);
     a.nbu = (unsigned)(9L * Cout * Cin * 4);
     a.nby = (unsigned)(4 * Pl * (y2 ? 32 : Cout) * 4);
-    int groups = g_wup_max_blocks / a.ntn;
+    int groups = conv_max_blocks() / a.ntn;
     if (groups < 1) groups = 1;
     const int even = ceil_div(a.nsp, groups);
     a.kt = even < 1 ? 1 : even;
@@ -1075,14 +1065,14 @@ int conv_wino_up_fwd(const float* x_low, const float* ws, const float* bias, flo
 
 // Weight gradient: Cin % 32, Cout % 32, low-resolution maps of whole 4 x 16 regions
 bool conv_wino_up_wgrad_ok(int Cin, int Cout, int N, int h, int w) {
-    if (!g_wup_env || g_wino_mode != 0 || Cin % 32 != 0 || Cout % 32 != 0 || w % 16 != 0 || h % 4 != 0 || N < 1) return false;
+    if (g_wino_mode != 0 || Cin % 32 != 0 || Cout % 32 != 0 || w % 16 != 0 || h % 4 != 0 || N < 1) return false;
     const long P = (long)N * 4 * h * w;
     return P * (Cin > Cout ? Cin : Cout) * 4 <= 0xFFFFFFE0L;
 }
 static int wup_wgrad_blocks(int Cin, int Cout, int N, int h, int w, int* kt_out) {
     const int nblk = (Cout / 32) * (Cin / 32);
     const int nsp = N * (h / 4) * (w / 16);
-    int nsb = g_wup_max_blocks_wg / nblk;
+    int nsb = conv_max_blocks() / nblk;
     if (nsb > nsp) nsb = nsp;
     if (nsb < 1) nsb = 1;
     const int kt = ceil_div(nsp, nsb);

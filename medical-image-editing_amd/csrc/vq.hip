@@ -22,9 +22,6 @@
 #include "../../include/vqwnet_hip.h"
 
 #define VQ_BLOCK 256
-#ifndef VQ_EXP
-#define VQ_EXP 0       // timing-only A/B builds (tools/vq_ab.sh): 1 = no arg-max epilogue, 2 = no stage refill / barrier, 4 = one MFMA chain per two blocks
-#endif
 #define VQ_LDS_FLOATS 15360  // 60 KiB of LDS for codebook + norms
 #define VQ_MAX_D 1024
 
@@ -506,10 +503,10 @@ __global__ void __launch_bounds__(256, 2) k_vq_mfma(const float* __restrict__ x,
     float best = -INFINITY;
     int bi = 0;
     for (int s = 0; s < nstage; ++s) {
-        const float* buf = smem + ((VQ_EXP & 2) ? 0 : (s & 1)) * STAGE;
+        const float* buf = smem + (s & 1) * STAGE;
         float* nbuf = smem + ((s + 1) & 1) * STAGE;
         const bool more = s + 1 < nstage;
-        if (more && !(VQ_EXP & 2)) {
+        if (more) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) pf[i] = buf_ld4(re, sel_u32(cvalid, goff0 + i * gstep + (unsigned)(s + 1) * stage_bytes, OOB));
         }
@@ -542,7 +539,7 @@ __global__ void __launch_bounds__(256, 2) k_vq_mfma(const float* __restrict__ x,
             const float* en = buf + TR * LS + b * 32 + 4 * h;
             const int code0 = s * TR + b * 32 + 4 * h;
 #pragma unroll
-            for (int g = 0; g < ((VQ_EXP & 1) ? 1 : 4); ++g) {
+            for (int g = 0; g < 4; ++g) {
                 const float4 e4 = *(const float4*)(en + 8 * g);
                 const float s0 = (2.f * acc[4 * g] - e4.x) - x2, s1 = (2.f * acc[4 * g + 1] - e4.y) - x2;
                 const float s2 = (2.f * acc[4 * g + 2] - e4.z) - x2, s3 = (2.f * acc[4 * g + 3] - e4.w) - x2;
@@ -552,12 +549,12 @@ __global__ void __launch_bounds__(256, 2) k_vq_mfma(const float* __restrict__ x,
                 if (s3 > best) { best = s3; bi = code0 + 8 * g + 3; }
             }
         }
-        if (more && !(VQ_EXP & 2)) {
+        if (more) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) *(float4*)(nbuf + loff0 + i * RSTEP * LS) = pf[i];
             if (tid < TR) nbuf[TR * LS + tid] = en_next;
         }
-        if (!(VQ_EXP & 2)) __syncthreads();
+        __syncthreads();
     }
     {   // the two halves of a pixel hold disjoint code rows: keep the larger score, ties to the lower code
         const float ob = __shfl_xor(best, 32, 64);

@@ -15,41 +15,30 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .library import Dispatch as _D
 
 CL = torch.channels_last
 
 
 # Kernels are reached through the PyTorch dispatcher: every entry point of the C ABI is an operator torch.ops.vqw.<name>
 # with a schema derived from its prototype (hipops/library.py; mutation annotations from the `const` qualifiers).
-# VQW_DISPATCH=0 calls the C functions directly through ctypes instead (A/B of the host-side cost).
-DISPATCH = os.environ.get("VQW_DISPATCH", "1") != "0"
 _dispatch = None
 
 
 def _L():
     global _dispatch
-    if not DISPATCH:
-        return _lib.load()
     if _dispatch is None:
-        from . import library
-        _dispatch = library.Dispatch()
+        _dispatch = _D()
     return _dispatch
 
 
-if DISPATCH:
-    from .library import Dispatch as _D
+# stream and tensor arguments as the dispatcher operators take them: the stream is torch's current one, tensors pass as they are
+def _st():
+    return _D.STREAM
 
-    def _st():
-        return _D.STREAM
 
-    def _p(t):
-        return t
-else:
-    def _st():
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def _p(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+def _p(t):
+    return t
 
 
 def _raw(t):
@@ -173,7 +162,7 @@ def reset_pending(params):
 # in the last tenth of the step when only weight gradients are left to run.  A gradient-ready listener that reads
 # gradients of several parameters (data parallel: a bucket is flattened on the lane that announces its last gradient)
 # orders its lane after the others first: sync_wgrad_lanes().
-WGRAD_LANES = max(1, int(os.environ.get("VQW_WGRAD_LANES", "2")))
+WGRAD_LANES = 2        # (one lane and three lanes measured slower: DESIGN §5)
 _lane_counter = 0
 
 
@@ -281,64 +270,8 @@ def _queue_lane_join():
         torch.autograd.Variable._execution_engine.queue_callback(_join_side_stream)
 
 
-# ----------------------------------------------------------------------------------------------
-# branch streams: independent sub-graphs of one forward pass on a second HIP stream
-# ----------------------------------------------------------------------------------------------
-# The SPADE modulation maps of the decoder depend only on the skip features, not on the up-path trunk; run on a branch
-# stream their MFMA-bound convolutions overlap the trunk's HBM-bound normalisation kernels.  Autograd replays each
-# node on the stream its forward ran on and orders the streams itself, so the backward pass forks the same way.
-# Off by default: measured at B=32, 256x256 it gains 2.5 % when the two views run one after the other (196 vs 191
-# img/s) but LOSES 8 % on top of the two-view streams (183 vs 200 img/s: five streams of persistent, LDS-filling conv
-# kernels starve each other), and two concurrent views alone are the fastest arrangement.  VQW_BRANCH_STREAMS=1 enables.
-BRANCH_STREAMS = os.environ.get("VQW_BRANCH_STREAMS", "0") != "0"
-_branch_streams = {}
-
-
-class Branch:
-    """with Branch(inputs...) as b: outs = f(...)   # on the branch stream of the current stream
-    b.join(outs...)                                  # current stream waits; tensors become usable on it"""
-
-    def __init__(self, *inputs):
-        self.inputs = [t for t in inputs if t is not None]
-        self.active = BRANCH_STREAMS and bool(self.inputs) and self.inputs[0].is_cuda
-
-    def __enter__(self):
-        if not self.active:
-            return self
-        self.cur = torch.cuda.current_stream()
-        key = (self.cur.device.index, self.cur.cuda_stream)
-        br = _branch_streams.get(key)
-        if br is None:
-            br = torch.cuda.Stream(device=self.cur.device, priority=self.cur.priority)
-            _branch_streams[key] = br
-        self.br = br
-        br.wait_event(self.cur.record_event())
-        for t in self.inputs:
-            t.record_stream(br)
-        self.ctx = torch.cuda.stream(br)
-        self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.active:
-            self.ev = self.br.record_event()
-            self.ctx.__exit__(*exc)
-        return False
-
-    def join(self, *outs):
-        if self.active:
-            self.cur.wait_event(self.ev)
-            for t in outs:
-                if t is not None:
-                    t.record_stream(self.cur)
-
-
 def join_streams():
-    """Order the current stream after every branch stream (end of a training step / before reading results elsewhere)."""
-    cur = torch.cuda.current_stream()
-    for br in _branch_streams.values():
-        if br.device == cur.device:
-            cur.wait_stream(br)
+    """End of a trainer step (begin_step() ... join_streams()): the BatchNorm counters deferred since begin_step() are bumped."""
     global _defer_counters
     _defer_counters = False
     flush_counters()
@@ -355,13 +288,8 @@ def bump_weight_epoch():
     _weight_epoch += 1
 
 
-_CACHE_ON = os.environ.get("VQW_WEIGHT_CACHE", "1") != "0"
-
-
 def _cached(weight, key, build, deps=()):
     """`deps`: further tensors the derived value is built from (concatenated convs)."""
-    if not _CACHE_ON:
-        return build()
     cache = weight.__dict__.setdefault("_vqw_cache", {})
     tag = (weight._version, _weight_epoch, weight.data_ptr()) + tuple((d._version, d.data_ptr()) for d in deps)
     cur = torch.cuda.current_stream()
@@ -467,10 +395,9 @@ def _conv_fwd_raw(x0, up0, x1, w, bias, N, H, W, Cout, ks, dil, relu=False):
     return y
 
 
-CONV_STATS = os.environ.get("VQW_CONV_STATS", "1") != "0"      # 0: InstanceNorm always reduces itself (A/B timing)
 # Winograd F(2x2, 3x3) form of plain 3x3 layers.  The INPUT and WEIGHT GRADIENTS take it whenever the library serves the
-# shape (VQW_WINOGRAD=0 turns the kernels off altogether): they are linear in dy given the forward's masks, so the form's
-# rounding difference (a few ulps of the accumulated magnitude) reaches the parameter gradients unamplified.  The training
+# shape: they are linear in dy given the forward's masks, so the form's rounding difference (a few ulps of the accumulated
+# magnitude) reaches the parameter gradients unamplified.  The training
 # FORWARD does not by default: the Winograd form computes the four pixels of a tile by four different formulas, so equal
 # inputs no longer give bit-equal outputs, and behind the quantised (piecewise constant) map the reference's max-pools sit
 # on exact ties - on the config-4 step fixture the broken ties moved decoder gradients 3-5x the reference's own fp32 spread
@@ -481,15 +408,12 @@ WINOGRAD_FWD = os.environ.get("VQW_WINOGRAD_FWD", "0") == "1"
 WINOGRAD_EVAL = os.environ.get("VQW_WINOGRAD_EVAL", "1") != "0"
 _in_custom_op = False          # set by hipops.functional around its no_grad() calls: those are training forwards
 
-
-WINOGRAD_FWD_ENCODER = os.environ.get("VQW_WINOGRAD_FWD_ENCODER", "0") == "1"
-WINOGRAD_FWD_POOLFREE = os.environ.get("VQW_WINOGRAD_FWD_POOLFREE", "1") != "0"      # decoder layers past its last max-pool
 _wino_fwd_scope = 0            # > 0 inside `with winograd_forward():`
 
 
 class winograd_forward:
-    """Context: plain 3x3 layers called inside take the Winograd forward also in training.  For sub-networks whose
-    activations are not piecewise constant (the encoder: its input is an image).  The Winograd form computes the four pixels
+    """Context: plain 3x3 layers called inside take the Winograd forward also in training.  For sub-networks in which nothing
+    compares activations of different pixels (the decoder past its last max-pool).  The Winograd form computes the four pixels
     of a 2x2 tile by four different formulas, so mathematically equal outputs are no longer bit-equal; behind the quantised
     (piecewise constant) map the reference's max-pools sit on exact ties and a broken tie re-routes gradients."""
 
@@ -1160,7 +1084,7 @@ def conv2d(x, weight, bias=None, dilation=1, up2x=False, skip=None, relu=False, 
     # norm_input=True: x is the output of instance_norm(...) and feeds this layer ONLY - its input-gradient launch then also
     # leaves that norm's backward sums (a gradient that autograd had to sum with another consumer's would miss them)
     in_src = getattr(x, "_vqw_in_src", None) if (norm_input and FUSE_IN_BWD) else None
-    if want_stats and CONV_STATS:
+    if want_stats:
         return _Conv2d.apply(x, skip, weight, bias, int(dilation), bool(up2x), bool(relu), True, wino, group, in_src)
     y = _Conv2d.apply(x, skip, weight, bias, int(dilation), bool(up2x), bool(relu), False, wino, group, in_src)
     return (y, None) if want_stats else y
@@ -1439,11 +1363,8 @@ def force_collectives(on=True):
     return old
 
 
-_FORCE_STATS = os.environ.get("VQW_DP_FORCE_STATS", "1") != "0"      # measurement aid: 0 = a forced one-rank run skips the statistics collectives
-
-
 def _dist_on():
-    return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or (FORCE_COLLECTIVES and _FORCE_STATS))
+    return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or FORCE_COLLECTIVES)
 
 
 def _all_reduce(t):
@@ -1626,9 +1547,6 @@ class _Add(torch.autograd.Function):
         return gy, gy, None, None
 
 
-ADD_NORM_FUSED = os.environ.get("VQW_ADD_NORM_FUSED", "1") != "0"      # 0: the norm writes its tensor, then the add reads it (A/B)
-
-
 class _AddNorm(torch.autograd.Function):
     """y = a + InstanceNorm(+ReLU)(x) with x the RAW convolution output and `part` its statistics partials (or None): the norm is
     applied inside the add's kernel (vqw_inorm_add_fwd), its output never written.  Backward: the gradient of `a` is gy (handed to
@@ -1673,7 +1591,7 @@ class _AddNorm(torch.autograd.Function):
 
 
 def add_norm_supported(a, x):
-    return bool(ADD_NORM_FUSED and x.is_cuda and x.dim() == 4 and tuple(a.shape) == tuple(x.shape) and _L().vqw_inorm_add_supported(x.shape[1]))
+    return bool(x.is_cuda and x.dim() == 4 and tuple(a.shape) == tuple(x.shape) and _L().vqw_inorm_add_supported(x.shape[1]))
 
 
 def add_norm(a, x, part=None, relu=False, eps=1e-5, a_group=None):
@@ -1745,7 +1663,6 @@ class _ResTail(torch.autograd.Function):
         return gx, gx
 
 
-IN_BWD_PAIR = os.environ.get("VQW_IN_BWD_PAIR", "1") != "0"      # 0: two separate InstanceNorm backward calls (A/B timing)
 RES_TAIL_BWD_FUSED = os.environ.get("VQW_RES_TAIL_BWD_FUSED", "1") != "0"      # 0: vqw_res_tail_bwd, then vqw_inorm_bwd_pair (A/B)
 
 
@@ -1800,7 +1717,7 @@ class _ResTailNorm(torch.autograd.Function):
         gp = nhwc(g_pooled) if g_pooled is not None else None
         go = nhwc(g_out) if g_out is not None else None
         g = torch.empty_like(out, memory_format=CL)
-        if RES_TAIL_BWD_FUSED and IN_BWD_PAIR and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not (C & 3):
+        if RES_TAIL_BWD_FUSED and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not (C & 3):
             # the tail's backward and both norms' backward sums in one pass over (out, gradients, x2, xid); g is written for the
             # apply pass only
             gx2 = torch.empty_like(x2, memory_format=CL)
@@ -1811,7 +1728,7 @@ class _ResTailNorm(torch.autograd.Function):
             return gx2, gxid, None, None, None
         _lib.check(L.vqw_res_tail_bwd(_p(out), _p(gp), _p(go), _p(g), N, H, W, C, _st()), "vqw_res_tail_bwd")
         gx2 = gxid = None
-        if IN_BWD_PAIR and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:      # both norms' backward, common gradient read once
+        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:      # both norms' backward, common gradient read once
             gx2 = torch.empty_like(x2, memory_format=CL)
             gxid = torch.empty_like(xid, memory_format=CL)
             ws = _ws(2 * L.vqw_plane_ws_bytes(N, C, H * W), x2)

@@ -84,7 +84,7 @@ class ResBlock(nn.Module):
         # (the 1 x 1 branch is created FIRST: autograd then runs it LAST in backward, where its input-gradient kernel adds to the
         # 3 x 3 convolution's gradient in its epilogue - every shape has that route, while a 16-channel 3 x 3 layer has no
         # accumulating kernel and its gradient used to be added by a separate three-pass kernel)
-        if RES_TAIL_NORM and dc.ends_in_norm_relu() and ds[1].eps == dc.double_conv[4].eps and not ds[1].relu:
+        if dc.ends_in_norm_relu() and ds[1].eps == dc.double_conv[4].eps and not ds[1].relu:
             xid, partid = ds[0](x, want_stats=True, grad_group=grp)
             x2, part2 = dc(x, raw_tail=True, grad_group=grp)
             got = ops.res_tail_norm(x2, xid, eps=ds[1].eps, part2=part2, partid=partid)
@@ -143,7 +143,6 @@ class DoubleConv(nn.Module):
 
 FUSE_GAMMA_BETA = os.environ.get("VQW_FUSE_GAMMA_BETA", "1") != "0"
 GRAD_GROUP_BLOCKS = os.environ.get("VQW_GRAD_GROUP_BLOCKS", "1") != "0"     # 0: autograd sums the ResBlock / style-input gradients (A/B)
-RES_TAIL_NORM = os.environ.get("VQW_RES_TAIL_NORM", "1") != "0"      # 0: ResBlock branches apply their norms themselves (A/B)
 
 
 class StyledDenorm(nn.Module):
@@ -221,23 +220,22 @@ class StyledResUpBlock(nn.Module):
         )
 
     def style_maps(self, skip_input):
-        """Modulation maps of both StyledDenorms on the branch stream (they do not depend on down_input)."""
+        """Modulation maps of both StyledDenorms (they do not depend on down_input)."""
         # both mlp_shared convolutions read skip_input: one gradient group (their input gradients meet in the second one's epilogue)
         grp = ops.GradGroup(2) if (GRAD_GROUP_BLOCKS and skip_input.requires_grad) else None
-        with ops.Branch(skip_input) as br:
-            c1, c2 = self.norm1.mlp_shared[0], self.norm2.mlp_shared[0]
-            if ops.conv2d_pair_supported(skip_input, c1.weight, c2.weight):
-                # both mlp_shared convolutions (+ReLU) read skip_input: one launch on the concatenated weights
-                a1, a2 = ops.conv2d_pair(skip_input, c1.weight, c1.bias, c2.weight, c2.bias, relu=True, grad_group=grp)
-                m1 = self.norm1.style_maps(skip_input, actv=a1)
-                m2 = self.norm2.style_maps(skip_input, actv=a2)
-            else:
-                m1 = self.norm1.style_maps(skip_input, grad_group=grp)
-                m2 = self.norm2.style_maps(skip_input, grad_group=grp)
-        return br, m1, m2
+        c1, c2 = self.norm1.mlp_shared[0], self.norm2.mlp_shared[0]
+        if ops.conv2d_pair_supported(skip_input, c1.weight, c2.weight):
+            # both mlp_shared convolutions (+ReLU) read skip_input: one launch on the concatenated weights
+            a1, a2 = ops.conv2d_pair(skip_input, c1.weight, c1.bias, c2.weight, c2.bias, relu=True, grad_group=grp)
+            m1 = self.norm1.style_maps(skip_input, actv=a1)
+            m2 = self.norm2.style_maps(skip_input, actv=a2)
+        else:
+            m1 = self.norm1.style_maps(skip_input, grad_group=grp)
+            m2 = self.norm2.style_maps(skip_input, grad_group=grp)
+        return m1, m2
 
     def forward(self, down_input, skip_input, maps=None):
-        br, m1, m2 = maps if maps is not None else self.style_maps(skip_input)
+        m1, m2 = maps if maps is not None else self.style_maps(skip_input)
         if self.use_pixel_shuffle:
             x, up = self.up_sample(down_input), False
         else:
@@ -255,7 +253,6 @@ class StyledResUpBlock(nn.Module):
         # the shortcut's InstanceNorm(+ReLU) is applied where its output is consumed - inside norm2's modulation kernel, from the
         # statistics its convolution's epilogue left: the normalised shortcut tensor is never written (ops.spade_norm, residual_norm)
         sn, part_s = self.conv[1], part
-        br.join(*m1, *m2)
         h = self.norm1(h, skip_input, relu=True, maps=m1, part=part1)
         h, part = self.conv2(h, want_stats=True)       # the epilogue leaves norm2's batch statistics
         return self.norm2(h, skip_input, relu=self.use_output_act, maps=m2, residual=s, part=part,

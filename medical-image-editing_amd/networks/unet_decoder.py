@@ -1,6 +1,4 @@
 """SPADE-style U-Net decoder (reference: networks/unet_decoder.py:19-164) on the HIP kernels."""
-import contextlib
-
 import torch
 import torch.nn as nn
 
@@ -54,13 +52,12 @@ class UNetDecoder(nn.Module):
                 d_skips[i] = torch.zeros_like(d_skips[i])
             else:
                 d_skips[i] = self.dropblock(d_skips[i])
-        # the SPADE modulation maps need only the skips: queue them on the branch stream, deepest level first, so
-        # they run beside the bottleneck and the up-path trunk (same arithmetic as evaluating them inside each block)
+        # the SPADE modulation maps need only the skips: computed up front, deepest level first (same arithmetic as
+        # evaluating them inside each block)
         # Past the last max-pool nothing downstream decides anything by comparing activations of different pixels, so the
         # layers from here on may take the Winograd forward in training too (ops.winograd_forward; the down path above
         # keeps the direct form: its pools sit on exact ties of the piecewise constant input)
-        scope = ops.winograd_forward() if ops.WINOGRAD_FWD_POOLFREE else contextlib.nullcontext()
-        with scope:
+        with ops.winograd_forward():
             maps = [u.style_maps(d_skip) for u, d_skip in zip(self.up_convs, d_skips)]
             x = self.double_conv2(x)
             for u, d_skip, m in zip(self.up_convs, d_skips, maps):

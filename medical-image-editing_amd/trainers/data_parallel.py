@@ -1,22 +1,23 @@
 """Data-parallel gradient exchange for one process per GPU (RCCL over xGMI via torch.distributed).
 
-Replaces the Lightning DDPPlugin the reference launches with (run_vqwnet.py:112-121).  Parameters are
-grouped into buckets in the order their gradients become ready in backward (decoder tail first); a
-post-accumulate hook on each parameter counts its bucket down, and the moment a bucket is complete
-its flat buffer is all-reduced asynchronously on a side stream while the remaining backward kernels
-keep running.  `finish()` waits for the outstanding collectives and scatters the averaged gradients back.
+Replaces the Lightning DDPPlugin the reference launches with (run_vqwnet.py:112-121).  By default (`overlap=False`,
+VQW_DP_OVERLAP=0) the gradients are exchanged in `finish()`, after the backward pass has been enqueued: the parameters'
+gradients are flattened, in the order they become ready in backward (decoder tail first), into ONE buffer, which is
+all-reduced with the blocking form of the call (it only enqueues: the host does not wait for the GPU); the averaged
+gradients are then scattered back.
 
 MI355X sizing: xGMI is point-to-point (7 links per GPU), so a ring all-reduce is per-link bound and the
-61.8 MB of fp32 gradients of the R-cfg model cost ~1 ms in total; few large buckets (16 MiB in the overlapped schedule)
-keep launch/latency overhead negligible against a >100 ms step.
+61.8 MB of fp32 gradients of the R-cfg model cost ~1 ms in total against a ~90 ms step.  One message instead of four
+16 MiB ones (round 4) gives the same step time on the one-rank RCCL path and pays one collective's fixed cost instead of
+four on a real ring.
 
-Two schedules.  `overlap=False` (default, VQW_DP_OVERLAP=0): the buckets are exchanged in finish(), after the backward pass
-has been enqueued - as ONE all-reduce of the whole 61.8 MB (round 4; four 16 MiB ones before: the same step time on the one-rank
-RCCL path, one collective's fixed cost instead of four on a real ring).  On this model the whole exchange is ~1 ms
-of a 98 ms step, while launching buckets from inside the backward pass (`overlap=True`) costs more than it hides: the
-stream that completes a bucket has to wait for every other producer stream of that bucket, which ties the two view streams
-and the weight-gradient lanes together (measured on one GPU with a one-rank RCCL group: +8.5 ms per step overlapped,
-profiles/r03_dp_one_gpu.txt).  The overlapped schedule stays for models whose gradient volume is worth hiding.
+Opt-in: the overlapped schedule (`overlap=True`, VQW_DP_OVERLAP=1).  Parameters are grouped into 16 MiB buckets; a
+post-accumulate hook on each parameter counts its bucket down, and the moment a bucket is complete its flat buffer is
+all-reduced asynchronously on the process group's stream while the remaining backward kernels keep running; `finish()`
+waits for the outstanding collectives.  On this model it costs more than it hides: the stream that completes a bucket has
+to wait for every other producer stream of that bucket, which ties the two view streams and the weight-gradient lanes
+together (measured on one GPU with a one-rank RCCL group: +8.5 ms per step, profiles/r03_dp_one_gpu.txt).  It stays for
+models whose gradient volume is worth hiding.
 Works unchanged on the gloo backend (CPU tests, world_size 2).
 """
 import os
@@ -32,15 +33,8 @@ import torch.distributed as dist
 # setting in the environment wins.
 os.environ.setdefault("TORCH_NCCL_AVOID_RECORD_STREAMS", "1")
 
-_SKIP_COLLECTIVE = os.environ.get("VQW_DP_DEBUG", "") == "noar"
-_TINY = os.environ.get("VQW_DP_DEBUG", "") == "tiny"
-_SYNC_AR = os.environ.get("VQW_DP_SYNC_AR", "1") != "0"     # after-backward schedule: the blocking form of the call
-_HOST_TIMING = os.environ.get("VQW_DP_HOST_TIMING", "0") == "1"     # measurement aid: host time spent inside dist.all_reduce
-
 
 class GradientAllReducer:
-    host_ms_in_all_reduce = 0.0
-
     def __init__(self, params, bucket_bytes=None, process_group=None, overlap=None):
         self.overlap = (os.environ.get("VQW_DP_OVERLAP", "0") != "0") if overlap is None else bool(overlap)
         if bucket_bytes is None:
@@ -169,28 +163,14 @@ class GradientAllReducer:
             flat = self._flat_buf[bi] = torch.empty(n, dtype=views[0].dtype, device=views[0].device)
         torch.cat(views, out=flat)
         self._flat[bi] = (flat, views)
-        # async: on RCCL the collective runs on the process group's own stream, ordered after the producing
-        # kernels by the event torch.distributed records, so it overlaps with the rest of backward
         self.launches += 1
-        if _HOST_TIMING:
-            import time
-            t0 = time.perf_counter()
-        if _SKIP_COLLECTIVE:       # measurement aid: flatten / scale / scatter without the collective (wrong on > 1 rank)
-            self._work.append((bi, None))
-            return
-        # (VQW_DP_DEBUG=tiny: the collective on 1 KiB of the bucket only - a measurement aid, wrong on > 1 rank: is the one-rank
-        # group's cost per call or per byte?)
-        # The after-backward schedule has nothing to overlap the exchange with and takes the BLOCKING form of the call (it still
-        # only enqueues: the host does not wait for the GPU): on the one-rank RCCL path the asynchronous form + work.wait() costs
-        # 6-8 ms per step whatever the message size or count (95.6-98.1 against 89.4 ms; the plain step: 88.9), the blocking
-        # form nothing.  VQW_DP_SYNC_AR=0 restores the asynchronous form there (A/B).
-        use_async = self.overlap or not _SYNC_AR
-        work = dist.all_reduce(flat[:256] if _TINY else flat, op=dist.ReduceOp.SUM, group=self.group, async_op=use_async)
-        if not use_async:
-            work = None
-        if _HOST_TIMING:
-            self.host_ms_in_all_reduce += (time.perf_counter() - t0) * 1e3
-        self._work.append((bi, work))
+        # overlapped: on RCCL the collective runs on the process group's own stream, ordered after the producing kernels by the
+        # event torch.distributed records, so it overlaps with the rest of backward.  The after-backward schedule has nothing to
+        # overlap the exchange with and takes the BLOCKING form of the call (it still only enqueues: the host does not wait for
+        # the GPU): on the one-rank RCCL path the asynchronous form + work.wait() costs 6-8 ms per step whatever the message
+        # size or count (95.6-98.1 against 89.4 ms; the plain step: 88.9), the blocking form nothing.
+        work = dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group, async_op=self.overlap)
+        self._work.append((bi, work if self.overlap else None))
 
     def finish(self):
         """Wait for every bucket, write the rank-mean back into p.grad."""
