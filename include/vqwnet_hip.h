@@ -419,6 +419,26 @@ int vqw_window_mse_fwd(const float* a, const float* b, float* loss, void* ws, si
 int vqw_window_mse_bwd(const float* a, const float* b, const float* gloss, float* ga, long n, float alpha, float beta,
                        float lo, float hi, void* stream);
 
+/* ---- focal frequency loss (ABI 9; the focal-frequency-loss package v0.3.0 as FFL(loss_weight, alpha) in
+ *      trainers/base.py:277-278, single_window_trainer.py:117-136, 286-309, 453-466, multi_window_trainer.py:100-126).
+ * pred, target: [N,H,W,C] cut into patch_factor^2 patches of h x w = H/pf x W/pf; per plane (n, patch, c)
+ * D = fft2(win(pred) - win(target), ortho), loss = loss_weight * mean(w |D|^2) with w = |D|^alpha (log(. + 1) with
+ * log_matrix) over its max per plane (over everything with batch_matrix), NaN -> 0.  win(x) = clamp(win_alpha * x +
+ * win_beta, win_lo, win_hi) when `windowed`, else the identity.  tw_h / tw_w: the twiddle tables of sides h and w
+ * ([n][2], vqw_freq_twiddles; built once per side and device).  The forward leaves D and the folded maxima in `ws`: the
+ * backward reads them from the same buffer (and uses the rest as scratch).  gpred = dL/dpred, gtarget = dL/dtarget
+ * (either may be NULL; zero where the window clamps). */
+size_t vqw_freq_loss_ws_bytes(int N, int C, int H, int W, int patch_factor);
+int vqw_freq_twiddles(float* tw, int n, void* stream);
+int vqw_freq_loss_fwd(const float* pred, const float* target, const float* tw_h, const float* tw_w, float* loss, void* ws,
+                      size_t ws_bytes, int N, int C, int H, int W, int patch_factor, float alpha, int log_matrix,
+                      int batch_matrix, float loss_weight, int windowed, float win_alpha, float win_beta, float win_lo,
+                      float win_hi, void* stream);
+int vqw_freq_loss_bwd(const float* pred, const float* target, const float* tw_h, const float* tw_w, const float* gloss,
+                      float* gpred, float* gtarget, void* ws, size_t ws_bytes, int N, int C, int H, int W, int patch_factor,
+                      float alpha, int log_matrix, float loss_weight, int windowed, float win_alpha, float win_beta,
+                      float win_lo, float win_hi, void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

@@ -140,6 +140,10 @@ SIGNATURES = {
     "vqw_hinge_bwd": (c_i, [c_p, c_l, c_i, c_p, c_p, c_p]),
     "vqw_window_mse_fwd": (c_i, [c_p, c_p, c_p, c_p, c_sz, c_l, c_f, c_f, c_f, c_f, c_p]),
     "vqw_window_mse_bwd": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_p]),
+    "vqw_freq_loss_ws_bytes": (c_sz, [c_i] * 5),
+    "vqw_freq_twiddles": (c_i, [c_p, c_i, c_p]),
+    "vqw_freq_loss_fwd": (c_i, [c_p] * 6 + [c_sz] + [c_i] * 5 + [c_f, c_i, c_i, c_f, c_i] + [c_f] * 4 + [c_p]),
+    "vqw_freq_loss_bwd": (c_i, [c_p] * 8 + [c_sz] + [c_i] * 5 + [c_f, c_i, c_f, c_i] + [c_f] * 4 + [c_p]),
     "vqw_pixel_shuffle2": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "vqw_dropblock_mask": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "vqw_dropblock_apply": (c_i, [c_p, c_p, c_p, c_p, c_l, c_i, c_p]),
@@ -158,7 +162,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 def load():

@@ -1867,6 +1867,72 @@ def window_mse_loss(a, b, dataset_window, target_window):
     return _WindowMse.apply(a, b.detach(), *window_map(dataset_window, target_window))
 
 
+_twiddles = {}
+
+
+def _twiddle_table(n, like):
+    """(cos, sin)(2 pi m / n) / sqrt(n), m < n, of the DFTs behind frequency_loss: built once per (device, n), the first
+    time a side is seen (a one-time set-up cost outside the steady-state step)."""
+    key = (like.device, n)
+    tw = _twiddles.get(key)
+    if tw is None:
+        tw = torch.empty(2 * n, dtype=torch.float32, device=like.device)
+        _lib.check(_L().vqw_freq_twiddles(_p(tw), n, _st()), "vqw_freq_twiddles")
+        if not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream().synchronize()    # later calls may read it from another stream
+        _twiddles[key] = tw
+    return tw
+
+
+class _FreqLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, alpha, pf, log_matrix, batch_matrix, loss_weight, win):
+        _dev(pred, target)
+        pred, target = nhwc(pred), nhwc(target)
+        if pred.shape != target.shape:
+            raise RuntimeError("frequency_loss: shape mismatch %s vs %s" % (tuple(pred.shape), tuple(target.shape)))
+        N, C, H, W = pred.shape
+        if pf < 1 or H % pf or W % pf:
+            raise RuntimeError("frequency_loss: H=%d and W=%d must be divisible by patch_factor=%d" % (H, W, pf))
+        if not alpha >= 0.0:
+            raise RuntimeError("frequency_loss: alpha must be >= 0 (got %r)" % (alpha,))
+        L = _L()
+        tw_h, tw_w = _twiddle_table(H // pf, pred), _twiddle_table(W // pf, pred)
+        out = torch.empty((), dtype=torch.float32, device=pred.device)
+        ws = _ws(L.vqw_freq_loss_ws_bytes(N, C, H, W, pf), pred)        # D and the folded maxima, kept for backward
+        wargs = (1,) + tuple(float(v) for v in win) if win is not None else (0, 1.0, 0.0, 0.0, 0.0)
+        ctx.args = (N, C, H, W, pf, float(alpha), int(bool(log_matrix)), float(loss_weight)) + wargs
+        _lib.check(L.vqw_freq_loss_fwd(_p(pred), _p(target), _p(tw_h), _p(tw_w), _p(out), _p(ws), ws.numel(), N, C, H, W, pf,
+                                       float(alpha), int(bool(log_matrix)), int(bool(batch_matrix)), float(loss_weight),
+                                       *wargs, _st()), "vqw_freq_loss_fwd")
+        ctx.save_for_backward(pred, target, tw_h, tw_w, ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, tw_h, tw_w, ws = ctx.saved_tensors
+        gp = torch.empty_like(pred, memory_format=CL) if ctx.needs_input_grad[0] else None
+        gt = torch.empty_like(target, memory_format=CL) if ctx.needs_input_grad[1] else None
+        if gp is None and gt is None:
+            return (None,) * 8
+        _lib.check(_L().vqw_freq_loss_bwd(_p(pred), _p(target), _p(tw_h), _p(tw_w), _p(g.contiguous()), _p(gp), _p(gt), _p(ws),
+                                          ws.numel(), *ctx.args, _st()), "vqw_freq_loss_bwd")
+        return gp, gt, None, None, None, None, None, None
+
+
+def frequency_loss(pred, target, alpha=1.0, patch_factor=1, log_matrix=False, batch_matrix=False, loss_weight=1.0,
+                   window=None):
+    """Focal frequency loss (focal-frequency-loss 0.3.0, FocalFrequencyLoss without ave_spectrum / matrix):
+    loss_weight * mean(w |fft2(pred - target)|^2) over the patch_factor^2 patches of every (n, c) plane, with the spectrum
+    weight w = |D|^alpha (log(. + 1) with log_matrix) normalised by its max per plane (over everything with batch_matrix),
+    detached.  window = (alpha, beta, lo, hi) of `window_map`: both images are re-windowed inside the kernel first.
+    Gradients flow to both inputs (target's is the negation of pred's, masked by its own window clamp)."""
+    if window is not None and len(window) != 4:
+        raise RuntimeError("frequency_loss: window must be the (alpha, beta, lo, hi) of window_map")
+    return _FreqLoss.apply(pred, target, float(alpha), int(patch_factor), bool(log_matrix), bool(batch_matrix),
+                           float(loss_weight), None if window is None else tuple(window))
+
+
 class _WeightedSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weights, *terms):

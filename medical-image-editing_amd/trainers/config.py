@@ -10,12 +10,14 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
                  use_regularization_loss}, use_recon_loss, use_frequency_loss, use_perceptual_loss}
     config.{enc_optim, dec_optim}.{lr, b1, b2, weight_decay}
     config.augmentation.{modules, ...}            (optional: absent -> the exact-integer flip views of the benchmark)
-    config.dataset.{window_width, window_center, window_scale}, config.loss.recon_weights   (multi-window runs, -w)
+    config.dataset.{window_width, window_center, window_scale}, config.loss.{recon_weights, freq_weights}   (multi-window
+                 runs, -w)
 
-Frequency (focal-frequency-loss) and perceptual (VGG / LPIPS weights that must be fetched) losses are third-party and
-absent offline: a config that switches them on raises instead of silently training something else.
+The focal frequency loss (use_frequency_loss) is functions.FocalFrequencyLoss, built on HIP kernels in place of the
+third-party focal-frequency-loss package.  The perceptual loss (VGG / LPIPS weights that must be fetched) is absent
+offline: a config that switches it on raises instead of silently training something else.
 """
-from functions import EmbeddingLoss
+from functions import EmbeddingLoss, FocalFrequencyLoss
 from hipops import Adam
 from networks import UNetEncoder, UNetDecoder, RandomTransform
 
@@ -72,11 +74,17 @@ def configure_losses(config):
     c = config.loss
     if _get(c, "use_perceptual_loss"):
         raise NotImplementedError("use_perceptual_loss needs pretrained VGG / LPIPS weights that cannot be fetched offline")
-    if _get(c, "use_frequency_loss"):
-        raise NotImplementedError("use_frequency_loss needs the third-party focal-frequency-loss package (absent offline)")
     return EmbeddingLoss(dict_size=config.model.vqmodel.dict_size, margin=c.embed_loss.margin,
                          use_distance_loss=c.embed_loss.use_distance_loss,
                          use_regularization_loss=c.embed_loss.use_regularization_loss)
+
+
+def configure_frequency_loss(config):
+    """-> FocalFrequencyLoss(loss_weight=1.0, alpha=1.0) as base.py:277-278 builds it when use_frequency_loss is set,
+    else None."""
+    if _get(config.loss, "use_frequency_loss"):
+        return FocalFrequencyLoss(loss_weight=1.0, alpha=1.0)
+    return None
 
 
 def loss_weights(config):
@@ -100,12 +108,20 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
     mode = _get(config.run, "training_mode", "first_step")
     if mode != "first_step":
         raise NotImplementedError("training_mode %r: use trainers.SecondStepTrainer for the GAN step" % mode)
-    encoder, decoder = configure_models(config)
-    if data_parallel is None:
-        data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    frequency_loss = configure_frequency_loss(config)
     if multi_window is None and _get(config.loss, "recon_weights") is not None and _get(config.dataset, "window_width") is not None:
         d = config.dataset
         multi_window = dict(dataset_window=(d.window_width, d.window_center, d.window_scale), recon_weights=tuple(config.loss.recon_weights))
+    freq_weights = None
+    if frequency_loss is not None and multi_window is not None:
+        freq_weights = _get(config.loss, "freq_weights")
+        if freq_weights is None:
+            raise ValueError("config.loss.freq_weights is required for a multi-window run with use_frequency_loss "
+                             "(multi_window_trainer.py:100-126)")
+        freq_weights = tuple(freq_weights)
+    encoder, decoder = configure_models(config)
+    if data_parallel is None:
+        data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     g = config.model.vqmodel
     return FirstStepTrainer(
         in_channels=g.in_channels, enc_filters=tuple(g.enc_filters), dec_filters=tuple(g.dec_filters), dict_size=g.dict_size,
@@ -113,4 +129,4 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
         views=views if views is not None else set_transform(config, seed=_get(config.run, "seed", 0) or 0), device=device,
         encoder=encoder, decoder=decoder, data_parallel=data_parallel, multi_window=multi_window,
         embed_loss=configure_losses(config), enc_optim=_adam_kwargs(config.enc_optim), dec_optim=_adam_kwargs(config.dec_optim),
-        use_recon_loss=bool(_get(config.loss, "use_recon_loss", True)))
+        use_recon_loss=bool(_get(config.loss, "use_recon_loss", True)), frequency_loss=frequency_loss, freq_weights=freq_weights)

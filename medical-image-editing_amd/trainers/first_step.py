@@ -91,7 +91,8 @@ class FirstStepTrainer:
                  dict_size=10, momentum=0.999, margin=0.5, loss_weight=None, lr=1e-4, betas=(0.5, 0.999),
                  weight_decay=0.0, use_pixel_shuffle=False, dropped_skip_layers=(), views=None, device="cuda",
                  encoder=None, decoder=None, data_parallel=False, use_onehot=False, concurrent_views=None,
-                 multi_window=None, embed_loss=None, enc_optim=None, dec_optim=None, use_recon_loss=True):
+                 multi_window=None, embed_loss=None, enc_optim=None, dec_optim=None, use_recon_loss=True,
+                 frequency_loss=None, freq_weights=None):
         self.device = torch.device(device)
         self.encoder = encoder if encoder is not None else UNetEncoder(
             in_channels, list(enc_filters), dict_size, momentum, 'torch', False, 1, True)
@@ -110,6 +111,12 @@ class FirstStepTrainer:
         # multi_window = dict(dataset_window=(width, center, scale), recon_weights=(w_full, w_lung, w_mediastinal)): the
         # reconstruction term of trainers/multi_window_trainer.py:93-118 (same step otherwise)
         self.multi_window = multi_window
+        # frequency_loss: functions.FocalFrequencyLoss (config.loss.use_frequency_loss) or None; in multi-window runs
+        # freq_weights = config.loss.freq_weights (w_full, w_lung, w_mediastinal), multi_window_trainer.py:100-126
+        self.frequency_loss = frequency_loss
+        self.freq_weights = tuple(freq_weights) if freq_weights is not None else None
+        if frequency_loss is not None and multi_window is not None and self.freq_weights is None:
+            raise ValueError("multi-window training with the frequency loss needs freq_weights (config.loss.freq_weights)")
         # base.py:165-175: one Adam per sub-network over its trainable parameters
         # (enc_optim / dec_optim: dicts with lr, betas, weight_decay per sub-network, as config.enc_optim / dec_optim give)
         eo = {**dict(lr=lr, betas=betas, weight_decay=weight_decay), **(enc_optim or {})}
@@ -163,21 +170,27 @@ class FirstStepTrainer:
             l_cross, l_dist, l_reg = self.embed_loss.forward_labels(embed_1, r_ids_1, embed_2, r_ids_2, codebook)
         recon_1 = self.decoder(embed_1)
         rec_1 = self._recon_terms(recon_1, clear_1)
+        frq_1 = self._freq_terms(recon_1, clear_1)
         with torch.cuda.stream(s2):
             recon_2 = self.decoder(embed_2)
             rec_2 = self._recon_terms(recon_2, clear_2)
+            frq_2 = self._freq_terms(recon_2, clear_2)
             ev2 = s2.record_event()
         s1.wait_event(ev2)
-        for t in [l_commit_2, recon_2, l_cross, embed_2, r_ids_2, ids_2] + [t for t, _ in rec_2] + \
+        for t in [l_commit_2, recon_2, l_cross, embed_2, r_ids_2, ids_2] + [t for t, _ in rec_2 + frq_2] + \
                 [t for t in (l_dist, l_reg) if torch.is_tensor(t)]:
             t.record_stream(s1)
         l_rec_1, l_rec_2 = rec_1[0][0], rec_2[0][0]
+        terms = rec_1 + rec_2 + frq_1 + frq_2
         l_total = ops.weighted_sum(
-            [l_commit_1, l_commit_2, l_cross, l_dist, l_reg] + [t for t, _ in rec_1 + rec_2],
-            [w.commit, w.commit, w.cross, w.dist, w.reg] + [c for _, c in rec_1 + rec_2])
-        return dict(total=l_total, commit_1=l_commit_1, commit_2=l_commit_2, cross=l_cross, dist=l_dist, reg=l_reg,
-                    recon_l1=l_rec_1, recon_l2=l_rec_2, ids_1=ids_1, ids_2=ids_2, recon_1=recon_1, recon_2=recon_2,
-                    embed_1=embed_1, embed_2=embed_2)
+            [l_commit_1, l_commit_2, l_cross, l_dist, l_reg] + [t for t, _ in terms],
+            [w.commit, w.commit, w.cross, w.dist, w.reg] + [c for _, c in terms])
+        out = dict(total=l_total, commit_1=l_commit_1, commit_2=l_commit_2, cross=l_cross, dist=l_dist, reg=l_reg,
+                   recon_l1=l_rec_1, recon_l2=l_rec_2, ids_1=ids_1, ids_2=ids_2, recon_1=recon_1, recon_2=recon_2,
+                   embed_1=embed_1, embed_2=embed_2)
+        if frq_1:                 # only with the frequency loss on: without it the step returns what it always did
+            out.update(freq_1=frq_1[0][0], freq_2=frq_2[0][0])
+        return out
 
     def _recon_terms(self, recon, clear):
         """[(loss term, weight)] of one view's reconstruction loss: plain MSE, or the multi-window mean of
@@ -190,6 +203,20 @@ class FirstStepTrainer:
         terms = [ops.mse_loss(recon, clear), ops.window_mse_loss(recon, clear, dw, LUNG_WINDOW),
                  ops.window_mse_loss(recon, clear, dw, MEDIASTINAL_WINDOW)]
         return [(t, self.w.recon * float(r) / 3.0) for t, r in zip(terms, rw)]
+
+    def _freq_terms(self, recon, clear):
+        """[(loss term, weight)] of one view's focal frequency loss (single_window_trainer.py:117-136): none without the
+        loss; FFL(recon, clear); or, multi-window, freq_weights[i] / 3 * FFL on the full / lung / mediastinal windows with
+        the window map applied inside the kernel (multi_window_trainer.py:100-126)."""
+        ffl = self.frequency_loss
+        if ffl is None:
+            return []
+        if self.multi_window is None:
+            return [(ffl(recon, clear), self.w.freq)]
+        dw = self.multi_window["dataset_window"]
+        terms = [ffl(recon, clear), ffl(recon, clear, window=ops.window_map(dw, LUNG_WINDOW)),
+                 ffl(recon, clear, window=ops.window_map(dw, MEDIASTINAL_WINDOW))]
+        return [(t, self.w.freq * float(f) / 3.0) for t, f in zip(terms, self.freq_weights)]
 
     def forward_losses(self, image, noise=None):
         """Lines 73-137 of the reference step.  `image` is in [-1, 1] (dataloader convention)."""
@@ -211,13 +238,18 @@ class FirstStepTrainer:
         recon_1 = self.decoder(embed_1)
         recon_2 = self.decoder(embed_2)
         rec_1, rec_2 = self._recon_terms(recon_1, clear_1), self._recon_terms(recon_2, clear_2)
+        frq_1, frq_2 = self._freq_terms(recon_1, clear_1), self._freq_terms(recon_2, clear_2)
         l_rec_1, l_rec_2 = rec_1[0][0], rec_2[0][0]
+        terms = rec_1 + rec_2 + frq_1 + frq_2
         l_total = ops.weighted_sum(
-            [l_commit_1, l_commit_2, l_cross, l_dist, l_reg] + [t for t, _ in rec_1 + rec_2],
-            [w.commit, w.commit, w.cross, w.dist, w.reg] + [c for _, c in rec_1 + rec_2])
-        return dict(total=l_total, commit_1=l_commit_1, commit_2=l_commit_2, cross=l_cross, dist=l_dist, reg=l_reg,
-                    recon_l1=l_rec_1, recon_l2=l_rec_2, ids_1=ids_1, ids_2=ids_2, recon_1=recon_1, recon_2=recon_2,
-                    embed_1=embed_1, embed_2=embed_2)
+            [l_commit_1, l_commit_2, l_cross, l_dist, l_reg] + [t for t, _ in terms],
+            [w.commit, w.commit, w.cross, w.dist, w.reg] + [c for _, c in terms])
+        out = dict(total=l_total, commit_1=l_commit_1, commit_2=l_commit_2, cross=l_cross, dist=l_dist, reg=l_reg,
+                   recon_l1=l_rec_1, recon_l2=l_rec_2, ids_1=ids_1, ids_2=ids_2, recon_1=recon_1, recon_2=recon_2,
+                   embed_1=embed_1, embed_2=embed_2)
+        if frq_1:                 # only with the frequency loss on: without it the step returns what it always did
+            out.update(freq_1=frq_1[0][0], freq_2=frq_2[0][0])
+        return out
 
     def training_step(self, batch, noise=None):
         image = batch['image'] if isinstance(batch, dict) else batch
@@ -243,7 +275,8 @@ class FirstStepTrainer:
 
     @staticmethod
     def scalars(out):
-        """Host copies of the logged scalars (one sync; keep out of timed regions)."""
+        """Host copies of the logged scalars (one sync; keep out of timed regions); `freq` is 0.0 without the frequency loss."""
         f = lambda t: float(t.detach()) if torch.is_tensor(t) else float(t)  # noqa: E731
         return dict(total=f(out["total"]), commit=f(out["commit_1"]) + f(out["commit_2"]), cross=f(out["cross"]),
-                    dist=f(out["dist"]), reg=f(out["reg"]), recon=f(out["recon_l1"]) + f(out["recon_l2"]))
+                    dist=f(out["dist"]), reg=f(out["reg"]), recon=f(out["recon_l1"]) + f(out["recon_l2"]),
+                    freq=f(out.get("freq_1", 0.0)) + f(out.get("freq_2", 0.0)))

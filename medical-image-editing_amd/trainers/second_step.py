@@ -1,9 +1,10 @@
 """Second training step (generator + PatchGAN discriminator) of the VQ-W-Net: reference
 trainers/single_window_trainer.py:434-488 (`_train_second_step_nl_dis`), optimisers per trainers/base.py:165-181.
 
-The encoder is frozen (eval mode, no_grad); the decoder is trained on  w.recon * MSE(recon, image) + w.gen * (-mean(D(recon)));
-then the discriminator on  w.dis * hinge_d_loss(D(image), D(recon.detach()))  for n_inner_loops.  Frequency / perceptual
-terms (LPIPS / VGG weights, FFT loss) are not part of this build, as in the first step.
+The encoder is frozen (eval mode, no_grad); the decoder is trained on  w.recon * MSE(recon, image) + w.gen * (-mean(D(recon)))
+(+ w.freq * FFL(recon, image) with a frequency_loss, :453-466); then the discriminator on  w.dis * hinge_d_loss(D(image),
+D(recon.detach()))  for n_inner_loops.  The perceptual term (LPIPS / VGG weights that must be fetched) is not part of this
+build, as in the first step.
 """
 from collections import namedtuple
 
@@ -13,12 +14,12 @@ from hipops import ops, Adam
 from networks.discriminator import NLayerDiscriminator
 from functions.gan_loss import hinge_d_loss, generator_loss
 
-GanLossWeights = namedtuple("GanLossWeights", "recon gen dis", defaults=(1.0, 1.0, 1.0))
+GanLossWeights = namedtuple("GanLossWeights", "recon gen dis freq", defaults=(1.0, 1.0, 1.0, 0.0))
 
 
 class SecondStepTrainer:
     def __init__(self, encoder, decoder, dis=None, loss_weight=None, n_inner_loops=1, lr=1e-4, betas=(0.5, 0.999),
-                 weight_decay=0.0, device="cuda", data_parallel=False):
+                 weight_decay=0.0, device="cuda", data_parallel=False, frequency_loss=None):
         self.device = torch.device(device)
         from .first_step import StepThrottle
         self.throttle = StepThrottle(self.device)      # at most two steps enqueued ahead of the GPU
@@ -27,6 +28,7 @@ class SecondStepTrainer:
         self.dis = (dis if dis is not None else NLayerDiscriminator()).to(self.device).train()
         self.w = loss_weight if loss_weight is not None else GanLossWeights()
         self.n_inner_loops = int(n_inner_loops)
+        self.frequency_loss = frequency_loss          # functions.FocalFrequencyLoss or None (use_frequency_loss)
         self.dec_optim = Adam([p for p in self.decoder.parameters() if p.requires_grad], lr=lr, betas=betas,
                               weight_decay=weight_decay)
         self.dis_optim = Adam([p for p in self.dis.parameters() if p.requires_grad], lr=lr, betas=betas,
@@ -52,6 +54,7 @@ class SecondStepTrainer:
             embed, _, ids = self.encoder(image)
         recon = self.decoder(embed.detach())
         l_recon = ops.mse_loss(recon, image)
+        l_freq = self.frequency_loss(recon, image) if self.frequency_loss is not None else None
         # The reference lets autograd fill the discriminator's parameter gradients in this pass and discards them
         # (dis_optim.zero_grad() below); they are not computed here.  Same decoder gradients, same update.
         dis_params = [p for p in self.dis.parameters() if p.requires_grad]
@@ -59,7 +62,11 @@ class SecondStepTrainer:
             p.requires_grad_(False)
         try:
             l_gen = generator_loss(self.dis(recon))
-            l_gen_total = ops.weighted_sum([l_recon, l_gen], [w.recon, w.gen])
+            terms, weights = [l_recon, l_gen], [w.recon, w.gen]
+            if l_freq is not None:
+                terms.append(l_freq)
+                weights.append(w.freq)
+            l_gen_total = ops.weighted_sum(terms, weights)
             self.dec_optim.zero_grad()
             if self.dec_reducer is not None:
                 self.dec_reducer.prepare()
@@ -85,4 +92,7 @@ class SecondStepTrainer:
                 self.dis_reducer.finish()
             self.dis_optim.step()
         self.throttle.end()
-        return dict(gen_total=l_gen_total, recon=l_recon, gen=l_gen, dis_total=l_dis_total, ids=ids, recon_image=recon)
+        out = dict(gen_total=l_gen_total, recon=l_recon, gen=l_gen, dis_total=l_dis_total, ids=ids, recon_image=recon)
+        if l_freq is not None:
+            out["freq"] = l_freq
+        return out
