@@ -372,6 +372,14 @@ struct FStats {
 // plane walking its splits one dependent load after the other made these launches ~13 us each; they sit on the
 // dependency chain between the reduction and the apply pass of every normalisation.
 static_assert(PLANE_MAX_SPLITS <= 64, "one lane per split");
+// var = E[x^2] - mean^2 from sums of squares that FStats / FStats4 rounded to fp32 (relative error <= 2^-24 each): a variance
+// within that bound of E[x^2] cannot be told from 0.  An exactly constant plane (x = 1.15: its fp32 square is 4.5e-8 above the
+// exact one, 0.45 % of eps) would otherwise keep the rounding residue as its variance and its rstd would be that far off
+// 1 / sqrt(eps).  Planes with |mean| / std < 4096 are untouched.
+__device__ __forceinline__ double var_from_squares(double ex2, double mean) {
+    const double var = ex2 - mean * mean;
+    return var <= 0x1p-24 * ex2 ? 0.0 : var;
+}
 __global__ void __launch_bounds__(256) k_inorm_finalize(const double* __restrict__ part, float* __restrict__ mr, int NC, int C,
                                                         int splits, double inv_hw, float eps) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), s = threadIdx.x & 63;
@@ -387,8 +395,7 @@ __global__ void __launch_bounds__(256) k_inorm_finalize(const double* __restrict
     b = wave_sum_d(b);
     if (s != 0) return;
     double mean = a * inv_hw;
-    double var = b * inv_hw - mean * mean;
-    if (var < 0.0) var = 0.0;
+    double var = var_from_squares(b * inv_hw, mean);
     mr[2 * i] = (float)mean;
     mr[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
 }
@@ -1348,8 +1355,7 @@ __global__ void k_bn_finalize(const double* __restrict__ sums, double count, flo
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     double mean = sums[2 * c] / count;
-    double var = sums[2 * c + 1] / count - mean * mean;
-    if (var < 0.0) var = 0.0;
+    double var = var_from_squares(sums[2 * c + 1] / count, mean);
     mr[2 * c] = (float)mean;
     mr[2 * c + 1] = (float)(1.0 / sqrt(var + (double)eps));
     if (rm) {
