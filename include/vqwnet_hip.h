@@ -439,6 +439,21 @@ int vqw_freq_loss_bwd(const float* pred, const float* target, const float* tw_h,
                       float alpha, int log_matrix, float loss_weight, int windowed, float win_alpha, float win_beta,
                       float win_lo, float win_hi, void* stream);
 
+/* ---- test-mode evaluation metrics (the reference's _test_step, single_window_trainer.py:781-827: torchmetrics 0.6.2
+ *      MeanSquaredError / StructuralSimilarityIndexMeasure / PeakSignalNoiseRatio with data_range=None, and
+ *      scipy.stats.entropy(bincount(ids, minlength=K+1)[1:], base=2)).  Added functions only; the ABI stays 9.
+ * pred, target: N*C planes of H x W, dense (C = 1: NCHW and NHWC coincide).  ksize: the SSIM window (odd, <= 15; 0 skips
+ * the SSIM pass); data_range > 0 replaces both the SSIM range max(range p, range t) and the zero-seeded PSNR range
+ * max(max t, 0) - min(min t, 0).  ids: n_ids codes (either may be NULL: pred/target = NULL computes the entropy alone,
+ * ids = NULL the image metrics alone).  out[16] (double): mse, ssim, psnr, SSIM range, PSNR range, SSE, min t, max t,
+ * entropy (bits, over bins 1..K), the number of ids outside [0, K], the number of ids; NaN for what was not computed.
+ * counts (optional): [K + 1] int64 counts of ids 0..K.  At most four launches, no host synchronisation. */
+size_t vqw_recon_metrics_ws_bytes(int N, int C, int H, int W, int K);
+int vqw_recon_metrics(const float* pred, const float* target, const int64_t* ids, double* out, int64_t* counts, void* ws,
+                      size_t ws_bytes, int N, int C, int H, int W, long n_ids, int K, int ksize, float sigma, float k1,
+                      float k2, float data_range, void* stream);
+int vqw_code_entropy(const int64_t* ids, double* out, int64_t* counts, void* ws, size_t ws_bytes, long n, int K, void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

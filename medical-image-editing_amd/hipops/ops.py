@@ -1933,6 +1933,162 @@ def frequency_loss(pred, target, alpha=1.0, patch_factor=1, log_matrix=False, ba
                            float(loss_weight), None if window is None else tuple(window))
 
 
+# out[] slots of vqw_recon_metrics (csrc/metrics.hip)
+METRIC_SLOTS = ("mse", "ssim", "psnr", "ssim_range", "psnr_range", "sse", "target_min", "target_max", "entropy", "bad_ids",
+                "n_ids")
+_MT_OUT = 16
+
+
+def _dense_storage(t):
+    """1-D view of a tensor's elements in storage order, without a copy when the tensor is a permutation of a dense
+    layout (the encoder's ids are a transposed view, unet_encoder.py:86); otherwise a contiguous copy.  Counting over
+    it counts the same multiset of values."""
+    if t.is_contiguous():
+        return t.reshape(-1)
+    dims = sorted((s, n) for s, n in zip(t.stride(), t.shape) if n != 1)
+    expect = 1
+    for s, n in dims:
+        if s != expect:
+            return t.contiguous().reshape(-1)
+        expect *= n
+    return t.as_strided((t.numel(),), (1,), t.storage_offset())
+
+
+def _image_pair(pred, target, name):
+    pred, target = pred.detach(), target.detach()
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise RuntimeError("%s: pred and target must be fp32 (got %s, %s)" % (name, pred.dtype, target.dtype))
+    if pred.shape != target.shape:
+        raise RuntimeError("%s: shape mismatch %s vs %s" % (name, tuple(pred.shape), tuple(target.shape)))
+    return pred, target
+
+
+def _ids_arg(ids, dict_size, name):
+    if dict_size is None:
+        raise RuntimeError("%s: ids need dict_size" % name)
+    _dev(ids)
+    ids = _dense_storage(ids.detach())
+    if ids.dtype != torch.int64:
+        raise RuntimeError("%s: ids must be int64 (got %s)" % (name, ids.dtype))
+    if ids.numel() == 0:
+        raise RuntimeError("%s: no ids" % name)
+    return ids
+
+
+def _metrics_launch(pred, target, ids, dict_size, data_range, kernel_size, sigma, k1, k2, counts=None):
+    """-> out (16,) float64 device tensor of METRIC_SLOTS; four launches at most, no synchronisation."""
+    like = pred if pred is not None else ids
+    if pred is not None:
+        N, C, H, W = pred.shape
+    else:
+        N = C = H = W = 0
+    K = int(dict_size) if ids is not None else 0
+    out = torch.empty(_MT_OUT, dtype=torch.float64, device=like.device)
+    L = _L()
+    ws = _ws(L.vqw_recon_metrics_ws_bytes(N, C, H, W, K), like)
+    dr = float(data_range) if data_range is not None else 0.0
+    L.vqw_recon_metrics(pred, target, ids, out, counts, ws, ws.numel(), N, C, H, W, ids.numel() if ids is not None else 0,
+                        K, int(kernel_size), float(sigma), float(k1), float(k2), dr, _st())
+    return out
+
+
+def _check_ids(host, name):
+    if host[METRIC_SLOTS.index("bad_ids")] > 0:
+        raise ValueError("%s: %d ids outside [0, dict_size]" % (name, int(host[METRIC_SLOTS.index("bad_ids")])))
+
+
+def image_metrics_raw(pred, target, data_range=None, kernel_size=11, sigma=1.5, k1=0.01, k2=0.03):
+    """Streaming statistics of any two equal-shape fp32 tensors (kernel_size=0: no SSIM pass, any shape) or the full
+    (N, C, H, W) set with SSIM -> the (16,) float64 device tensor of METRIC_SLOTS.  Used by the torchmetrics drop-ins."""
+    pred, target = _image_pair(pred, target, "image_metrics")
+    if kernel_size:
+        kernel_size, sigma = _recon_metrics_check(pred, kernel_size, sigma)
+    if pred.numel() == 0:
+        raise RuntimeError("image_metrics: empty input")
+    _dev(pred, target)
+    pred, target = pred.contiguous(), target.contiguous()     # no copy for C = 1 (NCHW and NHWC coincide)
+    if not kernel_size:
+        pred, target = pred.reshape(1, 1, 1, -1), target.reshape(1, 1, 1, -1)
+    return _metrics_launch(pred, target, None, None, data_range, kernel_size, sigma, k1, k2)
+
+
+def _recon_metrics_check(pred, kernel_size, sigma):
+    if isinstance(kernel_size, (tuple, list)) or isinstance(sigma, (tuple, list)):
+        ks, sg = tuple(kernel_size) if isinstance(kernel_size, (tuple, list)) else (kernel_size,) * 2, \
+            tuple(sigma) if isinstance(sigma, (tuple, list)) else (sigma,) * 2
+        if len(ks) != 2 or len(sg) != 2 or ks[0] != ks[1] or sg[0] != sg[1]:
+            raise NotImplementedError("recon_metrics: only square SSIM windows are built (kernel_size=%r, sigma=%r)"
+                                      % (kernel_size, sigma))
+        kernel_size, sigma = ks[0], sg[0]
+    kernel_size = int(kernel_size)
+    if kernel_size < 1 or kernel_size % 2 == 0:
+        raise ValueError("recon_metrics: kernel_size must be odd and positive (got %d)" % kernel_size)
+    if not float(sigma) > 0:
+        raise ValueError("recon_metrics: sigma must be > 0 (got %r)" % (sigma,))
+    if pred.dim() != 4:
+        raise RuntimeError("recon_metrics: expected (N, C, H, W) inputs, got shape %s" % (tuple(pred.shape),))
+    H, W = pred.shape[-2:]
+    if H < kernel_size or W < kernel_size:
+        raise ValueError("recon_metrics: H=%d and W=%d must be at least kernel_size=%d" % (H, W, kernel_size))
+    return kernel_size, float(sigma)
+
+
+def _recon_metrics_out(pred, target, ids, dict_size, data_range, kernel_size, sigma, k1, k2):
+    pred, target = _image_pair(pred, target, "recon_metrics")
+    kernel_size, sigma = _recon_metrics_check(pred, kernel_size, sigma)
+    if data_range is not None and not float(data_range) > 0:
+        raise ValueError("recon_metrics: data_range must be > 0 (got %r)" % (data_range,))
+    _dev(pred, target)
+    pred, target = pred.contiguous(), target.contiguous()     # no copy for C = 1 (NCHW and NHWC coincide)
+    if ids is not None:
+        ids = _ids_arg(ids, dict_size, "recon_metrics")
+    return _metrics_launch(pred, target, ids, dict_size, data_range, kernel_size, sigma, k1, k2)
+
+
+def recon_metrics(pred, target, ids=None, dict_size=None, data_range=None, kernel_size=11, sigma=1.5, k1=0.01, k2=0.03):
+    """The per-batch metrics of the reference's test step (single_window_trainer.py:781-827) as torchmetrics 0.6.2 and
+    scipy compute them -> {'mse', 'ssim', 'psnr'[, 'entropy']} as 0-d float64 device tensors (not differentiable).
+
+    mse: mean (pred - target)^2.  ssim: mean over the valid kernel_size^2 Gaussian windows of every (n, c) plane with
+    C1 = (k1 R)^2, C2 = (k2 R)^2, R = max(range pred, range target) over the batch.  psnr: 10 log10(R'^2 / mse) with the
+    package's zero-seeded R' = max(max target, 0) - min(min target, 0).  A given data_range replaces R and R'.
+    entropy (with ids and dict_size K): base-2 entropy of the counts of ids 1..K (id 0 = no code); ids outside [0, K]
+    raise, which reads the results to the host once.  Without ids nothing synchronises."""
+    out = _recon_metrics_out(pred, target, ids, dict_size, data_range, kernel_size, sigma, k1, k2)
+    if ids is not None:
+        _check_ids(out.cpu().tolist(), "recon_metrics")
+    res = dict(mse=out[0], ssim=out[1], psnr=out[2])
+    if ids is not None:
+        res["entropy"] = out[METRIC_SLOTS.index("entropy")]
+    return res
+
+
+def recon_metrics_values(pred, target, ids=None, dict_size=None, data_range=None, kernel_size=11, sigma=1.5, k1=0.01,
+                         k2=0.03):
+    """recon_metrics as Python floats, with one device-to-host read of the results."""
+    out = _recon_metrics_out(pred, target, ids, dict_size, data_range, kernel_size, sigma, k1, k2)
+    host = out.cpu().tolist()
+    if ids is not None:
+        _check_ids(host, "recon_metrics")
+    keys = ("mse", "ssim", "psnr") + (("entropy",) if ids is not None else ())
+    return {k: host[METRIC_SLOTS.index(k)] for k in keys}
+
+
+def code_entropy(ids, dict_size):
+    """-> (entropy, counts): scipy.stats.entropy(bincount(ids, minlength=K+1)[1:], base=2) as a 0-d float64 device
+    tensor (nan when no id is in 1..K) and the (K + 1,) int64 device counts of ids 0..K.  ids may be any dense view (no
+    copy); ids outside [0, K] raise (one host read)."""
+    ids = _ids_arg(ids, dict_size, "code_entropy")
+    K = int(dict_size)
+    out = torch.empty(_MT_OUT, dtype=torch.float64, device=ids.device)
+    counts = torch.empty(K + 1, dtype=torch.int64, device=ids.device)
+    L = _L()
+    ws = _ws(L.vqw_recon_metrics_ws_bytes(0, 0, 0, 0, K), ids)
+    L.vqw_code_entropy(ids, out, counts, ws, ws.numel(), ids.numel(), K, _st())
+    _check_ids(out.cpu().tolist(), "code_entropy")
+    return out[METRIC_SLOTS.index("entropy")], counts
+
+
 class _WeightedSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weights, *terms):

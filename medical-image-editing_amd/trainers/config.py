@@ -22,6 +22,7 @@ from hipops import Adam
 from networks import UNetEncoder, UNetDecoder, RandomTransform
 
 from .first_step import FirstStepTrainer, FlipViews, RandomTransformViews, LossWeights
+from .evaluation import Evaluator
 
 
 def _get(cfg, name, default=None):
@@ -99,6 +100,12 @@ def set_transform(config, seed=0):
     if aug is None:
         return FlipViews()
     return RandomTransformViews(RandomTransform(aug, seed=seed), RandomTransform(aug, seed=seed + 1))
+
+
+def build_evaluator(config, encoder, decoder):
+    """-> trainers.evaluation.Evaluator for `-m test` (the metrics of base.py:75-77 and the code entropy of
+    single_window_trainer.py:794-797 over config.model.vqmodel.dict_size codes)."""
+    return Evaluator(encoder, decoder, config.model.vqmodel.dict_size)
 
 
 def build_first_step_trainer(config, device="cuda", data_parallel=None, views=None, multi_window=None):

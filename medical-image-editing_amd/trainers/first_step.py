@@ -251,6 +251,12 @@ class FirstStepTrainer:
             out.update(freq_1=frq_1[0][0], freq_2=frq_2[0][0])
         return out
 
+    def test_step(self, batch):
+        """The reference's test step (single_window_trainer.py:781-827): {'NMSE', 'SSIM', 'PSNR', 'Entropy'} of one batch
+        through trainers.evaluation.Evaluator (eval mode, no gradients; training state untouched)."""
+        from .evaluation import Evaluator
+        return Evaluator(self.encoder, self.decoder, self.dict_size).test_step(batch)
+
     def training_step(self, batch, noise=None):
         image = batch['image'] if isinstance(batch, dict) else batch
         self.throttle.begin()

@@ -42,6 +42,12 @@ class SecondStepTrainer:
             self.dec_reducer = GradientAllReducer(list(reversed([p for p in self.decoder.parameters() if p.requires_grad])))
             self.dis_reducer = GradientAllReducer(list(reversed([p for p in self.dis.parameters() if p.requires_grad])))
 
+    def test_step(self, batch):
+        """{'NMSE', 'SSIM', 'PSNR', 'Entropy'} of one batch through trainers.evaluation.Evaluator (eval mode, no gradients;
+        training state untouched)."""
+        from .evaluation import Evaluator
+        return Evaluator(self.encoder, self.decoder, self.encoder.dict_size).test_step(batch)
+
     def training_step(self, batch):
         image = batch['image'] if isinstance(batch, dict) else batch
         w = self.w
