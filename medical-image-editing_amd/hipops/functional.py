@@ -55,9 +55,7 @@ def conv2d_backward(gy: Tensor, x: Tensor, weight: Tensor, skip: Optional[Tensor
     up_ws = None
     Cout, Cin = w.shape[0], w.shape[1]
     if up2x and x1 is None and w.shape[2] == 3 and dilation == 1 and ops._L().vqw_conv3x3_up2_supported(Cin, Cout, x0.shape[0], x0.shape[2], x0.shape[3]):
-        L = ops._L()
-        up_ws = ops._ws(L.vqw_conv3x3_up2_ws_bytes(Cin, Cout), x0)
-        ops._lib.check(L.vqw_conv3x3_up2_prepare(ops._p(w), ops._p(up_ws), up_ws.numel(), Cin, Cout, ops._st()), "vqw_conv3x3_up2_prepare")
+        up_ws = ops._up2_weights(ops._L(), w, Cin, Cout)
     g0, g1, gw, gb, _ = ops.conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up2x, has_bias, up_ws, True, x1 is not None, True, has_bias)
     return g0, (g1 if g1 is not None else torch.empty(0, device=gy.device)), gw, (gb if gb is not None else torch.empty(0, device=gy.device))
 

@@ -8,6 +8,7 @@ library or a CPU tensor raises (no eager fallback).
 4-D activations are logically NCHW and physically NHWC (torch.channels_last).
 Conv weights are logically OIHW and physically OHWI (channels_last too).
 """
+import contextlib
 import ctypes
 import os
 
@@ -337,19 +338,47 @@ def _run_wgrad(L, x0, x1, gy, gw, gb, up0, ks, dilation, N, H, W, Cout, acc, col
         _fold_keep.append(ws)
 
 
-def _deferred_wgrad(weight, bias, x0, x1, gy, up0, ks, dilation, N, H, W, Cout, collapsed=False):
-    """Enqueue dW (and db) on the side stream, writing into weight.grad / bias.grad."""
-    L = _L()
+def _out_of_band(needed, params, dense):
+    """Whether the weight and bias gradients of one layer go out-of-band to the side lanes (_side_lane) instead of through
+    autograd: `params` = (weight, bias) or, for a concatenated layer, (wa, ba, wb, bb), all of which must qualify; `needed`:
+    autograd wants them; `dense`: the weights are in the layout the kernels write.  A yes registers a pending use on
+    params[0], which the side lane counts down."""
+    defer = bool(WGRAD_ASYNC and needed and all(p.is_leaf for p in params if p is not None) and not wgrad_through_autograd(*params)
+                 and dense and all(b is None or b.is_contiguous() for b in params[1::2]))
+    if defer:
+        params[0]._vqw_pending = getattr(params[0], "_vqw_pending", 0) + 1
+    return defer
+
+
+@contextlib.contextmanager
+def _side_lane(owner, tensors, announce):
+    """Body runs on the weight-gradient lane of `owner`, ordered after what the current stream has enqueued; `tensors` are
+    read there.  On the owner's last pending use the gradients of `announce` are final: every gradient-ready listener hears
+    of them in that order.  The end-of-pass lane join is queued."""
     main = torch.cuda.current_stream()
-    side = wgrad_stream(gy.device, _wgrad_lane(weight))
+    side = wgrad_stream(tensors[-1].device, _wgrad_lane(owner))
     ev = main.record_event()
-    C0 = x0.shape[1]
-    C1 = 0 if x1 is None else x1.shape[1]
-    for t in (x0, x1, gy):
+    for t in tensors:
         if t is not None:
             t.record_stream(side)
     with torch.cuda.stream(side):
         side.wait_event(ev)
+        yield
+        owner._vqw_pending = getattr(owner, "_vqw_pending", 1) - 1
+        if owner._vqw_pending <= 0:
+            owner._vqw_pending = 0
+            for fn in grad_ready_listeners:
+                for p in announce:
+                    fn(p)
+    _queue_lane_join()
+
+
+def _deferred_wgrad(weight, bias, x0, x1, gy, up0, ks, dilation, N, H, W, Cout, collapsed=False):
+    """Enqueue dW (and db) on the side stream, writing into weight.grad / bias.grad."""
+    L = _L()
+    C0 = x0.shape[1]
+    C1 = 0 if x1 is None else x1.shape[1]
+    with _side_lane(weight, (x0, x1, gy), (weight,) if bias is None else (weight, bias)):
         acc = weight.grad is not None
         if not acc:
             # (the parameter's own strides: channels_last for a 3 x 3 weight, the default ones for a 1 x 1 weight - the same memory order)
@@ -360,14 +389,6 @@ def _deferred_wgrad(weight, bias, x0, x1, gy, up0, ks, dilation, N, H, W, Cout, 
         if gw.stride() != weight.stride():
             raise RuntimeError("conv2d: existing weight.grad layout does not match the parameter layout")
         _run_wgrad(L, x0, x1, gy, gw, gb, up0, ks, dilation, N, H, W, Cout, acc, collapsed, defer_fold=True)
-        weight._vqw_pending = getattr(weight, "_vqw_pending", 1) - 1
-        if weight._vqw_pending <= 0:
-            weight._vqw_pending = 0
-            for fn in grad_ready_listeners:
-                fn(weight)
-                if bias is not None:
-                    fn(bias)
-    _queue_lane_join()
 
 
 # ----------------------------------------------------------------------------------------------
@@ -388,11 +409,24 @@ def _wino_weights_dgrad(L, w_ohwi, Cin, Cout):
     return buf
 
 
-def _conv_fwd_raw(x0, up0, x1, w, bias, N, H, W, Cout, ks, dil, relu=False):
-    y = empty_nhwc(N, Cout, H, W, x0)
-    _lib.check(_L().vqw_conv2d_fwd(_p(x0), x0.shape[1], int(up0), _p(x1), 0 if x1 is None else x1.shape[1],
-                                   _p(w), _p(bias), _p(y), N, H, W, Cout, ks, dil, int(relu), _st()), "vqw_conv2d_fwd")
-    return y
+def _up2_weights(L, w_ohwi, Cin, Cout):
+    """The collapsed weights of a 3x3 layer over a nearest x2 up-sampled input (vqw_conv3x3_up2_prepare) in a fresh buffer."""
+    buf = _ws(L.vqw_conv3x3_up2_ws_bytes(Cin, Cout), w_ohwi)
+    _lib.check(L.vqw_conv3x3_up2_prepare(_p(w_ohwi), _p(buf), buf.numel(), Cin, Cout, _st()), "vqw_conv3x3_up2_prepare")
+    return buf
+
+
+def _concat_layers(wa, ba, wb, bb, prepare=None):
+    """(w, b) of the layers a and b concatenated along the output channels: w channels_last, or prepare(w) when the caller
+    wants a derived layout of it; b None unless both layers have a bias."""
+    Ca, Cin, ks, _ = wa.shape
+    w = torch.empty((Ca + wb.shape[0], Cin, ks, ks), dtype=torch.float32, device=wa.device, memory_format=CL)
+    w[:Ca].copy_(wa.detach())
+    w[Ca:].copy_(wb.detach())
+    if prepare is not None:
+        w = prepare(w)
+    b = torch.cat([ba.detach().reshape(-1), bb.detach().reshape(-1)]) if ba is not None and bb is not None else None
+    return w, b
 
 
 # Winograd F(2x2, 3x3) form of plain 3x3 layers.  The INPUT and WEIGHT GRADIENTS take it whenever the library serves the
@@ -453,83 +487,73 @@ class _Conv2d(torch.autograd.Function):
         N = x0.shape[0]
         H, W = (x0.shape[2] * 2, x0.shape[3] * 2) if up0 else (x0.shape[2], x0.shape[3])
         c1 = 0 if x1 is None else x1.shape[1]
-        part = None
         if x0.shape[1] + c1 != Cin:
             raise RuntimeError("conv2d: input channels %d+%d do not match weight %s" % (x0.shape[1], c1, tuple(weight.shape)))
         if x1 is not None and (x1.shape[0] != N or x1.shape[2] != H or x1.shape[3] != W):
             raise RuntimeError("conv2d: concat source shape %s does not match %s" % (tuple(x1.shape), (N, c1, H, W)))
         if bias is not None:
             bias = _flat(bias)
-        # 3x3 over a nearest x2 up-sampled single source: collapsed onto the low-res grid (4/9 of the FLOPs)
+        L = _L()
+        h, wl = H // 2, W // 2
         up_ws = None
-        if up0 and x1 is None and ks == 3 and dilation == 1 and \
-                _L().vqw_conv3x3_up2_supported(Cin, Cout, N, H // 2, W // 2):
-            L = _L()
-
-            def _collapse():
-                buf = _ws(L.vqw_conv3x3_up2_ws_bytes(Cin, Cout), x0)
-                _lib.check(L.vqw_conv3x3_up2_prepare(_p(w), _p(buf), buf.numel(), Cin, Cout, _st()), "vqw_conv3x3_up2_prepare")
-                return buf
-            up_ws = _cached(weight, "up2", _collapse)
-            y = empty_nhwc(N, Cout, H, W, x0)
-            nparts = L.vqw_conv3x3_up2_fwd_stats_parts(Cin, Cout, N, H // 2, W // 2) if (want_stats and not relu) else 0
-            if nparts > 0:
-                part = torch.empty(N * nparts * Cout * 2, dtype=torch.float32, device=x0.device)
-                _lib.check(L.vqw_conv3x3_up2_fwd_stats(_p(x0), _p(up_ws), _p(bias), _p(y), _p(part), N, H // 2, W // 2, Cin, Cout, _st()),
-                           "vqw_conv3x3_up2_fwd_stats")
-            else:
-                _lib.check(L.vqw_conv3x3_up2_fwd(_p(x0), _p(up_ws), _p(bias), _p(y), N, H // 2, W // 2, Cin, Cout, int(relu), _st()),
-                           "vqw_conv3x3_up2_fwd")
+        stats = want_stats and not relu
+        if up0 and x1 is None and ks == 3 and dilation == 1 and L.vqw_conv3x3_up2_supported(Cin, Cout, N, h, wl):
+            # 3x3 over a nearest x2 up-sampled single source: collapsed onto the low-res grid (4/9 of the FLOPs)
+            form = "up2"
+            up_ws = _cached(weight, "up2", lambda: _up2_weights(L, w, Cin, Cout))
         elif wino_fwd and not up0 and x1 is None and ks == 3 and dilation == 1 and \
-                _L().vqw_conv3x3_wino_supported(Cin, Cout, N, H, W) and \
-                (not (want_stats and not relu) or _L().vqw_conv3x3_wino_fwd_stats_parts(Cin, Cout, N, H, W) > 0
-                 or _L().vqw_conv2d_fwd_stats_parts(Cin, 0, 0, N, H, W, Cout, ks, dilation) == 0):
+                L.vqw_conv3x3_wino_supported(Cin, Cout, N, H, W) and \
+                (not stats or L.vqw_conv3x3_wino_fwd_stats_parts(Cin, Cout, N, H, W) > 0
+                 or L.vqw_conv2d_fwd_stats_parts(Cin, 0, 0, N, H, W, Cout, ks, dilation) == 0):
             # (wanted statistics that only the direct form can leave for this height keep the direct form)
             # plain 3x3 layer: Winograd F(2x2, 3x3), 4/9 of the matrix work; U = G w G^T is kept while w is unchanged
-            L = _L()
-            u = _cached(weight, "wino", lambda: _wino_weights(L, w, Cin, Cout))
-            y = empty_nhwc(N, Cout, H, W, x0)
-            nparts = L.vqw_conv3x3_wino_fwd_stats_parts(Cin, Cout, N, H, W) if (want_stats and not relu) else 0
-            if nparts > 0:
-                part = torch.empty(N * nparts * Cout * 2, dtype=torch.float32, device=x0.device)
-                _lib.check(L.vqw_conv3x3_wino_fwd_stats(_p(x0), _p(u), _p(bias), _p(y), _p(part), N, H, W, Cin, Cout, _st()),
-                           "vqw_conv3x3_wino_fwd_stats")
-            else:
-                _lib.check(L.vqw_conv3x3_wino_fwd(_p(x0), _p(u), _p(bias), _p(y), N, H, W, Cin, Cout, int(relu), _st()),
-                           "vqw_conv3x3_wino_fwd")
+            form = "wino"
         elif wino_fwd and not up0 and x1 is None and ks == 3 and dilation == 2 and \
-                _L().vqw_conv3x3_wino_dil2_supported(Cin, Cout, N, H, W) and \
-                (not (want_stats and not relu) or _L().vqw_conv3x3_wino_dil2_stats_parts(Cin, Cout, N, H, W) > 0):
+                L.vqw_conv3x3_wino_dil2_supported(Cin, Cout, N, H, W) and \
+                (not stats or L.vqw_conv3x3_wino_dil2_stats_parts(Cin, Cout, N, H, W) > 0):
             # dilation 2: the plain Winograd kernel on the four phase images of the tensors (same U as the plain layer)
-            L = _L()
-            u = _cached(weight, "wino", lambda: _wino_weights(L, w, Cin, Cout))
-            y = empty_nhwc(N, Cout, H, W, x0)
-            nparts = L.vqw_conv3x3_wino_dil2_stats_parts(Cin, Cout, N, H, W) if (want_stats and not relu) else 0
-            if nparts > 0:
-                part = torch.empty(N * nparts * Cout * 2, dtype=torch.float32, device=x0.device)
-            _lib.check(L.vqw_conv3x3_wino_dil2_fwd(_p(x0), _p(u), _p(bias), _p(y), _p(part) if nparts > 0 else None, 0, N, H, W, Cin, Cout,
-                                                   int(relu), _st()), "vqw_conv3x3_wino_dil2_fwd")
+            form = "dil2"
         else:
-            nparts = 0
-            if want_stats and not relu:
-                nparts = _L().vqw_conv2d_fwd_stats_parts(x0.shape[1], c1, int(up0), N, H, W, Cout, ks, dilation)
-            if nparts > 0:      # the epilogue leaves the following InstanceNorm's statistics (per-tile partial sums)
-                y = empty_nhwc(N, Cout, H, W, x0)
-                part = torch.empty(N * nparts * Cout * 2, dtype=torch.float32, device=x0.device)
-                _lib.check(_L().vqw_conv2d_fwd_stats(_p(x0), x0.shape[1], int(up0), _p(x1), c1, _p(w), _p(bias), _p(y), _p(part),
-                                                     N, H, W, Cout, ks, dilation, _st()), "vqw_conv2d_fwd_stats")
-            else:
-                y = _conv_fwd_raw(x0, up0, x1, w, bias, N, H, W, Cout, ks, dilation, relu)
+            form = "direct"
+        if form in ("wino", "dil2"):
+            u = _cached(weight, "wino", lambda: _wino_weights(L, w, Cin, Cout))
+        # the epilogue leaves the following InstanceNorm's statistics (per-tile partial sums) where the form can
+        nparts = 0
+        if stats:
+            nparts = (L.vqw_conv3x3_up2_fwd_stats_parts(Cin, Cout, N, h, wl) if form == "up2" else
+                      L.vqw_conv3x3_wino_fwd_stats_parts(Cin, Cout, N, H, W) if form == "wino" else
+                      L.vqw_conv3x3_wino_dil2_stats_parts(Cin, Cout, N, H, W) if form == "dil2" else
+                      L.vqw_conv2d_fwd_stats_parts(x0.shape[1], c1, int(up0), N, H, W, Cout, ks, dilation))
+        y = empty_nhwc(N, Cout, H, W, x0)
+        part = torch.empty(N * nparts * Cout * 2, dtype=torch.float32, device=x0.device) if nparts > 0 else None
+        if form == "up2" and part is not None:
+            _lib.check(L.vqw_conv3x3_up2_fwd_stats(_p(x0), _p(up_ws), _p(bias), _p(y), _p(part), N, h, wl, Cin, Cout, _st()),
+                       "vqw_conv3x3_up2_fwd_stats")
+        elif form == "up2":
+            _lib.check(L.vqw_conv3x3_up2_fwd(_p(x0), _p(up_ws), _p(bias), _p(y), N, h, wl, Cin, Cout, int(relu), _st()),
+                       "vqw_conv3x3_up2_fwd")
+        elif form == "wino" and part is not None:
+            _lib.check(L.vqw_conv3x3_wino_fwd_stats(_p(x0), _p(u), _p(bias), _p(y), _p(part), N, H, W, Cin, Cout, _st()),
+                       "vqw_conv3x3_wino_fwd_stats")
+        elif form == "wino":
+            _lib.check(L.vqw_conv3x3_wino_fwd(_p(x0), _p(u), _p(bias), _p(y), N, H, W, Cin, Cout, int(relu), _st()),
+                       "vqw_conv3x3_wino_fwd")
+        elif form == "dil2":
+            _lib.check(L.vqw_conv3x3_wino_dil2_fwd(_p(x0), _p(u), _p(bias), _p(y), _p(part), 0, N, H, W, Cin, Cout, int(relu), _st()),
+                       "vqw_conv3x3_wino_dil2_fwd")
+        elif part is not None:
+            _lib.check(L.vqw_conv2d_fwd_stats(_p(x0), x0.shape[1], int(up0), _p(x1), c1, _p(w), _p(bias), _p(y), _p(part),
+                                              N, H, W, Cout, ks, dilation, _st()), "vqw_conv2d_fwd_stats")
+        else:
+            _lib.check(L.vqw_conv2d_fwd(_p(x0), x0.shape[1], int(up0), _p(x1), c1, _p(w), _p(bias), _p(y),
+                                        N, H, W, Cout, ks, dilation, int(relu), _st()), "vqw_conv2d_fwd")
         ctx.up_ws = up_ws
         ctx.group = grad_group
         ctx.save_for_backward(x0, x1, w, y if relu else None)
         ctx.cfg = (dilation, up0, ks, N, H, W, Cout, bias is not None)
         # leaf parameters get their gradient written out-of-band on the side stream (see _deferred_wgrad)
-        ctx.defer = (WGRAD_ASYNC and ctx.needs_input_grad[2] and weight.is_leaf and w is weight and not wgrad_through_autograd(weight, bias)
-                     and (bias is None or (bias.is_leaf and bias.is_contiguous())))
-        if ctx.defer:
-            ctx.params = (weight, bias)
-            weight._vqw_pending = getattr(weight, "_vqw_pending", 0) + 1
+        ctx.params = (weight, bias)
+        ctx.defer = _out_of_band(ctx.needs_input_grad[2], ctx.params, w is weight)
         if want_stats:
             if part is not None:
                 ctx.mark_non_differentiable(part)
@@ -590,95 +614,103 @@ class _GradNotes:
 
 
 # ----------------------------------------------------------------------------------------------
-# two 32-cout 3x3 layers of one up-sampled input as ONE 64-cout launch (StyledResUpBlock's shortcut `conv` and `conv1`)
+# two 3x3 layers of one input as ONE launch on concatenated weights:
+#  - up-sampled: 32 couts each, one 64-cout launch (StyledResUpBlock's shortcut `conv` and `conv1`)
+#  - plain: StyledResUpBlock's mlp_shared convolutions of its two StyledDenorms read the same style tensor (blocks.py:72-75 / 100-134)
 # ----------------------------------------------------------------------------------------------
 UP_PAIR = os.environ.get("VQW_UP_PAIR", "1") != "0"      # 0: the two layers run one by one (A/B timing)
 up_pair_calls = 0
+CONV_PAIR = os.environ.get("VQW_CONV_PAIR", "1") != "0"      # 0: the two layers run one by one (A/B timing)
+conv_pair_calls = 0
 
 
-class _ConvUpPair(torch.autograd.Function):
-    """(y_a, part_a, y_b, part_b) = the forward of conv2d(x, w_a, b_a, up2x=True, want_stats=True) and of the same with (w_b, b_b),
-    computed by one launch of the nine-product kernel on the concatenated weights (a 32-cout layer alone falls back to the
-    collapsed 4-tap form at a third of that kernel's rate).  The backward is the two layers' own: each input gradient through
-    its layer's own collapsed / nine-product weights (the second added to the first in its kernel's epilogue when `group` is
-    given), each weight gradient on the side lanes."""
+class _ConvPair(torch.autograd.Function):
+    """Two 3x3 layers a and b of one input x, computed by one launch on their concatenated weights.
+    up=True: (y_a, part_a, y_b, part_b) = the forward of conv2d(x, w_a, b_a, up2x=True, want_stats=True) and of the same with
+    (w_b, b_b), one launch of the nine-product kernel (a 32-cout layer alone falls back to the collapsed 4-tap form at a third
+    of that kernel's rate).
+    up=False: (y_a, y_b) = conv2d(x, w_a, b_a, relu=relu), conv2d(x, w_b, b_b, relu=relu) in Winograd form, one launch of the
+    64-cout kernel with a two-tensor epilogue (vqw_conv3x3_wino_fwd_split): the input is read and transformed once, and two
+    32-cout layers leave the 128-tile x 32-cout workgroup shape for the 64 x 64 one.
+    The backward is the two layers' own: each input gradient through its layer's own weights (collapsed ones when up), the
+    second added to the first in its kernel's epilogue when `group` is given, each weight gradient on the side lanes."""
 
     @staticmethod
-    def forward(ctx, x, wa, ba, wb, bb, group):
-        global up_pair_calls
+    def forward(ctx, x, wa, ba, wb, bb, relu, group, up):
+        global up_pair_calls, conv_pair_calls
         _dev(x, wa, ba, wb, bb)
         x = nhwc(x)
         Ca, Cin, ks, _ = wa.shape
         N, _, h, w = x.shape
         L = _L()
-        nparts = L.vqw_conv3x3_up2_fwd_pair_supported(Cin, Ca, N, h, w)
-        if nparts <= 0 or tuple(wb.shape) != tuple(wa.shape) or ks != 3:
-            raise RuntimeError("conv2d_up_pair: shape not served (query vqw_conv3x3_up2_fwd_pair_supported)")
-
-        def _prep():
-            wc = torch.empty((2 * Ca, Cin, 3, 3), dtype=torch.float32, device=wa.device, memory_format=CL)
-            wc[:Ca].copy_(wa.detach())
-            wc[Ca:].copy_(wb.detach())
-            buf = _ws(L.vqw_conv3x3_up2_ws_bytes(Cin, 2 * Ca), wa)
-            _lib.check(L.vqw_conv3x3_up2_prepare(_p(wc), _p(buf), buf.numel(), Cin, 2 * Ca, _st()), "vqw_conv3x3_up2_prepare")
-            bc = None
-            if ba is not None and bb is not None:
-                bc = torch.cat([ba.detach().reshape(-1), bb.detach().reshape(-1)])
-            return buf, bc
         deps = (wb,) + tuple(t for t in (ba, bb) if t is not None)
-        up_ws, bias_cat = _cached(wa, "up2pair", _prep, deps=deps)
-        ya = empty_nhwc(N, Ca, 2 * h, 2 * w, x)
-        yb = empty_nhwc(N, Ca, 2 * h, 2 * w, x)
-        pa = torch.empty(N * nparts * Ca * 2, dtype=torch.float32, device=x.device)
-        pb = torch.empty(N * nparts * Ca * 2, dtype=torch.float32, device=x.device)
-        _lib.check(L.vqw_conv3x3_up2_fwd_pair(_p(x), _p(up_ws), _p(bias_cat), _p(ya), _p(yb), _p(pa), _p(pb), N, h, w, Cin, Ca, _st()),
-                   "vqw_conv3x3_up2_fwd_pair")
-        up_pair_calls += 1
-        ctx.save_for_backward(x, nhwc(wa), nhwc(wb))
+        if up:
+            nparts = L.vqw_conv3x3_up2_fwd_pair_supported(Cin, Ca, N, h, w)
+            if nparts <= 0 or tuple(wb.shape) != tuple(wa.shape) or ks != 3:
+                raise RuntimeError("conv2d_up_pair: shape not served (query vqw_conv3x3_up2_fwd_pair_supported)")
+            up_ws, bias_cat = _cached(wa, "up2pair", lambda: _concat_layers(wa, ba, wb, bb, lambda wc: _up2_weights(L, wc, Cin, 2 * Ca)),
+                                      deps=deps)
+            H, W = 2 * h, 2 * w
+            ya = empty_nhwc(N, Ca, H, W, x)
+            yb = empty_nhwc(N, Ca, H, W, x)
+            pa = torch.empty(N * nparts * Ca * 2, dtype=torch.float32, device=x.device)
+            pb = torch.empty(N * nparts * Ca * 2, dtype=torch.float32, device=x.device)
+            _lib.check(L.vqw_conv3x3_up2_fwd_pair(_p(x), _p(up_ws), _p(bias_cat), _p(ya), _p(yb), _p(pa), _p(pb), N, h, w, Cin, Ca, _st()),
+                       "vqw_conv3x3_up2_fwd_pair")
+            up_pair_calls += 1
+            ctx.mark_non_differentiable(pa, pb)
+            outs = (ya, pa, yb, pb)
+        else:
+            H, W = h, w
+            if tuple(wb.shape) != tuple(wa.shape) or ks != 3 or (ba is None) != (bb is None) \
+                    or not L.vqw_conv3x3_wino_split_supported(Cin, 2 * Ca, Ca, 0, N, H, W):
+                raise RuntimeError("conv2d_pair: shape not served (query vqw_conv3x3_wino_split_supported)")
+            u, bias_cat = _cached(wa, "pair_wino", lambda: _concat_layers(wa, ba, wb, bb, lambda wc: _wino_weights(L, wc, Cin, 2 * Ca)),
+                                  deps=deps)
+            ya = empty_nhwc(N, Ca, H, W, x)
+            yb = empty_nhwc(N, Ca, H, W, x)
+            _lib.check(L.vqw_conv3x3_wino_fwd_split(_p(x), _p(u), _p(bias_cat), _p(ya), _p(yb), N, H, W, Cin, 2 * Ca, Ca, 0, int(relu),
+                                                    _st()), "vqw_conv3x3_wino_fwd_split")
+            conv_pair_calls += 1
+            outs = (ya, yb)
+        wa_n, wb_n = nhwc(wa), nhwc(wb)
+        ctx.save_for_backward(x, wa_n, wb_n, ya if relu else None, yb if relu else None)
+        ctx.up = up
         ctx.group = group
-        ctx.cfg = (N, 2 * h, 2 * w, Ca, Cin)
+        ctx.cfg = (N, H, W, Ca, Cin)
         ctx.params = ((wa, ba), (wb, bb))
-        ctx.defer = []
-        for i, (wgt, bias) in enumerate(ctx.params):
-            d = (WGRAD_ASYNC and ctx.needs_input_grad[1 + 2 * i] and wgt.is_leaf and nhwc(wgt) is wgt
-                 and not wgrad_through_autograd(wgt, bias) and (bias is None or (bias.is_leaf and bias.is_contiguous())))
-            ctx.defer.append(d)
-            if d:
-                wgt._vqw_pending = getattr(wgt, "_vqw_pending", 0) + 1
-        ctx.mark_non_differentiable(pa, pb)
+        ctx.defer = [_out_of_band(ctx.needs_input_grad[1 + 2 * i], params, w_n is params[0])
+                     for i, (params, w_n) in enumerate(zip(ctx.params, (wa_n, wb_n)))]
         ctx.set_materialize_grads(False)
-        return ya, pa, yb, pb
+        return outs
 
     @staticmethod
-    def backward(ctx, ga, _gpa, gb, _gpb):
-        x, wa_n, wb_n = ctx.saved_tensors
+    def backward(ctx, *grads):
+        x, wa_n, wb_n, ya, yb = ctx.saved_tensors
         N, H, W, Cout, Cin = ctx.cfg
+        up = ctx.up
         L = _L()
-        out = [None] * 6
+        out = [None] * 8
         gx_total = None
         # (the second layer's input gradient runs first, like the second of two separate nodes would)
         for i in (1, 0):
-            gy = (ga, gb)[i]
+            gy = grads[2 * i] if up else grads[i]
             if gy is None:
                 if ctx.group is not None:
-                    raise RuntimeError("conv2d_up_pair: both outputs must take part in the backward pass of a gradient group")
+                    raise RuntimeError("%s: both outputs must take part in the backward pass of a gradient group"
+                                       % ("conv2d_up_pair" if up else "conv2d_pair"))
                 continue
             wgt, bias = ctx.params[i]
             w_n = (wa_n, wb_n)[i]
-
-            def _collapse(w_n=w_n):
-                buf = _ws(L.vqw_conv3x3_up2_ws_bytes(Cin, Cout), w_n)
-                _lib.check(L.vqw_conv3x3_up2_prepare(_p(w_n), _p(buf), buf.numel(), Cin, Cout, _st()), "vqw_conv3x3_up2_prepare")
-                return buf
-            up_ws = _cached(wgt, "up2", _collapse)
+            up_ws = _cached(wgt, "up2", lambda: _up2_weights(L, w_n, Cin, Cout)) if up else None
             need0 = ctx.needs_input_grad[0]
             needw, needb = ctx.needs_input_grad[1 + 2 * i], (bias is not None and ctx.needs_input_grad[2 + 2 * i])
             defer = ctx.defer[i] and (needw or needb)
-            g0, _, gw, gbias, gy_n = conv2d_backward_impl(gy, x, None, w_n, None, 1, True, bias is not None, up_ws, need0, False,
+            g0, _, gw, gbias, gy_n = conv2d_backward_impl(gy, x, None, w_n, (ya, yb)[i], 1, up, bias is not None, up_ws, need0, False,
                                                           needw and not defer, needb and not defer, group=ctx.group)
             if defer:
-                _deferred_wgrad(wgt, bias if (bias is not None and bias.requires_grad) else None, x, None, gy_n, True, 3, 1,
-                                N, H, W, Cout, collapsed=True)
+                _deferred_wgrad(wgt, bias if (bias is not None and bias.requires_grad) else None, x, None, gy_n, up, 3, 1,
+                                N, H, W, Cout, collapsed=up)
             out[1 + 2 * i], out[2 + 2 * i] = gw, gbias
             if g0 is not None:
                 gx_total = g0 if gx_total is None else gx_total.add_(g0)
@@ -696,91 +728,8 @@ def conv2d_up_pair_supported(x, weight_a, weight_b):
 
 def conv2d_up_pair(x, weight_a, bias_a, weight_b, bias_b, grad_group=None):
     """-> ((y_a, part_a), (y_b, part_b)): conv2d(x, w, b, up2x=True, want_stats=True) of two layers of one input, one launch."""
-    ya, pa, yb, pb = _ConvUpPair.apply(x, weight_a, bias_a, weight_b, bias_b, grad_group if GRAD_GROUPS else None)
+    ya, pa, yb, pb = _ConvPair.apply(x, weight_a, bias_a, weight_b, bias_b, False, grad_group if GRAD_GROUPS else None, True)
     return (ya, pa), (yb, pb)
-
-
-# ----------------------------------------------------------------------------------------------
-# two plain 3x3 layers of one input as ONE launch on concatenated weights (StyledResUpBlock: the mlp_shared convolutions of its two
-# StyledDenorms read the same style tensor, blocks.py:72-75 / 100-134)
-# ----------------------------------------------------------------------------------------------
-CONV_PAIR = os.environ.get("VQW_CONV_PAIR", "1") != "0"      # 0: the two layers run one by one (A/B timing)
-conv_pair_calls = 0
-
-
-class _ConvPair(torch.autograd.Function):
-    """(y_a, y_b) = conv2d(x, w_a, b_a, relu=relu), conv2d(x, w_b, b_b, relu=relu) in Winograd form, one launch of the 64-cout
-    kernel with a two-tensor epilogue (vqw_conv3x3_wino_fwd_split): the input is read and transformed once, and two 32-cout
-    layers leave the 128-tile x 32-cout workgroup shape for the 64 x 64 one.  The backward is the two layers' own."""
-
-    @staticmethod
-    def forward(ctx, x, wa, ba, wb, bb, relu, group):
-        global conv_pair_calls
-        _dev(x, wa, ba, wb, bb)
-        x = nhwc(x)
-        Ca, Cin, ks, _ = wa.shape
-        N, _, H, W = x.shape
-        L = _L()
-        if tuple(wb.shape) != tuple(wa.shape) or ks != 3 or (ba is None) != (bb is None) \
-                or not L.vqw_conv3x3_wino_split_supported(Cin, 2 * Ca, Ca, 0, N, H, W):
-            raise RuntimeError("conv2d_pair: shape not served (query vqw_conv3x3_wino_split_supported)")
-
-        def _prep():
-            wc = torch.empty((2 * Ca, Cin, 3, 3), dtype=torch.float32, device=wa.device, memory_format=CL)
-            wc[:Ca].copy_(wa.detach())
-            wc[Ca:].copy_(wb.detach())
-            u = _wino_weights(L, wc, Cin, 2 * Ca)
-            bc = torch.cat([ba.detach().reshape(-1), bb.detach().reshape(-1)]) if ba is not None else None
-            return u, bc
-        deps = (wb,) + tuple(t for t in (ba, bb) if t is not None)
-        u, bias_cat = _cached(wa, "pair_wino", _prep, deps=deps)
-        ya = empty_nhwc(N, Ca, H, W, x)
-        yb = empty_nhwc(N, Ca, H, W, x)
-        _lib.check(L.vqw_conv3x3_wino_fwd_split(_p(x), _p(u), _p(bias_cat), _p(ya), _p(yb), N, H, W, Cin, 2 * Ca, Ca, 0, int(relu), _st()),
-                   "vqw_conv3x3_wino_fwd_split")
-        conv_pair_calls += 1
-        ctx.save_for_backward(x, nhwc(wa), nhwc(wb), ya if relu else None, yb if relu else None)
-        ctx.group = group
-        ctx.cfg = (N, H, W, Ca, Cin)
-        ctx.params = ((wa, ba), (wb, bb))
-        ctx.defer = []
-        for i, (wgt, bias) in enumerate(ctx.params):
-            d = (WGRAD_ASYNC and ctx.needs_input_grad[1 + 2 * i] and wgt.is_leaf and nhwc(wgt) is wgt
-                 and not wgrad_through_autograd(wgt, bias) and (bias is None or (bias.is_leaf and bias.is_contiguous())))
-            ctx.defer.append(d)
-            if d:
-                wgt._vqw_pending = getattr(wgt, "_vqw_pending", 0) + 1
-        ctx.set_materialize_grads(False)
-        return ya, yb
-
-    @staticmethod
-    def backward(ctx, ga, gb):
-        x, wa_n, wb_n, ya, yb = ctx.saved_tensors
-        N, H, W, Cout, Cin = ctx.cfg
-        out = [None] * 7
-        gx_total = None
-        # (the second layer's input gradient runs first, like the second of two separate nodes would)
-        for i in (1, 0):
-            gy = (ga, gb)[i]
-            if gy is None:
-                if ctx.group is not None:
-                    raise RuntimeError("conv2d_pair: both outputs must take part in the backward pass of a gradient group")
-                continue
-            wgt, bias = ctx.params[i]
-            w_n = (wa_n, wb_n)[i]
-            need0 = ctx.needs_input_grad[0]
-            needw, needb = ctx.needs_input_grad[1 + 2 * i], (bias is not None and ctx.needs_input_grad[2 + 2 * i])
-            defer = ctx.defer[i] and (needw or needb)
-            g0, _, gw, gbias, gy_n = conv2d_backward_impl(gy, x, None, w_n, (ya, yb)[i], 1, False, bias is not None, None, need0, False,
-                                                          needw and not defer, needb and not defer, group=ctx.group)
-            if defer:
-                _deferred_wgrad(wgt, bias if (bias is not None and bias.requires_grad) else None, x, None, gy_n, False, 3, 1,
-                                N, H, W, Cout)
-            out[1 + 2 * i], out[2 + 2 * i] = gw, gbias
-            if g0 is not None:
-                gx_total = g0 if gx_total is None else gx_total.add_(g0)
-        out[0] = gx_total
-        return tuple(out)
 
 
 def conv2d_pair_supported(x, weight_a, weight_b):
@@ -797,7 +746,7 @@ def conv2d_pair_supported(x, weight_a, weight_b):
 
 def conv2d_pair(x, weight_a, bias_a, weight_b, bias_b, relu=False, grad_group=None):
     """-> (y_a, y_b): conv2d(x, w, b, relu=relu) of two 3x3 layers of one input, one launch."""
-    return _ConvPair.apply(x, weight_a, bias_a, weight_b, bias_b, bool(relu), grad_group if GRAD_GROUPS else None)
+    return _ConvPair.apply(x, weight_a, bias_a, weight_b, bias_b, bool(relu), grad_group if GRAD_GROUPS else None, False)
 
 
 # Gradients that arrive already multiplied by a fused ReLU's mask: payload = data_ptr of the ReLU output the gradient was masked
@@ -868,7 +817,7 @@ def conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up0, has_bias, up_ws, 
     """Input / weight / bias gradients of conv2d on the current stream -> (g0, g1, gw, gb, masked gy).  x0 / x1 / w are the
     NHWC tensors the forward saw, y_relu its output when the ReLU was fused (the incoming gradient is masked first),
     up_ws the collapsed-weight buffer when the forward took the low-resolution form."""
-    global group_acc_calls
+    global group_acc_calls, split_dgrad_calls, in_bwd_fused_calls
     L = _L()
     Cout, Cin, ks, _ = w.shape
     N = x0.shape[0]
@@ -885,6 +834,19 @@ def conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up0, has_bias, up_ws, 
     C0 = x0.shape[1]
     C1 = 0 if x1 is None else x1.shape[1]
     g0 = g1 = gw = gb = None
+
+    # derived weights of the input-gradient convolution, kept on w while it is unchanged: U of its Winograd form (the Winograd
+    # routes), the packed weights (the others)
+    def wino_u():
+        return _cached(w, "wino_dgrad", lambda: _wino_weights_dgrad(L, w, Cout, Cin))
+
+    def packed():
+        def _pack():
+            buf = torch.empty(Cin * ks * ks * Cout, dtype=torch.float32, device=gy.device)
+            _lib.check(L.vqw_pack_dgrad_weights(_p(w), _p(buf), Cout, Cin, ks, _st()), "vqw_pack_dgrad_weights")
+            return buf
+        return _cached(w, "dgrad", _pack)
+
     if need0 and up_ws is not None:
         if group is not None and group.buf is not None and L.vqw_conv3x3_up2_dgrad_acc_supported(Cin, Cout, N, H // 2, W // 2):
             # the other up-sampled convolution of this input has run: add to its gradient in this kernel's epilogue
@@ -899,114 +861,92 @@ def conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up0, has_bias, up_ws, 
             if group is not None:
                 g0 = group.member_done(g0)
     elif need0 or (need1 and x1 is not None):
-        def _pack():
-            buf = torch.empty(Cin * ks * ks * Cout, dtype=torch.float32, device=gy.device)
-            _lib.check(L.vqw_pack_dgrad_weights(_p(w), _p(buf), Cout, Cin, ks, _st()), "vqw_pack_dgrad_weights")
-            return buf
-        wt_of = lambda: _cached(w, "dgrad", _pack)          # noqa: E731  (only the non-Winograd routes read the packed weights)
-        if SPLIT_DGRAD and x1 is not None and need0 and need1 and group is None and ks == 3 and dilation == 1 \
-                and L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W) \
-                and L.vqw_conv3x3_wino_split_supported(Cout, Cin, C0, int(up0), N, H, W):
-            # two sources [up2x(x0) | x1]: both gradients leave the input-gradient kernel's epilogue (x0's summed over each 2 x 2
-            # tile when x0 was up-sampled: a Winograd tile IS one low-resolution pixel) instead of two gather passes over the
-            # concatenated gradient
-            global split_dgrad_calls
-            ut = _cached(w, "wino_dgrad", lambda: _wino_weights_dgrad(L, w, Cout, Cin))
-            g0 = torch.empty_like(x0, memory_format=CL)
-            g1 = torch.empty_like(x1, memory_format=CL)
-            _lib.check(L.vqw_conv3x3_wino_fwd_split(_p(gy), _p(ut), None, _p(g0), _p(g1), N, H, W, Cout, Cin, C0, int(up0), 0, _st()),
-                       "vqw_conv3x3_wino_fwd_split(dgrad)")
-            split_dgrad_calls += 1
-            if needw or (needb and has_bias):
-                gw = torch.empty((Cout, Cin, ks, ks), dtype=torch.float32, device=gy.device, memory_format=CL)
-                gb = torch.empty(Cout, dtype=torch.float32, device=gy.device) if has_bias else None
-                _run_wgrad(L, x0, x1, gy, gw, gb, up0, ks, dilation, N, H, W, Cout, False, up_ws is not None)
-            return g0, g1, gw, gb, gy
-        if SPLIT_DGRAD and x1 is not None and need0 and need1 and group is None and ks == 3 and dilation == 1 and Cin % 64 != 0 \
-                and C0 % 16 == 0 and C1 % 16 == 0:
-            # ... and for a channel total that is not a multiple of the kernel's cout tile (48 at the encoder's full-resolution
-            # level): the layer is widened to 64 input channels with zero weights, the padding couts of the launch are not stored
-            Cp = (Cin + 63) // 64 * 64
-            if L.vqw_conv3x3_wino_supported(Cout, Cp, N, H, W) and L.vqw_conv3x3_wino_split_padded_supported(Cout, Cp, C0, C1, int(up0), N, H, W):
+        # two sources [up2x(x0) | x1]: both gradients leave the input-gradient kernel's epilogue (x0's summed over each 2 x 2 tile
+        # when x0 was up-sampled: a Winograd tile IS one low-resolution pixel) instead of two gather passes over the concatenated
+        # gradient.  Cp: the input channels of that launch - the layer's own, or for a channel total that is not a multiple of the
+        # kernel's cout tile (48 at the encoder's full-resolution level) the layer widened to 64 with zero weights, the padding
+        # couts of the launch not stored
+        Cp = None
+        if SPLIT_DGRAD and x1 is not None and need0 and need1 and group is None and ks == 3 and dilation == 1:
+            if L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W) and L.vqw_conv3x3_wino_split_supported(Cout, Cin, C0, int(up0), N, H, W):
+                Cp = Cin
+            elif Cin % 64 != 0 and C0 % 16 == 0 and C1 % 16 == 0:
+                Cp = (Cin + 63) // 64 * 64
+                if not (L.vqw_conv3x3_wino_supported(Cout, Cp, N, H, W)
+                        and L.vqw_conv3x3_wino_split_padded_supported(Cout, Cp, C0, C1, int(up0), N, H, W)):
+                    Cp = None
+        if Cp is not None:
+            if Cp == Cin:
+                ut = wino_u()
+            else:
                 def _padded():
                     wp = torch.zeros((Cout, Cp, 3, 3), dtype=torch.float32, device=w.device).contiguous(memory_format=CL)
                     wp[:, :Cin].copy_(w.detach())
                     return _wino_weights_dgrad(L, wp, Cout, Cp)
                 ut = _cached(w, "wino_dgrad_pad", _padded)
-                g0 = torch.empty_like(x0, memory_format=CL)
-                g1 = torch.empty_like(x1, memory_format=CL)
+            g0 = torch.empty_like(x0, memory_format=CL)
+            g1 = torch.empty_like(x1, memory_format=CL)
+            if Cp == Cin:
+                _lib.check(L.vqw_conv3x3_wino_fwd_split(_p(gy), _p(ut), None, _p(g0), _p(g1), N, H, W, Cout, Cin, C0, int(up0), 0, _st()),
+                           "vqw_conv3x3_wino_fwd_split(dgrad)")
+            else:
                 _lib.check(L.vqw_conv3x3_wino_fwd_split_padded(_p(gy), _p(ut), None, _p(g0), _p(g1), N, H, W, Cout, Cp, C0, C1, int(up0), 0,
                                                                _st()), "vqw_conv3x3_wino_fwd_split_padded(dgrad)")
-                split_dgrad_calls += 1
-                if needw or (needb and has_bias):
-                    gw = torch.empty((Cout, Cin, ks, ks), dtype=torch.float32, device=gy.device, memory_format=CL)
-                    gb = torch.empty(Cout, dtype=torch.float32, device=gy.device) if has_bias else None
-                    _run_wgrad(L, x0, x1, gy, gw, gb, up0, ks, dilation, N, H, W, Cout, False, up_ws is not None)
-                return g0, g1, gw, gb, gy
-        if group is not None and need0 and group.buf is not None:
-            # a later member of a gradient group (single full-resolution source): add into the shared buffer
-            if ks == 3 and dilation == 1 and L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W) \
+            split_dgrad_calls += 1
+        else:
+            # a later member of a gradient group (single full-resolution source) adds into the shared buffer where a kernel can
+            acc = group is not None and need0 and group.buf is not None
+            g_full = None
+            if acc and ks == 3 and dilation == 1 and L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W) \
                     and L.vqw_conv3x3_wino_masked_supported(Cout, Cin, N, H, W):
                 # Winograd form, the shared buffer read and added in the kernel's epilogue
-                ut = _cached(w, "wino_dgrad", lambda: _wino_weights_dgrad(L, w, Cout, Cin))
-                _lib.check(L.vqw_conv3x3_wino_fwd_acc(_p(gy), _p(ut), _p(group.buf), N, H, W, Cout, Cin, _st()),
+                _lib.check(L.vqw_conv3x3_wino_fwd_acc(_p(gy), _p(wino_u()), _p(group.buf), N, H, W, Cout, Cin, _st()),
                            "vqw_conv3x3_wino_fwd_acc(dgrad)")
                 group_acc_calls += 1
-                g_full = None
-            elif ks == 3 and dilation == 2 and L.vqw_conv3x3_wino_dil2_supported(Cout, Cin, N, H, W):
+            elif acc and ks == 3 and dilation == 2 and L.vqw_conv3x3_wino_dil2_supported(Cout, Cin, N, H, W):
                 # dilation 2: the Winograd kernel on the phase images, adding to the shared buffer in its epilogue
-                ut = _cached(w, "wino_dgrad", lambda: _wino_weights_dgrad(L, w, Cout, Cin))
-                _lib.check(L.vqw_conv3x3_wino_dil2_fwd(_p(gy), _p(ut), None, _p(group.buf), None, 1, N, H, W, Cout, Cin, 0, _st()),
+                _lib.check(L.vqw_conv3x3_wino_dil2_fwd(_p(gy), _p(wino_u()), None, _p(group.buf), None, 1, N, H, W, Cout, Cin, 0, _st()),
                            "vqw_conv3x3_wino_dil2_fwd(dgrad, acc)")
-                g_full = None
-            elif L.vqw_conv2d_fwd_acc_supported(Cout, N, H, W, Cin, ks, dilation):
+            elif acc and L.vqw_conv2d_fwd_acc_supported(Cout, N, H, W, Cin, ks, dilation):
                 # row-chain kernel (dilated 3x3) or the implicit-GEMM kernel (1x1): y += conv in the epilogue
-                _lib.check(L.vqw_conv2d_fwd_acc(_p(gy), Cout, _p(wt_of()), _p(group.buf), N, H, W, Cin, ks, dilation, _st()),
+                _lib.check(L.vqw_conv2d_fwd_acc(_p(gy), Cout, _p(packed()), _p(group.buf), N, H, W, Cin, ks, dilation, _st()),
                            "vqw_conv2d_fwd_acc")
                 if ks == 1:
                     group_acc_calls += 1
-                g_full = None
             else:
                 g_full = empty_nhwc(N, Cin, H, W, gy)
-        else:
-            g_full = empty_nhwc(N, Cin, H, W, gy)
-        if g_full is None:
-            pass
-        elif in_src is not None and need0 and group is None and FUSE_IN_BWD \
-                and L.vqw_conv3x3_wino_fwd_inbwd_parts(Cout, Cin, N, H, W) > 0:
-            # x0 is the output of an InstanceNorm (+ReLU) and feeds this layer only: the norm's backward sums ride in this launch
-            global in_bwd_fused_calls
-            nparts = L.vqw_conv3x3_wino_fwd_inbwd_parts(Cout, Cin, N, H, W)
-            ut = _cached(w, "wino_dgrad", lambda: _wino_weights_dgrad(L, w, Cout, Cin))
-            bpart = torch.empty(N * nparts * Cin * 2, dtype=torch.float32, device=gy.device)
-            xraw, mr, nrelu = in_src
-            _lib.check(L.vqw_conv3x3_wino_fwd_inbwd(_p(gy), _p(ut), _p(xraw), _p(mr), int(nrelu), _p(g_full), _p(bpart),
-                                                    N, H, W, Cout, Cin, _st()), "vqw_conv3x3_wino_fwd_inbwd(dgrad)")
-            _IN_BWD_PARTS.put(g_full, (bpart, nparts, xraw.data_ptr()))
-        elif ks == 3 and dilation == 1 and L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W):
-            ut = _cached(w, "wino_dgrad", lambda: _wino_weights_dgrad(L, w, Cout, Cin))
-            _lib.check(L.vqw_conv3x3_wino_fwd(_p(gy), _p(ut), None, _p(g_full), N, H, W, Cout, Cin, 0, _st()),
-                       "vqw_conv3x3_wino_fwd(dgrad)")
-        elif ks == 3 and dilation == 2 and x1 is None and not up0 and L.vqw_conv3x3_wino_dil2_supported(Cout, Cin, N, H, W):
-            ut = _cached(w, "wino_dgrad", lambda: _wino_weights_dgrad(L, w, Cout, Cin))
-            _lib.check(L.vqw_conv3x3_wino_dil2_fwd(_p(gy), _p(ut), None, _p(g_full), None, 0, N, H, W, Cout, Cin, 0, _st()),
-                       "vqw_conv3x3_wino_dil2_fwd(dgrad)")
-        else:
-            _lib.check(L.vqw_conv2d_fwd(_p(gy), Cout, 0, None, 0, _p(wt_of()), None, _p(g_full), N, H, W, Cin, ks, dilation, 0, _st()),
-                       "vqw_conv2d_fwd(dgrad)")
-        if group is not None and need0:
-            g0 = group.member_done(g_full)
-        elif not up0 and x1 is None:
-            g0 = g_full
-        else:
-            if need0:
-                g0 = torch.empty_like(x0, memory_format=CL)
-                _lib.check(L.vqw_input_grad_gather(_p(g_full), Cin, 0, C0, int(up0), _p(g0), 0, N, H, W, _st()),
-                           "vqw_input_grad_gather")
-            if need1 and x1 is not None:
-                g1 = torch.empty_like(x1, memory_format=CL)
-                _lib.check(L.vqw_input_grad_gather(_p(g_full), Cin, C0, C1, 0, _p(g1), 0, N, H, W, _st()),
-                           "vqw_input_grad_gather")
+                if in_src is not None and need0 and group is None and FUSE_IN_BWD \
+                        and L.vqw_conv3x3_wino_fwd_inbwd_parts(Cout, Cin, N, H, W) > 0:
+                    # x0 is the output of an InstanceNorm (+ReLU) and feeds this layer only: the norm's backward sums ride in this launch
+                    nparts = L.vqw_conv3x3_wino_fwd_inbwd_parts(Cout, Cin, N, H, W)
+                    ut = wino_u()
+                    bpart = torch.empty(N * nparts * Cin * 2, dtype=torch.float32, device=gy.device)
+                    xraw, mr, nrelu = in_src
+                    _lib.check(L.vqw_conv3x3_wino_fwd_inbwd(_p(gy), _p(ut), _p(xraw), _p(mr), int(nrelu), _p(g_full), _p(bpart),
+                                                            N, H, W, Cout, Cin, _st()), "vqw_conv3x3_wino_fwd_inbwd(dgrad)")
+                    _IN_BWD_PARTS.put(g_full, (bpart, nparts, xraw.data_ptr()))
+                elif ks == 3 and dilation == 1 and L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W):
+                    _lib.check(L.vqw_conv3x3_wino_fwd(_p(gy), _p(wino_u()), None, _p(g_full), N, H, W, Cout, Cin, 0, _st()),
+                               "vqw_conv3x3_wino_fwd(dgrad)")
+                elif ks == 3 and dilation == 2 and x1 is None and not up0 and L.vqw_conv3x3_wino_dil2_supported(Cout, Cin, N, H, W):
+                    _lib.check(L.vqw_conv3x3_wino_dil2_fwd(_p(gy), _p(wino_u()), None, _p(g_full), None, 0, N, H, W, Cout, Cin, 0, _st()),
+                               "vqw_conv3x3_wino_dil2_fwd(dgrad)")
+                else:
+                    _lib.check(L.vqw_conv2d_fwd(_p(gy), Cout, 0, None, 0, _p(packed()), None, _p(g_full), N, H, W, Cin, ks, dilation, 0,
+                                                _st()), "vqw_conv2d_fwd(dgrad)")
+            if group is not None and need0:
+                g0 = group.member_done(g_full)
+            elif not up0 and x1 is None:
+                g0 = g_full
+            else:
+                if need0:
+                    g0 = torch.empty_like(x0, memory_format=CL)
+                    _lib.check(L.vqw_input_grad_gather(_p(g_full), Cin, 0, C0, int(up0), _p(g0), 0, N, H, W, _st()),
+                               "vqw_input_grad_gather")
+                if need1 and x1 is not None:
+                    g1 = torch.empty_like(x1, memory_format=CL)
+                    _lib.check(L.vqw_input_grad_gather(_p(g_full), Cin, C0, C1, 0, _p(g1), 0, N, H, W, _st()),
+                               "vqw_input_grad_gather")
     if needw or (needb and has_bias):
         gw = torch.empty((Cout, Cin, ks, ks), dtype=torch.float32, device=gy.device, memory_format=CL)
         gb = torch.empty(Cout, dtype=torch.float32, device=gy.device) if has_bias else None
@@ -1086,8 +1026,7 @@ def conv2d(x, weight, bias=None, dilation=1, up2x=False, skip=None, relu=False, 
     in_src = getattr(x, "_vqw_in_src", None) if (norm_input and FUSE_IN_BWD) else None
     if want_stats:
         return _Conv2d.apply(x, skip, weight, bias, int(dilation), bool(up2x), bool(relu), True, wino, group, in_src)
-    y = _Conv2d.apply(x, skip, weight, bias, int(dilation), bool(up2x), bool(relu), False, wino, group, in_src)
-    return (y, None) if want_stats else y
+    return _Conv2d.apply(x, skip, weight, bias, int(dilation), bool(up2x), bool(relu), False, wino, group, in_src)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1097,15 +1036,7 @@ def conv2d(x, weight, bias=None, dilation=1, up2x=False, skip=None, relu=False, 
 # halves of one buffer.
 # ----------------------------------------------------------------------------------------------
 def _cat_weights(wa, ba, wb, bb):
-    def _build():
-        Ca, Cin, ks, _ = wa.shape
-        Cb = wb.shape[0]
-        w = torch.empty((Ca + Cb, Cin, ks, ks), dtype=torch.float32, device=wa.device, memory_format=CL)
-        w[:Ca].copy_(wa.detach())
-        w[Ca:].copy_(wb.detach())
-        b = torch.cat([ba.detach().reshape(-1), bb.detach().reshape(-1)])
-        return w, b
-    return _cached(wa, "cat", _build, deps=(wb, ba, bb))
+    return _cached(wa, "cat", lambda: _concat_layers(wa, ba, wb, bb), deps=(wb, ba, bb))
 
 
 def _grad_halves_adjacent(pa, pb, ga, gb_):
@@ -1117,15 +1048,9 @@ def _grad_halves_adjacent(pa, pb, ga, gb_):
 
 def _deferred_wgrad_cat(wa, ba, wb, bb, x0, gy, ks, N, H, W):
     L = _L()
-    main = torch.cuda.current_stream()
-    side = wgrad_stream(gy.device, _wgrad_lane(wa))
-    ev = main.record_event()
     Ca, Cin = wa.shape[0], wa.shape[1]
     Ct = Ca + wb.shape[0]
-    x0.record_stream(side)
-    gy.record_stream(side)
-    with torch.cuda.stream(side):
-        side.wait_event(ev)
+    with _side_lane(wa, (x0, gy), (wa, ba, wb, bb)):
         fresh = wa.grad is None and wb.grad is None and ba.grad is None and bb.grad is None
         if fresh:
             gw = torch.empty((Ct, Cin, ks, ks), dtype=torch.float32, device=gy.device, memory_format=CL)
@@ -1144,13 +1069,6 @@ def _deferred_wgrad_cat(wa, ba, wb, bb, x0, gy, ks, N, H, W):
                     p.grad = g
                 else:
                     p.grad.add_(g)
-        wa._vqw_pending = getattr(wa, "_vqw_pending", 1) - 1
-        if wa._vqw_pending <= 0:
-            wa._vqw_pending = 0
-            for fn in grad_ready_listeners:
-                for p in (wa, ba, wb, bb):
-                    fn(p)
-    _queue_lane_join()
 
 
 class _ConvCat(torch.autograd.Function):
@@ -1171,14 +1089,12 @@ class _ConvCat(torch.autograd.Function):
             y = empty_nhwc(N, Ca + Cb, H, W, x)
             _lib.check(L.vqw_conv3x3_wino_fwd(_p(x), _p(u), _p(b), _p(y), N, H, W, Cin, Ca + Cb, 0, _st()), "vqw_conv3x3_wino_fwd")
         else:
-            y = _conv_fwd_raw(x, False, None, w, b, N, H, W, Ca + Cb, ks, 1, False)
+            y = empty_nhwc(N, Ca + Cb, H, W, x)
+            _lib.check(_L().vqw_conv2d_fwd(_p(x), Cin, 0, None, 0, _p(w), _p(b), _p(y), N, H, W, Ca + Cb, ks, 1, 0, _st()), "vqw_conv2d_fwd")
         ctx.save_for_backward(x, w)
         ctx.cfg = (ks, N, H, W, Ca, Cb)
         ctx.params = (wa, ba, wb, bb)
-        ctx.defer = (WGRAD_ASYNC and all(ctx.needs_input_grad[1:5]) and all(p.is_leaf for p in (wa, ba, wb, bb)) and not wgrad_through_autograd(wa, ba, wb, bb)
-                     and nhwc(wa) is wa and nhwc(wb) is wb and ba.is_contiguous() and bb.is_contiguous())
-        if ctx.defer:
-            wa._vqw_pending = getattr(wa, "_vqw_pending", 0) + 1
+        ctx.defer = _out_of_band(all(ctx.needs_input_grad[1:5]), ctx.params, nhwc(wa) is wa and nhwc(wb) is wb)
         return y
 
     @staticmethod

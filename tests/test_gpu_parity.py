@@ -1027,6 +1027,66 @@ def test_deferred_slab_folds_match_immediate_folds(monkeypatch):
         assert_close(got[k], ref[k], 2e-6, "gradient %s: one batched fold vs immediate folds" % k, atol=1e-7 * gmax)
 
 
+@pytest.mark.parametrize("kind", ["conv2d", "up_pair", "style_pair", "cat"])
+@pytest.mark.parametrize("route", ["default", "autograd", "preset"])
+def test_weight_gradient_routes_agree(kind, route):
+    """Every convolution operator (ops.conv2d, the up-sampled pair, the style-layer pair, conv2d_cat) hands its weight and bias
+    gradients either to the side lanes (default: written straight into .grad, slabs folded at the end of the pass) or to
+    autograd (ops.set_wgrad_route("autograd")).  Both routes give the same gradients, and with every .grad preset to a seeded
+    tensor the side lanes add to it instead of overwriting it: preset + gradient.  The reference is the autograd route on
+    fresh gradients; the bounds are those of the deferred slab folds."""
+    from networks import blocks as B
+    from hipops import ops
+    import contextlib
+    cl = lambda t: t.contiguous(memory_format=torch.channels_last)      # noqa: E731
+    counter = {"up_pair": "up_pair_calls", "style_pair": "conv_pair_calls", "cat": "masked_dgrad_calls"}.get(kind)
+
+    def run(wgrad_route, preset):
+        torch.manual_seed(31)
+        if kind == "conv2d":
+            mod = B.ResBlock(32, 64)
+            ins = [torch.randn(2, 32, 64, 64, device=DEV)]
+        elif kind == "cat":
+            mod = B.StyledDenorm(32, 32)
+            ins = [torch.randn(2, 32, 64, 64, device=DEV), torch.randn(2, 32, 64, 64, device=DEV)]
+        elif kind == "up_pair":
+            mod = B.StyledResUpBlock(64, 32, 32)
+            ins = [torch.randn(3, 64, 16, 32, device=DEV), torch.randn(3, 32, 32, 64, device=DEV)]
+        else:
+            mod = B.StyledResUpBlock(64, 32, 32)
+            ins = [torch.randn(2, 64, 20, 32, device=DEV), torch.randn(2, 32, 40, 64, device=DEV)]
+        mod.to(DEV).train()
+        ins = [cl(t).requires_grad_(True) for t in ins]
+        gen = torch.Generator(device=DEV).manual_seed(37)
+        pre = {k: torch.randn(p.shape, generator=gen, device=DEV) for k, p in mod.named_parameters()}
+        if preset:
+            for k, p in mod.named_parameters():
+                p.grad = torch.empty_like(p).copy_(pre[k])      # (the parameter's own strides)
+        n0, f0 = (getattr(ops, counter) if counter else 0), ops.fold_flushes
+        old = ops.set_wgrad_route(wgrad_route)
+        try:
+            with (ops.winograd_forward() if kind == "style_pair" else contextlib.nullcontext()):
+                out = mod(*ins)
+            outs = out if isinstance(out, tuple) else (out,)
+            sum((o * torch.randn_like(o)).sum() for o in outs).backward()
+        finally:
+            ops.set_wgrad_route(old)
+        torch.cuda.synchronize()
+        grads = {"in%d" % i: t.grad.clone() for i, t in enumerate(ins)}
+        grads.update({k: p.grad.clone() for k, p in mod.named_parameters()})
+        return grads, pre, (getattr(ops, counter) - n0 if counter else None), ops.fold_flushes - f0
+    ref, _, n_ref, f_ref = run("autograd", False)
+    got, pre, n_got, f_got = run("autograd" if route == "autograd" else "auto", route == "preset")
+    if counter:
+        assert n_ref == 1 and n_got == 1, (kind, n_ref, n_got)
+    # the side lanes' slab folds run in one launch at the end of the pass: taken on the default route only
+    assert f_ref == 0 and f_got == (0 if route == "autograd" else 1), (kind, route, f_ref, f_got)
+    gmax = max(float(v.abs().max()) for v in ref.values())
+    for k in ref:
+        want = ref[k] + pre[k] if (route == "preset" and k in pre) else ref[k]
+        assert_close(got[k], want, 2e-6, "gradient %s, %s route, %s" % (k, route, kind), atol=1e-7 * gmax)
+
+
 @pytest.mark.parametrize("second_first", [False, True])
 def test_fusion_notes_are_not_honoured_when_the_activation_has_a_second_consumer(monkeypatch, second_first):
     """The two epilogue fusions pass a note from the consumer's backward to the producer's, keyed by the gradient tensor
