@@ -454,6 +454,32 @@ int vqw_recon_metrics(const float* pred, const float* target, const int64_t* ids
                       float k2, float data_range, void* stream);
 int vqw_code_entropy(const int64_t* ids, double* out, int64_t* counts, void* ws, size_t ws_bytes, long n, int K, void* stream);
 
+/* ---- VGG perceptual loss (the reference's VGGLoss(conv_index='22') = vgg19.features[:8], functions/perceptual_loss.py,
+ *      trainers/base.py:271-275, single_window_trainer.py:124-137, 458-467, multi_window_trainer.py:54, 101-119).
+ *      Added functions only; the ABI stays 9.
+ * One batch of 2M = 2 * nwin * N images: the sr half [nwin][N] first, then the hr half [nwin][N].  The stem, conv1_2 (direct
+ * form: vqw_conv2d_fwd), the max-pool (vqw_maxpool2_fwd) and conv2_1 run on the whole batch; conv2_2 runs once on the
+ * difference of the two halves (its output is taken before its ReLU, so the bias cancels); the backward is the existing
+ * input-gradient convolutions on the sr half and the stem's input gradient below.
+ * sr, hr: [N,H,W,Cin], Cin = 1 (w = the stem weight summed over its 3 input channels, [64][3][3][1]) or 3 (w = the stem
+ * weight [64][3][3][3]).  win: NULL (no window, nwin = 1) or [nwin][4] device floats (alpha, beta, lo, hi) of
+ * x -> clamp(alpha x + beta, lo, hi) per window (alpha 1, beta 0, lo -inf, hi inf: none).  a1: [2M,H,W,64] = relu(stem).
+ * ..._supported: 0 when a shape is not served (Cin not 1 or 3, H or W below 2). */
+int vqw_percep_supported(int N, int Cin, int H, int W);
+int vqw_percep_stem_fwd(const float* sr, const float* hr, const float* w, const float* bias, const float* win, float* a1,
+                        int N, int nwin, int Cin, int H, int W, void* stream);
+/* d[i] = a2[i] - a2[n + i], i < n (the sr half minus the hr half; n % 4 == 0) */
+int vqw_percep_diff(const float* a2, float* d, long n, void* stream);
+/* loss[w] = sum over y[w * per_window .. (w + 1) * per_window) of y^2 / per_window, w < nwin: a fixed-order fold */
+size_t vqw_percep_loss_ws_bytes(int nwin);
+int vqw_percep_loss_fwd(const float* y, float* loss, void* ws, size_t ws_bytes, int nwin, long per_window, void* stream);
+/* gsr = sum_w 2 g_w / numel * win_w'(sr) * conv3x3^T(dz1[w], w): the stem's input gradient.  dz1: [nwin * N,H,W,64], the
+ * gradient in front of the stem's ReLU (sr half); g0 .. g2: the incoming gradient of each window's loss (device scalars;
+ * unused ones may be NULL); numel = N * 128 * (H/2) * (W/2).  win' = alpha where alpha sr + beta lies strictly inside
+ * (lo, hi), else 0 (the vqw_window_mse_bwd convention). */
+int vqw_percep_stem_bwd(const float* sr, const float* w, const float* win, const float* g0, const float* g1, const float* g2,
+                        const float* dz1, float* gsr, int N, int nwin, int Cin, int H, int W, long numel, void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

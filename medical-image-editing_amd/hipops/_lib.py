@@ -147,6 +147,12 @@ SIGNATURES = {
     "vqw_recon_metrics_ws_bytes": (c_sz, [c_i] * 5),
     "vqw_recon_metrics": (c_i, [c_p] * 6 + [c_sz] + [c_i] * 4 + [c_l] + [c_i] * 2 + [c_f] * 4 + [c_p]),
     "vqw_code_entropy": (c_i, [c_p] * 4 + [c_sz, c_l, c_i, c_p]),
+    "vqw_percep_supported": (c_i, [c_i] * 4),
+    "vqw_percep_stem_fwd": (c_i, [c_p] * 6 + [c_i] * 5 + [c_p]),
+    "vqw_percep_diff": (c_i, [c_p, c_p, c_l, c_p]),
+    "vqw_percep_loss_ws_bytes": (c_sz, [c_i]),
+    "vqw_percep_loss_fwd": (c_i, [c_p, c_p, c_p, c_sz, c_i, c_l, c_p]),
+    "vqw_percep_stem_bwd": (c_i, [c_p] * 8 + [c_i] * 5 + [c_l, c_p]),
     "vqw_pixel_shuffle2": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "vqw_dropblock_mask": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "vqw_dropblock_apply": (c_i, [c_p, c_p, c_p, c_p, c_l, c_i, c_p]),

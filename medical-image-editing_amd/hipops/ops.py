@@ -1850,6 +1850,159 @@ def frequency_loss(pred, target, alpha=1.0, patch_factor=1, log_matrix=False, ba
 
 
 # out[] slots of vqw_recon_metrics (csrc/metrics.hip)
+# ----------------------------------------------------------------------------------------------
+# VGG perceptual loss (functions/perceptual_loss.py: VGGLoss(conv_index='22') = vgg19.features[:8])
+# ----------------------------------------------------------------------------------------------
+_IDENTITY_WINDOW = (1.0, 0.0, float("-inf"), float("inf"))
+_window_tables = {}
+
+
+def _window_table(windows, like):
+    """[nwin][4] device table of (alpha, beta, lo, hi) per window (None: the identity), built once per (device, windows)."""
+    key = (like.device, windows)
+    t = _window_tables.get(key)
+    if t is None:
+        t = torch.tensor([v for w in windows for v in (w if w is not None else _IDENTITY_WINDOW)], dtype=torch.float32)
+        t = t.to(like.device)
+        if not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream().synchronize()    # later calls may read it from another stream
+        _window_tables[key] = t
+    return t
+
+
+def _pc_ohwi(w):
+    """The layer's weight as OHWI (channels_last) fp32, kept while the weight is unchanged."""
+    return _cached(w, "pc_ohwi", lambda: nhwc(w.detach().float()).clone())
+
+
+def _pc_stem(w1, C):
+    """The stem weight the kernels read: w1 summed over its 3 input channels for a 1-channel input (expand() feeds the
+    same value to all three), w1 itself for a 3-channel one."""
+    if C == 3:
+        return _pc_ohwi(w1)
+    return _cached(w1, "pc_stem1", lambda: nhwc(w1.detach().float().sum(dim=1, keepdim=True)).clone())
+
+
+def _pc_conv(L, x, w, b, Cin, Cout, N, H, W, relu):
+    """3x3 'same' convolution of the VGG slice: Winograd form where served (no max-pool follows these layers), else direct."""
+    y = empty_nhwc(N, Cout, H, W, x)
+    if L.vqw_conv3x3_wino_supported(Cin, Cout, N, H, W):
+        u = _cached(w, "pc_wino", lambda: _wino_weights(L, _pc_ohwi(w), Cin, Cout))
+        _lib.check(L.vqw_conv3x3_wino_fwd(_p(x), _p(u), _p(b), _p(y), N, H, W, Cin, Cout, int(relu), _st()), "vqw_conv3x3_wino_fwd")
+    else:
+        _lib.check(L.vqw_conv2d_fwd(_p(x), Cin, 0, None, 0, _p(_pc_ohwi(w)), _p(b), _p(y), N, H, W, Cout, 3, 1, int(relu), _st()),
+                   "vqw_conv2d_fwd")
+    return y
+
+
+def _pc_dgrad(L, gy, w, mask, Cin, Cout, N, H, W):
+    """Input gradient of a 3x3 layer (Cin -> Cout) from gy, zeroed where mask <= 0 (the ReLU in front of the layer; mask =
+    that ReLU's output) when a mask is given."""
+    gx = empty_nhwc(N, Cin, H, W, gy)
+    masked_wino = mask is not None and L.vqw_conv3x3_wino_masked_supported(Cout, Cin, N, H, W)
+    if masked_wino or (mask is None and L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W)):
+        u = _cached(w, "pc_wino_dgrad", lambda: _wino_weights_dgrad(L, _pc_ohwi(w), Cout, Cin))
+        if masked_wino:
+            _lib.check(L.vqw_conv3x3_wino_fwd_masked(_p(gy), _p(u), _p(mask), _p(gx), N, H, W, Cout, Cin, _st()),
+                       "vqw_conv3x3_wino_fwd_masked(dgrad)")
+        else:
+            _lib.check(L.vqw_conv3x3_wino_fwd(_p(gy), _p(u), None, _p(gx), N, H, W, Cout, Cin, 0, _st()), "vqw_conv3x3_wino_fwd(dgrad)")
+        return gx
+
+    def _pack():
+        buf = torch.empty(Cin * 9 * Cout, dtype=torch.float32, device=gy.device)
+        _lib.check(L.vqw_pack_dgrad_weights(_p(_pc_ohwi(w)), _p(buf), Cout, Cin, 3, _st()), "vqw_pack_dgrad_weights")
+        return buf
+    wt = _cached(w, "pc_dgrad", _pack)
+    _lib.check(L.vqw_conv2d_fwd(_p(gy), Cout, 0, None, 0, _p(wt), None, _p(gx), N, H, W, Cin, 3, 1, 0, _st()), "vqw_conv2d_fwd(dgrad)")
+    if mask is not None:
+        _lib.check(L.vqw_relu_bwd(_p(mask), _p(gx), _p(gx), gx.numel(), _st()), "vqw_relu_bwd")
+    return gx
+
+
+class _PerceptualLoss(torch.autograd.Function):
+    """Outputs: one 0-dim loss per window.  The batch of every launch is 2M = 2 * nwin * N images, the sr half first."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, windows, w1, b1, w2, b2, w3, b3, w4, b4):
+        _dev(sr, hr)
+        sr, hr = nhwc(sr), nhwc(hr)
+        if sr.shape != hr.shape:
+            raise RuntimeError("perceptual_loss: shape mismatch %s vs %s" % (tuple(sr.shape), tuple(hr.shape)))
+        N, C, H, W = sr.shape
+        L = _L()
+        if C not in (1, 3) or not L.vqw_percep_supported(N, C, H, W):
+            raise RuntimeError("perceptual_loss: input (N, C, H, W) = %s is not served: C must be 1 or 3 (the reference "
+                               "expands to 3 channels) and H, W at least 2" % (tuple(sr.shape),))
+        nwin = len(windows)
+        M, h, w = nwin * N, H // 2, W // 2
+        win = _window_table(windows, sr) if any(x is not None for x in windows) or nwin > 1 else None
+        ws1 = _pc_stem(w1, C)
+        b1, b2, b3 = _flat(b1.detach()), _flat(b2.detach()), _flat(b3.detach())
+        a1 = empty_nhwc(2 * M, 64, H, W, sr)                       # conv1_1 + ReLU
+        _lib.check(L.vqw_percep_stem_fwd(_p(sr), _p(hr), _p(ws1), _p(b1), _p(win), _p(a1), N, nwin, C, H, W, _st()),
+                   "vqw_percep_stem_fwd")
+        r12 = empty_nhwc(2 * M, 64, H, W, sr)                      # conv1_2 + ReLU: direct form (ties of the pool behind it)
+        _lib.check(L.vqw_conv2d_fwd(_p(a1), 64, 0, None, 0, _p(_pc_ohwi(w2)), _p(b2), _p(r12), 2 * M, H, W, 64, 3, 1, 1, _st()),
+                   "vqw_conv2d_fwd")
+        p1 = empty_nhwc(2 * M, 64, h, w, sr)
+        _lib.check(L.vqw_maxpool2_fwd(_p(r12), _p(p1), 2 * M, H, W, 64, _st()), "vqw_maxpool2_fwd")
+        a2 = _pc_conv(L, p1, w3, b3, 64, 128, 2 * M, h, w, True)  # conv2_1 + ReLU
+        d = empty_nhwc(M, 128, h, w, sr)
+        _lib.check(L.vqw_percep_diff(_p(a2), _p(d), d.numel(), _st()), "vqw_percep_diff")
+        y = _pc_conv(L, d, w4, None, 128, 128, M, h, w, False)    # conv2_2 before its ReLU: vgg(sr) - vgg(hr)
+        loss = torch.empty(nwin, dtype=torch.float32, device=sr.device)
+        lws = _ws(L.vqw_percep_loss_ws_bytes(nwin), sr)
+        _lib.check(L.vqw_percep_loss_fwd(_p(y), _p(loss), _p(lws), lws.numel(), nwin, N * 128 * h * w, _st()), "vqw_percep_loss_fwd")
+        ctx.save_for_backward(sr, a1[:M], r12[:M], p1[:M], a2[:M], y)
+        ctx.weights = (w1, w2, w3, w4)
+        ctx.win = win
+        ctx.shape = (N, nwin, C, H, W)
+        return loss[0] if nwin == 1 else tuple(loss.unbind())
+
+    @staticmethod
+    def backward(ctx, *gl):
+        none = (None,) * 11
+        if not ctx.needs_input_grad[0]:
+            return none
+        sr, a1, r12, p1, a2, y = ctx.saved_tensors
+        w1, w2, w3, w4 = ctx.weights
+        N, nwin, C, H, W = ctx.shape
+        M, h, w = nwin * N, H // 2, W // 2
+        L = _L()
+        dz2 = _pc_dgrad(L, y, w4, a2, 128, 128, M, h, w)           # conv2_2^T, ReLU of conv2_1
+        dp1 = _pc_dgrad(L, dz2, w3, None, 64, 128, M, h, w)        # conv2_1^T
+        _lib.check(L.vqw_relu_bwd(_p(p1), _p(dp1), _p(dp1), dp1.numel(), _st()), "vqw_relu_bwd")   # ReLU of conv1_2, pooled
+        dr12 = empty_nhwc(M, 64, H, W, sr)
+        _lib.check(L.vqw_maxpool2_bwd(_p(r12), _p(dp1), None, _p(dr12), M, H, W, 64, _st()), "vqw_maxpool2_bwd")
+        dz1 = _pc_dgrad(L, dr12, w2, a1, 64, 64, M, H, W)          # conv1_2^T, ReLU of conv1_1
+        gs = [g.contiguous() for g in gl]
+        gs += [None] * (3 - len(gs))
+        gsr = torch.empty_like(sr, memory_format=CL)
+        _lib.check(L.vqw_percep_stem_bwd(_p(sr), _p(_pc_stem(w1, C)), _p(ctx.win), _p(gs[0]), _p(gs[1]), _p(gs[2]), _p(dz1),
+                                         _p(gsr), N, nwin, C, H, W, N * 128 * h * w, _st()), "vqw_percep_stem_bwd")
+        return (gsr,) + none[1:]
+
+
+def perceptual_loss(sr, hr, w1, b1, w2, b2, w3, b3, w4, b4, window=None, windows=None):
+    """F.mse_loss(vgg(sr), vgg(hr)) of the reference's VGGLoss(conv_index='22'): vgg = vgg19.features[:8] (conv1_1, ReLU,
+    conv1_2, ReLU, MaxPool2d(2), conv2_1, ReLU, conv2_2 - the output is taken before the last ReLU) on the inputs expanded
+    to 3 channels.  w1..w4 / b1..b4: the four convolutions' weights (OIHW, [64,3,3,3] ... [128,128,3,3]) and biases.
+    The gradient flows to sr only; hr and the weights get none.
+    window = (alpha, beta, lo, hi) of `window_map`: both images are re-windowed inside the kernels first.  windows = a tuple
+    of such windows (None: the identity), all evaluated in one batch: returns one loss per window."""
+    single = windows is None
+    if single:
+        windows = (window,)
+    elif window is not None:
+        raise RuntimeError("perceptual_loss: pass window or windows, not both")
+    windows = tuple(None if x is None else tuple(float(v) for v in x) for x in windows)
+    if not 1 <= len(windows) <= 3 or any(x is not None and len(x) != 4 for x in windows):
+        raise RuntimeError("perceptual_loss: one to three windows, each the (alpha, beta, lo, hi) of window_map")
+    out = _PerceptualLoss.apply(sr, hr.detach(), windows, w1, b1, w2, b2, w3, b3, w4, b4)
+    return out if single or isinstance(out, tuple) else (out,)
+
+
 METRIC_SLOTS = ("mse", "ssim", "psnr", "ssim_range", "psnr_range", "sse", "target_min", "target_max", "entropy", "bad_ids",
                 "n_ids")
 _MT_OUT = 16

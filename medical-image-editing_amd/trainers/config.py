@@ -10,14 +10,19 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
                  use_regularization_loss}, use_recon_loss, use_frequency_loss, use_perceptual_loss}
     config.{enc_optim, dec_optim}.{lr, b1, b2, weight_decay}
     config.augmentation.{modules, ...}            (optional: absent -> the exact-integer flip views of the benchmark)
-    config.dataset.{window_width, window_center, window_scale}, config.loss.{recon_weights, freq_weights}   (multi-window
-                 runs, -w)
+    config.dataset.{window_width, window_center, window_scale}, config.loss.{recon_weights, freq_weights, percep_weights}
+                 (multi-window runs, -w)
+    config.loss.{perceptual_loss_type, conv_index, perceptual_weights}   (with use_perceptual_loss)
 
 The focal frequency loss (use_frequency_loss) is functions.FocalFrequencyLoss, built on HIP kernels in place of the
-third-party focal-frequency-loss package.  The perceptual loss (VGG / LPIPS weights that must be fetched) is absent
-offline: a config that switches it on raises instead of silently training something else.
+third-party focal-frequency-loss package.  The perceptual loss (use_perceptual_loss with perceptual_loss_type 'vgg', the
+reference's VGGLoss()) is functions.VGGLoss on HIP kernels.  The reference downloads its VGG19 weights; this build never
+downloads anything, so `config.loss.perceptual_weights` - a key of this project, not of the reference - names a local
+file: torchvision's vgg19 state dict (vgg19-dcbb9e9d.pth), a VGGLoss state dict or a reference checkpoint of a run with the
+loss on.  Without it a config that switches the loss on raises, as do perceptual_loss_type 'lpips' (the lpips package
+with AlexNet weights) and conv_index '54': neither is built, and nothing silently trains something else.
 """
-from functions import EmbeddingLoss, FocalFrequencyLoss
+from functions import EmbeddingLoss, FocalFrequencyLoss, VGGLoss
 from hipops import Adam
 from networks import UNetEncoder, UNetDecoder, RandomTransform
 
@@ -74,7 +79,7 @@ def configure_losses(config):
     """-> EmbeddingLoss (base.py:261-278); None-for-false flags pass through as the reference's do."""
     c = config.loss
     if _get(c, "use_perceptual_loss"):
-        raise NotImplementedError("use_perceptual_loss needs pretrained VGG / LPIPS weights that cannot be fetched offline")
+        _perceptual_settings(c)         # raises for what is not built
     return EmbeddingLoss(dict_size=config.model.vqmodel.dict_size, margin=c.embed_loss.margin,
                          use_distance_loss=c.embed_loss.use_distance_loss,
                          use_regularization_loss=c.embed_loss.use_regularization_loss)
@@ -86,6 +91,36 @@ def configure_frequency_loss(config):
     if _get(config.loss, "use_frequency_loss"):
         return FocalFrequencyLoss(loss_weight=1.0, alpha=1.0)
     return None
+
+
+def _perceptual_settings(c):
+    """-> (conv_index, weights path) of a config with use_perceptual_loss; NotImplementedError for what is not built."""
+    kind = _get(c, "perceptual_loss_type") or "vgg"
+    if kind == "lpips":
+        raise NotImplementedError("use_perceptual_loss with perceptual_loss_type 'lpips' (the lpips package with AlexNet "
+                                  "weights) is not built; use perceptual_loss_type 'vgg'")
+    if kind != "vgg":
+        raise NotImplementedError("use_perceptual_loss: unknown perceptual_loss_type %r" % (kind,))
+    conv_index = str(_get(c, "conv_index") or "22")
+    if conv_index != "22":
+        raise NotImplementedError("use_perceptual_loss with conv_index %r is not built: only VGGLoss()'s '22' slice "
+                                  "(vgg19.features[:8], trainers/base.py:273)" % (conv_index,))
+    path = _get(c, "perceptual_weights")
+    if not path:
+        raise NotImplementedError("use_perceptual_loss needs the pretrained VGG19 weights, which this build never downloads: "
+                                  "set config.loss.perceptual_weights to a local vgg19 state dict (vgg19-dcbb9e9d.pth), "
+                                  "a VGGLoss state dict or a reference checkpoint of a run with the loss on")
+    return conv_index, path
+
+
+def configure_perceptual_loss(config):
+    """-> VGGLoss() as base.py:271-275 builds it when use_perceptual_loss is set (weights from
+    config.loss.perceptual_weights), else None."""
+    c = config.loss
+    if not _get(c, "use_perceptual_loss"):
+        return None
+    conv_index, path = _perceptual_settings(c)
+    return VGGLoss(conv_index=conv_index, weights=path)
 
 
 def loss_weights(config):
@@ -119,6 +154,14 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
     if multi_window is None and _get(config.loss, "recon_weights") is not None and _get(config.dataset, "window_width") is not None:
         d = config.dataset
         multi_window = dict(dataset_window=(d.window_width, d.window_center, d.window_scale), recon_weights=tuple(config.loss.recon_weights))
+    perceptual_loss = configure_perceptual_loss(config)
+    percep_weights = None
+    if perceptual_loss is not None and multi_window is not None:
+        percep_weights = _get(config.loss, "percep_weights")
+        if percep_weights is None:
+            raise ValueError("config.loss.percep_weights is required for a multi-window run with use_perceptual_loss "
+                             "(multi_window_trainer.py:54, 101-119)")
+        percep_weights = tuple(percep_weights)
     freq_weights = None
     if frequency_loss is not None and multi_window is not None:
         freq_weights = _get(config.loss, "freq_weights")
@@ -136,4 +179,5 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
         views=views if views is not None else set_transform(config, seed=_get(config.run, "seed", 0) or 0), device=device,
         encoder=encoder, decoder=decoder, data_parallel=data_parallel, multi_window=multi_window,
         embed_loss=configure_losses(config), enc_optim=_adam_kwargs(config.enc_optim), dec_optim=_adam_kwargs(config.dec_optim),
-        use_recon_loss=bool(_get(config.loss, "use_recon_loss", True)), frequency_loss=frequency_loss, freq_weights=freq_weights)
+        use_recon_loss=bool(_get(config.loss, "use_recon_loss", True)), frequency_loss=frequency_loss, freq_weights=freq_weights,
+        perceptual_loss=perceptual_loss, percep_weights=percep_weights)

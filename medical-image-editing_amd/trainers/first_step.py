@@ -92,7 +92,7 @@ class FirstStepTrainer:
                  weight_decay=0.0, use_pixel_shuffle=False, dropped_skip_layers=(), views=None, device="cuda",
                  encoder=None, decoder=None, data_parallel=False, use_onehot=False, concurrent_views=None,
                  multi_window=None, embed_loss=None, enc_optim=None, dec_optim=None, use_recon_loss=True,
-                 frequency_loss=None, freq_weights=None):
+                 frequency_loss=None, freq_weights=None, perceptual_loss=None, percep_weights=None):
         self.device = torch.device(device)
         self.encoder = encoder if encoder is not None else UNetEncoder(
             in_channels, list(enc_filters), dict_size, momentum, 'torch', False, 1, True)
@@ -117,6 +117,12 @@ class FirstStepTrainer:
         self.freq_weights = tuple(freq_weights) if freq_weights is not None else None
         if frequency_loss is not None and multi_window is not None and self.freq_weights is None:
             raise ValueError("multi-window training with the frequency loss needs freq_weights (config.loss.freq_weights)")
+        # perceptual_loss: functions.VGGLoss (config.loss.use_perceptual_loss) or None; in multi-window runs
+        # percep_weights = config.loss.percep_weights (w_full, w_lung, w_mediastinal), multi_window_trainer.py:54, 101-119
+        self.perceptual_loss = perceptual_loss.to(self.device) if perceptual_loss is not None else None
+        self.percep_weights = tuple(percep_weights) if percep_weights is not None else None
+        if perceptual_loss is not None and multi_window is not None and self.percep_weights is None:
+            raise ValueError("multi-window training with the perceptual loss needs percep_weights (config.loss.percep_weights)")
         # base.py:165-175: one Adam per sub-network over its trainable parameters
         # (enc_optim / dec_optim: dicts with lr, betas, weight_decay per sub-network, as config.enc_optim / dec_optim give)
         eo = {**dict(lr=lr, betas=betas, weight_decay=weight_decay), **(enc_optim or {})}
@@ -171,17 +177,19 @@ class FirstStepTrainer:
         recon_1 = self.decoder(embed_1)
         rec_1 = self._recon_terms(recon_1, clear_1)
         frq_1 = self._freq_terms(recon_1, clear_1)
+        pcp_1 = self._percep_terms(recon_1, clear_1)
         with torch.cuda.stream(s2):
             recon_2 = self.decoder(embed_2)
             rec_2 = self._recon_terms(recon_2, clear_2)
             frq_2 = self._freq_terms(recon_2, clear_2)
+            pcp_2 = self._percep_terms(recon_2, clear_2)
             ev2 = s2.record_event()
         s1.wait_event(ev2)
-        for t in [l_commit_2, recon_2, l_cross, embed_2, r_ids_2, ids_2] + [t for t, _ in rec_2 + frq_2] + \
+        for t in [l_commit_2, recon_2, l_cross, embed_2, r_ids_2, ids_2] + [t for t, _ in rec_2 + frq_2 + pcp_2] + \
                 [t for t in (l_dist, l_reg) if torch.is_tensor(t)]:
             t.record_stream(s1)
         l_rec_1, l_rec_2 = rec_1[0][0], rec_2[0][0]
-        terms = rec_1 + rec_2 + frq_1 + frq_2
+        terms = rec_1 + rec_2 + frq_1 + frq_2 + pcp_1 + pcp_2
         l_total = ops.weighted_sum(
             [l_commit_1, l_commit_2, l_cross, l_dist, l_reg] + [t for t, _ in terms],
             [w.commit, w.commit, w.cross, w.dist, w.reg] + [c for _, c in terms])
@@ -190,6 +198,8 @@ class FirstStepTrainer:
                    embed_1=embed_1, embed_2=embed_2)
         if frq_1:                 # only with the frequency loss on: without it the step returns what it always did
             out.update(freq_1=frq_1[0][0], freq_2=frq_2[0][0])
+        if pcp_1:                 # likewise only with the perceptual loss on
+            out.update(perceptual_1=pcp_1[0][0], perceptual_2=pcp_2[0][0])
         return out
 
     def _recon_terms(self, recon, clear):
@@ -218,6 +228,20 @@ class FirstStepTrainer:
                  ffl(recon, clear, window=ops.window_map(dw, MEDIASTINAL_WINDOW))]
         return [(t, self.w.freq * float(f) / 3.0) for t, f in zip(terms, self.freq_weights)]
 
+    def _percep_terms(self, recon, clear):
+        """[(loss term, weight)] of one view's perceptual loss (single_window_trainer.py:124-137): none without the loss;
+        VGGLoss(recon, clear); or, multi-window, percep_weights[i] / 3 * VGGLoss on the full / lung / mediastinal windows
+        (multi_window_trainer.py:101-119), all three windows in one batch with the window map applied inside the kernels.
+        The first term is the full-window (or only) loss."""
+        vgg = self.perceptual_loss
+        if vgg is None:
+            return []
+        if self.multi_window is None:
+            return [(vgg(recon, clear), self.w.perceptual)]
+        dw = self.multi_window["dataset_window"]
+        terms = vgg(recon, clear, windows=(None, ops.window_map(dw, LUNG_WINDOW), ops.window_map(dw, MEDIASTINAL_WINDOW)))
+        return [(t, self.w.perceptual * float(p) / 3.0) for t, p in zip(terms, self.percep_weights)]
+
     def forward_losses(self, image, noise=None):
         """Lines 73-137 of the reference step.  `image` is in [-1, 1] (dataloader convention)."""
         if self.concurrent_views and not self.use_onehot:
@@ -239,8 +263,9 @@ class FirstStepTrainer:
         recon_2 = self.decoder(embed_2)
         rec_1, rec_2 = self._recon_terms(recon_1, clear_1), self._recon_terms(recon_2, clear_2)
         frq_1, frq_2 = self._freq_terms(recon_1, clear_1), self._freq_terms(recon_2, clear_2)
+        pcp_1, pcp_2 = self._percep_terms(recon_1, clear_1), self._percep_terms(recon_2, clear_2)
         l_rec_1, l_rec_2 = rec_1[0][0], rec_2[0][0]
-        terms = rec_1 + rec_2 + frq_1 + frq_2
+        terms = rec_1 + rec_2 + frq_1 + frq_2 + pcp_1 + pcp_2
         l_total = ops.weighted_sum(
             [l_commit_1, l_commit_2, l_cross, l_dist, l_reg] + [t for t, _ in terms],
             [w.commit, w.commit, w.cross, w.dist, w.reg] + [c for _, c in terms])
@@ -249,6 +274,8 @@ class FirstStepTrainer:
                    embed_1=embed_1, embed_2=embed_2)
         if frq_1:                 # only with the frequency loss on: without it the step returns what it always did
             out.update(freq_1=frq_1[0][0], freq_2=frq_2[0][0])
+        if pcp_1:                 # likewise only with the perceptual loss on
+            out.update(perceptual_1=pcp_1[0][0], perceptual_2=pcp_2[0][0])
         return out
 
     def test_step(self, batch):
@@ -281,8 +308,12 @@ class FirstStepTrainer:
 
     @staticmethod
     def scalars(out):
-        """Host copies of the logged scalars (one sync; keep out of timed regions); `freq` is 0.0 without the frequency loss."""
+        """Host copies of the logged scalars (one sync; keep out of timed regions); `freq` is 0.0 without the frequency loss,
+        `perceptual` is there only with the perceptual loss on."""
         f = lambda t: float(t.detach()) if torch.is_tensor(t) else float(t)  # noqa: E731
-        return dict(total=f(out["total"]), commit=f(out["commit_1"]) + f(out["commit_2"]), cross=f(out["cross"]),
-                    dist=f(out["dist"]), reg=f(out["reg"]), recon=f(out["recon_l1"]) + f(out["recon_l2"]),
-                    freq=f(out.get("freq_1", 0.0)) + f(out.get("freq_2", 0.0)))
+        sc = dict(total=f(out["total"]), commit=f(out["commit_1"]) + f(out["commit_2"]), cross=f(out["cross"]),
+                  dist=f(out["dist"]), reg=f(out["reg"]), recon=f(out["recon_l1"]) + f(out["recon_l2"]),
+                  freq=f(out.get("freq_1", 0.0)) + f(out.get("freq_2", 0.0)))
+        if "perceptual_1" in out:
+            sc["perceptual"] = f(out["perceptual_1"]) + f(out["perceptual_2"])
+        return sc

@@ -2,9 +2,8 @@
 trainers/single_window_trainer.py:434-488 (`_train_second_step_nl_dis`), optimisers per trainers/base.py:165-181.
 
 The encoder is frozen (eval mode, no_grad); the decoder is trained on  w.recon * MSE(recon, image) + w.gen * (-mean(D(recon)))
-(+ w.freq * FFL(recon, image) with a frequency_loss, :453-466); then the discriminator on  w.dis * hinge_d_loss(D(image),
-D(recon.detach()))  for n_inner_loops.  The perceptual term (LPIPS / VGG weights that must be fetched) is not part of this
-build, as in the first step.
+(+ w.freq * FFL(recon, image) with a frequency_loss, + w.perceptual * VGGLoss(recon, image) with a perceptual_loss,
+:453-467); then the discriminator on  w.dis * hinge_d_loss(D(image), D(recon.detach()))  for n_inner_loops.
 """
 from collections import namedtuple
 
@@ -14,12 +13,13 @@ from hipops import ops, Adam
 from networks.discriminator import NLayerDiscriminator
 from functions.gan_loss import hinge_d_loss, generator_loss
 
-GanLossWeights = namedtuple("GanLossWeights", "recon gen dis freq", defaults=(1.0, 1.0, 1.0, 0.0))
+GanLossWeights = namedtuple("GanLossWeights", "recon gen dis freq perceptual", defaults=(1.0, 1.0, 1.0, 0.0, 0.0))
 
 
 class SecondStepTrainer:
     def __init__(self, encoder, decoder, dis=None, loss_weight=None, n_inner_loops=1, lr=1e-4, betas=(0.5, 0.999),
-                 weight_decay=0.0, device="cuda", data_parallel=False, frequency_loss=None):
+                 weight_decay=0.0, device="cuda", data_parallel=False, frequency_loss=None,
+                 perceptual_loss=None):
         self.device = torch.device(device)
         from .first_step import StepThrottle
         self.throttle = StepThrottle(self.device)      # at most two steps enqueued ahead of the GPU
@@ -29,6 +29,8 @@ class SecondStepTrainer:
         self.w = loss_weight if loss_weight is not None else GanLossWeights()
         self.n_inner_loops = int(n_inner_loops)
         self.frequency_loss = frequency_loss          # functions.FocalFrequencyLoss or None (use_frequency_loss)
+        # functions.VGGLoss or None (use_perceptual_loss); no trainable parameters, so nothing to all-reduce
+        self.perceptual_loss = perceptual_loss.to(self.device) if perceptual_loss is not None else None
         self.dec_optim = Adam([p for p in self.decoder.parameters() if p.requires_grad], lr=lr, betas=betas,
                               weight_decay=weight_decay)
         self.dis_optim = Adam([p for p in self.dis.parameters() if p.requires_grad], lr=lr, betas=betas,
@@ -61,6 +63,7 @@ class SecondStepTrainer:
         recon = self.decoder(embed.detach())
         l_recon = ops.mse_loss(recon, image)
         l_freq = self.frequency_loss(recon, image) if self.frequency_loss is not None else None
+        l_percep = self.perceptual_loss(recon, image) if self.perceptual_loss is not None else None
         # The reference lets autograd fill the discriminator's parameter gradients in this pass and discards them
         # (dis_optim.zero_grad() below); they are not computed here.  Same decoder gradients, same update.
         dis_params = [p for p in self.dis.parameters() if p.requires_grad]
@@ -72,6 +75,9 @@ class SecondStepTrainer:
             if l_freq is not None:
                 terms.append(l_freq)
                 weights.append(w.freq)
+            if l_percep is not None:
+                terms.append(l_percep)
+                weights.append(w.perceptual)
             l_gen_total = ops.weighted_sum(terms, weights)
             self.dec_optim.zero_grad()
             if self.dec_reducer is not None:
@@ -101,4 +107,6 @@ class SecondStepTrainer:
         out = dict(gen_total=l_gen_total, recon=l_recon, gen=l_gen, dis_total=l_dis_total, ids=ids, recon_image=recon)
         if l_freq is not None:
             out["freq"] = l_freq
+        if l_percep is not None:
+            out["perceptual"] = l_percep
         return out

@@ -26,6 +26,17 @@ def load_discriminator_from_ckpt(path, dis):
     return dis
 
 
+def perceptual_state_from_ckpt(path):
+    """The VGG slice a reference run with use_perceptual_loss saved (`perceptual_loss.vgg.N.*`, base.py:271-275) as a
+    functions.VGGLoss state dict (`vgg.N.*`)."""
+    sd = _state_dict(path)
+    pre = 'perceptual_loss.'
+    out = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre + 'vgg.')}
+    if not out:
+        raise KeyError("%s holds no perceptual_loss.vgg.* entries" % (path,))
+    return out
+
+
 def init_from_ckpt(path, model, key_name, delete_string='model.'):
     """run_recon.py:98-112: keep the keys that start with `key_name`, strip `delete_string` from those that carry it."""
     sd = _state_dict(path)
