@@ -27,6 +27,10 @@
 #define VQWNET_HIP_H
 #include <stddef.h>
 #include <stdint.h>
+
+/* vqw_abi_version() returns it; the Python binding reads it from here and refuses a library built from another version */
+#define VQW_ABI_VERSION 9
+
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -6,6 +6,7 @@
 //   photometric  brightness add, contrast multiply (both clamped to [0,1]), posterize, additive Gaussian noise
 //   gauss_blur   separable Gaussian, reflect border, per-sample on/off
 #include "common.h"
+#include "../../include/vqwnet_hip.h"
 
 namespace {
 

@@ -91,7 +91,7 @@ def instance_norm(x: Tensor, relu: bool, eps: float) -> Tuple[Tensor, Tensor]:
     y = torch.empty_like(x, memory_format=CL)
     mr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
     ws = ops._ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-    ops._lib.check(L.vqw_inorm_fwd(ops._p(x), ops._p(y), C, 0, ops._p(mr), ops._p(ws), ws.numel(), N, H * W, C, eps, int(relu), ops._st()), "vqw_inorm_fwd")
+    L.vqw_inorm_fwd(x, y, C, 0, mr, ws, ws.numel(), N, H * W, C, eps, int(relu))
     return y, mr
 
 
@@ -107,8 +107,7 @@ def instance_norm_backward(gy: Tensor, x: Tensor, mean_rstd: Tensor, relu: bool)
     L = ops._L()
     gx = torch.empty_like(x, memory_format=CL)
     ws = ops._ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-    ops._lib.check(L.vqw_inorm_bwd(ops._p(x), ops._p(mean_rstd), ops._p(gy), C, 0, ops._p(gx), ops._p(ws), ws.numel(), N, H * W, C, int(relu), ops._st()),
-                   "vqw_inorm_bwd")
+    L.vqw_inorm_bwd(x, mean_rstd, gy, C, 0, gx, ws, ws.numel(), N, H * W, C, int(relu))
     return gx
 
 
@@ -143,8 +142,7 @@ def vq_forward(x: Tensor, embed: Tensor, id_base: int) -> Tuple[Tensor, Tensor, 
     q = torch.empty_like(x, memory_format=CL)
     commit = torch.empty((), dtype=torch.float32, device=x.device)
     ws = ops._ws(L.vqw_vq_ws_bytes(N * H * W, D, K), x)
-    ops._lib.check(L.vqw_vq_fwd(ops._p(x), ops._p(embed.contiguous()), ops._p(ids), id_base, ops._p(q), ops._p(commit), None, ops._p(ws), ws.numel(),
-                                N * H * W, D, K, ops._st()), "vqw_vq_fwd")
+    L.vqw_vq_fwd(x, embed.contiguous(), ids, id_base, q, commit, None, ws, ws.numel(), N * H * W, D, K)
     return q, commit, ids
 
 
@@ -161,7 +159,7 @@ def vq_backward(x: Tensor, q: Tensor, g_q: Optional[Tensor], g_commit: Optional[
     gx = torch.empty_like(x, memory_format=CL)
     gq = ops.nhwc(g_q) if g_q is not None else None
     gc = g_commit.contiguous() if g_commit is not None else None
-    ops._lib.check(ops._L().vqw_vq_bwd(ops._p(x), ops._p(ops.nhwc(q)), ops._p(gq), ops._p(gc), ops._p(gx), x.numel(), ops._st()), "vqw_vq_bwd")
+    ops._L().vqw_vq_bwd(x, ops.nhwc(q), gq, gc, gx, x.numel())
     return gx
 
 
@@ -194,8 +192,7 @@ def embed_cross_loss(embed: Tensor, labels: Tensor, codebook_kd: Tensor) -> Tupl
     loss = torch.empty((), dtype=torch.float32, device=e.device)
     coef = torch.empty(B * K, dtype=torch.float32, device=e.device)
     ws = ops._ws(L.vqw_cross_ws_bytes(B, K, H * W), e)
-    ops._lib.check(L.vqw_cross_loss_fwd(ops._p(e), ops._p(labels.contiguous()), ops._p(codebook_kd.contiguous()), ops._p(loss), ops._p(coef), ops._p(ws),
-                                        ws.numel(), B, H * W, D, K, ops._st()), "vqw_cross_loss_fwd")
+    L.vqw_cross_loss_fwd(e, labels.contiguous(), codebook_kd.contiguous(), loss, coef, ws, ws.numel(), B, H * W, D, K)
     return loss, coef
 
 
@@ -210,8 +207,8 @@ def embed_cross_loss_backward(g: Tensor, embed: Tensor, labels: Tensor, codebook
     B, D, H, W = e.shape
     K = codebook_kd.shape[0]
     ge = torch.empty_like(e, memory_format=CL)
-    ops._lib.check(ops._L().vqw_cross_loss_bwd(ops._p(e), ops._p(labels.contiguous()), ops._p(codebook_kd.contiguous()), ops._p(coef), ops._p(g.contiguous()),
-                                               ops._p(ge), B, H * W, D, K, ops._st()), "vqw_cross_loss_bwd")
+    ops._L().vqw_cross_loss_bwd(e, labels.contiguous(), codebook_kd.contiguous(),
+                                coef, g.contiguous(), ge, B, H * W, D, K)
     return ge
 
 
@@ -241,7 +238,7 @@ def res_tail(a: Tensor, b: Tensor) -> Tuple[Tensor, Tensor]:
     N, C, H, W = a.shape
     out = torch.empty_like(a, memory_format=CL)
     pooled = ops.empty_nhwc(N, C, H // 2, W // 2, a)
-    ops._lib.check(ops._L().vqw_res_tail_fwd(ops._p(a), ops._p(b), ops._p(out), ops._p(pooled), N, H, W, C, ops._st()), "vqw_res_tail_fwd")
+    ops._L().vqw_res_tail_fwd(a, b, out, pooled, N, H, W, C)
     return pooled, out
 
 
@@ -259,7 +256,7 @@ def res_tail_backward(out: Tensor, g_pooled: Optional[Tensor], g_out: Optional[T
     g = torch.empty_like(out, memory_format=CL)
     gp = ops.nhwc(g_pooled) if g_pooled is not None else None
     go = ops.nhwc(g_out) if g_out is not None else None
-    ops._lib.check(ops._L().vqw_res_tail_bwd(ops._p(out), ops._p(gp), ops._p(go), ops._p(g), N, H, W, C, ops._st()), "vqw_res_tail_bwd")
+    ops._L().vqw_res_tail_bwd(out, gp, go, g, N, H, W, C)
     return g
 
 

@@ -3,7 +3,7 @@ operator `torch.ops.vqw.<name>` with a schema string derived from its C prototyp
 
     const T* p      ->  Tensor? p            (read)
     T* p            ->  Tensor(a!)? p        (written: outputs, in-place buffer updates, workspaces)
-    int / long / size_t / int64_t  -> int,   float / double -> float
+    int / unsigned / long / size_t -> int,   float / double -> float
     void* stream    ->  dropped: the kernel is enqueued on torch's CURRENT stream
     int status      ->  () ; a non-zero status raises RuntimeError with vqw_last_error()
 
@@ -19,56 +19,21 @@ classes call; `functional.py` additionally exposes the main ones as functional d
 torch.library.register_autograd formulas.
 """
 import ctypes
-import os
-import re
 
 import torch
 
 from . import _lib
+from ._lib import parse_header
 
 NAMESPACE = "vqw"
-_HDR = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "include", "vqwnet_hip.h")
-
-_INT = {"int", "long", "size_t", "int64_t", "int32_t", "unsigned"}
-_FLT = {"float", "double"}
-
-
-def parse_header(path=_HDR):
-    """-> {name: (return type, [(kind, name)])} with kind in {'in', 'out', 'int', 'float', 'stream', 'host'}."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", " ", text)
-    protos = {}
-    for m in re.finditer(r"([\w\s\*]+?)\b(vqw_\w+)\s*\(([^()]*)\)\s*;", text):
-        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
-        args = []
-        if params and params != "void":
-            for p in params.split(","):
-                p = " ".join(p.split())
-                pname = re.findall(r"\w+", p)[-1]
-                if "*" in p:
-                    if pname == "stream":
-                        kind = "stream"
-                    elif name.endswith("_host"):
-                        kind = "host"                 # host arrays passed by value (vqw_weighted_sum_host)
-                    else:
-                        kind = "in" if p.startswith("const ") else "out"
-                else:
-                    base = p.replace("const ", "").split()[0]
-                    kind = "int" if base in _INT else "float" if base in _FLT else None
-                    if kind is None:
-                        raise RuntimeError("unhandled parameter %r of %s" % (p, name))
-                args.append((kind, pname))
-        protos[name] = (ret, args)
-    return protos
 
 
 def schema_of(name, args):
     """Schema string of a kernel entry point (None when it is not expressible as a tensor operator)."""
-    if not args or args[-1][0] != "stream" or any(k == "host" for k, _ in args):
+    if not args or args[-1][0] != "stream" or any(k == "host" for k, _, _ in args):
         return None
     parts, letter = [], 0
-    for kind, pname in args[:-1]:
+    for kind, pname, _ in args[:-1]:
         if kind == "in":
             parts.append("Tensor? %s" % pname)
         elif kind == "out":
@@ -88,7 +53,7 @@ SCHEMAS = {}
 
 def _make_kernel(name, args):
     cfn = getattr(_lib.load(), name)
-    kinds = [k for k, _ in args[:-1]]
+    kinds = [k for k, _, _ in args[:-1]]
     c_void_p = ctypes.c_void_p
 
     def kernel(*a):
@@ -122,24 +87,17 @@ def register():
 
 
 class Dispatch:
-    """`L.vqw_xxx(tensor or None, ..., scalars ..., STREAM)` with the argument list of the C function: kernels go through
-    torch.ops.vqw.*, tensor-free host queries straight to the C library.  Returns the C convention's 0 (errors raise)."""
-    STREAM = object()
+    """`L.vqw_xxx`: a kernel entry point is its operator torch.ops.vqw.xxx.default, called with the C argument list minus
+    the trailing stream (the kernel is enqueued on torch's current stream); it returns None and a non-zero status raises.
+    A tensor-free host query is the C function itself and returns its value."""
 
     def __init__(self):
         self._ops = register()
         self._c = _lib.load()
-        self._cache = {}
 
     def __getattr__(self, name):
-        fn = self._cache.get(name)
+        fn = self._ops.get(name)
         if fn is None:
-            op = self._ops.get(name)
-            if op is None:
-                fn = getattr(self._c, name)
-            else:
-                def fn(*a, _op=op):
-                    _op(*a[:-1])          # the trailing stream placeholder is implied by the current stream
-                    return 0
-            self._cache[name] = fn
+            fn = getattr(self._c, name)
+        setattr(self, name, fn)       # later lookups are plain attribute hits
         return fn

@@ -33,15 +33,6 @@ def _L():
     return _dispatch
 
 
-# stream and tensor arguments as the dispatcher operators take them: the stream is torch's current one, tensors pass as they are
-def _st():
-    return _D.STREAM
-
-
-def _p(t):
-    return t
-
-
 def _raw(t):
     """Raw device pointer for the few host-side entry points that take pointer arrays by value."""
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
@@ -316,12 +307,11 @@ def _run_wgrad(L, x0, x1, gy, gw, gb, up0, ks, dilation, N, H, W, Cout, acc, col
         try:
             if collapsed and L.vqw_conv3x3_up2_wgrad_supported(C0, Cout, N, H // 2, W // 2):
                 ws = _ws(L.vqw_conv3x3_up2_wgrad_ws_bytes(C0, Cout, N, H // 2, W // 2), gy)
-                _lib.check(L.vqw_conv3x3_up2_wgrad(_p(x0), _p(gy), _p(gw), _p(gb), _p(ws), ws.numel(), N, H // 2, W // 2, C0, Cout,
-                                                   int(acc), _st()), "vqw_conv3x3_up2_wgrad")
+                L.vqw_conv3x3_up2_wgrad(x0, gy, gw, gb, ws, ws.numel(), N, H // 2, W // 2, C0, Cout, int(acc))
             else:
                 ws = _ws(L.vqw_conv2d_wgrad_ws_bytes(C0, C1, N, H, W, Cout, ks), gy)
-                _lib.check(L.vqw_conv2d_wgrad(_p(x0), C0, int(up0), _p(x1), C1, _p(gy), _p(gw), _p(gb), _p(ws), ws.numel(),
-                                              N, H, W, Cout, ks, dilation, int(acc), _st()), "vqw_conv2d_wgrad")
+                L.vqw_conv2d_wgrad(x0, C0, int(up0), x1, C1, gy, gw, gb, ws, ws.numel(), N, H, W, Cout, ks, dilation,
+                                   int(acc))
         except RuntimeError as e:
             if defer_fold and attempt == 0 and "flush first" in str(e):
                 # a third use of one weight inside a pass: fold what is recorded (on this lane, after the other lanes), retry
@@ -397,7 +387,7 @@ def _deferred_wgrad(weight, bias, x0, x1, gy, up0, ks, dilation, N, H, W, Cout, 
 def _wino_weights(L, w_ohwi, Cin, Cout):
     """U = G w G^T [16][Cout][Cin] of a 3x3 layer (vqw_conv3x3_wino_prepare) in a fresh buffer."""
     buf = _ws(L.vqw_conv3x3_wino_ws_bytes(Cin, Cout), w_ohwi)
-    _lib.check(L.vqw_conv3x3_wino_prepare(_p(w_ohwi), _p(buf), buf.numel(), Cin, Cout, _st()), "vqw_conv3x3_wino_prepare")
+    L.vqw_conv3x3_wino_prepare(w_ohwi, buf, buf.numel(), Cin, Cout)
     return buf
 
 
@@ -405,14 +395,14 @@ def _wino_weights_dgrad(L, w_ohwi, Cin, Cout):
     """U of a 3x3 layer's INPUT-GRADIENT convolution (Cin = the layer's couts, Cout = its input channels), straight from the
     layer's weight: what _wino_weights gives on the packed input-gradient weights, without the pack launch."""
     buf = _ws(L.vqw_conv3x3_wino_ws_bytes(Cin, Cout), w_ohwi)
-    _lib.check(L.vqw_conv3x3_wino_prepare_dgrad(_p(w_ohwi), _p(buf), buf.numel(), Cin, Cout, _st()), "vqw_conv3x3_wino_prepare_dgrad")
+    L.vqw_conv3x3_wino_prepare_dgrad(w_ohwi, buf, buf.numel(), Cin, Cout)
     return buf
 
 
 def _up2_weights(L, w_ohwi, Cin, Cout):
     """The collapsed weights of a 3x3 layer over a nearest x2 up-sampled input (vqw_conv3x3_up2_prepare) in a fresh buffer."""
     buf = _ws(L.vqw_conv3x3_up2_ws_bytes(Cin, Cout), w_ohwi)
-    _lib.check(L.vqw_conv3x3_up2_prepare(_p(w_ohwi), _p(buf), buf.numel(), Cin, Cout, _st()), "vqw_conv3x3_up2_prepare")
+    L.vqw_conv3x3_up2_prepare(w_ohwi, buf, buf.numel(), Cin, Cout)
     return buf
 
 
@@ -527,26 +517,19 @@ class _Conv2d(torch.autograd.Function):
         y = empty_nhwc(N, Cout, H, W, x0)
         part = torch.empty(N * nparts * Cout * 2, dtype=torch.float32, device=x0.device) if nparts > 0 else None
         if form == "up2" and part is not None:
-            _lib.check(L.vqw_conv3x3_up2_fwd_stats(_p(x0), _p(up_ws), _p(bias), _p(y), _p(part), N, h, wl, Cin, Cout, _st()),
-                       "vqw_conv3x3_up2_fwd_stats")
+            L.vqw_conv3x3_up2_fwd_stats(x0, up_ws, bias, y, part, N, h, wl, Cin, Cout)
         elif form == "up2":
-            _lib.check(L.vqw_conv3x3_up2_fwd(_p(x0), _p(up_ws), _p(bias), _p(y), N, h, wl, Cin, Cout, int(relu), _st()),
-                       "vqw_conv3x3_up2_fwd")
+            L.vqw_conv3x3_up2_fwd(x0, up_ws, bias, y, N, h, wl, Cin, Cout, int(relu))
         elif form == "wino" and part is not None:
-            _lib.check(L.vqw_conv3x3_wino_fwd_stats(_p(x0), _p(u), _p(bias), _p(y), _p(part), N, H, W, Cin, Cout, _st()),
-                       "vqw_conv3x3_wino_fwd_stats")
+            L.vqw_conv3x3_wino_fwd_stats(x0, u, bias, y, part, N, H, W, Cin, Cout)
         elif form == "wino":
-            _lib.check(L.vqw_conv3x3_wino_fwd(_p(x0), _p(u), _p(bias), _p(y), N, H, W, Cin, Cout, int(relu), _st()),
-                       "vqw_conv3x3_wino_fwd")
+            L.vqw_conv3x3_wino_fwd(x0, u, bias, y, N, H, W, Cin, Cout, int(relu))
         elif form == "dil2":
-            _lib.check(L.vqw_conv3x3_wino_dil2_fwd(_p(x0), _p(u), _p(bias), _p(y), _p(part), 0, N, H, W, Cin, Cout, int(relu), _st()),
-                       "vqw_conv3x3_wino_dil2_fwd")
+            L.vqw_conv3x3_wino_dil2_fwd(x0, u, bias, y, part, 0, N, H, W, Cin, Cout, int(relu))
         elif part is not None:
-            _lib.check(L.vqw_conv2d_fwd_stats(_p(x0), x0.shape[1], int(up0), _p(x1), c1, _p(w), _p(bias), _p(y), _p(part),
-                                              N, H, W, Cout, ks, dilation, _st()), "vqw_conv2d_fwd_stats")
+            L.vqw_conv2d_fwd_stats(x0, x0.shape[1], int(up0), x1, c1, w, bias, y, part, N, H, W, Cout, ks, dilation)
         else:
-            _lib.check(L.vqw_conv2d_fwd(_p(x0), x0.shape[1], int(up0), _p(x1), c1, _p(w), _p(bias), _p(y),
-                                        N, H, W, Cout, ks, dilation, int(relu), _st()), "vqw_conv2d_fwd")
+            L.vqw_conv2d_fwd(x0, x0.shape[1], int(up0), x1, c1, w, bias, y, N, H, W, Cout, ks, dilation, int(relu))
         ctx.up_ws = up_ws
         ctx.group = grad_group
         ctx.save_for_backward(x0, x1, w, y if relu else None)
@@ -655,8 +638,7 @@ class _ConvPair(torch.autograd.Function):
             yb = empty_nhwc(N, Ca, H, W, x)
             pa = torch.empty(N * nparts * Ca * 2, dtype=torch.float32, device=x.device)
             pb = torch.empty(N * nparts * Ca * 2, dtype=torch.float32, device=x.device)
-            _lib.check(L.vqw_conv3x3_up2_fwd_pair(_p(x), _p(up_ws), _p(bias_cat), _p(ya), _p(yb), _p(pa), _p(pb), N, h, w, Cin, Ca, _st()),
-                       "vqw_conv3x3_up2_fwd_pair")
+            L.vqw_conv3x3_up2_fwd_pair(x, up_ws, bias_cat, ya, yb, pa, pb, N, h, w, Cin, Ca)
             up_pair_calls += 1
             ctx.mark_non_differentiable(pa, pb)
             outs = (ya, pa, yb, pb)
@@ -669,8 +651,7 @@ class _ConvPair(torch.autograd.Function):
                                   deps=deps)
             ya = empty_nhwc(N, Ca, H, W, x)
             yb = empty_nhwc(N, Ca, H, W, x)
-            _lib.check(L.vqw_conv3x3_wino_fwd_split(_p(x), _p(u), _p(bias_cat), _p(ya), _p(yb), N, H, W, Cin, 2 * Ca, Ca, 0, int(relu),
-                                                    _st()), "vqw_conv3x3_wino_fwd_split")
+            L.vqw_conv3x3_wino_fwd_split(x, u, bias_cat, ya, yb, N, H, W, Cin, 2 * Ca, Ca, 0, int(relu))
             conv_pair_calls += 1
             outs = (ya, yb)
         wa_n, wb_n = nhwc(wa), nhwc(wb)
@@ -829,7 +810,7 @@ def conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up0, has_bias, up_ws, 
             pass             # the consumer's input-gradient kernel has applied this very mask in its epilogue (_ConvCat.backward)
         else:
             gm = torch.empty_like(y_relu, memory_format=CL)
-            _lib.check(L.vqw_relu_bwd(_p(y_relu), _p(gy), _p(gm), gy.numel(), _st()), "vqw_relu_bwd")
+            L.vqw_relu_bwd(y_relu, gy, gm, gy.numel())
             gy = gm
     C0 = x0.shape[1]
     C1 = 0 if x1 is None else x1.shape[1]
@@ -843,21 +824,19 @@ def conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up0, has_bias, up_ws, 
     def packed():
         def _pack():
             buf = torch.empty(Cin * ks * ks * Cout, dtype=torch.float32, device=gy.device)
-            _lib.check(L.vqw_pack_dgrad_weights(_p(w), _p(buf), Cout, Cin, ks, _st()), "vqw_pack_dgrad_weights")
+            L.vqw_pack_dgrad_weights(w, buf, Cout, Cin, ks)
             return buf
         return _cached(w, "dgrad", _pack)
 
     if need0 and up_ws is not None:
         if group is not None and group.buf is not None and L.vqw_conv3x3_up2_dgrad_acc_supported(Cin, Cout, N, H // 2, W // 2):
             # the other up-sampled convolution of this input has run: add to its gradient in this kernel's epilogue
-            _lib.check(L.vqw_conv3x3_up2_dgrad_acc(_p(gy), _p(up_ws), _p(group.buf), N, H // 2, W // 2, Cin, Cout, _st()),
-                       "vqw_conv3x3_up2_dgrad_acc")
+            L.vqw_conv3x3_up2_dgrad_acc(gy, up_ws, group.buf, N, H // 2, W // 2, Cin, Cout)
             group_acc_calls += 1
             g0 = group.member_done(None)
         else:
             g0 = torch.empty_like(x0, memory_format=CL)
-            _lib.check(L.vqw_conv3x3_up2_dgrad(_p(gy), _p(up_ws), _p(g0), N, H // 2, W // 2, Cin, Cout, _st()),
-                       "vqw_conv3x3_up2_dgrad")
+            L.vqw_conv3x3_up2_dgrad(gy, up_ws, g0, N, H // 2, W // 2, Cin, Cout)
             if group is not None:
                 g0 = group.member_done(g0)
     elif need0 or (need1 and x1 is not None):
@@ -887,11 +866,9 @@ def conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up0, has_bias, up_ws, 
             g0 = torch.empty_like(x0, memory_format=CL)
             g1 = torch.empty_like(x1, memory_format=CL)
             if Cp == Cin:
-                _lib.check(L.vqw_conv3x3_wino_fwd_split(_p(gy), _p(ut), None, _p(g0), _p(g1), N, H, W, Cout, Cin, C0, int(up0), 0, _st()),
-                           "vqw_conv3x3_wino_fwd_split(dgrad)")
+                L.vqw_conv3x3_wino_fwd_split(gy, ut, None, g0, g1, N, H, W, Cout, Cin, C0, int(up0), 0)
             else:
-                _lib.check(L.vqw_conv3x3_wino_fwd_split_padded(_p(gy), _p(ut), None, _p(g0), _p(g1), N, H, W, Cout, Cp, C0, C1, int(up0), 0,
-                                                               _st()), "vqw_conv3x3_wino_fwd_split_padded(dgrad)")
+                L.vqw_conv3x3_wino_fwd_split_padded(gy, ut, None, g0, g1, N, H, W, Cout, Cp, C0, C1, int(up0), 0)
             split_dgrad_calls += 1
         else:
             # a later member of a gradient group (single full-resolution source) adds into the shared buffer where a kernel can
@@ -900,17 +877,14 @@ def conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up0, has_bias, up_ws, 
             if acc and ks == 3 and dilation == 1 and L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W) \
                     and L.vqw_conv3x3_wino_masked_supported(Cout, Cin, N, H, W):
                 # Winograd form, the shared buffer read and added in the kernel's epilogue
-                _lib.check(L.vqw_conv3x3_wino_fwd_acc(_p(gy), _p(wino_u()), _p(group.buf), N, H, W, Cout, Cin, _st()),
-                           "vqw_conv3x3_wino_fwd_acc(dgrad)")
+                L.vqw_conv3x3_wino_fwd_acc(gy, wino_u(), group.buf, N, H, W, Cout, Cin)
                 group_acc_calls += 1
             elif acc and ks == 3 and dilation == 2 and L.vqw_conv3x3_wino_dil2_supported(Cout, Cin, N, H, W):
                 # dilation 2: the Winograd kernel on the phase images, adding to the shared buffer in its epilogue
-                _lib.check(L.vqw_conv3x3_wino_dil2_fwd(_p(gy), _p(wino_u()), None, _p(group.buf), None, 1, N, H, W, Cout, Cin, 0, _st()),
-                           "vqw_conv3x3_wino_dil2_fwd(dgrad, acc)")
+                L.vqw_conv3x3_wino_dil2_fwd(gy, wino_u(), None, group.buf, None, 1, N, H, W, Cout, Cin, 0)
             elif acc and L.vqw_conv2d_fwd_acc_supported(Cout, N, H, W, Cin, ks, dilation):
                 # row-chain kernel (dilated 3x3) or the implicit-GEMM kernel (1x1): y += conv in the epilogue
-                _lib.check(L.vqw_conv2d_fwd_acc(_p(gy), Cout, _p(packed()), _p(group.buf), N, H, W, Cin, ks, dilation, _st()),
-                           "vqw_conv2d_fwd_acc")
+                L.vqw_conv2d_fwd_acc(gy, Cout, packed(), group.buf, N, H, W, Cin, ks, dilation)
                 if ks == 1:
                     group_acc_calls += 1
             else:
@@ -922,18 +896,14 @@ def conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up0, has_bias, up_ws, 
                     ut = wino_u()
                     bpart = torch.empty(N * nparts * Cin * 2, dtype=torch.float32, device=gy.device)
                     xraw, mr, nrelu = in_src
-                    _lib.check(L.vqw_conv3x3_wino_fwd_inbwd(_p(gy), _p(ut), _p(xraw), _p(mr), int(nrelu), _p(g_full), _p(bpart),
-                                                            N, H, W, Cout, Cin, _st()), "vqw_conv3x3_wino_fwd_inbwd(dgrad)")
+                    L.vqw_conv3x3_wino_fwd_inbwd(gy, ut, xraw, mr, int(nrelu), g_full, bpart, N, H, W, Cout, Cin)
                     _IN_BWD_PARTS.put(g_full, (bpart, nparts, xraw.data_ptr()))
                 elif ks == 3 and dilation == 1 and L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W):
-                    _lib.check(L.vqw_conv3x3_wino_fwd(_p(gy), _p(wino_u()), None, _p(g_full), N, H, W, Cout, Cin, 0, _st()),
-                               "vqw_conv3x3_wino_fwd(dgrad)")
+                    L.vqw_conv3x3_wino_fwd(gy, wino_u(), None, g_full, N, H, W, Cout, Cin, 0)
                 elif ks == 3 and dilation == 2 and x1 is None and not up0 and L.vqw_conv3x3_wino_dil2_supported(Cout, Cin, N, H, W):
-                    _lib.check(L.vqw_conv3x3_wino_dil2_fwd(_p(gy), _p(wino_u()), None, _p(g_full), None, 0, N, H, W, Cout, Cin, 0, _st()),
-                               "vqw_conv3x3_wino_dil2_fwd(dgrad)")
+                    L.vqw_conv3x3_wino_dil2_fwd(gy, wino_u(), None, g_full, None, 0, N, H, W, Cout, Cin, 0)
                 else:
-                    _lib.check(L.vqw_conv2d_fwd(_p(gy), Cout, 0, None, 0, _p(packed()), None, _p(g_full), N, H, W, Cin, ks, dilation, 0,
-                                                _st()), "vqw_conv2d_fwd(dgrad)")
+                    L.vqw_conv2d_fwd(gy, Cout, 0, None, 0, packed(), None, g_full, N, H, W, Cin, ks, dilation, 0)
             if group is not None and need0:
                 g0 = group.member_done(g_full)
             elif not up0 and x1 is None:
@@ -941,12 +911,10 @@ def conv2d_backward_impl(gy, x0, x1, w, y_relu, dilation, up0, has_bias, up_ws, 
             else:
                 if need0:
                     g0 = torch.empty_like(x0, memory_format=CL)
-                    _lib.check(L.vqw_input_grad_gather(_p(g_full), Cin, 0, C0, int(up0), _p(g0), 0, N, H, W, _st()),
-                               "vqw_input_grad_gather")
+                    L.vqw_input_grad_gather(g_full, Cin, 0, C0, int(up0), g0, 0, N, H, W)
                 if need1 and x1 is not None:
                     g1 = torch.empty_like(x1, memory_format=CL)
-                    _lib.check(L.vqw_input_grad_gather(_p(g_full), Cin, C0, C1, 0, _p(g1), 0, N, H, W, _st()),
-                               "vqw_input_grad_gather")
+                    L.vqw_input_grad_gather(g_full, Cin, C0, C1, 0, g1, 0, N, H, W)
     if needw or (needb and has_bias):
         gw = torch.empty((Cout, Cin, ks, ks), dtype=torch.float32, device=gy.device, memory_format=CL)
         gb = torch.empty(Cout, dtype=torch.float32, device=gy.device) if has_bias else None
@@ -1087,10 +1055,10 @@ class _ConvCat(torch.autograd.Function):
             L = _L()
             u = _cached(wa, "cat_wino", lambda: _wino_weights(L, w, Cin, Ca + Cb), deps=(wb,))
             y = empty_nhwc(N, Ca + Cb, H, W, x)
-            _lib.check(L.vqw_conv3x3_wino_fwd(_p(x), _p(u), _p(b), _p(y), N, H, W, Cin, Ca + Cb, 0, _st()), "vqw_conv3x3_wino_fwd")
+            L.vqw_conv3x3_wino_fwd(x, u, b, y, N, H, W, Cin, Ca + Cb, 0)
         else:
             y = empty_nhwc(N, Ca + Cb, H, W, x)
-            _lib.check(_L().vqw_conv2d_fwd(_p(x), Cin, 0, None, 0, _p(w), _p(b), _p(y), N, H, W, Ca + Cb, ks, 1, 0, _st()), "vqw_conv2d_fwd")
+            _L().vqw_conv2d_fwd(x, Cin, 0, None, 0, w, b, y, N, H, W, Ca + Cb, ks, 1, 0)
         ctx.save_for_backward(x, w)
         ctx.cfg = (ks, N, H, W, Ca, Cb)
         ctx.params = (wa, ba, wb, bb)
@@ -1109,25 +1077,22 @@ class _ConvCat(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             def _pack():
                 buf = torch.empty(Cin * ks * ks * Ct, dtype=torch.float32, device=gy.device)
-                _lib.check(L.vqw_pack_dgrad_weights(_p(w), _p(buf), Ct, Cin, ks, _st()), "vqw_pack_dgrad_weights")
+                L.vqw_pack_dgrad_weights(w, buf, Ct, Cin, ks)
                 return buf
             gx = empty_nhwc(N, Cin, H, W, gy)
             if ks == 3 and L.vqw_conv3x3_wino_supported(Ct, Cin, N, H, W):
                 ut = _cached(wa, "cat_wino_dgrad", lambda: _wino_weights_dgrad(L, w, Ct, Cin), deps=(wb,))
                 if ctx.relu_in and FUSE_RELU_MASK and L.vqw_conv3x3_wino_masked_supported(Ct, Cin, N, H, W):
                     # the gradient in FRONT of the producer's ReLU: its mask (x > 0) applied in this kernel's epilogue
-                    _lib.check(L.vqw_conv3x3_wino_fwd_masked(_p(gy), _p(ut), _p(x), _p(gx), N, H, W, Ct, Cin, _st()),
-                               "vqw_conv3x3_wino_fwd_masked(dgrad)")
+                    L.vqw_conv3x3_wino_fwd_masked(gy, ut, x, gx, N, H, W, Ct, Cin)
                     _MASKED_GRADS.put(gx, x.data_ptr())
                     global masked_dgrad_calls
                     masked_dgrad_calls += 1
                 else:
-                    _lib.check(L.vqw_conv3x3_wino_fwd(_p(gy), _p(ut), None, _p(gx), N, H, W, Ct, Cin, 0, _st()),
-                               "vqw_conv3x3_wino_fwd(dgrad)")
+                    L.vqw_conv3x3_wino_fwd(gy, ut, None, gx, N, H, W, Ct, Cin, 0)
             else:
                 wt = _cached(wa, "cat_dgrad", _pack, deps=(wb,))
-                _lib.check(L.vqw_conv2d_fwd(_p(gy), Ct, 0, None, 0, _p(wt), None, _p(gx), N, H, W, Cin, ks, 1, 0, _st()),
-                           "vqw_conv2d_fwd(dgrad)")
+                L.vqw_conv2d_fwd(gy, Ct, 0, None, 0, wt, None, gx, N, H, W, Cin, ks, 1, 0)
         if ctx.defer:
             _deferred_wgrad_cat(wa, ba, wb, bb, x, gy, ks, N, H, W)
         elif any(ctx.needs_input_grad[1:5]):
@@ -1159,11 +1124,10 @@ class _InstanceNorm(torch.autograd.Function):
         mr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
         if part is not None:        # statistics left by the producing convolution's epilogue
             nparts = part.numel() // (N * C * 2)
-            _lib.check(L.vqw_inorm_fwd_parts(_p(x), _p(y), C, 0, _p(mr), _p(part), nparts, N, H * W, C, eps, int(relu), _st()),
-                       "vqw_inorm_fwd_parts")
+            L.vqw_inorm_fwd_parts(x, y, C, 0, mr, part, nparts, N, H * W, C, eps, int(relu))
         else:
             ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            _lib.check(L.vqw_inorm_fwd(_p(x), _p(y), C, 0, _p(mr), _p(ws), ws.numel(), N, H * W, C, eps, int(relu), _st()), "vqw_inorm_fwd")
+            L.vqw_inorm_fwd(x, y, C, 0, mr, ws, ws.numel(), N, H * W, C, eps, int(relu))
         ctx.save_for_backward(x, mr)
         ctx.relu = relu
         ctx.mark_non_differentiable(mr)
@@ -1186,12 +1150,10 @@ class _InstanceNorm(torch.autograd.Function):
             in_bwd_fused_calls += 1
             bpart, nparts, _ = ent
             means = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
-            _lib.check(L.vqw_inorm_bwd_parts(_p(x), _p(mr), _p(gy), _p(bpart), nparts, _p(means), _p(gx), N, H * W, C,
-                                             int(ctx.relu), _st()), "vqw_inorm_bwd_parts")
+            L.vqw_inorm_bwd_parts(x, mr, gy, bpart, nparts, means, gx, N, H * W, C, int(ctx.relu))
             return gx, None, None, None
         ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-        _lib.check(L.vqw_inorm_bwd(_p(x), _p(mr), _p(gy), C, 0, _p(gx), _p(ws), ws.numel(), N, H * W, C, int(ctx.relu), _st()),
-                   "vqw_inorm_bwd")
+        L.vqw_inorm_bwd(x, mr, gy, C, 0, gx, ws, ws.numel(), N, H * W, C, int(ctx.relu))
         return gx, None, None, None
 
 
@@ -1225,12 +1187,10 @@ class _InstanceNormCat(torch.autograd.Function):
             mr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
             part = parts[len(mrs)] if parts is not None else None
             if part is not None:        # statistics left by the producing convolution's epilogue
-                _lib.check(L.vqw_inorm_fwd_parts(_p(x), _p(y), Ct, off, _p(mr), _p(part), part.numel() // (N * C * 2), N, H * W, C,
-                                                 eps, int(relu), _st()), "vqw_inorm_fwd_parts")
+                L.vqw_inorm_fwd_parts(x, y, Ct, off, mr, part, part.numel() // (N * C * 2), N, H * W, C, eps, int(relu))
             else:
                 ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-                _lib.check(L.vqw_inorm_fwd(_p(x), _p(y), Ct, off, _p(mr), _p(ws), ws.numel(), N, H * W, C, eps, int(relu), _st()),
-                           "vqw_inorm_fwd")
+                L.vqw_inorm_fwd(x, y, Ct, off, mr, ws, ws.numel(), N, H * W, C, eps, int(relu))
             mrs.append(mr)
             off += C
         ctx.save_for_backward(*xs, *mrs)
@@ -1249,8 +1209,7 @@ class _InstanceNormCat(torch.autograd.Function):
             C = x.shape[1]
             gx = torch.empty_like(x, memory_format=CL)
             ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            _lib.check(L.vqw_inorm_bwd(_p(x), _p(mr), _p(gy), Ct, off, _p(gx), _p(ws), ws.numel(), N, H * W, C, int(ctx.relu), _st()),
-                       "vqw_inorm_bwd")
+            L.vqw_inorm_bwd(x, mr, gy, Ct, off, gx, ws, ws.numel(), N, H * W, C, int(ctx.relu))
             outs.append(gx)
             off += C
         return (None, None, None, *outs)
@@ -1306,8 +1265,8 @@ class _Spade(torch.autograd.Function):
         else:
             beta = nhwc(beta)
         gbs = 2 * C if fused else C
-        gptr = _p(gamma)
-        bptr = _p(gamma.narrow(1, C, C) if fused else beta)      # fused: beta = channels C..2C of the same NHWC map
+        gptr = gamma
+        bptr = gamma.narrow(1, C, C) if fused else beta      # fused: beta = channels C..2C of the same NHWC map
         L = _L()
         mr = torch.empty(2 * C, dtype=torch.float32, device=x.device)
         count = float(N * H * W)
@@ -1318,10 +1277,10 @@ class _Spade(torch.autograd.Function):
                 pass
             elif part is not None:    # per-tile sums left by the producing convolution's epilogue
                 rows = part.numel() // (2 * C)
-                _lib.check(L.vqw_bn_stats_from_parts(_p(part), _p(sums), rows, C, count / rows, _st()), "vqw_bn_stats_from_parts")
+                L.vqw_bn_stats_from_parts(part, sums, rows, C, count / rows)
             else:
                 ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-                _lib.check(L.vqw_bn_partial_stats(_p(x), _p(sums), _p(ws), ws.numel(), N, H * W, C, _st()), "vqw_bn_partial_stats")
+                L.vqw_bn_partial_stats(x, sums, ws, ws.numel(), N, H * W, C)
             if sync and _dist_on():
                 # SyncBatchNorm semantics (run_vqwnet.py:121): global-batch statistics, one small all-reduce.
                 # Every rank holds the same per-rank batch (weak scaling), so the count needs no exchange.
@@ -1330,16 +1289,15 @@ class _Spade(torch.autograd.Function):
             cur = _order_begin(running_mean)
             if fused_finalize:
                 rows = part.numel() // (2 * C)
-                _lib.check(L.vqw_bn_finalize_parts(_p(part), rows, count / rows, _p(sums), count, _p(mr), _p(running_mean), _p(running_var),
-                                                   momentum, eps, C, _st()), "vqw_bn_finalize_parts")
+                L.vqw_bn_finalize_parts(part, rows, count / rows, sums, count, mr,
+                                        running_mean, running_var, momentum, eps, C)
             else:
-                _lib.check(L.vqw_bn_finalize(_p(sums), count, _p(mr), _p(running_mean), _p(running_var), momentum, eps, C, _st()),
-                           "vqw_bn_finalize")
+                L.vqw_bn_finalize(sums, count, mr, running_mean, running_var, momentum, eps, C)
             if nbt is not None:
                 _bump_counter(nbt)
             _order_end(running_mean, cur)
         else:
-            _lib.check(L.vqw_bn_eval_stats(_p(running_mean), _p(running_var), _p(mr), eps, C, _st()), "vqw_bn_eval_stats")
+            L.vqw_bn_eval_stats(running_mean, running_var, mr, eps, C)
         y = torch.empty_like(x, memory_format=CL)
         rmr = None
         if res is not None:         # y = act(...) + res: the block's `shortcut + main` inside this kernel
@@ -1350,19 +1308,16 @@ class _Spade(torch.autograd.Function):
             rpart, rrelu, reps = res_norm
             rmr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
             if rpart is not None:
-                _lib.check(L.vqw_inorm_stats_parts(_p(rpart), rpart.numel() // (N * C * 2), _p(rmr), N, H * W, C, reps, _st()),
-                           "vqw_inorm_stats_parts")
+                L.vqw_inorm_stats_parts(rpart, rpart.numel() // (N * C * 2), rmr, N, H * W, C, reps)
             else:
                 ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), res)
-                _lib.check(L.vqw_inorm_stats(_p(res), _p(rmr), _p(ws), ws.numel(), N, H * W, C, reps, _st()), "vqw_inorm_stats")
-            _lib.check(L.vqw_spade_fwd_res_norm(_p(x), _p(mr), gptr, bptr, gbs, _p(res), _p(rmr), int(rrelu), _p(y), N, H * W, C,
-                                                int(relu), _st()), "vqw_spade_fwd_res_norm")
+                L.vqw_inorm_stats(res, rmr, ws, ws.numel(), N, H * W, C, reps)
+            L.vqw_spade_fwd_res_norm(x, mr, gptr, bptr, gbs, res, rmr, int(rrelu), y, N, H * W, C, int(relu))
             ctx.res_relu = bool(rrelu)
         elif res is not None:
-            _lib.check(L.vqw_spade_fwd_res(_p(x), _p(mr), gptr, bptr, gbs, _p(res), _p(y), N * H * W, C, int(relu), _st()),
-                       "vqw_spade_fwd_res")
+            L.vqw_spade_fwd_res(x, mr, gptr, bptr, gbs, res, y, N * H * W, C, int(relu))
         else:
-            _lib.check(L.vqw_spade_fwd(_p(x), _p(mr), gptr, bptr, gbs, _p(y), N * H * W, C, int(relu), _st()), "vqw_spade_fwd")
+            L.vqw_spade_fwd(x, mr, gptr, bptr, gbs, y, N * H * W, C, int(relu))
         ctx.save_for_backward(x, gamma, beta, mr, res if rmr is not None else None, rmr)
         ctx.cfg = (training, relu, count, sync, fused)
         ctx.has_res = res is not None
@@ -1377,28 +1332,25 @@ class _Spade(torch.autograd.Function):
         gy = nhwc(gy)
         if fused:
             dgamma, dbeta, gbs = torch.empty_like(gamma, memory_format=CL), None, 2 * C
-            gptr, dgptr = _p(gamma), _p(dgamma)
-            bptr, dbptr = _p(gamma.narrow(1, C, C)), _p(dgamma.narrow(1, C, C))
+            gptr, dgptr = gamma, dgamma
+            bptr, dbptr = gamma.narrow(1, C, C), dgamma.narrow(1, C, C)
         else:
             dgamma = torch.empty_like(x, memory_format=CL)
             dbeta = torch.empty_like(x, memory_format=CL)
-            gbs, gptr, bptr, dgptr, dbptr = C, _p(gamma), _p(beta), _p(dgamma), _p(dbeta)
+            gbs, gptr, bptr, dgptr, dbptr = C, gamma, beta, dgamma, dbeta
         gx = torch.empty_like(x, memory_format=CL)
         sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
         ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-        _lib.check(L.vqw_spade_bwd_reduce(_p(x), _p(mr), gptr, bptr, _p(gy), dgptr, dbptr, gbs, _p(sums), _p(ws),
-                                          ws.numel(), N, H * W, C, int(relu), _st()), "vqw_spade_bwd_reduce")
+        L.vqw_spade_bwd_reduce(x, mr, gptr, bptr, gy, dgptr, dbptr, gbs, sums, ws, ws.numel(), N, H * W, C, int(relu))
         if training and sync and _dist_on():
             _all_reduce(sums)
-        _lib.check(L.vqw_spade_bwd_apply(_p(x), _p(mr), gptr, bptr, gbs, _p(gy), _p(sums), count, _p(gx), N * H * W, C,
-                                         int(relu), int(training), _st()), "vqw_spade_bwd_apply")
+        L.vqw_spade_bwd_apply(x, mr, gptr, bptr, gbs, gy, sums, count, gx, N * H * W, C, int(relu), int(training))
         gres = gy if ctx.has_res else None
         if rmr is not None and ctx.needs_input_grad[11]:
             # the residual was normalised in the forward kernel: its gradient goes back through that InstanceNorm(+ReLU) here
             gres = torch.empty_like(res_raw, memory_format=CL)
             ws2 = _ws(L.vqw_plane_ws_bytes(N, C, H * W), res_raw)
-            _lib.check(L.vqw_inorm_bwd(_p(res_raw), _p(rmr), _p(gy), C, 0, _p(gres), _p(ws2), ws2.numel(), N, H * W, C,
-                                       int(ctx.res_relu), _st()), "vqw_inorm_bwd(residual)")
+            L.vqw_inorm_bwd(res_raw, rmr, gy, C, 0, gres, ws2, ws2.numel(), N, H * W, C, int(ctx.res_relu))
         return gx, dgamma, dbeta, None, None, None, None, None, None, None, None, gres, None, None
 
 
@@ -1440,7 +1392,7 @@ class _Add(torch.autograd.Function):
         if a.shape != b.shape:
             raise RuntimeError("add: shape mismatch %s vs %s" % (tuple(a.shape), tuple(b.shape)))
         y = torch.empty_like(a, memory_format=CL)
-        _lib.check(_L().vqw_add(_p(a), _p(b), _p(y), a.numel(), int(relu), _st()), "vqw_add")
+        _L().vqw_add(a, b, y, a.numel(), int(relu))
         ctx.relu = relu
         ctx.a_group = a_group
         if relu:
@@ -1453,7 +1405,7 @@ class _Add(torch.autograd.Function):
             (y,) = ctx.saved_tensors
             gy = nhwc(gy)
             gx = torch.empty_like(y, memory_format=CL)
-            _lib.check(_L().vqw_relu_bwd(_p(y), _p(gy), _p(gx), y.numel(), _st()), "vqw_relu_bwd")
+            _L().vqw_relu_bwd(y, gy, gx, y.numel())
             gy = gx
         if ctx.a_group is not None:
             # `a` has further consumers that form a gradient group (their backward runs AFTER everything upstream of `b`, which
@@ -1478,12 +1430,12 @@ class _AddNorm(torch.autograd.Function):
         L = _L()
         mr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
         if part is not None:
-            _lib.check(L.vqw_inorm_stats_parts(_p(part), part.numel() // (N * C * 2), _p(mr), N, H * W, C, eps, _st()), "vqw_inorm_stats_parts")
+            L.vqw_inorm_stats_parts(part, part.numel() // (N * C * 2), mr, N, H * W, C, eps)
         else:
             ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            _lib.check(L.vqw_inorm_stats(_p(x), _p(mr), _p(ws), ws.numel(), N, H * W, C, eps, _st()), "vqw_inorm_stats")
+            L.vqw_inorm_stats(x, mr, ws, ws.numel(), N, H * W, C, eps)
         y = torch.empty_like(x, memory_format=CL)
-        _lib.check(L.vqw_inorm_add_fwd(_p(x), _p(mr), _p(a), _p(y), N, H * W, C, int(relu), _st()), "vqw_inorm_add_fwd")
+        L.vqw_inorm_add_fwd(x, mr, a, y, N, H * W, C, int(relu))
         ctx.save_for_backward(x, mr)
         ctx.relu, ctx.a_group = bool(relu), a_group
         return y
@@ -1498,8 +1450,7 @@ class _AddNorm(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             gx = torch.empty_like(x, memory_format=CL)
             ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            _lib.check(L.vqw_inorm_bwd(_p(x), _p(mr), _p(gy), C, 0, _p(gx), _p(ws), ws.numel(), N, H * W, C, int(ctx.relu), _st()),
-                       "vqw_inorm_bwd(add_norm)")
+            L.vqw_inorm_bwd(x, mr, gy, C, 0, gx, ws, ws.numel(), N, H * W, C, int(ctx.relu))
         ga = gy
         if ctx.a_group is not None:
             ga = ctx.a_group.member_done(gy)
@@ -1528,7 +1479,7 @@ class _MaxPool2(torch.autograd.Function):
         x = nhwc(x)
         N, C, H, W = x.shape
         y = empty_nhwc(N, C, H // 2, W // 2, x)
-        _lib.check(_L().vqw_maxpool2_fwd(_p(x), _p(y), N, H, W, C, _st()), "vqw_maxpool2_fwd")
+        _L().vqw_maxpool2_fwd(x, y, N, H, W, C)
         ctx.save_for_backward(x)
         return y
 
@@ -1538,7 +1489,7 @@ class _MaxPool2(torch.autograd.Function):
         N, C, H, W = x.shape
         gy = nhwc(gy)
         gx = torch.empty_like(x, memory_format=CL)
-        _lib.check(_L().vqw_maxpool2_bwd(_p(x), _p(gy), None, _p(gx), N, H, W, C, _st()), "vqw_maxpool2_bwd")
+        _L().vqw_maxpool2_bwd(x, gy, None, gx, N, H, W, C)
         return gx
 
 
@@ -1561,7 +1512,7 @@ class _ResTail(torch.autograd.Function):
         L = _L()
         out = torch.empty_like(a, memory_format=CL)
         pooled = empty_nhwc(N, C, H // 2, W // 2, a)
-        _lib.check(L.vqw_res_tail_fwd(_p(a), _p(b), _p(out), _p(pooled), N, H, W, C, _st()), "vqw_res_tail_fwd")
+        L.vqw_res_tail_fwd(a, b, out, pooled, N, H, W, C)
         ctx.save_for_backward(out)
         ctx.set_materialize_grads(False)       # an unused output's gradient arrives as None (the kernel takes a null pointer), not as a zero fill
         return pooled, out
@@ -1575,7 +1526,7 @@ class _ResTail(torch.autograd.Function):
         gp = nhwc(g_pooled) if g_pooled is not None else None
         go = nhwc(g_out) if g_out is not None else None
         gx = torch.empty_like(out, memory_format=CL)
-        _lib.check(_L().vqw_res_tail_bwd(_p(out), _p(gp), _p(go), _p(gx), N, H, W, C, _st()), "vqw_res_tail_bwd")
+        _L().vqw_res_tail_bwd(out, gp, go, gx, N, H, W, C)
         return gx, gx
 
 
@@ -1599,26 +1550,23 @@ class _ResTailNorm(torch.autograd.Function):
         mr2 = torch.empty(N * C * 2, dtype=torch.float32, device=x2.device)
         mrid = torch.empty(N * C * 2, dtype=torch.float32, device=x2.device)
         if part2 is not None and partid is not None:      # both norms' statistics from their convolutions' partials: one launch
-            _lib.check(L.vqw_inorm_stats_parts2(_p(part2), part2.numel() // (N * C * 2), _p(mr2), _p(partid), partid.numel() // (N * C * 2),
-                                                _p(mrid), N, H * W, C, eps, _st()), "vqw_inorm_stats_parts2")
+            L.vqw_inorm_stats_parts2(part2, part2.numel() // (N * C * 2), mr2, partid,
+                                     partid.numel() // (N * C * 2), mrid, N, H * W, C, eps)
         elif part2 is not None:
-            _lib.check(L.vqw_inorm_stats_parts(_p(part2), part2.numel() // (N * C * 2), _p(mr2), N, H * W, C, eps, _st()),
-                       "vqw_inorm_stats_parts")
+            L.vqw_inorm_stats_parts(part2, part2.numel() // (N * C * 2), mr2, N, H * W, C, eps)
         else:
             ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x2)
-            _lib.check(L.vqw_inorm_stats(_p(x2), _p(mr2), _p(ws), ws.numel(), N, H * W, C, eps, _st()), "vqw_inorm_stats")
+            L.vqw_inorm_stats(x2, mr2, ws, ws.numel(), N, H * W, C, eps)
         if part2 is not None and partid is not None:
             pass
         elif partid is not None:
-            _lib.check(L.vqw_inorm_stats_parts(_p(partid), partid.numel() // (N * C * 2), _p(mrid), N, H * W, C, eps, _st()),
-                       "vqw_inorm_stats_parts")
+            L.vqw_inorm_stats_parts(partid, partid.numel() // (N * C * 2), mrid, N, H * W, C, eps)
         else:
             ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), xid)
-            _lib.check(L.vqw_inorm_stats(_p(xid), _p(mrid), _p(ws), ws.numel(), N, H * W, C, eps, _st()), "vqw_inorm_stats")
+            L.vqw_inorm_stats(xid, mrid, ws, ws.numel(), N, H * W, C, eps)
         out = torch.empty_like(x2, memory_format=CL)
         pooled = empty_nhwc(N, C, H // 2, W // 2, x2)
-        _lib.check(L.vqw_res_tail_norm_fwd(_p(x2), _p(mr2), _p(xid), _p(mrid), _p(out), _p(pooled), N, H, W, C, _st()),
-                   "vqw_res_tail_norm_fwd")
+        L.vqw_res_tail_norm_fwd(x2, mr2, xid, mrid, out, pooled, N, H, W, C)
         ctx.save_for_backward(x2, xid, mr2, mrid, out)
         ctx.set_materialize_grads(False)
         return pooled, out
@@ -1639,26 +1587,24 @@ class _ResTailNorm(torch.autograd.Function):
             gx2 = torch.empty_like(x2, memory_format=CL)
             gxid = torch.empty_like(xid, memory_format=CL)
             ws = _ws(2 * L.vqw_plane_ws_bytes(N, C, H * W), x2)
-            _lib.check(L.vqw_res_tail_bwd_pair(_p(out), _p(gp), _p(go), _p(x2), _p(mr2), _p(xid), _p(mrid), _p(g), _p(gx2), _p(gxid),
-                                               _p(ws), ws.numel(), N, H, W, C, _st()), "vqw_res_tail_bwd_pair")
+            L.vqw_res_tail_bwd_pair(out, gp, go, x2, mr2, xid, mrid, g, gx2, gxid, ws, ws.numel(), N, H, W, C)
             return gx2, gxid, None, None, None
-        _lib.check(L.vqw_res_tail_bwd(_p(out), _p(gp), _p(go), _p(g), N, H, W, C, _st()), "vqw_res_tail_bwd")
+        L.vqw_res_tail_bwd(out, gp, go, g, N, H, W, C)
         gx2 = gxid = None
         if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:      # both norms' backward, common gradient read once
             gx2 = torch.empty_like(x2, memory_format=CL)
             gxid = torch.empty_like(xid, memory_format=CL)
             ws = _ws(2 * L.vqw_plane_ws_bytes(N, C, H * W), x2)
-            _lib.check(L.vqw_inorm_bwd_pair(_p(x2), _p(mr2), _p(xid), _p(mrid), _p(g), _p(gx2), _p(gxid), _p(ws), ws.numel(),
-                                            N, H * W, C, _st()), "vqw_inorm_bwd_pair")
+            L.vqw_inorm_bwd_pair(x2, mr2, xid, mrid, g, gx2, gxid, ws, ws.numel(), N, H * W, C)
             return gx2, gxid, None, None, None
         if ctx.needs_input_grad[0]:
             gx2 = torch.empty_like(x2, memory_format=CL)
             ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x2)
-            _lib.check(L.vqw_inorm_bwd(_p(x2), _p(mr2), _p(g), C, 0, _p(gx2), _p(ws), ws.numel(), N, H * W, C, 1, _st()), "vqw_inorm_bwd")
+            L.vqw_inorm_bwd(x2, mr2, g, C, 0, gx2, ws, ws.numel(), N, H * W, C, 1)
         if ctx.needs_input_grad[1]:
             gxid = torch.empty_like(xid, memory_format=CL)
             ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), xid)
-            _lib.check(L.vqw_inorm_bwd(_p(xid), _p(mrid), _p(g), C, 0, _p(gxid), _p(ws), ws.numel(), N, H * W, C, 0, _st()), "vqw_inorm_bwd")
+            L.vqw_inorm_bwd(xid, mrid, g, C, 0, gxid, ws, ws.numel(), N, H * W, C, 0)
         return gx2, gxid, None, None, None
 
 
@@ -1686,7 +1632,7 @@ class _Tanh(torch.autograd.Function):
         _dev(x)
         x = nhwc(x)
         y = torch.empty_like(x, memory_format=CL)
-        _lib.check(_L().vqw_tanh_fwd(_p(x), _p(y), x.numel(), _st()), "vqw_tanh_fwd")
+        _L().vqw_tanh_fwd(x, y, x.numel())
         ctx.save_for_backward(y)
         return y
 
@@ -1695,7 +1641,7 @@ class _Tanh(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         gy = nhwc(gy)
         gx = torch.empty_like(y, memory_format=CL)
-        _lib.check(_L().vqw_tanh_bwd(_p(y), _p(gy), _p(gx), y.numel(), _st()), "vqw_tanh_bwd")
+        _L().vqw_tanh_bwd(y, gy, gx, y.numel())
         return gx
 
 
@@ -1708,7 +1654,7 @@ def affine_(x, scale, shift):
     _dev(x)
     if not (x.is_contiguous() or x.is_contiguous(memory_format=CL)):
         raise RuntimeError("affine_: tensor must be dense")
-    _lib.check(_L().vqw_affine(_p(x), _p(x), float(scale), float(shift), x.numel(), _st()), "vqw_affine")
+    _L().vqw_affine(x, x, float(scale), float(shift), x.numel())
     return x
 
 
@@ -1722,7 +1668,7 @@ class _Mse(torch.autograd.Function):
         L = _L()
         out = torch.empty((), dtype=torch.float32, device=a.device)
         ws = _ws(L.vqw_reduce_ws_bytes(a.numel()), a)
-        _lib.check(L.vqw_mse_fwd(_p(a), _p(b), _p(out), _p(ws), ws.numel(), a.numel(), _st()), "vqw_mse_fwd")
+        L.vqw_mse_fwd(a, b, out, ws, ws.numel(), a.numel())
         ctx.save_for_backward(a, b)
         return out
 
@@ -1731,7 +1677,7 @@ class _Mse(torch.autograd.Function):
         a, b = ctx.saved_tensors
         g = g.contiguous()
         ga = torch.empty_like(a, memory_format=CL)
-        _lib.check(_L().vqw_mse_bwd(_p(a), _p(b), _p(g), _p(ga), a.numel(), _st()), "vqw_mse_bwd")
+        _L().vqw_mse_bwd(a, b, g, ga, a.numel())
         return ga, None
 
 
@@ -1750,8 +1696,7 @@ class _WindowMse(torch.autograd.Function):
         L = _L()
         out = torch.empty((), dtype=torch.float32, device=a.device)
         ws = _ws(L.vqw_reduce_ws_bytes(a.numel()), a)
-        _lib.check(L.vqw_window_mse_fwd(_p(a), _p(b), _p(out), _p(ws), ws.numel(), a.numel(), alpha, beta, lo, hi, _st()),
-                   "vqw_window_mse_fwd")
+        L.vqw_window_mse_fwd(a, b, out, ws, ws.numel(), a.numel(), alpha, beta, lo, hi)
         ctx.save_for_backward(a, b)
         ctx.win = (alpha, beta, lo, hi)
         return out
@@ -1760,7 +1705,7 @@ class _WindowMse(torch.autograd.Function):
     def backward(ctx, g):
         a, b = ctx.saved_tensors
         ga = torch.empty_like(a, memory_format=CL)
-        _lib.check(_L().vqw_window_mse_bwd(_p(a), _p(b), _p(g.contiguous()), _p(ga), a.numel(), *ctx.win, _st()), "vqw_window_mse_bwd")
+        _L().vqw_window_mse_bwd(a, b, g.contiguous(), ga, a.numel(), *ctx.win)
         return ga, None, None, None, None, None
 
 
@@ -1793,7 +1738,7 @@ def _twiddle_table(n, like):
     tw = _twiddles.get(key)
     if tw is None:
         tw = torch.empty(2 * n, dtype=torch.float32, device=like.device)
-        _lib.check(_L().vqw_freq_twiddles(_p(tw), n, _st()), "vqw_freq_twiddles")
+        _L().vqw_freq_twiddles(tw, n)
         if not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream().synchronize()    # later calls may read it from another stream
         _twiddles[key] = tw
@@ -1818,9 +1763,8 @@ class _FreqLoss(torch.autograd.Function):
         ws = _ws(L.vqw_freq_loss_ws_bytes(N, C, H, W, pf), pred)        # D and the folded maxima, kept for backward
         wargs = (1,) + tuple(float(v) for v in win) if win is not None else (0, 1.0, 0.0, 0.0, 0.0)
         ctx.args = (N, C, H, W, pf, float(alpha), int(bool(log_matrix)), float(loss_weight)) + wargs
-        _lib.check(L.vqw_freq_loss_fwd(_p(pred), _p(target), _p(tw_h), _p(tw_w), _p(out), _p(ws), ws.numel(), N, C, H, W, pf,
-                                       float(alpha), int(bool(log_matrix)), int(bool(batch_matrix)), float(loss_weight),
-                                       *wargs, _st()), "vqw_freq_loss_fwd")
+        L.vqw_freq_loss_fwd(pred, target, tw_h, tw_w, out, ws, ws.numel(), N, C, H, W, pf, float(alpha),
+                            int(bool(log_matrix)), int(bool(batch_matrix)), float(loss_weight), *wargs)
         ctx.save_for_backward(pred, target, tw_h, tw_w, ws)
         return out
 
@@ -1831,8 +1775,7 @@ class _FreqLoss(torch.autograd.Function):
         gt = torch.empty_like(target, memory_format=CL) if ctx.needs_input_grad[1] else None
         if gp is None and gt is None:
             return (None,) * 8
-        _lib.check(_L().vqw_freq_loss_bwd(_p(pred), _p(target), _p(tw_h), _p(tw_w), _p(g.contiguous()), _p(gp), _p(gt), _p(ws),
-                                          ws.numel(), *ctx.args, _st()), "vqw_freq_loss_bwd")
+        _L().vqw_freq_loss_bwd(pred, target, tw_h, tw_w, g.contiguous(), gp, gt, ws, ws.numel(), *ctx.args)
         return gp, gt, None, None, None, None, None, None
 
 
@@ -1888,10 +1831,9 @@ def _pc_conv(L, x, w, b, Cin, Cout, N, H, W, relu):
     y = empty_nhwc(N, Cout, H, W, x)
     if L.vqw_conv3x3_wino_supported(Cin, Cout, N, H, W):
         u = _cached(w, "pc_wino", lambda: _wino_weights(L, _pc_ohwi(w), Cin, Cout))
-        _lib.check(L.vqw_conv3x3_wino_fwd(_p(x), _p(u), _p(b), _p(y), N, H, W, Cin, Cout, int(relu), _st()), "vqw_conv3x3_wino_fwd")
+        L.vqw_conv3x3_wino_fwd(x, u, b, y, N, H, W, Cin, Cout, int(relu))
     else:
-        _lib.check(L.vqw_conv2d_fwd(_p(x), Cin, 0, None, 0, _p(_pc_ohwi(w)), _p(b), _p(y), N, H, W, Cout, 3, 1, int(relu), _st()),
-                   "vqw_conv2d_fwd")
+        L.vqw_conv2d_fwd(x, Cin, 0, None, 0, _pc_ohwi(w), b, y, N, H, W, Cout, 3, 1, int(relu))
     return y
 
 
@@ -1903,20 +1845,19 @@ def _pc_dgrad(L, gy, w, mask, Cin, Cout, N, H, W):
     if masked_wino or (mask is None and L.vqw_conv3x3_wino_supported(Cout, Cin, N, H, W)):
         u = _cached(w, "pc_wino_dgrad", lambda: _wino_weights_dgrad(L, _pc_ohwi(w), Cout, Cin))
         if masked_wino:
-            _lib.check(L.vqw_conv3x3_wino_fwd_masked(_p(gy), _p(u), _p(mask), _p(gx), N, H, W, Cout, Cin, _st()),
-                       "vqw_conv3x3_wino_fwd_masked(dgrad)")
+            L.vqw_conv3x3_wino_fwd_masked(gy, u, mask, gx, N, H, W, Cout, Cin)
         else:
-            _lib.check(L.vqw_conv3x3_wino_fwd(_p(gy), _p(u), None, _p(gx), N, H, W, Cout, Cin, 0, _st()), "vqw_conv3x3_wino_fwd(dgrad)")
+            L.vqw_conv3x3_wino_fwd(gy, u, None, gx, N, H, W, Cout, Cin, 0)
         return gx
 
     def _pack():
         buf = torch.empty(Cin * 9 * Cout, dtype=torch.float32, device=gy.device)
-        _lib.check(L.vqw_pack_dgrad_weights(_p(_pc_ohwi(w)), _p(buf), Cout, Cin, 3, _st()), "vqw_pack_dgrad_weights")
+        L.vqw_pack_dgrad_weights(_pc_ohwi(w), buf, Cout, Cin, 3)
         return buf
     wt = _cached(w, "pc_dgrad", _pack)
-    _lib.check(L.vqw_conv2d_fwd(_p(gy), Cout, 0, None, 0, _p(wt), None, _p(gx), N, H, W, Cin, 3, 1, 0, _st()), "vqw_conv2d_fwd(dgrad)")
+    L.vqw_conv2d_fwd(gy, Cout, 0, None, 0, wt, None, gx, N, H, W, Cin, 3, 1, 0)
     if mask is not None:
-        _lib.check(L.vqw_relu_bwd(_p(mask), _p(gx), _p(gx), gx.numel(), _st()), "vqw_relu_bwd")
+        L.vqw_relu_bwd(mask, gx, gx, gx.numel())
     return gx
 
 
@@ -1940,20 +1881,18 @@ class _PerceptualLoss(torch.autograd.Function):
         ws1 = _pc_stem(w1, C)
         b1, b2, b3 = _flat(b1.detach()), _flat(b2.detach()), _flat(b3.detach())
         a1 = empty_nhwc(2 * M, 64, H, W, sr)                       # conv1_1 + ReLU
-        _lib.check(L.vqw_percep_stem_fwd(_p(sr), _p(hr), _p(ws1), _p(b1), _p(win), _p(a1), N, nwin, C, H, W, _st()),
-                   "vqw_percep_stem_fwd")
+        L.vqw_percep_stem_fwd(sr, hr, ws1, b1, win, a1, N, nwin, C, H, W)
         r12 = empty_nhwc(2 * M, 64, H, W, sr)                      # conv1_2 + ReLU: direct form (ties of the pool behind it)
-        _lib.check(L.vqw_conv2d_fwd(_p(a1), 64, 0, None, 0, _p(_pc_ohwi(w2)), _p(b2), _p(r12), 2 * M, H, W, 64, 3, 1, 1, _st()),
-                   "vqw_conv2d_fwd")
+        L.vqw_conv2d_fwd(a1, 64, 0, None, 0, _pc_ohwi(w2), b2, r12, 2 * M, H, W, 64, 3, 1, 1)
         p1 = empty_nhwc(2 * M, 64, h, w, sr)
-        _lib.check(L.vqw_maxpool2_fwd(_p(r12), _p(p1), 2 * M, H, W, 64, _st()), "vqw_maxpool2_fwd")
+        L.vqw_maxpool2_fwd(r12, p1, 2 * M, H, W, 64)
         a2 = _pc_conv(L, p1, w3, b3, 64, 128, 2 * M, h, w, True)  # conv2_1 + ReLU
         d = empty_nhwc(M, 128, h, w, sr)
-        _lib.check(L.vqw_percep_diff(_p(a2), _p(d), d.numel(), _st()), "vqw_percep_diff")
+        L.vqw_percep_diff(a2, d, d.numel())
         y = _pc_conv(L, d, w4, None, 128, 128, M, h, w, False)    # conv2_2 before its ReLU: vgg(sr) - vgg(hr)
         loss = torch.empty(nwin, dtype=torch.float32, device=sr.device)
         lws = _ws(L.vqw_percep_loss_ws_bytes(nwin), sr)
-        _lib.check(L.vqw_percep_loss_fwd(_p(y), _p(loss), _p(lws), lws.numel(), nwin, N * 128 * h * w, _st()), "vqw_percep_loss_fwd")
+        L.vqw_percep_loss_fwd(y, loss, lws, lws.numel(), nwin, N * 128 * h * w)
         ctx.save_for_backward(sr, a1[:M], r12[:M], p1[:M], a2[:M], y)
         ctx.weights = (w1, w2, w3, w4)
         ctx.win = win
@@ -1972,15 +1911,15 @@ class _PerceptualLoss(torch.autograd.Function):
         L = _L()
         dz2 = _pc_dgrad(L, y, w4, a2, 128, 128, M, h, w)           # conv2_2^T, ReLU of conv2_1
         dp1 = _pc_dgrad(L, dz2, w3, None, 64, 128, M, h, w)        # conv2_1^T
-        _lib.check(L.vqw_relu_bwd(_p(p1), _p(dp1), _p(dp1), dp1.numel(), _st()), "vqw_relu_bwd")   # ReLU of conv1_2, pooled
+        L.vqw_relu_bwd(p1, dp1, dp1, dp1.numel())   # ReLU of conv1_2, pooled
         dr12 = empty_nhwc(M, 64, H, W, sr)
-        _lib.check(L.vqw_maxpool2_bwd(_p(r12), _p(dp1), None, _p(dr12), M, H, W, 64, _st()), "vqw_maxpool2_bwd")
+        L.vqw_maxpool2_bwd(r12, dp1, None, dr12, M, H, W, 64)
         dz1 = _pc_dgrad(L, dr12, w2, a1, 64, 64, M, H, W)          # conv1_2^T, ReLU of conv1_1
         gs = [g.contiguous() for g in gl]
         gs += [None] * (3 - len(gs))
         gsr = torch.empty_like(sr, memory_format=CL)
-        _lib.check(L.vqw_percep_stem_bwd(_p(sr), _p(_pc_stem(w1, C)), _p(ctx.win), _p(gs[0]), _p(gs[1]), _p(gs[2]), _p(dz1),
-                                         _p(gsr), N, nwin, C, H, W, N * 128 * h * w, _st()), "vqw_percep_stem_bwd")
+        L.vqw_percep_stem_bwd(sr, _pc_stem(w1, C), ctx.win, gs[0], gs[1], gs[2],
+                              dz1, gsr, N, nwin, C, H, W, N * 128 * h * w)
         return (gsr,) + none[1:]
 
 
@@ -2057,7 +1996,7 @@ def _metrics_launch(pred, target, ids, dict_size, data_range, kernel_size, sigma
     ws = _ws(L.vqw_recon_metrics_ws_bytes(N, C, H, W, K), like)
     dr = float(data_range) if data_range is not None else 0.0
     L.vqw_recon_metrics(pred, target, ids, out, counts, ws, ws.numel(), N, C, H, W, ids.numel() if ids is not None else 0,
-                        K, int(kernel_size), float(sigma), float(k1), float(k2), dr, _st())
+                        K, int(kernel_size), float(sigma), float(k1), float(k2), dr)
     return out
 
 
@@ -2153,7 +2092,7 @@ def code_entropy(ids, dict_size):
     counts = torch.empty(K + 1, dtype=torch.int64, device=ids.device)
     L = _L()
     ws = _ws(L.vqw_recon_metrics_ws_bytes(0, 0, 0, 0, K), ids)
-    L.vqw_code_entropy(ids, out, counts, ws, ws.numel(), ids.numel(), K, _st())
+    L.vqw_code_entropy(ids, out, counts, ws, ws.numel(), ids.numel(), K)
     _check_ids(out.cpu().tolist(), "code_entropy")
     return out[METRIC_SLOTS.index("entropy")], counts
 
@@ -2175,7 +2114,7 @@ class _WeightedSum(torch.autograd.Function):
         else:
             ptrs = torch.tensor([t.data_ptr() for t in terms], dtype=torch.int64).to(dev)
             w = torch.tensor(list(weights), dtype=torch.float32).to(dev)
-            _lib.check(_L().vqw_weighted_sum(_p(ptrs), _p(w), len(terms), _p(out), _st()), "vqw_weighted_sum")
+            _L().vqw_weighted_sum(ptrs, w, len(terms), out)
         ctx.weights = list(weights)
         ctx.keep = terms
         return out
@@ -2189,7 +2128,7 @@ class _WeightedSum(torch.autograd.Function):
                 continue
             o = torch.empty((), dtype=torch.float32, device=g.device)
             gc = g.contiguous()
-            _lib.check(_L().vqw_affine(_p(gc), _p(o), float(wgt), 0.0, 1, _st()), "vqw_affine")
+            _L().vqw_affine(gc, o, float(wgt), 0.0, 1)
             gs.append(o)
         return (None, *gs)
 
@@ -2221,8 +2160,7 @@ class _VQ(torch.autograd.Function):
         if not (embed.is_contiguous() and cluster_size.is_contiguous() and embed_avg.is_contiguous()):
             raise RuntimeError("VQ buffers must be contiguous")
         cur = _order_begin(embed)        # the codebook read AND its EMA update stay in program order across streams
-        _lib.check(L.vqw_vq_fwd(_p(x), _p(embed), _p(ids), int(id_base), _p(q), _p(commit), _p(stats), _p(ws), ws.numel(), npix, D, K, _st()),
-                   "vqw_vq_fwd")
+        L.vqw_vq_fwd(x, embed, ids, int(id_base), q, commit, stats, ws, ws.numel(), npix, D, K)
         if training:
             scale = 1.0
             if _dist_on() and dist_mode != "local":
@@ -2235,8 +2173,7 @@ class _VQ(torch.autograd.Function):
                     scale = 1.0 / dist.get_world_size()
                 else:
                     raise RuntimeError("unknown VQ dist_mode %r" % dist_mode)
-            _lib.check(L.vqw_vq_ema_update(_p(stats), _p(embed), _p(cluster_size), _p(embed_avg), momentum, eps, scale, D, K, _st()),
-                       "vqw_vq_ema_update")
+            L.vqw_vq_ema_update(stats, embed, cluster_size, embed_avg, momentum, eps, scale, D, K)
         _order_end(embed, cur)
         ctx.save_for_backward(x, q)
         ctx.mark_non_differentiable(ids)
@@ -2251,7 +2188,7 @@ class _VQ(torch.autograd.Function):
         gq = nhwc(gq) if gq is not None else None
         gc = gcommit.contiguous() if gcommit is not None else None
         gx = torch.empty_like(x, memory_format=CL)
-        _lib.check(_L().vqw_vq_bwd(_p(x), _p(q), _p(gq), _p(gc), _p(gx), x.numel(), _st()), "vqw_vq_bwd")
+        _L().vqw_vq_bwd(x, q, gq, gc, gx, x.numel())
         return gx, None, None, None, None, None, None, None, None
 
 
@@ -2284,9 +2221,8 @@ def kmeans_codebook(features, dict_size, seed=0, tol=1e-4, max_iter=100, return_
     ws2 = _ws(16 * dict_size, x)
     history = []
     for _ in range(int(max_iter)):
-        _lib.check(L.vqw_vq_fwd(_p(x), _p(centres), _p(ids), 0, _p(q), _p(commit), _p(stats), _p(ws), ws.numel(), P, D, dict_size, _st()),
-                   "vqw_vq_fwd")
-        _lib.check(L.vqw_kmeans_update(_p(stats), _p(centres), _p(shift), _p(ws2), ws2.numel(), D, dict_size, _st()), "vqw_kmeans_update")
+        L.vqw_vq_fwd(x, centres, ids, 0, q, commit, stats, ws, ws.numel(), P, D, dict_size)
+        L.vqw_kmeans_update(stats, centres, shift, ws2, ws2.numel(), D, dict_size)
         sh = shift.tolist()                      # one host sync per iteration of a one-off initialisation
         history.append((float(commit) * D, sh[0], int(sh[1])))       # commit = mean squared distance per element -> per row
         if sh[0] ** 2 < tol:
@@ -2303,8 +2239,7 @@ def vq_lookup(ids, embed, mask=None, scale=None):
     N, H, W = ids.shape
     K, D = embed.shape
     out = empty_nhwc(N, D, H, W, embed)
-    _lib.check(_L().vqw_vq_lookup(_p(ids), _p(embed.contiguous()), _p(mask), _p(scale), _p(out), N * H * W, D, K, _st()),
-               "vqw_vq_lookup")
+    _L().vqw_vq_lookup(ids, embed.contiguous(), mask, scale, out, N * H * W, D, K)
     return out
 
 
@@ -2315,7 +2250,7 @@ def mask_scale(label_map):
     mask = torch.empty(lab.shape, dtype=torch.uint8, device=lab.device)
     ids0 = torch.empty_like(lab)
     scale = torch.empty(1, dtype=torch.float32, device=lab.device)
-    _lib.check(_L().vqw_mask_scale(_p(lab), _p(mask), _p(ids0), _p(scale), lab.numel(), _st()), "vqw_mask_scale")
+    _L().vqw_mask_scale(lab, mask, ids0, scale, lab.numel())
     return mask, ids0, scale
 
 
@@ -2338,14 +2273,12 @@ class _CrossLoss(torch.autograd.Function):
             r = labels_or_r.contiguous()
             if tuple(r.shape) != (B, K, H, W) or r.dtype != torch.float32:
                 raise RuntimeError("cross loss: r_ids must be float (B,K,H,W) = %s, got %s" % ((B, K, H, W), tuple(r.shape)))
-            _lib.check(L.vqw_cross_loss_dense_fwd(_p(e), _p(r), _p(cb), _p(loss), _p(coef), _p(ws), ws.numel(), B, H * W, D, K, _st()),
-                       "vqw_cross_loss_dense_fwd")
+            L.vqw_cross_loss_dense_fwd(e, r, cb, loss, coef, ws, ws.numel(), B, H * W, D, K)
         else:
             r = labels_or_r.contiguous()
             if tuple(r.shape) != (B, H, W) or r.dtype != torch.int32:
                 raise RuntimeError("cross loss: labels must be int32 (B,H,W)")
-            _lib.check(L.vqw_cross_loss_fwd(_p(e), _p(r), _p(cb), _p(loss), _p(coef), _p(ws), ws.numel(), B, H * W, D, K, _st()),
-                       "vqw_cross_loss_fwd")
+            L.vqw_cross_loss_fwd(e, r, cb, loss, coef, ws, ws.numel(), B, H * W, D, K)
         ctx.save_for_backward(e, r, cb, coef)
         ctx.dense = dense
         return loss
@@ -2358,7 +2291,7 @@ class _CrossLoss(torch.autograd.Function):
         g = g.contiguous()
         ge = torch.empty_like(e, memory_format=CL)
         fn = _L().vqw_cross_loss_dense_bwd if ctx.dense else _L().vqw_cross_loss_bwd
-        _lib.check(fn(_p(e), _p(r), _p(cb), _p(coef), _p(g), _p(ge), B, H * W, D, K, _st()), "vqw_cross_loss_bwd")
+        fn(e, r, cb, coef, g, ge, B, H * W, D, K)
         return ge, None, None, None
 
 
@@ -2378,7 +2311,7 @@ def codebook_losses(codebook_kd, margin):
     ld = torch.empty((), dtype=torch.float32, device=cb.device)
     lr = torch.empty((), dtype=torch.float32, device=cb.device)
     ws = _ws(16 * K, cb)
-    _lib.check(_L().vqw_codebook_losses(_p(cb), float(margin), _p(ld), _p(lr), _p(ws), ws.numel(), D, K, _st()), "vqw_codebook_losses")
+    _L().vqw_codebook_losses(cb, float(margin), ld, lr, ws, ws.numel(), D, K)
     return ld, lr
 
 
@@ -2388,7 +2321,7 @@ def onehot(labels, n_classes):
     B = lab.shape[0]
     hw = lab.numel() // B
     out = torch.empty((B, n_classes) + tuple(lab.shape[1:]), dtype=torch.float32, device=lab.device)
-    _lib.check(_L().vqw_onehot(_p(lab), _p(out), B, hw, n_classes, _st()), "vqw_onehot")
+    _L().vqw_onehot(lab, out, B, hw, n_classes)
     return out
 
 
@@ -2398,7 +2331,7 @@ def flip_labels(ids, border=0):
     ids = ids.long().contiguous()
     B, H, W = ids.shape
     out = torch.empty((B, H, W), dtype=torch.int32, device=ids.device)
-    _lib.check(_L().vqw_flip_labels(_p(ids), _p(out), int(border), B, H, W, _st()), "vqw_flip_labels")
+    _L().vqw_flip_labels(ids, out, int(border), B, H, W)
     return out
 
 
@@ -2413,7 +2346,7 @@ def warp_image(x, minv):
     if tuple(minv.shape) != (B, 3, 3):
         raise RuntimeError("warp_image: expected %s matrices, got %s" % ((B, 3, 3), tuple(minv.shape)))
     y = torch.empty_like(x)
-    _lib.check(_L().vqw_warp_image(_p(x), _p(minv), _p(y), B, C, H, W, _st()), "vqw_warp_image")
+    _L().vqw_warp_image(x, minv, y, B, C, H, W)
     return y
 
 
@@ -2428,7 +2361,7 @@ def warp_labels(ids, minv):
     if tuple(minv.shape) != (B, 3, 3):
         raise RuntimeError("warp_labels: expected %s matrices, got %s" % ((B, 3, 3), tuple(minv.shape)))
     out = torch.empty((B, H, W), dtype=torch.int32, device=ids.device)
-    _lib.check(_L().vqw_warp_labels(_p(ids), int(ids.dtype == torch.int64), _p(minv), _p(out), B, H, W, _st()), "vqw_warp_labels")
+    _L().vqw_warp_labels(ids, int(ids.dtype == torch.int64), minv, out, B, H, W)
     return out
 
 
@@ -2444,7 +2377,7 @@ def photometric(x, params, noise=None):
         if noise.shape != x.shape:
             raise RuntimeError("photometric: noise shape %s != %s" % (tuple(noise.shape), tuple(x.shape)))
     y = torch.empty_like(x)
-    _lib.check(_L().vqw_photometric(_p(x), _p(params), _p(noise), _p(y), B, x.numel() // B, _st()), "vqw_photometric")
+    _L().vqw_photometric(x, params, noise, y, B, x.numel() // B)
     return y
 
 
@@ -2458,7 +2391,7 @@ def gauss_blur(x, taps, apply=None):
         if apply.numel() != B:
             raise RuntimeError("gauss_blur: apply must have one entry per sample")
     tmp, y = torch.empty_like(x), torch.empty_like(x)
-    _lib.check(_L().vqw_gauss_blur(_p(x), _p(taps), _p(apply), _p(tmp), _p(y), B, C, H, W, taps.numel(), _st()), "vqw_gauss_blur")
+    _L().vqw_gauss_blur(x, taps, apply, tmp, y, B, C, H, W, taps.numel())
     return y
 
 
@@ -2480,8 +2413,7 @@ class _SConv(torch.autograd.Function):
         y = empty_nhwc(N, Cout, Ho, Wo, x)
         L = _L()
         ws = _ws(L.vqw_sconv_fwd_ws_bytes(N, H, W, Cin, Cout, ks, stride, pad), x)
-        _lib.check(L.vqw_sconv_fwd(_p(x), _p(w), _p(bias), _p(y), _p(ws), ws.numel(), N, H, W, Cin, Cout, ks, stride, pad,
-                                   float(slope), _st()), "vqw_sconv_fwd")
+        L.vqw_sconv_fwd(x, w, bias, y, ws, ws.numel(), N, H, W, Cin, Cout, ks, stride, pad, float(slope))
         ctx.save_for_backward(x, w, y if slope != 1.0 else None)
         ctx.cfg = (stride, pad, float(slope), bias is not None)
         return y
@@ -2496,20 +2428,18 @@ class _SConv(torch.autograd.Function):
         N, _, H, W = x.shape
         if y is not None:
             gm = torch.empty_like(y, memory_format=CL)
-            _lib.check(L.vqw_leaky_relu_bwd(_p(y), _p(gy), _p(gm), slope, gy.numel(), _st()), "vqw_leaky_relu_bwd")
+            L.vqw_leaky_relu_bwd(y, gy, gm, slope, gy.numel())
             gy = gm
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x, memory_format=CL)
             ws = _ws(L.vqw_sconv_dgrad_ws_bytes(N, H, W, Cin, Cout, ks, stride, pad), gy)
-            _lib.check(L.vqw_sconv_dgrad(_p(gy), _p(w), _p(gx), _p(ws), ws.numel(), N, H, W, Cin, Cout, ks, stride, pad, _st()),
-                       "vqw_sconv_dgrad")
+            L.vqw_sconv_dgrad(gy, w, gx, ws, ws.numel(), N, H, W, Cin, Cout, ks, stride, pad)
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             gw = torch.empty((Cout, Cin, ks, ks), dtype=torch.float32, device=gy.device, memory_format=CL)
             gb = torch.empty(Cout, dtype=torch.float32, device=gy.device) if has_bias else None
             ws = _ws(L.vqw_sconv_wgrad_ws_bytes(Cin, Cout, ks, N, H, W, stride, pad), gy)
-            _lib.check(L.vqw_sconv_wgrad(_p(x), _p(gy), _p(gw), _p(gb), _p(ws), ws.numel(), N, H, W, Cin, Cout, ks, stride, pad, 0,
-                                         _st()), "vqw_sconv_wgrad")
+            L.vqw_sconv_wgrad(x, gy, gw, gb, ws, ws.numel(), N, H, W, Cin, Cout, ks, stride, pad, 0)
         return gx, gw, gb, None, None, None
 
 
@@ -2531,20 +2461,19 @@ class _BnLrelu(torch.autograd.Function):
         if training:
             sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
             ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            _lib.check(L.vqw_bn_partial_stats(_p(x), _p(sums), _p(ws), ws.numel(), N, H * W, C, _st()), "vqw_bn_partial_stats")
+            L.vqw_bn_partial_stats(x, sums, ws, ws.numel(), N, H * W, C)
             if sync and _dist_on():
                 _all_reduce(sums)
                 count *= dist.get_world_size()
             cur = _order_begin(running_mean)
-            _lib.check(L.vqw_bn_finalize(_p(sums), count, _p(mr), _p(running_mean), _p(running_var), momentum, eps, C, _st()),
-                       "vqw_bn_finalize")
+            L.vqw_bn_finalize(sums, count, mr, running_mean, running_var, momentum, eps, C)
             if nbt is not None:
                 _bump_counter(nbt)
             _order_end(running_mean, cur)
         else:
-            _lib.check(L.vqw_bn_eval_stats(_p(running_mean), _p(running_var), _p(mr), eps, C, _st()), "vqw_bn_eval_stats")
+            L.vqw_bn_eval_stats(running_mean, running_var, mr, eps, C)
         y = torch.empty_like(x, memory_format=CL)
-        _lib.check(L.vqw_bn_affine_fwd(_p(x), _p(mr), _p(gamma), _p(beta), _p(y), N * H * W, C, float(slope), _st()), "vqw_bn_affine_fwd")
+        L.vqw_bn_affine_fwd(x, mr, gamma, beta, y, N * H * W, C, float(slope))
         ctx.save_for_backward(x, gamma, beta, mr)
         ctx.cfg = (training, float(slope), count, sync)
         return y
@@ -2558,8 +2487,7 @@ class _BnLrelu(torch.autograd.Function):
         gy = nhwc(gy)
         sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
         ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-        _lib.check(L.vqw_bn_affine_bwd_reduce(_p(x), _p(mr), _p(gamma), _p(beta), _p(gy), _p(sums), _p(ws), ws.numel(), N, H * W, C,
-                                              slope, _st()), "vqw_bn_affine_bwd_reduce")
+        L.vqw_bn_affine_bwd_reduce(x, mr, gamma, beta, gy, sums, ws, ws.numel(), N, H * W, C, slope)
         # dgamma / dbeta are this rank's sums (DDP averages parameter gradients); dx needs the global-batch sums
         dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
         dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -2567,13 +2495,12 @@ class _BnLrelu(torch.autograd.Function):
         if training and sync and _dist_on():
             local = sums.clone()
             _all_reduce(sums)
-            _lib.check(L.vqw_bn_affine_bwd_apply(_p(x), _p(mr), _p(gamma), _p(beta), _p(gy), _p(sums), count, _p(gx), None, None,
-                                                 N * H * W, C, slope, 1, 0, _st()), "vqw_bn_affine_bwd_apply")
+            L.vqw_bn_affine_bwd_apply(x, mr, gamma, beta, gy, sums, count, gx, None, None, N * H * W, C, slope, 1, 0)
             dbeta.copy_(local[0::2])
             dgamma.copy_(local[1::2])
         else:
-            _lib.check(L.vqw_bn_affine_bwd_apply(_p(x), _p(mr), _p(gamma), _p(beta), _p(gy), _p(sums), count, _p(gx), _p(dgamma),
-                                                 _p(dbeta), N * H * W, C, slope, int(training), 0, _st()), "vqw_bn_affine_bwd_apply")
+            L.vqw_bn_affine_bwd_apply(x, mr, gamma, beta, gy, sums, count, gx, dgamma, dbeta,
+                                      N * H * W, C, slope, int(training), 0)
         return gx, dgamma, dbeta, None, None, None, None, None, None, None, None
 
 
@@ -2590,7 +2517,7 @@ class _Hinge(torch.autograd.Function):
         _dev(x)
         x = x.contiguous() if not (x.is_contiguous() or x.is_contiguous(memory_format=CL)) else x
         loss = torch.empty((), dtype=torch.float32, device=x.device)
-        _lib.check(_L().vqw_hinge_fwd(_p(x), x.numel(), mode, _p(loss), _st()), "vqw_hinge_fwd")
+        _L().vqw_hinge_fwd(x, x.numel(), mode, loss)
         ctx.save_for_backward(x)
         ctx.mode = mode
         return loss
@@ -2600,7 +2527,7 @@ class _Hinge(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         gx = torch.empty_like(x)
         g = g.contiguous().float()
-        _lib.check(_L().vqw_hinge_bwd(_p(x), x.numel(), ctx.mode, _p(g), _p(gx), _st()), "vqw_hinge_bwd")
+        _L().vqw_hinge_bwd(x, x.numel(), ctx.mode, g, gx)
         return gx, None
 
 
@@ -2639,7 +2566,7 @@ class _PixelShuffle2(torch.autograd.Function):
         if C4 % 4:
             raise RuntimeError("pixel_shuffle(2): channels must be a multiple of 4")
         y = empty_nhwc(N, C4 // 4, 2 * h, 2 * w, x)
-        _lib.check(_L().vqw_pixel_shuffle2(_p(x), _p(y), N, 2 * h, 2 * w, C4 // 4, 0, _st()), "vqw_pixel_shuffle2")
+        _L().vqw_pixel_shuffle2(x, y, N, 2 * h, 2 * w, C4 // 4, 0)
         return y
 
     @staticmethod
@@ -2647,7 +2574,7 @@ class _PixelShuffle2(torch.autograd.Function):
         gy = nhwc(gy)
         N, C, H, W = gy.shape
         gx = empty_nhwc(N, 4 * C, H // 2, W // 2, gy)
-        _lib.check(_L().vqw_pixel_shuffle2(_p(gy), _p(gx), N, H, W, C, 1, _st()), "vqw_pixel_shuffle2")
+        _L().vqw_pixel_shuffle2(gy, gx, N, H, W, C, 1)
         return gx
 
 
@@ -2662,7 +2589,7 @@ def dropblock_mask(seed_mask, block_size):
     B, H, W = seed.shape
     keep = torch.empty_like(seed)
     scale = torch.empty(1, dtype=torch.float32, device=seed.device)
-    _lib.check(_L().vqw_dropblock_mask(_p(seed), _p(keep), _p(scale), B, H, W, int(block_size), _st()), "vqw_dropblock_mask")
+    _L().vqw_dropblock_mask(seed, keep, scale, B, H, W, int(block_size))
     return keep, scale
 
 
@@ -2673,7 +2600,7 @@ class _DropBlockApply(torch.autograd.Function):
         x = nhwc(x)
         N, C, H, W = x.shape
         y = torch.empty_like(x, memory_format=CL)
-        _lib.check(_L().vqw_dropblock_apply(_p(x), _p(keep), _p(scale), _p(y), N * H * W, C, _st()), "vqw_dropblock_apply")
+        _L().vqw_dropblock_apply(x, keep, scale, y, N * H * W, C)
         ctx.save_for_backward(keep, scale)
         return y
 
@@ -2683,7 +2610,7 @@ class _DropBlockApply(torch.autograd.Function):
         gy = nhwc(gy)
         N, C, H, W = gy.shape
         gx = torch.empty_like(gy, memory_format=CL)
-        _lib.check(_L().vqw_dropblock_apply(_p(gy), _p(keep), _p(scale), _p(gx), N * H * W, C, _st()), "vqw_dropblock_apply")
+        _L().vqw_dropblock_apply(gy, keep, scale, gx, N * H * W, C)
         return gx, None, None
 
 
@@ -2705,8 +2632,7 @@ class _SegLosses(torch.autograd.Function):
         out = torch.empty(2, dtype=torch.float32, device=z.device)
         sums = torch.empty(2 * C + 2, dtype=torch.float64, device=z.device)
         ws = _ws(L.vqw_seg_ws_bytes(C), z)
-        _lib.check(L.vqw_seg_losses_fwd(_p(z), _p(t), _p(out), _p(sums), _p(ws), ws.numel(), B, HW, C, ignore_index, smooth, gamma,
-                                        eps, _st()), "vqw_seg_losses_fwd")
+        L.vqw_seg_losses_fwd(z, t, out, sums, ws, ws.numel(), B, HW, C, ignore_index, smooth, gamma, eps)
         ctx.save_for_backward(z, t, sums)
         ctx.cfg = (ignore_index, smooth, gamma, eps)
         return out[0], out[1]
@@ -2720,8 +2646,7 @@ class _SegLosses(torch.autograd.Function):
         gz = torch.empty_like(z)
         gd = g_dice.contiguous() if g_dice is not None else None
         gf = g_focal.contiguous() if g_focal is not None else None
-        _lib.check(_L().vqw_seg_losses_bwd(_p(z), _p(t), _p(sums), _p(gd), _p(gf), _p(gz), B, HW, C, ignore_index, smooth, gamma,
-                                           eps, _st()), "vqw_seg_losses_bwd")
+        _L().vqw_seg_losses_bwd(z, t, sums, gd, gf, gz, B, HW, C, ignore_index, smooth, gamma, eps)
         return gz, None, None, None, None, None
 
 

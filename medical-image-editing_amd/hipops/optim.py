@@ -4,13 +4,11 @@ Drop-in for the `torch.optim.Adam(params, lr, betas, weight_decay)` instances th
 reference builds in trainers/base.py:165-175: same constructor arguments, same update
 rule, same state_dict layout ('step', 'exp_avg', 'exp_avg_sq' per parameter).
 """
-import ctypes
 import os
 
 import numpy as np
 import torch
 
-from . import _lib
 from . import ops as _ops
 
 
@@ -61,10 +59,10 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L, st = _ops._L(), _ops._st()         # torch.ops.vqw.adam_step / adam_multi (hipops/library.py)
+        L = _ops._L()         # torch.ops.vqw.adam_step / adam_multi (hipops/library.py)
         for group in self.param_groups:
             b1, b2 = group["betas"]
-            if MULTI_TENSOR and self._step_multi(L, st, group):
+            if MULTI_TENSOR and self._step_multi(L, group):
                 continue
             for p in group["params"]:
                 if p.grad is None:
@@ -85,13 +83,12 @@ class Adam(torch.optim.Optimizer):
                 m, v = state["exp_avg"], state["exp_avg_sq"]
                 if not (_same_layout(m, p) and _same_layout(v, p)):
                     raise RuntimeError("Adam state layout does not match the parameter layout")
-                _lib.check(L.vqw_adam_step(_ops._p(p), _ops._p(g), _ops._p(m), _ops._p(v), p.numel(),
-                                           group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                                           1.0 - b1 ** t, 1.0 - b2 ** t, st), "vqw_adam_step")
+                L.vqw_adam_step(p, g, m, v, p.numel(), group["lr"], b1, b2, group["eps"],
+                                group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t)
         _ops.bump_weight_epoch()      # parameters changed through raw pointers: invalidate derived weight layouts
         return loss
 
-    def _step_multi(self, L, st, group):
+    def _step_multi(self, L, group):
         """All tensors of the group in one launch.  Falls back (returns False) when the tensors do not share a step
         count or a gradient needs a layout copy; the per-tensor path then handles the group."""
         params = [p for p in group["params"] if p.grad is not None]
@@ -141,7 +138,7 @@ class Adam(torch.optim.Optimizer):
         table = slot[0].to(dev, non_blocking=True).view(arr.shape)
         slot[1].record(torch.cuda.current_stream())
         b1, b2 = group["betas"]
-        _lib.check(L.vqw_adam_multi(_ops._p(table), len(rows), group["lr"], b1, b2, group["eps"],
-                                    group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t, st), "vqw_adam_multi")
+        L.vqw_adam_multi(table, len(rows), group["lr"], b1, b2, group["eps"],
+                         group["weight_decay"], 1.0 - b1 ** t, 1.0 - b2 ** t)
         table.record_stream(torch.cuda.current_stream())
         return True

@@ -2354,8 +2354,7 @@ def test_gradient_group_sums_branch_gradients_in_place():
         y0 = torch.randn(2, 32, 40, 64, device=DEV).contiguous(memory_format=torch.channels_last)
         want = y0 + ops.conv2d(x, w, dilation=d)
         got = y0.clone(memory_format=torch.channels_last)
-        from hipops import _lib
-        _lib.check(L.vqw_conv2d_fwd_acc(ops._p(ops.nhwc(x)), 32, ops._p(w), ops._p(got), 2, 40, 64, 32, 3, d, ops._st()), "acc")
+        L.vqw_conv2d_fwd_acc(ops.nhwc(x), 32, w, got, 2, 40, 64, 32, 3, d)
         torch.cuda.synchronize()
         assert_close(got, want, 1e-6, "y0 + conv, dilation %d" % d)
 

@@ -32,6 +32,23 @@ def test_cabi_exports_every_declared_symbol():
     assert L.vqw_vq_ws_bytes(1024, 16, 10) > 0
 
 
+def test_ctypes_prototypes_derived_from_header(tmp_path):
+    """_lib.SIGNATURES is read from include/vqwnet_hip.h: each C type maps to the ctypes type of its width, an unknown
+    C type raises instead of being truncated."""
+    from hipops import _lib
+    P, I, F, D, SZ, LG = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_long
+    assert _lib.SIGNATURES["vqw_bn_finalize"] == (I, [P, D, P, P, P, F, F, I, P])
+    assert _lib.SIGNATURES["vqw_vq_fwd"] == (I, [P, P, P, I, P, P, P, P, SZ, LG, I, I, P])
+    assert _lib.SIGNATURES["vqw_vq_ws_bytes"] == (SZ, [LG, I, I])
+    assert _lib.SIGNATURES["vqw_profile_families"] == (I, [ctypes.c_uint])
+    assert _lib.SIGNATURES["vqw_last_error"] == (ctypes.c_char_p, [])
+    hdr = tmp_path / "vqw.h"
+    for bad in ("int vqw_bad(int8_t n, void* stream);", "int vqw_bad(unsigned long n);", "float* vqw_bad(void);"):
+        hdr.write_text(bad + "\n")
+        with pytest.raises(RuntimeError, match="vqw_bad"):
+            _lib.signatures(str(hdr))
+
+
 def test_no_cpu_fallback():
     from hipops import ops
     from networks import blocks
@@ -115,6 +132,8 @@ def test_dispatcher_registration_matches_header():
     assert set(protos) == set(_lib.SIGNATURES)
     kernels = {n for n, (r, a) in protos.items() if a and a[-1][0] == "stream" and not n.endswith("_host")}
     assert set(ops) == kernels and len(kernels) >= 70
+    from hipops.ops import _L        # a kernel is its operator; a host query is the C function
+    assert _L().vqw_add is torch.ops.vqw.add.default and _L().vqw_plane_ws_bytes is _lib.load().vqw_plane_ws_bytes
     sch = str(torch.ops.vqw.vq_ema_update.default._schema)
     assert "Tensor(a!)? embed" in sch and "Tensor(b!)? cluster_size" in sch and "Tensor(c!)? embed_avg" in sch and "Tensor? stats" in sch
     sch = str(torch.ops.vqw.conv2d_fwd.default._schema)
