@@ -484,6 +484,48 @@ int vqw_percep_loss_fwd(const float* y, float* loss, void* ws, size_t ws_bytes, 
 int vqw_percep_stem_bwd(const float* sr, const float* w, const float* win, const float* g0, const float* g1, const float* g2,
                         const float* dz1, float* gsr, int N, int nwin, int Cin, int H, int W, long numel, void* stream);
 
+/* ---- LPIPS perceptual loss, lpips.LPIPS(net='alex') v0.1 with its defaults (the reference's LPIPSLoss,
+ *      functions/lpips_loss.py, trainers/base.py:271-275).  Added functions only; the ABI stays 9.
+ * One batch of 2M = 2 * nwin * N images as for the VGG loss: the sr half [nwin][N] first, then the hr half.  Front end:
+ * scaling layer + conv 11x11/4 pad 2 (3 -> 64) + ReLU [tap 0]; max-pool 3/2; conv 5x5 pad 2 (64 -> 192) + ReLU [tap 1];
+ * max-pool 3/2; three 3x3 layers (192 -> 384 -> 256 -> 256, each + ReLU) [taps 2..4] on the stock 3x3 entry points.  All
+ * tensors NHWC fp32; every sum has one fixed order (bit-deterministic; equal neighbourhoods give bit-equal outputs).
+ * ..._supported: 0 when a shape is not served (Cin not 1 or 3, H or W below 31: the second pool needs a 3-wide map).
+ * stem: wp = [planes][121][64] weights (tap = ky * 11 + kx).  Cin = 3: the three input channels' weights, and
+ * sc = shift[3], scale[3] of the scaling layer (x - shift) / scale, applied on load with zero padding after it.  Cin = 1
+ * (expand() feeds one value to all three): planes (wA, wB) = (sum_c w_c / scale_c, -sum_c w_c shift_c / scale_c), wB
+ * counting for in-bounds taps only, and cint[64] = wB summed over the 121 taps in tap order in fp32 (what the kernel's own
+ * sum gives where every tap is in bounds).  win: as in vqw_percep_stem_fwd.  f1: [2M,Ho,Wo,64], Ho = (H - 7) / 4 + 1. */
+int vqw_lpips_supported(int N, int Cin, int H, int W);
+int vqw_lpips_stem_fwd(const float* sr, const float* hr, const float* wp, const float* cint, const float* sc, const float* bias,
+                       const float* win, float* f1, int N, int nwin, int Cin, int H, int W, void* stream);
+/* gsr = sum_w g_w * win_w'(sr) / scale * conv11x11/4^T(dz1[w], wp): the stem's input gradient.  dz1: [nwin * N,Ho,Wo,64], the
+ * gradient in front of the stem's ReLU (sr half) for a unit loss gradient; g0 .. g2: the incoming gradient of each window's
+ * loss (device scalars; unused ones may be NULL).  win' as in vqw_percep_stem_bwd. */
+int vqw_lpips_stem_bwd(const float* sr, const float* wp, const float* sc, const float* win, const float* g0, const float* g1,
+                       const float* g2, const float* dz1, float* gsr, int N, int nwin, int Cin, int H, int W, void* stream);
+/* MaxPool2d(3, stride 2), floor mode: y [N,(H-3)/2+1,(W-3)/2+1,C], C % 4 == 0.  Backward as a gather: gx = [x > 0] * the
+ * gradients of the windows whose first row-major maximum (ATen's rule) the pixel is (x = the ReLU output that was pooled). */
+int vqw_lpips_pool_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
+int vqw_lpips_pool_bwd(const float* x, const float* gy, float* gx, int N, int H, int W, int C, void* stream);
+/* 5x5 padding-2 convolution (+ bias, ReLU with relu = 1) on the implicit-GEMM matrix-core kernel; w_ohwi [Cout][5][5][Cin].
+ * The input gradient is the same call on dY with vqw_pack_dgrad_weights(.., 5) weights, Cin / Cout swapped. */
+int vqw_lpips_conv5_supported(int Cin, int Cout, int N, int H, int W);
+int vqw_lpips_conv5_fwd(const float* x, const float* w_ohwi, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                        int relu, void* stream);
+/* Tap distance.  f: [2M,HW,C] (C in 64, 192, 384, 256), lw: [C] lin weights.  Per pixel a = f / (|f| + 1e-10), b likewise
+ * from the hr half, d = sum_c lw_c (a_c - b_c)^2; ..._dist_fwd leaves tap `tap`'s double partials per image in ws, and
+ * ..._loss_fold (after all five taps) loss[w] = sum_tap sum_n mean_pixels d / N, hw0 .. hw4 = the taps' pixel counts.
+ * ..._dist_bwd: gout = [f > 0] * (gin + d(mean d_tap / N)/df) for a unit loss gradient on the sr half [M,HW,C]; the distance
+ * term is zero at a pixel whose features are all zero; gin: the gradient from the deeper tap, NULL at the last, may be gout. */
+size_t vqw_lpips_ws_bytes(int N, int nwin);
+int vqw_lpips_dist_fwd(const float* f, const float* lw, void* ws, size_t ws_bytes, int tap, int N, int nwin, int HW, int C,
+                       void* stream);
+int vqw_lpips_loss_fold(const void* ws, size_t ws_bytes, float* loss, int N, int nwin, int hw0, int hw1, int hw2, int hw3,
+                        int hw4, void* stream);
+int vqw_lpips_dist_bwd(const float* f, const float* lw, const float* gin, float* gout, int N, int nwin, int HW, int C,
+                       void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

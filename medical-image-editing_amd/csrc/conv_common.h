@@ -181,6 +181,8 @@ int conv_k4s2_wgrad(const float* x_high, const float* gy_low, float* dw, float* 
                     hipStream_t st);
 int conv_k4s1_grid(const float* src, const float* w16, const float* bias, float* dst, int N, int H, int W, int Csrc, int Cdst,
                    int tap0, hipStream_t st);
+int conv_k5_grid(const float* src, const float* w25, const float* bias, float* dst, int N, int H, int W, int Csrc, int Cdst,
+                 int relu, hipStream_t st);
 size_t conv_k4s1_wgrad_ws_floats(int Cin, int Cout, long P);
 int conv_k4s1_wgrad_grid(const float* x, const float* dy_grid, float* dw, float* ws, int N, int H, int W, int Cin, int Cout, int acc,
                          hipStream_t st);

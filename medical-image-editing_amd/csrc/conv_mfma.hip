@@ -34,7 +34,7 @@ __device__ __forceinline__ float4 ld4_or_zero(const float* p, bool ok) {
 struct ConvGeom {
     int ntaps;
     int src_mode, out_mode, py, px;
-    signed char dy[16], dx[16];
+    signed char dy[25], dx[25];
 };
 
 // =============================================================================================
@@ -511,6 +511,13 @@ int conv_k4s1_grid(const float* src, const float* w16, const float* bias, float*
                    int tap0, hipStream_t st) {
     ConvIn in{src, nullptr, Csrc, 0, 0};
     return dispatch_fwd(in, w16, bias, dst, N, H, W, Cdst, plain_geom(4, 1, tap0), 0, st);
+}
+// 5x5 padding-2 convolution (the LPIPS AlexNet front end's second layer, lpips.hip): the 25-tap table; the input gradient is
+// the same call with the flipped, transposed weights
+int conv_k5_grid(const float* src, const float* w25, const float* bias, float* dst, int N, int H, int W, int Csrc, int Cdst,
+                 int relu, hipStream_t st) {
+    ConvIn in{src, nullptr, Csrc, 0, 0};
+    return dispatch_fwd(in, w25, bias, dst, N, H, W, Cdst, plain_geom(5, 1), relu, st);
 }
 
 // =============================================================================================

@@ -5,4 +5,5 @@ from .seg_loss import SoftDiceLoss, FocalLoss  # noqa: F401
 from .gan_loss import hinge_d_loss, generator_loss  # noqa: F401
 from .freq_loss import FocalFrequencyLoss  # noqa: F401
 from .perceptual_loss import VGGLoss  # noqa: F401
+from .lpips_loss import LPIPSLoss  # noqa: F401
 from .metrics import MeanSquaredError, StructuralSimilarityIndexMeasure, PeakSignalNoiseRatio, label_entropy  # noqa: F401

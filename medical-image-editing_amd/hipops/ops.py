@@ -1942,6 +1942,160 @@ def perceptual_loss(sr, hr, w1, b1, w2, b2, w3, b3, w4, b4, window=None, windows
     return out if single or isinstance(out, tuple) else (out,)
 
 
+# ----------------------------------------------------------------------------------------------
+# LPIPS perceptual loss (functions/lpips_loss.py: lpips.LPIPS(net='alex') v0.1, csrc/lpips.hip)
+# ----------------------------------------------------------------------------------------------
+LPIPS_CHANNELS = (64, 192, 384, 256, 256)      # the five taps
+
+
+def lpips_map_sizes(H, W):
+    """((h, w) of taps 0..4) for an H x W input: conv 11/4 pad 2, pool 3/2, (5x5 same), pool 3/2, (3x3 same) x 3."""
+    s0 = ((H - 7) // 4 + 1, (W - 7) // 4 + 1)
+    s1 = ((s0[0] - 3) // 2 + 1, (s0[1] - 3) // 2 + 1)
+    s2 = ((s1[0] - 3) // 2 + 1, (s1[1] - 3) // 2 + 1)
+    return (s0, s1, s2, s2, s2)
+
+
+def _lp_stem(w1, shift, scale, C):
+    """(wp, cint, sc) of vqw_lpips_stem_fwd for a C-channel input, built in double from the [64,3,11,11] weight and the
+    scaling layer's buffers and kept while they are unchanged."""
+    def _build():
+        w = w1.detach().double()
+        sh, sc = shift.detach().double().reshape(3), scale.detach().double().reshape(3)
+        if C == 3:
+            wp = w.permute(1, 2, 3, 0).reshape(3, 121, 64).float().contiguous()
+            return wp, None, torch.cat([sh, sc]).float().contiguous()
+        wa = (w / sc.view(1, 3, 1, 1)).sum(1)
+        wb = -(w * (sh / sc).view(1, 3, 1, 1)).sum(1)
+        wp = torch.stack([wa, wb]).permute(0, 2, 3, 1).reshape(2, 121, 64).float().contiguous()
+        rows = wp[1].cpu()
+        cint = torch.zeros(64, dtype=torch.float32)
+        for t in range(121):                      # the kernel's own order: one fp32 add per tap
+            cint = cint + rows[t]
+        return wp, cint.to(w1.device), None
+    return _cached(w1, "lp_stem%d" % C, _build, deps=(shift, scale))
+
+
+def _lp_lin(lw):
+    return _cached(lw, "lp_lin", lambda: lw.detach().float().reshape(-1).contiguous())
+
+
+def _lp_dgrad5(L, w, Cin, Cout):
+    def _pack():
+        buf = torch.empty(Cin * 25 * Cout, dtype=torch.float32, device=w.device)
+        L.vqw_pack_dgrad_weights(_pc_ohwi(w), buf, Cout, Cin, 5)
+        return buf
+    return _cached(w, "lp_dgrad5", _pack)
+
+
+class _LpipsLoss(torch.autograd.Function):
+    """Outputs: one 0-dim loss per window.  The batch of every launch is 2M = 2 * nwin * N images, the sr half first."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, windows, *params):
+        w1, b1, w2, b2, w3, b3, w4, b4, w5, b5 = params[:10]
+        lins, shift, scale = params[10:15], params[15], params[16]
+        _dev(sr, hr)
+        sr, hr = nhwc(sr), nhwc(hr)
+        if sr.shape != hr.shape:
+            raise RuntimeError("lpips_loss: shape mismatch %s vs %s" % (tuple(sr.shape), tuple(hr.shape)))
+        N, C, H, W = sr.shape
+        L = _L()
+        if C not in (1, 3) or not L.vqw_lpips_supported(N, C, H, W):
+            raise RuntimeError("lpips_loss: input (N, C, H, W) = %s is not served: C must be 1 or 3 (the reference expands "
+                               "to 3 channels) and H, W at least 31 (the second max-pool needs a 3-wide map)"
+                               % (tuple(sr.shape),))
+        nwin = len(windows)
+        M = nwin * N
+        sizes = lpips_map_sizes(H, W)
+        win = _window_table(windows, sr) if any(x is not None for x in windows) or nwin > 1 else None
+        wp, cint, sc = _lp_stem(w1, shift, scale, C)
+        (h0, w0), (h1, w1_), (h2, w2_) = sizes[0], sizes[1], sizes[2]
+        if not L.vqw_lpips_conv5_supported(64, 192, 2 * M, h1, w1_):
+            raise RuntimeError("lpips_loss: batch of %d images of %d x %d is too large for one launch" % (2 * M, H, W))
+        f0 = empty_nhwc(2 * M, 64, h0, w0, sr)
+        L.vqw_lpips_stem_fwd(sr, hr, wp, cint, sc, _flat(b1.detach()), win, f0, N, nwin, C, H, W)
+        p0 = empty_nhwc(2 * M, 64, h1, w1_, sr)
+        L.vqw_lpips_pool_fwd(f0, p0, 2 * M, h0, w0, 64)
+        f1 = empty_nhwc(2 * M, 192, h1, w1_, sr)
+        L.vqw_lpips_conv5_fwd(p0, _pc_ohwi(w2), _flat(b2.detach()), f1, 2 * M, h1, w1_, 64, 192, 1)
+        p1 = empty_nhwc(2 * M, 192, h2, w2_, sr)
+        L.vqw_lpips_pool_fwd(f1, p1, 2 * M, h1, w1_, 192)
+        f2 = _pc_conv(L, p1, w3, _flat(b3.detach()), 192, 384, 2 * M, h2, w2_, True)
+        f3 = _pc_conv(L, f2, w4, _flat(b4.detach()), 384, 256, 2 * M, h2, w2_, True)
+        f4 = _pc_conv(L, f3, w5, _flat(b5.detach()), 256, 256, 2 * M, h2, w2_, True)
+        feats = (f0, f1, f2, f3, f4)
+        ws = _ws(L.vqw_lpips_ws_bytes(N, nwin), sr)
+        for t, f in enumerate(feats):
+            L.vqw_lpips_dist_fwd(f, _lp_lin(lins[t]), ws, ws.numel(), t, N, nwin, sizes[t][0] * sizes[t][1], LPIPS_CHANNELS[t])
+        loss = torch.empty(nwin, dtype=torch.float32, device=sr.device)
+        L.vqw_lpips_loss_fold(ws, ws.numel(), loss, N, nwin, *[h * w for h, w in sizes])
+        ctx.save_for_backward(sr, *feats)
+        ctx.weights = (w1, w2, w3, w4, w5, lins, shift, scale)
+        ctx.win = win
+        ctx.shape = (N, nwin, C, H, W)
+        return loss[0] if nwin == 1 else tuple(loss.unbind())
+
+    @staticmethod
+    def backward(ctx, *gl):
+        N, nwin, C, H, W = ctx.shape
+        none = (None,) * 20
+        if not ctx.needs_input_grad[0]:
+            return none
+        sr, f0, f1, f2, f3, f4 = ctx.saved_tensors
+        w1, w2, w3, w4, w5, lins, shift, scale = ctx.weights
+        M = nwin * N
+        sizes = lpips_map_sizes(H, W)
+        (h0, w0), (h1, w1_), (h2, w2_) = sizes[0], sizes[1], sizes[2]
+        hw2 = h2 * w2_
+        L = _L()
+        # each tap: its own distance gradient + the gradient from the deeper tap, masked by its ReLU, in one launch
+        dz4 = empty_nhwc(M, 256, h2, w2_, sr)
+        L.vqw_lpips_dist_bwd(f4, _lp_lin(lins[4]), None, dz4, N, nwin, hw2, 256)
+        g3 = _pc_dgrad(L, dz4, w5, None, 256, 256, M, h2, w2_)
+        L.vqw_lpips_dist_bwd(f3, _lp_lin(lins[3]), g3, g3, N, nwin, hw2, 256)
+        g2 = _pc_dgrad(L, g3, w4, None, 384, 256, M, h2, w2_)
+        L.vqw_lpips_dist_bwd(f2, _lp_lin(lins[2]), g2, g2, N, nwin, hw2, 384)
+        gp1 = _pc_dgrad(L, g2, w3, None, 192, 384, M, h2, w2_)
+        g1 = empty_nhwc(M, 192, h1, w1_, sr)
+        L.vqw_lpips_pool_bwd(f1, gp1, g1, M, h1, w1_, 192)
+        L.vqw_lpips_dist_bwd(f1, _lp_lin(lins[1]), g1, g1, N, nwin, h1 * w1_, 192)
+        gp0 = empty_nhwc(M, 64, h1, w1_, sr)
+        L.vqw_lpips_conv5_fwd(g1, _lp_dgrad5(L, w2, 64, 192), None, gp0, M, h1, w1_, 192, 64, 0)
+        g0 = empty_nhwc(M, 64, h0, w0, sr)
+        L.vqw_lpips_pool_bwd(f0, gp0, g0, M, h0, w0, 64)
+        L.vqw_lpips_dist_bwd(f0, _lp_lin(lins[0]), g0, g0, N, nwin, h0 * w0, 64)
+        gs = [g.contiguous() for g in gl]
+        gs += [None] * (3 - len(gs))
+        wp, _, sc = _lp_stem(w1, shift, scale, C)
+        gsr = torch.empty_like(sr, memory_format=CL)
+        L.vqw_lpips_stem_bwd(sr, wp, sc, ctx.win, gs[0], gs[1], gs[2], g0, gsr, N, nwin, C, H, W)
+        return (gsr,) + none[1:]
+
+
+def lpips_loss(sr, hr, params, window=None, windows=None):
+    """lpips.LPIPS(net='alex') v0.1 (linear layers on, spatial=False, eval mode, normalize=False) of sr against hr, mean over
+    the batch: the reference's LPIPSLoss.  params: (w1, b1, ..., w5, b5, lin0, ..., lin4, shift, scale) - the five
+    convolutions of alexnet.features (OIHW: [64,3,11,11], [192,64,5,5], [384,192,3,3], [256,384,3,3], [256,256,3,3]) with
+    their biases, the five 1x1 lin weights ([1,C,1,1], no bias) and the scaling layer's shift / scale ([1,3,1,1]).  Inputs are
+    (N, 1 or 3, H, W) in [-1, 1] with H, W >= 31; a 1-channel input stands for its expand() to 3.  The gradient flows to sr
+    only; hr and the parameters get none.  At a pixel whose tap features are all zero the normalisation contributes a zero
+    gradient (autograd through sqrt gives NaN there, which the ReLU's backward then discards).  window / windows: as in `perceptual_loss`."""
+    single = windows is None
+    if single:
+        windows = (window,)
+    elif window is not None:
+        raise RuntimeError("lpips_loss: pass window or windows, not both")
+    windows = tuple(None if x is None else tuple(float(v) for v in x) for x in windows)
+    if not 1 <= len(windows) <= 3 or any(x is not None and len(x) != 4 for x in windows):
+        raise RuntimeError("lpips_loss: one to three windows, each the (alpha, beta, lo, hi) of window_map")
+    params = tuple(params)
+    if len(params) != 17:
+        raise RuntimeError("lpips_loss: params must be the 17 tensors (w1, b1, ..., w5, b5, lin0 .. lin4, shift, scale)")
+    out = _LpipsLoss.apply(sr, hr.detach(), windows, *params)
+    return out if single or isinstance(out, tuple) else (out,)
+
+
 METRIC_SLOTS = ("mse", "ssim", "psnr", "ssim_range", "psnr_range", "sse", "target_min", "target_max", "entropy", "bad_ids",
                 "n_ids")
 _MT_OUT = 16

@@ -12,17 +12,21 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
     config.augmentation.{modules, ...}            (optional: absent -> the exact-integer flip views of the benchmark)
     config.dataset.{window_width, window_center, window_scale}, config.loss.{recon_weights, freq_weights, percep_weights}
                  (multi-window runs, -w)
-    config.loss.{perceptual_loss_type, conv_index, perceptual_weights}   (with use_perceptual_loss)
+    config.loss.{perceptual_loss_type, conv_index, perceptual_weights, lpips_weights}   (with use_perceptual_loss)
 
 The focal frequency loss (use_frequency_loss) is functions.FocalFrequencyLoss, built on HIP kernels in place of the
 third-party focal-frequency-loss package.  The perceptual loss (use_perceptual_loss with perceptual_loss_type 'vgg', the
 reference's VGGLoss()) is functions.VGGLoss on HIP kernels.  The reference downloads its VGG19 weights; this build never
 downloads anything, so `config.loss.perceptual_weights` - a key of this project, not of the reference - names a local
 file: torchvision's vgg19 state dict (vgg19-dcbb9e9d.pth), a VGGLoss state dict or a reference checkpoint of a run with the
-loss on.  Without it a config that switches the loss on raises, as do perceptual_loss_type 'lpips' (the lpips package
-with AlexNet weights) and conv_index '54': neither is built, and nothing silently trains something else.
+loss on.  Without it a config that switches the loss on raises, as does conv_index '54', which is not built: nothing
+silently trains something else.  perceptual_loss_type 'lpips' (the reference's LPIPSLoss(): the lpips package with AlexNet
+weights) is functions.LPIPSLoss on HIP kernels, with its weights named by `config.loss.lpips_weights` - again a key of this
+project: a path to an LPIPS state dict / reference checkpoint, or a two-element list [alexnet-owt-7be5be79.pth, alex.pth]
+(torchvision's AlexNet and the package's weights/v0.1/alex.pth).  Without that key 'lpips' raises in the same way;
+`perceptual_weights` stays the VGG19 file's key.
 """
-from functions import EmbeddingLoss, FocalFrequencyLoss, VGGLoss
+from functions import EmbeddingLoss, FocalFrequencyLoss, LPIPSLoss, VGGLoss
 from hipops import Adam
 from networks import UNetEncoder, UNetDecoder, RandomTransform
 
@@ -94,11 +98,21 @@ def configure_frequency_loss(config):
 
 
 def _perceptual_settings(c):
-    """-> (conv_index, weights path) of a config with use_perceptual_loss; NotImplementedError for what is not built."""
+    """-> ('vgg', conv_index, weights path) or ('lpips', None, weights) of a config with use_perceptual_loss;
+    NotImplementedError for what is not built."""
     kind = _get(c, "perceptual_loss_type") or "vgg"
     if kind == "lpips":
-        raise NotImplementedError("use_perceptual_loss with perceptual_loss_type 'lpips' (the lpips package with AlexNet "
-                                  "weights) is not built; use perceptual_loss_type 'vgg'")
+        weights = _get(c, "lpips_weights")
+        if not weights:
+            raise NotImplementedError("use_perceptual_loss with perceptual_loss_type 'lpips' needs the pretrained LPIPS weights, "
+                                      "which this build never downloads: set config.loss.lpips_weights to a local LPIPS state "
+                                      "dict or reference checkpoint, or to the pair [alexnet-owt-7be5be79.pth, alex.pth] "
+                                      "(config.loss.perceptual_weights names the VGG19 file of the 'vgg' perceptual loss only)")
+        if not isinstance(weights, str):
+            weights = tuple(weights)
+            if len(weights) != 2:
+                raise ValueError("config.loss.lpips_weights: a path, or the two paths [alexnet, lins]")
+        return "lpips", None, weights
     if kind != "vgg":
         raise NotImplementedError("use_perceptual_loss: unknown perceptual_loss_type %r" % (kind,))
     conv_index = str(_get(c, "conv_index") or "22")
@@ -110,17 +124,19 @@ def _perceptual_settings(c):
         raise NotImplementedError("use_perceptual_loss needs the pretrained VGG19 weights, which this build never downloads: "
                                   "set config.loss.perceptual_weights to a local vgg19 state dict (vgg19-dcbb9e9d.pth), "
                                   "a VGGLoss state dict or a reference checkpoint of a run with the loss on")
-    return conv_index, path
+    return "vgg", conv_index, path
 
 
 def configure_perceptual_loss(config):
-    """-> VGGLoss() as base.py:271-275 builds it when use_perceptual_loss is set (weights from
-    config.loss.perceptual_weights), else None."""
+    """-> VGGLoss() or LPIPSLoss() as base.py:271-275 builds them when use_perceptual_loss is set (weights from
+    config.loss.perceptual_weights / config.loss.lpips_weights), else None."""
     c = config.loss
     if not _get(c, "use_perceptual_loss"):
         return None
-    conv_index, path = _perceptual_settings(c)
-    return VGGLoss(conv_index=conv_index, weights=path)
+    kind, conv_index, weights = _perceptual_settings(c)
+    if kind == "lpips":
+        return LPIPSLoss(net='alex', weights=weights)
+    return VGGLoss(conv_index=conv_index, weights=weights)
 
 
 def loss_weights(config):
