@@ -416,6 +416,27 @@ int vqw_bn_affine_bwd_apply(const float* x, const float* mean_rstd, const float*
 int vqw_hinge_fwd(const float* x, long n, int mode, float* loss, void* stream);
 int vqw_hinge_bwd(const float* x, long n, int mode, const float* gloss, float* gx, void* stream);
 
+/* ---- ActNorm and spectral normalisation of the discriminator (networks/actnorm.py:23-70, utils/__init__.py:54-64 =
+ * torch.nn.utils.spectral_norm defaults: one power iteration, eps 1e-12, dim 0).
+ * ActNorm runs on the vqw_bn_affine_* kernels with mean = -loc, rstd = 1, gamma = scale, beta = 0: vqw_actnorm_prepare writes
+ * mean_rstd_beta = [C][2] {-loc, 1} followed by [C] zeros; with `sums` ([C][2] doubles of vqw_bn_partial_stats over `count`
+ * pixels, the first training forward) it first sets loc = -mean, scale = 1 / (unbiased std + 1e-6) and initialized[0] = 1.
+ * vqw_actnorm_loc_grad: dloc = scale * dbeta. */
+int vqw_actnorm_prepare(const double* sums /*[C][2] or NULL*/, double count, float* loc, float* scale,
+                        unsigned char* initialized /*[1] or NULL*/, float* mean_rstd_beta /*[3C]*/, int C, void* stream);
+int vqw_actnorm_loc_grad(const float* dbeta, const float* scale, float* dloc, int C, void* stream);
+/* All spectrally normalised weights of one forward in three launches (two in eval mode).  layers_dev: n_layers records of 16
+ * int64 {W, u, v, out, save, t, s, rows, K, Cin, blk1, blk2, blk3, 0, 0, 0}: W / out [rows][K] in OHWI memory order
+ * (K = k*k*Cin), u [rows] and v [K] the module buffers (v in torch's logical (Cin, k, k) order), save [rows + K + 1] receives this
+ * forward's u, v (memory order) and sigma for its backward, t [K] and s [rows] scratch.  blkP = first workgroup of the layer in
+ * phase P: phase 1 has ceil(K / 64) workgroups per layer, phase 2 `rows`, phase 3 ceil(rows * K / 4096); blocksP their totals.
+ * training: v <- normalize(W^T u), u <- normalize(W v) in place first; eval: the stored u, v.  out = W / (u^T W v).
+ * vqw_spectral_norm_bwd: records of 8 int64 {G, weight, save, gW, part, rows, K, blk}: gW = (G - <G, weight> u v^T) / sigma with
+ * part [ceil(rows * K / 4096)] doubles of scratch per layer, blk = first workgroup, `blocks` their total; two launches. */
+int vqw_spectral_norm_fwd(const void* layers_dev, int n_layers, int blocks1, int blocks2, int blocks3, int training, float eps,
+                          void* stream);
+int vqw_spectral_norm_bwd(const void* grads_dev, int n_layers, int blocks, void* stream);
+
 /* ---- multi-window reconstruction loss (trainers/multi_window_trainer.py:93-109, base.py:290-314):
  * mean((w(a) - w(b))^2) with w(x) = clamp(alpha * x + beta, lo, hi); gradient w.r.t. a (zero where clamped). */
 int vqw_window_mse_fwd(const float* a, const float* b, float* loss, void* ws, size_t ws_bytes, long n, float alpha,

@@ -2665,6 +2665,177 @@ def batch_norm_lrelu(x, gamma, beta, running_mean, running_var, training, moment
                           float(eps), float(slope), bool(sync))
 
 
+class _ActNormLrelu(torch.autograd.Function):
+    """ActNorm + LeakyReLU on the BatchNorm-affine kernels in their eval form: mean = -loc, rstd = 1, gamma = scale, beta = 0
+    (`x - (-loc)`, `* 1`, `+ 0` are exact), so y = lrelu(scale * (x + loc)) bit for bit and no kernel is duplicated."""
+
+    @staticmethod
+    def forward(ctx, x, loc, scale, initialized, slope, sync):
+        _dev(x, loc, scale)
+        x = nhwc(x)
+        N, C, H, W = x.shape
+        if loc.numel() != C or scale.numel() != C:
+            raise RuntimeError("act_norm_lrelu: loc / scale have %d entries, input has %d channels" % (loc.numel(), C))
+        loc, scale = _flat(loc), _flat(scale)          # (1, C, 1, 1) parameters: dense, written in place when initialising
+        L = _L()
+        mrb = torch.empty(3 * C, dtype=torch.float32, device=x.device)       # [C][2] {-loc, 1}, then the zero beta
+        if initialized is not None:                    # data-dependent initialisation from this batch (first training forward)
+            count = float(N * H * W)
+            sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
+            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
+            L.vqw_bn_partial_stats(x, sums, ws, ws.numel(), N, H * W, C)
+            if sync and _dist_on():                    # every rank initialises from the global batch (DESIGN 6j)
+                _all_reduce(sums)
+                count *= dist.get_world_size()
+            L.vqw_actnorm_prepare(sums, count, loc, scale, initialized, mrb, C)
+        else:
+            L.vqw_actnorm_prepare(None, 0.0, loc, scale, None, mrb, C)
+        y = torch.empty_like(x, memory_format=CL)
+        L.vqw_bn_affine_fwd(x, mrb, scale, mrb[2 * C:], y, N * H * W, C, float(slope))
+        ctx.save_for_backward(x, scale, mrb)
+        ctx.slope = float(slope)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, scale, mrb = ctx.saved_tensors
+        N, C, H, W = x.shape
+        L = _L()
+        gy = nhwc(gy)
+        mr, beta = mrb, mrb[2 * C:]
+        need_params = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)     # not read by the eval-form apply without dgamma
+        dscale = dbeta = dloc = None
+        if need_params:
+            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
+            L.vqw_bn_affine_bwd_reduce(x, mr, scale, beta, gy, sums, ws, ws.numel(), N, H * W, C, ctx.slope)
+            dscale = torch.empty((1, C, 1, 1), dtype=torch.float32, device=x.device)
+            dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+        gx = torch.empty_like(x, memory_format=CL)
+        L.vqw_bn_affine_bwd_apply(x, mr, scale, beta, gy, sums, float(N * H * W), gx, dscale, dbeta, N * H * W, C, ctx.slope, 0, 0)
+        if need_params:
+            dloc = torch.empty((1, C, 1, 1), dtype=torch.float32, device=x.device)
+            L.vqw_actnorm_loc_grad(dbeta, scale, dloc, C)
+        return gx, dloc, dscale, None, None, None
+
+
+def act_norm_lrelu(x, loc, scale, initialized=None, slope=0.2, sync=True):
+    """ActNorm (logdet=False) followed by nn.LeakyReLU(slope) (slope = 1: plain ActNorm): lrelu(scale * (x + loc)).
+    With `initialized` (the module's uint8 flag buffer) loc / scale are first set from this batch - loc = -mean,
+    scale = 1 / (unbiased std + 1e-6) per channel, over all ranks when a process group is up - and the flag is raised."""
+    return _ActNormLrelu.apply(x, loc, scale, initialized, float(slope), bool(sync))
+
+
+# pointer tables of the multi-layer launches go up through a small ring of persistent pinned buffers, as hipops.Adam's do
+_table_rings = {}
+
+
+def _upload_table(rows, device):
+    import numpy as np
+    arr = np.asarray(rows, dtype=np.int64)
+    ring = _table_rings.setdefault((device, arr.size), [])
+    slot = None
+    for cand in ring:
+        if cand[1].query():
+            slot = cand
+            break
+    if slot is None:
+        if len(ring) >= 8:
+            slot = ring[0]
+            slot[1].synchronize()
+        else:
+            slot = [torch.empty(arr.size, dtype=torch.int64).pin_memory(), torch.cuda.Event()]
+            ring.append(slot)
+    slot[0].numpy()[:] = arr.reshape(-1)
+    table = slot[0].to(device, non_blocking=True)
+    slot[1].record(torch.cuda.current_stream())
+    return table
+
+
+SN_CHUNK, SN_COLS = 4096, 64         # csrc/spectral.hip
+
+
+class _SpectralNorm(torch.autograd.Function):
+    """weight_i = W_i / sigma_i for n layers at once (csrc/spectral.hip): three launches per forward in training mode, two in
+    eval mode, two per backward, whatever n is."""
+
+    @staticmethod
+    def forward(ctx, training, eps, n, *ts):
+        ws, us, vs = ts[:n], ts[n:2 * n], ts[2 * n:]
+        _dev(*ts)
+        dev = ws[0].device
+        dims = []
+        for w, u, v in zip(ws, us, vs):
+            rows, cin, kh, kw = w.shape
+            K = cin * kh * kw
+            if u.numel() != rows or v.numel() != K or u.dtype != torch.float32 or v.dtype != torch.float32:
+                raise RuntimeError("spectral_norm_weight: u / v must be fp32 of %d / %d entries for a weight of shape %s"
+                                   % (rows, K, tuple(w.shape)))
+            if not (u.is_contiguous() and v.is_contiguous()):
+                raise RuntimeError("spectral_norm_weight: u / v are updated in place and must be contiguous")
+            dims.append((rows, K, cin))
+        ws = [nhwc(w) for w in ws]
+        outs = [torch.empty(w.shape, dtype=torch.float32, device=dev, memory_format=CL) for w in ws]
+        scratch = torch.empty(sum(2 * (rows + K) + 1 for rows, K, _ in dims), dtype=torch.float32, device=dev)
+        table, off, b1, b2, b3 = [], scratch.data_ptr(), 0, 0, 0
+        saves = []
+        for w, u, v, o, (rows, K, cin) in zip(ws, us, vs, outs, dims):
+            save, t, s_ = off, off + 4 * (rows + K + 1), off + 4 * (rows + 2 * K + 1)
+            off += 4 * (2 * (rows + K) + 1)
+            saves.append(save)
+            table.append((w.data_ptr(), u.data_ptr(), v.data_ptr(), o.data_ptr(), save, t, s_, rows, K, cin, b1, b2, b3, 0, 0, 0))
+            b1 += -(-K // SN_COLS)
+            b2 += rows
+            b3 += -(-(rows * K) // SN_CHUNK)
+        tab = _upload_table(table, dev)
+        _L().vqw_spectral_norm_fwd(tab, n, b1, b2, b3, int(training), float(eps))
+        tab.record_stream(torch.cuda.current_stream())
+        ctx.save_for_backward(scratch, *outs)
+        ctx.cfg = (dims, [sv - scratch.data_ptr() for sv in saves])
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        scratch, *outs = ctx.saved_tensors
+        dims, save_off = ctx.cfg
+        n = len(outs)
+        todo = [i for i in range(n) if ctx.needs_input_grad[3 + i] and gs[i] is not None]
+        grads = [None] * n
+        if todo:
+            dev = scratch.device
+            chunks = [-(-(dims[i][0] * dims[i][1]) // SN_CHUNK) for i in todo]
+            part = torch.empty(sum(chunks), dtype=torch.float64, device=dev)
+            table, blk, keep = [], 0, []
+            for i, nc in zip(todo, chunks):
+                g = nhwc(gs[i])
+                keep.append(g)
+                grads[i] = torch.empty(outs[i].shape, dtype=torch.float32, device=dev, memory_format=CL)
+                table.append((g.data_ptr(), nhwc(outs[i]).data_ptr(), scratch.data_ptr() + save_off[i], grads[i].data_ptr(),
+                              part.data_ptr() + 8 * blk, dims[i][0], dims[i][1], blk))
+                blk += nc
+            tab = _upload_table(table, dev)
+            _L().vqw_spectral_norm_bwd(tab, len(todo), blk)
+            tab.record_stream(torch.cuda.current_stream())
+        return (None, None, None) + tuple(grads) + (None,) * (2 * n)
+
+
+def spectral_norm_weights(weight_origs, us, vs, training, eps=1e-12):
+    """torch.nn.utils.spectral_norm's forward (n_power_iterations=1, dim=0) for a list of conv weights (logical OIHW, OHWI in
+    memory) in a number of launches that does not depend on the list's length.  training: v <- normalize(W^T u),
+    u <- normalize(W v) in place (no gradient) before sigma = u^T W v; eval: the stored u, v.  -> [W / sigma] as OHWI tensors;
+    backward: (G - <G, weight> u v^T) / sigma with the u, v, sigma of that forward."""
+    n = len(weight_origs)
+    if n == 0:
+        return []
+    if not (len(us) == len(vs) == n):
+        raise RuntimeError("spectral_norm_weights: one u and one v per weight")
+    return list(_SpectralNorm.apply(bool(training), float(eps), n, *weight_origs, *us, *vs))
+
+
+def spectral_norm_weight(weight_orig, u, v, training, eps=1e-12):
+    return spectral_norm_weights([weight_orig], [u], [v], training, eps)[0]
+
+
 class _Hinge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mode):

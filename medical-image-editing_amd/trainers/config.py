@@ -8,7 +8,9 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
                           nr_steps, dropped_skip_layers, use_pixel_shuffle}
     config.loss.{loss_weight.{commit, cross, dist, reg, recon, freq, perceptual}, embed_loss.{margin, use_distance_loss,
                  use_regularization_loss}, use_recon_loss, use_frequency_loss, use_perceptual_loss}
-    config.{enc_optim, dec_optim}.{lr, b1, b2, weight_decay}
+    config.{enc_optim, dec_optim, dis_optim}.{lr, b1, b2, weight_decay}
+    config.model.dis.{model_name, n_filters, n_layers, normalization, apply_spectral_norm}, config.loss.{loss_weight.{gen, dis},
+                 n_inner_loops, dis_loss_type}, config.run.{first_stage_ckpt_path, discriminator_ckpt_path}   (second_step)
     config.augmentation.{modules, ...}            (optional: absent -> the exact-integer flip views of the benchmark)
     config.dataset.{window_width, window_center, window_scale}, config.loss.{recon_weights, freq_weights, percep_weights}
                  (multi-window runs, -w)
@@ -28,9 +30,12 @@ project: a path to an LPIPS state dict / reference checkpoint, or a two-element 
 """
 from functions import EmbeddingLoss, FocalFrequencyLoss, LPIPSLoss, VGGLoss
 from hipops import Adam
-from networks import UNetEncoder, UNetDecoder, RandomTransform
+from networks import UNetEncoder, UNetDecoder, RandomTransform, NLayerDiscriminator
+from utils import apply_spectral_norm
+from utils.checkpoint import load_first_stage_from_ckpt, load_discriminator_from_ckpt
 
 from .first_step import FirstStepTrainer, FlipViews, RandomTransformViews, LossWeights
+from .second_step import SecondStepTrainer, GanLossWeights
 from .evaluation import Evaluator
 
 
@@ -67,6 +72,31 @@ def configure_models(config):
         use_pixel_shuffle=bool(g.use_pixel_shuffle),
     )
     return encoder, decoder
+
+
+def configure_discriminator(config):
+    """-> the PatchGAN discriminator as base.py:249-259 builds it: NLayerDiscriminator over config.model.dis, with spectral
+    normalisation on its convolutions when dis.apply_spectral_norm is set."""
+    d = config.model.dis
+    name = _get(d, "model_name", "NLayerDiscriminator")
+    if name == "UNetDiscriminator":
+        raise NotImplementedError("model.dis.model_name 'UNetDiscriminator' is not built: its residual down / up blocks, "
+                                  "self-attention and per-pixel output head have no HIP kernels here; only "
+                                  "'NLayerDiscriminator' (batchnorm or actnorm, with or without spectral norm) is")
+    if name != "NLayerDiscriminator":
+        raise NotImplementedError("model.dis.model_name %r is unknown" % (name,))
+    dis = NLayerDiscriminator(in_channels=config.model.vqmodel.in_channels, out_channels=1, n_filters=d.n_filters,
+                              n_layers=d.n_layers, normalization=d.normalization)
+    if _get(d, "apply_spectral_norm"):
+        apply_spectral_norm(dis)
+    return dis
+
+
+def gan_loss_weights(config):
+    """-> GanLossWeights from config.loss.loss_weight.{recon, gen, dis, freq, perceptual}; an absent key keeps the
+    namedtuple's default."""
+    w = config.loss.loss_weight
+    return GanLossWeights(**{k: float(_get(w, k) or 0.0) for k in GanLossWeights._fields if hasattr(w, k)})
 
 
 def _adam_kwargs(o):
@@ -165,7 +195,8 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
     import torch.distributed as dist
     mode = _get(config.run, "training_mode", "first_step")
     if mode != "first_step":
-        raise NotImplementedError("training_mode %r: use trainers.SecondStepTrainer for the GAN step" % mode)
+        raise NotImplementedError("training_mode %r: use trainers.build_second_step_trainer (or trainers.SecondStepTrainer) "
+                                  "for the GAN step" % mode)
     frequency_loss = configure_frequency_loss(config)
     if multi_window is None and _get(config.loss, "recon_weights") is not None and _get(config.dataset, "window_width") is not None:
         d = config.dataset
@@ -197,3 +228,37 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
         embed_loss=configure_losses(config), enc_optim=_adam_kwargs(config.enc_optim), dec_optim=_adam_kwargs(config.dec_optim),
         use_recon_loss=bool(_get(config.loss, "use_recon_loss", True)), frequency_loss=frequency_loss, freq_weights=freq_weights,
         perceptual_loss=perceptual_loss, percep_weights=percep_weights)
+
+
+def build_second_step_trainer(config, device="cuda", data_parallel=None, first_stage_ckpt_path=None,
+                              discriminator_ckpt_path=None):
+    """config -> SecondStepTrainer (the `second_step` training mode of run_vqwnet.py with the PatchGAN discriminator,
+    single_window_trainer.py:434-488).  The first-stage weights (encoder strictly, decoder non-strictly) and, optionally, the
+    discriminator's come from the path arguments, else from config.run.first_stage_ckpt_path / discriminator_ckpt_path, as
+    TrainerBase.__init__ loads them (base.py:79-83).  Multi-window second steps train the U-Net discriminator in the
+    reference and are not built."""
+    import torch.distributed as dist
+    mode = _get(config.run, "training_mode", "second_step")
+    if mode != "second_step":
+        raise NotImplementedError("training_mode %r: build_second_step_trainer builds 'second_step' only" % (mode,))
+    c = config.loss
+    loss_type = _get(c, "dis_loss_type") or "hinge_d_loss"
+    if loss_type != "hinge_d_loss":
+        raise NotImplementedError("loss.dis_loss_type %r: only 'hinge_d_loss' is built (single_window_trainer.py:478)" % (loss_type,))
+    if _get(c, "recon_weights") is not None and _get(_get(config, "dataset"), "window_width") is not None:
+        raise NotImplementedError("a multi-window second step uses the U-Net discriminator, which is not built")
+    encoder, decoder = configure_models(config)
+    dis = configure_discriminator(config)
+    first = first_stage_ckpt_path or _get(config.run, "first_stage_ckpt_path")
+    if first:
+        load_first_stage_from_ckpt(first, encoder, decoder)
+    dck = discriminator_ckpt_path or _get(config.run, "discriminator_ckpt_path")
+    if dck:
+        load_discriminator_from_ckpt(dck, dis)
+    if data_parallel is None:
+        data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    return SecondStepTrainer(
+        encoder, decoder, dis=dis, loss_weight=gan_loss_weights(config), n_inner_loops=int(_get(c, "n_inner_loops") or 1),
+        device=device, data_parallel=data_parallel, frequency_loss=configure_frequency_loss(config),
+        perceptual_loss=configure_perceptual_loss(config), dec_optim=_adam_kwargs(config.dec_optim),
+        dis_optim=_adam_kwargs(config.dis_optim), use_recon_loss=bool(_get(c, "use_recon_loss", True)))

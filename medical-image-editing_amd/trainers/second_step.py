@@ -3,7 +3,10 @@ trainers/single_window_trainer.py:434-488 (`_train_second_step_nl_dis`), optimis
 
 The encoder is frozen (eval mode, no_grad); the decoder is trained on  w.recon * MSE(recon, image) + w.gen * (-mean(D(recon)))
 (+ w.freq * FFL(recon, image) with a frequency_loss, + w.perceptual * VGGLoss(recon, image) with a perceptual_loss,
-:453-467); then the discriminator on  w.dis * hinge_d_loss(D(image), D(recon.detach()))  for n_inner_loops.
+:453-467); then the discriminator on  w.dis * hinge_d_loss(D(image), D(recon.detach()))  for n_inner_loops.  `dec_optim` / `dis_optim`
+(dicts lr / betas / weight_decay, the reference's config.dec_optim / config.dis_optim, base.py:171-181) override the shared
+lr / betas / weight_decay per optimiser; use_recon_loss=False drops the reconstruction term (:448-451).
+trainers.build_second_step_trainer builds one from a config.
 """
 from collections import namedtuple
 
@@ -19,7 +22,7 @@ GanLossWeights = namedtuple("GanLossWeights", "recon gen dis freq perceptual", d
 class SecondStepTrainer:
     def __init__(self, encoder, decoder, dis=None, loss_weight=None, n_inner_loops=1, lr=1e-4, betas=(0.5, 0.999),
                  weight_decay=0.0, device="cuda", data_parallel=False, frequency_loss=None,
-                 perceptual_loss=None):
+                 perceptual_loss=None, dec_optim=None, dis_optim=None, use_recon_loss=True):
         self.device = torch.device(device)
         from .first_step import StepThrottle
         self.throttle = StepThrottle(self.device)      # at most two steps enqueued ahead of the GPU
@@ -31,10 +34,10 @@ class SecondStepTrainer:
         self.frequency_loss = frequency_loss          # functions.FocalFrequencyLoss or None (use_frequency_loss)
         # functions.VGGLoss or None (use_perceptual_loss); no trainable parameters, so nothing to all-reduce
         self.perceptual_loss = perceptual_loss.to(self.device) if perceptual_loss is not None else None
-        self.dec_optim = Adam([p for p in self.decoder.parameters() if p.requires_grad], lr=lr, betas=betas,
-                              weight_decay=weight_decay)
-        self.dis_optim = Adam([p for p in self.dis.parameters() if p.requires_grad], lr=lr, betas=betas,
-                              weight_decay=weight_decay)
+        self.use_recon_loss = bool(use_recon_loss)
+        shared = dict(lr=lr, betas=betas, weight_decay=weight_decay)
+        self.dec_optim = Adam([p for p in self.decoder.parameters() if p.requires_grad], **(dec_optim or shared))
+        self.dis_optim = Adam([p for p in self.dis.parameters() if p.requires_grad], **(dis_optim or shared))
         # one process per GPU (run_vqwnet.py:112-121): bucketed gradient all-reduce per optimiser, overlapped with
         # the rest of its backward pass; BatchNorm statistics (StyledDenorm and the discriminator's) are synchronised
         # inside their kernels' host code when a process group is up
@@ -61,7 +64,7 @@ class SecondStepTrainer:
         with torch.no_grad():
             embed, _, ids = self.encoder(image)
         recon = self.decoder(embed.detach())
-        l_recon = ops.mse_loss(recon, image)
+        l_recon = ops.mse_loss(recon, image) if self.use_recon_loss else None
         l_freq = self.frequency_loss(recon, image) if self.frequency_loss is not None else None
         l_percep = self.perceptual_loss(recon, image) if self.perceptual_loss is not None else None
         # The reference lets autograd fill the discriminator's parameter gradients in this pass and discards them
@@ -71,7 +74,7 @@ class SecondStepTrainer:
             p.requires_grad_(False)
         try:
             l_gen = generator_loss(self.dis(recon))
-            terms, weights = [l_recon, l_gen], [w.recon, w.gen]
+            terms, weights = ([l_recon, l_gen], [w.recon, w.gen]) if l_recon is not None else ([l_gen], [w.gen])
             if l_freq is not None:
                 terms.append(l_freq)
                 weights.append(w.freq)
@@ -105,6 +108,8 @@ class SecondStepTrainer:
             self.dis_optim.step()
         self.throttle.end()
         out = dict(gen_total=l_gen_total, recon=l_recon, gen=l_gen, dis_total=l_dis_total, ids=ids, recon_image=recon)
+        if l_recon is None:
+            del out["recon"]
         if l_freq is not None:
             out["freq"] = l_freq
         if l_percep is not None:

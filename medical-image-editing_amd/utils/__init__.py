@@ -1,4 +1,4 @@
-"""The slice of the reference's `utils` the hot path uses (utils/__init__.py:81-92, 99-114)."""
+"""The slice of the reference's `utils` the hot path uses (utils/__init__.py:54-64, 81-92, 99-114)."""
 import json
 import os
 from collections import namedtuple
@@ -14,6 +14,21 @@ def norm(x):
 def denorm(x, vmin=0, vmax=1):
     """[-1,1] -> [vmin,vmax], in place (utils/__init__.py:81-86)."""
     return ops.affine_(x, 0.5 * (vmax - vmin), 0.5 * (vmax - vmin) + vmin)
+
+
+def apply_spectral_norm(net):
+    """Spectral normalisation on every sub-module whose class name contains 'Conv2d' or 'Linear' (utils/__init__.py:54-64:
+    torch.nn.utils.spectral_norm with its defaults).  Here those are the discriminator's SConv2d layers, normalised by the
+    HIP kernels (networks.discriminator.install_spectral_norm); any other matching module raises."""
+    from networks.discriminator import install_spectral_norm
+
+    def _add_spectral_norm(m):
+        classname = m.__class__.__name__
+        if classname.find('Conv2d') != -1 or classname.find('Linear') != -1:
+            install_spectral_norm(m)
+
+    net.apply(_add_spectral_norm)
+    return net
 
 
 def load_json(path):

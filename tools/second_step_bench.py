@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Throughput of the second training step (frozen encoder -> decoder -> PatchGAN; generator then discriminator update)
-at the bench shape.   python tools/second_step_bench.py [--batch 32] [--size 256] [--steps 5]"""
+at the bench shape.   python tools/second_step_bench.py [--batch 32] [--size 256] [--steps 5]
+                            [--normalization batchnorm|actnorm] [--spectral-norm] [--digest]
+--digest also prints a SHA-256 over the losses, the reconstruction and the updated decoder / discriminator state of the first
+three steps (seeded): equal digests = bit-identical runs."""
 import argparse
 import os
 import sys
@@ -18,13 +21,31 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--normalization", default="batchnorm", choices=("batchnorm", "actnorm"))
+    ap.add_argument("--spectral-norm", action="store_true")
+    ap.add_argument("--digest", action="store_true")
     a = ap.parse_args()
     torch.manual_seed(0)
     enc = UNetEncoder(1, [16, 32, 64, 128, 256], 10, 0.999, 'torch', False, 1, True)
     dec = UNetDecoder(16, 1, [32, 64, 128, 256, 512], use_dropblock=False, dropped_skip_layers=[], use_styled_up_block=True,
                       use_pixel_shuffle=False)
-    tr = SecondStepTrainer(enc, dec, NLayerDiscriminator(), device="cuda")
+    dis = NLayerDiscriminator(normalization=a.normalization)
+    if a.spectral_norm:
+        from utils import apply_spectral_norm
+        apply_spectral_norm(dis)
+    tr = SecondStepTrainer(enc, dec, dis, device="cuda")
     img = torch.rand(a.batch, 1, a.size, a.size, device="cuda") * 2 - 1
+    if a.digest:
+        import hashlib
+        h = hashlib.sha256()
+        for _ in range(3):
+            out = tr.training_step(img)
+            for k in ("gen_total", "recon", "gen", "dis_total", "recon_image"):
+                h.update(out[k].detach().cpu().contiguous().numpy().tobytes())
+        for m in (tr.decoder, tr.dis):
+            for v in m.state_dict().values():
+                h.update(v.detach().cpu().contiguous().numpy().tobytes())
+        print("digest of three seeded steps: %s" % h.hexdigest())
     for _ in range(2):
         tr.training_step(img)
     torch.cuda.synchronize()
