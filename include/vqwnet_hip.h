@@ -547,6 +547,21 @@ int vqw_lpips_loss_fold(const void* ws, size_t ws_bytes, float* loss, int N, int
 int vqw_lpips_dist_bwd(const float* f, const float* lw, const float* gin, float* gout, int N, int nwin, int HW, int C,
                        void* stream);
 
+/* ---- 8-bit export (the validation mosaic, the inference export and test-mode pictures: what the reference's to_image /
+ *      save_image do on the host, single_window_trainer.py:563-638, 716-779).  Added functions only; the ABI stays 9.
+ * Both kernels read every input element once, take B * H * W < 2^31 and B <= 65535, and flip rows top to bottom with flip = 1.
+ * vqw_export_grey: x [B][H][W] float (a (B,1,H,W) tensor in either memory format), win [nwin][6] device floats
+ * (alpha, beta, lo, hi, vmin, vmax - vmin), nwin <= 8; out [nwin][B][H][W] bytes,
+ *   u8 = min(255, floor(256 * clamp((clamp(alpha * x + beta, lo, hi) - vmin) / (vmax - vmin), 0, 1)))
+ * with one float32 rounding per operation (no fused multiply-add).  alpha 1, beta 0, lo -inf, hi inf: no window.
+ * vqw_export_labels: ids [B][H][W] in [0, K], K <= 65535.  index_out (nullable): [B][H][W] uint8 when K <= 255, else uint16;
+ * rgb (nullable): [B][H][W][3] bytes = palette[id], palette [K + 1][3] bytes (held in LDS up to 4096 entries); counts
+ * (nullable): [B][K + 1] int32, exact integer atomics; err [1]: set to 1 when an id lies outside [0, K] (it exports as 0 and is
+ * not counted), else 0.  counts and err are cleared by the call. */
+int vqw_export_grey(const float* x, const float* win, uint8_t* out, int nwin, int B, int H, int W, int flip, void* stream);
+int vqw_export_labels(const int64_t* ids, const uint8_t* palette, void* index_out, uint8_t* rgb, int32_t* counts, int32_t* err,
+                      int B, int H, int W, int K, int flip, void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

@@ -6,6 +6,7 @@ import torch
 from torch.utils import data
 
 from .lung_dataset import NCCLungDataset, MICCAIBraTSDataset, CRCDataset
+from .synthetic import SyntheticSliceDataset
 
 
 class ToTensor:
@@ -57,9 +58,13 @@ class _Compose:
 
 
 def get_data_loader(mode, dataset_name, root_dir_path, batch_size, num_workers, modality=None, augmentations=None,
-                    drop_last=False, window_width=None, window_center=None, window_scale=None):
+                    drop_last=False, window_width=None, window_center=None, window_scale=None, sampler=None, generator=None,
+                    image_size=None, n_samples=None, seed=0):
+    """sampler (e.g. a DistributedSampler; replaces the loader's own shuffling) and generator (the torch.Generator the
+    shuffling and the workers' seeds are drawn from, so that a run can save and restore it) are passed to the DataLoader;
+    image_size / n_samples / seed describe the generated 'synthetic' dataset."""
     assert mode in {'train', 'val', 'test'}
-    assert dataset_name in {'MICCAIBraTSDataset', 'NCCLungDataset', 'CRCDataset'}
+    assert dataset_name in {'MICCAIBraTSDataset', 'NCCLungDataset', 'CRCDataset', 'synthetic'}
     intensity = [] if dataset_name == 'NCCLungDataset' else [NormalizeIntensity()]      # CT slices are windowed by the dataset
     if mode == 'train':
         if augmentations:
@@ -68,11 +73,13 @@ def get_data_loader(mode, dataset_name, root_dir_path, batch_size, num_workers, 
     else:
         assert augmentations is None
         transform, shuffle = _Compose([ToTensor()] + intensity), mode == 'val'
-    if dataset_name == 'MICCAIBraTSDataset':
+    if dataset_name == 'synthetic':         # generated in [-1, 1] as (1, H, W) tensors: no transform chain
+        dataset = SyntheticSliceDataset(mode, image_size or 256, n_samples or (256 if mode == 'train' else 64), seed)
+    elif dataset_name == 'MICCAIBraTSDataset':
         dataset = MICCAIBraTSDataset(root_dir_path, modality, transform)
     elif dataset_name == 'CRCDataset':
         dataset = CRCDataset(root_dir_path, transform)
     else:
         dataset = NCCLungDataset(root_dir_path, transform, window_width, window_center, window_scale)
-    return data.DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers, drop_last=drop_last,
-                           pin_memory=True)
+    return data.DataLoader(dataset, batch_size=batch_size, shuffle=shuffle if sampler is None else False, sampler=sampler,
+                           num_workers=num_workers, drop_last=drop_last, pin_memory=True, generator=generator)

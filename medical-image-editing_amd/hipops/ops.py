@@ -2978,3 +2978,147 @@ class _SegLosses(torch.autograd.Function):
 def seg_losses(logits, target, ignore_index=-1, smooth=1e-6, gamma=2.0, eps=1e-6):
     """-> (soft dice loss, focal loss) of functions/seg_loss.py for NCHW logits and one-hot targets."""
     return _SegLosses.apply(logits, target, int(ignore_index), float(smooth), float(gamma), float(eps))
+
+
+# ----------------------------------------------------------------------------------------------
+# 8-bit export (csrc/export.hip): grey tiles through display windows, id maps as index / RGB planes and counts
+# ----------------------------------------------------------------------------------------------
+EXPORT_MAX_WINDOWS = 8
+EXPORT_MAX_DICT_SIZE = 65535
+_export_tables = {}
+_palettes = {}
+
+
+def default_palette(dict_size):
+    """(K + 1, 3) uint8 numpy palette for ids 0..K: matplotlib's 'Spectral' colour map (the reference's CMAP) sampled at
+    K + 1 evenly spaced points when matplotlib imports, otherwise a fixed blue-to-red hue ramp of this project."""
+    import numpy as np
+    K = int(dict_size)
+    pal = _palettes.get(K)
+    if pal is None:
+        try:
+            import matplotlib
+            cmap = matplotlib.colormaps["Spectral"] if hasattr(matplotlib, "colormaps") else None
+            if cmap is None:
+                from matplotlib import cm
+                cmap = cm.get_cmap("Spectral")
+            pal = (np.asarray(cmap(np.linspace(0.0, 1.0, K + 1)))[:, :3] * 255.0 + 0.5).astype(np.uint8)
+        except Exception:
+            t = np.linspace(0.0, 1.0, K + 1)
+            pal = np.stack([255.0 * t, 255.0 * (1.0 - np.abs(2.0 * t - 1.0)), 255.0 * (1.0 - t)], axis=1)
+            pal = (pal + 0.5).astype(np.uint8)
+        _palettes[K] = pal = np.ascontiguousarray(pal)
+    return pal
+
+
+def _export_window_rows(windows, vmin, vmax):
+    import numpy as np
+    if not float(vmax) > float(vmin):
+        raise ValueError("export_grey: vmax must be greater than vmin (got %r, %r)" % (vmin, vmax))
+    if not 1 <= len(windows) <= EXPORT_MAX_WINDOWS:
+        raise ValueError("export_grey: 1..%d windows (got %d)" % (EXPORT_MAX_WINDOWS, len(windows)))
+    lo32 = np.float32(vmin)
+    rows = []
+    for w in windows:
+        w = _IDENTITY_WINDOW if w is None else tuple(float(v) for v in w)
+        if len(w) != 4:
+            raise ValueError("export_grey: a window is None or (alpha, beta, lo, hi) as ops.window_map returns it")
+        rows.append(w + (float(lo32), float(np.float32(vmax) - lo32)))
+    return tuple(rows)
+
+
+def export_grey(x, windows=(None,), vmin=-1.0, vmax=1.0, flip=False):
+    """(B, 1, H, W) fp32 images (either memory format) -> (n_windows, B, H, W) uint8 tiles,
+    u8 = min(255, floor(256 * clamp((w(x) - vmin) / (vmax - vmin), 0, 1))), w = the identity (None) or the window map
+    (alpha, beta, lo, hi) of ops.window_map: x -> clamp(alpha * x + beta, lo, hi).  One float32 rounding per operation.
+    All windows come from one read of x; flip=True writes the rows bottom to top (np.flipud per image)."""
+    windows = tuple(windows)
+    rows = _export_window_rows(windows, vmin, vmax)
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise RuntimeError("export_grey: expected an fp32 tensor (got %s)" % (getattr(x, "dtype", type(x)),))
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise RuntimeError("export_grey: expected a (B, 1, H, W) tensor, got shape %s" % (tuple(x.shape),))
+    if x.numel() == 0:
+        raise RuntimeError("export_grey: empty input")
+    _dev(x)
+    x = x.detach()
+    B, _, H, W = x.shape
+    x = x.reshape(B, H, W).contiguous()                # one channel: NCHW and NHWC hold the same bytes, no copy
+    key = (x.device, rows)
+    tab = _export_tables.get(key)
+    if tab is None:
+        tab = torch.tensor(rows, dtype=torch.float32).to(x.device)
+        if not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream().synchronize()
+        _export_tables[key] = tab
+    out = torch.empty((len(rows), B, H, W), dtype=torch.uint8, device=x.device)
+    _L().vqw_export_grey(x, tab, out, len(rows), B, H, W, int(bool(flip)))
+    return out
+
+
+class LabelExport:
+    """Result of ops.export_labels: device tensors `index` (B, H, W) uint8 / uint16, `rgb` (B, H, W, 3) uint8 and `counts`
+    (B, K + 1) int32 (each None when not asked for).  check() reads the error flag (one small device-to-host copy) and
+    raises ValueError when an id lay outside [0, dict_size]."""
+
+    def __init__(self, index, rgb, counts, err):
+        self.index, self.rgb, self.counts, self._err = index, rgb, counts, err
+
+    def check(self):
+        if self._err is not None:
+            bad = int(self._err.cpu()[0])
+            self._err = None
+            if bad:
+                raise ValueError("export_labels: ids outside [0, dict_size]")
+        return self
+
+
+def export_labels(ids, dict_size, palette=None, index=True, rgb=True, counts=True, flip=False, check=True):
+    """ids (B, H, W) int64 in [0, K] -> LabelExport(index plane, RGB plane through `palette` ((K + 1, 3) uint8; default
+    ops.default_palette), per-image counts of ids 0..K).  flip=True writes rows bottom to top.  With check=True (default)
+    an id outside [0, K] raises ValueError here, which reads the flag to the host; check=False leaves that to .check()."""
+    K = int(dict_size)
+    if not 1 <= K <= EXPORT_MAX_DICT_SIZE:
+        raise ValueError("export_labels: dict_size must be in [1, %d] (got %d)" % (EXPORT_MAX_DICT_SIZE, K))
+    if not torch.is_tensor(ids) or ids.dtype != torch.int64:
+        raise RuntimeError("export_labels: ids must be an int64 tensor (got %s)" % (getattr(ids, "dtype", type(ids)),))
+    if ids.dim() != 3:
+        raise RuntimeError("export_labels: expected (B, H, W) ids, got shape %s" % (tuple(ids.shape),))
+    if ids.numel() == 0:
+        raise RuntimeError("export_labels: no ids")
+    if rgb:
+        import numpy as np
+        if palette is None:
+            palette = default_palette(K)
+        if torch.is_tensor(palette):
+            if palette.dtype != torch.uint8 or tuple(palette.shape) != (K + 1, 3):
+                raise ValueError("export_labels: the palette must be (%d, 3) uint8 (got %s %s)"
+                                 % (K + 1, tuple(palette.shape), palette.dtype))
+        else:
+            palette = np.asarray(palette)
+            if palette.dtype != np.uint8 or palette.shape != (K + 1, 3):
+                raise ValueError("export_labels: the palette must be (%d, 3) uint8 (got %s %s)"
+                                 % (K + 1, palette.shape, palette.dtype))
+    _dev(ids)
+    ids = ids.detach().contiguous()                    # the encoder's ids are a transposed view: the planes need rows
+    dev = ids.device
+    B, H, W = ids.shape
+    pal_dev = None
+    if rgb:
+        if torch.is_tensor(palette):
+            pal_dev = palette.to(dev).contiguous()
+        else:
+            key = (dev, K, palette.tobytes())
+            pal_dev = _export_tables.get(key)
+            if pal_dev is None:
+                pal_dev = torch.from_numpy(np.ascontiguousarray(palette)).to(dev)
+                if not torch.cuda.is_current_stream_capturing():
+                    torch.cuda.current_stream().synchronize()
+                _export_tables[key] = pal_dev
+    idx_t = torch.empty((B, H, W), dtype=torch.uint8 if K <= 255 else torch.uint16, device=dev) if index else None
+    rgb_t = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) if rgb else None
+    cnt_t = torch.empty((B, K + 1), dtype=torch.int32, device=dev) if counts else None
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _L().vqw_export_labels(ids, pal_dev, idx_t, rgb_t, cnt_t, err, B, H, W, K, int(bool(flip)))
+    res = LabelExport(idx_t, rgb_t, cnt_t, err)
+    return res.check() if check else res

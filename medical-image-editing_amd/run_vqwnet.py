@@ -1,0 +1,216 @@
+"""Launcher: train, validate, test and export a VQ-W-Net from a config (the reference's run_vqwnet.py:61-155 command line).
+
+    python run_vqwnet.py -c CONFIG [-m train|test] [-w]
+
+run.training_mode picks the work: `first_step` / `second_step` train (-m train) or are scored (-m test: result.csv in the
+run directory); `inference` (-m test only) exports PNG and NIfTI files per slice.  -w selects the multi-window step and
+needs loss.recon_weights and dataset.window_width / window_center / window_scale.  -v (the VQGAN trainer) is not built.
+
+One process per GPU.  With run.num_gpus == 1 this process is the worker.  With more, this process never touches the GPU:
+it starts num_gpus fresh interpreters of this file (`--rank r`, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their
+environment), waits for them, and when one fails it terminates the others and exits non-zero.  VQW_DP_ONE_DEVICE=1 puts
+every rank on cuda:0 with the gloo backend (a rehearsal of the multi-process path on one card).
+"""
+import argparse
+import os
+import random
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+MAX_GPUS = 8
+WINDOW_KEYS = ("loss.recon_weights", "dataset.window_width", "dataset.window_center", "dataset.window_scale")
+TRAINING_MODES = ("first_step", "second_step", "inference")
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="Train, score or export a VQ-W-Net from a JSON config")
+    parser.add_argument("-c", "--config", required=True, help="path of the JSON config")
+    parser.add_argument("-m", "--mode", default="train", help="train (default) or test")
+    parser.add_argument("-w", "--multiwindow", action="store_true", help="multi-window training step")
+    parser.add_argument("-v", "--vqgan", action="store_true", help="accepted for compatibility; not built")
+    parser.add_argument('--rank', type=int, default=None, help='set by the launcher for its worker processes')
+    parser.add_argument('--seed', type=int, default=None, help='set by the launcher: the seed all workers share')
+    return parser
+
+
+def _get(cfg, name, default=None):
+    v = getattr(cfg, name, None) if cfg is not None else None
+    return default if v is None else v
+
+
+def _lookup(config, dotted):
+    node = config
+    for part in dotted.split("."):
+        node = getattr(node, part, None)
+        if node is None:
+            return None
+    return node
+
+
+def check_arguments(config, args):
+    """Everything that can be refused before a device is touched or a process started."""
+    if args.vqgan:
+        raise NotImplementedError("-v: the VQGAN trainer (model_name 'VQGAN', U-Net discriminator) is not built")
+    if args.mode not in ("train", "test"):
+        raise ValueError("-m %r: the mode is 'train' or 'test'" % (args.mode,))
+    mode = _get(config.run, "training_mode", "first_step")
+    if mode not in TRAINING_MODES:
+        raise ValueError("run.training_mode %r: one of %s" % (mode, ", ".join(TRAINING_MODES)))
+    if mode == "inference" and args.mode != "test":
+        raise ValueError("run.training_mode 'inference' exports with -m test; it cannot be trained (-m %s)" % args.mode)
+    if args.multiwindow:
+        missing = [k for k in WINDOW_KEYS if _lookup(config, k) is None]
+        if missing:
+            raise ValueError("-w (multi-window) needs the config keys %s; missing: %s" % (", ".join(WINDOW_KEYS), ", ".join(missing)))
+    n = int(_get(config.run, "num_gpus", 1))
+    if n < 1 or n > MAX_GPUS:
+        raise ValueError("run.num_gpus = %d: one node of 1..%d GPUs" % (n, MAX_GPUS))
+    return mode, n
+
+
+def _free_port():
+    import socket
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def launch(args, num_gpus, seed, child_command=None, poll_seconds=0.2, grace_seconds=10.0):
+    """Start one worker per GPU and wait -> exit status (0, or the first failing worker's).  This process creates no GPU
+    context.  child_command: the command line up to the per-rank arguments (default: this file under this interpreter)."""
+    base = list(child_command) if child_command is not None else [sys.executable, os.path.abspath(__file__)]
+    common = ["-c", args.config, "-m", args.mode, "--seed", str(seed)] + (["-w"] if args.multiwindow else [])
+    env = dict(os.environ, WORLD_SIZE=str(num_gpus), MASTER_ADDR=os.environ.get("MASTER_ADDR", "127.0.0.1"),
+               MASTER_PORT=os.environ.get("MASTER_PORT") or str(_free_port()))
+    procs = []
+    for r in range(num_gpus):
+        procs.append(subprocess.Popen(base + common + ["--rank", str(r)], env=dict(env, RANK=str(r), LOCAL_RANK=str(r))))
+    status = 0
+    live = list(procs)
+    while live and status == 0:
+        time.sleep(poll_seconds)
+        for p in list(live):
+            rc = p.poll()
+            if rc is None:
+                continue
+            live.remove(p)
+            if rc != 0:
+                status = rc if rc > 0 else 1
+                print("run_vqwnet: worker %d exited with status %d; stopping the others" % (procs.index(p), rc), file=sys.stderr)
+                break
+    if status != 0:
+        for p in live:
+            p.terminate()
+        deadline = time.time() + grace_seconds
+        for p in live:
+            try:
+                p.wait(timeout=max(0.1, deadline - time.time()))
+            except subprocess.TimeoutExpired:
+                p.kill()
+                p.wait()
+    return status
+
+
+def seed_everything(seed):
+    import numpy as np
+    import torch
+    random.seed(seed)
+    np.random.seed(seed % (2 ** 32))
+    torch.manual_seed(seed)
+
+
+def _digest(trainer, fit, path, rank):
+    """Test aid (VQW_RUN_DIGEST=<path prefix>): a hash per module of this rank's parameters and buffers, and the sample
+    indices its sampler handed out."""
+    import hashlib
+    import json
+    import torch
+    out = {"rank": rank, "modules": {}, "seen": fit.sampler.seen if fit.sampler is not None else []}
+    for name, m in trainer.modules().items():
+        h = hashlib.sha256()
+        for k, v in m.state_dict().items():
+            h.update(k.encode())
+            h.update(v.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes())
+        out["modules"][name] = h.hexdigest()
+    with open("%s.rank%d.json" % (path, rank), "w") as f:
+        json.dump(out, f)
+
+
+def worker(config, args, training_mode, rank, world_size, seed):
+    import torch
+    import torch.distributed as dist
+    from trainers import Fit, InferenceModels, build_first_step_trainer, build_second_step_trainer
+    from utils.logger import Logger
+
+    seed_everything(seed)                       # shared by all ranks: the replicas start from the same weights
+    print('Seed: {}'.format(seed))
+    if rank == 0:
+        print('Config: ', config)
+    distributed = world_size > 1
+    device = "cuda:0"
+    if distributed:
+        one_device = os.environ.get("VQW_DP_ONE_DEVICE", "0") == "1"
+        device = "cuda:0" if one_device else "cuda:%d" % rank
+        torch.cuda.set_device(torch.device(device))
+        dist.init_process_group("gloo" if one_device else "nccl", rank=rank, world_size=world_size)
+    try:
+        if training_mode == "first_step":
+            trainer = build_first_step_trainer(config, device=device, data_parallel=distributed,
+                                               multi_window=None if args.multiwindow else False)
+        elif training_mode == "second_step":
+            if args.multiwindow:
+                raise NotImplementedError("a multi-window second step uses the U-Net discriminator, which is not built")
+            trainer = build_second_step_trainer(config, device=device, data_parallel=distributed)
+        else:
+            trainer = InferenceModels(config, device=device)
+        # utils/init_seed.py:14-24: from here on every rank has its own seed; all of them are saved with the config
+        seed_list = _get(config.run, "seed_list")
+        rank_seed = int(seed_list[rank]) if seed_list else random.randint(1, 10000)
+        seed_everything(rank_seed)
+        print('Seed set to {} in gpu-rank: {}'.format(rank_seed, rank))
+        seeds = [rank_seed]
+        if distributed:
+            seeds = [None] * world_size
+            dist.all_gather_object(seeds, rank_seed)
+        logger = None
+        if rank == 0:
+            logger = Logger(save_dir=config.save.save_dir, config=config, name=config.save.study_name,
+                            monitoring_metrics=config.run.monitoring_metrics)
+        fit = Fit(config, trainer, logger, device=device, rank=rank, world_size=world_size, seed=rank_seed, seeds=seeds,
+                  data_seed=seed)
+        if training_mode == "inference":
+            fit.export()
+        elif args.mode == "train":
+            fit.fit()
+        else:
+            fit.test()
+        if os.environ.get("VQW_RUN_DIGEST"):
+            _digest(trainer, fit, os.environ["VQW_RUN_DIGEST"], rank)
+        torch.cuda.synchronize()
+        if distributed:
+            dist.barrier()
+    finally:
+        if distributed and dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def main(argv=None, child_command=None):
+    args = build_parser().parse_args(argv)
+    from utils import load_json
+    config = load_json(args.config)
+    training_mode, num_gpus = check_arguments(config, args)
+    seed = args.seed if args.seed is not None else (_get(config.run, "seed") or random.randint(1, 10000))
+    if num_gpus > 1 and args.rank is None:
+        return launch(args, num_gpus, seed, child_command=child_command)
+    rank = args.rank if args.rank is not None else 0
+    worker(config, args, training_mode, rank, num_gpus, int(seed))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -5,3 +5,4 @@ from .config import (build_first_step_trainer, build_second_step_trainer, config
                      configure_perceptual_loss,
                      loss_weights, set_transform, build_evaluator)
 from .evaluation import Evaluator, write_result_csv  # noqa: F401
+from .fit import Fit, InferenceModels, build_loader  # noqa: F401

@@ -201,6 +201,8 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
     if multi_window is None and _get(config.loss, "recon_weights") is not None and _get(config.dataset, "window_width") is not None:
         d = config.dataset
         multi_window = dict(dataset_window=(d.window_width, d.window_center, d.window_scale), recon_weights=tuple(config.loss.recon_weights))
+    if multi_window is False:           # the launcher without -w: the single-window step whatever keys the config carries
+        multi_window = None
     perceptual_loss = configure_perceptual_loss(config)
     percep_weights = None
     if perceptual_loss is not None and multi_window is not None:

@@ -81,6 +81,50 @@ class RandomTransformViews:
         own, other = (self.t[0], self.t[1]) if which == 1 else (self.t[1], self.t[0])
         return other.forward_transform(own.reverse_transform(ids))
 
+    def state_dict(self):
+        """The two host generators the augmentation parameters are drawn from."""
+        return {"generators": [t.generator.get_state() for t in self.t]}
+
+    def load_state_dict(self, state):
+        for t, g in zip(self.t, state["generators"]):
+            t.generator.set_state(g)
+
+
+def trainer_state_dict(trainer):
+    """{'modules': {name: state_dict}, 'optimizers': {name: state_dict}, 'extra': ...} of a trainer that has modules() and
+    optimizers().  `extra` is what the module and optimiser state dicts do not hold and a bit-exact continuation needs:
+    the views' generators, the DropBlock schedule's position and the encoder's codebook-initialised flag."""
+    mods = trainer.modules()
+    extra = {"init_embed": bool(mods["encoder"].init_embed)}
+    views = getattr(trainer, "views", None)
+    if hasattr(views, "state_dict"):
+        extra["views"] = views.state_dict()
+    sched = getattr(mods["decoder"], "dropblock", None)
+    if hasattr(sched, "drop_values"):
+        extra["dropblock"] = {"i": int(sched.i), "drop_prob": float(sched.dropblock.drop_prob)}
+    return {"modules": {k: m.state_dict() for k, m in mods.items()},
+            "optimizers": {k: o.state_dict() for k, o in trainer.optimizers().items()}, "extra": extra}
+
+
+def load_trainer_state_dict(trainer, state):
+    mods = trainer.modules()
+    for k, m in mods.items():
+        if k in state.get("modules", {}):
+            m.load_state_dict(state["modules"][k], strict=True)
+    for k, o in trainer.optimizers().items():
+        if k in state.get("optimizers", {}):
+            o.load_state_dict(state["optimizers"][k])
+    extra = state.get("extra") or {}
+    if "init_embed" in extra:
+        mods["encoder"].init_embed = bool(extra["init_embed"])
+    views = getattr(trainer, "views", None)
+    if "views" in extra and hasattr(views, "load_state_dict"):
+        views.load_state_dict(extra["views"])
+    sched = getattr(mods["decoder"], "dropblock", None)
+    if "dropblock" in extra and hasattr(sched, "drop_values"):
+        sched.i = int(extra["dropblock"]["i"])
+        sched.dropblock.drop_prob = extra["dropblock"]["drop_prob"]
+
 
 LUNG_WINDOW = (1500, -550, 2.0)             # trainers/base.py:33-43
 MEDIASTINAL_WINDOW = (400, 20, 2.0)
@@ -277,6 +321,19 @@ class FirstStepTrainer:
         if pcp_1:                 # likewise only with the perceptual loss on
             out.update(perceptual_1=pcp_1[0][0], perceptual_2=pcp_2[0][0])
         return out
+
+    # -- what a run saves and restores (trainers/fit.py); `modules` / `optimizers` are in the reference's order
+    def modules(self):
+        return {"encoder": self.encoder, "decoder": self.decoder}
+
+    def optimizers(self):
+        return {"enc": self.enc_optim, "dec": self.dec_optim}
+
+    def state_dict(self):
+        return trainer_state_dict(self)
+
+    def load_state_dict(self, state):
+        load_trainer_state_dict(self, state)
 
     def test_step(self, batch):
         """The reference's test step (single_window_trainer.py:781-827): {'NMSE', 'SSIM', 'PSNR', 'Entropy'} of one batch

@@ -1,0 +1,478 @@
+"""The training run: epochs, logging, validation pictures, checkpoints, resume, test-mode scoring and the inference
+export (reference: run_vqwnet.py:61-129, trainers/base.py:116-187, single_window_trainer.py:541-644, 716-779), as a plain
+class over the trainers of this package - no PyTorch-Lightning.
+
+    Fit(config, trainer, logger).fit()            train run.n_epochs epochs (from run.resume_checkpoint when set)
+    Fit(config, trainer, logger).test()           result.csv of trainers.evaluation.Evaluator over the test loader
+    Fit(config, trainer, logger).export()         training_mode 'inference': PNG + NIfTI of image, recon, label per slice
+
+Nothing here reads a scalar from the device inside a step: the logged losses of a step go to the host in one small
+copy that is looked at two steps later (after that step's StepThrottle event), so the loop adds host work only.
+"""
+import collections
+import contextlib
+import os
+import random
+
+import numpy as np
+import torch
+from torch.utils.data.distributed import DistributedSampler
+
+from dataio import get_data_loader
+from hipops import ops
+from utils import checkpoint as ckpt_io
+from utils import logger as run_logger
+from utils import nifti, png
+
+from .first_step import (FlipViews, LUNG_WINDOW, MEDIASTINAL_WINDOW, LossWeights, trainer_state_dict,
+                         load_trainer_state_dict)
+from .evaluation import Evaluator
+
+LIMIT_VAL_BATCHES = 2              # run_vqwnet.py:127
+SANITY_VAL_BATCHES = 2             # run_vqwnet.py:125
+CKPT_LIMIT_NUM, CKPT_SAVE_INTERVAL = 10, 10        # run_vqwnet.py:72-74
+DEFAULT_LOG_EVERY_N_STEPS = 50     # Lightning 1.5's Trainer default, which the reference does not override
+DEFAULT_NOISE_STD = 0.02           # the second view's additive noise when there is no `augmentation` section
+
+
+def _get(cfg, name, default=None):
+    v = getattr(cfg, name, None) if cfg is not None else None
+    return default if v is None else v
+
+
+def dataset_window(config):
+    d = config.dataset
+    if all(_get(d, k) is not None for k in ("window_width", "window_center", "window_scale")):
+        return (d.window_width, d.window_center, d.window_scale)
+    return None
+
+
+def build_loader(config, mode, seed=0, sampler=None, generator=None):
+    """The reference's train / val / test loader (base.py:116-162) from config.dataset.  The file datasets shuffle their
+    file list once at construction with Python's `random`: it is seeded from (seed, mode) around the construction - and
+    put back - so the list is the same in every process and run that names the same seed."""
+    d = config.dataset
+    state = random.getstate()
+    random.seed(int(seed) * 3 + ("train", "val", "test").index(mode))
+    try:
+        return get_data_loader(
+            mode=mode, dataset_name=d.dataset_name, root_dir_path=_get(d, "root_dir_path"), batch_size=d.batch_size,
+            num_workers=_get(d, "num_workers", 0), modality=_get(d, "modality"),
+            augmentations=_get(d, "augmentations") if mode == "train" else None, drop_last=mode == "train",
+            window_width=_get(d, "window_width"), window_center=_get(d, "window_center"), window_scale=_get(d, "window_scale"),
+            sampler=sampler, generator=generator, image_size=_get(d, "image_size"), n_samples=_get(d, "n_samples_" + mode),
+            seed=seed)
+    finally:
+        random.setstate(state)
+
+
+# ----------------------------------------------------------------------------------------------------
+# logged scalars: the reference's self.log keys and weighting (single_window_trainer.py:149-159, 490-499)
+# ----------------------------------------------------------------------------------------------------
+def _first_step_terms(out):
+    names = ["total", "commit_1", "commit_2", "cross", "dist", "reg", "recon_l1", "recon_l2", "freq_1", "freq_2",
+             "perceptual_1", "perceptual_2"]
+    return [(n, out[n]) for n in names if n in out]
+
+
+def _first_step_row(v, w):
+    f = np.float32
+    pair = lambda a, b: f(v.get(a, 0.0)) + f(v.get(b, 0.0))  # noqa: E731
+    return {"total": v["total"], "gen_total": v["total"], "commit": f(w.commit) * pair("commit_1", "commit_2"),
+            "cross": f(w.cross) * f(v["cross"]), "dist": f(w.dist) * f(v["dist"]), "reg": f(w.reg) * f(v["reg"]),
+            "recon": f(w.recon) * pair("recon_l1", "recon_l2"), "freq": f(w.freq) * pair("freq_1", "freq_2"),
+            "perceptual": f(w.perceptual) * pair("perceptual_1", "perceptual_2")}
+
+
+def _second_step_terms(out):
+    return [(n, out[n]) for n in ("gen_total", "dis_total", "recon", "gen", "freq", "perceptual") if out.get(n) is not None]
+
+
+def _second_step_row(v, w):
+    f = np.float32
+    return {"total": f(v["gen_total"]) + f(v["dis_total"]), "gen_total": v["gen_total"], "recon": f(w.recon) * f(v.get("recon", 0.0)),
+            "freq": f(w.freq) * f(v.get("freq", 0.0)), "perceptual": f(w.perceptual) * f(v.get("perceptual", 0.0)),
+            "gen": f(w.gen) * f(v["gen"]), "dis_total": v["dis_total"], "dis": v["dis_total"]}
+
+
+class _ScalarQueue:
+    """Logged scalars on their way to the host.  push() packs a step's 0-d device tensors into one small tensor and
+    starts its copy into a pinned buffer; a row is handed to `emit` once `lag` later steps have been pushed (by then the
+    throttle has waited for that step's event, so waiting for the copy's own event does not stall the GPU) or on flush()."""
+
+    def __init__(self, emit, lag, cuda):
+        self.emit, self.lag, self.cuda = emit, lag, cuda
+        self.pending = collections.deque()
+        self.age = 0
+
+    def push(self, meta, named):
+        names = [n for n, _ in named]
+        tensors = [t.detach().reshape(()).float() if torch.is_tensor(t) else None for _, t in named]
+        consts = {n: float(t) for (n, t), x in zip(named, tensors) if x is None}
+        names = [n for n, x in zip(names, tensors) if x is not None]
+        packed = torch.stack([x for x in tensors if x is not None])
+        if self.cuda:
+            host = torch.empty(packed.shape, dtype=torch.float32, pin_memory=True)
+            host.copy_(packed, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream())
+        else:
+            host, event = packed.clone(), None
+        self.pending.append((self.age, meta, names, consts, host, event))
+
+    def step(self):
+        """One training step has been enqueued: emit what is `lag` steps old."""
+        self.age += 1
+        while self.pending and self.age - self.pending[0][0] > self.lag:
+            self._pop()
+
+    def flush(self):
+        while self.pending:
+            self._pop()
+
+    def _pop(self):
+        _, meta, names, consts, host, event = self.pending.popleft()
+        if event is not None:
+            event.synchronize()
+        values = dict(consts)
+        values.update({n: np.float32(x) for n, x in zip(names, host.numpy())})
+        self.emit(meta, values)
+
+
+def _rng_state(device):
+    st = {"torch_cpu": torch.get_rng_state(), "python": list(_flatten_py(random.getstate())),
+          "numpy": _numpy_state()}
+    if device.type == "cuda":
+        st["torch_device"] = torch.cuda.get_rng_state(device)
+    return st
+
+
+def _flatten_py(state):
+    version, internal, gauss = state
+    return [int(version), [int(x) for x in internal], gauss]
+
+
+def _numpy_state():
+    name, keys, pos, has_gauss, cached = np.random.get_state()
+    return {"name": name, "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos), "has_gauss": int(has_gauss),
+            "cached_gaussian": float(cached)}
+
+
+def _set_rng_state(st, device):
+    torch.set_rng_state(st["torch_cpu"])
+    version, internal, gauss = st["python"]
+    random.setstate((version, tuple(internal), gauss))
+    n = st["numpy"]
+    np.random.set_state((n["name"], n["keys"].numpy().astype(np.uint32), n["pos"], n["has_gauss"], n["cached_gaussian"]))
+    if device.type == "cuda" and "torch_device" in st:
+        torch.cuda.set_rng_state(st["torch_device"], device)
+
+
+class _RecordingSampler(DistributedSampler):
+    """DistributedSampler that remembers what it handed out: `seen` = [(epoch, this rank's sample indices)]."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.seen = []
+
+    def __iter__(self):
+        indices = list(super().__iter__())
+        self.seen.append((self.epoch, indices))
+        return iter(indices)
+
+
+class InferenceModels:
+    """Encoder and decoder alone, behind the part of the trainers' interface Fit.test() / Fit.export() use: what
+    `training_mode: "inference"` needs (no optimisers, no losses)."""
+
+    def __init__(self, config, device="cuda"):
+        from .config import configure_models
+        self.device = torch.device(device)
+        self.encoder, self.decoder = configure_models(config)
+        self.encoder.to(self.device).eval()
+        self.decoder.to(self.device).eval()
+        self.dict_size = config.model.vqmodel.dict_size
+        self.w = LossWeights()
+
+    def modules(self):
+        return {"encoder": self.encoder, "decoder": self.decoder}
+
+    def optimizers(self):
+        return {}
+
+    def state_dict(self):
+        return trainer_state_dict(self)
+
+    def load_state_dict(self, state):
+        load_trainer_state_dict(self, state)
+
+
+class Fit:
+    """seed: this rank's seed (run.seed_list[rank]: the noise generator); data_seed: the seed every rank shares (run.seed:
+    dataset file order, the distributed sampler's permutation, the loaders' generators); seeds: all ranks' seeds, saved
+    with the hyper-parameters."""
+
+    def __init__(self, config, trainer, logger=None, device="cuda", rank=0, world_size=1, seed=0, seeds=None,
+                 data_seed=None, validate=True, save_checkpoints=True, log=print):
+        self.config, self.trainer, self.logger = config, trainer, logger
+        self.device = torch.device(device)
+        self.rank, self.world_size = int(rank), int(world_size)
+        self.seed = int(seed)
+        self.data_seed = int(data_seed) if data_seed is not None else self.seed
+        self.seeds = list(seeds) if seeds is not None else [self.seed]
+        self.do_validate, self.do_save = validate, save_checkpoints
+        self.print = log
+        self.mode = _get(config.run, "training_mode", "first_step")
+        self.dict_size = config.model.vqmodel.dict_size
+        self.n_epochs = int(_get(config.run, "n_epochs", 1))
+        self.log_every = int(_get(config.run, "log_every_n_steps", DEFAULT_LOG_EVERY_N_STEPS))
+        self.noise_std = float(_get(config.run, "noise_std", DEFAULT_NOISE_STD))
+        self.epoch, self.global_step = 0, 0
+        # generators the run owns, so that a checkpoint can hold them: the training shuffle (and workers' seeds), the
+        # validation shuffle, the second view's additive noise
+        self.train_gen = torch.Generator().manual_seed(self.data_seed)
+        self.val_gen = torch.Generator().manual_seed(self.data_seed + 1)
+        self.noise_gen = torch.Generator(device=self.device).manual_seed(self.seed)
+        self.sampler = None
+        self._loaders = {}
+        throttle = getattr(trainer, "throttle", None)
+        self.queue = _ScalarQueue(self._emit_row, lag=getattr(throttle, "max_inflight", 2), cuda=self.device.type == "cuda")
+
+    # ---------------------------------------------------------------- data
+    def loader(self, mode):
+        if mode not in self._loaders:
+            if mode == "train":
+                if self.world_size > 1:
+                    probe = build_loader(self.config, "train", self.data_seed)
+                    self.sampler = _RecordingSampler(probe.dataset, num_replicas=self.world_size, rank=self.rank,
+                                                     shuffle=True, seed=self.data_seed, drop_last=False)
+                    self.sampler.dataset = None
+                    loader = build_loader(self.config, "train", self.data_seed, sampler=self.sampler, generator=self.train_gen)
+                    self.sampler.dataset = loader.dataset
+                    self._loaders[mode] = loader
+                else:
+                    self._loaders[mode] = build_loader(self.config, "train", self.data_seed, generator=self.train_gen)
+            else:
+                self._loaders[mode] = build_loader(self.config, mode, self.data_seed,
+                                                   generator=self.val_gen if mode == "val" else None)
+        return self._loaders[mode]
+
+    def _to_device(self, batch):
+        image = batch["image"] if isinstance(batch, dict) else batch
+        return image.to(self.device, non_blocking=True)
+
+    # ---------------------------------------------------------------- state
+    def run_state(self):
+        st = {"rng": _rng_state(self.device), "train_generator": self.train_gen.get_state(),
+              "val_generator": self.val_gen.get_state(), "noise_generator": self.noise_gen.get_state(),
+              "sampler_epoch": int(self.sampler.epoch) if self.sampler is not None else -1, "seed": self.seed}
+        return st
+
+    def load_run_state(self, st):
+        if not st:
+            return
+        _set_rng_state(st["rng"], self.device)
+        self.train_gen.set_state(st["train_generator"])
+        self.val_gen.set_state(st["val_generator"])
+        self.noise_gen.set_state(st["noise_generator"])
+        if self.sampler is not None and st.get("sampler_epoch", -1) >= 0:
+            self.sampler.set_epoch(st["sampler_epoch"])
+
+    def save_checkpoint(self, epoch):
+        """rank 0: ckpt-epoch=<epoch:04d>-total_loss=0.00.ckpt in the run directory, then the reference's pruning rule."""
+        os.makedirs(self.logger.log_dir, exist_ok=True)
+        path = os.path.join(self.logger.log_dir, run_logger.checkpoint_name(epoch))
+        ckpt_io.save_run_checkpoint(path, self.trainer.state_dict(), epoch, self.global_step, self.run_state())
+        run_logger.prune_checkpoints(self.logger.log_dir, CKPT_LIMIT_NUM, CKPT_SAVE_INTERVAL)
+        return path
+
+    # ---------------------------------------------------------------- logging
+    def _emit_row(self, meta, values):
+        w = self.trainer.w
+        row = _first_step_row(values, w) if isinstance(w, LossWeights) else _second_step_row(values, w)
+        row = {k: float(v) for k, v in row.items()}
+        row.update(epoch=meta[0], iteration=meta[1])
+        if self.rank == 0 and self.logger is not None:
+            self.logger.log_metrics(row)
+
+    def _log_step(self, out):
+        if (self.global_step + 1) % self.log_every == 0:
+            terms = _first_step_terms(out) if self.mode == "first_step" else _second_step_terms(out)
+            self.queue.push((self.epoch, self.global_step), terms)
+        self.queue.step()
+
+    # ---------------------------------------------------------------- training
+    def fit(self):
+        cfg = self.config
+        if self.mode not in ("first_step", "second_step"):
+            raise ValueError("training_mode %r cannot be trained (inference runs with -m test)" % (self.mode,))
+        start_epoch = 0
+        resume = _get(cfg.run, "resume_checkpoint")
+        run_state = None
+        if resume:
+            self.print("Loading model from {}".format(resume))
+            state, last_epoch, self.global_step, run_state = ckpt_io.load_run_checkpoint(resume)
+            self.trainer.load_state_dict(state)
+            start_epoch = last_epoch + 1
+        if self.rank == 0 and self.logger is not None:
+            self.logger.log_hyperparams(self.seeds)
+        train_loader = self.loader("train")
+        if self.rank == 0 and self.do_validate and _get(cfg.run, "use_validation_sanity_check"):
+            self.validate(start_epoch, limit=SANITY_VAL_BATCHES)
+        if run_state:
+            self.load_run_state(run_state)         # last: nothing between here and the first step draws a random number
+        noise_views = self.mode == "first_step" and isinstance(self.trainer.views, FlipViews) and self.noise_std > 0
+        use_dropblock = bool(_get(cfg.model.vqmodel, "use_dropblock"))
+        # as in bench.py: the step's dependency chain runs on a high-priority stream, the off-chain weight gradients on the
+        # normal-priority side stream of hipops, so the hardware dispatches chain kernels first (VQW_RUN_PRIORITY=0: off)
+        chain = contextlib.nullcontext()
+        if self.device.type == "cuda" and os.environ.get("VQW_RUN_PRIORITY", "1") != "0":
+            stream = torch.cuda.Stream(device=self.device, priority=-1)
+            stream.wait_stream(torch.cuda.current_stream(self.device))
+            chain = torch.cuda.stream(stream)
+        with chain:
+            for epoch in range(start_epoch, self.n_epochs):
+                self.epoch = epoch
+                if self.sampler is not None:
+                    self.sampler.set_epoch(epoch)
+                for batch in train_loader:
+                    image = self._to_device(batch)
+                    if self.mode == "first_step":
+                        noise = None
+                        if noise_views:
+                            noise = torch.randn(image.shape, device=self.device, dtype=torch.float32, generator=self.noise_gen)
+                            noise = ops.affine_(noise, self.noise_std, 0.0)
+                        out = self.trainer.training_step({"image": image}, noise=noise)
+                    else:
+                        out = self.trainer.training_step({"image": image})
+                    self._log_step(out)
+                    self.global_step += 1
+                self.queue.flush()
+                if use_dropblock:
+                    self.trainer.decoder.dropblock.step()          # base.py:185-187
+                if self.rank == 0:
+                    if self.do_validate:
+                        self.validate(epoch)
+                    if self.do_save and self.logger is not None:
+                        self.save_checkpoint(epoch)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        return self
+
+    # ---------------------------------------------------------------- validation
+    @torch.no_grad()
+    def _eval_forward(self, image):
+        enc, dec = self.trainer.encoder, self.trainer.decoder
+        modes = (enc.training, dec.training)
+        enc.eval()
+        dec.eval()
+        try:
+            embed, _, ids = enc(image)
+            recon = dec(embed)
+        finally:
+            enc.train(modes[0])
+            dec.train(modes[1])
+        return recon, ids
+
+    def mosaic(self, image, recon, ids, n_rows):
+        """-> ((n_rows * H, n_cols * W, 3) uint8 picture, (B, K + 1) counts) of one batch: one row per image; CRC (and any
+        dataset without a CT window): image, recon, ids; otherwise lung image, lung recon, mediastinal image, mediastinal
+        recon, ids (single_window_trainer.py:578-638 without the discriminator maps, which are all zero for the PatchGAN)."""
+        dw = dataset_window(self.config)
+        single = self.config.dataset.dataset_name == "CRCDataset" or dw is None
+        labels = ops.export_labels(ids, self.dict_size, index=False)
+        counts = labels.counts.cpu().numpy()
+        if n_rows <= 0:
+            return None, counts
+        if single:
+            grey = [ops.export_grey(image[:n_rows])[0], ops.export_grey(recon[:n_rows])[0]]
+        else:
+            wins = (ops.window_map(dw, LUNG_WINDOW), ops.window_map(dw, MEDIASTINAL_WINDOW))
+            gi, gr = ops.export_grey(image[:n_rows], windows=wins), ops.export_grey(recon[:n_rows], windows=wins)
+            grey = [gi[0], gr[0], gi[1], gr[1]]
+        tiles = [np.repeat(g.cpu().numpy()[..., None], 3, axis=3) for g in grey] + [labels.rgb[:n_rows].cpu().numpy()]
+        rows = [np.concatenate([t[i] for t in tiles], axis=1) for i in range(n_rows)]
+        return np.concatenate(rows, axis=0), counts
+
+    def validate(self, epoch, limit=LIMIT_VAL_BATCHES):
+        """At most `limit` validation batches in eval mode without gradients (rank 0): prints every batch's id histogram and
+        writes <run dir>/<epoch:06d>.png from the last one (the reference saves each batch's figure to the same path)."""
+        if self.rank != 0:
+            return None
+        n_save = int(_get(self.config.save, "n_save_images", 0) or 0)
+        picture = None
+        for i, batch in enumerate(self.loader("val")):
+            if i >= limit:
+                break
+            image = self._to_device(batch)
+            recon, ids = self._eval_forward(image)
+            picture, counts = self.mosaic(image, recon, ids, min(n_save, image.shape[0]))
+            self.print("IDs: ", counts.sum(axis=0))
+        if picture is not None and self.logger is not None:
+            os.makedirs(self.logger.log_dir, exist_ok=True)
+            path = os.path.join(self.logger.log_dir, "%06d.png" % epoch)
+            png.save(path, picture)
+            return path
+        return None
+
+    # ---------------------------------------------------------------- -m test
+    def _load_weights_for_test(self):
+        resume = _get(self.config.run, "resume_checkpoint")
+        if resume:
+            self.print("Loading model from {}".format(resume))
+            state, _, _, _ = ckpt_io.load_run_checkpoint(resume)
+            state = {"modules": state["modules"], "optimizers": {}, "extra": {"init_embed": True}}
+            self.trainer.load_state_dict(state)
+
+    def test(self):
+        """`-m test` for the training modes: Evaluator over the test loader -> result.csv in the run directory."""
+        self._load_weights_for_test()
+        if self.rank != 0:
+            return None
+        ev = Evaluator(self.trainer.encoder, self.trainer.decoder, self.dict_size)
+        result = ev.run(self.loader("test"), self.logger.log_dir)
+        self.print("Test results are saved: {}".format(os.path.join(self.logger.log_dir, "result.csv")))
+        return result
+
+    def export(self):
+        """training_mode 'inference' (single_window_trainer.py:716-779): per test slice, under
+        <save_dir>/<study_name>/<patient_id>/: image_%04d / recon_%04d / label_%04d as .png (the export kernels' bytes: grey
+        over [-1, 1], ids through the palette) and as .nii.gz (float32 image / recon, int32 label; to_nifti orientation).
+        NCCLungDataset: image and recon through the lung window first; CRCDataset: all three flipped upside down."""
+        self._load_weights_for_test()
+        if self.rank != 0:
+            return []
+        cfg = self.config
+        name = cfg.dataset.dataset_name
+        flip = name == "CRCDataset"
+        dw = dataset_window(cfg)
+        lung = ops.window_map(dw, LUNG_WINDOW) if (name == "NCCLungDataset" and dw is not None) else None
+        root = os.path.join(cfg.save.save_dir, cfg.save.study_name)
+        palette = ops.default_palette(self.dict_size)
+        written = []
+        for batch in self.loader("test"):
+            image = self._to_device(batch)
+            recon, ids = self._eval_forward(image)
+            grey_i = ops.export_grey(image, windows=(lung,), flip=flip)[0].cpu().numpy()
+            grey_r = ops.export_grey(recon, windows=(lung,), flip=flip)[0].cpu().numpy()
+            lab = ops.export_labels(ids, self.dict_size, palette=palette, counts=False, flip=flip)
+            index, rgb = lab.index.cpu().numpy(), lab.rgb.cpu().numpy()
+            img_f, rec_f = image[:, 0].cpu().numpy(), recon[:, 0].cpu().numpy()
+            if lung is not None:
+                a, b, lo, hi = (np.float32(v) for v in lung)
+                img_f, rec_f = np.clip(a * img_f + b, lo, hi), np.clip(a * rec_f + b, lo, hi)
+            if flip:
+                img_f, rec_f = img_f[:, ::-1], rec_f[:, ::-1]
+            patient_ids, slice_nums = batch["patient_id"], batch["slice_num"]
+            for i in range(image.shape[0]):
+                out_dir = os.path.join(root, str(patient_ids[i]))
+                os.makedirs(out_dir, exist_ok=True)
+                num = "%04d" % int(slice_nums[i])
+                png.save(os.path.join(out_dir, "image_%s.png" % num), grey_i[i])
+                png.save(os.path.join(out_dir, "recon_%s.png" % num), grey_r[i])
+                png.save(os.path.join(out_dir, "label_%s.png" % num), rgb[i])
+                for stem, arr in (("image", img_f[i].astype(np.float32)), ("recon", rec_f[i].astype(np.float32)),
+                                  ("label", index[i].astype(np.int32))):
+                    nifti.save(np.ascontiguousarray(np.transpose(arr)[::-1, ::-1]), os.path.join(out_dir, "%s_%s.nii.gz" % (stem, num)))
+                written.append(os.path.join(out_dir, num))
+        return written

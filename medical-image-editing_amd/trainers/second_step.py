@@ -47,6 +47,21 @@ class SecondStepTrainer:
             self.dec_reducer = GradientAllReducer(list(reversed([p for p in self.decoder.parameters() if p.requires_grad])))
             self.dis_reducer = GradientAllReducer(list(reversed([p for p in self.dis.parameters() if p.requires_grad])))
 
+    # -- what a run saves and restores (trainers/fit.py); `modules` / `optimizers` are in the reference's order
+    def modules(self):
+        return {"encoder": self.encoder, "decoder": self.decoder, "dis": self.dis}
+
+    def optimizers(self):
+        return {"dec": self.dec_optim, "dis": self.dis_optim}
+
+    def state_dict(self):
+        from .first_step import trainer_state_dict
+        return trainer_state_dict(self)
+
+    def load_state_dict(self, state):
+        from .first_step import load_trainer_state_dict
+        load_trainer_state_dict(self, state)
+
     def test_step(self, batch):
         """{'NMSE', 'SSIM', 'PSNR', 'Entropy'} of one batch through trainers.evaluation.Evaluator (eval mode, no gradients;
         training state untouched)."""

@@ -60,3 +60,64 @@ def save_lightning_style_ckpt(path, encoder=None, decoder=None, dis=None, extra=
     d = {"state_dict": sd}
     d.update(extra or {})
     torch.save(d, path)
+
+
+# ----------------------------------------------------------------------------------------------------
+# checkpoints of this build's own runs (trainers/fit.py): the reference's wire format plus one project-own key
+# ----------------------------------------------------------------------------------------------------
+OPTIMIZER_ORDER = ("enc", "dec", "dis")          # configure_optimizers' list, trainers/base.py:164-183
+MODULE_ORDER = ("encoder", "decoder", "dis")
+RUN_STATE_KEY = "vqw_run_state"                  # not a key of the reference: everything a bit-exact continuation needs
+
+
+def _to_cpu(obj):
+    """Tensors of a nested state moved to the host, values, dtypes and strides as they are."""
+    if torch.is_tensor(obj):
+        return obj.detach().cpu().clone()
+    if isinstance(obj, dict):
+        return {k: _to_cpu(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_cpu(v) for v in obj)
+    return obj
+
+
+def save_run_checkpoint(path, trainer_state, epoch, global_step, run_state=None):
+    """Write `trainer_state` (a trainer's state_dict(): {'modules', 'optimizers', 'extra'}) as a Lightning-style checkpoint:
+    'state_dict' with the attribute prefixes `encoder.` / `decoder.` / `dis.` (plain contiguous tensors, read unchanged by
+    load_first_stage_from_ckpt, load_discriminator_from_ckpt and init_from_ckpt), 'epoch', 'global_step',
+    'optimizer_states' (the reference's list enc, dec, dis without the optimisers the training mode does not own;
+    'optimizer_indices' records which positions of that order are present), and RUN_STATE_KEY = {'trainer': the trainer's
+    `extra`, **run_state}."""
+    sd = {}
+    for name in MODULE_ORDER:
+        for k, v in (trainer_state["modules"].get(name) or {}).items():
+            sd[name + "." + k] = v.detach().cpu().contiguous().clone()
+    present = [i for i, k in enumerate(OPTIMIZER_ORDER) if k in trainer_state["optimizers"]]
+    ckpt = {"state_dict": sd, "epoch": int(epoch), "global_step": int(global_step),
+            "optimizer_states": [_to_cpu(trainer_state["optimizers"][OPTIMIZER_ORDER[i]]) for i in present],
+            "optimizer_indices": present,
+            RUN_STATE_KEY: dict(_to_cpu(run_state or {}), trainer=_to_cpu(trainer_state.get("extra") or {}))}
+    tmp = str(path) + ".tmp"
+    torch.save(ckpt, tmp)
+    import os
+    os.replace(tmp, path)           # a run killed while writing leaves the previous checkpoint, never half a file
+    return ckpt
+
+
+def load_run_checkpoint(path):
+    """-> (trainer_state for a trainer's load_state_dict(), epoch, global_step, run_state) of a file save_run_checkpoint
+    wrote.  A reference checkpoint (no RUN_STATE_KEY, three optimiser states) loads too, with an empty run state."""
+    ckpt = torch.load(path, map_location="cpu")      # tensors and plain containers only: loads with torch's safe unpickler
+    sd = ckpt["state_dict"]
+    modules = {}
+    for name in MODULE_ORDER:
+        sub = {k[len(name) + 1:]: v for k, v in sd.items() if k.startswith(name + ".")}
+        if sub:
+            modules[name] = sub
+    states = ckpt.get("optimizer_states") or []
+    indices = ckpt.get("optimizer_indices", list(range(len(states))))
+    optimizers = {OPTIMIZER_ORDER[i]: s for i, s in zip(indices, states)}
+    run_state = dict(ckpt.get(RUN_STATE_KEY) or {})
+    extra = run_state.pop("trainer", {})
+    return ({"modules": modules, "optimizers": optimizers, "extra": extra}, int(ckpt.get("epoch", 0)),
+            int(ckpt.get("global_step", 0)), run_state)
