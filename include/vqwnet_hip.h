@@ -562,6 +562,32 @@ int vqw_export_grey(const float* x, const float* win, uint8_t* out, int nwin, in
 int vqw_export_labels(const int64_t* ids, const uint8_t* palette, void* index_out, uint8_t* rgb, int32_t* counts, int32_t* err,
                       int B, int H, int W, int K, int flip, void* stream);
 
+/* ---- preprocessing: NIfTI volumes -> per-slice datasets (the reference's src/preprocess/preprocess_crc.py,
+ *      make_crc_testing_dataset.py, preprocess_brats.py).  Added functions only; the ABI stays 9.
+ * vol: the volume as stored, [Z][Y][X] with x fastest (NIfTI's Fortran order), dtype = 0 uint8, 1 int16, 2 uint16, 3 int32,
+ * 4 float32, 5 float64.  A voxel's value is double(stored), then * slope + inter in double when scaled != 0 (nibabel's
+ * get_fdata).  Every operation rounds once (the file is compiled without contraction) and sums run in a fixed order.
+ * vqw_volume_stats: stats [5] doubles = min, max, then over the voxels whose float32(value) > 0: count, mean and population
+ * standard deviation of the float32 values, summed in double (two passes for the deviation; per-workgroup partials, then one
+ * fold: no floating-point atomics, the same bits every run).  ws: vqw_volume_stats_ws_bytes() bytes.
+ * vqw_volume_to_slices: out [Z][S][S] float = PIL's F-mode bilinear Image.resize((S, S)) of every oriented, normalised
+ * slice.  norm 0: float32(v); 1: float32(((v - min) / (max - min)) * 255) in double; 2: (float32(v) - float32(mean)) /
+ * float32(std) in float32, with min, max, mean, std read from stats (device; nullable for norm 0).  orient 0: the slice
+ * v[x, y] as it is (rows along x); 1: np.rot90(slice[::-1]); 2: np.rot90(slice, k=3) (both: Y rows, X columns).  kh [S][ksh]
+ * doubles and bh [S][2] ints (first tap, tap count) are the horizontal pass's normalised coefficients, kv / bv [S][ksv] the
+ * vertical pass's; ksh = 0 / ksv = 0: that pass keeps its size (PIL skips it).  The horizontal pass is rounded to float32
+ * into tmp [Z][rows][S] (nullable when ksv = 0), then the vertical pass; both accumulate in double in index order.
+ * vqw_label_slices: out [Z][S][S] int32 = the oriented slice at rows ytab [S], columns xtab [S] (PIL's NEAREST); relabel 1
+ * writes label 4 as 3 and sets err [1] to 1 when any voxel of the volume already is 3, else err = 0. */
+long vqw_volume_stats_ws_bytes(void);
+int vqw_volume_stats(const void* vol, double* stats, double* ws, int dtype, long n, double slope, double inter, int scaled,
+                     void* stream);
+int vqw_volume_to_slices(const void* vol, const double* stats, const double* kh, const int* bh, const double* kv,
+                         const int* bv, float* tmp, float* out, int dtype, int X, int Y, int Z, int S, int ksh, int ksv,
+                         int norm, int orient, double slope, double inter, int scaled, void* stream);
+int vqw_label_slices(const int32_t* vol, const int* xtab, const int* ytab, int32_t* out, int32_t* err, int X, int Y, int Z,
+                     int S, int orient, int relabel, void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

@@ -3122,3 +3122,156 @@ def export_labels(ids, dict_size, palette=None, index=True, rgb=True, counts=Tru
     _L().vqw_export_labels(ids, pal_dev, idx_t, rgb_t, cnt_t, err, B, H, W, K, int(bool(flip)))
     res = LabelExport(idx_t, rgb_t, cnt_t, err)
     return res.check() if check else res
+
+
+# ---- preprocessing: NIfTI volumes -> slice datasets (csrc/resample.hip) -------------------------------------------------
+VOLUME_DTYPES = {"uint8": 0, "int16": 1, "uint16": 2, "int32": 3, "float32": 4, "float64": 5}
+NORMS = {None: 0, "minmax": 1, "zscore": 2}
+ORIENTATIONS = {None: 0, "crc": 1, "brats": 2}        # crc: np.rot90(s[::-1]); brats: np.rot90(s, k=3)
+_resample_tables = {}
+
+
+def bilinear_coefficients(in_size, out_size):
+    """PIL's precompute_coeffs for its bilinear filter (support 1) over the whole axis, in double: -> (k [out][ksize]
+    float64 normalised coefficients, bounds [out][2] int32 = first tap, tap count).  The filter argument is formed as
+    (x - center + 0.5) * (1.0 / filterscale), the reciprocal taken once, as PIL does."""
+    import numpy as np
+    scale = float(in_size) / float(out_size)
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(np.ceil(support)) * 2 + 1
+    k = np.zeros((out_size, ksize), dtype=np.float64)
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    ss = 1.0 / filterscale
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = np.abs((np.arange(xmax, dtype=np.float64) + xmin - center + 0.5) * ss)
+        w = np.where(w < 1.0, 1.0 - w, 0.0)
+        ww = 0.0
+        for v in w:                                   # PIL's running sum, in index order
+            ww += float(v)
+        if ww != 0.0:
+            w = w / ww
+        k[xx, :xmax] = w
+        bounds[xx] = (xmin, xmax)
+    return k, bounds
+
+
+def nearest_indices(in_size, out_size):
+    """Source index of every output pixel of PIL's NEAREST resize: PIL steps a double coordinate, xo = 0.5 * scale, then
+    xo += scale per pixel, and truncates it (equal to floor((i + 0.5) * in / out) wherever that running sum is exact)."""
+    import numpy as np
+    scale = float(in_size) / float(out_size)
+    idx = np.empty(out_size, dtype=np.int32)
+    xo = 0.0 + scale * 0.5
+    for i in range(out_size):
+        idx[i] = min(int(xo), in_size - 1)
+        xo += scale
+    return idx
+
+
+def _resample_table(kind, in_size, out_size, device):
+    key = (kind, int(in_size), int(out_size), device)
+    tab = _resample_tables.get(key)
+    if tab is None:
+        if kind == "bilinear":
+            k, b = bilinear_coefficients(int(in_size), int(out_size))
+            tab = (torch.from_numpy(k).to(device), torch.from_numpy(b).to(device), k.shape[1])
+        else:
+            tab = torch.from_numpy(nearest_indices(int(in_size), int(out_size))).to(device)
+        torch.cuda.current_stream().synchronize()
+        _resample_tables[key] = tab
+    return tab
+
+
+def _volume_arg(vol, name):
+    if not torch.is_tensor(vol):
+        raise RuntimeError("%s: expected a tensor (got %s)" % (name, type(vol)))
+    code = VOLUME_DTYPES.get(str(vol.dtype).replace("torch.", ""))
+    if code is None:
+        raise RuntimeError("%s: the volume must be one of %s (got %s)" % (name, ", ".join(VOLUME_DTYPES), vol.dtype))
+    if vol.dim() != 3 or vol.numel() == 0:
+        raise RuntimeError("%s: expected a non-empty (Z, Y, X) volume, got shape %s" % (name, tuple(vol.shape)))
+    _dev(vol)
+    return vol.detach().contiguous(), code
+
+
+def _scaling(slope, inter):
+    """nibabel applies scl_slope / scl_inter unless they are the identity; a slope of 0 means 'not set'."""
+    slope, inter = float(slope), float(inter)
+    if slope == 0.0:
+        slope = 1.0
+    return slope, inter, int(slope != 1.0 or inter != 0.0)
+
+
+def volume_stats(vol, slope=1.0, inter=0.0):
+    """vol: (Z, Y, X) device tensor in the dtype the file stores (the NIfTI array with its axes reversed, so x is the
+    fastest) -> (5,) float64 device tensor: min, max of value = double(stored) [* slope + inter], then count, mean and
+    population standard deviation of the float32(value) > 0, summed in double in a fixed order (bit-identical run to run)."""
+    vol, code = _volume_arg(vol, "volume_stats")
+    slope, inter, scaled = _scaling(slope, inter)
+    L = _L()
+    stats = torch.empty(5, dtype=torch.float64, device=vol.device)
+    ws = torch.empty(int(L.vqw_volume_stats_ws_bytes()) // 8, dtype=torch.float64, device=vol.device)
+    L.vqw_volume_stats(vol, stats, ws, code, vol.numel(), slope, inter, scaled)
+    return stats
+
+
+def volume_to_slices(vol, size, norm=None, orient=None, stats=None, slope=1.0, inter=0.0):
+    """vol (Z, Y, X) as volume_stats takes it -> (Z, size, size) float32: every slice normalised (norm 'minmax': ((v - min) /
+    (max - min)) * 255 in double, rounded once to float32; 'zscore': (float32(v) - mean32) / std32; None: float32(v)),
+    oriented (orient 'crc': np.rot90(s[::-1]); 'brats': np.rot90(s, k=3); None: s[x, y]) and resized like PIL's
+    Image.resize((size, size), BILINEAR) in mode F, bit for bit.  stats: ops.volume_stats of the volume (computed here when a
+    normalisation needs it and none is given)."""
+    if norm not in NORMS or orient not in ORIENTATIONS:
+        raise ValueError("volume_to_slices: norm is one of %s, orient one of %s" % (sorted(map(str, NORMS)), sorted(map(str, ORIENTATIONS))))
+    S = int(size)
+    if S < 1:
+        raise ValueError("volume_to_slices: size must be positive (got %d)" % S)
+    n, o = NORMS[norm], ORIENTATIONS[orient]
+    vol, code = _volume_arg(vol, "volume_to_slices")
+    if n and stats is None:
+        stats = volume_stats(vol, slope, inter)
+    if stats is not None:
+        _dev(stats)
+        if stats.dtype != torch.float64 or stats.numel() != 5:
+            raise RuntimeError("volume_to_slices: stats is the (5,) float64 tensor of ops.volume_stats")
+        stats = stats.contiguous()
+    slope, inter, scaled = _scaling(slope, inter)
+    Z, Y, X = vol.shape
+    h, w = (X, Y) if o == 0 else (Y, X)
+    dev = vol.device
+    kh, bh, ksh = _resample_table("bilinear", w, S, dev) if w != S else (None, None, 0)
+    kv, bv, ksv = _resample_table("bilinear", h, S, dev) if h != S else (None, None, 0)
+    tmp = torch.empty((Z, h, S), dtype=torch.float32, device=dev) if ksv else None
+    out = torch.empty((Z, S, S), dtype=torch.float32, device=dev)
+    _L().vqw_volume_to_slices(vol, stats, kh, bh, kv, bv, tmp, out, code, X, Y, Z, S, ksh, ksv, n, o, slope, inter, scaled)
+    return out
+
+
+def label_volume_to_slices(vol, size, orient=None, relabel=False):
+    """vol (Z, Y, X) int32 labels -> (Z, size, size) int32: every oriented slice resized like PIL's NEAREST.  relabel=True is
+    the BraTS training relabel 4 -> 3, and raises ValueError when a voxel of the volume already carries label 3 (the
+    reference's assertion; one small device-to-host copy)."""
+    if not torch.is_tensor(vol) or vol.dtype != torch.int32:
+        raise RuntimeError("label_volume_to_slices: labels must be an int32 tensor (got %s)" % (getattr(vol, "dtype", type(vol)),))
+    if orient not in ORIENTATIONS:
+        raise ValueError("label_volume_to_slices: orient is one of %s" % sorted(map(str, ORIENTATIONS)))
+    S = int(size)
+    if S < 1:
+        raise ValueError("label_volume_to_slices: size must be positive (got %d)" % S)
+    o = ORIENTATIONS[orient]
+    vol, _ = _volume_arg(vol, "label_volume_to_slices")
+    Z, Y, X = vol.shape
+    h, w = (X, Y) if o == 0 else (Y, X)
+    dev = vol.device
+    xtab = _resample_table("nearest", w, S, dev)
+    ytab = _resample_table("nearest", h, S, dev)
+    out = torch.empty((Z, S, S), dtype=torch.int32, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _L().vqw_label_slices(vol, xtab, ytab, out, err, X, Y, Z, S, o, int(bool(relabel)))
+    if relabel and int(err.cpu()[0]):
+        raise ValueError("label_volume_to_slices: the volume already carries label 3; 4 -> 3 would merge two classes")
+    return out

@@ -50,8 +50,8 @@ def save(array, path, affine=None):
         f.write(np.asfortranarray(a).astype(a.dtype.newbyteorder("<"), copy=False).tobytes(order="F"))
 
 
-def load(path):
-    """-> (array as stored, scaled by scl_slope / scl_inter when set -> float64 like nibabel's get_fdata; affine 4x4)."""
+def _read(path):
+    """-> (array as stored, in the file's byte order, Fortran-ordered view of the bytes; scl_slope; scl_inter; affine)."""
     with _open(path, "rb") as f:
         raw = f.read()
     if len(raw) < 352:
@@ -73,12 +73,26 @@ def load(path):
     dt = np.dtype(_DTYPES[code]).newbyteorder(end)
     n = int(np.prod(shape))
     data = np.frombuffer(raw, dtype=dt, count=n, offset=off).reshape(shape, order="F")
-    out = data.astype(np.float64)
-    if slope not in (0.0, 1.0) or inter != 0.0:
-        out = out * (slope if slope != 0.0 else 1.0) + inter
     aff = np.eye(4)
     if struct.unpack_from(end + "h", raw, 254)[0] > 0:
         aff[0] = struct.unpack_from(end + "4f", raw, 280)
         aff[1] = struct.unpack_from(end + "4f", raw, 296)
         aff[2] = struct.unpack_from(end + "4f", raw, 312)
+    return data, slope, inter, aff
+
+
+def load(path):
+    """-> (array as stored, scaled by scl_slope / scl_inter when set -> float64 like nibabel's get_fdata; affine 4x4)."""
+    data, slope, inter, aff = _read(path)
+    out = data.astype(np.float64)
+    if slope not in (0.0, 1.0) or inter != 0.0:
+        out = out * (slope if slope != 0.0 else 1.0) + inter
     return out, aff
+
+
+def load_raw(path):
+    """-> (array in the stored dtype and native byte order, Fortran-ordered as the file holds it; scl_slope; scl_inter;
+    affine 4x4).  Nothing is scaled: value = array * slope + inter applies when slope is not 0 or 1 or inter is not 0, as
+    `load` does it; the preprocess commands do that on the device from the stored dtype."""
+    data, slope, inter, aff = _read(path)
+    return data.astype(data.dtype.newbyteorder("="), order="F", copy=True), float(slope), float(inter), aff
