@@ -426,16 +426,57 @@ int vqw_actnorm_prepare(const double* sums /*[C][2] or NULL*/, double count, flo
                         unsigned char* initialized /*[1] or NULL*/, float* mean_rstd_beta /*[3C]*/, int C, void* stream);
 int vqw_actnorm_loc_grad(const float* dbeta, const float* scale, float* dloc, int C, void* stream);
 /* All spectrally normalised weights of one forward in three launches (two in eval mode).  layers_dev: n_layers records of 16
- * int64 {W, u, v, out, save, t, s, rows, K, Cin, blk1, blk2, blk3, 0, 0, 0}: W / out [rows][K] in OHWI memory order
+ * int64 {W, u, v, out, save, t, s, rows, K, Cin, blk1, blk2, blk3, sv, 0, 0}: W / out [rows][K] in OHWI memory order
  * (K = k*k*Cin), u [rows] and v [K] the module buffers (v in torch's logical (Cin, k, k) order), save [rows + K + 1] receives this
  * forward's u, v (memory order) and sigma for its backward, t [K] and s [rows] scratch.  blkP = first workgroup of the layer in
  * phase P: phase 1 has ceil(K / 64) workgroups per layer, phase 2 `rows`, phase 3 ceil(rows * K / 4096); blocksP their totals.
  * training: v <- normalize(W^T u), u <- normalize(W v) in place first; eval: the stored u, v.  out = W / (u^T W v).
+ * sv (0 = none): one float that receives sigma in training - BigGAN's SN (networks/biggan/layers.py:25-94: buffers u0, sv0, no
+ * stored v) is this training arithmetic with `v` a scratch array; its eval forward iterates too, on a copy of u0.
  * vqw_spectral_norm_bwd: records of 8 int64 {G, weight, save, gW, part, rows, K, blk}: gW = (G - <G, weight> u v^T) / sigma with
  * part [ceil(rows * K / 4096)] doubles of scratch per layer, blk = first workgroup, `blocks` their total; two launches. */
 int vqw_spectral_norm_fwd(const void* layers_dev, int n_layers, int blocks1, int blocks2, int blocks3, int training, float eps,
                           void* stream);
 int vqw_spectral_norm_bwd(const void* grads_dev, int n_layers, int blocks, void* stream);
+
+/* ---- U-Net discriminator (networks/unet_discriminator.py:386-627, BigGAN blocks networks/biggan/layers.py:416-506) and its
+ *      second training step (trainers/single_window_trainer.py:264-432).  Added functions only; the ABI stays 9.
+ * Down-block tail: out [N,H/2,W/2,C] = avgpool2(a) (+ s_low), relu_out = relu(out).  s_low and either output may be NULL.
+ * Backward: g = g_out + g_relu * [relu_out > 0] (either gradient NULL), g_full = g / 4 at the four positions of each window
+ * (d/da), g_low = g (d/ds_low); either may be NULL.  H, W even. */
+int vqw_unet_dtail_fwd(const float* a, const float* s_low, float* out, float* relu_out, int N, int H, int W, int C, void* stream);
+int vqw_unet_dtail_bwd(const float* relu_out, const float* g_out, const float* g_relu, float* g_full, float* g_low, int N, int H,
+                       int W, int C, void* stream);
+/* Up-block tail: out [N,H,W,C] = h + up2x(s_low [N,H/2,W/2,C]); cat [N,H,W,C+Cr] = [relu(out) | relu(res [N,H,W,Cr])] (channel
+ * concat; Cr = 0: no residual): the rectified concat input of the next up block.  out or cat may be NULL.  Backward:
+ * g = g_out + g_cat[.., :C] * [cat[.., :C] > 0]; g_h = g, g_s_low = the sum of g over each 2x2 window, g_res = g_cat[.., C:] *
+ * [cat[.., C:] > 0] (NULL: not wanted). */
+int vqw_unet_utail_fwd(const float* h, const float* s_low, const float* res, float* out, float* cat, int N, int H, int W, int C,
+                       int Cr, void* stream);
+int vqw_unet_utail_bwd(const float* cat, const float* g_out, const float* g_cat, float* g_h, float* g_s_low, float* g_res, int N,
+                       int H, int W, int C, int Cr, void* stream);
+/* Bottleneck head: y[n] = bias + sum_c w[c] * sum_p relu(h[n, p, c]), h [N][HW][C]; backward g_h = gy[n] w[c] [h > 0],
+ * g_w[c] = sum_n gy[n] sum_p relu(h), g_bias = sum_n gy[n] (each may be NULL). */
+int vqw_unet_head_fwd(const float* h, const float* w, const float* bias, float* y, int N, int HW, int C, void* stream);
+int vqw_unet_head_bwd(const float* h, const float* w, const float* gy, float* g_h, float* g_w, float* g_bias, int N, int HW, int C,
+                      void* stream);
+/* CutMix (utils/__init__.py:208-218 with mask = 1 outside the rectangle [y0, y1) x [x0, x1), 0 inside; flip: 1 - mask):
+ * out = image where the mask is 1, recon where it is 0.  [N,H,W,C]. */
+int vqw_cutmix_select(const float* image, const float* recon, float* out, int N, int H, int W, int C, int y0, int y1, int x0, int x1,
+                      int flip, void* stream);
+/* The discriminator half's three losses in one pass over the maps [B,H,W] and bottlenecks [B], the mask given by the rectangle:
+ *   l_dis = hinge_d_loss(r_map, f_map) + hinge_d_loss(r_bottle, f_bottle)          (gan_loss.py:6-10)
+ *   l_cutmix = mean(relu(1 + c_bottle)) + mean(relu(1 - (2 mask - 1) c_map))
+ *   l_consistency = mean((c_map - (mask r_map + (1 - mask) f_map))^2)
+ * Backward: all six gradients from dL/d(l_dis, l_cutmix, l_consistency) (device scalars; NULL = 0). */
+size_t vqw_unet_dis_losses_ws_bytes(long n);
+int vqw_unet_dis_losses_fwd(const float* r_map, const float* f_map, const float* c_map, const float* r_bottle, const float* f_bottle,
+                            const float* c_bottle, float* l_dis, float* l_cutmix, float* l_consistency, void* ws, size_t ws_bytes,
+                            int B, int H, int W, int y0, int y1, int x0, int x1, int flip, void* stream);
+int vqw_unet_dis_losses_bwd(const float* r_map, const float* f_map, const float* c_map, const float* r_bottle, const float* f_bottle,
+                            const float* c_bottle, const float* g_dis, const float* g_cutmix, const float* g_consistency,
+                            float* g_r_map, float* g_f_map, float* g_c_map, float* g_r_bottle, float* g_f_bottle, float* g_c_bottle,
+                            int B, int H, int W, int y0, int y1, int x0, int x1, int flip, void* stream);
 
 /* ---- multi-window reconstruction loss (trainers/multi_window_trainer.py:93-109, base.py:290-314):
  * mean((w(a) - w(b))^2) with w(x) = clamp(alpha * x + beta, lo, hi); gradient w.r.t. a (zero where clamped). */

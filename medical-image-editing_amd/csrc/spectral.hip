@@ -30,7 +30,8 @@ struct SnLayer {                 // 16 x 8 bytes; the table layout is part of th
     float* s;                    // [rows] scratch: W v
     long rows, K, Cin;
     long blk1, blk2, blk3;       // first workgroup of this layer in phases 1, 2, 3
-    long pad_[3];
+    float* sv;                   // [1] or NULL: receives sigma in training (BigGAN's logging buffer sv0)
+    long pad_[2];
 };
 struct SnGrad {                  // 8 x 8 bytes
     const float* G;              // [rows][K] dL/d weight (OHWI)
@@ -118,7 +119,10 @@ __global__ void __launch_bounds__(256) k_sn_scale(const SnLayer* __restrict__ ta
         }
     }
     const float sigma = (float)block_sum_d(a, sm);
-    if (chunk == 0 && threadIdx.x == 0) L.save[L.rows + L.K] = sigma;
+    if (chunk == 0 && threadIdx.x == 0) {
+        L.save[L.rows + L.K] = sigma;
+        if (training && L.sv) L.sv[0] = sigma;
+    }
     const long total = L.rows * L.K, e0 = chunk * SN_CHUNK;
     const long e1 = e0 + SN_CHUNK < total ? e0 + SN_CHUNK : total;
     for (long e = e0 + threadIdx.x; e < e1; e += 256) L.out[e] = L.W[e] / sigma;
@@ -181,7 +185,7 @@ __global__ void k_actnorm_loc_grad(const float* __restrict__ dbeta, const float*
 
 extern "C" int vqw_spectral_norm_fwd(const void* layers_dev, int n_layers, int blocks1, int blocks2, int blocks3, int training,
                                      float eps, void* stream) {
-    static_assert(sizeof(SnLayer) == 128, "layer table layout is part of the ABI: 7 pointers + 6 int64 + 3 spare");
+    static_assert(sizeof(SnLayer) == 128, "layer table layout is part of the ABI: 7 pointers + 6 int64 + sv + 2 spare");
     VQW_CHECK(layers_dev && n_layers > 0 && n_layers <= 64 && blocks1 > 0 && blocks2 > 0 && blocks3 > 0 && eps > 0.f,
               "vqw_spectral_norm_fwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;

@@ -2761,7 +2761,7 @@ class _SpectralNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, training, eps, n, *ts):
-        ws, us, vs = ts[:n], ts[n:2 * n], ts[2 * n:]
+        ws, us, vs, svs = ts[:n], ts[n:2 * n], ts[2 * n:3 * n], ts[3 * n:]       # svs: none, or one per layer (BigGAN's sv0)
         _dev(*ts)
         dev = ws[0].device
         dims = []
@@ -2779,11 +2779,12 @@ class _SpectralNorm(torch.autograd.Function):
         scratch = torch.empty(sum(2 * (rows + K) + 1 for rows, K, _ in dims), dtype=torch.float32, device=dev)
         table, off, b1, b2, b3 = [], scratch.data_ptr(), 0, 0, 0
         saves = []
-        for w, u, v, o, (rows, K, cin) in zip(ws, us, vs, outs, dims):
+        for i, (w, u, v, o, (rows, K, cin)) in enumerate(zip(ws, us, vs, outs, dims)):
             save, t, s_ = off, off + 4 * (rows + K + 1), off + 4 * (rows + 2 * K + 1)
             off += 4 * (2 * (rows + K) + 1)
             saves.append(save)
-            table.append((w.data_ptr(), u.data_ptr(), v.data_ptr(), o.data_ptr(), save, t, s_, rows, K, cin, b1, b2, b3, 0, 0, 0))
+            table.append((w.data_ptr(), u.data_ptr(), v.data_ptr(), o.data_ptr(), save, t, s_, rows, K, cin, b1, b2, b3,
+                          svs[i].data_ptr() if svs else 0, 0, 0))
             b1 += -(-K // SN_COLS)
             b2 += rows
             b3 += -(-(rows * K) // SN_CHUNK)
@@ -2816,17 +2817,32 @@ class _SpectralNorm(torch.autograd.Function):
             tab = _upload_table(table, dev)
             _L().vqw_spectral_norm_bwd(tab, len(todo), blk)
             tab.record_stream(torch.cuda.current_stream())
-        return (None, None, None) + tuple(grads) + (None,) * (2 * n)
+        return (None, None, None) + tuple(grads) + (None,) * (len(ctx.needs_input_grad) - 3 - n)
 
 
-def spectral_norm_weights(weight_origs, us, vs, training, eps=1e-12):
+def spectral_norm_weights(weight_origs, us, vs, training, eps=1e-12, svs=None, biggan=False):
     """torch.nn.utils.spectral_norm's forward (n_power_iterations=1, dim=0) for a list of conv weights (logical OIHW, OHWI in
     memory) in a number of launches that does not depend on the list's length.  training: v <- normalize(W^T u),
     u <- normalize(W v) in place (no gradient) before sigma = u^T W v; eval: the stored u, v.  -> [W / sigma] as OHWI tensors;
-    backward: (G - <G, weight> u v^T) / sigma with the u, v, sigma of that forward."""
+    backward: (G - <G, weight> u v^T) / sigma with the u, v, sigma of that forward.
+
+    biggan=True is the SN of networks/biggan/layers.py:25-94 (one singular vector, one iteration): `us` are the buffers u0
+    (1, Cout), `vs` is ignored (v is scratch), `svs` the logging buffers sv0 (1); a 2-D weight (SNLinear) is a (rows, K, 1, 1)
+    one.  Every forward iterates; training stores u0 and sv0, eval iterates on a copy and stores nothing."""
     n = len(weight_origs)
     if n == 0:
         return []
+    if biggan:
+        if svs is None or not (len(us) == len(svs) == n):
+            raise RuntimeError("spectral_norm_weights(biggan=True): one u0 and one sv0 per weight")
+        _dev(*weight_origs)
+        w4 = [w if w.dim() == 4 else w.view(w.shape[0], -1, 1, 1) for w in weight_origs]
+        vs = torch.empty(sum(w[0].numel() for w in w4), dtype=torch.float32, device=w4[0].device).split([w[0].numel() for w in w4])
+        if not training:
+            us = torch.cat([u.reshape(-1) for u in us]).split([u.numel() for u in us])
+            svs = ()
+        outs = _SpectralNorm.apply(True, float(eps), n, *w4, *us, *vs, *svs)
+        return [o.view(w.shape) if w.dim() != 4 else o for o, w in zip(outs, weight_origs)]
     if not (len(us) == len(vs) == n):
         raise RuntimeError("spectral_norm_weights: one u and one v per weight")
     return list(_SpectralNorm.apply(bool(training), float(eps), n, *weight_origs, *us, *vs))
@@ -2834,6 +2850,190 @@ def spectral_norm_weights(weight_origs, us, vs, training, eps=1e-12):
 
 def spectral_norm_weight(weight_orig, u, v, training, eps=1e-12):
     return spectral_norm_weights([weight_orig], [u], [v], training, eps)[0]
+
+
+# ----------------------------------------------------------------------------------------------
+# U-Net discriminator (csrc/unet_dis.hip): block tails, bottleneck head, CutMix, the discriminator half's losses
+# ----------------------------------------------------------------------------------------------
+class _UNetDownTail(torch.autograd.Function):
+    """(out, relu) with out = avgpool2(a) (+ s_low), relu = ReLU(out); one pass each way."""
+
+    @staticmethod
+    def forward(ctx, a, s_low, want_out, want_relu):
+        _dev(a, s_low)
+        a = nhwc(a)
+        s_low = nhwc(s_low) if s_low is not None else None
+        N, C, H, W = a.shape
+        if H % 2 or W % 2:
+            raise RuntimeError("unet_down_tail: H and W must be even (got %d x %d)" % (H, W))
+        if s_low is not None and tuple(s_low.shape) != (N, C, H // 2, W // 2):
+            raise RuntimeError("unet_down_tail: shortcut %s does not match %s at half the size" % (tuple(s_low.shape), tuple(a.shape)))
+        out = empty_nhwc(N, C, H // 2, W // 2, a) if want_out else None
+        relu = empty_nhwc(N, C, H // 2, W // 2, a) if want_relu else None
+        _L().vqw_unet_dtail_fwd(a, s_low, out, relu, N, H, W, C)
+        ctx.save_for_backward(relu)
+        ctx.cfg = (N, C, H, W, s_low is not None)
+        ctx.set_materialize_grads(False)
+        return out, relu
+
+    @staticmethod
+    def backward(ctx, g_out, g_relu):
+        if g_out is None and g_relu is None:
+            return (None,) * 4
+        (relu,) = ctx.saved_tensors
+        N, C, H, W, has_s = ctx.cfg
+        g_out = nhwc(g_out) if g_out is not None else None
+        g_relu = nhwc(g_relu) if g_relu is not None else None
+        need_low = has_s and ctx.needs_input_grad[1]
+        like = g_out if g_out is not None else g_relu
+        g_full = empty_nhwc(N, C, H, W, like) if ctx.needs_input_grad[0] else None
+        g_low = empty_nhwc(N, C, H // 2, W // 2, like) if need_low else None
+        if g_full is not None or g_low is not None:
+            _L().vqw_unet_dtail_bwd(relu, g_out, g_relu, g_full, g_low, N, H, W, C)
+        return g_full, g_low, None, None
+
+
+def unet_down_tail(a, s_low=None, want_out=True, want_relu=True):
+    """DBlock tail (biggan/layers.py:503-506 with AvgPool2d(2)): out = avgpool2(a) (+ s_low) and ReLU(out), the next block's
+    conv1 input.  s_low is the 1x1 shortcut evaluated on the pooled block input.  -> (out or None, relu or None)."""
+    return _UNetDownTail.apply(a, s_low, bool(want_out), bool(want_relu))
+
+
+class _UNetUpTail(torch.autograd.Function):
+    """(out, cat) with out = h + up2x(s_low) and cat = [ReLU(out) | ReLU(res)] (channel concat), one pass each way."""
+
+    @staticmethod
+    def forward(ctx, h, s_low, res, want_out, want_cat):
+        _dev(h, s_low, res)
+        h, s_low = nhwc(h), nhwc(s_low)
+        res = nhwc(res) if res is not None else None
+        N, C, H, W = h.shape
+        if H % 2 or W % 2 or tuple(s_low.shape) != (N, C, H // 2, W // 2):
+            raise RuntimeError("unet_up_tail: shortcut %s does not match %s at half the size" % (tuple(s_low.shape), tuple(h.shape)))
+        Cr = 0
+        if res is not None:
+            if not want_cat or res.shape[0] != N or tuple(res.shape[2:]) != (H, W):
+                raise RuntimeError("unet_up_tail: residual %s does not match %s" % (tuple(res.shape), tuple(h.shape)))
+            Cr = res.shape[1]
+        out = empty_nhwc(N, C, H, W, h) if want_out else None
+        cat = empty_nhwc(N, C + Cr, H, W, h) if want_cat else None
+        _L().vqw_unet_utail_fwd(h, s_low, res, out, cat, N, H, W, C, Cr)
+        ctx.save_for_backward(cat)
+        ctx.cfg = (N, C, H, W, Cr)
+        ctx.set_materialize_grads(False)
+        return out, cat
+
+    @staticmethod
+    def backward(ctx, g_out, g_cat):
+        if g_out is None and g_cat is None:
+            return (None,) * 5
+        (cat,) = ctx.saved_tensors
+        N, C, H, W, Cr = ctx.cfg
+        g_out = nhwc(g_out) if g_out is not None else None
+        g_cat = nhwc(g_cat) if g_cat is not None else None
+        like = g_out if g_out is not None else g_cat
+        g_h = empty_nhwc(N, C, H, W, like)
+        g_s = empty_nhwc(N, C, H // 2, W // 2, like)
+        g_res = empty_nhwc(N, Cr, H, W, like) if (Cr and g_cat is not None and ctx.needs_input_grad[2]) else None
+        _L().vqw_unet_utail_bwd(cat, g_out, g_cat, g_h, g_s, g_res, N, H, W, C, Cr)
+        return g_h, g_s, g_res, None, None
+
+
+def unet_up_tail(h, s_low, res=None, want_out=True, want_cat=True):
+    """GBlock2 tail (biggan/layers.py:449-457): out = h + up2x(s_low), s_low the 1x1 shortcut at the low resolution, and the
+    rectified concat [ReLU(out) | ReLU(res)] that the next up block's up-sampled 3x3 reads.  -> (out or None, cat or None)."""
+    return _UNetUpTail.apply(h, s_low, res, bool(want_out), bool(want_cat))
+
+
+class _UNetHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, w, bias):
+        _dev(h, w, bias)
+        h = nhwc(h)
+        N, C, H, W = h.shape
+        if w.numel() != C or (bias is not None and bias.numel() != 1):
+            raise RuntimeError("unet_bottleneck_head: weight of %d entries for %d channels" % (w.numel(), C))
+        w = _flat(w)
+        y = torch.empty((N, 1), dtype=torch.float32, device=h.device)
+        _L().vqw_unet_head_fwd(h, w, bias, y, N, H * W, C)
+        ctx.save_for_backward(h, w)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        h, w = ctx.saved_tensors
+        N, C, H, W = h.shape
+        gy = _flat(gy)
+        g_h = torch.empty_like(h, memory_format=CL) if ctx.needs_input_grad[0] else None
+        g_w = torch.empty_like(w) if ctx.needs_input_grad[1] else None
+        g_b = torch.empty(1, dtype=torch.float32, device=h.device) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        if g_h is not None or g_w is not None or g_b is not None:
+            _L().vqw_unet_head_bwd(h, w, gy, g_h, g_w, g_b, N, H * W, C)
+        return g_h, g_w, g_b
+
+
+def unet_bottleneck_head(h, weight, bias=None):
+    """linear(sum(relu(h), [2, 3])) with one output (unet_discriminator.py:600-604) -> (N, 1)."""
+    return _UNetHead.apply(h, weight, bias)
+
+
+def _box(box, H, W):
+    (y0, y1), (x0, x1) = box
+    y0, y1, x0, x1 = int(y0), int(y1), int(x0), int(x1)
+    if not (0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W):
+        raise RuntimeError("cutmix rectangle [%d, %d) x [%d, %d) outside %d x %d" % (y0, y1, x0, x1, H, W))
+    return y0, y1, x0, x1
+
+
+def cutmix_select(image, recon, box, flip):
+    """mask_src_tgt(image, recon, mask) (utils/__init__.py:216-218) for mask = 1 outside the rectangle box = ((y0, y1), (x0, x1))
+    and 0 inside, 1 - mask when `flip`.  No gradient (the reference detaches the result)."""
+    _dev(image, recon)
+    image, recon = nhwc(image.detach()), nhwc(recon.detach())
+    if image.shape != recon.shape:
+        raise RuntimeError("cutmix_select: shape mismatch %s vs %s" % (tuple(image.shape), tuple(recon.shape)))
+    N, C, H, W = image.shape
+    out = torch.empty_like(image, memory_format=CL)
+    _L().vqw_cutmix_select(image, recon, out, N, H, W, C, *_box(box, H, W), int(bool(flip)))
+    return out
+
+
+class _UNetDisLosses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r_map, f_map, c_map, r_b, f_b, c_b, box, flip):
+        _dev(r_map, f_map, c_map, r_b, f_b, c_b)
+        B, C, H, W = r_map.shape
+        if C != 1 or f_map.shape != r_map.shape or c_map.shape != r_map.shape or not (r_b.numel() == f_b.numel() == c_b.numel() == B):
+            raise RuntimeError("unet_dis_losses: maps (B, 1, H, W) and bottlenecks (B, 1) expected")
+        maps = [nhwc(t) for t in (r_map, f_map, c_map)]
+        bots = [_flat(t) for t in (r_b, f_b, c_b)]
+        L = _L()
+        losses = [torch.empty((), dtype=torch.float32, device=r_map.device) for _ in range(3)]
+        ws = _ws(L.vqw_unet_dis_losses_ws_bytes(B * H * W), r_map)
+        ctx.cfg = (B, H, W) + _box(box, H, W) + (int(bool(flip)),)
+        L.vqw_unet_dis_losses_fwd(*maps, *bots, *losses, ws, ws.numel(), *ctx.cfg)
+        ctx.save_for_backward(*maps, *bots)
+        ctx.shapes = (r_b.shape, f_b.shape, c_b.shape)
+        ctx.set_materialize_grads(False)
+        return tuple(losses)
+
+    @staticmethod
+    def backward(ctx, g_dis, g_cutmix, g_cons):
+        if g_dis is None and g_cutmix is None and g_cons is None:
+            return (None,) * 8
+        t = ctx.saved_tensors
+        gl = [g.contiguous().float() if g is not None else None for g in (g_dis, g_cutmix, g_cons)]
+        gm = [torch.empty_like(x, memory_format=CL) for x in t[:3]]
+        gb = [torch.empty(sh, dtype=torch.float32, device=t[0].device) for sh in ctx.shapes]
+        _L().vqw_unet_dis_losses_bwd(*t, *gl, *gm, *gb, *ctx.cfg)
+        return (*gm, *gb, None, None)
+
+
+def unet_dis_losses(r_map, f_map, cutmix_map, r_bottle, f_bottle, cutmix_bottle, box, flip):
+    """(l_dis, l_cutmix, l_consistency) of single_window_trainer.py:324-349 in one pass; the mask is given by the rectangle
+    box = ((y0, y1), (x0, x1)) (0 inside, 1 outside) and `flip` (1 - mask).  Gradients reach all six inputs."""
+    return _UNetDisLosses.apply(r_map, f_map, cutmix_map, r_bottle, f_bottle, cutmix_bottle, box, bool(flip))
 
 
 class _Hinge(torch.autograd.Function):

@@ -8,3 +8,4 @@ from .vq import VQ  # noqa: F401
 from .vqwnet import VQWNet  # noqa: F401
 from .random_transform import RandomTransform  # noqa: F401
 from .discriminator import NLayerDiscriminator  # noqa: F401
+from .unet_discriminator import UNetDiscriminator  # noqa: F401

@@ -164,7 +164,7 @@ def worker(config, args, training_mode, rank, world_size, seed):
                                                multi_window=None if args.multiwindow else False)
         elif training_mode == "second_step":
             if args.multiwindow:
-                raise NotImplementedError("a multi-window second step uses the U-Net discriminator, which is not built")
+                raise NotImplementedError("a multi-window second step (-w with training_mode second_step) is not built")
             trainer = build_second_step_trainer(config, device=device, data_parallel=distributed)
         else:
             trainer = InferenceModels(config, device=device)

@@ -11,6 +11,8 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
     config.{enc_optim, dec_optim, dis_optim}.{lr, b1, b2, weight_decay}
     config.model.dis.{model_name, n_filters, n_layers, normalization, apply_spectral_norm}, config.loss.{loss_weight.{gen, dis},
                  n_inner_loops, dis_loss_type}, config.run.{first_stage_ckpt_path, discriminator_ckpt_path}   (second_step)
+    config.model.dis.{D_ch, D_wide, D_attn, resolution}, config.loss.{loss_weight.{unet_perceptual, cutmix, consistency},
+                 use_unet_perceptual_loss, use_l1_loss}                  (second_step with model_name 'UNetDiscriminator')
     config.augmentation.{modules, ...}            (optional: absent -> the exact-integer flip views of the benchmark)
     config.dataset.{window_width, window_center, window_scale}, config.loss.{recon_weights, freq_weights, percep_weights}
                  (multi-window runs, -w)
@@ -30,12 +32,13 @@ project: a path to an LPIPS state dict / reference checkpoint, or a two-element 
 """
 from functions import EmbeddingLoss, FocalFrequencyLoss, LPIPSLoss, VGGLoss
 from hipops import Adam
-from networks import UNetEncoder, UNetDecoder, RandomTransform, NLayerDiscriminator
+from networks import UNetEncoder, UNetDecoder, RandomTransform, NLayerDiscriminator, UNetDiscriminator
 from utils import apply_spectral_norm
 from utils.checkpoint import load_first_stage_from_ckpt, load_discriminator_from_ckpt
 
 from .first_step import FirstStepTrainer, FlipViews, RandomTransformViews, LossWeights
 from .second_step import SecondStepTrainer, GanLossWeights
+from .second_step_unet import UNetSecondStepTrainer, UNetGanLossWeights
 from .evaluation import Evaluator
 
 
@@ -74,15 +77,22 @@ def configure_models(config):
     return encoder, decoder
 
 
+_UNET_DIS_KEYS = ("D_ch", "D_wide", "D_attn", "resolution")
+
+
 def configure_discriminator(config):
-    """-> the PatchGAN discriminator as base.py:249-259 builds it: NLayerDiscriminator over config.model.dis, with spectral
-    normalisation on its convolutions when dis.apply_spectral_norm is set."""
+    """-> the discriminator as base.py:239-259 builds it.  PatchGAN: NLayerDiscriminator over config.model.dis, with spectral
+    normalisation on its convolutions when dis.apply_spectral_norm is set.  model_name 'UNetDiscriminator': the U-Net
+    discriminator over config.model.dis.{D_ch, D_wide, D_attn, resolution} (only the 512 arch, no attention)."""
     d = config.model.dis
     name = _get(d, "model_name", "NLayerDiscriminator")
     if name == "UNetDiscriminator":
-        raise NotImplementedError("model.dis.model_name 'UNetDiscriminator' is not built: its residual down / up blocks, "
-                                  "self-attention and per-pixel output head have no HIP kernels here; only "
-                                  "'NLayerDiscriminator' (batchnorm or actnorm, with or without spectral norm) is")
+        missing = [k for k in _UNET_DIS_KEYS if not hasattr(d, k)]
+        if missing:
+            raise NotImplementedError("model.dis.model_name 'UNetDiscriminator' needs model.dis.{%s} (missing: %s), as the "
+                                      "reference's constructor call does (base.py:239-247)" % (", ".join(_UNET_DIS_KEYS), ", ".join(missing)))
+        return UNetDiscriminator(in_channels=config.model.vqmodel.in_channels, D_ch=d.D_ch, D_wide=bool(d.D_wide), D_attn=str(d.D_attn),
+                                 resolution=d.resolution, unconditional=True)
     if name != "NLayerDiscriminator":
         raise NotImplementedError("model.dis.model_name %r is unknown" % (name,))
     dis = NLayerDiscriminator(in_channels=config.model.vqmodel.in_channels, out_channels=1, n_filters=d.n_filters,
@@ -97,6 +107,13 @@ def gan_loss_weights(config):
     namedtuple's default."""
     w = config.loss.loss_weight
     return GanLossWeights(**{k: float(_get(w, k) or 0.0) for k in GanLossWeights._fields if hasattr(w, k)})
+
+
+def unet_gan_loss_weights(config):
+    """-> UNetGanLossWeights from config.loss.loss_weight.{recon, gen, dis, freq, perceptual, unet_perceptual, cutmix,
+    consistency}; an absent key keeps the namedtuple's default."""
+    w = config.loss.loss_weight
+    return UNetGanLossWeights(**{k: float(_get(w, k) or 0.0) for k in UNetGanLossWeights._fields if hasattr(w, k)})
 
 
 def _adam_kwargs(o):
@@ -235,7 +252,8 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
 def build_second_step_trainer(config, device="cuda", data_parallel=None, first_stage_ckpt_path=None,
                               discriminator_ckpt_path=None):
     """config -> SecondStepTrainer (the `second_step` training mode of run_vqwnet.py with the PatchGAN discriminator,
-    single_window_trainer.py:434-488).  The first-stage weights (encoder strictly, decoder non-strictly) and, optionally, the
+    single_window_trainer.py:434-488) or, when model.dis names the U-Net discriminator, UNetSecondStepTrainer
+    (:264-432).  The first-stage weights (encoder strictly, decoder non-strictly) and, optionally, the
     discriminator's come from the path arguments, else from config.run.first_stage_ckpt_path / discriminator_ckpt_path, as
     TrainerBase.__init__ loads them (base.py:79-83).  Multi-window second steps train the U-Net discriminator in the
     reference and are not built."""
@@ -248,7 +266,7 @@ def build_second_step_trainer(config, device="cuda", data_parallel=None, first_s
     if loss_type != "hinge_d_loss":
         raise NotImplementedError("loss.dis_loss_type %r: only 'hinge_d_loss' is built (single_window_trainer.py:478)" % (loss_type,))
     if _get(c, "recon_weights") is not None and _get(_get(config, "dataset"), "window_width") is not None:
-        raise NotImplementedError("a multi-window second step uses the U-Net discriminator, which is not built")
+        raise NotImplementedError("a multi-window second step (loss.recon_weights with dataset.window_width) is not built")
     encoder, decoder = configure_models(config)
     dis = configure_discriminator(config)
     first = first_stage_ckpt_path or _get(config.run, "first_stage_ckpt_path")
@@ -259,6 +277,13 @@ def build_second_step_trainer(config, device="cuda", data_parallel=None, first_s
         load_discriminator_from_ckpt(dck, dis)
     if data_parallel is None:
         data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    if isinstance(dis, UNetDiscriminator):          # single_window_trainer.py:264-432
+        return UNetSecondStepTrainer(
+            encoder, decoder, dis=dis, loss_weight=unet_gan_loss_weights(config), n_inner_loops=int(_get(c, "n_inner_loops") or 1),
+            device=device, data_parallel=data_parallel, frequency_loss=configure_frequency_loss(config),
+            perceptual_loss=configure_perceptual_loss(config), dec_optim=_adam_kwargs(config.dec_optim),
+            dis_optim=_adam_kwargs(config.dis_optim), use_recon_loss=bool(_get(c, "use_recon_loss", True)),
+            use_unet_perceptual_loss=bool(_get(c, "use_unet_perceptual_loss")), use_l1_loss=bool(_get(c, "use_l1_loss")))
     return SecondStepTrainer(
         encoder, decoder, dis=dis, loss_weight=gan_loss_weights(config), n_inner_loops=int(_get(c, "n_inner_loops") or 1),
         device=device, data_parallel=data_parallel, frequency_loss=configure_frequency_loss(config),

@@ -85,11 +85,18 @@ def _first_step_row(v, w):
 
 
 def _second_step_terms(out):
-    return [(n, out[n]) for n in ("gen_total", "dis_total", "recon", "gen", "freq", "perceptual") if out.get(n) is not None]
+    names = ("gen_total", "dis_total", "recon", "gen", "freq", "perceptual", "unet_perceptual", "dis", "cutmix", "consistency")
+    return [(n, out[n]) for n in names if out.get(n) is not None]
 
 
 def _second_step_row(v, w):
     f = np.float32
+    if hasattr(w, "cutmix"):         # the U-Net discriminator's step: single_window_trainer.py:361-374
+        return {"total": f(v["gen_total"]) + f(v["dis_total"]), "gen_total": v["gen_total"], "recon": f(w.recon) * f(v.get("recon", 0.0)),
+                "freq": f(w.freq) * f(v.get("freq", 0.0)), "perceptual": f(w.perceptual) * f(v.get("perceptual", 0.0)),
+                "gen": f(w.gen) * f(v["gen"]), "unet_perceptual": f(w.unet_perceptual) * f(v.get("unet_perceptual", 0.0)),
+                "dis_total": v["dis_total"], "dis": f(w.dis) * f(v["dis"]), "cutmix": f(w.cutmix) * f(v["cutmix"]),
+                "consistency": f(w.consistency) * f(v["consistency"])}
     return {"total": f(v["gen_total"]) + f(v["dis_total"]), "gen_total": v["gen_total"], "recon": f(w.recon) * f(v.get("recon", 0.0)),
             "freq": f(w.freq) * f(v.get("freq", 0.0)), "perceptual": f(w.perceptual) * f(v.get("perceptual", 0.0)),
             "gen": f(w.gen) * f(v["gen"]), "dis_total": v["dis_total"], "dis": v["dis_total"]}

@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""The second training step with the U-Net discriminator (configs/second_step_unet_512.json) on one GPU, one JSON line per
+measurement:
+
+  step      ms per step (median and all windows of --steps steps after --warmup steps) and its split into the generator half
+            (up to and including the decoder's Adam step) and the discriminator half, from HIP events on the launch stream
+  kernels   each HBM-bound kernel of csrc/unet_dis.hip alone at the config's largest shape, HIP events around --reps launches:
+            ms and achieved bytes/s, bytes = the tensors it reads and writes, once each
+
+    python tools/unet_step_bench.py [--steps 10] [--warmup 4] [--windows 5] [--reps 50]
+
+The share of the step spent in convolution kernels comes from a kernel trace of the same step:
+
+    rocprofv3 --kernel-trace --stats -d prof -o t -- python tools/unet_step_bench.py --only-step --windows 1
+    python tools/unet_step_bench.py --stats prof/.../t_kernel_stats.csv
+"""
+import argparse, csv, json, os, re, statistics, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "medical-image-editing_amd"))
+
+CONV = re.compile(r"k_conv_|k_pw_|k_stem_|k_head_|k_wino_|k_pack_|k_input_grad_gather|k_reduce_|k_fold_multi|k_collapse_up|k_bias_grad")
+OWN = re.compile(r"k_dtail_|k_utail_|k_bottleneck_|k_cutmix_select|k_dis_losses_|k_sn_")
+
+
+def stats(path):
+    rows = list(csv.DictReader(open(path)))
+    total = sum(float(r["TotalDurationNs"]) for r in rows)
+    conv = sum(float(r["TotalDurationNs"]) for r in rows if CONV.search(r["Name"]))
+    own = {}
+    for r in rows:
+        m = OWN.search(r["Name"])
+        if m:
+            name = re.search(r"k_\w+", r["Name"]).group(0)
+            own[name] = round(own.get(name, 0.0) + float(r["TotalDurationNs"]) / 1e6, 3)
+    print(json.dumps(dict(what="kernel time of the traced run", total_ms=round(total / 1e6, 2), convolution_ms=round(conv / 1e6, 2),
+                          convolution_share=round(conv / total, 4), unet_dis_and_spectral_ms=own)))
+
+
+def step_rows(args):
+    import torch
+    from utils import load_json
+    from trainers import build_second_step_trainer
+    c = load_json(os.path.join(ROOT, "configs", "second_step_unet_512.json"))
+    torch.manual_seed(0)
+    tr = build_second_step_trainer(c, device="cuda")
+    B, S = c.dataset.batch_size, c.dataset.image_size
+    imgs = [torch.rand(B, 1, S, S, device="cuda") * 2 - 1 for _ in range(4)]
+    mids = []
+    dec_step = tr.dec_optim.step
+
+    def step_and_mark(*a, **k):                 # the generator half ends with the decoder's Adam step
+        r = dec_step(*a, **k)
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        mids.append(e)
+        return r
+    tr.dec_optim.step = step_and_mark
+    for i in range(args.warmup):
+        tr.training_step({"image": imgs[i % 4]})
+    torch.cuda.synchronize()
+    windows, gen, dis = [], [], []
+    for _ in range(args.windows):
+        del mids[:]
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        marks[0].record()
+        for i in range(args.steps):
+            tr.training_step({"image": imgs[i % 4]})
+            marks[i + 1].record()
+        torch.cuda.synchronize()
+        windows.append(marks[0].elapsed_time(marks[-1]) / args.steps)
+        gen.append(sum(marks[i].elapsed_time(mids[i]) for i in range(args.steps)) / args.steps)
+        dis.append(sum(mids[i].elapsed_time(marks[i + 1]) for i in range(args.steps)) / args.steps)
+    print(json.dumps(dict(what="step", config="second_step_unet_512", batch=B, steps=args.steps, ms_per_step=round(statistics.median(windows), 2),
+                          windows=[round(v, 2) for v in windows], generator_half_ms=round(statistics.median(gen), 2),
+                          discriminator_half_ms=round(statistics.median(dis), 2))), flush=True)
+    return c
+
+
+def kernel_rows(args, c):
+    import torch
+    from hipops import ops
+    L = ops._L()
+    B, S, ch = c.dataset.batch_size, c.dataset.image_size, c.model.dis.D_ch
+    dev = "cuda"
+
+    def t(*shape):
+        return torch.randn(*shape, device=dev)
+
+    def timed(name, shape, nbytes, fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / args.reps
+        print(json.dumps(dict(what="kernel", kernel=name, shape=shape, ms=round(ms, 4), mbytes=round(nbytes / 1e6, 1),
+                              tbytes_per_s=round(nbytes / ms / 1e9, 2))), flush=True)
+
+    f = 4 * B                                    # bytes per pixel and channel over the batch
+    # block 0's tail: (B, ch, 512, 512) -> 256 x 256, shortcut added, both outputs
+    C, H = ch, S
+    a, s, out, r = t(B, H, H, C), t(B, H // 2, H // 2, C), t(B, H // 2, H // 2, C), t(B, H // 2, H // 2, C)
+    gf, gl = t(B, H, H, C), t(B, H // 2, H // 2, C)
+    px = H * H * C
+    timed("unet_dtail_fwd", [B, C, H, H], f * px * (1 + 3 / 4), lambda: L.vqw_unet_dtail_fwd(a, s, out, r, B, H, H, C))
+    timed("unet_dtail_bwd", [B, C, H, H], f * px * (1 + 4 / 4), lambda: L.vqw_unet_dtail_bwd(r, out, s, gf, gl, B, H, H, C))
+    # the pooling of the 1-channel input (scalar accesses)
+    x1, p1 = t(B, S, S, 1), t(B, S // 2, S // 2, 1)
+    timed("unet_dtail_fwd (pool only, C = 1)", [B, 1, S, S], f * S * S * (1 + 1 / 4), lambda: L.vqw_unet_dtail_fwd(x1, None, p1, None, B, S, S, 1))
+    # block 13's tail (no concat) and block 12's (concat with the output of block 0) 
+    h, sl, o = t(B, S, S, ch), t(B, S // 2, S // 2, ch), t(B, S, S, ch)
+    timed("unet_utail_fwd (last block)", [B, ch, S, S], f * S * S * ch * (2 + 1 / 4), lambda: L.vqw_unet_utail_fwd(h, sl, None, o, None, B, S, S, ch, 0))
+    timed("unet_utail_bwd (last block)", [B, ch, S, S], f * S * S * ch * (2 + 1 / 4), lambda: L.vqw_unet_utail_bwd(None, o, None, h, sl, None, B, S, S, ch, 0))
+    H, C, Cr = S // 2, ch, ch
+    h, sl, res = t(B, H, H, C), t(B, H // 2, H // 2, C), t(B, H, H, Cr)
+    o, cat, gcat, gres = t(B, H, H, C), t(B, H, H, C + Cr), t(B, H, H, C + Cr), t(B, H, H, Cr)
+    px = H * H * C
+    timed("unet_utail_fwd (concat)", [B, C, H, H, Cr], f * px * (1 + 1 / 4 + 1 + 1 + 2), lambda: L.vqw_unet_utail_fwd(h, sl, res, o, cat, B, H, H, C, Cr))
+    timed("unet_utail_bwd (concat)", [B, C, H, H, Cr], f * px * (1 + 2 + 2 + 1 + 1 / 4 + 1),
+          lambda: L.vqw_unet_utail_bwd(cat, o, gcat, h, sl, gres, B, H, H, C, Cr))
+    # CutMix select and the losses on (B, 1, 512, 512)
+    img, rec, mix = t(B, S, S, 1), t(B, S, S, 1), t(B, S, S, 1)
+    n = B * S * S
+    timed("cutmix_select", [B, 1, S, S], 4 * n * 3, lambda: L.vqw_cutmix_select(img, rec, mix, B, S, S, 1, 100, 300, 64, 200, 0))
+    maps = [t(B, S, S) for _ in range(3)]
+    bots = [t(B) for _ in range(3)]
+    losses = [torch.empty((), device=dev) for _ in range(3)]
+    ws = torch.empty(int(L.vqw_unet_dis_losses_ws_bytes(n)), dtype=torch.uint8, device=dev)
+    gm = [t(B, S, S) for _ in range(3)]
+    gb = [t(B) for _ in range(3)]
+    one = [torch.ones((), device=dev) for _ in range(3)]
+    timed("unet_dis_losses_fwd", [B, 1, S, S], 4 * n * 3,
+          lambda: L.vqw_unet_dis_losses_fwd(*maps, *bots, *losses, ws, ws.numel(), B, S, S, 100, 300, 64, 200, 0))
+    timed("unet_dis_losses_bwd", [B, 1, S, S], 4 * n * 6,
+          lambda: L.vqw_unet_dis_losses_bwd(*maps, *bots, *one, *gm, *gb, B, S, S, 100, 300, 64, 200, 0))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--only-step", action="store_true")
+    ap.add_argument("--stats", help="a rocprofv3 --stats kernel CSV of a run with --only-step: print the convolution share")
+    args = ap.parse_args()
+    if args.stats:
+        return stats(args.stats)
+    c = step_rows(args)
+    if not args.only_step:
+        kernel_rows(args, c)
+
+
+if __name__ == "__main__":
+    main()
