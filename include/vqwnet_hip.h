@@ -338,7 +338,9 @@ int vqw_mask_scale(const int64_t* label_map, uint8_t* mask, int64_t* ids0, float
 /* ---- losses: functions/embed_loss.py:22-88, functions/onehot.py:11-20 */
 size_t vqw_cross_ws_bytes(int B, int K, long HW);
 /* labels int32 [B][HW] in [0,K] (0 = out of frame); embed [B][HW][D]; codebook [K][D] (= vq.embed).
- * loss = mean over present (b,k) of sum_p |e-c_k|^2 / (cnt+1e-6); coef[B][K] saved for backward. */
+ * loss = mean over present (b,k) of sum_p |e-c_k|^2 / (cnt+1e-6); coef[B][K] saved for backward.
+ * Both forward entry points (this one and the dense one) accept K <= 5120 and reject anything larger in their argument check:
+ * the partial sums live in 32 K bytes of LDS per workgroup (160 KiB at most; the opt-in above 64 KiB is taken here). */
 int vqw_cross_loss_fwd(const float* embed, const int32_t* labels, const float* codebook_kd,
                        float* loss, float* coef, void* ws, size_t ws_bytes,
                        int B, long HW, int D, int K, void* stream);

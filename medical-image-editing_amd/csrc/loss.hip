@@ -19,6 +19,28 @@ extern "C" size_t vqw_cross_ws_bytes(int B, int K, long HW) {
     (void)HW;
     return (size_t)B * CL_MAX_SPLITS * K * 2 * sizeof(float);
 }
+// Dynamic LDS of the two partial kernels, computed here only: one (sum, count) slab of K pairs per wave = 32 K bytes, plus the
+// staged codebook (4 K D bytes) where the label form wants it (*cb_lds, dropped when it would not fit beside the slabs).
+// A workgroup can have CL_LDS_MAX = 160 KiB, so K <= CL_MAX_K = 5120 is what can launch; anything above the default 64 KiB
+// needs the kernel's opt-in first.
+#define CL_LDS_MAX (160 * 1024)
+#define CL_MAX_K (CL_LDS_MAX / ((CL_BLOCK / 64) * 2 * (int)sizeof(float)))
+static inline size_t cl_lds_bytes(int K, int D, int* cb_lds) {
+    const size_t slabs = (size_t)(CL_BLOCK / 64) * 2 * K * sizeof(float);
+    if (cb_lds && *cb_lds) {
+        const size_t staged = (size_t)K * D * sizeof(float);
+        if (slabs + staged <= CL_LDS_MAX) return slabs + staged;
+        *cb_lds = 0;
+    }
+    return slabs;
+}
+static int cl_reserve_lds(const void* kernel, size_t lds, const char* who) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        vqw_set_error("%s: cannot reserve %zu bytes of LDS", who, lds);      // large dictionaries only: not on a training step's path
+        return VQW_ERR_HIP;
+    }
+    return VQW_OK;
+}
 
 // labels variant.  part[b][split][k][2] = (sum of squared distances, count)
 __global__ void __launch_bounds__(CL_BLOCK) k_cross_partial(const float* __restrict__ embed, const int32_t* __restrict__ labels,
@@ -166,11 +188,13 @@ extern "C" int vqw_cross_loss_fwd(const float* embed, const int32_t* labels, con
     VQW_CHECK(embed && labels && codebook_kd && loss && coef && ws && B > 0 && HW > 0 && D > 0 && K > 0,
               "vqw_cross_loss_fwd: bad arguments");
     VQW_CHECK(ws_bytes >= vqw_cross_ws_bytes(B, K, HW), "vqw_cross_loss_fwd: workspace too small");
-    VQW_CHECK(K <= 8192, "vqw_cross_loss_fwd: K too large");
+    VQW_CHECK(K <= CL_MAX_K, "vqw_cross_loss_fwd: K = %d too large (the per-wave class slabs fit the LDS up to K = %d)", K, CL_MAX_K);
     hipStream_t st = (hipStream_t)stream;
     int splits = cl_splits(B, HW);
-    const int cb_lds = (D % 4 == 0 && (long)K * D <= 4096 && (((uintptr_t)embed) & 15) == 0) ? 1 : 0;
-    k_cross_partial<<<dim3(splits, B), CL_BLOCK, ((CL_BLOCK / 64) * 2 * K + (cb_lds ? K * D : 0)) * sizeof(float), st>>>(embed, labels, codebook_kd, (float*)ws, HW, D, K, splits, cb_lds);
+    int cb_lds = (D % 4 == 0 && (long)K * D <= 4096 && (((uintptr_t)embed) & 15) == 0) ? 1 : 0;
+    const size_t lds = cl_lds_bytes(K, D, &cb_lds);
+    if (int rc = cl_reserve_lds((const void*)k_cross_partial, lds, "vqw_cross_loss_fwd")) return rc;
+    k_cross_partial<<<dim3(splits, B), CL_BLOCK, lds, st>>>(embed, labels, codebook_kd, (float*)ws, HW, D, K, splits, cb_lds);
     k_cross_finalize<<<1, 256, 0, st>>>((const float*)ws, loss, coef, B * K, K, splits);
     VQW_LAUNCH_CHECK("vqw_cross_loss_fwd");
     return VQW_OK;
@@ -180,10 +204,12 @@ extern "C" int vqw_cross_loss_dense_fwd(const float* embed, const float* r_nchw,
     VQW_CHECK(embed && r_nchw && codebook_kd && loss && coef && ws && B > 0 && HW > 0 && D > 0 && K > 0,
               "vqw_cross_loss_dense_fwd: bad arguments");
     VQW_CHECK(ws_bytes >= vqw_cross_ws_bytes(B, K, HW), "vqw_cross_loss_dense_fwd: workspace too small");
-    VQW_CHECK(K <= 8192, "vqw_cross_loss_dense_fwd: K too large");
+    VQW_CHECK(K <= CL_MAX_K, "vqw_cross_loss_dense_fwd: K = %d too large (the per-wave class slabs fit the LDS up to K = %d)", K, CL_MAX_K);
     hipStream_t st = (hipStream_t)stream;
     int splits = cl_splits(B, HW);
-    k_cross_partial_dense<<<dim3(splits, B), CL_BLOCK, (CL_BLOCK / 64) * 2 * K * sizeof(float), st>>>(embed, r_nchw, codebook_kd, (float*)ws, HW, D, K, splits);
+    const size_t lds = cl_lds_bytes(K, D, nullptr);
+    if (int rc = cl_reserve_lds((const void*)k_cross_partial_dense, lds, "vqw_cross_loss_dense_fwd")) return rc;
+    k_cross_partial_dense<<<dim3(splits, B), CL_BLOCK, lds, st>>>(embed, r_nchw, codebook_kd, (float*)ws, HW, D, K, splits);
     k_cross_finalize<<<1, 256, 0, st>>>((const float*)ws, loss, coef, B * K, K, splits);
     VQW_LAUNCH_CHECK("vqw_cross_loss_dense_fwd");
     return VQW_OK;
