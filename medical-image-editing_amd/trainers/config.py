@@ -102,18 +102,23 @@ def configure_discriminator(config):
     return dis
 
 
+def _weights(kind, config, absent_is_zero=False):
+    """-> the namedtuple `kind` from config.loss.loss_weight; an absent key keeps the namedtuple's default or, with
+    absent_is_zero, is 0.0 like a key that is `false`."""
+    w = config.loss.loss_weight
+    return kind(**{k: float(_get(w, k) or 0.0) for k in kind._fields if absent_is_zero or hasattr(w, k)})
+
+
 def gan_loss_weights(config):
     """-> GanLossWeights from config.loss.loss_weight.{recon, gen, dis, freq, perceptual}; an absent key keeps the
     namedtuple's default."""
-    w = config.loss.loss_weight
-    return GanLossWeights(**{k: float(_get(w, k) or 0.0) for k in GanLossWeights._fields if hasattr(w, k)})
+    return _weights(GanLossWeights, config)
 
 
 def unet_gan_loss_weights(config):
     """-> UNetGanLossWeights from config.loss.loss_weight.{recon, gen, dis, freq, perceptual, unet_perceptual, cutmix,
     consistency}; an absent key keeps the namedtuple's default."""
-    w = config.loss.loss_weight
-    return UNetGanLossWeights(**{k: float(_get(w, k) or 0.0) for k in UNetGanLossWeights._fields if hasattr(w, k)})
+    return _weights(UNetGanLossWeights, config)
 
 
 def _adam_kwargs(o):
@@ -187,8 +192,7 @@ def configure_perceptual_loss(config):
 
 
 def loss_weights(config):
-    w = config.loss.loss_weight
-    return LossWeights(**{k: float(_get(w, k) or 0.0) for k in LossWeights._fields})
+    return _weights(LossWeights, config, absent_is_zero=True)
 
 
 def set_transform(config, seed=0):
@@ -277,15 +281,12 @@ def build_second_step_trainer(config, device="cuda", data_parallel=None, first_s
         load_discriminator_from_ckpt(dck, dis)
     if data_parallel is None:
         data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    kw = dict(dis=dis, n_inner_loops=int(_get(c, "n_inner_loops") or 1), device=device, data_parallel=data_parallel,
+              frequency_loss=configure_frequency_loss(config), perceptual_loss=configure_perceptual_loss(config),
+              dec_optim=_adam_kwargs(config.dec_optim), dis_optim=_adam_kwargs(config.dis_optim),
+              use_recon_loss=bool(_get(c, "use_recon_loss", True)))
     if isinstance(dis, UNetDiscriminator):          # single_window_trainer.py:264-432
-        return UNetSecondStepTrainer(
-            encoder, decoder, dis=dis, loss_weight=unet_gan_loss_weights(config), n_inner_loops=int(_get(c, "n_inner_loops") or 1),
-            device=device, data_parallel=data_parallel, frequency_loss=configure_frequency_loss(config),
-            perceptual_loss=configure_perceptual_loss(config), dec_optim=_adam_kwargs(config.dec_optim),
-            dis_optim=_adam_kwargs(config.dis_optim), use_recon_loss=bool(_get(c, "use_recon_loss", True)),
-            use_unet_perceptual_loss=bool(_get(c, "use_unet_perceptual_loss")), use_l1_loss=bool(_get(c, "use_l1_loss")))
-    return SecondStepTrainer(
-        encoder, decoder, dis=dis, loss_weight=gan_loss_weights(config), n_inner_loops=int(_get(c, "n_inner_loops") or 1),
-        device=device, data_parallel=data_parallel, frequency_loss=configure_frequency_loss(config),
-        perceptual_loss=configure_perceptual_loss(config), dec_optim=_adam_kwargs(config.dec_optim),
-        dis_optim=_adam_kwargs(config.dis_optim), use_recon_loss=bool(_get(c, "use_recon_loss", True)))
+        return UNetSecondStepTrainer(encoder, decoder, loss_weight=unet_gan_loss_weights(config),
+                                     use_unet_perceptual_loss=bool(_get(c, "use_unet_perceptual_loss")),
+                                     use_l1_loss=bool(_get(c, "use_l1_loss")), **kw)
+    return SecondStepTrainer(encoder, decoder, loss_weight=gan_loss_weights(config), **kw)

@@ -8,6 +8,7 @@ pair (identity, horizontal flip + additive noise on the noised copy) whose cross
 map is an index flip.
 """
 from collections import namedtuple
+import os
 
 import torch
 
@@ -15,36 +16,10 @@ from hipops import ops, Adam
 from networks import UNetEncoder, UNetDecoder
 from functions import EmbeddingLoss, OneHotEncoder
 from utils import norm, denorm
+from .base import StepThrottle, TrainerBase  # noqa: F401  (StepThrottle: imported from here by older code)
 from .data_parallel import GradientAllReducer
 
 LossWeights = namedtuple("LossWeights", "commit cross dist reg recon freq perceptual", defaults=(1.0,) * 5 + (0.0, 0.0))
-
-
-class StepThrottle:
-    """At most `max_inflight` training steps enqueued ahead of the GPU (VQW_MAX_INFLIGHT, default 2).
-
-    The host enqueues a step five times faster than the GPU runs it.  Unthrottled it gets many steps ahead, and every
-    tensor that was handed to another stream (record_stream: conv inputs / gradients used by the weight-gradient lanes,
-    the second view) cannot be reused by the caching allocator until the GPU has passed its last use: the allocator
-    then hipMallocs a fresh working set for every step in flight (+10 GB of reserved memory per step measured, with
-    sporadic stalls of 0.3-1 s in those calls).  Two steps in flight keep the GPU fed and the pool bounded."""
-
-    def __init__(self, device):
-        import collections
-        import os
-        self.cuda = torch.device(device).type == "cuda"
-        self.events = collections.deque()
-        self.max_inflight = max(1, int(os.environ.get("VQW_MAX_INFLIGHT", "2")))
-
-    def begin(self):
-        while len(self.events) >= self.max_inflight:
-            self.events.popleft().synchronize()
-
-    def end(self):
-        if self.cuda:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            self.events.append(ev)
 
 
 class FlipViews:
@@ -90,54 +65,22 @@ class RandomTransformViews:
             t.generator.set_state(g)
 
 
-def trainer_state_dict(trainer):
-    """{'modules': {name: state_dict}, 'optimizers': {name: state_dict}, 'extra': ...} of a trainer that has modules() and
-    optimizers().  `extra` is what the module and optimiser state dicts do not hold and a bit-exact continuation needs:
-    the views' generators, the DropBlock schedule's position and the encoder's codebook-initialised flag."""
-    mods = trainer.modules()
-    extra = {"init_embed": bool(mods["encoder"].init_embed)}
-    views = getattr(trainer, "views", None)
-    if hasattr(views, "state_dict"):
-        extra["views"] = views.state_dict()
-    sched = getattr(mods["decoder"], "dropblock", None)
-    if hasattr(sched, "drop_values"):
-        extra["dropblock"] = {"i": int(sched.i), "drop_prob": float(sched.dropblock.drop_prob)}
-    return {"modules": {k: m.state_dict() for k, m in mods.items()},
-            "optimizers": {k: o.state_dict() for k, o in trainer.optimizers().items()}, "extra": extra}
-
-
-def load_trainer_state_dict(trainer, state):
-    mods = trainer.modules()
-    for k, m in mods.items():
-        if k in state.get("modules", {}):
-            m.load_state_dict(state["modules"][k], strict=True)
-    for k, o in trainer.optimizers().items():
-        if k in state.get("optimizers", {}):
-            o.load_state_dict(state["optimizers"][k])
-    extra = state.get("extra") or {}
-    if "init_embed" in extra:
-        mods["encoder"].init_embed = bool(extra["init_embed"])
-    views = getattr(trainer, "views", None)
-    if "views" in extra and hasattr(views, "load_state_dict"):
-        views.load_state_dict(extra["views"])
-    sched = getattr(mods["decoder"], "dropblock", None)
-    if "dropblock" in extra and hasattr(sched, "drop_values"):
-        sched.i = int(extra["dropblock"]["i"])
-        sched.dropblock.drop_prob = extra["dropblock"]["drop_prob"]
+trainer_state_dict = TrainerBase.state_dict              # (trainer) and (trainer, state), for anything that has modules()
+load_trainer_state_dict = TrainerBase.load_state_dict    # and optimizers(): the names these had as functions of this module
 
 
 LUNG_WINDOW = (1500, -550, 2.0)             # trainers/base.py:33-43
 MEDIASTINAL_WINDOW = (400, 20, 2.0)
 
 
-class FirstStepTrainer:
+class FirstStepTrainer(TrainerBase):
     def __init__(self, in_channels=1, enc_filters=(16, 32, 64, 128, 256), dec_filters=(32, 64, 128, 256, 512),
                  dict_size=10, momentum=0.999, margin=0.5, loss_weight=None, lr=1e-4, betas=(0.5, 0.999),
                  weight_decay=0.0, use_pixel_shuffle=False, dropped_skip_layers=(), views=None, device="cuda",
                  encoder=None, decoder=None, data_parallel=False, use_onehot=False, concurrent_views=None,
                  multi_window=None, embed_loss=None, enc_optim=None, dec_optim=None, use_recon_loss=True,
                  frequency_loss=None, freq_weights=None, perceptual_loss=None, percep_weights=None):
-        self.device = torch.device(device)
+        super().__init__(device)
         self.encoder = encoder if encoder is not None else UNetEncoder(
             in_channels, list(enc_filters), dict_size, momentum, 'torch', False, 1, True)
         self.decoder = decoder if decoder is not None else UNetDecoder(
@@ -177,11 +120,9 @@ class FirstStepTrainer:
         # order with events): running them on two streams lets HBM-bound kernels of one overlap MFMA-bound kernels of
         # the other.  VQW_CONCURRENT_VIEWS=0/1 overrides the default.
         if concurrent_views is None:
-            import os
             concurrent_views = os.environ.get("VQW_CONCURRENT_VIEWS", "1") != "0"
         self.concurrent_views = bool(concurrent_views) and self.device.type == "cuda"
         self._s2 = None
-        self.throttle = StepThrottle(self.device)
         self.reducer = None
         self._params = list(self.encoder.parameters()) + list(self.decoder.parameters())
         if data_parallel:
@@ -191,7 +132,6 @@ class FirstStepTrainer:
 
     def _forward_losses_two_streams(self, image, noise):
         """Same arithmetic as forward_losses; view 1 on the current stream, view 2 on a second stream."""
-        w = self.w
         s1 = torch.cuda.current_stream()
         if self._s2 is None:
             self._s2 = torch.cuda.Stream(device=self.device, priority=-1)
@@ -219,32 +159,39 @@ class FirstStepTrainer:
             codebook = self.encoder.vq.get_codebook()
             l_cross, l_dist, l_reg = self.embed_loss.forward_labels(embed_1, r_ids_1, embed_2, r_ids_2, codebook)
         recon_1 = self.decoder(embed_1)
-        rec_1 = self._recon_terms(recon_1, clear_1)
-        frq_1 = self._freq_terms(recon_1, clear_1)
-        pcp_1 = self._percep_terms(recon_1, clear_1)
+        terms_1 = self._view_terms(recon_1, clear_1)
         with torch.cuda.stream(s2):
             recon_2 = self.decoder(embed_2)
-            rec_2 = self._recon_terms(recon_2, clear_2)
-            frq_2 = self._freq_terms(recon_2, clear_2)
-            pcp_2 = self._percep_terms(recon_2, clear_2)
+            terms_2 = self._view_terms(recon_2, clear_2)
             ev2 = s2.record_event()
         s1.wait_event(ev2)
-        for t in [l_commit_2, recon_2, l_cross, embed_2, r_ids_2, ids_2] + [t for t, _ in rec_2 + frq_2 + pcp_2] + \
+        for t in [l_commit_2, recon_2, l_cross, embed_2, r_ids_2, ids_2] + [t for part in terms_2 for t, _ in part] + \
                 [t for t in (l_dist, l_reg) if torch.is_tensor(t)]:
             t.record_stream(s1)
-        l_rec_1, l_rec_2 = rec_1[0][0], rec_2[0][0]
+        return self._assemble(l_commit_1, l_commit_2, l_cross, l_dist, l_reg, terms_1, terms_2, (ids_1, ids_2),
+                              (recon_1, recon_2), (embed_1, embed_2))
+
+    def _assemble(self, l_commit_1, l_commit_2, l_cross, l_dist, l_reg, terms_1, terms_2, ids, recons, embeds):
+        """The total and the returned dict of either forward path.  terms_i: view i's (reconstruction, frequency, perceptual)
+        lists of (loss term, weight).  ops.weighted_sum adds in the order given, so the order is part of the total's bits."""
+        w = self.w
+        (rec_1, frq_1, pcp_1), (rec_2, frq_2, pcp_2) = terms_1, terms_2
         terms = rec_1 + rec_2 + frq_1 + frq_2 + pcp_1 + pcp_2
         l_total = ops.weighted_sum(
             [l_commit_1, l_commit_2, l_cross, l_dist, l_reg] + [t for t, _ in terms],
             [w.commit, w.commit, w.cross, w.dist, w.reg] + [c for _, c in terms])
         out = dict(total=l_total, commit_1=l_commit_1, commit_2=l_commit_2, cross=l_cross, dist=l_dist, reg=l_reg,
-                   recon_l1=l_rec_1, recon_l2=l_rec_2, ids_1=ids_1, ids_2=ids_2, recon_1=recon_1, recon_2=recon_2,
-                   embed_1=embed_1, embed_2=embed_2)
+                   recon_l1=rec_1[0][0], recon_l2=rec_2[0][0], ids_1=ids[0], ids_2=ids[1], recon_1=recons[0], recon_2=recons[1],
+                   embed_1=embeds[0], embed_2=embeds[1])
         if frq_1:                 # only with the frequency loss on: without it the step returns what it always did
             out.update(freq_1=frq_1[0][0], freq_2=frq_2[0][0])
         if pcp_1:                 # likewise only with the perceptual loss on
             out.update(perceptual_1=pcp_1[0][0], perceptual_2=pcp_2[0][0])
         return out
+
+    def _view_terms(self, recon, clear):
+        """One view's (reconstruction, frequency, perceptual) term lists."""
+        return self._recon_terms(recon, clear), self._freq_terms(recon, clear), self._percep_terms(recon, clear)
 
     def _recon_terms(self, recon, clear):
         """[(loss term, weight)] of one view's reconstruction loss: plain MSE, or the multi-window mean of
@@ -290,7 +237,6 @@ class FirstStepTrainer:
         """Lines 73-137 of the reference step.  `image` is in [-1, 1] (dataloader convention)."""
         if self.concurrent_views and not self.use_onehot:
             return self._forward_losses_two_streams(image, noise)
-        w = self.w
         (noised_1, clear_1), (noised_2, clear_2) = self.views(image, noise)
         embed_1, l_commit_1, ids_1 = self.encoder(noised_1)
         embed_2, l_commit_2, ids_2 = self.encoder(noised_2)
@@ -308,59 +254,38 @@ class FirstStepTrainer:
         rec_1, rec_2 = self._recon_terms(recon_1, clear_1), self._recon_terms(recon_2, clear_2)
         frq_1, frq_2 = self._freq_terms(recon_1, clear_1), self._freq_terms(recon_2, clear_2)
         pcp_1, pcp_2 = self._percep_terms(recon_1, clear_1), self._percep_terms(recon_2, clear_2)
-        l_rec_1, l_rec_2 = rec_1[0][0], rec_2[0][0]
-        terms = rec_1 + rec_2 + frq_1 + frq_2 + pcp_1 + pcp_2
-        l_total = ops.weighted_sum(
-            [l_commit_1, l_commit_2, l_cross, l_dist, l_reg] + [t for t, _ in terms],
-            [w.commit, w.commit, w.cross, w.dist, w.reg] + [c for _, c in terms])
-        out = dict(total=l_total, commit_1=l_commit_1, commit_2=l_commit_2, cross=l_cross, dist=l_dist, reg=l_reg,
-                   recon_l1=l_rec_1, recon_l2=l_rec_2, ids_1=ids_1, ids_2=ids_2, recon_1=recon_1, recon_2=recon_2,
-                   embed_1=embed_1, embed_2=embed_2)
-        if frq_1:                 # only with the frequency loss on: without it the step returns what it always did
-            out.update(freq_1=frq_1[0][0], freq_2=frq_2[0][0])
-        if pcp_1:                 # likewise only with the perceptual loss on
-            out.update(perceptual_1=pcp_1[0][0], perceptual_2=pcp_2[0][0])
-        return out
+        return self._assemble(l_commit_1, l_commit_2, l_cross, l_dist, l_reg, (rec_1, frq_1, pcp_1), (rec_2, frq_2, pcp_2),
+                              (ids_1, ids_2), (recon_1, recon_2), (embed_1, embed_2))
 
-    # -- what a run saves and restores (trainers/fit.py); `modules` / `optimizers` are in the reference's order
+    # `modules` / `optimizers` are in the reference's order
     def modules(self):
         return {"encoder": self.encoder, "decoder": self.decoder}
 
     def optimizers(self):
         return {"enc": self.enc_optim, "dec": self.dec_optim}
 
-    def state_dict(self):
-        return trainer_state_dict(self)
+    def _join(self):
+        """After the backward pass: the second view's stream back into the current one, then the end of the ops' step."""
+        if self._s2 is not None:
+            torch.cuda.current_stream().wait_stream(self._s2)
+        ops.join_streams()
 
-    def load_state_dict(self, state):
-        load_trainer_state_dict(self, state)
-
-    def test_step(self, batch):
-        """The reference's test step (single_window_trainer.py:781-827): {'NMSE', 'SSIM', 'PSNR', 'Entropy'} of one batch
-        through trainers.evaluation.Evaluator (eval mode, no gradients; training state untouched)."""
-        from .evaluation import Evaluator
-        return Evaluator(self.encoder, self.decoder, self.dict_size).test_step(batch)
-
-    def training_step(self, batch, noise=None):
+    def training_step(self, batch, noise=None, mark=None):
+        """`mark(name)`, if given, is called at the end of each phase: 'begin', 'forward', those of TrainerBase.update, 'end'."""
         image = batch['image'] if isinstance(batch, dict) else batch
         self.throttle.begin()
         ops.begin_step()
         if self.reducer is not None:
             ops.reset_pending(self._params)
+        if mark is not None:
+            mark("begin")
         out = self.forward_losses(image, noise)
-        self.enc_optim.zero_grad()
-        self.dec_optim.zero_grad()
-        if self.reducer is not None:
-            self.reducer.prepare()
-        out["total"].backward()
-        if self._s2 is not None:
-            torch.cuda.current_stream().wait_stream(self._s2)
-        ops.join_streams()
-        if self.reducer is not None:
-            self.reducer.finish()
-        self.enc_optim.step()
-        self.dec_optim.step()
+        if mark is not None:
+            mark("forward")
+        self.update(out["total"], [self.enc_optim, self.dec_optim], self.reducer, self._join, mark)
         self.throttle.end()
+        if mark is not None:
+            mark("end")
         return out
 
     @staticmethod

@@ -24,8 +24,9 @@ from utils import checkpoint as ckpt_io
 from utils import logger as run_logger
 from utils import nifti, png
 
-from .first_step import (FlipViews, LUNG_WINDOW, MEDIASTINAL_WINDOW, LossWeights, trainer_state_dict,
-                         load_trainer_state_dict)
+from .base import TrainerBase
+from .config import configure_models
+from .first_step import FlipViews, LUNG_WINDOW, MEDIASTINAL_WINDOW, LossWeights
 from .evaluation import Evaluator
 
 LIMIT_VAL_BATCHES = 2              # run_vqwnet.py:127
@@ -89,17 +90,21 @@ def _second_step_terms(out):
     return [(n, out[n]) for n in names if out.get(n) is not None]
 
 
+_SWITCHED_OFF_IS_ZERO = ("recon", "freq", "perceptual", "unet_perceptual")      # terms a step leaves out when they are off
+
+
 def _second_step_row(v, w):
+    """The row of either second step, from the fields its loss weights have (U-Net: single_window_trainer.py:361-374)."""
     f = np.float32
-    if hasattr(w, "cutmix"):         # the U-Net discriminator's step: single_window_trainer.py:361-374
-        return {"total": f(v["gen_total"]) + f(v["dis_total"]), "gen_total": v["gen_total"], "recon": f(w.recon) * f(v.get("recon", 0.0)),
-                "freq": f(w.freq) * f(v.get("freq", 0.0)), "perceptual": f(w.perceptual) * f(v.get("perceptual", 0.0)),
-                "gen": f(w.gen) * f(v["gen"]), "unet_perceptual": f(w.unet_perceptual) * f(v.get("unet_perceptual", 0.0)),
-                "dis_total": v["dis_total"], "dis": f(w.dis) * f(v["dis"]), "cutmix": f(w.cutmix) * f(v["cutmix"]),
-                "consistency": f(w.consistency) * f(v["consistency"])}
-    return {"total": f(v["gen_total"]) + f(v["dis_total"]), "gen_total": v["gen_total"], "recon": f(w.recon) * f(v.get("recon", 0.0)),
-            "freq": f(w.freq) * f(v.get("freq", 0.0)), "perceptual": f(w.perceptual) * f(v.get("perceptual", 0.0)),
-            "gen": f(w.gen) * f(v["gen"]), "dis_total": v["dis_total"], "dis": v["dis_total"]}
+    term = lambda k: f(getattr(w, k)) * f(v.get(k, 0.0) if k in _SWITCHED_OFF_IS_ZERO else v[k])  # noqa: E731
+    row = {"total": f(v["gen_total"]) + f(v["dis_total"]), "gen_total": v["gen_total"]}
+    row.update((k, term(k)) for k in ("recon", "freq", "perceptual", "gen", "unet_perceptual") if k in w._fields)
+    row["dis_total"] = v["dis_total"]
+    if "cutmix" in w._fields:
+        row.update((k, term(k)) for k in ("dis", "cutmix", "consistency"))
+    else:                            # the PatchGAN step has one discriminator term: `dis` is its total
+        row["dis"] = v["dis_total"]
+    return row
 
 
 class _ScalarQueue:
@@ -188,13 +193,12 @@ class _RecordingSampler(DistributedSampler):
         return iter(indices)
 
 
-class InferenceModels:
+class InferenceModels(TrainerBase):
     """Encoder and decoder alone, behind the part of the trainers' interface Fit.test() / Fit.export() use: what
     `training_mode: "inference"` needs (no optimisers, no losses)."""
 
     def __init__(self, config, device="cuda"):
-        from .config import configure_models
-        self.device = torch.device(device)
+        super().__init__(device)
         self.encoder, self.decoder = configure_models(config)
         self.encoder.to(self.device).eval()
         self.decoder.to(self.device).eval()
@@ -206,12 +210,6 @@ class InferenceModels:
 
     def optimizers(self):
         return {}
-
-    def state_dict(self):
-        return trainer_state_dict(self)
-
-    def load_state_dict(self, state):
-        load_trainer_state_dict(self, state)
 
 
 class Fit:

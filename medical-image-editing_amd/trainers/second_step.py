@@ -7,6 +7,9 @@ The encoder is frozen (eval mode, no_grad); the decoder is trained on  w.recon *
 (dicts lr / betas / weight_decay, the reference's config.dec_optim / config.dis_optim, base.py:171-181) override the shared
 lr / betas / weight_decay per optimiser; use_recon_loss=False drops the reconstruction term (:448-451).
 trainers.build_second_step_trainer builds one from a config.
+
+SecondStepBase is the step itself; a discriminator's trainer (here the PatchGAN's, second_step_unet.py the U-Net's) adds what
+depends on the discriminator: its generator terms, its update and its loss-weight namedtuple.
 """
 from collections import namedtuple
 
@@ -15,21 +18,25 @@ import torch
 from hipops import ops, Adam
 from networks.discriminator import NLayerDiscriminator
 from functions.gan_loss import hinge_d_loss, generator_loss
+from . import data_parallel as dp
+from .base import TrainerBase
 
 GanLossWeights = namedtuple("GanLossWeights", "recon gen dis freq perceptual", defaults=(1.0, 1.0, 1.0, 0.0, 0.0))
 
 
-class SecondStepTrainer:
+class SecondStepBase(TrainerBase):
+    """A subclass sets `Weights` (its loss-weight namedtuple) and `dis_keys` (the names of what discriminator_update returns)
+    and supplies generator_terms() and discriminator_update()."""
+
     def __init__(self, encoder, decoder, dis=None, loss_weight=None, n_inner_loops=1, lr=1e-4, betas=(0.5, 0.999),
                  weight_decay=0.0, device="cuda", data_parallel=False, frequency_loss=None,
                  perceptual_loss=None, dec_optim=None, dis_optim=None, use_recon_loss=True):
-        self.device = torch.device(device)
-        from .first_step import StepThrottle
-        self.throttle = StepThrottle(self.device)      # at most two steps enqueued ahead of the GPU
+        super().__init__(device)
         self.encoder = encoder.to(self.device)
         self.decoder = decoder.to(self.device).train()
         self.dis = (dis if dis is not None else NLayerDiscriminator()).to(self.device).train()
-        self.w = loss_weight if loss_weight is not None else GanLossWeights()
+        self.dict_size = encoder.dict_size
+        self.w = loss_weight if loss_weight is not None else self.Weights()
         self.n_inner_loops = int(n_inner_loops)
         self.frequency_loss = frequency_loss          # functions.FocalFrequencyLoss or None (use_frequency_loss)
         # functions.VGGLoss or None (use_perceptual_loss); no trainable parameters, so nothing to all-reduce
@@ -43,30 +50,29 @@ class SecondStepTrainer:
         # inside their kernels' host code when a process group is up
         self.dec_reducer = self.dis_reducer = None
         if data_parallel:
-            from .data_parallel import GradientAllReducer
-            self.dec_reducer = GradientAllReducer(list(reversed([p for p in self.decoder.parameters() if p.requires_grad])))
-            self.dis_reducer = GradientAllReducer(list(reversed([p for p in self.dis.parameters() if p.requires_grad])))
+            self.dec_reducer = dp.GradientAllReducer(list(reversed([p for p in self.decoder.parameters() if p.requires_grad])))
+            self.dis_reducer = dp.GradientAllReducer(list(reversed(self.reduced_dis_params())))
 
-    # -- what a run saves and restores (trainers/fit.py); `modules` / `optimizers` are in the reference's order
+    # `modules` / `optimizers` are in the reference's order
     def modules(self):
         return {"encoder": self.encoder, "decoder": self.decoder, "dis": self.dis}
 
     def optimizers(self):
         return {"dec": self.dec_optim, "dis": self.dis_optim}
 
-    def state_dict(self):
-        from .first_step import trainer_state_dict
-        return trainer_state_dict(self)
+    def reduced_dis_params(self):
+        """The discriminator's parameters whose gradients a data-parallel run all-reduces."""
+        return [p for p in self.dis.parameters() if p.requires_grad]
 
-    def load_state_dict(self, state):
-        from .first_step import load_trainer_state_dict
-        load_trainer_state_dict(self, state)
+    def generator_terms(self, image, recon, shared):
+        """-> [(name, term or None, weight)] of the generator total in the order ops.weighted_sum adds them (the order is
+        part of the total's bits), the discriminator's forward on `recon` included; `shared`: the (recon, freq, perceptual)
+        entries.  Runs with the discriminator's parameters frozen."""
+        raise NotImplementedError
 
-    def test_step(self, batch):
-        """{'NMSE', 'SSIM', 'PSNR', 'Entropy'} of one batch through trainers.evaluation.Evaluator (eval mode, no gradients;
-        training state untouched)."""
-        from .evaluation import Evaluator
-        return Evaluator(self.encoder, self.decoder, self.encoder.dict_size).test_step(batch)
+    def discriminator_update(self, image, recon):
+        """One inner loop of the discriminator half, its Adam step included -> the tensors `dis_keys` names."""
+        raise NotImplementedError
 
     def training_step(self, batch):
         image = batch['image'] if isinstance(batch, dict) else batch
@@ -79,54 +85,51 @@ class SecondStepTrainer:
         with torch.no_grad():
             embed, _, ids = self.encoder(image)
         recon = self.decoder(embed.detach())
-        l_recon = ops.mse_loss(recon, image) if self.use_recon_loss else None
-        l_freq = self.frequency_loss(recon, image) if self.frequency_loss is not None else None
-        l_percep = self.perceptual_loss(recon, image) if self.perceptual_loss is not None else None
+        shared = [("recon", ops.mse_loss(recon, image) if self.use_recon_loss else None, w.recon),
+                  ("freq", self.frequency_loss(recon, image) if self.frequency_loss is not None else None, w.freq),
+                  ("perceptual", self.perceptual_loss(recon, image) if self.perceptual_loss is not None else None, w.perceptual)]
         # The reference lets autograd fill the discriminator's parameter gradients in this pass and discards them
-        # (dis_optim.zero_grad() below); they are not computed here.  Same decoder gradients, same update.
+        # (dis_optim.zero_grad() in the discriminator half); they are not computed here.  Same decoder gradients, same
+        # update; the discriminator's buffers advance as in the reference.
         dis_params = [p for p in self.dis.parameters() if p.requires_grad]
+
+        def thaw():
+            for p in dis_params:
+                p.requires_grad_(True)
+
+        def thaw_and_join():
+            thaw()
+            ops.join_streams()
+
         for p in dis_params:
             p.requires_grad_(False)
         try:
-            l_gen = generator_loss(self.dis(recon))
-            terms, weights = ([l_recon, l_gen], [w.recon, w.gen]) if l_recon is not None else ([l_gen], [w.gen])
-            if l_freq is not None:
-                terms.append(l_freq)
-                weights.append(w.freq)
-            if l_percep is not None:
-                terms.append(l_percep)
-                weights.append(w.perceptual)
-            l_gen_total = ops.weighted_sum(terms, weights)
-            self.dec_optim.zero_grad()
-            if self.dec_reducer is not None:
-                self.dec_reducer.prepare()
-            l_gen_total.backward()
+            terms = [t for t in self.generator_terms(image, recon, shared) if t[1] is not None]
+            l_gen_total = ops.weighted_sum([t for _, t, _ in terms], [c for _, _, c in terms])
+            self.update(l_gen_total, [self.dec_optim], self.dec_reducer, thaw_and_join)
         finally:
-            for p in dis_params:
-                p.requires_grad_(True)
-        ops.join_streams()
-        if self.dec_reducer is not None:
-            self.dec_reducer.finish()
-        self.dec_optim.step()
-        l_dis_total = None
+            thaw()
+        last = ()
         for _ in range(self.n_inner_loops):
-            l_real = self.dis(image.detach())
-            l_fake = self.dis(recon.detach())
-            l_dis = hinge_d_loss(l_real, l_fake)
-            l_dis_total = ops.weighted_sum([l_dis], [w.dis])
-            self.dis_optim.zero_grad()
-            if self.dis_reducer is not None:
-                self.dis_reducer.prepare()
-            l_dis_total.backward()
-            if self.dis_reducer is not None:
-                self.dis_reducer.finish()
-            self.dis_optim.step()
+            last = self.discriminator_update(image, recon)
         self.throttle.end()
-        out = dict(gen_total=l_gen_total, recon=l_recon, gen=l_gen, dis_total=l_dis_total, ids=ids, recon_image=recon)
-        if l_recon is None:
-            del out["recon"]
-        if l_freq is not None:
-            out["freq"] = l_freq
-        if l_percep is not None:
-            out["perceptual"] = l_percep
+        out = dict(gen_total=l_gen_total)
+        out.update((name, t) for name, t, _ in terms)
+        out.update(zip(self.dis_keys, last), ids=ids, recon_image=recon)
         return out
+
+
+class SecondStepTrainer(SecondStepBase):
+    Weights = GanLossWeights
+    dis_keys = ("dis_total",)
+
+    def generator_terms(self, image, recon, shared):
+        l_recon, l_freq, l_percep = shared
+        return [l_recon, ("gen", generator_loss(self.dis(recon)), self.w.gen), l_freq, l_percep]
+
+    def discriminator_update(self, image, recon):
+        """-> (l_dis_total,): hinge loss on D(image), D(recon), one Adam step (single_window_trainer.py:472-486)."""
+        l_dis = hinge_d_loss(self.dis(image.detach()), self.dis(recon.detach()))
+        l_dis_total = ops.weighted_sum([l_dis], [self.w.dis])
+        self.update(l_dis_total, [self.dis_optim], self.dis_reducer)
+        return (l_dis_total,)

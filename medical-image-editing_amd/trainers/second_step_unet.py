@@ -20,8 +20,9 @@ import random
 import numpy as np
 import torch
 
-from hipops import ops, Adam
+from hipops import ops
 from networks.unet_discriminator import UNetDiscriminator
+from .second_step import SecondStepBase
 
 UNetGanLossWeights = namedtuple("UNetGanLossWeights", "recon gen dis freq perceptual unet_perceptual cutmix consistency",
                                 defaults=(1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 1.0, 1.0))
@@ -42,7 +43,10 @@ def draw_cutmix_box(height, width):
     return span(centre["y"], height), span(centre["x"], width)
 
 
-class UNetSecondStepTrainer:
+class UNetSecondStepTrainer(SecondStepBase):
+    Weights = UNetGanLossWeights
+    dis_keys = ("dis_total", "dis", "cutmix", "consistency")
+
     def __init__(self, encoder, decoder, dis, loss_weight=None, n_inner_loops=1, lr=1e-4, betas=(0.5, 0.999), weight_decay=0.0,
                  device="cuda", data_parallel=False, frequency_loss=None, perceptual_loss=None, dec_optim=None, dis_optim=None,
                  use_recon_loss=True, use_unet_perceptual_loss=False, use_l1_loss=False, cutmix_box=None):
@@ -50,52 +54,29 @@ class UNetSecondStepTrainer:
             raise NotImplementedError("loss.use_l1_loss: the L1 reconstruction loss is not built (MSE is)")
         if not isinstance(dis, UNetDiscriminator):
             raise TypeError("UNetSecondStepTrainer trains a networks.UNetDiscriminator (SecondStepTrainer the PatchGAN)")
-        self.device = torch.device(device)
-        from .first_step import StepThrottle
-        self.throttle = StepThrottle(self.device)      # at most two steps enqueued ahead of the GPU
-        self.encoder = encoder.to(self.device)
-        self.decoder = decoder.to(self.device).train()
-        self.dis = dis.to(self.device).train()
-        self.w = loss_weight if loss_weight is not None else UNetGanLossWeights()
-        self.n_inner_loops = int(n_inner_loops)
-        self.frequency_loss = frequency_loss
-        self.perceptual_loss = perceptual_loss.to(self.device) if perceptual_loss is not None else None
-        self.use_recon_loss = bool(use_recon_loss)
+        super().__init__(encoder, decoder, dis, loss_weight, n_inner_loops, lr, betas, weight_decay, device, data_parallel,
+                         frequency_loss, perceptual_loss, dec_optim, dis_optim, use_recon_loss)
         self.use_unet_perceptual_loss = bool(use_unet_perceptual_loss)
         self.cutmix_box = cutmix_box
-        shared = dict(lr=lr, betas=betas, weight_decay=weight_decay)
-        self.dec_optim = Adam([p for p in self.decoder.parameters() if p.requires_grad], **(dec_optim or shared))
-        self.dis_optim = Adam([p for p in self.dis.parameters() if p.requires_grad], **(dis_optim or shared))
-        self.dec_reducer = self.dis_reducer = None
-        if data_parallel:
-            from .data_parallel import GradientAllReducer
-            unused = {id(p) for p in self.dis.linear.parameters()}       # `linear` is never used: it never has a gradient
-            self.dec_reducer = GradientAllReducer(list(reversed([p for p in self.decoder.parameters() if p.requires_grad])))
-            self.dis_reducer = GradientAllReducer(list(reversed([p for p in self.dis.parameters()
-                                                                 if p.requires_grad and id(p) not in unused])))
 
-    def modules(self):
-        return {"encoder": self.encoder, "decoder": self.decoder, "dis": self.dis}
-
-    def optimizers(self):
-        return {"dec": self.dec_optim, "dis": self.dis_optim}
-
-    def state_dict(self):
-        from .first_step import trainer_state_dict
-        return trainer_state_dict(self)
-
-    def load_state_dict(self, state):
-        from .first_step import load_trainer_state_dict
-        load_trainer_state_dict(self, state)
-
-    def test_step(self, batch):
-        from .evaluation import Evaluator
-        return Evaluator(self.encoder, self.decoder, self.encoder.dict_size).test_step(batch)
+    def reduced_dis_params(self):
+        unused = {id(p) for p in self.dis.linear.parameters()}       # `linear` is never used: it never has a gradient
+        return [p for p in super().reduced_dis_params() if id(p) not in unused]
 
     def _draw_box(self, H, W):
         if self.cutmix_box is not None:
             return self.cutmix_box() if callable(self.cutmix_box) else self.cutmix_box
         return draw_cutmix_box(H, W), random.random() > 0.5
+
+    def generator_terms(self, image, recon, shared):
+        f_map, f_bottle, f_feat = self.dis(recon)
+        l_gen = ops.weighted_sum([ops.neg_mean(f_map), ops.neg_mean(f_bottle)], [1.0, 1.0])
+        l_unet = None
+        if self.use_unet_perceptual_loss:
+            with torch.no_grad():
+                _, _, r_feat = self.dis(image.detach())
+            l_unet = ops.weighted_sum([ops.mse_loss(f, r) for f, r in zip(f_feat, r_feat)], [1.0] * len(f_feat))
+        return [("gen", l_gen, self.w.gen), *shared, ("unet_perceptual", l_unet, self.w.unet_perceptual)]
 
     def discriminator_update(self, image, recon):
         """One inner loop of the discriminator half (single_window_trainer.py:319-357): D(image), D(recon), one CutMix draw,
@@ -108,63 +89,5 @@ class UNetSecondStepTrainer:
         c_map, c_bottle, _ = self.dis(cutmix_images)
         l_dis, l_cutmix, l_cons = ops.unet_dis_losses(r_map, f_map, c_map, r_bottle, f_bottle, c_bottle, box, flip)
         l_dis_total = ops.weighted_sum([l_dis, l_cutmix, l_cons], [w.dis, w.cutmix, w.consistency])
-        self.dis_optim.zero_grad()
-        if self.dis_reducer is not None:
-            self.dis_reducer.prepare()
-        l_dis_total.backward()
-        if self.dis_reducer is not None:
-            self.dis_reducer.finish()
-        self.dis_optim.step()
+        self.update(l_dis_total, [self.dis_optim], self.dis_reducer)
         return l_dis_total, l_dis, l_cutmix, l_cons
-
-    def training_step(self, batch):
-        image = batch['image'] if isinstance(batch, dict) else batch
-        w = self.w
-        self.throttle.begin()
-        ops.begin_step()
-        if self.dec_reducer is not None:
-            ops.reset_pending(self.dec_optim.param_groups[0]["params"])
-        self.encoder.eval()
-        with torch.no_grad():
-            embed, _, ids = self.encoder(image)
-        recon = self.decoder(embed.detach())
-        l_recon = ops.mse_loss(recon, image) if self.use_recon_loss else None
-        l_freq = self.frequency_loss(recon, image) if self.frequency_loss is not None else None
-        l_percep = self.perceptual_loss(recon, image) if self.perceptual_loss is not None else None
-        # the discriminator's parameter gradients of this pass are discarded by the reference (dis_optim.zero_grad() below):
-        # they are not computed; its buffers advance as in the reference
-        dis_params = [p for p in self.dis.parameters() if p.requires_grad]
-        for p in dis_params:
-            p.requires_grad_(False)
-        try:
-            f_map, f_bottle, f_feat = self.dis(recon)
-            l_gen = ops.weighted_sum([ops.neg_mean(f_map), ops.neg_mean(f_bottle)], [1.0, 1.0])
-            l_unet = None
-            if self.use_unet_perceptual_loss:
-                with torch.no_grad():
-                    _, _, r_feat = self.dis(image.detach())
-                l_unet = ops.weighted_sum([ops.mse_loss(f, r) for f, r in zip(f_feat, r_feat)], [1.0] * len(f_feat))
-            terms, weights = [l_gen], [w.gen]
-            for t, wt in ((l_recon, w.recon), (l_freq, w.freq), (l_percep, w.perceptual), (l_unet, w.unet_perceptual)):
-                if t is not None:
-                    terms.append(t)
-                    weights.append(wt)
-            l_gen_total = ops.weighted_sum(terms, weights)
-            self.dec_optim.zero_grad()
-            if self.dec_reducer is not None:
-                self.dec_reducer.prepare()
-            l_gen_total.backward()
-        finally:
-            for p in dis_params:
-                p.requires_grad_(True)
-        ops.join_streams()
-        if self.dec_reducer is not None:
-            self.dec_reducer.finish()
-        self.dec_optim.step()
-        l_dis_total = l_dis = l_cutmix = l_cons = None
-        for _ in range(self.n_inner_loops):
-            l_dis_total, l_dis, l_cutmix, l_cons = self.discriminator_update(image, recon)
-        self.throttle.end()
-        out = dict(gen_total=l_gen_total, recon=l_recon, gen=l_gen, freq=l_freq, perceptual=l_percep, unet_perceptual=l_unet,
-                   dis_total=l_dis_total, dis=l_dis, cutmix=l_cutmix, consistency=l_cons, ids=ids, recon_image=recon)
-        return {k: v for k, v in out.items() if v is not None}

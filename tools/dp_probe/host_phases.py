@@ -8,7 +8,6 @@ forced = os.environ.get("VQW_DP_FORCE", "0") == "1"
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29674")
 import torch, torch.distributed as dist
 import bench
-from hipops import ops
 from trainers import build_first_step_trainer
 from utils import load_json
 if forced:
@@ -23,25 +22,7 @@ acc = dict.fromkeys(names, 0.0)
 
 def step(image, noise, rec):
     t = [time.perf_counter()]
-    def mark(): t.append(time.perf_counter())
-    tr.throttle.begin()
-    if tr.reducer is not None:
-        ops.reset_pending(tr._params)
-    mark()
-    out = tr.forward_losses(image, noise); mark()
-    tr.enc_optim.zero_grad(); tr.dec_optim.zero_grad()
-    if tr.reducer is not None:
-        tr.reducer.prepare()
-    mark()
-    out["total"].backward(); mark()
-    if tr._s2 is not None:
-        torch.cuda.current_stream().wait_stream(tr._s2)
-    ops.join_streams(); mark()
-    if tr.reducer is not None:
-        tr.reducer.finish()
-    mark()
-    tr.enc_optim.step(); tr.dec_optim.step(); mark()
-    tr.throttle.end(); mark()
+    tr.training_step({"image": image}, noise=noise, mark=lambda name: t.append(time.perf_counter()))    # marks: `names`, in order
     if rec:
         for n, a, b in zip(names, t[:-1], t[1:]):
             acc[n] += (b - a) * 1e3

@@ -43,15 +43,11 @@ print("GPU step %.1f ms; host enqueue per step: mean %.1f ms, first %.1f, last %
 # host-only phases of one step, un-throttled (GPU idle at start)
 torch.cuda.synchronize()
 img, noise = pool[0]
+t = {}
 with torch.cuda.stream(chain):
     a = time.perf_counter()
-    out = tr.forward_losses(img, noise)
-    b = time.perf_counter()
-    tr.enc_optim.zero_grad(); tr.dec_optim.zero_grad()
-    out["total"].backward()
-    c = time.perf_counter()
-    tr.enc_optim.step(); tr.dec_optim.step()
-    d = time.perf_counter()
+    tr.training_step({"image": img}, noise=noise, mark=lambda name: t.__setitem__(name, time.perf_counter()))
+b, c, d = t["forward"], t["backward"], t["end"]
 torch.cuda.synchronize()
 e = time.perf_counter()
 print("host: forward %.1f ms, backward %.1f ms, optimiser %.1f ms; GPU done %.1f ms after the host" %

@@ -11,10 +11,9 @@ tr = FirstStepTrainer(device="cuda")
 img, noise = synthetic_batch(32, 256, 1234, "cuda")
 def sync(): torch.cuda.synchronize(); return time.perf_counter()
 for it in range(4):
-    t0 = sync(); out = tr.forward_losses(img, noise)
-    t1 = sync(); tr.enc_optim.zero_grad(); tr.dec_optim.zero_grad(); out["total"].backward()
-    t2 = sync(); tr.enc_optim.step(); tr.dec_optim.step()
-    t3 = sync()
+    t = {"start": sync()}
+    tr.training_step({"image": img}, noise=noise, mark=lambda name: t.__setitem__(name, sync()))      # the trainer's own phases
+    t0, t1, t2, t3 = t["start"], t["forward"], t["backward"], t["end"]
     # host-side enqueue time of a whole step (no syncs inside)
     h0 = time.perf_counter(); tr.training_step({"image": img}, noise=noise); h1 = time.perf_counter(); t4 = sync()
     print("iter %d: forward %.1f ms  backward %.1f ms  optimiser %.1f ms | async step: host enqueue %.1f ms, total %.1f ms"
