@@ -3,6 +3,7 @@
 // All statistics use a deterministic two-stage reduction: stage 1 writes double partials
 // part[n][split][c][2] (fixed pixel ranges per block, fixed tree inside the block), stage 2 sums the
 // partials in index order.  No float atomics -> bitwise reproducible run to run.
+#include <type_traits>
 #include "common.h"
 #include "prof.h"
 #include "../../include/vqwnet_hip.h"
@@ -22,6 +23,128 @@ static inline size_t plane_part_bytes(int N, int C) { return (size_t)N * PLANE_M
 extern "C" size_t vqw_plane_ws_bytes(int N, int C, int HW) {
     (void)HW;
     return plane_part_bytes(N, C) + (size_t)N * C * 2 * sizeof(float);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The per-element formulas, each written once.  The scalar form is the definition; the *4 wrappers apply it to the four
+// channels of a float4, whose (mean, rstd) pairs arrive as the quads m0 = (mean0, rstd0, mean1, rstd1), m1 = (mean2, ..).
+// Every tier of every map and every reduction functor below goes through these.
+__device__ __forceinline__ float norm_xhat(float x, float mean, float rstd) { return (x - mean) * rstd; }
+__device__ __forceinline__ void stats_terms(float v, float& a, float& b) { a = v; b = v * v; }
+// InstanceNorm backward: ghat = gy * [xhat > 0] (relu); dx = rstd * (ghat - mean(ghat) - xhat * mean(ghat * xhat))
+__device__ __forceinline__ float inorm_bwd_term(float g, float xh, bool relu) { return (relu && !(xh > 0.f)) ? 0.f : g; }
+__device__ __forceinline__ float inorm_bwd_out(float gg, float xh, float rstd, float e0, float e1) { return rstd * (gg - e0 - xh * e1); }
+// SPADE: out = xhat * (1 + gamma) + beta.  Backward: g = gy * [out > 0] (relu); dgamma = g * xhat; dbeta = g;
+// dxhat = g * (1 + gamma); dx = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat * xhat)) (training) or rstd * dxhat (eval)
+__device__ __forceinline__ float spade_out(float xh, float gamma, float beta) { return xh * (1.f + gamma) + beta; }
+__device__ __forceinline__ void spade_bwd_grad(float g, float xh, float gamma, float beta, bool relu, float& dgamma, float& dbeta,
+                                               float& dxhat) {
+    if (relu && !(spade_out(xh, gamma, beta) > 0.f)) g = 0.f;
+    dgamma = g * xh;
+    dbeta = g;
+    dxhat = g * (1.f + gamma);
+}
+__device__ __forceinline__ float spade_bwd_out(float dxh, float xh, float rstd, float s1, float s2, bool train) {
+    return train ? rstd * (dxh - s1 - xh * s2) : rstd * dxh;
+}
+
+__device__ __forceinline__ void unpack4(const float4& v, float* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+// the (mean, rstd) quads as per-channel arrays
+__device__ __forceinline__ void unpack_mr(const float4& m0, const float4& m1, float* mean, float* rstd) {
+    mean[0] = m0.x; mean[1] = m0.z; mean[2] = m1.x; mean[3] = m1.z;
+    rstd[0] = m0.y; rstd[1] = m0.w; rstd[2] = m1.y; rstd[3] = m1.w;
+}
+__device__ __forceinline__ void xhat4(const float4& v, const float4& m0, const float4& m1, float* xh) {
+    xh[0] = norm_xhat(v.x, m0.x, m0.y); xh[1] = norm_xhat(v.y, m0.z, m0.w);
+    xh[2] = norm_xhat(v.z, m1.x, m1.y); xh[3] = norm_xhat(v.w, m1.z, m1.w);
+}
+__device__ __forceinline__ float4 inorm4(const float4& v, const float4& m0, const float4& m1, const bool relu) {
+    float o[4];
+    xhat4(v, m0, m1, o);
+    if (relu) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = fmaxf(o[k], 0.f);
+    }
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+// the two sums of the InstanceNorm backward: a = ghat, b = ghat * xhat
+__device__ __forceinline__ void inorm_bwd_terms4(const float4& v, const float4& g, const float4& m0, const float4& m1, const bool relu,
+                                                 float* a, float* b) {
+    float xh[4], gg[4];
+    xhat4(v, m0, m1, xh);
+    unpack4(g, gg);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        a[k] = inorm_bwd_term(gg[k], xh[k], relu);
+        b[k] = a[k] * xh[k];
+    }
+}
+// e0 / e1: the (mean(ghat), mean(ghat * xhat)) quads, laid out like m0 / m1
+__device__ __forceinline__ float4 inorm_bwd4(const float4& v, const float4& g, const float4& m0, const float4& m1, const float4& e0,
+                                             const float4& e1, const bool relu) {
+    float xv[4], gg[4], mean[4], rs[4], ea[4], eb[4], o[4];
+    unpack4(v, xv);
+    unpack4(g, gg);
+    unpack_mr(m0, m1, mean, rs);
+    unpack_mr(e0, e1, ea, eb);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float xh = norm_xhat(xv[k], mean[k], rs[k]);
+        o[k] = inorm_bwd_out(inorm_bwd_term(gg[k], xh, relu), xh, rs[k], ea[k], eb[k]);
+    }
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+// (written per component: this order keeps the walks' instruction streams what they were)
+__device__ __forceinline__ float4 spade4(const float4& v, const float4& ga, const float4& be, const float4& m0, const float4& m1,
+                                         const bool relu) {
+    float4 o;
+    o.x = spade_out(norm_xhat(v.x, m0.x, m0.y), ga.x, be.x);
+    o.y = spade_out(norm_xhat(v.y, m0.z, m0.w), ga.y, be.y);
+    o.z = spade_out(norm_xhat(v.z, m1.x, m1.y), ga.z, be.z);
+    o.w = spade_out(norm_xhat(v.w, m1.z, m1.w), ga.w, be.w);
+    if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+    return o;
+}
+// the two sums of the SPADE backward, a = dxhat and b = dxhat * xhat, with dgamma and dbeta of the quad
+__device__ __forceinline__ void spade_bwd_terms4(const float4& v, const float4& g, const float4& ga, const float4& be, const float4& m0,
+                                                 const float4& m1, const bool relu, float4& dgamma, float4& dbeta, float* a, float* b) {
+    float xh[4], gg[4], gm[4], bb[4], dg[4], db[4];
+    xhat4(v, m0, m1, xh);
+    unpack4(g, gg);
+    unpack4(ga, gm);
+    unpack4(be, bb);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        spade_bwd_grad(gg[k], xh[k], gm[k], bb[k], relu, dg[k], db[k], a[k]);
+        b[k] = a[k] * xh[k];
+    }
+    dgamma = make_float4(dg[0], dg[1], dg[2], dg[3]);
+    dbeta = make_float4(db[0], db[1], db[2], db[3]);
+}
+// s1 / s2: mean(dxhat) and mean(dxhat * xhat) of the quad's channels (unused in eval mode)
+__device__ __forceinline__ float4 spade_bwd4(const float4& v, const float4& g, const float4& ga, const float4& be, const float4& m0,
+                                             const float4& m1, const float* s1, const float* s2, const bool relu, const bool train) {
+    float xv[4], gg[4], gm[4], bb[4], mean[4], rs[4], o[4];
+    unpack4(v, xv);
+    unpack4(g, gg);
+    unpack4(ga, gm);
+    unpack4(be, bb);
+    unpack_mr(m0, m1, mean, rs);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float xh = norm_xhat(xv[k], mean[k], rs[k]);
+        float dg, db, dxh;
+        spade_bwd_grad(gg[k], xh, gm[k], bb[k], relu, dg, db, dxh);
+        o[k] = spade_bwd_out(dxh, xh, rs[k], s1[k], s2[k], train);
+    }
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+__device__ __forceinline__ void spade_bwd_means4(const double* sums, double inv_count, int c4, const bool train, float* s1, float* s2) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        s1[k] = train ? (float)(sums[2 * (4 * c4 + k)] * inv_count) : 0.f;
+        s2[k] = train ? (float)(sums[2 * (4 * c4 + k) + 1] * inv_count) : 0.f;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -65,11 +188,22 @@ __global__ void __launch_bounds__(256) k_plane_reduce(F f, double* __restrict__ 
 }
 
 // float4 variant for C % 4 == 0: a lane owns 4 consecutive channels, C/4 lanes span a pixel, 256/(C/4) pixel rows per
-// pass (1 KiB contiguous per wave-instruction).  Functor F4: (float4 index i4, n, channel c) -> a[4], b[4].
+// pass (1 KiB contiguous per wave-instruction).  Functor F4: consts(n, c4) -> the per-(n, quad) constants m0, m1;
+// load(float4 index i4, pixel of the batch, c4) -> Raw; eval(Raw, pixel, c4, m0, m1) -> a[4], b[4] (no integer division per
+// element).  This form evaluates one element at a time through eval_one4; the pipelined form below keeps the constants in
+// registers and separates the loads from the evaluation.
 // (round 4: at least four waves per SIMD - the compiler's 214-register schedule left two, ~64 KB of loads in flight per CU,
 // and the pure-read passes ran at 3.6-4.1 TB/s; a group of four elements is summed in fp32 before it joins the double
 // accumulators unless the functor asks for doubles throughout (F4::kDoubleTree: the forward statistics, where E[x^2] - mean^2
 // cancels))
+template <class F4>
+__device__ __forceinline__ void eval_one4(const F4& f, long i4, long pix, int n, int c4, float* a, float* b) {
+    float4 m0 = make_float4(0.f, 0.f, 0.f, 0.f), m1 = m0;
+    typename F4::Raw r;
+    f.consts(n, c4, m0, m1);
+    f.load(i4, pix, c4, r);
+    f.eval(r, pix, c4, m0, m1, a, b);
+}
 template <class F4>
 __global__ void __launch_bounds__(256, F4::kMinWaves) k_plane_reduce4(F4 f, double* __restrict__ part, int HW, int C, int splits) {
     __shared__ double sa[4][256], sb[4][256];
@@ -91,10 +225,10 @@ __global__ void __launch_bounds__(256, F4::kMinWaves) k_plane_reduce4(F4 f, doub
             for (; p + 3 * rows < p1; p += 4 * rows) {  // four independent element loads in flight per lane
                 float va[4], vb[4], wa[4], wb[4], xa[4], xb[4], ya[4], yb[4];
                 const long q = (long)n * HW + p;
-                f(q * C4 + c4, q, n, c4 * 4, va, vb);
-                f((q + rows) * C4 + c4, q + rows, n, c4 * 4, wa, wb);
-                f((q + 2 * rows) * C4 + c4, q + 2 * rows, n, c4 * 4, xa, xb);
-                f((q + 3 * rows) * C4 + c4, q + 3 * rows, n, c4 * 4, ya, yb);
+                eval_one4(f, q * C4 + c4, q, n, c4, va, vb);
+                eval_one4(f, (q + rows) * C4 + c4, q + rows, n, c4, wa, wb);
+                eval_one4(f, (q + 2 * rows) * C4 + c4, q + 2 * rows, n, c4, xa, xb);
+                eval_one4(f, (q + 3 * rows) * C4 + c4, q + 3 * rows, n, c4, ya, yb);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     if (F4::kDoubleTree) {
@@ -109,15 +243,15 @@ __global__ void __launch_bounds__(256, F4::kMinWaves) k_plane_reduce4(F4 f, doub
             for (; p + rows < p1; p += 2 * rows) {
                 float va[4], vb[4], wa[4], wb[4];
                 const long q = (long)n * HW + p;
-                f(q * C4 + c4, q, n, c4 * 4, va, vb);
-                f((q + rows) * C4 + c4, q + rows, n, c4 * 4, wa, wb);
+                eval_one4(f, q * C4 + c4, q, n, c4, va, vb);
+                eval_one4(f, (q + rows) * C4 + c4, q + rows, n, c4, wa, wb);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { a[k] += (double)va[k] + (double)wa[k]; b[k] += (double)vb[k] + (double)wb[k]; }
             }
             for (; p < p1; p += rows) {
                 float va[4], vb[4];
                 const long q = (long)n * HW + p;
-                f(q * C4 + c4, q, n, c4 * 4, va, vb);
+                eval_one4(f, q * C4 + c4, q, n, c4, va, vb);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { a[k] += (double)va[k]; b[k] += (double)vb[k]; }
             }
@@ -241,7 +375,7 @@ static inline int plane_splits_p(int N, int HW, int C4) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// InstanceNorm
+// Reduction functors: forward statistics, InstanceNorm backward sums, SPADE backward sums
 struct FStats4 {
     static constexpr bool kDoubleTree = true;
     static constexpr int kMinWaves = 4;
@@ -250,13 +384,10 @@ struct FStats4 {
     __device__ void consts(int, int, float4&, float4&) const {}
     __device__ void load(long i4, long, int, Raw& r) const { r.v = x[i4]; }
     __device__ void eval(const Raw& r, long, int, const float4&, const float4&, float* a, float* b) const {
-        a[0] = r.v.x; a[1] = r.v.y; a[2] = r.v.z; a[3] = r.v.w;
-        b[0] = r.v.x * r.v.x; b[1] = r.v.y * r.v.y; b[2] = r.v.z * r.v.z; b[3] = r.v.w * r.v.w;
-    }
-    __device__ void operator()(long i4, long, int, int, float* a, float* b) const {
-        float4 v = x[i4];
-        a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
-        b[0] = v.x * v.x; b[1] = v.y * v.y; b[2] = v.z * v.z; b[3] = v.w * v.w;
+        float v[4];
+        unpack4(r.v, v);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) stats_terms(v[k], a[k], b[k]);
     }
 };
 template <int RELU>
@@ -274,29 +405,10 @@ struct FInBwd4 {
     }
     __device__ void load(long i4, long pix, int c4, Raw& r) const { r.v = x[i4]; r.g = gy[pix * gcs4 + gco4 + c4]; }
     __device__ void eval(const Raw& r, long, int, const float4& m0, const float4& m1, float* a, float* b) const {
-        const float xh[4] = {(r.v.x - m0.x) * m0.y, (r.v.y - m0.z) * m0.w, (r.v.z - m1.x) * m1.y, (r.v.w - m1.z) * m1.w};
-        const float gg[4] = {r.g.x, r.g.y, r.g.z, r.g.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float q = (RELU && !(xh[k] > 0.f)) ? 0.f : gg[k];
-            a[k] = q;
-            b[k] = q * xh[k];
-        }
-    }
-    // i4 = (pix * C4 + c4) with pix = n * HW + p the pixel of the batch, c = 4 * c4 (no integer division per element)
-    __device__ void operator()(long i4, long pix, int n, int c, float* a, float* b) const {
-        const float4* m = (const float4*)(mr + 2 * ((long)n * C + c));
-        float4 m0 = m[0], m1 = m[1], v = x[i4], g = gy[pix * gcs4 + gco4 + (c >> 2)];
-        float xh[4] = {(v.x - m0.x) * m0.y, (v.y - m0.z) * m0.w, (v.z - m1.x) * m1.y, (v.w - m1.z) * m1.w};
-        float gg[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float q = (RELU && !(xh[k] > 0.f)) ? 0.f : gg[k];
-            a[k] = q;
-            b[k] = q * xh[k];
-        }
+        inorm_bwd_terms4(r.v, r.g, m0, m1, RELU, a, b);
     }
 };
+// per-channel sums of (dxhat, dxhat * xhat); dgamma / dbeta are written as a side effect of the reduction
 template <int RELU>
 struct FSpadeBwd4 {
     static constexpr bool kDoubleTree = false;
@@ -319,58 +431,71 @@ struct FSpadeBwd4 {
         r.be = RELU ? beta[pix * gbs4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __device__ void eval(const Raw& r, long pix, int c4, const float4& m0, const float4& m1, float* a, float* b) const {
-        const float xh[4] = {(r.v.x - m0.x) * m0.y, (r.v.y - m0.z) * m0.w, (r.v.z - m1.x) * m1.y, (r.v.w - m1.z) * m1.w};
-        const float gg[4] = {r.g.x, r.g.y, r.g.z, r.g.w}, gm[4] = {1.f + r.ga.x, 1.f + r.ga.y, 1.f + r.ga.z, 1.f + r.ga.w};
-        const float bb[4] = {r.be.x, r.be.y, r.be.z, r.be.w};
-        float dg[4], db[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float q = gg[k];
-            if (RELU && !(xh[k] * gm[k] + bb[k] > 0.f)) q = 0.f;
-            dg[k] = q * xh[k];
-            db[k] = q;
-            const float dxh = q * gm[k];
-            a[k] = dxh;
-            b[k] = dxh * xh[k];
-        }
+        float4 dg, db;
+        spade_bwd_terms4(r.v, r.g, r.ga, r.be, m0, m1, RELU, dg, db, a, b);
         const long j4 = pix * gbs4 + c4;
-        dgamma[j4] = make_float4(dg[0], dg[1], dg[2], dg[3]);
-        dbeta[j4] = make_float4(db[0], db[1], db[2], db[3]);
+        dgamma[j4] = dg;
+        dbeta[j4] = db;
     }
-    __device__ void operator()(long i4, long pix, int, int c, float* a, float* b) const {
-        const float4* m = (const float4*)(mr + 2 * c);
-        const long j4 = pix * gbs4 + (c >> 2);
-        float4 m0 = m[0], m1 = m[1], v = x[i4], g = gy[i4], ga = gamma[j4], be = beta[j4];
-        float xh[4] = {(v.x - m0.x) * m0.y, (v.y - m0.z) * m0.w, (v.z - m1.x) * m1.y, (v.w - m1.z) * m1.w};
-        float gg[4] = {g.x, g.y, g.z, g.w}, gm[4] = {1.f + ga.x, 1.f + ga.y, 1.f + ga.z, 1.f + ga.w};
-        float bb[4] = {be.x, be.y, be.z, be.w}, dg[4], db[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float q = gg[k];
-            if (RELU && !(xh[k] * gm[k] + bb[k] > 0.f)) q = 0.f;
-            dg[k] = q * xh[k];
-            db[k] = q;
-            float dxh = q * gm[k];
-            a[k] = dxh;
-            b[k] = dxh * xh[k];
-        }
-        float4 o1, o2;
-        o1.x = dg[0]; o1.y = dg[1]; o1.z = dg[2]; o1.w = dg[3];
-        o2.x = db[0]; o2.y = db[1]; o2.z = db[2]; o2.w = db[3];
-        dgamma[j4] = o1;
-        dbeta[j4] = o2;
+    // k_plane_reduce4's one-element form (eval_one4 below): through consts/load/eval that kernel takes 212 registers
+    // instead of 150 and loses a wave per SIMD.  Plumbing only, the arithmetic is spade_bwd_terms4's.
+    __device__ void one(long i4, long pix, int c4, float* a, float* b) const {
+        const float4* m = (const float4*)(mr + 8 * c4);
+        const long j4 = pix * gbs4 + c4;
+        const float4 m0 = m[0], m1 = m[1], v = x[i4], g = gy[i4], ga = gamma[j4], be = beta[j4];
+        float4 dg, db;
+        spade_bwd_terms4(v, g, ga, be, m0, m1, RELU, dg, db, a, b);
+        dgamma[j4] = dg;
+        dbeta[j4] = db;
     }
 };
-static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+template <int RELU>
+__device__ __forceinline__ void eval_one4(const FSpadeBwd4<RELU>& f, long i4, long pix, int, int c4, float* a, float* b) { f.one(i4, pix, c4, a, b); }
 
+// the scalar tier's functors: (x-element index i, n, c) -> (a, b)
 struct FStats {
     const float* x;
-    __device__ void operator()(long i, int, int, float& a, float& b) const { float v = x[i]; a = v; b = v * v; }
+    __device__ void operator()(long i, int, int, float& a, float& b) const { stats_terms(x[i], a, b); }
+};
+template <int RELU>
+struct FInBwd {
+    const float* x;
+    const float* mr;
+    const float* gy;
+    int C, gcs, gco;
+    __device__ void operator()(long i, int n, int c, float& a, float& b) const {
+        const float* m = mr + 2 * ((long)n * C + c);
+        const float xh = norm_xhat(x[i], m[0], m[1]);
+        a = inorm_bwd_term(gy[(i / C) * gcs + gco + c], xh, RELU);
+        b = a * xh;
+    }
+};
+template <int RELU>
+struct FSpadeBwd {
+    const float* x;
+    const float* mr;
+    const float* gamma;
+    const float* beta;
+    const float* gy;
+    float* dgamma;
+    float* dbeta;
+    int C, gbs;
+    __device__ void operator()(long i, int, int c, float& a, float& b) const {
+        const long j = (i / C) * gbs + c;
+        const float xh = norm_xhat(x[i], mr[2 * c], mr[2 * c + 1]);
+        spade_bwd_grad(gy[i], xh, gamma[j], RELU ? beta[j] : 0.f, RELU, dgamma[j], dbeta[j], a);
+        b = a * xh;
+    }
 };
 
-// One WAVE per (n, c): lane s holds the partial of split s (splits <= 64), summed by the fixed butterfly.  A thread per
-// plane walking its splits one dependent load after the other made these launches ~13 us each; they sit on the
-// dependency chain between the reduction and the apply pass of every normalisation.
+// ---------------------------------------------------------------------------------------------
+// Finalise kernels.  A partial source hands out one (a, b) pair per row of a partial array [rows][C][2]; the kernels below sum
+// the rows of a plane (one wave per (n, c)) or of a channel (one workgroup per channel) in double, in a fixed order.
+// The variance rule belongs to the source and is stated here once:
+//  - SplitSums: double sums of fp32 squares from FStats / FStats4 -> var_from_squares;
+//  - TileMoments: float (sum, M2 about the tile mean) per tile from a convolution's epilogue, M2 >= 0 by construction and
+//    turned into a sum of squares in double -> E[x^2] - mean^2 with a clamp at 0;
+//  - RegionSums: float (sum a, sum b) per region, sums only (no statistics are made from them).
 static_assert(PLANE_MAX_SPLITS <= 64, "one lane per split");
 // var = E[x^2] - mean^2 from sums of squares that FStats / FStats4 rounded to fp32 (relative error <= 2^-24 each): a variance
 // within that bound of E[x^2] cannot be told from 0.  An exactly constant plane (x = 1.15: its fp32 square is 4.5e-8 above the
@@ -380,26 +505,97 @@ __device__ __forceinline__ double var_from_squares(double ex2, double mean) {
     const double var = ex2 - mean * mean;
     return var <= 0x1p-24 * ex2 ? 0.0 : var;
 }
-__global__ void __launch_bounds__(256) k_inorm_finalize(const double* __restrict__ part, float* __restrict__ mr, int NC, int C,
-                                                        int splits, double inv_hw, float eps) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), s = threadIdx.x & 63;
-    if (i >= NC) return;              // wave-uniform
-    int n = i / C, c = i % C;
-    double a = 0.0, b = 0.0;
-    if (s < splits) {
-        const double* o = part + (((long)n * splits + s) * C + c) * 2;
+struct SplitSums {
+    static constexpr bool kLanePerRow = true;     // rows per plane = splits <= 64
+    const double* part;
+    int rows;
+    __device__ void get(long row, int C, int c, double& a, double& b) const {
+        const double* o = part + (row * C + c) * 2;
         a = o[0];
         b = o[1];
+    }
+    static __device__ double variance(double ex2, double mean) { return var_from_squares(ex2, mean); }
+};
+struct TileMoments {
+    static constexpr bool kLanePerRow = false;
+    const float* part;
+    int rows;
+    double inv_tile;                              // 1 / pixels per tile
+    __device__ void get(long row, int C, int c, double& a, double& b) const {
+        const float* o = part + (row * C + c) * 2;
+        const double st = (double)o[0];
+        a = st;
+        b = (double)o[1] + st * st * inv_tile;
+    }
+    static __device__ double variance(double ex2, double mean) {
+        const double var = ex2 - mean * mean;
+        return var < 0.0 ? 0.0 : var;
+    }
+};
+struct RegionSums {
+    static constexpr bool kLanePerRow = false;
+    const float* part;
+    int rows;
+    __device__ void get(long row, int C, int c, double& a, double& b) const {
+        const float* o = part + (row * C + c) * 2;
+        a = (double)o[0];
+        b = (double)o[1];
+    }
+};
+// One WAVE per (n, c): the lanes take the plane's rows (lane s the partial of split s, or the tiles round-robin), summed by
+// the fixed butterfly.  A thread per plane walking its splits one dependent load after the other made these launches ~13 us
+// each; they sit on the dependency chain between the reduction and the apply pass of every normalisation.
+// STATS: out = (mean, rstd) by the source's variance rule, else out = the two sums times `scale`.  JOBS = 2: two jobs of
+// one shape (a ResBlock's tail: main branch and 1x1 branch) in ONE launch, blockIdx.y selects the job.
+template <class Src, int JOBS>
+struct PlaneJobs {
+    Src src[JOBS];
+    float* out[JOBS];
+};
+template <class Src, bool STATS, int JOBS>
+__global__ void __launch_bounds__(256) k_plane_finalize(PlaneJobs<Src, JOBS> jobs, int NC, int C, double scale, float eps) {
+    const bool second = JOBS > 1 && blockIdx.y;
+    const Src src = second ? jobs.src[JOBS - 1] : jobs.src[0];
+    float* out = second ? jobs.out[JOBS - 1] : jobs.out[0];
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), s = threadIdx.x & 63;
+    if (i >= NC) return;              // wave-uniform
+    const int n = i / C, c = i % C;
+    double a = 0.0, b = 0.0;
+    if (Src::kLanePerRow) {
+        if (s < src.rows) src.get((long)n * src.rows + s, C, c, a, b);
+    } else {
+        for (int t = s; t < src.rows; t += 64) {
+            double ta, tb;
+            src.get((long)n * src.rows + t, C, c, ta, tb);
+            a += ta;
+            b += tb;
+        }
     }
     a = wave_sum_d(a);
     b = wave_sum_d(b);
     if (s != 0) return;
-    double mean = a * inv_hw;
-    double var = var_from_squares(b * inv_hw, mean);
-    mr[2 * i] = (float)mean;
-    mr[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    if constexpr (STATS) {
+        const double mean = a * scale;
+        const double var = Src::variance(b * scale, mean);
+        out[2 * i] = (float)mean;
+        out[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    } else {
+        out[2 * i] = (float)(a * scale);
+        out[2 * i + 1] = (float)(b * scale);
+    }
+}
+template <bool STATS, class Src>
+static void launch_plane_finalize(Src src, float* out, int N, int C, double scale, float eps, hipStream_t st) {
+    k_plane_finalize<Src, STATS, 1><<<ceil_div((long)N * C, 4), 256, 0, st>>>(PlaneJobs<Src, 1>{{src}, {out}}, N * C, C, scale, eps);
+}
+template <bool STATS, class Src>
+static void launch_plane_finalize2(Src sa, float* oa, Src sb, float* ob, int N, int C, double scale, float eps, hipStream_t st) {
+    k_plane_finalize<Src, STATS, 2><<<dim3(ceil_div((long)N * C, 4), 2), 256, 0, st>>>(PlaneJobs<Src, 2>{{sa, sb}, {oa, ob}}, N * C, C, scale, eps);
 }
 
+// ---------------------------------------------------------------------------------------------
+// InstanceNorm apply maps: scalar flat index, float4 flat index (C % 4 == 0 and un-sliced or 4-aligned slices: 16 B per lane
+// streams), float4 walk (below)
 template <int RELU>
 __global__ void k_inorm_apply(const float* __restrict__ x, const float* __restrict__ mr, float* __restrict__ y,
                               long total, int HW, int C, int ycs, int yco) {
@@ -409,12 +605,10 @@ __global__ void k_inorm_apply(const float* __restrict__ x, const float* __restri
         int c = (int)(i % C);
         int n = (int)(i / plane);
         const float* m = mr + 2 * ((long)n * C + c);
-        float v = (x[i] - m[0]) * m[1];
+        float v = norm_xhat(x[i], m[0], m[1]);
         y[(i / C) * ycs + yco + c] = RELU ? fmaxf(v, 0.f) : v;
     }
 }
-
-// float4 variants for C % 4 == 0 and un-sliced tensors (the common case): 16 B per lane streams
 template <int RELU>
 __global__ void k_inorm_apply4(const float4* __restrict__ x, const float* __restrict__ mr, float4* __restrict__ y, long total4,
                                int HW, int C4, int ycs4, int yco4) {
@@ -424,11 +618,23 @@ __global__ void k_inorm_apply4(const float4* __restrict__ x, const float* __rest
         int c = (int)(i % C4) * 4;
         int n = (int)(i / plane4);
         const float4* m = (const float4*)(mr + 2 * ((long)n * C4 * 4 + c));
-        float4 m0 = m[0], m1 = m[1];          // (mean,rstd) pairs of channels c..c+3
-        float4 v = x[i], r;
-        r.x = (v.x - m0.x) * m0.y; r.y = (v.y - m0.z) * m0.w; r.z = (v.z - m1.x) * m1.y; r.w = (v.w - m1.z) * m1.w;
-        if (RELU) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
-        y[(i / C4) * ycs4 + yco4 + (i % C4)] = r;
+        const float4 m0 = m[0], m1 = m[1], v = x[i];          // (mean,rstd) pairs of channels c..c+3
+        y[(i / C4) * ycs4 + yco4 + (i % C4)] = inorm4(v, m0, m1, RELU);
+    }
+}
+template <int RELU>
+__global__ void k_inorm_bwd_apply(const float* __restrict__ x, const float* __restrict__ mr, const float* __restrict__ gy,
+                                  const float* __restrict__ means, float* __restrict__ gx, long total, int HW, int C,
+                                  int gcs, int gco) {
+    long stride = (long)gridDim.x * blockDim.x;
+    long plane = (long)HW * C;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        int c = (int)(i % C);
+        int n = (int)(i / plane);
+        long k = 2 * ((long)n * C + c);
+        float r = mr[k + 1];
+        float xh = norm_xhat(x[i], mr[k], r);
+        gx[i] = inorm_bwd_out(inorm_bwd_term(gy[(i / C) * gcs + gco + c], xh, RELU), xh, r, means[k], means[k + 1]);
     }
 }
 template <int RELU>
@@ -443,27 +649,67 @@ __global__ void k_inorm_bwd_apply4(const float4* __restrict__ x, const float* __
         long k = 2 * ((long)n * C4 * 4 + c);
         const float4* m = (const float4*)(mr + k);
         const float4* e = (const float4*)(means + k);
+        const float4 m0 = m[0], m1 = m[1], e0 = e[0], e1 = e[1];
+        const float4 v = x[i], g = gy[(i / C4) * gcs4 + gco4 + (i % C4)];
+        gx[i] = inorm_bwd4(v, g, m0, m1, e0, e1, RELU);
+    }
+}
+// two InstanceNorms that receive the same gradient (a with its ReLU, b without), flat float4 index
+__global__ void k_inorm_bwd_pair_apply4(const float4* __restrict__ xa, const float* __restrict__ mra, const float* __restrict__ ea,
+                                        const float4* __restrict__ xb, const float* __restrict__ mrb, const float* __restrict__ eb,
+                                        const float4* __restrict__ gy, float4* __restrict__ gxa, float4* __restrict__ gxb,
+                                        long total4, int HW, int C4) {
+    long stride = (long)gridDim.x * blockDim.x;
+    long plane4 = (long)HW * C4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += stride) {
+        const int c = (int)(i % C4) * 4;
+        const int n = (int)(i / plane4);
+        const long k = 2 * ((long)n * C4 * 4 + c);
+        const float4* m = (const float4*)(mra + k);
+        const float4* e = (const float4*)(ea + k);
         float4 m0 = m[0], m1 = m[1], e0 = e[0], e1 = e[1];
-        float4 v = x[i], g = gy[(i / C4) * gcs4 + gco4 + (i % C4)], o;
-        float xh, gg;
-        xh = (v.x - m0.x) * m0.y; gg = (RELU && !(xh > 0.f)) ? 0.f : g.x; o.x = m0.y * (gg - e0.x - xh * e0.y);
-        xh = (v.y - m0.z) * m0.w; gg = (RELU && !(xh > 0.f)) ? 0.f : g.y; o.y = m0.w * (gg - e0.z - xh * e0.w);
-        xh = (v.z - m1.x) * m1.y; gg = (RELU && !(xh > 0.f)) ? 0.f : g.z; o.z = m1.y * (gg - e1.x - xh * e1.y);
-        xh = (v.w - m1.z) * m1.w; gg = (RELU && !(xh > 0.f)) ? 0.f : g.w; o.w = m1.w * (gg - e1.z - xh * e1.w);
-        gx[i] = o;
+        const float4 g = gy[i];
+        float4 v = xa[i];
+        gxa[i] = inorm_bwd4(v, g, m0, m1, e0, e1, true);
+        m = (const float4*)(mrb + k);
+        e = (const float4*)(eb + k);
+        m0 = m[0]; m1 = m[1]; e0 = e[0]; e1 = e[1];
+        v = xb[i];
+        gxb[i] = inorm_bwd4(v, g, m0, m1, e0, e1, false);
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// Division-free walks (round 4).  The flat-index kernels above spend ~220 vector instructions per float4 on 64-bit integer
-// divisions (i / plane4, i % C4, (i / C4) * stride with run-time divisors) and re-load the per-(n, c) constants for every
-// element.  When C4 = C / 4 is a power of two <= 256 a 256-thread workgroup covers 256 consecutive float4 = R = 256 / C4 whole
-// pixels: thread t keeps its channel quad c4 = t & (C4 - 1) for the whole walk (its constants stay in registers), its pixel is
-// p = base + (t >> log2 C4) and advances by R per step; grid.y = image for the per-image constants.  Four independent
-// 16-byte loads per tensor in flight per thread.
+// Tier choice and flag dispatch, each written once.
+// Tiers of an element-wise map: scalar flat index; float4 flat index (C % 4 == 0, every channel stride and offset % 4 == 0,
+// every tensor 16-byte aligned); float4 division-free walk (additionally C / 4 a power of two <= 256, see below).  A reduction
+// on the float4 tiers is k_plane_reduce4 / k_plane_reduce4p (launch_plane_reduce4 picks by the same walk_ok).
+static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static inline int ilog2_exact(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
 static inline bool walk_ok(int C4) { return C4 >= 1 && C4 <= 256 && ilog2_exact(C4) >= 0; }
-// the float4 plane reduction in its pipelined form where C4 allows; returns the number of splits it wrote
+enum Tier { TIER_SCALAR, TIER_FLAT4, TIER_WALK4 };
+// strides: the OR of the channel strides and offsets of the call; ptrs: exactly the tensors the launch will read as float4
+template <class... P>
+static inline Tier pick_tier(int C, int strides, const P*... ptrs) {
+    const uintptr_t bits = (... | (uintptr_t)ptrs);
+    if ((C & 3) || (strides & 3) || (bits & 15)) return TIER_SCALAR;
+    return walk_ok(C / 4) ? TIER_WALK4 : TIER_FLAT4;
+}
+// a run-time flag as a template argument: with_flag(relu, [&](auto R) { constexpr int RELU = decltype(R)::value; ... })
+template <class Fn>
+static inline void with_flag(int on, Fn&& fn) {
+    if (on) fn(std::true_type{});
+    else fn(std::false_type{});
+}
+
+// the plane reductions; each returns the number of splits it wrote
+template <class F>
+static int launch_plane_reduce(F f, double* part, int N, int HW, int C, hipStream_t st) {
+    const int sp = plane_splits(N, HW);
+    k_plane_reduce<<<dim3(sp, N), 256, 0, st>>>(f, part, HW, C, sp);
+    return sp;
+}
+// float4: the pipelined form where C4 allows
 template <class F4>
 static int launch_plane_reduce4(F4 f, double* part, int N, int HW, int C, hipStream_t st) {
     const int C4 = C / 4;
@@ -476,6 +722,19 @@ static int launch_plane_reduce4(F4 f, double* part, int N, int HW, int C, hipStr
     k_plane_reduce4<<<dim3(sp, N), 256, 0, st>>>(f, part, HW, C, sp);
     return sp;
 }
+// (sum x, sum x^2) per plane and split
+static int launch_stats_reduce(const float* x, double* part, int N, int HW, int C, hipStream_t st) {
+    if (pick_tier(C, 0, x) != TIER_SCALAR) return launch_plane_reduce4(FStats4{(const float4*)x}, part, N, HW, C, st);
+    return launch_plane_reduce(FStats{x}, part, N, HW, C, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Division-free walks (round 4).  The flat-index kernels above spend ~220 vector instructions per float4 on 64-bit integer
+// divisions (i / plane4, i % C4, (i / C4) * stride with run-time divisors) and re-load the per-(n, c) constants for every
+// element.  When C4 = C / 4 is a power of two <= 256 a 256-thread workgroup covers 256 consecutive float4 = R = 256 / C4 whole
+// pixels: thread t keeps its channel quad c4 = t & (C4 - 1) for the whole walk (its constants stay in registers), its pixel is
+// p = base + (t >> log2 C4) and advances by R per step; grid.y = image for the per-image constants.  Four independent
+// 16-byte loads per tensor in flight per thread.
 static inline int walk_blocks(int N, int HW, int C4) {       // workgroups per image: ~2048 in all, each >= one 4 R-pixel step
     const int R = 256 / C4;
     int per = ceil_div(2048, N);
@@ -501,10 +760,7 @@ __global__ void __launch_bounds__(256) k_inorm_apply4w(const float4* __restrict_
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (p0 + u * R >= HW) break;
-            float4 o;
-            o.x = (v[u].x - m0.x) * m0.y; o.y = (v[u].y - m0.z) * m0.w; o.z = (v[u].z - m1.x) * m1.y; o.w = (v[u].w - m1.z) * m1.w;
-            if (RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-            yn[(long)(p0 + u * R) * ycs4] = o;
+            yn[(long)(p0 + u * R) * ycs4] = inorm4(v[u], m0, m1, RELU);
         }
     }
 }
@@ -527,9 +783,7 @@ __global__ void __launch_bounds__(256) k_inorm_add4w(const float4* __restrict__ 
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (p0 + u * R >= HW) break;
-            float4 o;
-            o.x = (v[u].x - m0.x) * m0.y; o.y = (v[u].y - m0.z) * m0.w; o.z = (v[u].z - m1.x) * m1.y; o.w = (v[u].w - m1.z) * m1.w;
-            if (RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+            float4 o = inorm4(v[u], m0, m1, RELU);
             o.x = w[u].x + o.x; o.y = w[u].y + o.y; o.z = w[u].z + o.z; o.w = w[u].w + o.w;
             y[base + (long)(p0 + u * R) * C4] = o;
         }
@@ -545,21 +799,11 @@ extern "C" int vqw_inorm_add_fwd(const float* x, const float* mean_rstd, const f
     const int C4 = C / 4;
     const dim3 g(walk_blocks(N, HW, C4), N);
     hipStream_t st = (hipStream_t)stream;
-    if (relu) k_inorm_add4w<1><<<g, 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)a, (float4*)y, HW, C4, ilog2_exact(C4));
-    else k_inorm_add4w<0><<<g, 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)a, (float4*)y, HW, C4, ilog2_exact(C4));
+    with_flag(relu, [&](auto R) {
+        k_inorm_add4w<decltype(R)::value><<<g, 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)a, (float4*)y, HW, C4, ilog2_exact(C4));
+    });
     VQW_LAUNCH_CHECK("vqw_inorm_add_fwd");
     return VQW_OK;
-}
-
-__device__ __forceinline__ float4 inorm_bwd_elem(const float4 v, const float4 g, const float4 m0, const float4 m1, const float4 e0,
-                                                 const float4 e1, const bool relu) {
-    float4 o;
-    float xh, gg;
-    xh = (v.x - m0.x) * m0.y; gg = (relu && !(xh > 0.f)) ? 0.f : g.x; o.x = m0.y * (gg - e0.x - xh * e0.y);
-    xh = (v.y - m0.z) * m0.w; gg = (relu && !(xh > 0.f)) ? 0.f : g.y; o.y = m0.w * (gg - e0.z - xh * e0.w);
-    xh = (v.z - m1.x) * m1.y; gg = (relu && !(xh > 0.f)) ? 0.f : g.z; o.z = m1.y * (gg - e1.x - xh * e1.y);
-    xh = (v.w - m1.z) * m1.w; gg = (relu && !(xh > 0.f)) ? 0.f : g.w; o.w = m1.w * (gg - e1.z - xh * e1.w);
-    return o;
 }
 
 template <int RELU>
@@ -582,7 +826,7 @@ __global__ void __launch_bounds__(256) k_inorm_bwd_apply4w(const float4* __restr
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (p0 + u * R >= HW) break;
-            on[(long)(p0 + u * R) * C4] = inorm_bwd_elem(v[u], g[u], m0, m1, e0, e1, RELU);
+            on[(long)(p0 + u * R) * C4] = inorm_bwd4(v[u], g[u], m0, m1, e0, e1, RELU);
         }
     }
 }
@@ -612,8 +856,8 @@ __global__ void __launch_bounds__(256) k_inorm_bwd_pair_apply4w(const float4* __
         for (int u = 0; u < 2; ++u) {
             if (p0 + u * R >= HW) break;
             const long i = base + (long)(p0 + u * R) * C4;
-            gxa[i] = inorm_bwd_elem(va[u], g[u], a0, a1, f0, f1, true);
-            gxb[i] = inorm_bwd_elem(vb[u], g[u], b0, b1, h0, h1, false);
+            gxa[i] = inorm_bwd4(va[u], g[u], a0, a1, f0, f1, true);
+            gxb[i] = inorm_bwd4(vb[u], g[u], b0, b1, h0, h1, false);
         }
     }
 }
@@ -641,20 +885,16 @@ __global__ void __launch_bounds__(256) k_spade_fwd4w(const float4* __restrict__ 
                 if (RES == 2) {
                     const float4* q = (const float4*)(rmr + (((p >> lgHW) << lgC4) + c4) * 8);      // (mean, rstd) of 4 channels
                     const float4 q0 = q[0], q1 = q[1];
-                    rr[u].x = fmaxf((rr[u].x - q0.x) * q0.y, rlo); rr[u].y = fmaxf((rr[u].y - q0.z) * q0.w, rlo);
-                    rr[u].z = fmaxf((rr[u].z - q1.x) * q1.y, rlo); rr[u].w = fmaxf((rr[u].w - q1.z) * q1.w, rlo);
+                    float h[4];
+                    xhat4(rr[u], q0, q1, h);
+                    rr[u] = make_float4(fmaxf(h[0], rlo), fmaxf(h[1], rlo), fmaxf(h[2], rlo), fmaxf(h[3], rlo));
                 }
             }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (p0 + u * R >= P) break;
-            float4 o;
-            o.x = (v[u].x - m0.x) * m0.y * (1.f + ga[u].x) + be[u].x;
-            o.y = (v[u].y - m0.z) * m0.w * (1.f + ga[u].y) + be[u].y;
-            o.z = (v[u].z - m1.x) * m1.y * (1.f + ga[u].z) + be[u].z;
-            o.w = (v[u].w - m1.z) * m1.w * (1.f + ga[u].w) + be[u].w;
-            if (RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-            if (RES) { o.x += rr[u].x; o.y += rr[u].y; o.z += rr[u].z; o.w += rr[u].w; }
+            float4 o = spade4(v[u], ga[u], be[u], m0, m1, RELU);
+            if (RES) { o.x += rr[u].x; o.y += rr[u].y; o.z += rr[u].z; o.w += rr[u].w; }      // AFTER the activation (blocks.py:134)
             y[(p0 + u * R) * C4 + c4] = o;
         }
     }
@@ -667,13 +907,8 @@ __global__ void __launch_bounds__(256) k_spade_bwd_apply4w(const float4* __restr
                                                            double inv_count, float4* __restrict__ gx, long P, int C4, int lgC4, int gbs4) {
     WALK4_SETUP;
     const float4 m0 = ((const float4*)(mr + 8 * c4))[0], m1 = ((const float4*)(mr + 8 * c4))[1];
-    const float mean[4] = {m0.x, m0.z, m1.x, m1.z}, rs[4] = {m0.y, m0.w, m1.y, m1.w};
     float s1[4], s2[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        s1[k] = TRAIN ? (float)(sums[2 * (4 * c4 + k)] * inv_count) : 0.f;
-        s2[k] = TRAIN ? (float)(sums[2 * (4 * c4 + k) + 1] * inv_count) : 0.f;
-    }
+    spade_bwd_means4(sums, inv_count, c4, TRAIN, s1, s2);
     for (long p0 = (long)blockIdx.x * 2 * R + r; p0 < P; p0 += (long)gridDim.x * 2 * R) {
         float4 v[2], ga4[2], g4[2], be4[2];
 #pragma unroll
@@ -686,23 +921,7 @@ __global__ void __launch_bounds__(256) k_spade_bwd_apply4w(const float4* __restr
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             if (p0 + u * R >= P) break;
-            const float xv[4] = {v[u].x, v[u].y, v[u].z, v[u].w}, gav[4] = {ga4[u].x, ga4[u].y, ga4[u].z, ga4[u].w};
-            const float gv[4] = {g4[u].x, g4[u].y, g4[u].z, g4[u].w}, bev[4] = {be4[u].x, be4[u].y, be4[u].z, be4[u].w};
-            float o[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float rk = rs[k];
-                const float xh = (xv[k] - mean[k]) * rk;
-                const float ga = 1.f + gav[k];
-                float g = gv[k];
-                if (RELU) {
-                    const float out = xh * ga + bev[k];
-                    if (!(out > 0.f)) g = 0.f;
-                }
-                const float dxh = g * ga;
-                o[k] = TRAIN ? rk * (dxh - s1[k] - xh * s2[k]) : rk * dxh;
-            }
-            gx[(p0 + u * R) * C4 + c4] = make_float4(o[0], o[1], o[2], o[3]);
+            gx[(p0 + u * R) * C4 + c4] = spade_bwd4(v[u], g4[u], ga4[u], be4[u], m0, m1, s1, s2, RELU, TRAIN);
         }
     }
 }
@@ -712,89 +931,51 @@ static inline int walk_blocks_flat(long P, int C4, int per_step) {
     return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
 }
 
-// launchers: the walk form where C4 allows, else the flat-index form
-static void launch_inorm_apply4(const float* x, const float* mr, float* y, int N, int HW, int C, int ycs, int yco, int relu, hipStream_t st) {
+// ---------------------------------------------------------------------------------------------
+// InstanceNorm entry points
+static void launch_inorm_apply(Tier tier, const float* x, const float* mr, float* y, int N, int HW, int C, int ycs, int yco, int relu,
+                               hipStream_t st) {
     const int C4 = C / 4;
-    if (walk_ok(C4)) {
-        const dim3 g(walk_blocks(N, HW, C4), N);
-        if (relu) k_inorm_apply4w<1><<<g, 256, 0, st>>>((const float4*)x, mr, (float4*)y, HW, C4, ilog2_exact(C4), ycs / 4, yco / 4);
-        else k_inorm_apply4w<0><<<g, 256, 0, st>>>((const float4*)x, mr, (float4*)y, HW, C4, ilog2_exact(C4), ycs / 4, yco / 4);
-        return;
-    }
-    const long t4 = (long)N * HW * C4;
-    if (relu) k_inorm_apply4<1><<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)x, mr, (float4*)y, t4, HW, C4, ycs / 4, yco / 4);
-    else k_inorm_apply4<0><<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)x, mr, (float4*)y, t4, HW, C4, ycs / 4, yco / 4);
+    const long total = (long)N * HW * C;
+    with_flag(relu, [&](auto R) {
+        constexpr int RELU = decltype(R)::value;
+        if (tier == TIER_WALK4)
+            k_inorm_apply4w<RELU><<<dim3(walk_blocks(N, HW, C4), N), 256, 0, st>>>((const float4*)x, mr, (float4*)y, HW, C4, ilog2_exact(C4), ycs / 4, yco / 4);
+        else if (tier == TIER_FLAT4)
+            k_inorm_apply4<RELU><<<stream_grid(total / 4, 256), 256, 0, st>>>((const float4*)x, mr, (float4*)y, total / 4, HW, C4, ycs / 4, yco / 4);
+        else k_inorm_apply<RELU><<<stream_grid(total, 256), 256, 0, st>>>(x, mr, y, total, HW, C, ycs, yco);
+    });
 }
-static void launch_inorm_bwd_apply4(const float* x, const float* mr, const float* gy, const float* means, float* gx, int N, int HW, int C,
-                                    int gcs, int gco, int relu, hipStream_t st) {
+static void launch_inorm_bwd_apply(Tier tier, const float* x, const float* mr, const float* gy, const float* means, float* gx, int N, int HW,
+                                   int C, int gcs, int gco, int relu, hipStream_t st) {
     const int C4 = C / 4;
-    if (walk_ok(C4)) {
-        const dim3 g(walk_blocks(N, HW, C4), N);
-        if (relu) k_inorm_bwd_apply4w<1><<<g, 256, 0, st>>>((const float4*)x, mr, (const float4*)gy, means, (float4*)gx, HW, C4, ilog2_exact(C4), gcs / 4, gco / 4);
-        else k_inorm_bwd_apply4w<0><<<g, 256, 0, st>>>((const float4*)x, mr, (const float4*)gy, means, (float4*)gx, HW, C4, ilog2_exact(C4), gcs / 4, gco / 4);
-        return;
-    }
-    const long t4 = (long)N * HW * C4;
-    if (relu) k_inorm_bwd_apply4<1><<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)x, mr, (const float4*)gy, means, (float4*)gx, t4, HW, C4, gcs / 4, gco / 4);
-    else k_inorm_bwd_apply4<0><<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)x, mr, (const float4*)gy, means, (float4*)gx, t4, HW, C4, gcs / 4, gco / 4);
+    const long total = (long)N * HW * C;
+    with_flag(relu, [&](auto R) {
+        constexpr int RELU = decltype(R)::value;
+        if (tier == TIER_WALK4)
+            k_inorm_bwd_apply4w<RELU><<<dim3(walk_blocks(N, HW, C4), N), 256, 0, st>>>((const float4*)x, mr, (const float4*)gy, means, (float4*)gx, HW, C4, ilog2_exact(C4), gcs / 4, gco / 4);
+        else if (tier == TIER_FLAT4)
+            k_inorm_bwd_apply4<RELU><<<stream_grid(total / 4, 256), 256, 0, st>>>((const float4*)x, mr, (const float4*)gy, means, (float4*)gx, total / 4, HW, C4, gcs / 4, gco / 4);
+        else k_inorm_bwd_apply<RELU><<<stream_grid(total, 256), 256, 0, st>>>(x, mr, gy, means, gx, total, HW, C, gcs, gco);
+    });
+}
+// (mean, rstd) per (n, c) from the tensor itself, or from the per-tile partials part[n][nparts][C][2] the conv that produced x left
+static void inorm_stats_from_x(const float* x, float* mr, double* part, int N, int HW, int C, float eps, hipStream_t st) {
+    const int splits = launch_stats_reduce(x, part, N, HW, C, st);
+    launch_plane_finalize<true>(SplitSums{part, splits}, mr, N, C, 1.0 / (double)HW, eps, st);
+}
+static void inorm_stats_from_tiles(const float* part, int nparts, float* mr, int N, int HW, int C, float eps, hipStream_t st) {
+    launch_plane_finalize<true>(TileMoments{part, nparts, (double)nparts / (double)HW}, mr, N, C, 1.0 / (double)HW, eps, st);
 }
 
-// statistics from per-tile float partials part[n][nparts][C][2] (written by the conv that produced x): one wave per
-// (n, c), lanes take the tiles round-robin and sum in double, fixed butterfly
-__global__ void __launch_bounds__(256) k_inorm_finalize_parts(const float* __restrict__ part, float* __restrict__ mr, int NC, int C,
-                                                              int nparts, double inv_hw, float eps, double inv_tile) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), s = threadIdx.x & 63;
-    if (i >= NC) return;              // wave-uniform
-    const int n = i / C, c = i % C;
-    double a = 0.0, b = 0.0;
-    for (int t = s; t < nparts; t += 64) {
-        const float* o = part + (((long)n * nparts + t) * C + c) * 2;     // (sum, M2 about the tile mean) of one tile
-        const double st = (double)o[0];
-        a += st;
-        b += (double)o[1] + st * st * inv_tile;                           // -> sum of squares, in double
-    }
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    if (s != 0) return;
-    double mean = a * inv_hw;
-    double var = b * inv_hw - mean * mean;
-    if (var < 0.0) var = 0.0;
-    mr[2 * i] = (float)mean;
-    mr[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
-}
-// two norms of one shape (a ResBlock's tail: main branch and 1x1 branch) in ONE launch: blockIdx.y selects the job
-__global__ void __launch_bounds__(256) k_inorm_finalize_parts2(const float* __restrict__ part_a, float* __restrict__ mr_a, int nparts_a,
-                                                               const float* __restrict__ part_b, float* __restrict__ mr_b, int nparts_b,
-                                                               int NC, int C, double inv_hw, float eps) {
-    const float* part = blockIdx.y ? part_b : part_a;
-    float* mr = blockIdx.y ? mr_b : mr_a;
-    const int nparts = blockIdx.y ? nparts_b : nparts_a;
-    const double inv_tile = (double)nparts * inv_hw;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), s = threadIdx.x & 63;
-    if (i >= NC) return;              // wave-uniform
-    const int n = i / C, c = i % C;
-    double a = 0.0, b = 0.0;
-    for (int t = s; t < nparts; t += 64) {
-        const float* o = part + (((long)n * nparts + t) * C + c) * 2;
-        const double st = (double)o[0];
-        a += st;
-        b += (double)o[1] + st * st * inv_tile;
-    }
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    if (s != 0) return;
-    double mean = a * inv_hw;
-    double var = b * inv_hw - mean * mean;
-    if (var < 0.0) var = 0.0;
-    mr[2 * i] = (float)mean;
-    mr[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
-}
+// two norms of one shape (a ResBlock's tail: main branch and 1x1 branch) in ONE launch
 extern "C" int vqw_inorm_stats_parts2(const float* part_a, int nparts_a, float* mean_rstd_a, const float* part_b, int nparts_b,
                                       float* mean_rstd_b, int N, int HW, int C, float eps, void* stream) {
     VQW_CHECK(part_a && part_b && mean_rstd_a && mean_rstd_b && nparts_a > 0 && nparts_b > 0 && N > 0 && HW > 0 && C > 0,
               "vqw_inorm_stats_parts2: bad arguments");
-    k_inorm_finalize_parts2<<<dim3(ceil_div((long)N * C, 4), 2), 256, 0, (hipStream_t)stream>>>(part_a, mean_rstd_a, nparts_a, part_b, mean_rstd_b,
-                                                                                                  nparts_b, N * C, C, 1.0 / (double)HW, eps);
+    const double inv_hw = 1.0 / (double)HW;
+    launch_plane_finalize2<true>(TileMoments{part_a, nparts_a, (double)nparts_a * inv_hw}, mean_rstd_a,
+                                 TileMoments{part_b, nparts_b, (double)nparts_b * inv_hw}, mean_rstd_b, N, C, inv_hw, eps, (hipStream_t)stream);
     VQW_LAUNCH_CHECK("vqw_inorm_stats_parts2");
     return VQW_OK;
 }
@@ -805,12 +986,8 @@ extern "C" int vqw_inorm_fwd_parts(const float* x, float* y, int y_cstride, int 
     VQW_CHECK(x && y && mean_rstd && part && nparts > 0 && N > 0 && HW > 0 && C > 0, "vqw_inorm_fwd_parts: bad arguments");
     VQW_CHECK(y_coff >= 0 && y_coff + C <= y_cstride, "vqw_inorm_fwd_parts: output channel slice [%d,%d) outside stride %d", y_coff, y_coff + C, y_cstride);
     hipStream_t st = (hipStream_t)stream;
-    k_inorm_finalize_parts<<<ceil_div((long)N * C, 4), 256, 0, st>>>(part, mean_rstd, N * C, C, nparts, 1.0 / (double)HW, eps, (double)nparts / (double)HW);
-    long total = (long)N * HW * C;
-    if ((C & 3) == 0 && (y_cstride & 3) == 0 && (y_coff & 3) == 0 && ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)mean_rstd) & 15) == 0)) {
-        launch_inorm_apply4(x, mean_rstd, y, N, HW, C, y_cstride, y_coff, relu, st);
-    } else if (relu) k_inorm_apply<1><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, y, total, HW, C, y_cstride, y_coff);
-    else k_inorm_apply<0><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, y, total, HW, C, y_cstride, y_coff);
+    inorm_stats_from_tiles(part, nparts, mean_rstd, N, HW, C, eps, st);
+    launch_inorm_apply(pick_tier(C, y_cstride | y_coff, x, y, mean_rstd), x, mean_rstd, y, N, HW, C, y_cstride, y_coff, relu, st);
     VQW_LAUNCH_CHECK("vqw_inorm_fwd_parts");
     return VQW_OK;
 }
@@ -820,22 +997,13 @@ extern "C" int vqw_inorm_stats(const float* x, float* mean_rstd, void* ws, size_
                                void* stream) {
     VQW_CHECK(x && mean_rstd && ws && N > 0 && HW > 0 && C > 0, "vqw_inorm_stats: bad arguments");
     VQW_CHECK(ws_bytes >= vqw_plane_ws_bytes(N, C, HW), "vqw_inorm_stats: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    int splits = plane_splits(N, HW);
-    if ((C & 3) == 0 && al16(x)) {
-        FStats4 f{(const float4*)x};
-        splits = launch_plane_reduce4(f, (double*)ws, N, HW, C, st);
-    } else {
-        FStats f{x};
-        k_plane_reduce<<<dim3(splits, N), 256, 0, st>>>(f, (double*)ws, HW, C, splits);
-    }
-    k_inorm_finalize<<<ceil_div((long)N * C, 4), 256, 0, st>>>((const double*)ws, mean_rstd, N * C, C, splits, 1.0 / (double)HW, eps);
+    inorm_stats_from_x(x, mean_rstd, (double*)ws, N, HW, C, eps, (hipStream_t)stream);
     VQW_LAUNCH_CHECK("vqw_inorm_stats");
     return VQW_OK;
 }
 extern "C" int vqw_inorm_stats_parts(const float* part, int nparts, float* mean_rstd, int N, int HW, int C, float eps, void* stream) {
     VQW_CHECK(part && mean_rstd && nparts > 0 && N > 0 && HW > 0 && C > 0, "vqw_inorm_stats_parts: bad arguments");
-    k_inorm_finalize_parts<<<ceil_div((long)N * C, 4), 256, 0, (hipStream_t)stream>>>(part, mean_rstd, N * C, C, nparts, 1.0 / (double)HW, eps, (double)nparts / (double)HW);
+    inorm_stats_from_tiles(part, nparts, mean_rstd, N, HW, C, eps, (hipStream_t)stream);
     VQW_LAUNCH_CHECK("vqw_inorm_stats_parts");
     return VQW_OK;
 }
@@ -847,98 +1015,10 @@ extern "C" int vqw_inorm_fwd(const float* x, float* y, int y_cstride, int y_coff
     VQW_CHECK(y_coff >= 0 && y_coff + C <= y_cstride, "vqw_inorm_fwd: output channel slice [%d,%d) outside stride %d", y_coff, y_coff + C, y_cstride);
     VQW_CHECK(ws_bytes >= vqw_plane_ws_bytes(N, C, HW), "vqw_inorm_fwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    int splits = plane_splits(N, HW);
-    if ((C & 3) == 0 && al16(x)) {
-        FStats4 f{(const float4*)x};
-        splits = launch_plane_reduce4(f, (double*)ws, N, HW, C, st);
-    } else {
-        FStats f{x};
-        k_plane_reduce<<<dim3(splits, N), 256, 0, st>>>(f, (double*)ws, HW, C, splits);
-    }
-    k_inorm_finalize<<<ceil_div((long)N * C, 4), 256, 0, st>>>((const double*)ws, mean_rstd, N * C, C, splits,
-                                                                 1.0 / (double)HW, eps);
-    long total = (long)N * HW * C;
-    if ((C & 3) == 0 && (y_cstride & 3) == 0 && (y_coff & 3) == 0 && ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)mean_rstd) & 15) == 0)) {
-        launch_inorm_apply4(x, mean_rstd, y, N, HW, C, y_cstride, y_coff, relu, st);
-    } else if (relu) k_inorm_apply<1><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, y, total, HW, C, y_cstride, y_coff);
-    else k_inorm_apply<0><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, y, total, HW, C, y_cstride, y_coff);
+    inorm_stats_from_x(x, mean_rstd, (double*)ws, N, HW, C, eps, st);
+    launch_inorm_apply(pick_tier(C, y_cstride | y_coff, x, y, mean_rstd), x, mean_rstd, y, N, HW, C, y_cstride, y_coff, relu, st);
     VQW_LAUNCH_CHECK("vqw_inorm_fwd");
     return VQW_OK;
-}
-
-// backward: ghat = gy * [xhat > 0] (relu) ; dx = rstd * (ghat - mean(ghat) - xhat * mean(ghat*xhat))
-template <int RELU>
-struct FInBwd {
-    const float* x;
-    const float* mr;
-    const float* gy;
-    int C, gcs, gco;
-    __device__ void operator()(long i, int n, int c, float& a, float& b) const {
-        const float* m = mr + 2 * ((long)n * C + c);
-        float xh = (x[i] - m[0]) * m[1];
-        float g = gy[(i / C) * gcs + gco + c];
-        if (RELU && !(xh > 0.f)) g = 0.f;
-        a = g;
-        b = g * xh;
-    }
-};
-
-__global__ void __launch_bounds__(256) k_plane_sum_finalize(const double* __restrict__ part, float* __restrict__ out, int NC, int C,
-                                                            int splits, double scale) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), s = threadIdx.x & 63;       // one wave per (n, c), see k_inorm_finalize
-    if (i >= NC) return;
-    int n = i / C, c = i % C;
-    double a = 0.0, b = 0.0;
-    if (s < splits) {
-        const double* o = part + (((long)n * splits + s) * C + c) * 2;
-        a = o[0];
-        b = o[1];
-    }
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    if (s != 0) return;
-    out[2 * i] = (float)(a * scale);
-    out[2 * i + 1] = (float)(b * scale);
-}
-
-// two jobs of one shape in one launch (the paired backward of a ResBlock's tail norms): blockIdx.y selects the job
-__global__ void __launch_bounds__(256) k_plane_sum_finalize2(const double* __restrict__ part_a, float* __restrict__ out_a,
-                                                             const double* __restrict__ part_b, float* __restrict__ out_b, int NC, int C,
-                                                             int splits, double scale) {
-    const double* part = blockIdx.y ? part_b : part_a;
-    float* out = blockIdx.y ? out_b : out_a;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), s = threadIdx.x & 63;
-    if (i >= NC) return;
-    int n = i / C, c = i % C;
-    double a = 0.0, b = 0.0;
-    if (s < splits) {
-        const double* o = part + (((long)n * splits + s) * C + c) * 2;
-        a = o[0];
-        b = o[1];
-    }
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    if (s != 0) return;
-    out[2 * i] = (float)(a * scale);
-    out[2 * i + 1] = (float)(b * scale);
-}
-
-template <int RELU>
-__global__ void k_inorm_bwd_apply(const float* __restrict__ x, const float* __restrict__ mr, const float* __restrict__ gy,
-                                  const float* __restrict__ means, float* __restrict__ gx, long total, int HW, int C,
-                                  int gcs, int gco) {
-    long stride = (long)gridDim.x * blockDim.x;
-    long plane = (long)HW * C;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        int c = (int)(i % C);
-        int n = (int)(i / plane);
-        long k = 2 * ((long)n * C + c);
-        float r = mr[k + 1];
-        float xh = (x[i] - mr[k]) * r;
-        float g = gy[(i / C) * gcs + gco + c];
-        if (RELU && !(xh > 0.f)) g = 0.f;
-        gx[i] = r * (g - means[k] - xh * means[k + 1]);
-    }
 }
 
 extern "C" int vqw_inorm_bwd(const float* x, const float* mean_rstd, const float* gy, int gy_cstride, int gy_coff,
@@ -949,30 +1029,18 @@ extern "C" int vqw_inorm_bwd(const float* x, const float* mean_rstd, const float
     size_t need = vqw_plane_ws_bytes(N, C, HW);
     VQW_CHECK(ws_bytes >= need, "vqw_inorm_bwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    int splits = plane_splits(N, HW);
     double* part = (double*)ws;
     float* means = (float*)((char*)ws + plane_part_bytes(N, C));
-    long total = (long)N * HW * C;
-    const bool vec = (C & 3) == 0 && (gy_cstride & 3) == 0 && (gy_coff & 3) == 0 && al16(x) && al16(gy) && al16(mean_rstd);
-    if (vec && relu) {
-        FInBwd4<1> f{(const float4*)x, mean_rstd, (const float4*)gy, C, gy_cstride / 4, gy_coff / 4};
-        splits = launch_plane_reduce4(f, part, N, HW, C, st);
-    } else if (vec) {
-        FInBwd4<0> f{(const float4*)x, mean_rstd, (const float4*)gy, C, gy_cstride / 4, gy_coff / 4};
-        splits = launch_plane_reduce4(f, part, N, HW, C, st);
-    } else if (relu) {
-        FInBwd<1> f{x, mean_rstd, gy, C, gy_cstride, gy_coff};
-        k_plane_reduce<<<dim3(splits, N), 256, 0, st>>>(f, part, HW, C, splits);
-    } else {
-        FInBwd<0> f{x, mean_rstd, gy, C, gy_cstride, gy_coff};
-        k_plane_reduce<<<dim3(splits, N), 256, 0, st>>>(f, part, HW, C, splits);
-    }
-    k_plane_sum_finalize<<<ceil_div((long)N * C, 4), 256, 0, st>>>(part, means, N * C, C, splits, 1.0 / (double)HW);
-    if ((C & 3) == 0 && (gy_cstride & 3) == 0 && (gy_coff & 3) == 0 &&
-        ((((uintptr_t)x | (uintptr_t)gy | (uintptr_t)gx | (uintptr_t)mean_rstd | (uintptr_t)means) & 15) == 0)) {
-        launch_inorm_bwd_apply4(x, mean_rstd, gy, means, gx, N, HW, C, gy_cstride, gy_coff, relu, st);
-    } else if (relu) k_inorm_bwd_apply<1><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, gy, means, gx, total, HW, C, gy_cstride, gy_coff);
-    else k_inorm_bwd_apply<0><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, gy, means, gx, total, HW, C, gy_cstride, gy_coff);
+    const int gs = gy_cstride | gy_coff;
+    int splits = 0;
+    with_flag(relu, [&](auto R) {
+        constexpr int RELU = decltype(R)::value;
+        if (pick_tier(C, gs, x, gy, mean_rstd) != TIER_SCALAR)
+            splits = launch_plane_reduce4(FInBwd4<RELU>{(const float4*)x, mean_rstd, (const float4*)gy, C, gy_cstride / 4, gy_coff / 4}, part, N, HW, C, st);
+        else splits = launch_plane_reduce(FInBwd<RELU>{x, mean_rstd, gy, C, gy_cstride, gy_coff}, part, N, HW, C, st);
+    });
+    launch_plane_finalize<false>(SplitSums{part, splits}, means, N, C, 1.0 / (double)HW, 0.f, st);
+    launch_inorm_bwd_apply(pick_tier(C, gs, x, gy, gx, mean_rstd, means), x, mean_rstd, gy, means, gx, N, HW, C, gy_cstride, gy_coff, relu, st);
     VQW_LAUNCH_CHECK("vqw_inorm_bwd");
     return VQW_OK;
 }
@@ -980,35 +1048,13 @@ extern "C" int vqw_inorm_bwd(const float* x, const float* mean_rstd, const float
 // The same backward with the two sums taken from per-region partials part[N][nparts][C][2] = (sum gm, sum gm * xhat) that the
 // consumer convolution's input-gradient launch left in its epilogue (vqw_conv3x3_wino_fwd_inbwd): no reduction pass over x and
 // gy.  One wave per (n, c) adds the regions in double, then the apply kernel of vqw_inorm_bwd.
-__global__ void __launch_bounds__(256) k_plane_sum_finalize_f(const float* __restrict__ part, float* __restrict__ out, int NC, int C,
-                                                              int nparts, double scale) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), s = threadIdx.x & 63;
-    if (i >= NC) return;              // wave-uniform
-    const int n = i / C, c = i % C;
-    double a = 0.0, b = 0.0;
-    for (int t = s; t < nparts; t += 64) {
-        const float* o = part + (((long)n * nparts + t) * C + c) * 2;
-        a += (double)o[0];
-        b += (double)o[1];
-    }
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    if (s != 0) return;
-    out[2 * i] = (float)(a * scale);
-    out[2 * i + 1] = (float)(b * scale);
-}
-
 extern "C" int vqw_inorm_bwd_parts(const float* x, const float* mean_rstd, const float* gy, const float* part, int nparts, float* means_ws,
                                    float* gx, int N, int HW, int C, int relu, void* stream) {
     VQW_PROF_HBM(stream, 3, (double)N * HW * C);
     VQW_CHECK(x && mean_rstd && gy && part && means_ws && gx && nparts > 0 && N > 0 && HW > 0 && C > 0, "vqw_inorm_bwd_parts: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    k_plane_sum_finalize_f<<<ceil_div((long)N * C, 4), 256, 0, st>>>(part, means_ws, N * C, C, nparts, 1.0 / (double)HW);
-    const long total = (long)N * HW * C;
-    if ((C & 3) == 0 && ((((uintptr_t)x | (uintptr_t)gy | (uintptr_t)gx | (uintptr_t)mean_rstd | (uintptr_t)means_ws) & 15) == 0)) {
-        launch_inorm_bwd_apply4(x, mean_rstd, gy, means_ws, gx, N, HW, C, C, 0, relu, st);
-    } else if (relu) k_inorm_bwd_apply<1><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, gy, means_ws, gx, total, HW, C, C, 0);
-    else k_inorm_bwd_apply<0><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, gy, means_ws, gx, total, HW, C, C, 0);
+    launch_plane_finalize<false>(RegionSums{part, nparts}, means_ws, N, C, 1.0 / (double)HW, 0.f, st);
+    launch_inorm_bwd_apply(pick_tier(C, 0, x, gy, gx, mean_rstd, means_ws), x, mean_rstd, gy, means_ws, gx, N, HW, C, C, 0, relu, st);
     VQW_LAUNCH_CHECK("vqw_inorm_bwd_parts");
     return VQW_OK;
 }
@@ -1017,11 +1063,36 @@ extern "C" int vqw_inorm_bwd_parts(const float* x, const float* mean_rstd, const
 // Backward of TWO InstanceNorms that receive the SAME gradient (the two branches in front of a ResBlock tail: a with
 // its ReLU, b without): one reduction and one apply kernel read the common gradient once instead of twice each.
 // Arithmetic per element is that of vqw_inorm_bwd.
+// acc[quantity: a.sum, a.dot, b.sum, b.dot][channel of the quad]: the fold over the pixel rows of a workgroup through LDS
+// (sq[quantity][channel][thread]), then the partials of both norms; c0 = row * C + first channel of the quad
+__device__ __forceinline__ void pair_fold_store(const double (&acc)[4][4], double (&sq)[4][4][256], bool lead, int rows, int tcn, int tc,
+                                                long c0, double* __restrict__ parta, double* __restrict__ partb) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sq[q][k][t] = acc[q][k];
+    __syncthreads();
+    if (lead) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            double tq[4] = {acc[0][k], acc[1][k], acc[2][k], acc[3][k]};
+            for (int r = 1; r < rows; ++r)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) tq[q] += sq[q][k][r * tcn + tc];
+            double* oa = parta + (c0 + k) * 2;
+            double* ob = partb + (c0 + k) * 2;
+            oa[0] = tq[0]; oa[1] = tq[1];
+            ob[0] = tq[2]; ob[1] = tq[3];
+        }
+    }
+    __syncthreads();
+}
 __global__ void __launch_bounds__(256, 4) k_inorm_bwd_pair_reduce4(const float4* __restrict__ xa, const float* __restrict__ mra,
                                                                 const float4* __restrict__ xb, const float* __restrict__ mrb,
                                                                 const float4* __restrict__ gy, double* __restrict__ parta,
                                                                 double* __restrict__ partb, int HW, int C, int splits) {
-    __shared__ double sq[4][4][256];        // [quantity: a.sum, a.dot, b.sum, b.dot][channel of the quad][thread]
+    __shared__ double sq[4][4][256];
     const int n = blockIdx.y, s = blockIdx.x;
     const int C4 = C >> 2;
     const int tcn = C4 < 256 ? C4 : 256;
@@ -1046,38 +1117,19 @@ __global__ void __launch_bounds__(256, 4) k_inorm_bwd_pair_reduce4(const float4*
             for (int p = p0 + tr; p < p1; p += rows) {
                 const long i4 = ((long)n * HW + p) * C4 + c4;
                 const float4 va = xa[i4], vb = xb[i4], g = gy[i4];
-                const float xha[4] = {(va.x - a0.x) * a0.y, (va.y - a0.z) * a0.w, (va.z - a1.x) * a1.y, (va.w - a1.z) * a1.w};
-                const float xhb[4] = {(vb.x - b0.x) * b0.y, (vb.y - b0.z) * b0.w, (vb.z - b1.x) * b1.y, (vb.w - b1.z) * b1.w};
-                const float gg[4] = {g.x, g.y, g.z, g.w};
+                float ta[4], tb[4], ua[4], ub[4];
+                inorm_bwd_terms4(va, g, a0, a1, true, ta, tb);        // branch a: ReLU after the norm
+                inorm_bwd_terms4(vb, g, b0, b1, false, ua, ub);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float qa = !(xha[k] > 0.f) ? 0.f : gg[k];        // branch a: ReLU after the norm
-                    acc[0][k] += (double)qa;
-                    acc[1][k] += (double)(qa * xha[k]);
-                    acc[2][k] += (double)gg[k];
-                    acc[3][k] += (double)(gg[k] * xhb[k]);
+                    acc[0][k] += (double)ta[k];
+                    acc[1][k] += (double)tb[k];
+                    acc[2][k] += (double)ua[k];
+                    acc[3][k] += (double)ub[k];
                 }
             }
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) sq[q][k][t] = acc[q][k];
-        __syncthreads();
-        if (tr == 0 && c4 < C4) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                double tq[4] = {acc[0][k], acc[1][k], acc[2][k], acc[3][k]};
-                for (int r = 1; r < rows; ++r)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) tq[q] += sq[q][k][r * tcn + tc];
-                double* oa = parta + (((long)n * splits + s) * C + c4 * 4 + k) * 2;
-                double* ob = partb + (((long)n * splits + s) * C + c4 * 4 + k) * 2;
-                oa[0] = tq[0]; oa[1] = tq[1];
-                ob[0] = tq[2]; ob[1] = tq[3];
-            }
-        }
-        __syncthreads();
+        pair_fold_store(acc, sq, tr == 0 && c4 < C4, rows, tcn, tc, ((long)n * splits + s) * C + c4 * 4, parta, partb);
     }
 }
 // k_res_tail_bwd4 (elementwise.hip) and k_inorm_bwd_pair_reduce4 in ONE pass: a thread takes a 2 x 2 pooling window of its channel
@@ -1141,8 +1193,8 @@ __global__ void __launch_bounds__(256, 2) k_res_tail_bwd_pair_reduce4(const floa
                         const float tt = gf[4 * k + ch] + (k == amx ? gyf[ch] : 0.f);
                         const float gg = vf[4 * k + ch] > 0.f ? tt : 0.f;
                         gf[4 * k + ch] = gg;
-                        const float xha = (af[4 * k + ch] - am[ch]) * ar[ch], xhb = (bf[4 * k + ch] - bm[ch]) * br[ch];
-                        const float qa = !(xha > 0.f) ? 0.f : gg;        // branch a: ReLU after the norm
+                        const float xha = norm_xhat(af[4 * k + ch], am[ch], ar[ch]), xhb = norm_xhat(bf[4 * k + ch], bm[ch], br[ch]);
+                        const float qa = inorm_bwd_term(gg, xha, true);        // branch a: ReLU after the norm
                         acc[0][ch] += (double)qa;
                         acc[1][ch] += (double)(qa * xha);
                         acc[2][ch] += (double)gg;
@@ -1153,58 +1205,32 @@ __global__ void __launch_bounds__(256, 2) k_res_tail_bwd_pair_reduce4(const floa
                 for (int k = 0; k < 4; ++k) gw[idx[k]] = g[k];
             }
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) sq[q][k][t] = acc[q][k];
-        __syncthreads();
-        if (tr == 0 && c4 < C4) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                double tq[4] = {acc[0][k], acc[1][k], acc[2][k], acc[3][k]};
-                for (int r = 1; r < rows; ++r)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) tq[q] += sq[q][k][r * tcn + tc];
-                double* oa = parta + (((long)n * splits + s) * C + c4 * 4 + k) * 2;
-                double* ob = partb + (((long)n * splits + s) * C + c4 * 4 + k) * 2;
-                oa[0] = tq[0]; oa[1] = tq[1];
-                ob[0] = tq[2]; ob[1] = tq[3];
-            }
-        }
-        __syncthreads();
+        pair_fold_store(acc, sq, tr == 0 && c4 < C4, rows, tcn, tc, ((long)n * splits + s) * C + c4 * 4, parta, partb);
     }
 }
-__global__ void k_inorm_bwd_pair_apply4(const float4* __restrict__ xa, const float* __restrict__ mra, const float* __restrict__ ea,
-                                        const float4* __restrict__ xb, const float* __restrict__ mrb, const float* __restrict__ eb,
-                                        const float4* __restrict__ gy, float4* __restrict__ gxa, float4* __restrict__ gxb,
-                                        long total4, int HW, int C4) {
-    long stride = (long)gridDim.x * blockDim.x;
-    long plane4 = (long)HW * C4;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += stride) {
-        const int c = (int)(i % C4) * 4;
-        const int n = (int)(i / plane4);
-        const long k = 2 * ((long)n * C4 * 4 + c);
-        const float4* m = (const float4*)(mra + k);
-        const float4* e = (const float4*)(ea + k);
-        float4 m0 = m[0], m1 = m[1], e0 = e[0], e1 = e[1];
-        const float4 g = gy[i];
-        float4 v = xa[i], o;
-        float xh, gg;
-        xh = (v.x - m0.x) * m0.y; gg = !(xh > 0.f) ? 0.f : g.x; o.x = m0.y * (gg - e0.x - xh * e0.y);
-        xh = (v.y - m0.z) * m0.w; gg = !(xh > 0.f) ? 0.f : g.y; o.y = m0.w * (gg - e0.z - xh * e0.w);
-        xh = (v.z - m1.x) * m1.y; gg = !(xh > 0.f) ? 0.f : g.z; o.z = m1.y * (gg - e1.x - xh * e1.y);
-        xh = (v.w - m1.z) * m1.w; gg = !(xh > 0.f) ? 0.f : g.w; o.w = m1.w * (gg - e1.z - xh * e1.w);
-        gxa[i] = o;
-        m = (const float4*)(mrb + k);
-        e = (const float4*)(eb + k);
-        m0 = m[0]; m1 = m[1]; e0 = e[0]; e1 = e[1];
-        v = xb[i];
-        xh = (v.x - m0.x) * m0.y; o.x = m0.y * (g.x - e0.x - xh * e0.y);
-        xh = (v.y - m0.z) * m0.w; o.y = m0.w * (g.y - e0.z - xh * e0.w);
-        xh = (v.z - m1.x) * m1.y; o.z = m1.y * (g.z - e1.x - xh * e1.y);
-        xh = (v.w - m1.z) * m1.w; o.w = m1.w * (g.w - e1.z - xh * e1.w);
-        gxb[i] = o;
-    }
+// the workspace of the pair entry points: 2 x vqw_plane_ws_bytes(N, C, HW), each partials followed by the finalised means
+struct PairWs {
+    double *parta, *partb;
+    float *ea, *eb;
+};
+static PairWs pair_ws(void* ws, int N, int C, int HW) {
+    const size_t one = vqw_plane_ws_bytes(N, C, HW), pb = plane_part_bytes(N, C);
+    return PairWs{(double*)ws, (double*)((char*)ws + one), (float*)((char*)ws + pb), (float*)((char*)ws + one + pb)};
+}
+// second half of both pair entry points: the means of the sums in one launch, then the apply pass over (xa, xb, g)
+static void inorm_bwd_pair_finish(const float* xa, const float* mra, const float* xb, const float* mrb, const float* g, float* gxa,
+                                  float* gxb, const PairWs& w, int splits, int N, int HW, int C, hipStream_t st) {
+    launch_plane_finalize2<false>(SplitSums{w.parta, splits}, w.ea, SplitSums{w.partb, splits}, w.eb, N, C, 1.0 / (double)HW, 0.f, st);
+    const int C4 = C / 4;
+    const long t4 = (long)N * HW * C / 4;
+    if (walk_ok(C4)) {
+        const int R = 256 / C4;
+        const dim3 gr(imax(1, imin(ceil_div(2048, N), ceil_div(HW, 2 * R))), N);
+        k_inorm_bwd_pair_apply4w<<<gr, 256, 0, st>>>((const float4*)xa, mra, w.ea, (const float4*)xb, mrb, w.eb, (const float4*)g, (float4*)gxa,
+                                                      (float4*)gxb, HW, C4, ilog2_exact(C4));
+    } else
+        k_inorm_bwd_pair_apply4<<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)xa, mra, w.ea, (const float4*)xb, mrb, w.eb,
+                                                                      (const float4*)g, (float4*)gxa, (float4*)gxb, t4, HW, C4);
 }
 // a: InstanceNorm + ReLU, b: InstanceNorm; both get gy.  ws: 2 x vqw_plane_ws_bytes(N, C, HW).
 extern "C" int vqw_inorm_bwd_pair(const float* xa, const float* mra, const float* xb, const float* mrb, const float* gy, float* gxa,
@@ -1218,22 +1244,10 @@ extern "C" int vqw_inorm_bwd_pair(const float* xa, const float* mra, const float
     VQW_CHECK(ws_bytes >= 2 * one && (one & 15) == 0, "vqw_inorm_bwd_pair: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int splits = plane_splits(N, HW);
-    double* parta = (double*)ws;
-    float* ea = (float*)((char*)ws + plane_part_bytes(N, C));
-    double* partb = (double*)((char*)ws + one);
-    float* eb = (float*)((char*)ws + one + plane_part_bytes(N, C));
-    k_inorm_bwd_pair_reduce4<<<dim3(splits, N), 256, 0, st>>>((const float4*)xa, mra, (const float4*)xb, mrb, (const float4*)gy, parta,
-                                                               partb, HW, C, splits);
-    k_plane_sum_finalize2<<<dim3(ceil_div((long)N * C, 4), 2), 256, 0, st>>>(parta, ea, partb, eb, N * C, C, splits, 1.0 / (double)HW);
-    const long t4 = (long)N * HW * C / 4;
-    if (walk_ok(C / 4)) {
-        const int R = 256 / (C / 4);
-        const dim3 g(imax(1, imin(ceil_div(2048, N), ceil_div(HW, 2 * R))), N);
-        k_inorm_bwd_pair_apply4w<<<g, 256, 0, st>>>((const float4*)xa, mra, ea, (const float4*)xb, mrb, eb, (const float4*)gy, (float4*)gxa,
-                                                     (float4*)gxb, HW, C / 4, ilog2_exact(C / 4));
-    } else
-    k_inorm_bwd_pair_apply4<<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)xa, mra, ea, (const float4*)xb, mrb, eb,
-                                                                  (const float4*)gy, (float4*)gxa, (float4*)gxb, t4, HW, C / 4);
+    const PairWs w = pair_ws(ws, N, C, HW);
+    k_inorm_bwd_pair_reduce4<<<dim3(splits, N), 256, 0, st>>>((const float4*)xa, mra, (const float4*)xb, mrb, (const float4*)gy, w.parta,
+                                                               w.partb, HW, C, splits);
+    inorm_bwd_pair_finish(xa, mra, xb, mrb, gy, gxa, gxb, w, splits, N, HW, C, st);
     VQW_LAUNCH_CHECK("vqw_inorm_bwd_pair");
     return VQW_OK;
 }
@@ -1253,39 +1267,46 @@ extern "C" int vqw_res_tail_bwd_pair(const float* out, const float* g_pooled, co
     VQW_CHECK(ws_bytes >= 2 * one && (one & 15) == 0, "vqw_res_tail_bwd_pair: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int splits = plane_splits(N, HW);
-    double* parta = (double*)ws;
-    float* ea = (float*)((char*)ws + plane_part_bytes(N, C));
-    double* partb = (double*)((char*)ws + one);
-    float* eb = (float*)((char*)ws + one + plane_part_bytes(N, C));
+    const PairWs w = pair_ws(ws, N, C, HW);
     k_res_tail_bwd_pair_reduce4<<<dim3(splits, N), 256, 0, st>>>((const float4*)out, (const float4*)g_pooled, (const float4*)g_out,
-                                                                  (const float4*)xa, mra, (const float4*)xb, mrb, (float4*)g, parta, partb, H, W, C,
+                                                                  (const float4*)xa, mra, (const float4*)xb, mrb, (float4*)g, w.parta, w.partb, H, W, C,
                                                                   splits);
-    k_plane_sum_finalize2<<<dim3(ceil_div((long)N * C, 4), 2), 256, 0, st>>>(parta, ea, partb, eb, N * C, C, splits, 1.0 / (double)HW);
-    const long t4 = (long)N * HW * C / 4;
-    if (walk_ok(C / 4)) {
-        const int R = 256 / (C / 4);
-        const dim3 gr(imax(1, imin(ceil_div(2048, N), ceil_div(HW, 2 * R))), N);
-        k_inorm_bwd_pair_apply4w<<<gr, 256, 0, st>>>((const float4*)xa, mra, ea, (const float4*)xb, mrb, eb, (const float4*)g, (float4*)gxa,
-                                                      (float4*)gxb, HW, C / 4, ilog2_exact(C / 4));
-    } else
-    k_inorm_bwd_pair_apply4<<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)xa, mra, ea, (const float4*)xb, mrb, eb,
-                                                                  (const float4*)g, (float4*)gxa, (float4*)gxb, t4, HW, C / 4);
+    inorm_bwd_pair_finish(xa, mra, xb, mrb, g, gxa, gxb, w, splits, N, HW, C, st);
     VQW_LAUNCH_CHECK("vqw_res_tail_bwd_pair");
     return VQW_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // BatchNorm statistics (per channel over N*H*W) -> double sums[C][2] so ranks can be summed (SyncBN).
-// sums[c] = sum over `rows` partial rows; one workgroup per channel: 256 threads take the rows round-robin, then a
-// fixed-order tree through LDS -> deterministic (16 row groups per channel walked 128 rows each one load after the other)
-__global__ void __launch_bounds__(256) k_channel_sum_finalize(const double* __restrict__ part, double* __restrict__ sums, int C, int rows) {
+// (mean, rstd) of a channel and its running statistics (unbiased variance): the tail of k_bn_finalize and of the fused form
+struct BnOut {
+    double count;
+    float *mr, *rm, *rv;
+    float momentum, eps;
+};
+__device__ __forceinline__ void bn_tail(int c, double mean, double var, const BnOut& o) {
+    o.mr[2 * c] = (float)mean;
+    o.mr[2 * c + 1] = (float)(1.0 / sqrt(var + (double)o.eps));
+    if (o.rm) {
+        double unb = o.count > 1.0 ? var * (o.count / (o.count - 1.0)) : var;
+        o.rm[c] = (1.f - o.momentum) * o.rm[c] + o.momentum * (float)mean;
+        o.rv[c] = (1.f - o.momentum) * o.rv[c] + o.momentum * (float)unb;
+    }
+}
+// sums[c] = sum over the rows of a partial source (see the finalise kernels above); one workgroup per channel: 256 threads
+// take the rows round-robin, then a fixed-order tree through LDS -> deterministic (16 row groups per channel walked 128 rows
+// each one load after the other).  BN: k_bn_finalize's work in the same launch (no collective between them: one GPU, or
+// SyncBN off), the variance by the source's rule; `sums` is still written (the caller may want it).
+template <class Src, bool BN>
+__global__ void __launch_bounds__(256) k_channel_finalize(Src src, double* __restrict__ sums, int C, BnOut bn) {
     __shared__ double sa[256], sb[256];
     const int c = blockIdx.x, t = threadIdx.x;
     double a = 0.0, b = 0.0;
-    for (int r = t; r < rows; r += 256) {
-        const double* o = part + ((long)r * C + c) * 2;
-        a += o[0];
-        b += o[1];
+    for (int r = t; r < src.rows; r += 256) {
+        double ta, tb;
+        src.get(r, C, c, ta, tb);
+        a += ta;
+        b += tb;
     }
     sa[t] = a;
     sb[t] = b;
@@ -1297,36 +1318,22 @@ __global__ void __launch_bounds__(256) k_channel_sum_finalize(const double* __re
     if (t == 0) {
         sums[2 * c] = sa[0];
         sums[2 * c + 1] = sb[0];
+        if constexpr (BN) {
+            const double mean = sa[0] / bn.count;
+            bn_tail(c, mean, Src::variance(sb[0] / bn.count, mean), bn);
+        }
     }
 }
-
-// the same from the per-tile float partials part[rows][C][2] a convolution's epilogue left (vqw_conv2d_fwd_stats)
-__global__ void __launch_bounds__(256) k_channel_sum_finalize_f(const float* __restrict__ part, double* __restrict__ sums, int C, int rows,
-                                                                double inv_tile) {
-    __shared__ double sa[256], sb[256];
-    const int c = blockIdx.x, t = threadIdx.x;
-    double a = 0.0, b = 0.0;
-    for (int r = t; r < rows; r += 256) {
-        const float* o = part + ((long)r * C + c) * 2;          // (sum, M2 about the tile mean)
-        const double st = (double)o[0];
-        a += st;
-        b += (double)o[1] + st * st * inv_tile;
-    }
-    sa[t] = a;
-    sb[t] = b;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) { sa[t] += sa[t + w]; sb[t] += sb[t + w]; }
-        __syncthreads();
-    }
-    if (t == 0) {
-        sums[2 * c] = sa[0];
-        sums[2 * c + 1] = sb[0];
-    }
+__global__ void k_bn_finalize(const double* __restrict__ sums, BnOut bn, int C) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double mean = sums[2 * c] / bn.count;
+    bn_tail(c, mean, SplitSums::variance(sums[2 * c + 1] / bn.count, mean), bn);
 }
+// sums from the per-tile float partials part[rows][C][2] a convolution's epilogue left (vqw_conv2d_fwd_stats)
 extern "C" int vqw_bn_stats_from_parts(const float* part, double* sums, int rows, int C, double tile_count, void* stream) {
     VQW_CHECK(part && sums && rows > 0 && C > 0 && tile_count >= 1.0, "vqw_bn_stats_from_parts: bad arguments");
-    k_channel_sum_finalize_f<<<C, 256, 0, (hipStream_t)stream>>>(part, sums, C, rows, 1.0 / tile_count);
+    k_channel_finalize<TileMoments, false><<<C, 256, 0, (hipStream_t)stream>>>(TileMoments{part, rows, 1.0 / tile_count}, sums, C, BnOut{});
     VQW_LAUNCH_CHECK("vqw_bn_stats_from_parts");
     return VQW_OK;
 }
@@ -1337,75 +1344,18 @@ extern "C" int vqw_bn_partial_stats(const float* x, double* sums, void* ws, size
     VQW_CHECK(x && sums && ws && N > 0 && HW > 0 && C > 0, "vqw_bn_partial_stats: bad arguments");
     VQW_CHECK(ws_bytes >= vqw_plane_ws_bytes(N, C, HW), "vqw_bn_partial_stats: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    int splits = plane_splits(N, HW);
-    if ((C & 3) == 0 && al16(x)) {
-        FStats4 f{(const float4*)x};
-        splits = launch_plane_reduce4(f, (double*)ws, N, HW, C, st);
-    } else {
-        FStats f{x};
-        k_plane_reduce<<<dim3(splits, N), 256, 0, st>>>(f, (double*)ws, HW, C, splits);
-    }
-    k_channel_sum_finalize<<<C, 256, 0, st>>>((const double*)ws, sums, C, N * splits);
+    const int splits = launch_stats_reduce(x, (double*)ws, N, HW, C, st);
+    k_channel_finalize<SplitSums, false><<<C, 256, 0, st>>>(SplitSums{(const double*)ws, N * splits}, sums, C, BnOut{});
     VQW_LAUNCH_CHECK("vqw_bn_partial_stats");
     return VQW_OK;
 }
 
-__global__ void k_bn_finalize(const double* __restrict__ sums, double count, float* __restrict__ mr, float* __restrict__ rm,
-                              float* __restrict__ rv, float momentum, float eps, int C) {
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double mean = sums[2 * c] / count;
-    double var = var_from_squares(sums[2 * c + 1] / count, mean);
-    mr[2 * c] = (float)mean;
-    mr[2 * c + 1] = (float)(1.0 / sqrt(var + (double)eps));
-    if (rm) {
-        double unb = count > 1.0 ? var * (count / (count - 1.0)) : var;
-        rm[c] = (1.f - momentum) * rm[c] + momentum * (float)mean;
-        rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unb;
-    }
-}
-// k_channel_sum_finalize_f + k_bn_finalize in one launch (no collective between them: one GPU, or SyncBN off): same sums, same
-// arithmetic; `sums` is still written (the caller may want it)
-__global__ void __launch_bounds__(256) k_bn_finalize_parts(const float* __restrict__ part, double* __restrict__ sums, int C, int rows,
-                                                           double inv_tile, double count, float* __restrict__ mr, float* __restrict__ rm,
-                                                           float* __restrict__ rv, float momentum, float eps) {
-    __shared__ double sa[256], sb[256];
-    const int c = blockIdx.x, t = threadIdx.x;
-    double a = 0.0, b = 0.0;
-    for (int r = t; r < rows; r += 256) {
-        const float* o = part + ((long)r * C + c) * 2;
-        const double st = (double)o[0];
-        a += st;
-        b += (double)o[1] + st * st * inv_tile;
-    }
-    sa[t] = a;
-    sb[t] = b;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) { sa[t] += sa[t + w]; sb[t] += sb[t + w]; }
-        __syncthreads();
-    }
-    if (t == 0) {
-        sums[2 * c] = sa[0];
-        sums[2 * c + 1] = sb[0];
-        double mean = sa[0] / count;
-        double var = sb[0] / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        mr[2 * c] = (float)mean;
-        mr[2 * c + 1] = (float)(1.0 / sqrt(var + (double)eps));
-        if (rm) {
-            double unb = count > 1.0 ? var * (count / (count - 1.0)) : var;
-            rm[c] = (1.f - momentum) * rm[c] + momentum * (float)mean;
-            rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unb;
-        }
-    }
-}
 extern "C" int vqw_bn_finalize_parts(const float* part, int rows, double tile_count, double* sums, double count, float* mean_rstd,
                                      float* running_mean, float* running_var, float momentum, float eps, int C, void* stream) {
     VQW_CHECK(part && sums && mean_rstd && rows > 0 && C > 0 && tile_count >= 1.0 && count > 0, "vqw_bn_finalize_parts: bad arguments");
     VQW_CHECK((running_mean == nullptr) == (running_var == nullptr), "vqw_bn_finalize_parts: running stats must both be set or both NULL");
-    k_bn_finalize_parts<<<C, 256, 0, (hipStream_t)stream>>>(part, sums, C, rows, 1.0 / tile_count, count, mean_rstd, running_mean, running_var,
-                                                            momentum, eps);
+    k_channel_finalize<TileMoments, true><<<C, 256, 0, (hipStream_t)stream>>>(TileMoments{part, rows, 1.0 / tile_count}, sums, C,
+                                                                              BnOut{count, mean_rstd, running_mean, running_var, momentum, eps});
     VQW_LAUNCH_CHECK("vqw_bn_finalize_parts");
     return VQW_OK;
 }
@@ -1413,8 +1363,7 @@ extern "C" int vqw_bn_finalize(const double* sums, double count, float* mean_rst
                                float* running_var, float momentum, float eps, int C, void* stream) {
     VQW_CHECK(sums && mean_rstd && count > 0 && C > 0, "vqw_bn_finalize: bad arguments");
     VQW_CHECK((running_mean == nullptr) == (running_var == nullptr), "vqw_bn_finalize: running stats must both be set or both NULL");
-    k_bn_finalize<<<ceil_div(C, 256), 256, 0, (hipStream_t)stream>>>(sums, count, mean_rstd, running_mean, running_var,
-                                                                     momentum, eps, C);
+    k_bn_finalize<<<ceil_div(C, 256), 256, 0, (hipStream_t)stream>>>(sums, BnOut{count, mean_rstd, running_mean, running_var, momentum, eps}, C);
     VQW_LAUNCH_CHECK("vqw_bn_finalize");
     return VQW_OK;
 }
@@ -1432,6 +1381,8 @@ extern "C" int vqw_bn_eval_stats(const float* running_mean, const float* running
     return VQW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// StyledDenorm (SPADE) maps on the scalar and flat float4 tiers (the walks are above)
 template <int RELU>
 __global__ void k_spade_fwd(const float* __restrict__ x, const float* __restrict__ mr, const float* __restrict__ gamma,
                             const float* __restrict__ beta, float* __restrict__ y, long total, int C, int gbs) {
@@ -1439,8 +1390,7 @@ __global__ void k_spade_fwd(const float* __restrict__ x, const float* __restrict
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         int c = (int)(i % C);
         long j = (i / C) * gbs + c;
-        float xh = (x[i] - mr[2 * c]) * mr[2 * c + 1];
-        float v = xh * (1.f + gamma[j]) + beta[j];
+        float v = spade_out(norm_xhat(x[i], mr[2 * c], mr[2 * c + 1]), gamma[j], beta[j]);
         y[i] = RELU ? fmaxf(v, 0.f) : v;
     }
 }
@@ -1454,18 +1404,42 @@ __global__ void __launch_bounds__(256) k_spade_fwd4(const float4* __restrict__ x
         int c4 = (int)(i % C4);
         long j = (i / C4) * gbs4 + c4;
         const float4* m = (const float4*)(mr + 8 * c4);
-        float4 m0 = m[0], m1 = m[1], v = x[i], ga = gamma[j], be = beta[j], o;
-        o.x = (v.x - m0.x) * m0.y * (1.f + ga.x) + be.x;
-        o.y = (v.y - m0.z) * m0.w * (1.f + ga.y) + be.y;
-        o.z = (v.z - m1.x) * m1.y * (1.f + ga.z) + be.z;
-        o.w = (v.w - m1.z) * m1.w * (1.f + ga.w) + be.w;
-        if (RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+        const float4 m0 = m[0], m1 = m[1], v = x[i], ga = gamma[j], be = beta[j];
+        float4 o = spade4(v, ga, be, m0, m1, RELU);
         if (res) {      // residual added AFTER the activation (StyledResUpBlock: shortcut + main path, blocks.py:134)
             const float4 r = res[i];
             o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
         }
         y[i] = o;
     }
+}
+// RES 0: plain; 1: + res; 2: + InstanceNorm(+ReLU)(res) from its statistics rmr (HW = 2^lgHW pixels per image).  The residual forms
+// exist on the float4 tiers only, RES 2 on the walk only: asked for anything else, nothing is launched and the call fails.
+struct SpadeRes {
+    const float* res;
+    const float* rmr;
+    int lgHW, rrelu;
+};
+template <int RES>
+static int launch_spade_fwd(Tier tier, const float* x, const float* mr, const float* gamma, const float* beta, int gbs, float* y, long P,
+                            int C, int relu, SpadeRes r, hipStream_t st) {
+    if ((RES == 2 && tier != TIER_WALK4) || (RES == 1 && tier == TIER_SCALAR)) {
+        vqw_set_error("spade forward: no kernel with residual form %d on tier %d", RES, (int)tier);
+        return VQW_ERR_ARG;
+    }
+    const int C4 = C / 4;
+    const long total = P * C;
+    const float4 *x4 = (const float4*)x, *ga4 = (const float4*)gamma, *be4 = (const float4*)beta;
+    with_flag(relu, [&](auto R) {
+        constexpr int RELU = decltype(R)::value;
+        if (tier == TIER_WALK4)
+            k_spade_fwd4w<RELU, RES><<<walk_blocks_flat(P, C4, 4), 256, 0, st>>>(x4, mr, ga4, be4, (float4*)y, P, C4, ilog2_exact(C4), gbs / 4,
+                                                                                  (const float4*)r.res, r.rmr, r.lgHW, r.rrelu);
+        else if (tier == TIER_FLAT4)
+            k_spade_fwd4<RELU><<<stream_grid(total / 4, 256), 256, 0, st>>>(x4, mr, ga4, be4, (float4*)y, total / 4, C4, gbs / 4, (const float4*)r.res);
+        else k_spade_fwd<RELU><<<stream_grid(total, 256), 256, 0, st>>>(x, mr, gamma, beta, y, total, C, gbs);
+    });
+    return VQW_OK;
 }
 // y = act(spade(x)) + res: the block's final `shortcut + main` (blocks.py:134) inside the last modulation kernel
 extern "C" int vqw_spade_fwd_res(const float* x, const float* mean_rstd, const float* gamma, const float* beta, int gb_stride,
@@ -1474,15 +1448,9 @@ extern "C" int vqw_spade_fwd_res(const float* x, const float* mean_rstd, const f
     VQW_CHECK(x && mean_rstd && gamma && beta && res && y && P > 0 && C > 0 && gb_stride >= C, "vqw_spade_fwd_res: bad arguments");
     VQW_CHECK((C & 3) == 0 && (gb_stride & 3) == 0 && al16(x) && al16(gamma) && al16(beta) && al16(y) && al16(mean_rstd) && al16(res),
               "vqw_spade_fwd_res: needs C %% 4 == 0 and 16-byte aligned tensors");
-    const long t4 = P * C / 4;
-    hipStream_t st = (hipStream_t)stream;
-    if (walk_ok(C / 4)) {
-        const int C4 = C / 4, gr = walk_blocks_flat(P, C4, 4);
-        if (relu) k_spade_fwd4w<1, 1><<<gr, 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, P, C4, ilog2_exact(C4), gb_stride / 4, (const float4*)res);
-        else k_spade_fwd4w<0, 1><<<gr, 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, P, C4, ilog2_exact(C4), gb_stride / 4, (const float4*)res);
-    } else
-    if (relu) k_spade_fwd4<1><<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, t4, C / 4, gb_stride / 4, (const float4*)res);
-    else k_spade_fwd4<0><<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, t4, C / 4, gb_stride / 4, (const float4*)res);
+    const int rc = launch_spade_fwd<1>(walk_ok(C / 4) ? TIER_WALK4 : TIER_FLAT4, x, mean_rstd, gamma, beta, gb_stride, y, P, C, relu,
+                                       SpadeRes{res, nullptr, 0, 0}, (hipStream_t)stream);
+    if (rc != VQW_OK) return rc;
     VQW_LAUNCH_CHECK("vqw_spade_fwd_res");
     return VQW_OK;
 }
@@ -1500,13 +1468,11 @@ extern "C" int vqw_spade_fwd_res_norm(const float* x, const float* mean_rstd, co
     VQW_CHECK(vqw_spade_fwd_res_norm_supported(HW, C) && (gb_stride & 3) == 0 && al16(x) && al16(gamma) && al16(beta) && al16(y) &&
                   al16(mean_rstd) && al16(res_raw) && al16(res_mean_rstd),
               "vqw_spade_fwd_res_norm: shape not served (query vqw_spade_fwd_res_norm_supported) or unaligned tensors");
-    const long P = (long)N * HW;
     int lg = 0;
     while ((1L << lg) < HW) ++lg;
-    const int C4 = C / 4, gr = walk_blocks_flat(P, C4, 4);
-    hipStream_t st = (hipStream_t)stream;
-    if (relu) k_spade_fwd4w<1, 2><<<gr, 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, P, C4, ilog2_exact(C4), gb_stride / 4, (const float4*)res_raw, res_mean_rstd, lg, res_relu);
-    else k_spade_fwd4w<0, 2><<<gr, 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, P, C4, ilog2_exact(C4), gb_stride / 4, (const float4*)res_raw, res_mean_rstd, lg, res_relu);
+    const int rc = launch_spade_fwd<2>(TIER_WALK4, x, mean_rstd, gamma, beta, gb_stride, y, (long)N * HW, C, relu,
+                                       SpadeRes{res_raw, res_mean_rstd, lg, res_relu}, (hipStream_t)stream);
+    if (rc != VQW_OK) return rc;
     VQW_LAUNCH_CHECK("vqw_spade_fwd_res_norm");
     return VQW_OK;
 }
@@ -1514,51 +1480,14 @@ extern "C" int vqw_spade_fwd(const float* x, const float* mean_rstd, const float
                              float* y, long P, int C, int relu, void* stream) {
     VQW_PROF_HBM(stream, 4, (double)P * C);
     VQW_CHECK(x && mean_rstd && gamma && beta && y && P > 0 && C > 0 && gb_stride >= C, "vqw_spade_fwd: bad arguments");
-    long total = P * C;
-    hipStream_t st = (hipStream_t)stream;
-    if ((C & 3) == 0 && (gb_stride & 3) == 0 && al16(x) && al16(gamma) && al16(beta) && al16(y) && al16(mean_rstd)) {
-        long t4 = total / 4;
-        if (walk_ok(C / 4)) {
-            const int C4 = C / 4, gr = walk_blocks_flat(P, C4, 4);
-            if (relu) k_spade_fwd4w<1, 0><<<gr, 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, P, C4, ilog2_exact(C4), gb_stride / 4, nullptr);
-            else k_spade_fwd4w<0, 0><<<gr, 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, P, C4, ilog2_exact(C4), gb_stride / 4, nullptr);
-        } else
-        if (relu) k_spade_fwd4<1><<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, t4, C / 4, gb_stride / 4);
-        else k_spade_fwd4<0><<<stream_grid(t4, 256), 256, 0, st>>>((const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (float4*)y, t4, C / 4, gb_stride / 4);
-    } else if (relu) k_spade_fwd<1><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, gamma, beta, y, total, C, gb_stride);
-    else k_spade_fwd<0><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, gamma, beta, y, total, C, gb_stride);
+    const int rc = launch_spade_fwd<0>(pick_tier(C, gb_stride, x, gamma, beta, y, mean_rstd), x, mean_rstd, gamma, beta, gb_stride, y, P, C, relu,
+                                       SpadeRes{}, (hipStream_t)stream);
+    if (rc != VQW_OK) return rc;
     VQW_LAUNCH_CHECK("vqw_spade_fwd");
     return VQW_OK;
 }
 
-// backward phase 1: g = gy * [out>0]; dgamma = g*xhat; dbeta = g; dxhat = g*(1+gamma);
-// per-channel sums of (dxhat, dxhat*xhat).  dgamma/dbeta are written as a side effect of the reduction.
-template <int RELU>
-struct FSpadeBwd {
-    const float* x;
-    const float* mr;
-    const float* gamma;
-    const float* beta;
-    const float* gy;
-    float* dgamma;
-    float* dbeta;
-    int C, gbs;
-    __device__ void operator()(long i, int, int c, float& a, float& b) const {
-        const long j = (i / C) * gbs + c;
-        float xh = (x[i] - mr[2 * c]) * mr[2 * c + 1];
-        float ga = 1.f + gamma[j];
-        float g = gy[i];
-        if (RELU) {
-            float out = xh * ga + beta[j];
-            if (!(out > 0.f)) g = 0.f;
-        }
-        dgamma[j] = g * xh;
-        dbeta[j] = g;
-        float dxh = g * ga;
-        a = dxh;
-        b = dxh * xh;
-    }
-};
+// backward phase 1: per-channel sums of (dxhat, dxhat * xhat); dgamma / dbeta are written as a side effect of the reduction
 extern "C" int vqw_spade_bwd_reduce(const float* x, const float* mean_rstd, const float* gamma, const float* beta,
                                     const float* gy, float* dgamma, float* dbeta, int gb_stride, double* sums, void* ws,
                                     size_t ws_bytes, int N, int HW, int C, int relu, void* stream) {
@@ -1567,26 +1496,20 @@ extern "C" int vqw_spade_bwd_reduce(const float* x, const float* mean_rstd, cons
                   gb_stride >= C, "vqw_spade_bwd_reduce: bad arguments");
     VQW_CHECK(ws_bytes >= vqw_plane_ws_bytes(N, C, HW), "vqw_spade_bwd_reduce: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    int splits = plane_splits(N, HW);
-    const bool vec = (C & 3) == 0 && (gb_stride & 3) == 0 && al16(x) && al16(gamma) && al16(beta) && al16(gy) && al16(dgamma) && al16(dbeta) && al16(mean_rstd);
-    if (vec && relu) {
-        FSpadeBwd4<1> f{(const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (const float4*)gy, (float4*)dgamma, (float4*)dbeta, C / 4, gb_stride / 4};
-        splits = launch_plane_reduce4(f, (double*)ws, N, HW, C, st);
-    } else if (vec) {
-        FSpadeBwd4<0> f{(const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (const float4*)gy, (float4*)dgamma, (float4*)dbeta, C / 4, gb_stride / 4};
-        splits = launch_plane_reduce4(f, (double*)ws, N, HW, C, st);
-    } else if (relu) {
-        FSpadeBwd<1> f{x, mean_rstd, gamma, beta, gy, dgamma, dbeta, C, gb_stride};
-        k_plane_reduce<<<dim3(splits, N), 256, 0, st>>>(f, (double*)ws, HW, C, splits);
-    } else {
-        FSpadeBwd<0> f{x, mean_rstd, gamma, beta, gy, dgamma, dbeta, C, gb_stride};
-        k_plane_reduce<<<dim3(splits, N), 256, 0, st>>>(f, (double*)ws, HW, C, splits);
-    }
-    k_channel_sum_finalize<<<C, 256, 0, st>>>((const double*)ws, sums, C, N * splits);
+    int splits = 0;
+    with_flag(relu, [&](auto R) {
+        constexpr int RELU = decltype(R)::value;
+        if (pick_tier(C, gb_stride, x, gamma, beta, gy, dgamma, dbeta, mean_rstd) != TIER_SCALAR)
+            splits = launch_plane_reduce4(FSpadeBwd4<RELU>{(const float4*)x, mean_rstd, (const float4*)gamma, (const float4*)beta, (const float4*)gy,
+                                                           (float4*)dgamma, (float4*)dbeta, C / 4, gb_stride / 4}, (double*)ws, N, HW, C, st);
+        else splits = launch_plane_reduce(FSpadeBwd<RELU>{x, mean_rstd, gamma, beta, gy, dgamma, dbeta, C, gb_stride}, (double*)ws, N, HW, C, st);
+    });
+    k_channel_finalize<SplitSums, false><<<C, 256, 0, st>>>(SplitSums{(const double*)ws, N * splits}, sums, C, BnOut{});
     VQW_LAUNCH_CHECK("vqw_spade_bwd_reduce");
     return VQW_OK;
 }
 
+// backward phase 2
 template <int RELU, int TRAIN>
 __global__ void k_spade_bwd_apply(const float* __restrict__ x, const float* __restrict__ mr, const float* __restrict__ gamma,
                                   const float* __restrict__ beta, const float* __restrict__ gy, const double* __restrict__ sums,
@@ -1596,24 +1519,14 @@ __global__ void k_spade_bwd_apply(const float* __restrict__ x, const float* __re
         int c = (int)(i % C);
         long j = (i / C) * gbs + c;
         float r = mr[2 * c + 1];
-        float xh = (x[i] - mr[2 * c]) * r;
-        float ga = 1.f + gamma[j];
-        float g = gy[i];
-        if (RELU) {
-            float out = xh * ga + beta[j];
-            if (!(out > 0.f)) g = 0.f;
-        }
-        float dxh = g * ga;
-        if (TRAIN) {
-            float m1 = (float)(sums[2 * c] * inv_count);
-            float m2 = (float)(sums[2 * c + 1] * inv_count);
-            gx[i] = r * (dxh - m1 - xh * m2);
-        } else {
-            gx[i] = r * dxh;
-        }
+        float xh = norm_xhat(x[i], mr[2 * c], r);
+        float dg, db, dxh;
+        spade_bwd_grad(gy[i], xh, gamma[j], RELU ? beta[j] : 0.f, RELU, dg, db, dxh);
+        float s1 = TRAIN ? (float)(sums[2 * c] * inv_count) : 0.f;
+        float s2 = TRAIN ? (float)(sums[2 * c + 1] * inv_count) : 0.f;
+        gx[i] = spade_bwd_out(dxh, xh, r, s1, s2, TRAIN);
     }
 }
-// float4 form: same per-element arithmetic, four channels per lane
 template <int RELU, int TRAIN>
 __global__ void __launch_bounds__(256) k_spade_bwd_apply4(const float4* __restrict__ x, const float* __restrict__ mr,
                                                           const float4* __restrict__ gamma, const float4* __restrict__ beta,
@@ -1624,31 +1537,11 @@ __global__ void __launch_bounds__(256) k_spade_bwd_apply4(const float4* __restri
         int c4 = (int)(i % C4);
         long j = (i / C4) * gbs4 + c4;
         const float4* m = (const float4*)(mr + 8 * c4);
-        float4 m0 = m[0], m1 = m[1], v = x[i], ga4 = gamma[j], g4 = gy[i], be4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (RELU) be4 = beta[j];
-        float mean[4] = {m0.x, m0.z, m1.x, m1.z}, rs[4] = {m0.y, m0.w, m1.y, m1.w};
-        float xv[4] = {v.x, v.y, v.z, v.w}, gav[4] = {ga4.x, ga4.y, ga4.z, ga4.w}, gv[4] = {g4.x, g4.y, g4.z, g4.w};
-        float bev[4] = {be4.x, be4.y, be4.z, be4.w}, o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float r = rs[k];
-            float xh = (xv[k] - mean[k]) * r;
-            float ga = 1.f + gav[k];
-            float g = gv[k];
-            if (RELU) {
-                float out = xh * ga + bev[k];
-                if (!(out > 0.f)) g = 0.f;
-            }
-            float dxh = g * ga;
-            if (TRAIN) {
-                float s1 = (float)(sums[2 * (4 * c4 + k)] * inv_count);
-                float s2 = (float)(sums[2 * (4 * c4 + k) + 1] * inv_count);
-                o[k] = r * (dxh - s1 - xh * s2);
-            } else {
-                o[k] = r * dxh;
-            }
-        }
-        gx[i] = make_float4(o[0], o[1], o[2], o[3]);
+        const float4 m0 = m[0], m1 = m[1], v = x[i], ga = gamma[j], g = gy[i];
+        const float4 be = RELU ? beta[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+        float s1[4], s2[4];
+        spade_bwd_means4(sums, inv_count, c4, TRAIN, s1, s2);
+        gx[i] = spade_bwd4(v, g, ga, be, m0, m1, s1, s2, RELU, TRAIN);
     }
 }
 extern "C" int vqw_spade_bwd_apply(const float* x, const float* mean_rstd, const float* gamma, const float* beta, int gb_stride,
@@ -1657,31 +1550,22 @@ extern "C" int vqw_spade_bwd_apply(const float* x, const float* mean_rstd, const
     VQW_PROF_HBM(stream, 4, (double)P * C);
     VQW_CHECK(x && mean_rstd && gamma && beta && gy && gx && P > 0 && C > 0 && gb_stride >= C, "vqw_spade_bwd_apply: bad arguments");
     VQW_CHECK(!training || (sums && count > 0), "vqw_spade_bwd_apply: training needs sums and count");
-    long total = P * C;
+    const long total = P * C;
     hipStream_t st = (hipStream_t)stream;
-    double ic = training ? 1.0 / count : 0.0;
-    if ((C & 3) == 0 && (gb_stride & 3) == 0 && al16(x) && al16(gamma) && al16(beta) && al16(gy) && al16(gx) && al16(mean_rstd)) {
-        long t4 = total / 4;
-        int g = stream_grid(t4, 256), C4 = C / 4, s4 = gb_stride / 4;
-        const float4 *x4 = (const float4*)x, *ga4 = (const float4*)gamma, *be4 = (const float4*)beta, *gy4 = (const float4*)gy;
-        if (walk_ok(C4)) {
-            const int gw = walk_blocks_flat(P, C4, 2), lg = ilog2_exact(C4);
-            if (relu && training) k_spade_bwd_apply4w<1, 1><<<gw, 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, P, C4, lg, s4);
-            else if (relu) k_spade_bwd_apply4w<1, 0><<<gw, 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, P, C4, lg, s4);
-            else if (training) k_spade_bwd_apply4w<0, 1><<<gw, 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, P, C4, lg, s4);
-            else k_spade_bwd_apply4w<0, 0><<<gw, 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, P, C4, lg, s4);
-        } else
-        if (relu && training) k_spade_bwd_apply4<1, 1><<<g, 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, t4, C4, s4);
-        else if (relu) k_spade_bwd_apply4<1, 0><<<g, 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, t4, C4, s4);
-        else if (training) k_spade_bwd_apply4<0, 1><<<g, 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, t4, C4, s4);
-        else k_spade_bwd_apply4<0, 0><<<g, 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, t4, C4, s4);
-    } else {
-        int g = stream_grid(total, 256);
-        if (relu && training) k_spade_bwd_apply<1, 1><<<g, 256, 0, st>>>(x, mean_rstd, gamma, beta, gy, sums, ic, gx, total, C, gb_stride);
-        else if (relu) k_spade_bwd_apply<1, 0><<<g, 256, 0, st>>>(x, mean_rstd, gamma, beta, gy, sums, ic, gx, total, C, gb_stride);
-        else if (training) k_spade_bwd_apply<0, 1><<<g, 256, 0, st>>>(x, mean_rstd, gamma, beta, gy, sums, ic, gx, total, C, gb_stride);
-        else k_spade_bwd_apply<0, 0><<<g, 256, 0, st>>>(x, mean_rstd, gamma, beta, gy, sums, ic, gx, total, C, gb_stride);
-    }
+    const double ic = training ? 1.0 / count : 0.0;
+    const Tier tier = pick_tier(C, gb_stride, x, gamma, beta, gy, gx, mean_rstd);
+    const int C4 = C / 4, s4 = gb_stride / 4;
+    const float4 *x4 = (const float4*)x, *ga4 = (const float4*)gamma, *be4 = (const float4*)beta, *gy4 = (const float4*)gy;
+    with_flag(relu, [&](auto R) {
+        with_flag(training, [&](auto T) {
+            constexpr int RELU = decltype(R)::value, TRAIN = decltype(T)::value;
+            if (tier == TIER_WALK4)
+                k_spade_bwd_apply4w<RELU, TRAIN><<<walk_blocks_flat(P, C4, 2), 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, P, C4, ilog2_exact(C4), s4);
+            else if (tier == TIER_FLAT4)
+                k_spade_bwd_apply4<RELU, TRAIN><<<stream_grid(total / 4, 256), 256, 0, st>>>(x4, mean_rstd, ga4, be4, gy4, sums, ic, (float4*)gx, total / 4, C4, s4);
+            else k_spade_bwd_apply<RELU, TRAIN><<<stream_grid(total, 256), 256, 0, st>>>(x, mean_rstd, gamma, beta, gy, sums, ic, gx, total, C, gb_stride);
+        });
+    });
     VQW_LAUNCH_CHECK("vqw_spade_bwd_apply");
     return VQW_OK;
 }
@@ -1730,10 +1614,8 @@ extern "C" int vqw_bn_affine_bwd_reduce(const float* x, const float* mean_rstd, 
     VQW_CHECK(x && mean_rstd && gamma && beta && gy && sums && ws && N > 0 && HW > 0 && C > 0, "vqw_bn_affine_bwd_reduce: bad arguments");
     VQW_CHECK(ws_bytes >= vqw_plane_ws_bytes(N, C, HW), "vqw_bn_affine_bwd_reduce: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    int splits = plane_splits(N, HW);
-    FBnAffineBwd f{x, mean_rstd, gamma, beta, gy, slope};
-    k_plane_reduce<<<dim3(splits, N), 256, 0, st>>>(f, (double*)ws, HW, C, splits);
-    k_channel_sum_finalize<<<C, 256, 0, st>>>((const double*)ws, sums, C, N * splits);
+    const int splits = launch_plane_reduce(FBnAffineBwd{x, mean_rstd, gamma, beta, gy, slope}, (double*)ws, N, HW, C, st);
+    k_channel_finalize<SplitSums, false><<<C, 256, 0, st>>>(SplitSums{(const double*)ws, N * splits}, sums, C, BnOut{});
     VQW_LAUNCH_CHECK("vqw_bn_affine_bwd_reduce");
     return VQW_OK;
 }

@@ -72,6 +72,43 @@ def _ws(nbytes, like):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=like.device)
 
 
+def _mean_rstd(x, part, eps):
+    """(mean, rstd) per (image, channel) of the NHWC tensor x, [N * C * 2] floats: from the statistics partials `part` that the
+    convolution which produced x left in its epilogue when given, else by a reduction pass over x."""
+    N, C, H, W = x.shape
+    L = _L()
+    mr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
+    if part is not None:
+        L.vqw_inorm_stats_parts(part, part.numel() // (N * C * 2), mr, N, H * W, C, eps)
+    else:
+        ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
+        L.vqw_inorm_stats(x, mr, ws, ws.numel(), N, H * W, C, eps)
+    return mr
+
+
+def _inorm_fwd(x, y, y_cstride, y_coff, part, eps, relu):
+    """InstanceNorm(+ReLU) of x into the channels [y_coff, y_coff + C) of y (statistics as in _mean_rstd); returns (mean, rstd)."""
+    N, C, H, W = x.shape
+    L = _L()
+    mr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
+    if part is not None:
+        L.vqw_inorm_fwd_parts(x, y, y_cstride, y_coff, mr, part, part.numel() // (N * C * 2), N, H * W, C, eps, int(relu))
+    else:
+        ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
+        L.vqw_inorm_fwd(x, y, y_cstride, y_coff, mr, ws, ws.numel(), N, H * W, C, eps, int(relu))
+    return mr
+
+
+def _inorm_bwd(x, mr, gy, relu, gy_cstride=None, gy_coff=0):
+    """Gradient of InstanceNorm(+ReLU) at its raw input x; gy_cstride / gy_coff: where x's channels sit in a wider gy."""
+    N, C, H, W = x.shape
+    L = _L()
+    gx = torch.empty_like(x, memory_format=CL)
+    ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
+    L.vqw_inorm_bwd(x, mr, gy, C if gy_cstride is None else gy_cstride, gy_coff, gx, ws, ws.numel(), N, H * W, C, int(relu))
+    return gx
+
+
 def _flat(t):
     if t.dtype != torch.float32:
         raise RuntimeError("expected fp32")
@@ -1118,16 +1155,8 @@ class _InstanceNorm(torch.autograd.Function):
     def forward(ctx, x, relu, eps, part=None):
         _dev(x)
         x = nhwc(x)
-        N, C, H, W = x.shape
-        L = _L()
         y = torch.empty_like(x, memory_format=CL)
-        mr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
-        if part is not None:        # statistics left by the producing convolution's epilogue
-            nparts = part.numel() // (N * C * 2)
-            L.vqw_inorm_fwd_parts(x, y, C, 0, mr, part, nparts, N, H * W, C, eps, int(relu))
-        else:
-            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            L.vqw_inorm_fwd(x, y, C, 0, mr, ws, ws.numel(), N, H * W, C, eps, int(relu))
+        mr = _inorm_fwd(x, y, x.shape[1], 0, part, eps, relu)
         ctx.save_for_backward(x, mr)
         ctx.relu = relu
         ctx.mark_non_differentiable(mr)
@@ -1143,18 +1172,16 @@ class _InstanceNorm(torch.autograd.Function):
         L = _L()
         ent = _IN_BWD_PARTS.take(gy)
         gy = nhwc(gy)
-        gx = torch.empty_like(x, memory_format=CL)
         if ent is not None and ent[2] == x.data_ptr():
             # the only consumer's input-gradient launch has left (sum gm, sum gm * xhat) per region: no reduction pass
             global in_bwd_fused_calls
             in_bwd_fused_calls += 1
             bpart, nparts, _ = ent
+            gx = torch.empty_like(x, memory_format=CL)
             means = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
             L.vqw_inorm_bwd_parts(x, mr, gy, bpart, nparts, means, gx, N, H * W, C, int(ctx.relu))
             return gx, None, None, None
-        ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-        L.vqw_inorm_bwd(x, mr, gy, C, 0, gx, ws, ws.numel(), N, H * W, C, int(ctx.relu))
-        return gx, None, None, None
+        return _inorm_bwd(x, mr, gy, ctx.relu), None, None, None
 
 
 def instance_norm(x, relu=False, eps=1e-5, part=None):
@@ -1177,22 +1204,14 @@ class _InstanceNormCat(torch.autograd.Function):
         xs = [nhwc(x) for x in xs]
         N, _, H, W = xs[0].shape
         Ct = sum(x.shape[1] for x in xs)
-        L = _L()
         y = empty_nhwc(N, Ct, H, W, xs[0])
         mrs, off = [], 0
         for x in xs:
-            C = x.shape[1]
             if x.shape[0] != N or x.shape[2] != H or x.shape[3] != W:
                 raise RuntimeError("instance_norm_cat: shape mismatch")
-            mr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
             part = parts[len(mrs)] if parts is not None else None
-            if part is not None:        # statistics left by the producing convolution's epilogue
-                L.vqw_inorm_fwd_parts(x, y, Ct, off, mr, part, part.numel() // (N * C * 2), N, H * W, C, eps, int(relu))
-            else:
-                ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-                L.vqw_inorm_fwd(x, y, Ct, off, mr, ws, ws.numel(), N, H * W, C, eps, int(relu))
-            mrs.append(mr)
-            off += C
+            mrs.append(_inorm_fwd(x, y, Ct, off, part, eps, relu))
+            off += x.shape[1]
         ctx.save_for_backward(*xs, *mrs)
         ctx.relu, ctx.n = relu, len(xs)
         return y
@@ -1202,16 +1221,11 @@ class _InstanceNormCat(torch.autograd.Function):
         saved = ctx.saved_tensors
         xs, mrs = saved[:ctx.n], saved[ctx.n:]
         gy = nhwc(gy)
-        N, Ct, H, W = gy.shape
-        L = _L()
+        Ct = gy.shape[1]
         outs, off = [], 0
         for x, mr in zip(xs, mrs):
-            C = x.shape[1]
-            gx = torch.empty_like(x, memory_format=CL)
-            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            L.vqw_inorm_bwd(x, mr, gy, Ct, off, gx, ws, ws.numel(), N, H * W, C, int(ctx.relu))
-            outs.append(gx)
-            off += C
+            outs.append(_inorm_bwd(x, mr, gy, ctx.relu, Ct, off))
+            off += x.shape[1]
         return (None, None, None, *outs)
 
 
@@ -1306,12 +1320,7 @@ class _Spade(torch.autograd.Function):
                 raise RuntimeError("spade_norm: residual shape %s does not match %s" % (tuple(res.shape), tuple(x.shape)))
         if res is not None and res_norm is not None:
             rpart, rrelu, reps = res_norm
-            rmr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
-            if rpart is not None:
-                L.vqw_inorm_stats_parts(rpart, rpart.numel() // (N * C * 2), rmr, N, H * W, C, reps)
-            else:
-                ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), res)
-                L.vqw_inorm_stats(res, rmr, ws, ws.numel(), N, H * W, C, reps)
+            rmr = _mean_rstd(res, rpart, reps)
             L.vqw_spade_fwd_res_norm(x, mr, gptr, bptr, gbs, res, rmr, int(rrelu), y, N, H * W, C, int(relu))
             ctx.res_relu = bool(rrelu)
         elif res is not None:
@@ -1348,9 +1357,7 @@ class _Spade(torch.autograd.Function):
         gres = gy if ctx.has_res else None
         if rmr is not None and ctx.needs_input_grad[11]:
             # the residual was normalised in the forward kernel: its gradient goes back through that InstanceNorm(+ReLU) here
-            gres = torch.empty_like(res_raw, memory_format=CL)
-            ws2 = _ws(L.vqw_plane_ws_bytes(N, C, H * W), res_raw)
-            L.vqw_inorm_bwd(res_raw, rmr, gy, C, 0, gres, ws2, ws2.numel(), N, H * W, C, int(ctx.res_relu))
+            gres = _inorm_bwd(res_raw, rmr, gy, ctx.res_relu)
         return gx, dgamma, dbeta, None, None, None, None, None, None, None, None, gres, None, None
 
 
@@ -1428,12 +1435,7 @@ class _AddNorm(torch.autograd.Function):
             raise RuntimeError("add_norm: shape mismatch %s vs %s" % (tuple(a.shape), tuple(x.shape)))
         N, C, H, W = x.shape
         L = _L()
-        mr = torch.empty(N * C * 2, dtype=torch.float32, device=x.device)
-        if part is not None:
-            L.vqw_inorm_stats_parts(part, part.numel() // (N * C * 2), mr, N, H * W, C, eps)
-        else:
-            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            L.vqw_inorm_stats(x, mr, ws, ws.numel(), N, H * W, C, eps)
+        mr = _mean_rstd(x, part, eps)
         y = torch.empty_like(x, memory_format=CL)
         L.vqw_inorm_add_fwd(x, mr, a, y, N, H * W, C, int(relu))
         ctx.save_for_backward(x, mr)
@@ -1443,14 +1445,8 @@ class _AddNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, mr = ctx.saved_tensors
-        N, C, H, W = x.shape
-        L = _L()
         gy = nhwc(gy)
-        gx = None
-        if ctx.needs_input_grad[1]:
-            gx = torch.empty_like(x, memory_format=CL)
-            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            L.vqw_inorm_bwd(x, mr, gy, C, 0, gx, ws, ws.numel(), N, H * W, C, int(ctx.relu))
+        gx = _inorm_bwd(x, mr, gy, ctx.relu) if ctx.needs_input_grad[1] else None
         ga = gy
         if ctx.a_group is not None:
             ga = ctx.a_group.member_done(gy)
@@ -1547,23 +1543,14 @@ class _ResTailNorm(torch.autograd.Function):
             raise RuntimeError("res_tail_norm: shape mismatch %s vs %s" % (tuple(x2.shape), tuple(xid.shape)))
         N, C, H, W = x2.shape
         L = _L()
-        mr2 = torch.empty(N * C * 2, dtype=torch.float32, device=x2.device)
-        mrid = torch.empty(N * C * 2, dtype=torch.float32, device=x2.device)
         if part2 is not None and partid is not None:      # both norms' statistics from their convolutions' partials: one launch
+            mr2 = torch.empty(N * C * 2, dtype=torch.float32, device=x2.device)
+            mrid = torch.empty(N * C * 2, dtype=torch.float32, device=x2.device)
             L.vqw_inorm_stats_parts2(part2, part2.numel() // (N * C * 2), mr2, partid,
                                      partid.numel() // (N * C * 2), mrid, N, H * W, C, eps)
-        elif part2 is not None:
-            L.vqw_inorm_stats_parts(part2, part2.numel() // (N * C * 2), mr2, N, H * W, C, eps)
         else:
-            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x2)
-            L.vqw_inorm_stats(x2, mr2, ws, ws.numel(), N, H * W, C, eps)
-        if part2 is not None and partid is not None:
-            pass
-        elif partid is not None:
-            L.vqw_inorm_stats_parts(partid, partid.numel() // (N * C * 2), mrid, N, H * W, C, eps)
-        else:
-            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), xid)
-            L.vqw_inorm_stats(xid, mrid, ws, ws.numel(), N, H * W, C, eps)
+            mr2 = _mean_rstd(x2, part2, eps)
+            mrid = _mean_rstd(xid, partid, eps)
         out = torch.empty_like(x2, memory_format=CL)
         pooled = empty_nhwc(N, C, H // 2, W // 2, x2)
         L.vqw_res_tail_norm_fwd(x2, mr2, xid, mrid, out, pooled, N, H, W, C)
@@ -1598,13 +1585,9 @@ class _ResTailNorm(torch.autograd.Function):
             L.vqw_inorm_bwd_pair(x2, mr2, xid, mrid, g, gx2, gxid, ws, ws.numel(), N, H * W, C)
             return gx2, gxid, None, None, None
         if ctx.needs_input_grad[0]:
-            gx2 = torch.empty_like(x2, memory_format=CL)
-            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x2)
-            L.vqw_inorm_bwd(x2, mr2, g, C, 0, gx2, ws, ws.numel(), N, H * W, C, 1)
+            gx2 = _inorm_bwd(x2, mr2, g, True)
         if ctx.needs_input_grad[1]:
-            gxid = torch.empty_like(xid, memory_format=CL)
-            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), xid)
-            L.vqw_inorm_bwd(xid, mrid, g, C, 0, gxid, ws, ws.numel(), N, H * W, C, 0)
+            gxid = _inorm_bwd(xid, mrid, g, False)
         return gx2, gxid, None, None, None
 
 

@@ -204,7 +204,7 @@ def test_instance_norm_misaligned_input():
 @pytest.mark.parametrize("relu", [False, True], ids=["norm", "norm_relu"])
 def test_instance_norm_from_conv_partials(relu):
     """instance_norm(y, part=...) with the (sum, M2) partials of the producing convolution's epilogue at 256 x 256
-    (k_inorm_finalize_parts, then the walks), against float64 of the same y - not against the HIP reduction."""
+    (k_plane_finalize<TileMoments>, then the walks), against float64 of the same y - not against the HIP reduction."""
     ops = _ops()
     torch.manual_seed(7)
     N, Cin, C, S = 4, 32, 32, 256
@@ -229,7 +229,7 @@ def test_instance_norm_from_conv_partials(relu):
 
 def test_instance_norm_backward_sums_from_the_consumer_conv():
     """InstanceNorm + ReLU feeding ONE 3x3 convolution (conv2d(..., norm_input=True)): the convolution's input-gradient launch
-    leaves the norm's backward sums and the norm's backward finalises them (k_plane_sum_finalize_f) - against float64 of
+    leaves the norm's backward sums and the norm's backward finalises them (k_plane_finalize<RegionSums>) - against float64 of
     conv(relu(IN(x)))."""
     ops = _ops()
     g = torch.Generator().manual_seed(9)
@@ -259,7 +259,7 @@ def test_instance_norm_backward_sums_from_the_consumer_conv():
 CAT_CASES = [
     # (N, H, W, channels per input, parts from the producing convolutions)
     (2, 128, 128, (32, 32, 32, 32, 32), False),   # five slices of a 160-channel output at offsets 0, 32, ...: walks with strides ycs4 = gcs4 = 40
-    (2, 128, 128, (32, 32, 32, 32, 32), True),    # the same with every input's statistics from its convolution (k_inorm_finalize_parts)
+    (2, 128, 128, (32, 32, 32, 32, 32), True),    # the same with every input's statistics from its convolution (k_plane_finalize<TileMoments>)
     (2, 40, 40, (16, 5, 32), False),              # total 53 channels, offsets 0, 16, 21: the stride (and offset 21) defeat float4, C = 5 generic throughout
     (2, 40, 40, (8, 4, 36), False),               # offsets 0, 8, 12 keep float4: C4 = 2, 1 walks and C4 = 9 flat k_inorm_apply4 / k_inorm_bwd_apply4 on a 12-float4 stride
 ]
@@ -345,9 +345,9 @@ def _window_keep(out64):
 
 RES_TAIL_CASES = [
     # (N, C, H, W, statistics of x2 / xid from: "stats" own reduction, "parts" conv partials of both, "part2" of x2 only)
-    (2, 32, 256, 256, "stats"),   # vqw_inorm_stats twice (k_plane_reduce4p), fused backward k_res_tail_bwd_pair_reduce4 + k_plane_sum_finalize2 + k_inorm_bwd_pair_apply4w
-    (2, 32, 256, 256, "parts"),   # both norms' statistics in one launch (k_inorm_finalize_parts2)
-    (2, 32, 256, 256, "part2"),   # x2 from partials (k_inorm_finalize_parts), xid by its own reduction
+    (2, 32, 256, 256, "stats"),   # vqw_inorm_stats twice (k_plane_reduce4p), fused backward k_res_tail_bwd_pair_reduce4 + two-job k_plane_finalize<SplitSums> + k_inorm_bwd_pair_apply4w
+    (2, 32, 256, 256, "parts"),   # both norms' statistics in one launch (two-job k_plane_finalize<TileMoments>)
+    (2, 32, 256, 256, "part2"),   # x2 from partials (k_plane_finalize<TileMoments>), xid by its own reduction
     (2, 48, 64, 64, "stats"),     # C4 = 12: flat k_inorm_bwd_pair_apply4
 ]
 
@@ -400,8 +400,8 @@ def test_res_tail_norm_vs_float64(case, fused_bwd, monkeypatch):
 SPADE_CASES = [
     # (N, C, H, W, [gamma|beta] fused, residual: None / "plain" / "norm" / "norm_part", relu, x from a conv with partials)
     (4, 32, 256, 256, True, None, True, False),           # FSpadeBwd4 in k_plane_reduce4p, k_spade_fwd4w<RES 0>, k_spade_bwd_apply4w; k_bn_finalize
-    (4, 32, 256, 256, False, "plain", False, True),       # k_spade_fwd4w<RES 1>; statistics from the producing conv (k_bn_finalize_parts)
-    (4, 32, 256, 256, False, "norm_part", True, False),   # shortcut norm inside the kernel: k_spade_fwd4w<RES 2> with k_inorm_finalize_parts
+    (4, 32, 256, 256, False, "plain", False, True),       # k_spade_fwd4w<RES 1>; statistics from the producing conv (k_channel_finalize<TileMoments, BN>)
+    (4, 32, 256, 256, False, "norm_part", True, False),   # shortcut norm inside the kernel: k_spade_fwd4w<RES 2> with k_plane_finalize<TileMoments>
     (4, 32, 256, 256, True, "norm", False, True),         # RES 2 with the shortcut's statistics by vqw_inorm_stats (k_plane_reduce4p)
     (2, 32, 48, 64, False, "norm_part", True, False),     # H * W = 3072 not a power of two: residual_norm falls back to instance_norm(part) + RES 1
     (4, 48, 64, 64, False, "plain", True, True),          # C4 = 12: k_plane_reduce4, flat k_spade_fwd4 (with residual), k_spade_bwd_apply4
