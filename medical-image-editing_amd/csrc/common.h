@@ -29,6 +29,21 @@ extern "C" __attribute__((visibility("hidden"))) void vqw_set_error(const char* 
         }                                                                      \
     } while (0)
 
+// A kernel that asks for more than 64 KB of dynamic LDS opts in first: once per kernel (the static flag belongs to the
+// instantiation for that kernel).  Returns VQW_OK or, with the error text set, VQW_ERR_HIP.
+template <auto Kernel>
+static inline int lds_opt_in(int bytes, const char* name) {
+    static bool done = false;
+    if (!done) {
+        if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+            vqw_set_error("%s: cannot raise the dynamic LDS limit", name);
+            return VQW_ERR_HIP;
+        }
+        done = true;
+    }
+    return VQW_OK;
+}
+
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int imin(int a, int b) { return a < b ? a : b; }
 static inline int imax(int a, int b) { return a > b ? a : b; }

@@ -15,6 +15,18 @@ inline int conv_max_blocks() {
     return v;
 }
 
+// Slabs of a weight-gradient kernel whose workgroups each own one of nblk (co, ci) blocks and a run of consecutive regions:
+// as many runs as fill the GPU once, at most max_slabs, over nsp regions.  *kt_out = regions per run; returns the runs.
+inline int conv_slab_split(int nsp, int nblk, int max_slabs, int* kt_out) {
+    int nsb = conv_max_blocks() / nblk;
+    if (nsb > max_slabs) nsb = max_slabs;
+    if (nsb > nsp) nsb = nsp;
+    if (nsb < 1) nsb = 1;
+    const int kt = (nsp + nsb - 1) / nsb;
+    if (kt_out) *kt_out = kt;
+    return (nsp + kt - 1) / kt;
+}
+
 // Virtual conv input: channel-concat of src0 (C0 channels; up0=1 -> nearest x2 up-sampled from H/2 x W/2)
 // and src1 (C1 channels at full resolution; C1 == 0 -> absent).
 struct ConvIn {
@@ -123,15 +135,13 @@ int conv_wino_fwd(const float* x, const float* u, const float* bias, float* y, i
                   const float* in_mr = nullptr, int in_relu = 0);
 bool conv_wino_wgrad_ok(int Cin, int Cout, int N, int H, int W);
 int conv_wino_wgrad_blocks(const ConvIn& in, int Cout, int N, int H, int W, int max_slabs, int* kt_out);
-bool conv_wino64_wgrad_ok(int C0, int C1, int up0, int Cout, int H, int W);
-bool conv_wino32_wgrad_ok(int C0, int C1, int up0, int Cout, int H, int W);       // (32 co x 32 ci) blocks: Cout % 64 == 32
-int conv_wino32_wgrad_blocks(int Cin, int Cout, int N, int H, int W, int max_slabs, int* kt_out);
-int conv_wino32_wgrad(const ConvIn& in, const float* dy, float* ws, float* bpart, int N, int H, int W, int Cin, int Cout, int nsb, int kt,
-                      hipStream_t st, int dil = 1);
-bool conv_wino32_wgrad_dil2_ok(int C0, int Cout, int H, int W);
-int conv_wino64_wgrad_blocks(int Cin, int Cout, int N, int H, int W, int max_slabs, int* kt_out);
-int conv_wino64_wgrad(const ConvIn& in, const float* dy, float* ws, float* bpart, int N, int H, int W, int Cin, int Cout, int nsb, int kt,
-                      hipStream_t st);
+// ... on the block kernel of conv_wino64.hip: (64 co x 32 ci) blocks for Cout % 64 == 0, (32 co x 32 ci) for Cout % 64 == 32;
+// dil 2 (the 32-co form only): on the four phase images, blocks counted with 4 N, H / 2, W / 2
+bool conv_wino_blk_wgrad_ok(int C0, int C1, int up0, int Cout, int H, int W);
+bool conv_wino_blk_wgrad_dil2_ok(int C0, int Cout, int H, int W);
+int conv_wino_blk_wgrad_blocks(int Cin, int Cout, int N, int H, int W, int max_slabs, int* kt_out);
+int conv_wino_blk_wgrad(const ConvIn& in, const float* dy, float* ws, float* bpart, int N, int H, int W, int Cin, int Cout, int nsb, int kt,
+                        hipStream_t st, int dil = 1);
 int conv_wino_wgrad(const ConvIn& in, const float* dy, float* ws, float* bpart, int N, int H, int W, int Cout, int nsb, int kt,
                     hipStream_t st);
 // 3x3 over an up-sampled input in Winograd form, nine of the sixteen products (conv_wino_up.hip)

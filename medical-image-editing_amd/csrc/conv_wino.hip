@@ -276,7 +276,6 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
     // cycles).  Two reads off one base register get merged into ds_read2_b64, which is served in 16-lane groups over 32
     // banks: 8 cycles and 2-way conflicts on these layouts - the LDS, not the matrix cores, then paces the item.  Each read
     // of a pair / quad therefore goes through a base register of its own that the compiler cannot relate to the others.
-    auto opaque = [](int x) { asm volatile("" : "+v"(x)); return x; };
     const int a_row0 = opaque(a_base), a_row1 = opaque(a_base + WN_HW * WN_KPH), a_row2 = opaque(a_base + 2 * WN_HW * WN_KPH),
               a_row3 = opaque(a_base + 3 * WN_HW * WN_KPH);
     const int b_nb0 = opaque(b_base), b_nb1 = opaque(b_base + 16 * WN_KPU);
@@ -485,15 +484,7 @@ int conv_wino_fwd(const float* x, const float* u, const float* bias, float* y, i
     const bool wide = W % 32 == 0;
     const size_t lds = (size_t)(3 * (wide ? WinoGeo<32>::HBUF : WinoGeo<16>::HBUF) + 2 * 16 * 32 * WN_KPU + 2 * 8 * 32 * 2 + 512 * 4) * sizeof(float);
     static_assert((size_t)(3 * WinoGeo<16>::HBUF + 2 * 16 * 32 * WN_KPU + 2 * 8 * 32 * 2 + 512 * 4) * sizeof(float) <= 160 * 1024, "Winograd buffers do not fit the 160 KB LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_conv_wino<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_conv_wino<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            vqw_set_error("conv_wino: cannot raise the dynamic LDS limit");
-            return VQW_ERR_HIP;
-        }
-        attr_set = true;
-    }
+    if (int rc = wide ? lds_opt_in<k_conv_wino<32>>(160 * 1024, "conv_wino") : lds_opt_in<k_conv_wino<16>>(160 * 1024, "conv_wino")) return rc;
     WinoArgs a;
     a.x = x; a.u = u; a.bias = bias; a.y = y;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
@@ -786,41 +777,24 @@ bool conv_wino_wgrad_ok(int Cin, int Cout, int N, int H, int W) {
 // slabs for a given upper bound
 int conv_wino_wgrad_blocks(const ConvIn& in, int Cout, int N, int H, int W, int max_slabs, int* kt_out) {
     const int Cin = in.C0 + in.C1;
-    if (conv_wino64_wgrad_ok(in.C0, in.C1, in.up0, Cout, H, W)) return conv_wino64_wgrad_blocks(Cin, Cout, N, H, W, max_slabs, kt_out);
-    if (conv_wino32_wgrad_ok(in.C0, in.C1, in.up0, Cout, H, W)) return conv_wino32_wgrad_blocks(Cin, Cout, N, H, W, max_slabs, kt_out);
-    const int nblk = (Cout / 32) * (Cin / 16);
+    if (conv_wino_blk_wgrad_ok(in.C0, in.C1, in.up0, Cout, H, W)) return conv_wino_blk_wgrad_blocks(Cin, Cout, N, H, W, max_slabs, kt_out);
     const int rw = W % 32 == 0 ? 32 : 16;
-    const int nsp = N * ceil_div(H, 256 / rw) * (W / rw);
-    int nsb = conv_max_blocks() / nblk;
-    if (nsb > max_slabs) nsb = max_slabs;
-    if (nsb > nsp) nsb = nsp;
-    if (nsb < 1) nsb = 1;
-    const int kt = ceil_div(nsp, nsb);
-    if (kt_out) *kt_out = kt;
-    return ceil_div(nsp, kt);
+    return conv_slab_split(N * ceil_div(H, 256 / rw) * (W / rw), (Cout / 32) * (Cin / 16), max_slabs, kt_out);
 }
 int conv_wino_wgrad(const ConvIn& in, const float* dy, float* ws, float* bpart, int N, int H, int W, int Cout, int nsb, int kt,
                     hipStream_t st) {
     const int Cin = in.C0 + in.C1;
-    if (conv_wino64_wgrad_ok(in.C0, in.C1, in.up0, Cout, H, W)) return conv_wino64_wgrad(in, dy, ws, bpart, N, H, W, Cin, Cout, nsb, kt, st);
-    if (conv_wino32_wgrad_ok(in.C0, in.C1, in.up0, Cout, H, W)) return conv_wino32_wgrad(in, dy, ws, bpart, N, H, W, Cin, Cout, nsb, kt, st);
+    if (conv_wino_blk_wgrad_ok(in.C0, in.C1, in.up0, Cout, H, W)) return conv_wino_blk_wgrad(in, dy, ws, bpart, N, H, W, Cin, Cout, nsb, kt, st);
     constexpr size_t lds = (size_t)(2 * (WW_D + WW_X) + 512 * 4) * sizeof(float);
     static_assert(lds <= 160 * 1024 && lds >= 8 * 512 * sizeof(float), "Winograd wgrad tiles do not fit the LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_conv_wino_wgrad<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_conv_wino_wgrad<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            vqw_set_error("conv_wino_wgrad: cannot raise the dynamic LDS limit");
-            return VQW_ERR_HIP;
-        }
-        attr_set = true;
-    }
+    const int rw = W % 32 == 0 ? 32 : 16;
+    if (int rc = rw == 32 ? lds_opt_in<k_conv_wino_wgrad<32>>((int)lds, "conv_wino_wgrad") : lds_opt_in<k_conv_wino_wgrad<16>>((int)lds, "conv_wino_wgrad"))
+        return rc;
     const long P = (long)N * H * W;
     WinoWgArgs a;
     a.x = in.src0; a.x1 = in.src1; a.C0 = in.C0; a.C1 = in.C1; a.up0 = in.up0;
     a.dy = dy; a.part = ws; a.bias_part = bpart;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    const int rw = W % 32 == 0 ? 32 : 16;
     a.tilesY = ceil_div(H, 256 / rw); a.tilesX = W / rw; a.nsp = N * a.tilesY * a.tilesX;
     a.n_ci_b = Cin / 16; a.nblk = (Cout / 32) * a.n_ci_b; a.kt = kt;
     a.nbx = (unsigned)((in.up0 ? P / 4 : P) * in.C0 * 4);

@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
     // M block (mb, mbw) of the wave: RW = 32: tile row MBW mb + mbw, columns m; RW = 16: tile rows 2 mb + (m >> 3), columns m & 7
     const int prow = RW == 32 ? 2 * MBW * mb : 2 * (2 * mb + (m >> 3)), pcol = RW == 32 ? 2 * m : 2 * (m & 7);
     constexpr int MBW_STEP = 2 * HWS * W6_KPH;             // the wave's second M block: one tile row = two halo rows further
-    auto opaque = [](int x) { asm volatile("" : "+v"(x)); return x; };     // distinct base registers: no ds_read2 merging
+    // (opaque: distinct base registers, no ds_read2 merging)
     const int a_A = opaque(((prow + rA) * HWS + pcol) * W6_KPH + 2 * q);
     const int a_B = opaque(((prow + rB) * HWS + pcol) * W6_KPH + 2 * q);
     const int a_C = opaque(((prow + rC) * HWS + pcol) * W6_KPH + 2 * q);
@@ -640,14 +640,7 @@ static int launch_wino64(W64Args& a, hipStream_t st) {
     using G = W64Geo<RW, MBW, NW>;
     constexpr size_t lds = G::LDS_FLOATS * sizeof(float);
     static_assert(lds * (8 / NW) <= 160 * 1024, "buffers do not fit the 160 KB LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_conv_wino64<RW, MBW, EPI, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            vqw_set_error("conv_wino64: cannot raise the dynamic LDS limit");
-            return VQW_ERR_HIP;
-        }
-        attr_set = true;
-    }
+    if (int rc = lds_opt_in<k_conv_wino64<RW, MBW, EPI, NW>>((int)lds, "conv_wino64")) return rc;
     a.tilesY = ceil_div(a.H, G::TR); a.tilesX = a.W / RW; a.nsp = a.N * a.tilesY * a.tilesX;
     a.ntn = a.Cout / G::NCO;
     int groups = conv_max_blocks() * (8 / NW) / a.ntn;
@@ -736,17 +729,20 @@ int conv_wino64_fwd_split(const float* x, const float* u, const float* bias, flo
 }
 
 // =====================================================================================================================
-// Weight gradient in Winograd form for Cout % 64 == 0, Cin % 32 == 0 (one full-resolution source)
+// Weight gradient in Winograd form on (16 MB co x 32 ci) blocks of dU: MB = 4 for Cout % 64 == 0, MB = 2 for Cout % 64 == 32
 // =====================================================================================================================
 //   dU[xi][co][ci] = sum over tiles of dM[xi][tile][co] V[xi][tile][ci],   dM = A dY A^T,  V = B^T d B,   dW = G^T dU G
 // Same accounting as above: k_conv_wino_wgrad (conv_wino.hip) spends ~3 VALU instructions per MFMA (both operands are
 // transformed by the wave that multiplies them, every prefetch address is computed in the loop).  Here a workgroup owns a
-// (64 co x 32 ci) block of dU; wave (r, kh) = xi ROW r (4 of the 16 xi) x all 64 x 32 entries (4 x 4 x 2 x 4 = 128
-// accumulators) x half of the region's tiles as its K slice.  Per k-step of 4 tiles a lane builds row r of dM for its co in
-// 4 instructions per co block (the row of A dY is one fma, the columns p0, p0 + p1, p0 - p1, p1 two more; signs of row 3 /
-// column 3 are folded into the final transform) and row r of V for its ci in 8 per ci block: 32 VALU for 32 MFMAs.
+// (16 MB co x 32 ci) block of dU; wave (r, kh) = xi ROW r (4 of the 16 xi) x all entries of the block (4 xi columns x MB x 2
+// accumulator tiles) x half of the region's tiles as its K slice.  Per k-step of 4 tiles a lane builds row r of dM for its co
+// in 4 instructions per co block (the row of A dY is one fma, the columns p0, p0 + p1, p0 - p1, p1 two more; signs of row 3 /
+// column 3 are folded into the final transform) and row r of V for its ci in 8 per ci block:
+//   MB = 4: 32 VALU for 32 MFMAs, 128 accumulators;
+//   MB = 2 (round 4): 24 VALU for 16 MFMAs = 1.5 per MFMA, 64 accumulators - two VALU operations and two LDS reads per MFMA
+//           position instead of one (k_conv_wino_wgrad, which these layers ran on: ~3 with its in-loop address arithmetic).
 // Operands are built one k-step ahead of the MFMAs that consume them, across the region barrier too (one barrier per
-// 128 MFMAs); prefetch addresses are per-thread constants against a buffer descriptor whose base moves with the region
+// 32 MB MFMAs); prefetch addresses are per-thread constants against a buffer descriptor whose base moves with the region
 // (SALU), image-edge padding costs three VALU instructions per slot and region (edge bits of the slot & the region's flags).
 namespace {
 
@@ -765,25 +761,34 @@ struct W64WgArgs {
     const float* x1;
     int C0, up0;
     unsigned nbx1;
-    // pixel index of (n, y, x) as in W64Args (k_conv_wino_wgrad32 only): dense, or the phase images of a dilation-2 layer
+    // pixel index of (n, y, x) as in W64Args (MB = 2 only): dense, or the phase images of a dilation-2 layer
     unsigned img_px, rowb_px, rpx, ppx;
     int n_sh, n_m;
 };
 
 constexpr int W6_WLS = 2;                  // MFMA positions between two prefetch loads of the weight-gradient kernel
-constexpr int WG_DP = 72, WG_XP = 40;     // floats per dY pixel (64 co + 8) / X pixel (32 ci + 8): adjacent tiles 16 banks apart
-template <int RW> struct WgGeo {
-    static constexpr int TRP = RW == 32 ? 4 : 8;           // pixel rows per region: 32 tiles
+constexpr int WG_XP = 40;                  // floats per X pixel (32 ci + 8): adjacent tiles 16 banks apart
+// Region = 32 tiles: 4 x 32 pixels, or - for maps whose width is a multiple of 16 only (MB = 4) - 8 x 16
+template <int RW, int MB> struct WgGeo {
+    static_assert((MB == 4 && (RW == 32 || RW == 16)) || (MB == 2 && RW == 32), "the 16-wide region needs the dense rows of the 64-cout form");
+    static constexpr int DP = 16 * MB + 8;                 // floats per dY pixel (the block's couts + 8: adjacent tiles 16 banks apart)
+    static constexpr int TRP = RW == 32 ? 4 : 8;           // pixel rows per region
     static constexpr int XW = RW + 2, XR = TRP + 2, XPIX = XR * XW;
-    static constexpr int DBUF = 128 * WG_DP, XBUF = XPIX * WG_XP;
+    static constexpr int DBUF = 128 * DP, XBUF = XPIX * WG_XP;
+    static constexpr size_t LDS_BYTES = (size_t)2 * (DBUF + XBUF) * sizeof(float);
+    static_assert(LDS_BYTES <= 160 * 1024 && LDS_BYTES >= 64 * 1024, "tiles fit the LDS; the fold needs 64 KB");
 };
 
-template <int RW>
-__global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
-    using G = WgGeo<RW>;
-    constexpr int NT = 512, DBUF = G::DBUF, XBUF = G::XBUF, XW = G::XW;
+template <int RW, int MB>
+__global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad_blk(W64WgArgs a) {
+    using G = WgGeo<RW, MB>;
+    constexpr int NT = 512, DP = G::DP, DBUF = G::DBUF, XBUF = G::XBUF, XW = G::XW;
     constexpr int XF = G::XPIX * 8;                        // float4 per X halo: 1632 / 1440
     constexpr int LX = (XF + NT - 1) / NT;                 // 4 / 3 slots
+    constexpr int QD = 4 * MB;                             // float4 per dY pixel
+    constexpr int DPX = NT / QD, LD = MB;                  // dY: 128 pixels x QD float4 = LD slots of DPX pixels (DPX / RW rows)
+    constexpr int NP = 8 * MB;                             // MFMA positions of a phase
+    constexpr bool PITCH = MB == 2;                        // pixels through the pitch fields of the arguments; MB = 4: dense
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // layout: dY tiles [2][DBUF], then X halos [2][XBUF]
 
@@ -794,18 +799,18 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
     // the (co, ci) blocks of one spatial split read the same dY / X regions: keep them on one XCD's L2
     const int lb = xcd_remap(blockIdx.x, gridDim.x);
     const int blk = lb % a.nblk, sblk = lb / a.nblk;
-    const int co_base = (blk / a.n_ci_b) * 64, ci_base = (blk % a.n_ci_b) * 32;
+    const int co_base = (blk / a.n_ci_b) * (16 * MB), ci_base = (blk % a.n_ci_b) * 32;
     const int sp0 = sblk * a.kt;
     const int my_tiles = min(a.kt, a.nsp - sp0);
-    const int per_img = a.tilesY * a.tilesX;
     const bool do_bias = a.bias_part != nullptr && ci_base == 0;
+    const unsigned rpx = PITCH ? a.rpx : (unsigned)W, ppx = PITCH ? a.ppx : 1u;       // pixels from row to row, column to column
 
     // ---- loader slots ----
-    // dY float4 f = tid + 512 j -> pixel f / 16, co quad f % 16 = tid & 15
-    const int d_px = tid >> 4;                                            // + 32 j
-    const unsigned d_fix = ((unsigned)((RW == 32 ? 0 : (d_px >> 4)) * W + (RW == 32 ? d_px : (d_px & 15))) * Cout + co_base + (tid & 15) * 4) * 4u;
-    const unsigned d_jstride = (unsigned)((RW == 32 ? 1 : 2) * W) * Cout * 4u;      // 32 pixels further: one / two rows
-    const int d_lds = d_px * WG_DP + (tid & 15) * 4;                      // + j * 32 * WG_DP
+    // dY float4 f = tid + 512 j -> pixel f / QD of the region (rows of RW), co quad f % QD
+    const int d_px = tid / QD;                                            // + DPX j
+    const unsigned d_fix = (((unsigned)(d_px / RW) * rpx + (unsigned)(d_px % RW) * ppx) * Cout + co_base + (tid % QD) * 4) * 4u;
+    const unsigned d_jstride = (unsigned)(DPX / RW) * rpx * Cout * 4u;    // DPX pixels further: one / two rows
+    const int d_lds = d_px * DP + (tid % QD) * 4;                         // + j * DPX * DP
     // X float4 f = tid + 512 j -> halo pixel f / 8, ci quad f % 8 = tid & 7; slots past the end repeat another thread's
     // the source of this workgroup's ci block (uniform): its pointer, channels per pixel, first channel, row length
     const bool x_s1 = ci_base >= a.C0;
@@ -814,6 +819,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
     const int x_cs = x_s1 ? Cin - a.C0 : a.C0, x_cb = x_s1 ? ci_base - a.C0 : ci_base;
     const int x_w = x_up ? W >> 1 : W, x_h = x_up ? H >> 1 : H;
     const long x_nb = x_s1 ? (long)a.nbx1 : (long)a.nbx;
+    const unsigned x_rpx = x_up ? (unsigned)x_w : rpx, x_ppx = x_up ? 1u : ppx;
     unsigned x_fix[LX];
     int x_lds[LX];
     unsigned x_bits = 0;                   // 4 bits per slot: the pixel lies on the halo's top / bottom row, left / right column
@@ -823,43 +829,43 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
         if (f >= XF) f -= XF;
         const int hp = f >> 3, hy = hp / XW, hx = hp - hy * XW;
         // against the pixel (y0 - 1, x0 - 1); an up-sampled source: against the low-resolution pixel (y0 / 2 - 1, x0 / 2 - 1)
-        x_fix[j] = ((unsigned)((x_up ? (hy + 1) >> 1 : hy) * x_w + (x_up ? (hx + 1) >> 1 : hx)) * x_cs + x_cb + (tid & 7) * 4) * 4u;
+        x_fix[j] = (((unsigned)(x_up ? (hy + 1) >> 1 : hy) * x_rpx + (unsigned)(x_up ? (hx + 1) >> 1 : hx) * x_ppx) * x_cs + x_cb + (tid & 7) * 4) * 4u;
         x_lds[j] = 2 * DBUF + hp * WG_XP + (tid & 7) * 4;
         x_bits |= (unsigned)((hy == 0 ? 1 : 0) | (hy == G::XR - 1 ? 2 : 0) | (hx == 0 ? 4 : 0) | (hx == XW - 1 ? 8 : 0)) << (4 * j);
     }
-    float4 rd[4], rx[LX];
+    float4 rd[LD], rx[LX];
     float4 bsum;
     bsum.x = bsum.y = bsum.z = bsum.w = 0.f;
-    auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
-        u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, (int)soff, 0);
-        float4 f;
-        unsigned a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];
-        f.x = __uint_as_float(a0); f.y = __uint_as_float(a1); f.z = __uint_as_float(a2); f.w = __uint_as_float(a3);
-        return f;
-    };
     // region (n, tx, ty): descriptors whose base is the region's first dY pixel / the pixel (y0 - 1, x0 - 1) of X.  Offsets
     // are range-checked against the rest of the tensor; what lies before its start is masked by the lane masks.
     __amdgpu_buffer_rsrc_t rsd, rsx;
     unsigned x_edges = 0;               // the region's edge flags (top, bottom, left, right), once per slot nibble
     auto region_setup = [&](int n, int tx, int ty) {
         const int y0 = ty * G::TRP, x0 = tx * RW;
-        const long dpix = ((long)n * H + y0) * W + x0;
+        long dpix;
+        if constexpr (PITCH) {
+            const long nbase = (long)(n >> a.n_sh) * a.img_px + (long)((n >> 1) & a.n_m) * a.rowb_px + (n & a.n_m);
+            dpix = nbase + (long)y0 * a.rpx + (long)x0 * a.ppx;
+        } else {
+            dpix = ((long)n * H + y0) * W + x0;
+        }
         const long doff = dpix * Cout * 4;
         rsd = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.dy + doff), 0, (int)(unsigned)((long)a.nbd - doff), 0x00020000);
-        const long xpix = x_up ? ((long)n * x_h + (y0 >> 1) - 1) * x_w + (x0 >> 1) - 1 : dpix - W - 1;
+        const long xpix = x_up ? ((long)n * x_h + (y0 >> 1) - 1) * x_w + (x0 >> 1) - 1
+                               : PITCH ? dpix - (long)a.rpx - (long)a.ppx : dpix - W - 1;
         const long xoff = xpix * x_cs * 4;                                // may lie before the tensor (first region): masked
         const long xleft = x_nb - xoff;
         rsx = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)x_ptr + xoff), 0, (int)(unsigned)(xleft > 0xFFFFFFF0L ? 0xFFFFFFF0L : xleft), 0x00020000);
         x_edges = ((y0 == 0 ? 1u : 0u) | (y0 + G::TRP == H ? 2u : 0u) | (x0 == 0 ? 4u : 0u) | (x0 + RW == W ? 8u : 0u)) * 0x1111u;
     };
-    auto issue_d = [&](int j) { rd[j] = ld4(rsd, d_fix, j * d_jstride); };
+    auto issue_d = [&](int j) { rd[j] = buf_ld4(rsd, d_fix, j * d_jstride); };
     auto issue_x = [&](int j) {
         const unsigned vo = (x_bits & x_edges & (0xFu << (4 * j))) ? 0xFFFFFFFFu : x_fix[j];      // padding: out of range -> 0
-        rx[j] = ld4(rsx, vo, 0);
+        rx[j] = buf_ld4(rsx, vo, 0);
     };
     float once_v = 1.f;                 // 0 for the prefetch past the workgroup's share (a repeat of its last region)
     auto commit_d = [&](int j, int buf) {
-        *(float4*)&smem[d_lds + buf * DBUF + j * 32 * WG_DP] = rd[j];
+        *(float4*)&smem[d_lds + buf * DBUF + j * DPX * DP] = rd[j];
         if (do_bias) {                  // uniform; fused bias gradient
             bsum.x = __builtin_fmaf(once_v, rd[j].x, bsum.x); bsum.y = __builtin_fmaf(once_v, rd[j].y, bsum.y);
             bsum.z = __builtin_fmaf(once_v, rd[j].z, bsum.z); bsum.w = __builtin_fmaf(once_v, rd[j].w, bsum.w);
@@ -873,12 +879,11 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
     // rows of A dY: r = 0: y0.; 1: y0. + y1.; 2: y0. - y1.; 3: y1. (negated: folded)  ->  p = yF + sA * yS
     const int aF = r == 3 ? 1 : 0, aS = r == 0 ? 0 : 1;
     const int trow0 = RW == 32 ? kh : 2 * kh;
-    auto opaque = [](int x) { asm volatile("" : "+v"(x)); return x; };
-    const int a_F = opaque(((2 * trow0 + aF) * RW + 2 * k) * WG_DP + idx);       // + s-part, + b * WG_DP, + mbk * 16
-    const int a_S = opaque(((2 * trow0 + aS) * RW + 2 * k) * WG_DP + idx);
+    const int a_F = opaque(((2 * trow0 + aF) * RW + 2 * k) * DP + idx);          // + s-part, + b * DP, + mbk * 16
+    const int a_S = opaque(((2 * trow0 + aS) * RW + 2 * k) * DP + idx);
     // rows of B^T d: r = 0: d0 - d2; 1: d1 + d2; 2: d2 - d1; 3: d1 - d3  ->  e = dA + sB * dB
     const int iA = r == 0 ? 0 : r == 2 ? 2 : 1, iB = r == 0 ? 2 : r == 1 ? 2 : r == 2 ? 1 : 3;
-    // (the X buffers start 72 KB into the LDS, beyond the 64 KB immediate of a ds_read: their offset lives in the base register)
+    // (MB = 4: the X buffers start 72 KB into the LDS, beyond the 64 KB immediate of a ds_read: their offset lives in the base register)
     const int x_A = opaque(2 * DBUF + ((2 * trow0 + iA) * XW + 2 * k) * WG_XP + idx);       // + s-part, + column * WG_XP, + nbk * 16
     const int x_B = opaque(2 * DBUF + ((2 * trow0 + iB) * XW + 2 * k) * WG_XP + idx);
     float sA, sB;
@@ -888,32 +893,32 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
     auto s_px_d = [](int s) { return RW == 32 ? 8 * s : 2 * (s >> 1) * 16 + 8 * (s & 1); };
     auto s_px_x = [](int s) { return RW == 32 ? 8 * s : 2 * (s >> 1) * XW + 8 * (s & 1); };
 
-    f32x4 acc[4][4][2];                // [xi column][co block][ci block]
+    f32x4 acc[4][MB][2];               // [xi column][co block][ci block]
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
+        for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) acc[c][mb][nb][q] = 0.f;
-    float dm[2][4][4];                 // [operand set][co block][xi column]
+    float dm[2][MB][4];                // [operand set][co block][xi column]
     float vv[2][2][4];                 // [operand set][ci block][xi column]
     float ra[2][4], rb[2][8];          // raw LDS values of two groups in flight
 
-    // Operand build for k-step s from the buffers (Db, Xb), as six groups: g = 0..3 co block g (4 reads, 4 VALU),
-    // g = 4, 5 ci block g - 4 (8 reads, 8 VALU)
+    // Operand build for k-step s from the buffers (Db, Xb), as MB + 2 groups: g < MB co block g (4 reads, 4 VALU),
+    // g = MB, MB + 1 ci block g - MB (8 reads, 8 VALU)
     auto rd_grp = [&](int nbuf, int s, int g, int i) {       // read i of group g from buffer nbuf
-        if (g < 4) {
-            const int o = nbuf * DBUF + s_px_d(s) * WG_DP + g * 16 + (i & 1) * WG_DP;
+        if (g < MB) {
+            const int o = nbuf * DBUF + s_px_d(s) * DP + g * 16 + (i & 1) * DP;
             ra[g & 1][i] = i < 2 ? smem[a_F + o] : smem[a_S + o];
         } else {
-            const int o = nbuf * XBUF + s_px_x(s) * WG_XP + (g - 4) * 16 + (i & 3) * WG_XP;
+            const int o = nbuf * XBUF + s_px_x(s) * WG_XP + (g - MB) * 16 + (i & 3) * WG_XP;
             rb[g & 1][i] = i < 4 ? smem[x_A + o] : smem[x_B + o];
         }
     };
     auto op_grp = [&](int set, int g, int i) {          // VALU operation i of group g
-        if (g < 4) {
+        if (g < MB) {
             float* d = dm[set][g];
             const float* q = ra[g & 1];
             if (i == 0) d[0] = __builtin_fmaf(sA, q[2], q[0]);          // p0
@@ -921,7 +926,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
             if (i == 2) d[1] = d[0] + d[3];
             if (i == 3) d[2] = d[0] - d[3];
         } else {
-            float* o = vv[set][g - 4];
+            float* o = vv[set][g - MB];
             float* q = rb[g & 1];
             if (i < 4) q[i] = __builtin_fmaf(sB, q[4 + i], q[i]);       // e[i] in place
             if (i == 4) o[0] = q[0] - q[2];
@@ -930,59 +935,66 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
             if (i == 7) o[3] = q[1] - q[3];
         }
     };
-    // position p = 0..31 of a phase -> what is built beside MFMA p:
-    //   p 0-3 reads A0 | 4-7 ops A0, reads A1 | 8-11 ops A1, reads A2 | 12-15 ops A2, reads A3 | 16-19 ops A3, reads B0 (2 each)
-    //   | 20-27 ops B0, reads B1 | 28-31 ops B1 (2 each)
+    // what is built beside MFMA position p of a phase (A = co group, B = ci group): the hand-written schedule of each block shape
     auto build_slot = [&](int nbuf, int s, int set, int p) {
-        if (p < 4) rd_grp(nbuf, s, 0, p);
-        else if (p < 16) { op_grp(set, (p - 4) >> 2, (p - 4) & 3); rd_grp(nbuf, s, ((p - 4) >> 2) + 1, (p - 4) & 3); }
-        else if (p < 20) { op_grp(set, 3, p - 16); rd_grp(nbuf, s, 4, 2 * (p - 16)); rd_grp(nbuf, s, 4, 2 * (p - 16) + 1); }
-        else if (p < 28) { op_grp(set, 4, p - 20); rd_grp(nbuf, s, 5, p - 20); }
-        else { op_grp(set, 5, 2 * (p - 28)); op_grp(set, 5, 2 * (p - 28) + 1); }
+        if constexpr (MB == 4) {
+            // p = 0..31: 0-3 reads A0 | 4-7 ops A0, reads A1 | 8-11 ops A1, reads A2 | 12-15 ops A2, reads A3 | 16-19 ops A3,
+            //   reads B0 (2 each) | 20-27 ops B0, reads B1 | 28-31 ops B1 (2 each)
+            if (p < 4) rd_grp(nbuf, s, 0, p);
+            else if (p < 16) { op_grp(set, (p - 4) >> 2, (p - 4) & 3); rd_grp(nbuf, s, ((p - 4) >> 2) + 1, (p - 4) & 3); }
+            else if (p < 20) { op_grp(set, 3, p - 16); rd_grp(nbuf, s, 4, 2 * (p - 16)); rd_grp(nbuf, s, 4, 2 * (p - 16) + 1); }
+            else if (p < 28) { op_grp(set, 4, p - 20); rd_grp(nbuf, s, 5, p - 20); }
+            else { op_grp(set, 5, 2 * (p - 28)); op_grp(set, 5, 2 * (p - 28) + 1); }
+        } else {
+            // p = 0..15 (reads land two positions before their first use; two reads / two operations per position):
+            //   0-1 reads A0 | 2 reads A1 | 3 reads A1, ops A0 | 4 ops A0, reads B0 | 5-6 ops A1, reads B0 | 7 reads B0 |
+            //   8-11 ops B0, reads B1 | 12-15 ops B1
+            auto rd2 = [&](int g, int i0) { rd_grp(nbuf, s, g, i0); rd_grp(nbuf, s, g, i0 + 1); };
+            auto op2 = [&](int g, int i0) { op_grp(set, g, i0); op_grp(set, g, i0 + 1); };
+            if (p == 0) rd2(0, 0);
+            else if (p == 1) rd2(0, 2);
+            else if (p == 2) rd2(1, 0);
+            else if (p == 3) { op2(0, 0); rd2(1, 2); }
+            else if (p == 4) { op2(0, 2); rd2(2, 0); }
+            else if (p == 5) { op2(1, 0); rd2(2, 2); }
+            else if (p == 6) { op2(1, 2); rd2(2, 4); }
+            else if (p == 7) rd2(2, 6);
+            else if (p < 12) { op2(2, 2 * (p - 8)); rd2(3, 2 * (p - 8)); }
+            else op2(3, 2 * (p - 12));
+        }
     };
 
     // ---- region cursors ----
-    int cn = sp0 / per_img, ctx, cty;
-    {
-        const int rem = sp0 - cn * per_img;
-        ctx = rem / a.tilesY;
-        cty = rem - ctx * a.tilesY;
-    }
-    auto next_region = [&](int& n, int& tx, int& ty) {
-        const int ty1 = ty + 1, wy = ty1 == a.tilesY ? 1 : 0;
-        ty = wy ? 0 : ty1;
-        const int tx1 = tx + wy, wx = tx1 == a.tilesX ? 1 : 0;
-        tx = wx ? 0 : tx1;
-        n += wx;
-    };
+    int cn, ctx, cty;
+    region_start(sp0, a.tilesY, a.tilesX, cn, ctx, cty);
     if (my_tiles > 0) {
         // prologue: region 0 into buffer 0, operands of its first k-step; the dY loads of region 1 in flight
         region_setup(cn, ctx, cty);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) issue_d(j);
+        for (int j = 0; j < LD; ++j) issue_d(j);
 #pragma unroll
         for (int j = 0; j < LX; ++j) issue_x(j);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) commit_d(j, 0);
+        for (int j = 0; j < LD; ++j) commit_d(j, 0);
 #pragma unroll
         for (int j = 0; j < LX; ++j) commit_x(j, 0);
         __syncthreads();
 #pragma unroll
-        for (int p = 0; p < 32; ++p) build_slot(0, 0, 0, p);
+        for (int p = 0; p < NP; ++p) build_slot(0, 0, 0, p);
     }
     // the region whose data is fetched next (clamped to the workgroup's share: past it the last region is fetched again)
     int ln = cn, ltx = ctx, lty = cty, lcount = 0;
     auto load_advance = [&]() {
-        if (lcount + 1 < my_tiles) { next_region(ln, ltx, lty); ++lcount; once_v = 1.f; } else once_v = 0.f;
+        if (lcount + 1 < my_tiles) { region_next(a.tilesY, a.tilesX, ln, ltx, lty); ++lcount; once_v = 1.f; } else once_v = 0.f;
         region_setup(ln, ltx, lty);
     };
     if (my_tiles > 0) {
         load_advance();
 #pragma unroll
-        for (int j = 0; j < 4; ++j) issue_d(j);
+        for (int j = 0; j < LD; ++j) issue_d(j);
     }
 
-    // One phase = the 32 MFMAs of k-step s (operand set SET) + the build of the next k-step's operands (set SET ^ 1) from
+    // One phase = the NP MFMAs of k-step s (operand set SET) + the build of the next k-step's operands (set SET ^ 1) from
     // buffer NB + what LOADS says: 0 commit dY, 1 issue X, 2 commit X (all of the next region), 3 issue dY of the one after it
     auto phase = [&](auto SET, auto SNEXT, auto NBUF, auto DBUFW, auto LOADS) {
         constexpr int set = decltype(SET)::value, sn = decltype(SNEXT)::value, nbuf = decltype(NBUF)::value;
@@ -990,17 +1002,17 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int mb = 0; mb < 4; ++mb)
+            for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb) {
-                    const int p = c * 8 + mb * 2 + nb;
+                    const int p = c * 2 * MB + mb * 2 + nb;
                     acc[c][mb][nb] = MFMA16(dm[set][mb][c], vv[set][nb][c], acc[c][mb][nb]);
                     build_slot(nbuf, sn, set ^ 1, p);
                     // prefetch: a phase (1 us) between a load and its LDS commit (twice that changed nothing and costs registers)
-                    if (loads == 0 && p >= 8 && p < 12) commit_d(p - 8, wbuf);
+                    if (loads == 0 && p >= 8 && p < 8 + LD) commit_d(p - 8, wbuf);
                     if (loads == 1 && p >= 2 && p < 2 + W6_WLS * LX && (p - 2) % W6_WLS == 0) issue_x((p - 2) / W6_WLS);
                     if (loads == 2 && p >= 8 && p < 8 + LX) commit_x(p - 8, wbuf);
-                    if (loads == 3 && p >= 2 && p < 2 + W6_WLS * 4 && (p - 2) % W6_WLS == 0) issue_d((p - 2) / W6_WLS);
+                    if (loads == 3 && p >= 2 && p < 2 + W6_WLS * LD && (p - 2) % W6_WLS == 0) issue_d((p - 2) / W6_WLS);
                     __builtin_amdgcn_sched_barrier(0);
                 }
     };
@@ -1027,13 +1039,13 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
     // ---- fold: the two K halves and the four xi rows meet in LDS, one co block (16 couts) per round ----
     __syncthreads();
     float* red = smem;                     // [kh][r][c][16 co][32 ci] = 64 KB
-    if (do_bias) {                         // threads with equal (tid & 15) hold the same 4 couts
+    if (do_bias) {                         // threads with equal (tid % QD) hold the same 4 couts
         *(float4*)&red[tid * 4] = bsum;
         __syncthreads();
-        if (tid < 64) {
+        if (tid < 16 * MB) {
             const int cq = tid >> 2, comp = tid & 3;
             float sum = 0.f;
-            for (int i = 0; i < 32; ++i) sum += red[(i * 16 + cq) * 4 + comp];
+            for (int i = 0; i < DPX; ++i) sum += red[(i * QD + cq) * 4 + comp];
             a.bias_part[(size_t)sblk * Cout + co_base + tid] = sum;
         }
         __syncthreads();
@@ -1043,7 +1055,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
     int fold_w = ((kh * 4 + r) * 4 * 16 + 4 * (lane >> 4)) * 32 + idx, fold_r = tid;
     asm volatile("" : "+v"(fold_w), "+v"(fold_r));
 #pragma unroll
-    for (int mb = 0; mb < 4; ++mb) {
+    for (int mb = 0; mb < MB; ++mb) {
         // C/D layout (16x16): col = lane & 15 (ci), row = 4 (lane >> 4) + q (co within the block)
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -1082,421 +1094,55 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad64(W64WgArgs a) {
     }
 }
 
-
-// =====================================================================================================================
-// The same weight-gradient structure for layers whose Cout is a multiple of 32 but not of 64 (round 4): a workgroup owns a
-// (32 co x 32 ci) block of dU.  Wave (r, kh) as above; a k-step is 16 MFMAs (4 xi columns x 2 co blocks x 2 ci blocks, 64
-// accumulators) and its operand build 2 x 4 + 2 x 8 = 24 VALU = 1.5 per MFMA (the 64 x 32 block: 1.0; k_conv_wino_wgrad of
-// conv_wino.hip, which these layers ran on: ~3 with its in-loop address arithmetic).  Two VALU operations and two LDS reads per
-// MFMA position instead of one; everything else - region walk, descriptors that move with the region, edge bits, fold - is
-// the 64-cout kernel's.  32-pixel-wide regions only (the layers concerned live on the 128- and 256-pixel levels).
-constexpr int WH_DP = 40, WH_XP = 40;      // floats per dY pixel (32 co + 8) / X pixel (32 ci + 8): adjacent tiles 16 banks apart
-struct WhGeo {
-    static constexpr int RW = 32, TRP = 4;
-    static constexpr int XW = RW + 2, XR = TRP + 2, XPIX = XR * XW;
-    static constexpr int DBUF = 128 * WH_DP, XBUF = XPIX * WH_XP;
-};
-
-__global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad32(W64WgArgs a) {
-    using G = WhGeo;
-    constexpr int RW = 32, NT = 512, DBUF = G::DBUF, XBUF = G::XBUF, XW = G::XW;
-    constexpr int XF = G::XPIX * 8;                        // float4 per X halo: 1632
-    constexpr int LX = (XF + NT - 1) / NT;                 // 4 slots
-    constexpr int LD = 2;                                  // dY: 128 pixels x 8 float4 = 1024 = 2 slots
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    // layout: dY tiles [2][DBUF], then X halos [2][XBUF]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = wv & 3, kh = wv >> 2;
-    const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
-    const int lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int blk = lb % a.nblk, sblk = lb / a.nblk;
-    const int co_base = (blk / a.n_ci_b) * 32, ci_base = (blk % a.n_ci_b) * 32;
-    const int sp0 = sblk * a.kt;
-    const int my_tiles = min(a.kt, a.nsp - sp0);
-    const int per_img = a.tilesY * a.tilesX;
-    const bool do_bias = a.bias_part != nullptr && ci_base == 0;
-
-    // ---- loader slots ----
-    // dY float4 f = tid + 512 j -> pixel f / 8 = (tid >> 3) + 64 j (two pixel rows per slot), co quad tid & 7
-    const int d_px = tid >> 3;
-    const unsigned d_fix = (((unsigned)(d_px >> 5) * a.rpx + (unsigned)(d_px & 31) * a.ppx) * Cout + co_base + (tid & 7) * 4) * 4u;
-    const unsigned d_jstride = 2u * a.rpx * Cout * 4u;
-    const int d_lds = d_px * WH_DP + (tid & 7) * 4;                       // + j * 64 * WH_DP
-    // the source of this workgroup's ci block (uniform): its pointer, channels per pixel, first channel, row length
-    const bool x_s1 = ci_base >= a.C0;
-    const bool x_up = !x_s1 && a.up0;
-    const float* x_ptr = x_s1 ? a.x1 : a.x;
-    const int x_cs = x_s1 ? Cin - a.C0 : a.C0, x_cb = x_s1 ? ci_base - a.C0 : ci_base;
-    const int x_w = x_up ? W >> 1 : W, x_h = x_up ? H >> 1 : H;
-    const long x_nb = x_s1 ? (long)a.nbx1 : (long)a.nbx;
-    unsigned x_fix[LX];
-    int x_lds[LX];
-    unsigned x_bits = 0;
-#pragma unroll
-    for (int j = 0; j < LX; ++j) {
-        int f = tid + j * NT;
-        if (f >= XF) f -= XF;
-        const int hp = f >> 3, hy = hp / XW, hx = hp - hy * XW;
-        const unsigned xpx = x_up ? (unsigned)(((hy + 1) >> 1) * x_w + ((hx + 1) >> 1)) : (unsigned)hy * a.rpx + (unsigned)hx * a.ppx;
-        x_fix[j] = (xpx * x_cs + x_cb + (tid & 7) * 4) * 4u;
-        x_lds[j] = 2 * DBUF + hp * WH_XP + (tid & 7) * 4;
-        x_bits |= (unsigned)((hy == 0 ? 1 : 0) | (hy == G::XR - 1 ? 2 : 0) | (hx == 0 ? 4 : 0) | (hx == XW - 1 ? 8 : 0)) << (4 * j);
-    }
-    float4 rd[LD], rx[LX];
-    float4 bsum;
-    bsum.x = bsum.y = bsum.z = bsum.w = 0.f;
-    auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
-        u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, (int)soff, 0);
-        float4 f;
-        unsigned a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];
-        f.x = __uint_as_float(a0); f.y = __uint_as_float(a1); f.z = __uint_as_float(a2); f.w = __uint_as_float(a3);
-        return f;
-    };
-    __amdgpu_buffer_rsrc_t rsd, rsx;
-    unsigned x_edges = 0;
-    auto region_setup = [&](int n, int tx, int ty) {
-        const int y0 = ty * G::TRP, x0 = tx * RW;
-        const long nbase = (long)(n >> a.n_sh) * a.img_px + (long)((n >> 1) & a.n_m) * a.rowb_px + (n & a.n_m);
-        const long dpix = nbase + (long)y0 * a.rpx + (long)x0 * a.ppx;
-        const long doff = dpix * Cout * 4;
-        rsd = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.dy + doff), 0, (int)(unsigned)((long)a.nbd - doff), 0x00020000);
-        const long xpix = x_up ? ((long)n * x_h + (y0 >> 1) - 1) * x_w + (x0 >> 1) - 1 : dpix - (long)a.rpx - (long)a.ppx;
-        const long xoff = xpix * x_cs * 4;
-        const long xleft = x_nb - xoff;
-        rsx = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)x_ptr + xoff), 0, (int)(unsigned)(xleft > 0xFFFFFFF0L ? 0xFFFFFFF0L : xleft), 0x00020000);
-        x_edges = ((y0 == 0 ? 1u : 0u) | (y0 + G::TRP == H ? 2u : 0u) | (x0 == 0 ? 4u : 0u) | (x0 + RW == W ? 8u : 0u)) * 0x1111u;
-    };
-    auto issue_d = [&](int j) { rd[j] = ld4(rsd, d_fix, j * d_jstride); };
-    auto issue_x = [&](int j) {
-        const unsigned vo = (x_bits & x_edges & (0xFu << (4 * j))) ? 0xFFFFFFFFu : x_fix[j];
-        rx[j] = ld4(rsx, vo, 0);
-    };
-    float once_v = 1.f;
-    auto commit_d = [&](int j, int buf) {
-        *(float4*)&smem[d_lds + buf * DBUF + j * 64 * WH_DP] = rd[j];
-        if (do_bias) {
-            bsum.x = __builtin_fmaf(once_v, rd[j].x, bsum.x); bsum.y = __builtin_fmaf(once_v, rd[j].y, bsum.y);
-            bsum.z = __builtin_fmaf(once_v, rd[j].z, bsum.z); bsum.w = __builtin_fmaf(once_v, rd[j].w, bsum.w);
-        }
-    };
-    auto commit_x = [&](int j, int buf) { *(float4*)&smem[x_lds[j] + buf * XBUF] = rx[j]; };
-
-    // ---- fragment addressing: lane (channel idx = lane & 15, tile k = lane >> 4 of the k-step) ----
-    const int idx = lane & 15, k = lane >> 4;
-    const int aF = r == 3 ? 1 : 0, aS = r == 0 ? 0 : 1;
-    const int trow0 = kh;
-    auto opaque = [](int x) { asm volatile("" : "+v"(x)); return x; };
-    const int a_F = opaque(((2 * trow0 + aF) * RW + 2 * k) * WH_DP + idx);
-    const int a_S = opaque(((2 * trow0 + aS) * RW + 2 * k) * WH_DP + idx);
-    const int iA = r == 0 ? 0 : r == 2 ? 2 : 1, iB = r == 0 ? 2 : r == 1 ? 2 : r == 2 ? 1 : 3;
-    const int x_A = opaque(2 * DBUF + ((2 * trow0 + iA) * XW + 2 * k) * WH_XP + idx);
-    const int x_B = opaque(2 * DBUF + ((2 * trow0 + iB) * XW + 2 * k) * WH_XP + idx);
-    float sA, sB;
-    { float s = (r == 1) ? 1.f : (r == 2) ? -1.f : 0.f; asm volatile("v_mov_b32 %0, %1" : "=v"(sA) : "v"(s)); }
-    { float s = (r == 1) ? 1.f : -1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(sB) : "v"(s)); }
-
-    f32x4 acc[4][2][2];                // [xi column][co block][ci block]
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[c][mb][nb][q] = 0.f;
-    float dm[2][2][4];                 // [operand set][co block][xi column]
-    float vv[2][2][4];                 // [operand set][ci block][xi column]
-    float ra[2][4], rb[2][8];          // raw LDS values: ra[co group], rb[ci group]
-
-    // groups of a k-step: g = 0, 1 co block g (4 reads, 4 VALU), g = 2, 3 ci block g - 2 (8 reads, 8 VALU)
-    auto rd_grp = [&](int nbuf, int s, int g, int i) {
-        if (g < 2) {
-            const int o = nbuf * DBUF + 8 * s * WH_DP + g * 16 + (i & 1) * WH_DP;
-            ra[g][i] = i < 2 ? smem[a_F + o] : smem[a_S + o];
-        } else {
-            const int o = nbuf * XBUF + 8 * s * WH_XP + (g - 2) * 16 + (i & 3) * WH_XP;
-            rb[g - 2][i] = i < 4 ? smem[x_A + o] : smem[x_B + o];
-        }
-    };
-    auto op_grp = [&](int set, int g, int i) {
-        if (g < 2) {
-            float* d = dm[set][g];
-            const float* q = ra[g];
-            if (i == 0) d[0] = __builtin_fmaf(sA, q[2], q[0]);
-            if (i == 1) d[3] = __builtin_fmaf(sA, q[3], q[1]);
-            if (i == 2) d[1] = d[0] + d[3];
-            if (i == 3) d[2] = d[0] - d[3];
-        } else {
-            float* o = vv[set][g - 2];
-            float* q = rb[g - 2];
-            if (i < 4) q[i] = __builtin_fmaf(sB, q[4 + i], q[i]);
-            if (i == 4) o[0] = q[0] - q[2];
-            if (i == 5) o[1] = q[1] + q[2];
-            if (i == 6) o[2] = q[2] - q[1];
-            if (i == 7) o[3] = q[1] - q[3];
-        }
-    };
-    // position p = 0..15 of a phase -> what is built beside MFMA p (reads land two positions before their first use):
-    //   p 0-1 reads A0 | 2 reads A1 | 3 reads A1, ops A0 | 4 ops A0, reads B0 | 5-6 ops A1, reads B0 | 7 reads B0 |
-    //   8-11 ops B0, reads B1 | 12-15 ops B1            (two reads / two operations per position)
-    auto build_slot = [&](int nbuf, int s, int set, int p) {
-        auto rd2 = [&](int g, int i0) { rd_grp(nbuf, s, g, i0); rd_grp(nbuf, s, g, i0 + 1); };
-        auto op2 = [&](int g, int i0) { op_grp(set, g, i0); op_grp(set, g, i0 + 1); };
-        if (p == 0) rd2(0, 0);
-        else if (p == 1) rd2(0, 2);
-        else if (p == 2) rd2(1, 0);
-        else if (p == 3) { op2(0, 0); rd2(1, 2); }
-        else if (p == 4) { op2(0, 2); rd2(2, 0); }
-        else if (p == 5) { op2(1, 0); rd2(2, 2); }
-        else if (p == 6) { op2(1, 2); rd2(2, 4); }
-        else if (p == 7) rd2(2, 6);
-        else if (p < 12) { op2(2, 2 * (p - 8)); rd2(3, 2 * (p - 8)); }
-        else op2(3, 2 * (p - 12));
-    };
-
-    int cn = sp0 / per_img, ctx, cty;
-    {
-        const int rem = sp0 - cn * per_img;
-        ctx = rem / a.tilesY;
-        cty = rem - ctx * a.tilesY;
-    }
-    auto next_region = [&](int& n, int& tx, int& ty) {
-        const int ty1 = ty + 1, wy = ty1 == a.tilesY ? 1 : 0;
-        ty = wy ? 0 : ty1;
-        const int tx1 = tx + wy, wx = tx1 == a.tilesX ? 1 : 0;
-        tx = wx ? 0 : tx1;
-        n += wx;
-    };
-    if (my_tiles > 0) {
-        region_setup(cn, ctx, cty);
-#pragma unroll
-        for (int j = 0; j < LD; ++j) issue_d(j);
-#pragma unroll
-        for (int j = 0; j < LX; ++j) issue_x(j);
-#pragma unroll
-        for (int j = 0; j < LD; ++j) commit_d(j, 0);
-#pragma unroll
-        for (int j = 0; j < LX; ++j) commit_x(j, 0);
-        __syncthreads();
-#pragma unroll
-        for (int p = 0; p < 16; ++p) build_slot(0, 0, 0, p);
-    }
-    int ln = cn, ltx = ctx, lty = cty, lcount = 0;
-    auto load_advance = [&]() {
-        if (lcount + 1 < my_tiles) { next_region(ln, ltx, lty); ++lcount; once_v = 1.f; } else once_v = 0.f;
-        region_setup(ln, ltx, lty);
-    };
-    if (my_tiles > 0) {
-        load_advance();
-#pragma unroll
-        for (int j = 0; j < LD; ++j) issue_d(j);
-    }
-
-    // One phase = the 16 MFMAs of k-step s (operand set SET) + the build of the next k-step's operands (set SET ^ 1) from
-    // buffer NB + what LOADS says: 0 commit dY, 1 issue X, 2 commit X (all of the next region), 3 issue dY of the one after it
-    auto phase = [&](auto SET, auto SNEXT, auto NBUF, auto DBUFW, auto LOADS) {
-        constexpr int set = decltype(SET)::value, sn = decltype(SNEXT)::value, nbuf = decltype(NBUF)::value;
-        constexpr int wbuf = decltype(DBUFW)::value, loads = decltype(LOADS)::value;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb) {
-                    const int p = c * 4 + mb * 2 + nb;
-                    acc[c][mb][nb] = MFMA16(dm[set][mb][c], vv[set][nb][c], acc[c][mb][nb]);
-                    build_slot(nbuf, sn, set ^ 1, p);
-                    if (loads == 0 && p >= 8 && p < 8 + LD) commit_d(p - 8, wbuf);
-                    if (loads == 1 && p >= 2 && p < 2 + 2 * LX && (p - 2) % 2 == 0) issue_x((p - 2) / 2);
-                    if (loads == 2 && p >= 8 && p < 8 + LX) commit_x(p - 8, wbuf);
-                    if (loads == 3 && p >= 2 && p < 2 + 2 * LD && (p - 2) % 2 == 0) issue_d((p - 2) / 2);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    auto region = [&](auto BUF) {
-        constexpr int b = decltype(BUF)::value;
-        using B = std::integral_constant<int, b>;
-        using NB = std::integral_constant<int, b ^ 1>;
-        phase(I0{}, I1{}, B{}, NB{}, I0{});
-        phase(I1{}, I2{}, B{}, NB{}, I1{});
-        phase(I0{}, I3{}, B{}, NB{}, I2{});
-        __syncthreads();
-        load_advance();
-        phase(I1{}, I0{}, NB{}, B{}, I3{});
-    };
-    for (int g = 0; g < my_tiles; g += 2) {
-        region(I0{});
-        if (g + 1 < my_tiles) region(I1{});
-    }
-
-    // ---- fold: the two K halves and the four xi rows meet in LDS, one co block (16 couts) per round ----
-    __syncthreads();
-    float* red = smem;                     // [kh][r][c][16 co][32 ci] = 64 KB
-    if (do_bias) {                         // threads with equal (tid & 7) hold the same 4 couts
-        *(float4*)&red[tid * 4] = bsum;
-        __syncthreads();
-        if (tid < 32) {
-            const int cq = tid >> 2, comp = tid & 3;
-            float sum = 0.f;
-            for (int i = 0; i < 64; ++i) sum += red[(i * 8 + cq) * 4 + comp];
-            a.bias_part[(size_t)sblk * Cout + co_base + tid] = sum;
-        }
-        __syncthreads();
-    }
-    int fold_w = ((kh * 4 + r) * 4 * 16 + 4 * (lane >> 4)) * 32 + idx, fold_r = tid;
-    asm volatile("" : "+v"(fold_w), "+v"(fold_r));
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    red[fold_w + c * 512 + q * 32 + nb * 16] = acc[c][mb][nb][q];
-        __syncthreads();
-        {
-            const int e = fold_r;          // (co16, ci32) = (tid >> 5, tid & 31)
-            float tcol[3][4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float u[4];
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) {
-                    const float t = red[((0 * 4 + rr) * 4 + c) * 512 + e] + red[((1 * 4 + rr) * 4 + c) * 512 + e];
-                    u[rr] = ((rr == 3) != (c == 3)) ? -t : t;
-                }
-                tcol[0][c] = u[0] + 0.5f * (u[1] + u[2]);
-                tcol[1][c] = 0.5f * (u[1] - u[2]);
-                tcol[2][c] = u[3] + 0.5f * (u[1] + u[2]);
-            }
-            const int co = co_base + mb * 16 + (tid >> 5), ci = ci_base + (tid & 31);
-            float* o = a.part + (size_t)sblk * Cout * 9 * Cin + ((size_t)co * 9) * Cin + ci;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const float t0 = tcol[ky][0], t1 = tcol[ky][1], t2 = tcol[ky][2], t3 = tcol[ky][3];
-                o[(ky * 3 + 0) * Cin] = t0 + 0.5f * (t1 + t2);
-                o[(ky * 3 + 1) * Cin] = 0.5f * (t1 - t2);
-                o[(ky * 3 + 2) * Cin] = t3 + 0.5f * (t1 + t2);
-            }
-        }
-        __syncthreads();
-    }
-}
-
 }  // namespace
 
-// one full-resolution source or two sources [up2x?(a) | b] with 32-channel-aligned widths; whole regions (4 x 32 or 8 x 16 pixels)
-static bool wgrad_sources_ok(int C0, int C1, int up0, int H, int W) {
-    if (C1 == 0) return !up0 && C0 % 32 == 0;          // (a single up-sampled source has the nine-product kernel)
-    return C0 % 32 == 0 && C1 % 32 == 0 && (!up0 || (H % 2 == 0 && W % 2 == 0));
+// Which block shape serves a layer: MB = 4 co blocks per workgroup whenever Cout % 64 == 0 (whole regions of 4 x 32 or 8 x 16
+// pixels), 2 for Cout % 64 == 32 on maps whose width is a multiple of 32, 0: none (the generic kernel of conv_wino.hip).
+// Sources: one at full resolution or two [up2x?(a) | b] with 32-channel-aligned widths (a ci block never straddles them).
+static int wgrad_blk_mb(int C0, int C1, int up0, int Cout, int H, int W) {
+    if (C1 == 0 ? (up0 || C0 % 32 != 0)            // (a single up-sampled source has the nine-product kernel)
+                : (C0 % 32 != 0 || C1 % 32 != 0 || (up0 && (H % 2 != 0 || W % 2 != 0)))) return 0;
+    if (Cout % 64 == 0) return (W % 16 == 0 && H % (W % 32 == 0 ? 4 : 8) == 0) ? 4 : 0;
+    return (Cout % 32 == 0 && W % 32 == 0 && H % 4 == 0) ? 2 : 0;
 }
-bool conv_wino64_wgrad_ok(int C0, int C1, int up0, int Cout, int H, int W) {
-    if (!wgrad_sources_ok(C0, C1, up0, H, W) || Cout % 64 != 0 || W % 16 != 0) return false;
-    return H % (W % 32 == 0 ? 4 : 8) == 0;
+bool conv_wino_blk_wgrad_ok(int C0, int C1, int up0, int Cout, int H, int W) { return wgrad_blk_mb(C0, C1, up0, Cout, H, W) != 0; }
+// the weight gradient of a dilation-2 layer = the plain one summed over the four phase images of x and dy (see W64Args):
+// the pitched (MB = 2) form only
+bool conv_wino_blk_wgrad_dil2_ok(int C0, int Cout, int H, int W) {
+    return H % 2 == 0 && W % 2 == 0 && wgrad_blk_mb(C0, 0, 0, Cout, H / 2, W / 2) == 2;
 }
-int conv_wino64_wgrad_blocks(int Cin, int Cout, int N, int H, int W, int max_slabs, int* kt_out) {
-    const int nblk = (Cout / 64) * (Cin / 32);
+// (a dilation-2 layer: N, H, W of its phase images - 4 N, H / 2, W / 2)
+int conv_wino_blk_wgrad_blocks(int Cin, int Cout, int N, int H, int W, int max_slabs, int* kt_out) {
     const int rw = W % 32 == 0 ? 32 : 16;
-    const int nsp = N * (H / (128 / rw)) * (W / rw);
-    int nsb = conv_max_blocks() / nblk;
-    if (nsb > max_slabs) nsb = max_slabs;
-    if (nsb > nsp) nsb = nsp;
-    if (nsb < 1) nsb = 1;
-    const int kt = ceil_div(nsp, nsb);
-    if (kt_out) *kt_out = kt;
-    return ceil_div(nsp, kt);
+    return conv_slab_split(N * (H / (128 / rw)) * (W / rw), (Cout / (Cout % 64 == 0 ? 64 : 32)) * (Cin / 32), max_slabs, kt_out);
 }
-static void wgrad_dense(W64WgArgs& a) {
-    a.img_px = (unsigned)(a.H * a.W); a.rowb_px = 0; a.rpx = (unsigned)a.W; a.ppx = 1; a.n_sh = 0; a.n_m = 0;
+template <int RW, int MB>
+static int launch_wgrad_blk(const W64WgArgs& a, int nsb, hipStream_t st) {
+    if (int rc = lds_opt_in<k_conv_wino_wgrad_blk<RW, MB>>(160 * 1024, "conv_wino_blk_wgrad")) return rc;
+    k_conv_wino_wgrad_blk<RW, MB><<<a.nblk * nsb, 512, WgGeo<RW, MB>::LDS_BYTES, st>>>(a);
+    VQW_LAUNCH_CHECK("conv_wino_blk_wgrad");
+    return VQW_OK;
 }
-static void wgrad_sources(W64WgArgs& a, const ConvIn& in, long P) {
-    wgrad_dense(a);
+// nsb, kt: from conv_wino_blk_wgrad_blocks
+int conv_wino_blk_wgrad(const ConvIn& in, const float* dy, float* ws, float* bpart, int N, int H, int W, int Cin, int Cout, int nsb, int kt,
+                        hipStream_t st, int dil) {
+    const long P = (long)N * H * W;
+    W64WgArgs a;
+    a.dy = dy; a.part = ws; a.bias_part = bpart;
+    a.Cin = Cin; a.Cout = Cout;
     a.x = in.src0; a.x1 = in.C1 ? in.src1 : in.src0; a.C0 = in.C0; a.up0 = in.C1 ? in.up0 : 0;
     a.nbx = (unsigned)((a.up0 ? P / 4 : P) * in.C0 * 4);
     a.nbx1 = (unsigned)(P * in.C1 * 4);
-}
-int conv_wino64_wgrad(const ConvIn& in, const float* dy, float* ws, float* bpart, int N, int H, int W, int Cin, int Cout, int nsb, int kt,
-                      hipStream_t st) {
-    const int rw = W % 32 == 0 ? 32 : 16;
-    const size_t lds = (size_t)2 * (rw == 32 ? WgGeo<32>::DBUF + WgGeo<32>::XBUF : WgGeo<16>::DBUF + WgGeo<16>::XBUF) * sizeof(float);
-    static_assert((size_t)2 * (WgGeo<32>::DBUF + WgGeo<32>::XBUF) * sizeof(float) <= 160 * 1024, "wgrad tiles do not fit the LDS");
-    static_assert((size_t)2 * (WgGeo<16>::DBUF + WgGeo<16>::XBUF) * sizeof(float) >= 64 * 1024, "the fold needs 64 KB");
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_conv_wino_wgrad64<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_conv_wino_wgrad64<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            vqw_set_error("conv_wino64_wgrad: cannot raise the dynamic LDS limit");
-            return VQW_ERR_HIP;
-        }
-        attr_set = true;
+    a.nbd = (unsigned)(P * Cout * 4);
+    a.img_px = (unsigned)(H * W); a.rowb_px = 0; a.rpx = (unsigned)W; a.ppx = 1; a.n_sh = 0; a.n_m = 0;
+    if (dil == 2) {
+        a.rowb_px = (unsigned)W; a.rpx = 2u * (unsigned)W; a.ppx = 2; a.n_sh = 2; a.n_m = 1;
+        N *= 4; H /= 2; W /= 2;
     }
-    const long P = (long)N * H * W;
-    W64WgArgs a;
-    a.dy = dy; a.part = ws; a.bias_part = bpart;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+    a.N = N; a.H = H; a.W = W;
+    const int rw = W % 32 == 0 ? 32 : 16, mb = Cout % 64 == 0 ? 4 : 2;
     a.tilesY = H / (128 / rw); a.tilesX = W / rw; a.nsp = N * a.tilesY * a.tilesX;
-    a.n_ci_b = Cin / 32; a.nblk = (Cout / 64) * a.n_ci_b; a.kt = kt;
-    wgrad_sources(a, in, P);
-    a.nbd = (unsigned)(P * Cout * 4);
-    if (rw == 32) k_conv_wino_wgrad64<32><<<a.nblk * nsb, 512, lds, st>>>(a);
-    else k_conv_wino_wgrad64<16><<<a.nblk * nsb, 512, lds, st>>>(a);
-    VQW_LAUNCH_CHECK("conv_wino64_wgrad");
-    return VQW_OK;
-}
-
-// (32 co x 32 ci) blocks: Cout a multiple of 32 but not of 64 (those take the 64-cout kernel), one full-resolution source,
-// 32-pixel-wide whole regions (4 x 32 pixels).
-bool conv_wino32_wgrad_ok(int C0, int C1, int up0, int Cout, int H, int W) {
-    if (!wgrad_sources_ok(C0, C1, up0, H, W) || Cout % 32 != 0 || Cout % 64 == 0 || W % 32 != 0) return false;
-    return H % 4 == 0;
-}
-int conv_wino32_wgrad_blocks(int Cin, int Cout, int N, int H, int W, int max_slabs, int* kt_out) {
-    const int nblk = (Cout / 32) * (Cin / 32);
-    const int nsp = N * (H / 4) * (W / 32);
-    int nsb = conv_max_blocks() / nblk;
-    if (nsb > max_slabs) nsb = max_slabs;
-    if (nsb > nsp) nsb = nsp;
-    if (nsb < 1) nsb = 1;
-    const int kt = ceil_div(nsp, nsb);
-    if (kt_out) *kt_out = kt;
-    return ceil_div(nsp, kt);
-}
-// the weight gradient of a dilation-2 layer = the plain one summed over the four phase images of x and dy (see W64Args)
-bool conv_wino32_wgrad_dil2_ok(int C0, int Cout, int H, int W) {
-    return H % 2 == 0 && W % 2 == 0 && conv_wino32_wgrad_ok(C0, 0, 0, Cout, H / 2, W / 2);
-}
-int conv_wino32_wgrad(const ConvIn& in, const float* dy, float* ws, float* bpart, int N, int H, int W, int Cin, int Cout, int nsb, int kt,
-                      hipStream_t st, int dil) {
-    constexpr size_t lds = (size_t)2 * (WhGeo::DBUF + WhGeo::XBUF) * sizeof(float);
-    static_assert(lds <= 160 * 1024 && lds >= 64 * 1024, "the fold needs 64 KB");
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_conv_wino_wgrad32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            vqw_set_error("conv_wino32_wgrad: cannot raise the dynamic LDS limit");
-            return VQW_ERR_HIP;
-        }
-        attr_set = true;
-    }
-    const long P = (long)N * H * W;
-    W64WgArgs a;
-    a.dy = dy; a.part = ws; a.bias_part = bpart;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    wgrad_sources(a, in, P);
-    if (dil == 2) {        // (nsb, kt: from conv_wino32_wgrad_blocks(Cin, Cout, 4 N, H / 2, W / 2, ..))
-        a.img_px = (unsigned)(H * W); a.rowb_px = (unsigned)W; a.rpx = 2u * (unsigned)W; a.ppx = 2; a.n_sh = 2; a.n_m = 1;
-        a.N = 4 * N; a.H = H / 2; a.W = W / 2;
-    }
-    a.tilesY = a.H / 4; a.tilesX = a.W / 32; a.nsp = a.N * a.tilesY * a.tilesX;
-    a.n_ci_b = Cin / 32; a.nblk = (Cout / 32) * a.n_ci_b; a.kt = kt;
-    a.nbd = (unsigned)(P * Cout * 4);
-    k_conv_wino_wgrad32<<<a.nblk * nsb, 512, lds, st>>>(a);
-    VQW_LAUNCH_CHECK("conv_wino32_wgrad");
-    return VQW_OK;
+    a.n_ci_b = Cin / 32; a.nblk = (Cout / (16 * mb)) * a.n_ci_b; a.kt = kt;
+    if (mb == 2) return launch_wgrad_blk<32, 2>(a, nsb, st);
+    return rw == 32 ? launch_wgrad_blk<32, 4>(a, nsb, st) : launch_wgrad_blk<16, 4>(a, nsb, st);
 }

@@ -163,16 +163,9 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
     const unsigned u_cstride = 9u * Cin * 32u;         // per 8-channel chunk
 
     float4 rh[LH], ru[LU];
-    auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
-        u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, (int)soff, 0);
-        float4 f;
-        unsigned a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];
-        f.x = __uint_as_float(a0); f.y = __uint_as_float(a1); f.z = __uint_as_float(a2); f.w = __uint_as_float(a3);
-        return f;
-    };
-    auto issue_h = [&](int j, int chunk) { rh[j] = ld4(rsd, h_voff[j], chunk * 32); };
+    auto issue_h = [&](int j, int chunk) { rh[j] = buf_ld4(rsd, h_voff[j], chunk * 32); };
     // (readfirstlane: left alone the compiler multiplies in a VGPR and wraps the load in a waterfall loop)
-    auto issue_u = [&](int j, int chunk) { ru[j] = ld4(rsu, u_voff[j], __builtin_amdgcn_readfirstlane(chunk * u_cstride)); };
+    auto issue_u = [&](int j, int chunk) { ru[j] = buf_ld4(rsu, u_voff[j], __builtin_amdgcn_readfirstlane(chunk * u_cstride)); };
     auto commit_h = [&](int j, int buf) {
         float* p = smem + buf * HBUF + h_lds[j];
         f32x2 lo, hi;
@@ -206,7 +199,6 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
 
     // ---- fragments: lane (tile m = lane & 15, channel pair q = lane >> 4); wave = tile row ----
     const int m = lane & 15, q = lane >> 4;
-    auto opaque = [](int x) { asm volatile("" : "+v"(x)); return x; };
     int a_row[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) a_row[r] = opaque(((2 * wv + r) * HWS + 2 * m) * WU_KPH + 2 * q);
@@ -439,15 +431,8 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
     const unsigned u_cstride = 9u * Cout * 32u;
 
     float4 rh, ru[LU];
-    auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
-        u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, (int)soff, 0);
-        float4 f;
-        unsigned a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];
-        f.x = __uint_as_float(a0); f.y = __uint_as_float(a1); f.z = __uint_as_float(a2); f.w = __uint_as_float(a3);
-        return f;
-    };
-    auto issue_h = [&](int chunk) { rh = ld4(rsx, h_voff, chunk * 32); };
-    auto issue_u = [&](int j, int chunk) { ru[j] = ld4(rsu, u_voff[j], __builtin_amdgcn_readfirstlane(chunk * u_cstride)); };
+    auto issue_h = [&](int chunk) { rh = buf_ld4(rsx, h_voff, chunk * 32); };
+    auto issue_u = [&](int j, int chunk) { ru[j] = buf_ld4(rsu, u_voff[j], __builtin_amdgcn_readfirstlane(chunk * u_cstride)); };
     auto commit_h = [&](int buf) { *(float4*)&smem[buf * HBUF + h_lds] = rh; };
     auto commit_u = [&](int j, int buf) { *(float4*)&smem[u_lds[j] + buf * UBUF] = ru[j]; };
 
@@ -475,7 +460,6 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
 
     // ---- fragments: lane (tile m = lane & 15 = low-resolution column, channel pair q = lane >> 4); wave = tile row ----
     const int m = lane & 15, q = lane >> 4;
-    auto opaque = [](int x) { asm volatile("" : "+v"(x)); return x; };
     int a_row[3];                      // f32x2 units
 #pragma unroll
     for (int r = 0; r < 3; ++r) a_row[r] = opaque((((wv + r) * LWS + m) * WF_KPH + 2 * q) / 2);
@@ -708,7 +692,6 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_wgrad(WUpWgArgs a) {
     const int co_base = (blk / a.n_ci_b) * 32, ci_base = (blk % a.n_ci_b) * 32;
     const int sp0 = sblk * a.kt;
     const int my_tiles = min(a.kt, a.nsp - sp0);
-    const int per_img = a.tilesY * a.tilesX;
     const bool do_bias = a.bias_part != nullptr && ci_base == 0;
 
     // ---- loader slots ----
@@ -733,13 +716,6 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_wgrad(WUpWgArgs a) {
     float4 rd[4], rx[LX];
     float4 bsum;
     bsum.x = bsum.y = bsum.z = bsum.w = 0.f;
-    auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
-        u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, (int)soff, 0);
-        float4 f;
-        unsigned a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];
-        f.x = __uint_as_float(a0); f.y = __uint_as_float(a1); f.z = __uint_as_float(a2); f.w = __uint_as_float(a3);
-        return f;
-    };
     __amdgpu_buffer_rsrc_t rsd, rsx;
     unsigned x_edges = 0;
     auto region_setup = [&](int n, int tx, int ty) {      // region = full-res rows 8 ty .., columns 32 tx ..; low-res rows 4 ty .., columns 16 tx ..
@@ -752,10 +728,10 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_wgrad(WUpWgArgs a) {
         rsx = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.x + xoff), 0, (int)(unsigned)(xleft > 0xFFFFFFF0L ? 0xFFFFFFF0L : xleft), 0x00020000);
         x_edges = ((ty == 0 ? 1u : 0u) | (4 * ty + 4 >= h ? 2u : 0u) | (tx == 0 ? 4u : 0u) | (16 * tx + 16 == w ? 8u : 0u)) * 0x11u;
     };
-    auto issue_d = [&](int j) { rd[j] = ld4(rsd, d_fix, j * d_jstride); };
+    auto issue_d = [&](int j) { rd[j] = buf_ld4(rsd, d_fix, j * d_jstride); };
     auto issue_x = [&](int j) {
         const unsigned vo = (x_bits & x_edges & (0xFu << (4 * j))) ? 0xFFFFFFFFu : x_fix[j];
-        rx[j] = ld4(rsx, vo, 0);
+        rx[j] = buf_ld4(rsx, vo, 0);
     };
     float once_v = 1.f;
     auto commit_d = [&](int j, int buf) {
@@ -770,7 +746,6 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_wgrad(WUpWgArgs a) {
     // ---- fragment addressing: lane (channel idx = lane & 15, tile k = lane >> 4 of the k-step) ----
     // k-step s of the wave: tile row trow, tile columns 8 thalf + 4 s + k
     const int idx = lane & 15, k = lane >> 4;
-    auto opaque = [](int x) { asm volatile("" : "+v"(x)); return x; };
     const int a_0 = opaque(((2 * trow) * 32 + 2 * (8 * thalf + k)) * WW_DP + idx);            // dY row 2 trow: + s * 8 px, + b px, + cb * 16
     const int a_1 = opaque(((2 * trow + 1) * 32 + 2 * (8 * thalf + k)) * WW_DP + idx);
     int x_r[3];
@@ -841,22 +816,11 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_wgrad(WUpWgArgs a) {
     };
 
     // ---- region cursors ----
-    int cn = sp0 / per_img, ctx, cty;
-    {
-        const int rem = sp0 - cn * per_img;
-        ctx = rem / a.tilesY;
-        cty = rem - ctx * a.tilesY;
-    }
-    auto next_region = [&](int& n, int& tx, int& ty) {
-        const int ty1 = ty + 1, wy = ty1 == a.tilesY ? 1 : 0;
-        ty = wy ? 0 : ty1;
-        const int tx1 = tx + wy, wx = tx1 == a.tilesX ? 1 : 0;
-        tx = wx ? 0 : tx1;
-        n += wx;
-    };
+    int cn, ctx, cty;
+    region_start(sp0, a.tilesY, a.tilesX, cn, ctx, cty);
     int ln = cn, ltx = ctx, lty = cty, lcount = 0;
     auto load_advance = [&]() {
-        if (lcount + 1 < my_tiles) { next_region(ln, ltx, lty); ++lcount; once_v = 1.f; } else once_v = 0.f;
+        if (lcount + 1 < my_tiles) { region_next(a.tilesY, a.tilesX, ln, ltx, lty); ++lcount; once_v = 1.f; } else once_v = 0.f;
         region_setup(ln, ltx, lty);
     };
     if (my_tiles > 0) {
@@ -997,14 +961,7 @@ template <int NBW, bool ACC>
 static int launch_up_dgrad(WUpDgArgs& a, hipStream_t st) {
     constexpr size_t lds = (size_t)(2 * 18 * 34 * WU_KPH + 2 * 9 * 16 * NBW * 8) * sizeof(float);
     static_assert(lds <= 160 * 1024, "buffers do not fit the 160 KB LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_conv_wino_up_dgrad<NBW, ACC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            vqw_set_error("conv_wino_up_dgrad: cannot raise the dynamic LDS limit");
-            return VQW_ERR_HIP;
-        }
-        attr_set = true;
-    }
+    if (int rc = lds_opt_in<k_conv_wino_up_dgrad<NBW, ACC>>(160 * 1024, "conv_wino_up_dgrad")) return rc;
     a.ntn = a.Cin / (16 * NBW);
     int groups = conv_max_blocks() / a.ntn;
     if (groups < 1) groups = 1;
@@ -1070,14 +1027,8 @@ bool conv_wino_up_wgrad_ok(int Cin, int Cout, int N, int h, int w) {
     return P * (Cin > Cout ? Cin : Cout) * 4 <= 0xFFFFFFE0L;
 }
 static int wup_wgrad_blocks(int Cin, int Cout, int N, int h, int w, int* kt_out) {
-    const int nblk = (Cout / 32) * (Cin / 32);
     const int nsp = N * (h / 4) * (w / 16);
-    int nsb = conv_max_blocks() / nblk;
-    if (nsb > nsp) nsb = nsp;
-    if (nsb < 1) nsb = 1;
-    const int kt = ceil_div(nsp, nsb);
-    if (kt_out) *kt_out = kt;
-    return ceil_div(nsp, kt);
+    return conv_slab_split(nsp, (Cout / 32) * (Cin / 32), nsp, kt_out);      // (no cap of its own)
 }
 size_t conv_wino_up_wgrad_ws_floats(int Cin, int Cout, int N, int h, int w) {
     return (size_t)wup_wgrad_blocks(Cin, Cout, N, h, w, nullptr) * ((size_t)Cout * 9 * Cin + Cout);
@@ -1086,14 +1037,7 @@ int conv_wino_up_wgrad(const float* x_low, const float* dy, float* dw, float* db
                        int acc, hipStream_t st) {
     constexpr size_t lds = (size_t)(2 * 256 * WW_DP + 2 * 6 * 18 * WW_XP) * sizeof(float);
     static_assert(lds <= 160 * 1024 && lds >= 36 * 1024, "wgrad tiles / fold area");
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_conv_wino_up_wgrad, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            vqw_set_error("conv_wino_up_wgrad: cannot raise the dynamic LDS limit");
-            return VQW_ERR_HIP;
-        }
-        attr_set = true;
-    }
+    if (int rc = lds_opt_in<k_conv_wino_up_wgrad>(160 * 1024, "conv_wino_up_wgrad")) return rc;
     int kt = 1;
     const int nsb = wup_wgrad_blocks(Cin, Cout, N, h, w, &kt);
     const long nout = (long)Cout * 9 * Cin;

@@ -1,4 +1,4 @@
-// Device helpers shared by the MFMA convolution kernels (conv_mfma.hip, conv_halo.hip).
+// Device helpers shared by the MFMA convolution kernels (conv_mfma.hip, conv_halo.hip, conv_dil.hip, conv_wino*.hip).
 #pragma once
 #include "common.h"
 
@@ -21,8 +21,9 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p, unsigned nbytes) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, nbytes, 0x00020000);
 }
-__device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0);
+// (soff: a wave-uniform byte offset added after the range check of byte_off)
+__device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, unsigned soff = 0) {
+    u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, (int)soff, 0);
     float4 f;     // (index, then convert: __builtin_bit_cast on a vector element mis-reads element 0 with this clang)
     unsigned a = v[0], b = v[1], c = v[2], d = v[3];
     f.x = __uint_as_float(a); f.y = __uint_as_float(b); f.z = __uint_as_float(c); f.w = __uint_as_float(d);
@@ -33,6 +34,27 @@ __device__ __forceinline__ void buf_st4(__amdgpu_buffer_rsrc_t r, unsigned byte_
     u32x4 v;
     v[0] = __float_as_uint(f.x); v[1] = __float_as_uint(f.y); v[2] = __float_as_uint(f.z); v[3] = __float_as_uint(f.w);
     __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)byte_off, 0, 0);
+}
+
+// A value the compiler cannot see through: LDS base addresses kept in registers of their own (no ds_read2 merging, no
+// re-derivation from a common base inside an MFMA loop).
+__device__ __forceinline__ int opaque(int x) { asm volatile("" : "+v"(x)); return x; }
+
+// Walk over the regions of a tensor in the order (image, region column, region row): the cursor of region number sp, and its
+// successor.  tilesY / tilesX = regions per image column / row.
+__device__ __forceinline__ void region_start(int sp, int tilesY, int tilesX, int& n, int& tx, int& ty) {
+    const int per_img = tilesY * tilesX;
+    n = sp / per_img;
+    const int rem = sp - n * per_img;
+    tx = rem / tilesY;
+    ty = rem - tx * tilesY;
+}
+__device__ __forceinline__ void region_next(int tilesY, int tilesX, int& n, int& tx, int& ty) {
+    const int ty1 = ty + 1, wy = ty1 == tilesY ? 1 : 0;
+    ty = wy ? 0 : ty1;
+    const int tx1 = tx + wy, wx = tx1 == tilesX ? 1 : 0;
+    tx = wx ? 0 : tx1;
+    n += wx;
 }
 
 // A select between two values that are both evaluated.  Written as `c ? f(x) : k` the address arithmetic of f lands in

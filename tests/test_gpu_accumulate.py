@@ -138,12 +138,18 @@ WG_CASES = [
     ("wino", (1, 24, 32, 16, 32, False, 32, 3, 1, True, False), True, False),
     # Winograd form, (64 x 32)-block kernel: Cout % 64 == 0, C0 % 32 == 0, W % 32 == 0, H % 4 == 0
     ("wino64", (2, 16, 32, 64, 0, False, 64, 3, 1, True, False), True, False),
+    # ... with an odd number of regions in a workgroup's run (the skipped second region of the last pair, a short last run).
+    # wg9_split_blocks caps the slabs at max(P / 256, 1), a region is 128 pixels, one (co, ci) block:
+    # W = 32, H = 20: 5 regions of 4 x 32, cap 640 / 256 = 2 -> kt = ceil(5 / 2) = 3: runs of 3 and 2 regions;
+    # W = 16, H = 24 (H % 8 == 0): 3 regions of 8 x 16, cap 384 / 256 = 1 -> kt = 3: one run of 3 regions
+    ("wino64", (1, 20, 32, 32, 0, False, 64, 3, 1, True, False), True, False),
+    ("wino64", (1, 24, 16, 32, 0, False, 64, 3, 1, True, False), True, False),
     # Winograd form, (32 x 32)-block kernel: Cout % 64 == 32, sources % 32 == 0, W % 32 == 0, H % 4 == 0; two sources, the first
     # up-sampled; three co blocks; no bias
     ("wino32", (2, 32, 32, 64, 32, True, 32, 3, 1, True, False), True, False),
     ("wino32", (3, 64, 64, 32, 0, False, 96, 3, 1, True, False), True, False),
     ("wino32", (2, 12, 96, 64, 0, False, 32, 3, 1, False, False), True, False),
-    # dilation 2 on the four phase images (conv_wino32_wgrad_dil2_ok: the (32 x 32)-block predicate at H / 2, W / 2)
+    # dilation 2 on the four phase images (conv_wino_blk_wgrad_dil2_ok: the (32 x 32)-block predicate at H / 2, W / 2)
     ("wino-dil2", (2, 16, 64, 32, 0, False, 32, 3, 2, True, False), True, False),
     # vqw_conv3x3_up2_wgrad, k_conv_wgrad_up + k_reduce_wgup: Cout = 16 / 48 keeps the nine-product form away (Cout % 32 != 0).
     # (CONV_CASES lists (1, 40, 32, 64 -> 16) with the nine-product FORWARD; its weight gradient is this kernel, and (2, 32, 32,

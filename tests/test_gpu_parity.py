@@ -84,6 +84,10 @@ CONV_CASES = [
     (1, 20, 16, 128, 0, False, 64, 3, 1, True, False),
     (1, 256, 320, 16, 0, False, 64, 3, 1, True, False),
     (2, 22, 32, 64, 0, False, 16, 3, 1, False, False),     # its input gradient: 16 -> 64
+    # (64 co x 32 ci)-block Winograd weight gradient with an odd number of regions per workgroup (the slab cap of the weight
+    # gradient is P / 256, a region is 128 pixels): 5 regions of 4 x 32 pixels as runs of 3 and 2; 3 regions of 8 x 16 as one run
+    (1, 20, 32, 32, 0, False, 64, 3, 1, True, False),
+    (1, 24, 16, 32, 0, False, 64, 3, 1, True, False),
     # (32 co x 32 ci)-block Winograd weight gradient (round 4: Cout % 64 == 32, Cin % 32 == 0, W % 32 == 0, H % 4 == 0): three co
     # blocks, several regions per workgroup and images, an odd number of regions, no bias
     (3, 64, 64, 32, 0, False, 96, 3, 1, True, False),
