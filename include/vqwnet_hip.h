@@ -421,9 +421,12 @@ int vqw_hinge_bwd(const float* x, long n, int mode, const float* gloss, float* g
 /* ---- ActNorm and spectral normalisation of the discriminator (networks/actnorm.py:23-70, utils/__init__.py:54-64 =
  * torch.nn.utils.spectral_norm defaults: one power iteration, eps 1e-12, dim 0).
  * ActNorm runs on the vqw_bn_affine_* kernels with mean = -loc, rstd = 1, gamma = scale, beta = 0: vqw_actnorm_prepare writes
- * mean_rstd_beta = [C][2] {-loc, 1} followed by [C] zeros; with `sums` ([C][2] doubles of vqw_bn_partial_stats over `count`
+ * mean_rstd_beta = [C][2] {-loc, 1} followed by [C] zeros; with `sums` ([C][2] doubles of vqw_actnorm_stats over `count`
  * pixels, the first training forward) it first sets loc = -mean, scale = 1 / (unbiased std + 1e-6) and initialized[0] = 1.
+ * vqw_actnorm_stats: sums[c] = {sum x, sum x^2} over the P pixels of an NHWC tensor with every square and addition in double
+ * (ActNorm divides by the std itself: the fp32 squares of vqw_bn_partial_stats are not exact enough for it).
  * vqw_actnorm_loc_grad: dloc = scale * dbeta. */
+int vqw_actnorm_stats(const float* x, double* sums /*[C][2]*/, long P, int C, void* stream);
 int vqw_actnorm_prepare(const double* sums /*[C][2] or NULL*/, double count, float* loc, float* scale,
                         unsigned char* initialized /*[1] or NULL*/, float* mean_rstd_beta /*[3C]*/, int C, void* stream);
 int vqw_actnorm_loc_grad(const float* dbeta, const float* scale, float* dloc, int C, void* stream);

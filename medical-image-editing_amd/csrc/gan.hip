@@ -15,10 +15,12 @@ namespace {
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
-// one thread per output element (pixel, co); adjacent threads = adjacent co
+// one thread per output element (pixel, co); adjacent threads = adjacent co.  vec4 (set by the host: Cin % 4 == 0 and x, w
+// 16-byte aligned, so every pixel / tap row is) reads the channels as float4; otherwise one float at a time
 __global__ void __launch_bounds__(256) k_sconv_fwd(const float* __restrict__ x, const float* __restrict__ w,
                                                    const float* __restrict__ bias, float* __restrict__ y, int N, int H, int W,
-                                                   int Ho, int Wo, int Cin, int Cout, int ks, int stride, int pad, float slope) {
+                                                   int Ho, int Wo, int Cin, int Cout, int ks, int stride, int pad, float slope,
+                                                   int vec4) {
     const int taps = ks * ks;
     long total = (long)N * Ho * Wo * Cout;
     long gstride = (long)gridDim.x * blockDim.x;
@@ -35,7 +37,7 @@ __global__ void __launch_bounds__(256) k_sconv_fwd(const float* __restrict__ x, 
             if ((unsigned)hy >= (unsigned)H || (unsigned)wx >= (unsigned)W) continue;
             const float* wr = w + ((long)co * taps + t) * Cin;
             const float* s = x + (((long)n * H + hy) * W + wx) * Cin;
-            if ((Cin & 3) == 0) {
+            if (vec4) {
                 for (int c = 0; c < Cin; c += 4) {
                     float4 a = *(const float4*)(s + c), b = *(const float4*)(wr + c);
                     acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc); acc = fmaf(a.z, b.z, acc); acc = fmaf(a.w, b.w, acc);
@@ -386,7 +388,9 @@ extern "C" int vqw_sconv_fwd(const float* x, const float* w_ohwi, const float* b
     } else if (ks == 4 && Cout == 1 && Cin % 4 == 0 && (((uintptr_t)x | (uintptr_t)w_ohwi) & 15) == 0) {
         k_sconv_fwd_o1<<<stream_grid(total * 64, 256), 256, 0, st>>>(x, w_ohwi, bias, y, N, H, W, Ho, Wo, Cin, stride, pad, slope);
     } else {
-        k_sconv_fwd<<<stream_grid(total, 256), 256, 0, st>>>(x, w_ohwi, bias, y, N, H, W, Ho, Wo, Cin, Cout, ks, stride, pad, slope);
+        const int vec4 = Cin % 4 == 0 && (((uintptr_t)x | (uintptr_t)w_ohwi) & 15) == 0;
+        k_sconv_fwd<<<stream_grid(total, 256), 256, 0, st>>>(x, w_ohwi, bias, y, N, H, W, Ho, Wo, Cin, Cout, ks, stride, pad, slope,
+                                                             vec4);
     }
     VQW_LAUNCH_CHECK("vqw_sconv_fwd");
     return VQW_OK;

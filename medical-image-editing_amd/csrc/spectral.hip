@@ -159,14 +159,49 @@ __global__ void __launch_bounds__(256) k_sn_bwd_apply(const SnGrad* __restrict__
 // ActNorm (networks/actnorm.py:23-70) on the BatchNorm-affine kernels: mean = -loc, rstd = 1, gamma = scale, beta = 0.
 // With `sums` (first training forward) the data-dependent initialisation comes first: loc = -mean, scale = 1 / (std + 1e-6),
 // std unbiased (torch.std), and the `initialized` flag is raised.
+//
+// The initialisation takes its sums from k_actnorm_stats, not from the statistics pass of norm.hip: that pass squares in fp32,
+// a relative error of 2^-24 per square which E[x^2] - mean^2 multiplies by (mean / std)^2.  BatchNorm divides by sqrt(var + eps)
+// and absorbs it; ActNorm divides by std + 1e-6, so a channel 1e3 standard deviations off zero got its scale 2e-4 ... 8e-4 wrong
+// from 126 pixels, and an exactly constant channel (x = 1.15: the fp32 square is 4.5e-8 above the exact one) a scale of 4.7e3
+// in place of 1 / 1e-6.  Here every square and every addition is a double, in a fixed order: a workgroup owns 64 channels
+// (lanes) x 16 pixel lanes and walks the whole batch.  It runs once per layer and training run.  sums[c] = {sum x, sum x^2}, the
+// [C][2] layout of vqw_bn_partial_stats, so a process group all-reduces it the same way.
+__global__ void __launch_bounds__(1024) k_actnorm_stats(const float* __restrict__ x, double* __restrict__ sums, long P, int C) {
+    __shared__ double sa[16][64], sb[16][64];
+    const int lc = threadIdx.x & 63, lp = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lc;
+    double a = 0.0, b = 0.0;
+    if (c < C) {
+        for (long p = lp; p < P; p += 16) {
+            const double v = (double)x[p * C + c];
+            a += v;
+            b += v * v;
+        }
+    }
+    sa[lp][lc] = a;
+    sb[lp][lc] = b;
+    __syncthreads();
+    if (lp == 0 && c < C) {
+        for (int k = 1; k < 16; ++k) {
+            a += sa[k][lc];
+            b += sb[k][lc];
+        }
+        sums[2 * c] = a;
+        sums[2 * c + 1] = b;
+    }
+}
+// var = E[x^2] - mean^2 from those double sums.  What their rounding leaves of an exactly constant channel (at most one part in
+// 2^53 per addition of a thread's chain) must come out 0: a variance within 2^-36 of E[x^2] - chains of 2^17 additions; a
+// channel with |mean| / std above 2^18 - is that residue.
 __global__ void k_actnorm_prepare(const double* __restrict__ sums, double count, float* __restrict__ loc, float* __restrict__ scale,
                                   unsigned char* __restrict__ initialized, float* __restrict__ mrb, int C) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     if (sums) {
-        const double mean = sums[2 * c] / count;
-        double var = sums[2 * c + 1] / count - mean * mean;
-        if (var < 0.0) var = 0.0;
+        const double mean = sums[2 * c] / count, ex2 = sums[2 * c + 1] / count;
+        double var = ex2 - mean * mean;
+        if (var <= 0x1p-36 * ex2) var = 0.0;
         if (count > 1.0) var *= count / (count - 1.0);
         loc[c] = -(float)mean;
         scale[c] = 1.f / ((float)sqrt(var) + 1e-6f);
@@ -204,6 +239,13 @@ extern "C" int vqw_spectral_norm_bwd(const void* grads_dev, int n_layers, int bl
     k_sn_bwd_dot<<<blocks, 256, 0, st>>>((const SnGrad*)grads_dev, n_layers);
     k_sn_bwd_apply<<<blocks, 256, 0, st>>>((const SnGrad*)grads_dev, n_layers);
     VQW_LAUNCH_CHECK("vqw_spectral_norm_bwd");
+    return VQW_OK;
+}
+
+extern "C" int vqw_actnorm_stats(const float* x, double* sums, long P, int C, void* stream) {
+    VQW_CHECK(x && sums && P > 0 && C > 0, "vqw_actnorm_stats: bad arguments");
+    k_actnorm_stats<<<ceil_div(C, 64), 1024, 0, (hipStream_t)stream>>>(x, sums, P, C);
+    VQW_LAUNCH_CHECK("vqw_actnorm_stats");
     return VQW_OK;
 }
 

@@ -2665,8 +2665,7 @@ class _ActNormLrelu(torch.autograd.Function):
         if initialized is not None:                    # data-dependent initialisation from this batch (first training forward)
             count = float(N * H * W)
             sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
-            ws = _ws(L.vqw_plane_ws_bytes(N, C, H * W), x)
-            L.vqw_bn_partial_stats(x, sums, ws, ws.numel(), N, H * W, C)
+            L.vqw_actnorm_stats(x, sums, N * H * W, C)  # exact squares: scale = 1 / (std + 1e-6) has no eps to hide behind
             if sync and _dist_on():                    # every rank initialises from the global batch
                 _all_reduce(sums)
                 count *= dist.get_world_size()
