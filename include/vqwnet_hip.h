@@ -490,6 +490,15 @@ int vqw_window_mse_fwd(const float* a, const float* b, float* loss, void* ws, si
 int vqw_window_mse_bwd(const float* a, const float* b, const float* gloss, float* ga, long n, float alpha, float beta,
                        float lo, float hi, void* stream);
 
+/* ---- window stack (trainers/multi_window_trainer.py:226-227): 1 <= nwin <= 3 re-windowed copies of x[n] from one read,
+ * o_w = clamp(alpha_w * x + beta_w, lo_w, hi_w) (one fma, one clamp) with win = the [nwin][4] DEVICE table of
+ * (alpha, beta, lo, hi) rows; a NULL o_w is skipped.  Backward: gx = sum over w, in window order, of
+ * g_w * (alpha_w where lo_w < alpha_w * x + beta_w < hi_w, else 0) (the vqw_window_mse_bwd convention); a NULL g_w
+ * contributes nothing and with all of them NULL gx is zero.  Pointers past nwin are ignored. */
+int vqw_window_stack_fwd(const float* x, const float* win, float* o0, float* o1, float* o2, int nwin, long n, void* stream);
+int vqw_window_stack_bwd(const float* x, const float* win, const float* g0, const float* g1, const float* g2, float* gx, int nwin,
+                         long n, void* stream);
+
 /* ---- focal frequency loss (ABI 9; the focal-frequency-loss package v0.3.0 as FFL(loss_weight, alpha) in
  *      trainers/base.py:277-278, single_window_trainer.py:117-136, 286-309, 453-466, multi_window_trainer.py:100-126).
  * pred, target: [N,H,W,C] cut into patch_factor^2 patches of h x w = H/pf x W/pf; per plane (n, patch, c)

@@ -418,6 +418,119 @@ extern "C" int vqw_window_mse_bwd(const float* a, const float* b, const float* g
     return VQW_OK;
 }
 
+// Window stack (trainers/multi_window_trainer.py:226-227): up to three re-windowed copies of one image from one read of it,
+// out_w = clamp(alpha_w * x + beta_w, lo_w, hi_w) with the rows (alpha, beta, lo, hi) of a device table - what the U-Net
+// discriminator sees of the reconstruction in a multi-window second step.  The gradient sums the windows in order, each with
+// the slope inside (lo, hi) and zero elsewhere (the k_window_mse_bwd convention).  A null output / gradient is skipped.
+struct WinRows {
+    float a[3], b[3], lo[3], hi[3];
+};
+__device__ __forceinline__ WinRows win_rows(const float* __restrict__ win, int nwin) {
+    WinRows r;
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+        const bool on = w < nwin;
+        r.a[w] = on ? win[4 * w] : 0.f;
+        r.b[w] = on ? win[4 * w + 1] : 0.f;
+        r.lo[w] = on ? win[4 * w + 2] : 0.f;
+        r.hi[w] = on ? win[4 * w + 3] : 0.f;
+    }
+    return r;
+}
+__device__ __forceinline__ float win_slope(float x, float g, float alpha, float beta, float lo, float hi, float acc) {
+    float z = fmaf(alpha, x, beta);
+    return fmaf(g, (z > lo && z < hi) ? alpha : 0.f, acc);
+}
+// n4: the number of float4 groups taken by the vector loop (0 when a pointer is not 16-byte aligned); the rest is scalar
+__global__ void __launch_bounds__(256) k_window_stack_fwd(const float* __restrict__ x, const float* __restrict__ win,
+                                                          float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2,
+                                                          int nwin, long n, long n4) {
+    const WinRows r = win_rows(win, nwin);
+    float* const o[3] = {o0, o1, o2};
+    const long stride = (long)gridDim.x * blockDim.x, t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long i = t; i < n4; i += stride) {
+        const float4 v = ((const float4*)x)[i];
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+            if (!o[w]) continue;
+            float4 y;
+            y.x = fminf(fmaxf(fmaf(r.a[w], v.x, r.b[w]), r.lo[w]), r.hi[w]);
+            y.y = fminf(fmaxf(fmaf(r.a[w], v.y, r.b[w]), r.lo[w]), r.hi[w]);
+            y.z = fminf(fmaxf(fmaf(r.a[w], v.z, r.b[w]), r.lo[w]), r.hi[w]);
+            y.w = fminf(fmaxf(fmaf(r.a[w], v.w, r.b[w]), r.lo[w]), r.hi[w]);
+            ((float4*)o[w])[i] = y;
+        }
+    }
+    for (long i = (n4 << 2) + t; i < n; i += stride) {
+        const float v = x[i];
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+            if (o[w]) o[w][i] = fminf(fmaxf(fmaf(r.a[w], v, r.b[w]), r.lo[w]), r.hi[w]);
+    }
+}
+__global__ void __launch_bounds__(256) k_window_stack_bwd(const float* __restrict__ x, const float* __restrict__ win,
+                                                          const float* __restrict__ g0, const float* __restrict__ g1,
+                                                          const float* __restrict__ g2, float* __restrict__ gx, int nwin, long n,
+                                                          long n4) {
+    const WinRows r = win_rows(win, nwin);
+    const float* const g[3] = {g0, g1, g2};
+    const long stride = (long)gridDim.x * blockDim.x, t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long i = t; i < n4; i += stride) {
+        const float4 v = ((const float4*)x)[i];
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+            if (!g[w]) continue;
+            const float4 gv = ((const float4*)g[w])[i];
+            acc.x = win_slope(v.x, gv.x, r.a[w], r.b[w], r.lo[w], r.hi[w], acc.x);
+            acc.y = win_slope(v.y, gv.y, r.a[w], r.b[w], r.lo[w], r.hi[w], acc.y);
+            acc.z = win_slope(v.z, gv.z, r.a[w], r.b[w], r.lo[w], r.hi[w], acc.z);
+            acc.w = win_slope(v.w, gv.w, r.a[w], r.b[w], r.lo[w], r.hi[w], acc.w);
+        }
+        ((float4*)gx)[i] = acc;
+    }
+    for (long i = (n4 << 2) + t; i < n; i += stride) {
+        const float v = x[i];
+        float acc = 0.f;
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+            if (g[w]) acc = win_slope(v, g[w][i], r.a[w], r.b[w], r.lo[w], r.hi[w], acc);
+        gx[i] = acc;
+    }
+}
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+extern "C" int vqw_window_stack_fwd(const float* x, const float* win, float* o0, float* o1, float* o2, int nwin, long n,
+                                    void* stream) {
+    VQW_CHECK(x && win && nwin >= 1 && nwin <= 3 && n > 0, "vqw_window_stack_fwd: bad arguments (nwin=%d, n=%ld)", nwin, n);
+    float* o[3] = {o0, nwin > 1 ? o1 : nullptr, nwin > 2 ? o2 : nullptr};
+    int live = 0;
+    bool vec = aligned16(x);
+    for (int w = 0; w < 3; ++w) {
+        live += o[w] != nullptr;
+        vec = vec && aligned16(o[w]);
+    }
+    if (!live) return VQW_OK;
+    VQW_PROF_HBM(stream, 1 + live, n);
+    k_window_stack_fwd<<<stream_grid((n + 3) / 4, 256), 256, 0, (hipStream_t)stream>>>(x, win, o[0], o[1], o[2], nwin, n, vec ? n >> 2 : 0);
+    VQW_LAUNCH_CHECK("vqw_window_stack_fwd");
+    return VQW_OK;
+}
+extern "C" int vqw_window_stack_bwd(const float* x, const float* win, const float* g0, const float* g1, const float* g2, float* gx,
+                                    int nwin, long n, void* stream) {
+    VQW_CHECK(x && win && gx && nwin >= 1 && nwin <= 3 && n > 0, "vqw_window_stack_bwd: bad arguments (nwin=%d, n=%ld)", nwin, n);
+    const float* g[3] = {g0, nwin > 1 ? g1 : nullptr, nwin > 2 ? g2 : nullptr};
+    int live = 0;
+    bool vec = aligned16(x) && aligned16(gx);
+    for (int w = 0; w < 3; ++w) {
+        live += g[w] != nullptr;
+        vec = vec && aligned16(g[w]);
+    }
+    VQW_PROF_HBM(stream, 2 + live, n);
+    k_window_stack_bwd<<<stream_grid((n + 3) / 4, 256), 256, 0, (hipStream_t)stream>>>(x, win, g[0], g[1], g[2], gx, nwin, n, vec ? n >> 2 : 0);
+    VQW_LAUNCH_CHECK("vqw_window_stack_bwd");
+    return VQW_OK;
+}
+
 __global__ void k_weighted_sum(const float* const* __restrict__ terms, const float* __restrict__ w, int n, float* __restrict__ out) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         float s = 0.f;

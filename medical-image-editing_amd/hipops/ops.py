@@ -1692,9 +1692,15 @@ class _WindowMse(torch.autograd.Function):
         return ga, None, None, None, None, None
 
 
-def window_map(dataset_window, target_window):
+F32_MAX = 3.4028234663852886e38           # the largest finite float32 (prints as 3.4028235e38)
+
+
+def window_map(dataset_window, target_window, clamp=True):
     """(alpha, beta, lo, hi) of w(x) = normalize(denormalize(x, dataset window), target window) for x in the dataset's
-    normalised units (utils/__init__.py:17-51 as used by trainers/base.py:290-314); windows are (width, center, scale)."""
+    normalised units (utils/__init__.py:17-51 as used by trainers/base.py:290-314); windows are (width, center, scale).
+    clamp=False: the same alpha and beta with lo, hi = -/+ the largest finite float32 - the pure affine map of the
+    reference's `t_normalize` (utils/__init__.py:30-40, whose clamp is commented out).  The bounds stay finite, so no kernel
+    meets an infinity and the "strictly inside (lo, hi)" gradient rule passes every finite value."""
     w0, c0, s0 = dataset_window
     w1, c1, s1 = target_window
     vmax0, vmin0 = c0 + w0 // 2, c0 - w0 // 2
@@ -1703,12 +1709,14 @@ def window_map(dataset_window, target_window):
     a_hu, b_hu = (vmax0 - vmin0) / s0, 0.5 * (vmax0 - vmin0) + vmin0
     k = s1 / (vmax1 - vmin1)
     alpha, beta = a_hu * k, (b_hu - vmin1) * k - 0.5 * s1
+    if not clamp:
+        return float(alpha), float(beta), -F32_MAX, F32_MAX
     return float(alpha), float(beta), float(-0.5 * s1), float(0.5 * s1)
 
 
-def window_mse_loss(a, b, dataset_window, target_window):
+def window_mse_loss(a, b, dataset_window, target_window, clamp=True):
     """F.mse_loss(to_window(a), to_window(b)): the lung / mediastinal terms of the multi-window reconstruction loss."""
-    return _WindowMse.apply(a, b.detach(), *window_map(dataset_window, target_window))
+    return _WindowMse.apply(a, b.detach(), *window_map(dataset_window, target_window, clamp=clamp))
 
 
 _twiddles = {}
@@ -1794,6 +1802,43 @@ def _window_table(windows, like):
             torch.cuda.current_stream().synchronize()    # later calls may read it from another stream
         _window_tables[key] = t
     return t
+
+
+class _WindowStack(torch.autograd.Function):
+    """Outputs: one re-windowed copy of x per window, all from one launch; backward: one launch for all of them."""
+
+    @staticmethod
+    def forward(ctx, x, windows):
+        _dev(x)
+        x = nhwc(x)
+        win = _window_table(windows, x)
+        outs = [torch.empty_like(x, memory_format=CL) for _ in windows]
+        o = outs + [None] * (3 - len(outs))
+        _L().vqw_window_stack_fwd(x, win, o[0], o[1], o[2], len(windows), x.numel())
+        ctx.set_materialize_grads(False)       # an unused window's gradient arrives as None (the kernel takes a null pointer)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(x, win)
+            ctx.nwin = len(windows)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        x, win = ctx.saved_tensors
+        g = [None if t is None else nhwc(t) for t in gs] + [None] * (3 - len(gs))
+        gx = torch.empty_like(x, memory_format=CL)
+        _L().vqw_window_stack_bwd(x, win, g[0], g[1], g[2], gx, ctx.nwin, x.numel())
+        return gx, None
+
+
+def window_stack(x, windows):
+    """One re-windowed copy of x per window, w(x) = clamp(alpha * x + beta, lo, hi): `windows` is a tuple of one to three
+    windows, each None (the identity) or the (alpha, beta, lo, hi) of `window_map`.  All copies come from one read of x in one
+    kernel, the identity's too: every output is a fresh channels-last tensor, and x receives ONE gradient, the sum over the
+    windows that have one (slope inside (lo, hi), zero elsewhere), from one kernel.  Without x.requires_grad no tape is kept."""
+    windows = tuple(None if w is None else tuple(float(v) for v in w) for w in windows)
+    if not 1 <= len(windows) <= 3 or any(w is not None and len(w) != 4 for w in windows):
+        raise RuntimeError("window_stack: one to three windows, each None or the (alpha, beta, lo, hi) of window_map")
+    return _WindowStack.apply(x, windows)
 
 
 def _pc_ohwi(w):

@@ -163,9 +163,8 @@ def worker(config, args, training_mode, rank, world_size, seed):
             trainer = build_first_step_trainer(config, device=device, data_parallel=distributed,
                                                multi_window=None if args.multiwindow else False)
         elif training_mode == "second_step":
-            if args.multiwindow:
-                raise NotImplementedError("a multi-window second step (-w with training_mode second_step) is not built")
-            trainer = build_second_step_trainer(config, device=device, data_parallel=distributed)
+            trainer = build_second_step_trainer(config, device=device, data_parallel=distributed,
+                                                multi_window=None if args.multiwindow else False)
         else:
             trainer = InferenceModels(config, device=device)
         # utils/init_seed.py:14-24: from here on every rank has its own seed; all of them are saved with the config

@@ -15,7 +15,8 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
                  use_unet_perceptual_loss, use_l1_loss}                  (second_step with model_name 'UNetDiscriminator')
     config.augmentation.{modules, ...}            (optional: absent -> the exact-integer flip views of the benchmark)
     config.dataset.{window_width, window_center, window_scale}, config.loss.{recon_weights, freq_weights, percep_weights}
-                 (multi-window runs, -w)
+                 (multi-window runs, -w); config.loss.clamp_windows (second_step, a key of this project: absent -> true, see
+                 trainers/second_step_unet_mw.py)
     config.loss.{perceptual_loss_type, conv_index, perceptual_weights, lpips_weights}   (with use_perceptual_loss)
 
 The focal frequency loss (use_frequency_loss) is functions.FocalFrequencyLoss, built on HIP kernels in place of the
@@ -39,6 +40,7 @@ from utils.checkpoint import load_first_stage_from_ckpt, load_discriminator_from
 from .first_step import FirstStepTrainer, FlipViews, RandomTransformViews, LossWeights
 from .second_step import SecondStepTrainer, GanLossWeights
 from .second_step_unet import UNetSecondStepTrainer, UNetGanLossWeights
+from .second_step_unet_mw import UNetMultiWindowSecondStepTrainer
 from .evaluation import Evaluator
 
 
@@ -210,21 +212,15 @@ def build_evaluator(config, encoder, decoder):
     return Evaluator(encoder, decoder, config.model.vqmodel.dict_size)
 
 
-def build_first_step_trainer(config, device="cuda", data_parallel=None, views=None, multi_window=None):
-    """config -> FirstStepTrainer (the `first_step` training mode of run_vqwnet.py).  data_parallel defaults to
-    torch.distributed being initialised with more than one rank."""
-    import torch.distributed as dist
-    mode = _get(config.run, "training_mode", "first_step")
-    if mode != "first_step":
-        raise NotImplementedError("training_mode %r: use trainers.build_second_step_trainer (or trainers.SecondStepTrainer) "
-                                  "for the GAN step" % mode)
-    frequency_loss = configure_frequency_loss(config)
-    if multi_window is None and _get(config.loss, "recon_weights") is not None and _get(config.dataset, "window_width") is not None:
+def _multi_window(config, multi_window, frequency_loss, perceptual_loss):
+    """-> (multi_window, freq_weights, percep_weights) of a builder's `multi_window` argument: None derives the dict from
+    loss.recon_weights and dataset.window_*, False (the launcher without -w) is the single-window step whatever keys the
+    config carries; the per-window weights of a loss that is on are required in a multi-window run."""
+    if multi_window is None and _get(config.loss, "recon_weights") is not None and _get(_get(config, "dataset"), "window_width") is not None:
         d = config.dataset
         multi_window = dict(dataset_window=(d.window_width, d.window_center, d.window_scale), recon_weights=tuple(config.loss.recon_weights))
-    if multi_window is False:           # the launcher without -w: the single-window step whatever keys the config carries
+    if multi_window is False:
         multi_window = None
-    perceptual_loss = configure_perceptual_loss(config)
     percep_weights = None
     if perceptual_loss is not None and multi_window is not None:
         percep_weights = _get(config.loss, "percep_weights")
@@ -239,6 +235,20 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
             raise ValueError("config.loss.freq_weights is required for a multi-window run with use_frequency_loss "
                              "(multi_window_trainer.py:100-126)")
         freq_weights = tuple(freq_weights)
+    return multi_window, freq_weights, percep_weights
+
+
+def build_first_step_trainer(config, device="cuda", data_parallel=None, views=None, multi_window=None):
+    """config -> FirstStepTrainer (the `first_step` training mode of run_vqwnet.py).  data_parallel defaults to
+    torch.distributed being initialised with more than one rank."""
+    import torch.distributed as dist
+    mode = _get(config.run, "training_mode", "first_step")
+    if mode != "first_step":
+        raise NotImplementedError("training_mode %r: use trainers.build_second_step_trainer (or trainers.SecondStepTrainer) "
+                                  "for the GAN step" % mode)
+    frequency_loss = configure_frequency_loss(config)
+    perceptual_loss = configure_perceptual_loss(config)
+    multi_window, freq_weights, percep_weights = _multi_window(config, multi_window, frequency_loss, perceptual_loss)
     encoder, decoder = configure_models(config)
     if data_parallel is None:
         data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
@@ -254,13 +264,15 @@ def build_first_step_trainer(config, device="cuda", data_parallel=None, views=No
 
 
 def build_second_step_trainer(config, device="cuda", data_parallel=None, first_stage_ckpt_path=None,
-                              discriminator_ckpt_path=None):
+                              discriminator_ckpt_path=None, multi_window=None):
     """config -> SecondStepTrainer (the `second_step` training mode of run_vqwnet.py with the PatchGAN discriminator,
     single_window_trainer.py:434-488) or, when model.dis names the U-Net discriminator, UNetSecondStepTrainer
-    (:264-432).  The first-stage weights (encoder strictly, decoder non-strictly) and, optionally, the
-    discriminator's come from the path arguments, else from config.run.first_stage_ckpt_path / discriminator_ckpt_path, as
-    TrainerBase.__init__ loads them (base.py:79-83).  Multi-window second steps train the U-Net discriminator in the
-    reference and are not built."""
+    (:264-432) or, multi-window, UNetMultiWindowSecondStepTrainer (multi_window_trainer.py:208-321).  multi_window: as in
+    build_first_step_trainer - None derives it from loss.recon_weights and dataset.window_*, False builds the single-window
+    step whatever keys the config carries.  The multi-window step trains the U-Net discriminator only (the reference unpacks
+    three outputs of self.dis): with the PatchGAN it raises.  The first-stage weights (encoder strictly, decoder
+    non-strictly) and, optionally, the discriminator's come from the path arguments, else from
+    config.run.first_stage_ckpt_path / discriminator_ckpt_path, as TrainerBase.__init__ loads them (base.py:79-83)."""
     import torch.distributed as dist
     mode = _get(config.run, "training_mode", "second_step")
     if mode != "second_step":
@@ -269,10 +281,14 @@ def build_second_step_trainer(config, device="cuda", data_parallel=None, first_s
     loss_type = _get(c, "dis_loss_type") or "hinge_d_loss"
     if loss_type != "hinge_d_loss":
         raise NotImplementedError("loss.dis_loss_type %r: only 'hinge_d_loss' is built (single_window_trainer.py:478)" % (loss_type,))
-    if _get(c, "recon_weights") is not None and _get(_get(config, "dataset"), "window_width") is not None:
-        raise NotImplementedError("a multi-window second step (loss.recon_weights with dataset.window_width) is not built")
+    frequency_loss, perceptual_loss = configure_frequency_loss(config), configure_perceptual_loss(config)
+    multi_window, freq_weights, percep_weights = _multi_window(config, multi_window, frequency_loss, perceptual_loss)
     encoder, decoder = configure_models(config)
     dis = configure_discriminator(config)
+    if multi_window is not None and not isinstance(dis, UNetDiscriminator):
+        raise NotImplementedError("a multi-window second step trains the U-Net discriminator (model.dis.model_name "
+                                  "'UNetDiscriminator'): the reference's step unpacks three outputs of its discriminator "
+                                  "(multi_window_trainer.py:245); with the PatchGAN it is not built")
     first = first_stage_ckpt_path or _get(config.run, "first_stage_ckpt_path")
     if first:
         load_first_stage_from_ckpt(first, encoder, decoder)
@@ -282,11 +298,16 @@ def build_second_step_trainer(config, device="cuda", data_parallel=None, first_s
     if data_parallel is None:
         data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     kw = dict(dis=dis, n_inner_loops=int(_get(c, "n_inner_loops") or 1), device=device, data_parallel=data_parallel,
-              frequency_loss=configure_frequency_loss(config), perceptual_loss=configure_perceptual_loss(config),
+              frequency_loss=frequency_loss, perceptual_loss=perceptual_loss,
               dec_optim=_adam_kwargs(config.dec_optim), dis_optim=_adam_kwargs(config.dis_optim),
               use_recon_loss=bool(_get(c, "use_recon_loss", True)))
     if isinstance(dis, UNetDiscriminator):          # single_window_trainer.py:264-432
-        return UNetSecondStepTrainer(encoder, decoder, loss_weight=unet_gan_loss_weights(config),
-                                     use_unet_perceptual_loss=bool(_get(c, "use_unet_perceptual_loss")),
-                                     use_l1_loss=bool(_get(c, "use_l1_loss")), **kw)
+        kw.update(loss_weight=unet_gan_loss_weights(config), use_unet_perceptual_loss=bool(_get(c, "use_unet_perceptual_loss")),
+                  use_l1_loss=bool(_get(c, "use_l1_loss")))
+        if multi_window is not None:
+            # (a JSON `false` arrives as None: only an absent key means true)
+            clamp = bool(c.clamp_windows) if hasattr(c, "clamp_windows") else True
+            return UNetMultiWindowSecondStepTrainer(encoder, decoder, multi_window=multi_window, freq_weights=freq_weights,
+                                                    percep_weights=percep_weights, clamp_windows=clamp, **kw)
+        return UNetSecondStepTrainer(encoder, decoder, **kw)
     return SecondStepTrainer(encoder, decoder, loss_weight=gan_loss_weights(config), **kw)

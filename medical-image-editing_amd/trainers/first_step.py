@@ -18,6 +18,7 @@ from functions import EmbeddingLoss, OneHotEncoder
 from utils import norm, denorm
 from .base import StepThrottle, TrainerBase  # noqa: F401  (StepThrottle: imported from here by older code)
 from .data_parallel import GradientAllReducer
+from . import window_terms
 
 LossWeights = namedtuple("LossWeights", "commit cross dist reg recon freq perceptual", defaults=(1.0,) * 5 + (0.0, 0.0))
 
@@ -69,8 +70,7 @@ trainer_state_dict = TrainerBase.state_dict              # (trainer) and (traine
 load_trainer_state_dict = TrainerBase.load_state_dict    # and optimizers(): the names these had as functions of this module
 
 
-LUNG_WINDOW = (1500, -550, 2.0)             # trainers/base.py:33-43
-MEDIASTINAL_WINDOW = (400, 20, 2.0)
+LUNG_WINDOW, MEDIASTINAL_WINDOW = window_terms.LUNG_WINDOW, window_terms.MEDIASTINAL_WINDOW    # the names they have here
 
 
 class FirstStepTrainer(TrainerBase):
@@ -194,44 +194,19 @@ class FirstStepTrainer(TrainerBase):
         return self._recon_terms(recon, clear), self._freq_terms(recon, clear), self._percep_terms(recon, clear)
 
     def _recon_terms(self, recon, clear):
-        """[(loss term, weight)] of one view's reconstruction loss: plain MSE, or the multi-window mean of
-        recon_weights[i] * MSE on the full / lung / mediastinal windows (multi_window_trainer.py:93-118)."""
+        """[(loss term, weight)] of one view's reconstruction loss (window_terms.recon_terms)."""
         if not self.use_recon_loss:          # l_recon = 0.0 upstream: the term is still reported, with weight zero
             return [(ops.mse_loss(recon.detach(), clear), 0.0)]
-        if self.multi_window is None:
-            return [(ops.mse_loss(recon, clear), self.w.recon)]
-        dw, rw = self.multi_window["dataset_window"], self.multi_window["recon_weights"]
-        terms = [ops.mse_loss(recon, clear), ops.window_mse_loss(recon, clear, dw, LUNG_WINDOW),
-                 ops.window_mse_loss(recon, clear, dw, MEDIASTINAL_WINDOW)]
-        return [(t, self.w.recon * float(r) / 3.0) for t, r in zip(terms, rw)]
+        return window_terms.recon_terms(recon, clear, self.multi_window, self.w.recon)
 
     def _freq_terms(self, recon, clear):
-        """[(loss term, weight)] of one view's focal frequency loss (single_window_trainer.py:117-136): none without the
-        loss; FFL(recon, clear); or, multi-window, freq_weights[i] / 3 * FFL on the full / lung / mediastinal windows with
-        the window map applied inside the kernel (multi_window_trainer.py:100-126)."""
-        ffl = self.frequency_loss
-        if ffl is None:
-            return []
-        if self.multi_window is None:
-            return [(ffl(recon, clear), self.w.freq)]
-        dw = self.multi_window["dataset_window"]
-        terms = [ffl(recon, clear), ffl(recon, clear, window=ops.window_map(dw, LUNG_WINDOW)),
-                 ffl(recon, clear, window=ops.window_map(dw, MEDIASTINAL_WINDOW))]
-        return [(t, self.w.freq * float(f) / 3.0) for t, f in zip(terms, self.freq_weights)]
+        """[(loss term, weight)] of one view's focal frequency loss (window_terms.freq_terms)."""
+        return window_terms.freq_terms(self.frequency_loss, recon, clear, self.multi_window, self.freq_weights, self.w.freq)
 
     def _percep_terms(self, recon, clear):
-        """[(loss term, weight)] of one view's perceptual loss (single_window_trainer.py:124-137): none without the loss;
-        VGGLoss(recon, clear); or, multi-window, percep_weights[i] / 3 * VGGLoss on the full / lung / mediastinal windows
-        (multi_window_trainer.py:101-119), all three windows in one batch with the window map applied inside the kernels.
-        The first term is the full-window (or only) loss."""
-        vgg = self.perceptual_loss
-        if vgg is None:
-            return []
-        if self.multi_window is None:
-            return [(vgg(recon, clear), self.w.perceptual)]
-        dw = self.multi_window["dataset_window"]
-        terms = vgg(recon, clear, windows=(None, ops.window_map(dw, LUNG_WINDOW), ops.window_map(dw, MEDIASTINAL_WINDOW)))
-        return [(t, self.w.perceptual * float(p) / 3.0) for t, p in zip(terms, self.percep_weights)]
+        """[(loss term, weight)] of one view's perceptual loss (window_terms.percep_terms)."""
+        return window_terms.percep_terms(self.perceptual_loss, recon, clear, self.multi_window, self.percep_weights,
+                                         self.w.perceptual)
 
     def forward_losses(self, image, noise=None):
         """Lines 73-137 of the reference step.  `image` is in [-1, 1] (dataloader convention)."""

@@ -26,7 +26,8 @@ GanLossWeights = namedtuple("GanLossWeights", "recon gen dis freq perceptual", d
 
 class SecondStepBase(TrainerBase):
     """A subclass sets `Weights` (its loss-weight namedtuple) and `dis_keys` (the names of what discriminator_update returns)
-    and supplies generator_terms() and discriminator_update()."""
+    and supplies generator_terms() and discriminator_update(); a multi-window step also overrides shared_terms() and
+    discriminator_inputs().  training_step is the one step body of all of them."""
 
     def __init__(self, encoder, decoder, dis=None, loss_weight=None, n_inner_loops=1, lr=1e-4, betas=(0.5, 0.999),
                  weight_decay=0.0, device="cuda", data_parallel=False, frequency_loss=None,
@@ -64,6 +65,19 @@ class SecondStepBase(TrainerBase):
         """The discriminator's parameters whose gradients a data-parallel run all-reduces."""
         return [p for p in self.dis.parameters() if p.requires_grad]
 
+    def shared_terms(self, image, recon):
+        """-> the ("recon", "freq", "perceptual") entries (name, term or None, weight) of the generator total: the terms that
+        do not depend on the discriminator."""
+        w = self.w
+        return [("recon", ops.mse_loss(recon, image) if self.use_recon_loss else None, w.recon),
+                ("freq", self.frequency_loss(recon, image) if self.frequency_loss is not None else None, w.freq),
+                ("perceptual", self.perceptual_loss(recon, image) if self.perceptual_loss is not None else None, w.perceptual)]
+
+    def discriminator_inputs(self, image, recon):
+        """-> (image, recon) as generator_terms and discriminator_update get them, made once per step: the tensors
+        themselves here, one view per window in a multi-window step."""
+        return image, recon
+
     def generator_terms(self, image, recon, shared):
         """-> [(name, term or None, weight)] of the generator total in the order ops.weighted_sum adds them (the order is
         part of the total's bits), the discriminator's forward on `recon` included; `shared`: the (recon, freq, perceptual)
@@ -76,7 +90,6 @@ class SecondStepBase(TrainerBase):
 
     def training_step(self, batch):
         image = batch['image'] if isinstance(batch, dict) else batch
-        w = self.w
         self.throttle.begin()
         ops.begin_step()
         if self.dec_reducer is not None:
@@ -85,9 +98,8 @@ class SecondStepBase(TrainerBase):
         with torch.no_grad():
             embed, _, ids = self.encoder(image)
         recon = self.decoder(embed.detach())
-        shared = [("recon", ops.mse_loss(recon, image) if self.use_recon_loss else None, w.recon),
-                  ("freq", self.frequency_loss(recon, image) if self.frequency_loss is not None else None, w.freq),
-                  ("perceptual", self.perceptual_loss(recon, image) if self.perceptual_loss is not None else None, w.perceptual)]
+        shared = self.shared_terms(image, recon)
+        d_image, d_recon = self.discriminator_inputs(image, recon)
         # The reference lets autograd fill the discriminator's parameter gradients in this pass and discards them
         # (dis_optim.zero_grad() in the discriminator half); they are not computed here.  Same decoder gradients, same
         # update; the discriminator's buffers advance as in the reference.
@@ -104,14 +116,14 @@ class SecondStepBase(TrainerBase):
         for p in dis_params:
             p.requires_grad_(False)
         try:
-            terms = [t for t in self.generator_terms(image, recon, shared) if t[1] is not None]
+            terms = [t for t in self.generator_terms(d_image, d_recon, shared) if t[1] is not None]
             l_gen_total = ops.weighted_sum([t for _, t, _ in terms], [c for _, _, c in terms])
             self.update(l_gen_total, [self.dec_optim], self.dec_reducer, thaw_and_join)
         finally:
             thaw()
         last = ()
         for _ in range(self.n_inner_loops):
-            last = self.discriminator_update(image, recon)
+            last = self.discriminator_update(d_image, d_recon)
         self.throttle.end()
         out = dict(gen_total=l_gen_total)
         out.update((name, t) for name, t, _ in terms)

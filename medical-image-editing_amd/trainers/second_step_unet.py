@@ -68,7 +68,8 @@ class UNetSecondStepTrainer(SecondStepBase):
             return self.cutmix_box() if callable(self.cutmix_box) else self.cutmix_box
         return draw_cutmix_box(H, W), random.random() > 0.5
 
-    def generator_terms(self, image, recon, shared):
+    def generator_pass(self, image, recon):
+        """D(recon) with a tape, then, with use_unet_perceptual_loss, D(image) without one -> (l_gen, l_unet_perceptual or None)"""
         f_map, f_bottle, f_feat = self.dis(recon)
         l_gen = ops.weighted_sum([ops.neg_mean(f_map), ops.neg_mean(f_bottle)], [1.0, 1.0])
         l_unet = None
@@ -76,18 +77,29 @@ class UNetSecondStepTrainer(SecondStepBase):
             with torch.no_grad():
                 _, _, r_feat = self.dis(image.detach())
             l_unet = ops.weighted_sum([ops.mse_loss(f, r) for f, r in zip(f_feat, r_feat)], [1.0] * len(f_feat))
+        return l_gen, l_unet
+
+    def generator_terms(self, image, recon, shared):
+        l_gen, l_unet = self.generator_pass(image, recon)
         return [("gen", l_gen, self.w.gen), *shared, ("unet_perceptual", l_unet, self.w.unet_perceptual)]
 
-    def discriminator_update(self, image, recon):
-        """One inner loop of the discriminator half (single_window_trainer.py:319-357): D(image), D(recon), one CutMix draw,
-        D(cutmix_images), the three losses, one Adam step.  -> (l_dis_total, l_dis, l_cutmix, l_consistency)"""
-        w = self.w
+    def discriminator_pass(self, image, recon):
+        """D(image), D(recon), one CutMix draw, D(cutmix_images) (single_window_trainer.py:319-349) -> (l_dis, l_cutmix, l_consistency)"""
         r_map, r_bottle, _ = self.dis(image.detach())
         f_map, f_bottle, _ = self.dis(recon.detach())
         box, flip = self._draw_box(image.shape[2], image.shape[3])
         cutmix_images = ops.cutmix_select(image, recon, box, flip)
         c_map, c_bottle, _ = self.dis(cutmix_images)
-        l_dis, l_cutmix, l_cons = ops.unet_dis_losses(r_map, f_map, c_map, r_bottle, f_bottle, c_bottle, box, flip)
+        return ops.unet_dis_losses(r_map, f_map, c_map, r_bottle, f_bottle, c_bottle, box, flip)
+
+    def discriminator_step(self, l_dis, l_cutmix, l_cons):
+        """The weighted total of the three losses and one Adam step -> (l_dis_total, l_dis, l_cutmix, l_consistency)"""
+        w = self.w
         l_dis_total = ops.weighted_sum([l_dis, l_cutmix, l_cons], [w.dis, w.cutmix, w.consistency])
         self.update(l_dis_total, [self.dis_optim], self.dis_reducer)
         return l_dis_total, l_dis, l_cutmix, l_cons
+
+    def discriminator_update(self, image, recon):
+        """One inner loop of the discriminator half (single_window_trainer.py:319-357): the three passes and their losses, one
+        Adam step.  -> (l_dis_total, l_dis, l_cutmix, l_consistency)"""
+        return self.discriminator_step(*self.discriminator_pass(image, recon))

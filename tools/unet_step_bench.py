@@ -7,24 +7,30 @@ measurement:
   kernels   each HBM-bound kernel of csrc/unet_dis.hip alone at the config's largest shape, HIP events around --reps launches:
             ms and achieved bytes/s, bytes = the tensors it reads and writes, once each
 
-    python tools/unet_step_bench.py [--steps 10] [--warmup 4] [--windows 5] [--reps 50]
+    python tools/unet_step_bench.py [--steps 10] [--warmup 4] [--windows 5] [--reps 50] [--multi-window]
+
+--multi-window measures the multi-window step (configs/second_step_unet_512_mw.json, `run_vqwnet.py -w`) instead, and the
+window-stack kernels of csrc/elementwise.hip among the kernels.
 
 The share of the step spent in convolution kernels comes from a kernel trace of the same step:
 
     rocprofv3 --kernel-trace --stats -d prof -o t -- python tools/unet_step_bench.py --only-step --windows 1
-    python tools/unet_step_bench.py --stats prof/.../t_kernel_stats.csv
+    python tools/unet_step_bench.py --stats prof/.../t_kernel_stats.csv [--traced-steps WARMUP+STEPS]
+
+--stats also prints the number of kernel launches of the traced run and, with --traced-steps, per step.
 """
 import argparse, csv, json, os, re, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "medical-image-editing_amd"))
 
 CONV = re.compile(r"k_conv_|k_pw_|k_stem_|k_head_|k_wino_|k_pack_|k_input_grad_gather|k_reduce_|k_fold_multi|k_collapse_up|k_bias_grad")
-OWN = re.compile(r"k_dtail_|k_utail_|k_bottleneck_|k_cutmix_select|k_dis_losses_|k_sn_")
+OWN = re.compile(r"k_dtail_|k_utail_|k_bottleneck_|k_cutmix_select|k_dis_losses_|k_sn_|k_window_stack_")
 
 
-def stats(path):
+def stats(path, traced_steps=None):
     rows = list(csv.DictReader(open(path)))
     total = sum(float(r["TotalDurationNs"]) for r in rows)
+    launches = sum(int(r["Calls"]) for r in rows)
     conv = sum(float(r["TotalDurationNs"]) for r in rows if CONV.search(r["Name"]))
     own = {}
     for r in rows:
@@ -33,16 +39,18 @@ def stats(path):
             name = re.search(r"k_\w+", r["Name"]).group(0)
             own[name] = round(own.get(name, 0.0) + float(r["TotalDurationNs"]) / 1e6, 3)
     print(json.dumps(dict(what="kernel time of the traced run", total_ms=round(total / 1e6, 2), convolution_ms=round(conv / 1e6, 2),
-                          convolution_share=round(conv / total, 4), unet_dis_and_spectral_ms=own)))
+                          convolution_share=round(conv / total, 4), unet_dis_and_spectral_ms=own, launches=launches,
+                          launches_per_step=round(launches / traced_steps, 1) if traced_steps else None)))
 
 
 def step_rows(args):
     import torch
     from utils import load_json
     from trainers import build_second_step_trainer
-    c = load_json(os.path.join(ROOT, "configs", "second_step_unet_512.json"))
+    name = "second_step_unet_512_mw" if args.multi_window else "second_step_unet_512"
+    c = load_json(os.path.join(ROOT, "configs", name + ".json"))
     torch.manual_seed(0)
-    tr = build_second_step_trainer(c, device="cuda")
+    tr = build_second_step_trainer(c, device="cuda", multi_window=None if args.multi_window else False)
     B, S = c.dataset.batch_size, c.dataset.image_size
     imgs = [torch.rand(B, 1, S, S, device="cuda") * 2 - 1 for _ in range(4)]
     mids = []
@@ -70,7 +78,7 @@ def step_rows(args):
         windows.append(marks[0].elapsed_time(marks[-1]) / args.steps)
         gen.append(sum(marks[i].elapsed_time(mids[i]) for i in range(args.steps)) / args.steps)
         dis.append(sum(mids[i].elapsed_time(marks[i + 1]) for i in range(args.steps)) / args.steps)
-    print(json.dumps(dict(what="step", config="second_step_unet_512", batch=B, steps=args.steps, ms_per_step=round(statistics.median(windows), 2),
+    print(json.dumps(dict(what="step", config=name, batch=B, steps=args.steps, ms_per_step=round(statistics.median(windows), 2),
                           windows=[round(v, 2) for v in windows], generator_half_ms=round(statistics.median(gen), 2),
                           discriminator_half_ms=round(statistics.median(dis), 2))), flush=True)
     return c
@@ -137,6 +145,13 @@ def kernel_rows(args, c):
           lambda: L.vqw_unet_dis_losses_fwd(*maps, *bots, *losses, ws, ws.numel(), B, S, S, 100, 300, 64, 200, 0))
     timed("unet_dis_losses_bwd", [B, 1, S, S], 4 * n * 6,
           lambda: L.vqw_unet_dis_losses_bwd(*maps, *bots, *one, *gm, *gb, B, S, S, 100, 300, 64, 200, 0))
+    if args.multi_window:                        # the three views of (B, 1, 512, 512) and their one gradient
+        from trainers import window_terms
+        d = c.dataset
+        win = ops._window_table(window_terms.window_maps((d.window_width, d.window_center, d.window_scale)), img)
+        views, gv, gx = [t(B, S, S, 1) for _ in range(3)], [t(B, S, S, 1) for _ in range(3)], t(B, S, S, 1)
+        timed("window_stack_fwd", [B, 1, S, S], 4 * n * 4, lambda: L.vqw_window_stack_fwd(img, win, *views, 3, n))
+        timed("window_stack_bwd", [B, 1, S, S], 4 * n * 5, lambda: L.vqw_window_stack_bwd(img, win, *gv, gx, 3, n))
 
 
 def main():
@@ -146,10 +161,12 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--only-step", action="store_true")
+    ap.add_argument("--multi-window", action="store_true", help="the multi-window step (configs/second_step_unet_512_mw.json)")
+    ap.add_argument("--traced-steps", type=int, help="with --stats: the steps of the traced run (warm-up included)")
     ap.add_argument("--stats", help="a rocprofv3 --stats kernel CSV of a run with --only-step: print the convolution share")
     args = ap.parse_args()
     if args.stats:
-        return stats(args.stats)
+        return stats(args.stats, args.traced_steps)
     c = step_rows(args)
     if not args.only_step:
         kernel_rows(args, c)
