@@ -643,6 +643,37 @@ int vqw_volume_to_slices(const void* vol, const double* stats, const double* kh,
 int vqw_label_slices(const int32_t* vol, const int* xtab, const int* ytab, int32_t* out, int32_t* err, int X, int Y, int Z,
                      int S, int orient, int relabel, void* stream);
 
+/* ---- VQGAN decoder blocks (networks/vqgan.py:10-19 Normalize / nonlinearity, :125-180 AttnBlock).  Added functions only; the
+ *      ABI stays 9.
+ * GroupNorm(32 groups, affine) with or without swish: y = act(gamma_c (x - mean_{n,g}) rstd_{n,g} + beta_c), act = identity or
+ * u sigmoid(u); x, y [N][HW][C], C a multiple of 32 (anything else is rejected, as torch rejects it), at most 1024.  The
+ * statistics are double sums folded in a fixed order (per-thread, workgroup rows, splits): the same bits every run, and no fp32
+ * E[x^2] - mean^2.  mean, rstd [N][32] are what the backward needs besides x: it recomputes gamma xhat + beta.
+ * vqw_groupnorm_splits: workgroups per image of the reduction passes; 1 = the plane is reduced and finalised by one workgroup
+ * (H W C <= 16384), else it is split and a finalise pass folds the partials.  ws: vqw_groupnorm_ws_bytes() bytes.
+ * Backward: a reduce pass (per image and channel sum g', sum g' xhat with g' = gy act'(gamma xhat + beta); from them
+ * dgamma_c, dbeta_c and per group sum gamma g', sum gamma g' xhat), then the apply pass
+ * gx = rstd (gamma g' - mean_g(gamma g') - xhat mean_g(gamma g' xhat)).  dgamma, dbeta [C] are overwritten. */
+int vqw_groupnorm_splits(int HW, int C);
+size_t vqw_groupnorm_ws_bytes(int N, int HW, int C);
+int vqw_groupnorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, void* ws,
+                      size_t ws_bytes, int N, int HW, int C, float eps, int swish, void* stream);
+int vqw_groupnorm_bwd(const float* x, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                      const float* gy, float* gx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, int N, int HW,
+                      int C, int swish, void* stream);
+/* swish on its own, y = x sigmoid(x) (vqgan.py:10-12 `nonlinearity`), and its gradient gx = gy swish'(x): n elements */
+int vqw_swish_fwd(const float* x, float* y, long n, void* stream);
+int vqw_swish_bwd(const float* x, const float* gy, float* gx, long n, void* stream);
+/* Single-head self-attention over a feature map: o = softmax(scale q k^T) v per batch element; q, k, v, o [B][N][C] (N = H W of
+ * an NHWC map), C a multiple of 32 up to 512; lse [B][N] = the row log-sum-exp of scale q k^T.  Both matrix products run on the
+ * exact-fp32 matrix cores; the softmax is online (running row maximum), the N x N scores never reach memory.
+ * Backward: d_ws [B][N] receives D_i = sum_c go o; P = exp(scale S - lse) is recomputed; one pass over query tiles writes
+ * gq = scale (P o (go v^T - D)) k, one pass over key tiles gk = scale (P o (go v^T - D))^T q and gv = P^T go.  No atomics. */
+int vqw_attention_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int N, int C, float scale,
+                      void* stream);
+int vqw_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
+                      float* d_ws, float* gq, float* gk, float* gv, int B, int N, int C, float scale, void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

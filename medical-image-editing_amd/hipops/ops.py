@@ -1468,6 +1468,114 @@ def add(a, b, relu=False, a_group=None):
     return _Add.apply(a, b, bool(relu), a_group)
 
 
+# ----------------------------------------------------------------------------------------------
+# VQGAN decoder blocks (networks/vqgan.py): GroupNorm(32)(+swish) and single-head self-attention
+# ----------------------------------------------------------------------------------------------
+class _GroupNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, swish):
+        _dev(x, weight, bias)
+        x = nhwc(x)
+        weight, bias = _flat(weight), _flat(bias)
+        N, C, H, W = x.shape
+        if C % 32 != 0 or weight.numel() != C or bias.numel() != C:
+            raise RuntimeError("group_norm: num_channels (%d) must be divisible by num_groups (32), weight / bias of that size" % C)
+        L = _L()
+        y = torch.empty_like(x, memory_format=CL)
+        mean = torch.empty(N, 32, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(N, 32, dtype=torch.float32, device=x.device)
+        ws = _ws(L.vqw_groupnorm_ws_bytes(N, H * W, C), x)
+        L.vqw_groupnorm_fwd(x, weight, bias, y, mean, rstd, ws, ws.numel(), N, H * W, C, eps, int(swish))
+        ctx.save_for_backward(x, weight, bias, mean, rstd)      # not the pre-activation: the backward recomputes it
+        ctx.swish = swish
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, bias, mean, rstd = ctx.saved_tensors
+        N, C, H, W = x.shape
+        L = _L()
+        gy = nhwc(gy)
+        gx = torch.empty_like(x, memory_format=CL)
+        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws = _ws(L.vqw_groupnorm_ws_bytes(N, H * W, C), x)
+        L.vqw_groupnorm_bwd(x, weight, bias, mean, rstd, gy, gx, dgamma, dbeta, ws, ws.numel(), N, H * W, C, int(ctx.swish))
+        return gx, dgamma, dbeta, None, None
+
+
+def group_norm(x, weight, bias, eps=1e-6, swish=False):
+    """nn.GroupNorm(32, C, eps, affine=True)(x), with swish=True followed by y * sigmoid(y), as one pass."""
+    return _GroupNorm.apply(x, weight, bias, float(eps), bool(swish))
+
+
+class _Swish(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        _dev(x)
+        x = nhwc(x) if x.dim() == 4 else _flat(x)
+        y = torch.empty_like(x)
+        _L().vqw_swish_fwd(x, y, x.numel())
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        gy = nhwc(gy) if x.dim() == 4 else _flat(gy)
+        gx = torch.empty_like(x)
+        _L().vqw_swish_bwd(x, gy, gx, x.numel())
+        return gx
+
+
+def swish(x):
+    """x * sigmoid(x) on its own; behind a GroupNorm use group_norm(..., swish=True) instead."""
+    return _Swish.apply(x)
+
+
+class _SelfAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        _dev(q, k, v)
+        if not (q.shape == k.shape == v.shape):
+            raise RuntimeError("self_attention: q, k, v must have one shape (got %s, %s, %s)" % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+        q, k, v = nhwc(q), nhwc(k), nhwc(v)
+        B, C, H, W = q.shape
+        o = torch.empty_like(q, memory_format=CL)
+        lse = torch.empty(B, H * W, dtype=torch.float32, device=q.device)
+        _L().vqw_attention_fwd(q, k, v, o, lse, B, H * W, C, scale)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, o, lse = ctx.saved_tensors
+        B, C, H, W = q.shape
+        go = nhwc(go)
+        gq, gk, gv = (torch.empty_like(q, memory_format=CL) for _ in range(3))
+        d = torch.empty_like(lse)
+        _L().vqw_attention_bwd(q, k, v, o, lse, go, d, gq, gk, gv, B, H * W, C, ctx.scale)
+        return gq, gk, gv, None
+
+
+def self_attention(q, k, v, scale):
+    """softmax(scale * q^T k) applied to v over the H*W positions of three (B, C, H, W) maps of one shape (the reference's
+    AttnBlock, vqgan.py:163-176); returns a map of that shape.  The (HW x HW) score matrix is never materialised."""
+    return _SelfAttention.apply(q, k, v, float(scale))
+
+
+def self_attention_lse(q, k, v, scale):
+    """(output, row log-sum-exp [B, H*W]) of self_attention without a tape: for tests and measurement."""
+    _dev(q, k, v)
+    q, k, v = nhwc(q), nhwc(k), nhwc(v)
+    B, C, H, W = q.shape
+    o = torch.empty_like(q, memory_format=CL)
+    lse = torch.empty(B, H * W, dtype=torch.float32, device=q.device)
+    _L().vqw_attention_fwd(q, k, v, o, lse, B, H * W, C, float(scale))
+    return o, lse
+
+
 class _MaxPool2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

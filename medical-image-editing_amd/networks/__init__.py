@@ -9,3 +9,4 @@ from .vqwnet import VQWNet  # noqa: F401
 from .random_transform import RandomTransform  # noqa: F401
 from .discriminator import NLayerDiscriminator  # noqa: F401
 from .unet_discriminator import UNetDiscriminator  # noqa: F401
+from .vqgan import Normalize, nonlinearity, Upsample, ResnetBlock, AttnBlock, Decoder  # noqa: F401
