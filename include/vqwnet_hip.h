@@ -320,6 +320,11 @@ int vqw_vq_fwd(const float* x, const float* embed, int64_t* ids, int id_base, fl
  * sum_scale multiplies embed_sum before the EMA (1/world_size in the reference's quirk mode). */
 int vqw_vq_ema_update(const double* stats, float* embed, float* cluster_size, float* embed_avg,
                       float momentum, float eps, float sum_scale, int D, int K, void* stream);
+/* The same with the weight of the new statistics given: vqw_vq_ema_update uses 1.f - momentum formed in float32; the reference's
+ * add_(update, alpha=1 - momentum) rounds the double once, which is what a caller passes here to follow it to the last bit
+ * of that weight (9.5e-7 apart at momentum 0.99). */
+int vqw_vq_ema_update_w(const double* stats, float* embed, float* cluster_size, float* embed_avg, float momentum,
+                        float new_weight, float eps, float sum_scale, int D, int K, void* stream);
 /* One Lloyd iteration of the k-means codebook initialisation (unet_encoder.py:66-91): centres[k] <- mean of its members
  * from the statistics vqw_vq_fwd leaves (codes without members keep their centre).  shift[0] = sum_k |delta_k|_2,
  * shift[1] = number of empty codes.  ws: 16 K bytes. */
@@ -404,6 +409,20 @@ size_t vqw_sconv_wgrad_ws_bytes(int Cin, int Cout, int ks, int N, int H, int W, 
 int vqw_sconv_wgrad(const float* x, const float* gy, float* dw_ohwi, float* dbias, void* ws, size_t ws_bytes, int N, int H,
                     int W, int Cin, int Cout, int ks, int stride, int pad, int accumulate, void* stream);
 int vqw_leaky_relu_bwd(const float* y, const float* gy, float* gx, float slope, long n, void* stream);
+/* 3x3 stride-2 convolution behind a zero pad of one pixel at the bottom and right only (the VQGAN `Downsample`, vqgan.py:40-58:
+ * F.pad(x, (0, 1, 0, 1)) then Conv2d(C, C, 3, 2, 0)): y[n][yo][xo][co] = bias + sum w[co][ky][kx][ci] x[n][2 yo + ky][2 xo + kx][ci].
+ * x [N][H][W][Cin], y / gy [N][H/2][W/2][Cout], OHWI weights; H, W (the INPUT dims) even, Cin and Cout multiples of 32, every
+ * tensor below 4 GiB: anything else is refused.  Exact-fp32 matrix cores, nine taps on each pass: the input gradient multiplies
+ * 4 / 2 / 2 / 1 taps by output parity.  The weight gradient sums its split partials in a fixed order (no atomics); dbias may be
+ * NULL; accumulate: dw_ohwi (and dbias) += the result. */
+int vqw_conv3s2_fwd(const float* x, const float* w_ohwi, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                    void* stream);
+size_t vqw_conv3s2_dgrad_ws_bytes(int Cin, int Cout);
+int vqw_conv3s2_dgrad(const float* gy, const float* w_ohwi, float* gx, void* ws, size_t ws_bytes, int N, int H, int W, int Cin,
+                      int Cout, void* stream);
+size_t vqw_conv3s2_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout);
+int vqw_conv3s2_wgrad(const float* x, const float* gy, float* dw_ohwi, float* dbias, void* ws, size_t ws_bytes, int N, int H,
+                      int W, int Cin, int Cout, int accumulate, void* stream);
 /* BatchNorm2d(affine) + LeakyReLU: y = lrelu(((x - mean) * rstd) * gamma + beta); statistics through
  * vqw_bn_partial_stats / vqw_bn_finalize.  bwd_reduce: sums[C][2] = {sum g', sum g' * xhat} (dbeta, dgamma);
  * bwd_apply: dx, and dgamma / dbeta (may be NULL) written or accumulated. */
@@ -665,10 +684,11 @@ int vqw_groupnorm_bwd(const float* x, const float* gamma, const float* beta, con
 int vqw_swish_fwd(const float* x, float* y, long n, void* stream);
 int vqw_swish_bwd(const float* x, const float* gy, float* gx, long n, void* stream);
 /* Single-head self-attention over a feature map: o = softmax(scale q k^T) v per batch element; q, k, v, o [B][N][C] (N = H W of
- * an NHWC map), C a multiple of 32 up to 512; lse [B][N] = the row log-sum-exp of scale q k^T.  Both matrix products run on the
+ * an NHWC map), C a multiple of 32 up to 512 or a multiple of 64 up to 1024; lse [B][N] = the row log-sum-exp of scale q k^T.  Both matrix products run on the
  * exact-fp32 matrix cores; the softmax is online (running row maximum), the N x N scores never reach memory.
  * Backward: d_ws [B][N] receives D_i = sum_c go o; P = exp(scale S - lse) is recomputed; one pass over query tiles writes
- * gq = scale (P o (go v^T - D)) k, one pass over key tiles gk = scale (P o (go v^T - D))^T q and gv = P^T go.  No atomics. */
+ * gq = scale (P o (go v^T - D)) k, one pass over key tiles gk = scale (P o (go v^T - D))^T q and gv = P^T go.  No atomics.
+ * Above 512 channels every pass runs as two halves of the value / output columns, each recomputing its score tiles. */
 int vqw_attention_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int N, int C, float scale,
                       void* stream);
 int vqw_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,

@@ -189,6 +189,16 @@ bool conv_k4s2_wgrad_ok(int Cin, int Cout, int N, int h, int w);
 size_t conv_k4s2_wgrad_ws_floats(int Cin, int Cout, int N, int h, int w);
 int conv_k4s2_wgrad(const float* x_high, const float* gy_low, float* dw, float* ws, int N, int h, int w, int Cin, int Cout, int acc,
                     hipStream_t st);
+// 3x3 stride-2 convolution behind a bottom / right pad of one pixel, (2h, 2w) -> (h, w); Cin, Cout multiples of 32
+bool conv_k3s2_ok(int Cin, int Cout, int N, int h, int w);
+int conv_k3s2_fwd(const float* x_high, const float* w, const float* bias, float* y_low, int N, int h, int w_, int Cin, int Cout,
+                  hipStream_t st);
+size_t conv_k3s2_dgrad_ws_floats(int Cin, int Cout);
+int conv_k3s2_dgrad(const float* gy_low, const float* w, float* ws, float* gx_high, int N, int h, int w_, int Cin, int Cout,
+                    hipStream_t st);
+size_t conv_k3s2_wgrad_ws_floats(int Cin, int Cout, int N, int h, int w);
+int conv_k3s2_wgrad(const float* x_high, const float* gy_low, float* dw, float* ws, int N, int h, int w, int Cin, int Cout, int acc,
+                    hipStream_t st);
 int conv_k4s1_grid(const float* src, const float* w16, const float* bias, float* dst, int N, int H, int W, int Csrc, int Cdst,
                    int tap0, hipStream_t st);
 int conv_k5_grid(const float* src, const float* w25, const float* bias, float* dst, int N, int H, int W, int Csrc, int Cdst,

@@ -31,10 +31,13 @@ __device__ __forceinline__ float4 ld4_or_zero(const float* p, bool ok) {
 //   src_mode 2: source pixel = (2y + dy, 2x + dx) on a 2H x 2W tensor    (collapsed dgrad: M grid is the low-res map)
 //   out_mode 0: output pixel = M-grid pixel
 //   out_mode 1: output pixel = (2y + py, 2x + px) of a 2H x 2W tensor    (collapsed forward, one launch per parity)
+//               parity p = 2 py + px (the grid's y dimension) multiplies taps [ptap0[p], ptap0[p] + pntaps[p]) of the table;
+//               its weight block [Cout][pntaps[p]][Cin] starts at Cout * ptap0[p] * Cin.  ntaps = the largest pntaps.
 struct ConvGeom {
     int ntaps;
     int src_mode, out_mode, py, px;
     signed char dy[25], dx[25];
+    signed char ptap0[4], pntaps[4];
 };
 
 // =============================================================================================
@@ -42,10 +45,14 @@ struct ConvGeom {
 // =============================================================================================
 // Index arithmetic is 32-bit (the host checks numel < 2^31) and hoisted: pixel coordinates once per thread,
 // bounds / base offsets once per TAP, only an add per channel chunk.
-template <int BM, int BN, int WM, int WN, int KC, bool DEEP>
+// FOLD: every FOLD_CHUNKS chunks the running sums are added to a second set of accumulators, so that no chain of dependent
+// roundings is longer than FOLD_CHUNKS * KC / 2 MFMAs (two-level summation; the 3x3 stride-2 layers, whose accuracy gate is
+// twice the error of torch's blocked fp32 convolution: a single chain over 9 x 512 products is four times as far from float64).
+#define FOLD_CHUNKS 4
+template <int BM, int BN, int WM, int WN, int KC, bool DEEP, bool FOLD = false>
 __global__ void __launch_bounds__(256, 2)
 k_conv_mfma_fwd(ConvIn in, const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ y, int N, int H,
-                int W, int Cout, ConvGeom geo, int ntn, int relu, unsigned nb0, unsigned nb1, unsigned nbw, float* __restrict__ stats) {
+                int W, int Cout, ConvGeom geo, int ntn, int relu, unsigned nb0, unsigned nb1, unsigned nbw_all, float* __restrict__ stats) {
     constexpr int LDK = KC + 4;           // padded row length (floats)
     constexpr int C4 = KC / 4;            // float4 per row
     constexpr int LA = BM * C4 / 256;     // A float4 loads per thread per chunk
@@ -61,7 +68,10 @@ k_conv_mfma_fwd(ConvIn in, const float* __restrict__ w, const float* __restrict_
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int C0 = in.C0, C1 = in.C1, Cin = C0 + C1;
-    const int taps = geo.ntaps;
+    // collapsed forward: the four output parities are the y dimension of the grid, each with its own taps and weight block
+    const int tap_first = geo.out_mode == 1 ? geo.ptap0[blockIdx.y] : 0;
+    const int taps = geo.out_mode == 1 ? geo.pntaps[blockIdx.y] : geo.ntaps;
+    const unsigned nbw = geo.out_mode == 1 ? (unsigned)(Cout * taps * Cin) * 4u : nbw_all;
     const unsigned P = (unsigned)N * H * W;
     const int swz = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_n = swz % ntn, tile_m = swz / ntn;
@@ -69,9 +79,8 @@ k_conv_mfma_fwd(ConvIn in, const float* __restrict__ w, const float* __restrict_
     const int co_base = tile_n * BN;
     const int Hs = H >> 1, Ws = W >> 1;
     const int up0 = in.up0;
-    // collapsed forward: the four output parities are the y dimension of the grid, each with its own weight block
     const int par_y = geo.out_mode == 1 ? (int)(blockIdx.y >> 1) : 0, par_x = geo.out_mode == 1 ? (int)(blockIdx.y & 1) : 0;
-    if (geo.out_mode == 1) w += (size_t)blockIdx.y * Cout * taps * Cin;
+    if (geo.out_mode == 1) w += (size_t)Cout * tap_first * Cin;
     const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(in.src0, nb0), rs1 = make_rsrc(in.src1, nb1), rsw = make_rsrc(w, nbw);
 
     // per-thread pixel coordinates of the A rows it loads (fixed for the whole K loop)
@@ -108,8 +117,7 @@ k_conv_mfma_fwd(ConvIn in, const float* __restrict__ w, const float* __restrict_
     int l_t = 0, l_cc = 0;
     unsigned t_off0[LA], t_off1[LA];
     auto setup_tap = [&]() {
-        const int dyy = geo.out_mode == 1 ? par_y - 1 + (l_t >> 1) : geo.dy[l_t];
-        const int dxx = geo.out_mode == 1 ? par_x - 1 + (l_t & 1) : geo.dx[l_t];
+        const int dyy = geo.dy[tap_first + l_t], dxx = geo.dx[tap_first + l_t];
         if (geo.src_mode == 2) {
 #pragma unroll
             for (int j = 0; j < LA; ++j) {
@@ -202,6 +210,31 @@ k_conv_mfma_fwd(ConvIn in, const float* __restrict__ w, const float* __restrict_
         }
     };
 
+    f32x16 tot[FOLD ? TM : 1][FOLD ? TN : 1];
+    if constexpr (FOLD) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
+    }
+    auto fold = [&](int it) {             // after chunk `it` has been multiplied
+        if constexpr (FOLD) {
+            if ((it + 1) % FOLD_CHUNKS == 0 || it + 1 == nchunks) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            tot[i][j][r] += acc[i][j][r];
+                            acc[i][j][r] = it + 1 == nchunks ? tot[i][j][r] : 0.f;
+                        }
+            }
+        }
+    };
+
     setup_tap();
     load_chunk(ra0, rb0);
     store_chunk(0, ra0, rb0);
@@ -216,11 +249,13 @@ k_conv_mfma_fwd(ConvIn in, const float* __restrict__ w, const float* __restrict_
             if (it + 1 < nchunks) store_chunk(1, ra0, rb0);
             if (it + 3 < nchunks) load_chunk(ra0, rb0);
             compute(0);
+            fold(it);
             __syncthreads();
             if (it + 1 >= nchunks) break;
             if (it + 2 < nchunks) store_chunk(0, ra1, rb1);
             if (it + 4 < nchunks) load_chunk(ra1, rb1);
             compute(1);
+            fold(it + 1);
             __syncthreads();
         }
     } else {
@@ -230,6 +265,7 @@ k_conv_mfma_fwd(ConvIn in, const float* __restrict__ w, const float* __restrict_
             const int cur = it & 1;
             if (it + 1 < nchunks) load_chunk(ra0, rb0);
             compute(cur);
+            fold(it);
             if (it + 1 < nchunks) store_chunk(cur ^ 1, ra0, rb0);
             __syncthreads();
         }
@@ -325,7 +361,23 @@ static ConvGeom plain_geom(int ks, int dil, int tap0 = -1) {
     return g;
 }
 
-template <int BM, int BN, int WM, int WN, int KC, bool DEEP>
+// out_mode 1 with four taps per parity: (py - 1 + a, px - 1 + b) on the low-resolution grid, a, b in {0, 1}
+static ConvGeom parity2x2_geom() {
+    ConvGeom g{};
+    g.ntaps = 4;
+    g.out_mode = 1;
+    for (int p = 0; p < 4; ++p) {
+        g.ptap0[p] = (signed char)(4 * p);
+        g.pntaps[p] = 4;
+        for (int t = 0; t < 4; ++t) {
+            g.dy[4 * p + t] = (signed char)((p >> 1) - 1 + (t >> 1));
+            g.dx[4 * p + t] = (signed char)((p & 1) - 1 + (t & 1));
+        }
+    }
+    return g;
+}
+
+template <int BM, int BN, int WM, int WN, int KC, bool DEEP, bool FOLD = false>
 static int launch_fwd(const ConvIn& in, const float* w, const float* bias, float* y, int N, int H, int W, int Cout,
                       const ConvGeom& geo, int relu, hipStream_t st, float* stats = nullptr) {
     if (stats && ((long)H * W) % BM != 0) { vqw_set_error("conv_mfma_fwd: statistics need H*W to be a multiple of the pixel tile"); return VQW_ERR_ARG; }
@@ -334,7 +386,7 @@ static int launch_fwd(const ConvIn& in, const float* w, const float* bias, float
     const long src_px = geo.src_mode == 2 ? 4 * P : (in.up0 ? P / 4 : P);
     const unsigned nb0 = (unsigned)(src_px * in.C0 * 4), nb1 = (unsigned)(P * in.C1 * 4);
     const unsigned nbw = (unsigned)((long)Cout * geo.ntaps * (in.C0 + in.C1) * 4);
-    k_conv_mfma_fwd<BM, BN, WM, WN, KC, DEEP><<<dim3(ntm * ntn, geo.out_mode == 1 ? 4 : 1), 256, 0, st>>>(
+    k_conv_mfma_fwd<BM, BN, WM, WN, KC, DEEP, FOLD><<<dim3(ntm * ntn, geo.out_mode == 1 ? 4 : 1), 256, 0, st>>>(
         in, w, bias, y, N, H, W, Cout, geo, ntn, relu, nb0, nb1, nbw, stats);
     VQW_LAUNCH_CHECK("conv_mfma_fwd");
     return VQW_OK;
@@ -434,10 +486,7 @@ int conv_up2_fwd(const float* x_low, const float* ws, const float* bias, float* 
     if (conv_halo_up2_ok(Cin, Cout, N, h, w) && (!stats || conv_halo_up2_stat_tiles(h, w) > 0))
         return conv_halo_up2_fwd(x_low, ws, bias, y, N, h, w, Cin, Cout, relu, st, stats);
     ConvIn in{x_low, nullptr, Cin, 0, 0};
-    ConvGeom g{};
-    g.ntaps = 4;
-    g.out_mode = 1;      // parity = blockIdx.y; tap offsets and the weight block are derived from it in the kernel
-    return dispatch_fwd(in, ws, bias, y, N, h, w, Cout, g, relu, st, stats);
+    return dispatch_fwd(in, ws, bias, y, N, h, w, Cout, parity2x2_geom(), relu, st, stats);
 }
 bool conv_up2_dgrad_is_wino(int Cin, int Cout, int N, int h, int w) { return conv_wino_up_dgrad_ok(Cin, Cout, N, h, w); }
 bool conv_up2_fwd_is_wino(int Cin, int Cout, int N, int h, int w) { return conv_wino_up_fwd_ok(Cin, Cout, N, h, w); }
@@ -501,10 +550,74 @@ int conv_k4s2_dgrad(const float* gy_low, const float* w, float* ws, float* gx_hi
     k_pack_k4s2_dgrad<<<stream_grid(n, 256), 256, 0, st>>>(w, ws, Cout, Cin);
     VQW_LAUNCH_CHECK("pack_k4s2_dgrad");
     ConvIn in{gy_low, nullptr, Cout, 0, 0};
+    return dispatch_fwd(in, ws, nullptr, gx_high, N, h, w_, Cin, parity2x2_geom(), 0, st);
+}
+// ---------------------------------------------------------------------------------------------
+// 3x3 stride-2 convolution behind a bottom / right zero pad of one pixel (the VQGAN Downsample), (2h, 2w) -> (h, w).
+//   forward:  nine taps at (2y + ky, 2x + kx) (src_mode 2); taps past the bottom / right edge read the zero padding.
+//   dgrad:    gx[2y + py, 2x + px] takes the taps with ky = py, kx = px (mod 2): 4 / 2 / 2 / 1 per parity (out_mode 1),
+//             ky = 2a reads gy row y - a, ky = 1 reads row y; weights re-ordered by k_pack_k3s2_dgrad.
+__global__ void k_pack_k3s2_dgrad(const float* __restrict__ w, float* __restrict__ wc, int Cout, int Cin) {
+    // parity block p at Cin * tap0(p) * Cout, tap0 = 0, 4, 6, 8:  wc[ci][a * nx + b][co] = w[co][py ? 1 : 2a][px ? 1 : 2b][ci]
+    long total = 9L * Cin * Cout;
+    long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        int co = (int)(i % Cout);
+        long r = i / Cout;                                   // row (ci, tap) of the concatenated blocks
+        int par = r < 4L * Cin ? 0 : (r < 6L * Cin ? 1 : (r < 8L * Cin ? 2 : 3));
+        int py = par >> 1, px = par & 1, nx = px ? 1 : 2, nt = (py ? 1 : 2) * nx;
+        r -= (long)(par == 0 ? 0 : 2 + 2 * par) * Cin;
+        int t = (int)(r % nt), ci = (int)(r / nt);
+        int ky = py ? 1 : 2 * (t / nx), kx = px ? 1 : 2 * (t % nx);
+        wc[i] = w[(((long)co * 3 + ky) * 3 + kx) * Cin + ci];
+    }
+}
+// the two-level-summation variants (FOLD): 64 couts per tile where Cout allows (twice the accumulators of the plain kernel: the
+// 128-wide tile would not fit two workgroups per CU), else 32; channel counts are multiples of 32
+static int dispatch_fwd_fold(const ConvIn& in, const float* w, const float* bias, float* y, int N, int H, int W, int Cout,
+                             const ConvGeom& geo, hipStream_t st) {
+    const bool deep = geo.ntaps * (in.C0 / 32) >= 12;
+    if (Cout % 64 == 0 && deep) return launch_fwd<128, 64, 64, 32, 32, true, true>(in, w, bias, y, N, H, W, Cout, geo, 0, st);
+    if (Cout % 64 == 0) return launch_fwd<128, 64, 64, 32, 32, false, true>(in, w, bias, y, N, H, W, Cout, geo, 0, st);
+    return launch_fwd<128, 32, 32, 32, 32, false, true>(in, w, bias, y, N, H, W, Cout, geo, 0, st);
+}
+bool conv_k3s2_ok(int Cin, int Cout, int N, int h, int w) {
+    return Cin % 32 == 0 && Cout % 32 == 0 && Cin >= 32 && Cout >= 32 && fits_u32(4L * N * h * w, Cin, Cout);
+}
+int conv_k3s2_fwd(const float* x_high, const float* w, const float* bias, float* y_low, int N, int h, int w_, int Cin, int Cout,
+                  hipStream_t st) {
+    ConvIn in{x_high, nullptr, Cin, 0, 0};
+    ConvGeom g{};
+    g.ntaps = 9;
+    g.src_mode = 2;
+    for (int t = 0; t < 9; ++t) {
+        g.dy[t] = (signed char)(t / 3);
+        g.dx[t] = (signed char)(t % 3);
+    }
+    return dispatch_fwd_fold(in, w, bias, y_low, N, h, w_, Cout, g, st);
+}
+size_t conv_k3s2_dgrad_ws_floats(int Cin, int Cout) { return (size_t)9 * Cin * Cout; }
+int conv_k3s2_dgrad(const float* gy_low, const float* w, float* ws, float* gx_high, int N, int h, int w_, int Cin, int Cout,
+                    hipStream_t st) {
+    long n = 9L * Cin * Cout;
+    k_pack_k3s2_dgrad<<<stream_grid(n, 256), 256, 0, st>>>(w, ws, Cout, Cin);
+    VQW_LAUNCH_CHECK("pack_k3s2_dgrad");
+    ConvIn in{gy_low, nullptr, Cout, 0, 0};
     ConvGeom g{};
     g.ntaps = 4;
     g.out_mode = 1;
-    return dispatch_fwd(in, ws, nullptr, gx_high, N, h, w_, Cin, g, 0, st);
+    int t = 0;
+    for (int p = 0; p < 4; ++p) {
+        const int ny = (p >> 1) ? 1 : 2, nx = (p & 1) ? 1 : 2;
+        g.ptap0[p] = (signed char)t;
+        g.pntaps[p] = (signed char)(ny * nx);
+        for (int a = 0; a < ny; ++a)
+            for (int b = 0; b < nx; ++b, ++t) {
+                g.dy[t] = (signed char)-a;
+                g.dx[t] = (signed char)-b;
+            }
+    }
+    return dispatch_fwd_fold(in, ws, nullptr, gx_high, N, h, w_, Cin, g, st);
 }
 // stride 1 on a common grid: x, y (or gy, gx) are both N x H x W maps; tap0 = 1 forward, 2 for the flipped dgrad weights
 int conv_k4s1_grid(const float* src, const float* w16, const float* bias, float* dst, int N, int H, int W, int Csrc, int Cdst,
@@ -523,7 +636,8 @@ int conv_k5_grid(const float* src, const float* w25, const float* bias, float* d
 // =============================================================================================
 // wgrad, one tap per workgroup (1x1 convs, ragged widths)
 // =============================================================================================
-template <int BM, int BN, int WM, int WN, int KP>
+// S2: the M grid is the (H, W) map of dy and tap (ky, kx) reads pixel (2y + ky - tap0, 2x + kx - tap0) of a 2H x 2W input
+template <int BM, int BN, int WM, int WN, int KP, bool S2 = false>
 __global__ void __launch_bounds__(64 * (BM / WM) * (BN / WN))
 k_conv_mfma_wgrad(ConvIn in, const float* __restrict__ dy, float* __restrict__ part, int N, int H, int W, int Cout, int ks,
                   int dil, int ntm, int ntn, long per_split, int tap0) {
@@ -594,9 +708,11 @@ k_conv_mfma_wgrad(ConvIn in, const float* __restrict__ dy, float* __restrict__ p
         d_p += KP;
 #pragma unroll
         for (int j = 0; j < LX; ++j) {
-            int hy = x_h[j] + dyy, wx = x_w[j] + dxx;
-            bool ok = x_p[j] < pe && x_cok && (unsigned)hy < (unsigned)H && (unsigned)wx < (unsigned)W;
-            unsigned pix = x_up ? ((unsigned)x_n[j] * Hs + (hy >> 1)) * Ws + (wx >> 1) : x_p[j] + (unsigned)shift;
+            int hy = (S2 ? 2 : 1) * x_h[j] + dyy, wx = (S2 ? 2 : 1) * x_w[j] + dxx;
+            bool ok = x_p[j] < pe && x_cok && (unsigned)hy < (unsigned)((S2 ? 2 : 1) * H) && (unsigned)wx < (unsigned)((S2 ? 2 : 1) * W);
+            unsigned pix = S2     ? ((unsigned)x_n[j] * (2 * H) + hy) * (2 * W) + wx
+                           : x_up ? ((unsigned)x_n[j] * Hs + (hy >> 1)) * Ws + (wx >> 1)
+                                  : x_p[j] + (unsigned)shift;
             rx[j] = ld4_or_zero(x_src + (size_t)pix * xC, ok);
             // advance this slot by KP pixels
             x_p[j] += KP;
@@ -878,6 +994,9 @@ static inline int wg9_split_blocks(int Cin, int Cout, long P) {
 // full-resolution pixels of a row Y = 2y+py.  k-steps pair pixels of EQUAL column parity (X, X+2), so both k slots of
 // an MFMA share the same (px, a, b); the dY tile and two 18-pixel halo segments of X_low sit in the wave's private LDS.
 // Slab layout [split][py][Cout][8][Cin]; k_reduce_wgup folds it into dW (and accumulates if asked).
+// K3 (the 3x3 stride-2 weight gradient, roles swapped as for the 4x4 one below): only nine of the sixteen G matrices exist,
+// the ones with (py, a) != (1, 1) and (px, b) != (1, 1); the others are neither multiplied nor written.
+template <bool K3>
 __global__ void __launch_bounds__(256, 2)
 k_conv_wgrad_up(const float* __restrict__ xlow, const float* __restrict__ dy, float* __restrict__ part, float* __restrict__ bias_part,
                 int N, int h, int w, int Cin, int Cout, int n_ci_t, int ntiles, int nsplit_blocks, unsigned nbx, unsigned nbd) {
@@ -957,11 +1076,12 @@ k_conv_wgrad_up(const float* __restrict__ xlow, const float* __restrict__ dy, fl
             const float* x0 = Xs + xr * 32 + lcol;
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
-                const float v0 = x0[(a * 18 + 0) * 32], v1 = x0[(a * 18 + 1) * 32], v2 = x0[(a * 18 + 2) * 32];
+                if (K3 && a == 1 && py == 1) continue;            // uniform over the workgroup
+                const float v0 = x0[(a * 18 + 0) * 32], v1 = x0[(a * 18 + 1) * 32];
                 acc[0 * 4 + a * 2 + 0] = MFMA32(ae, v0, acc[0 * 4 + a * 2 + 0]);   // px=0: columns xr + b
                 acc[0 * 4 + a * 2 + 1] = MFMA32(ae, v1, acc[0 * 4 + a * 2 + 1]);
                 acc[1 * 4 + a * 2 + 0] = MFMA32(ao, v1, acc[1 * 4 + a * 2 + 0]);   // px=1: columns xr + 1 + b
-                acc[1 * 4 + a * 2 + 1] = MFMA32(ao, v2, acc[1 * 4 + a * 2 + 1]);
+                if (!K3) acc[1 * 4 + a * 2 + 1] = MFMA32(ao, x0[(a * 18 + 2) * 32], acc[1 * 4 + a * 2 + 1]);
             }
         }
     }
@@ -978,6 +1098,7 @@ k_conv_wgrad_up(const float* __restrict__ xlow, const float* __restrict__ dy, fl
     const int ci = ci_base + (lane & 31);
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
+        if (K3 && (t == 5 || t == 7 || (py == 1 && (t & 2)))) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             int co = co_base + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
@@ -1051,7 +1172,7 @@ int conv_up2_wgrad(const float* xlow, const float* dy, float* dw, float* dbias, 
     const int nsb = wgup_split_blocks(Cin, Cout, Plow);
     const unsigned nbx = (unsigned)(Plow * Cin * 4), nbd = (unsigned)(4 * Plow * Cout * 4);
     float* bpart = dbias ? ws + (size_t)nsb * 4 * 2 * Cout * 8 * Cin : nullptr;
-    k_conv_wgrad_up<<<ntiles * 2 * nsb, 256, 0, st>>>(xlow, dy, ws, bpart, N, h, w, Cin, Cout, n_ci_t, ntiles, nsb, nbx, nbd);
+    k_conv_wgrad_up<false><<<ntiles * 2 * nsb, 256, 0, st>>>(xlow, dy, ws, bpart, N, h, w, Cin, Cout, n_ci_t, ntiles, nsb, nbx, nbd);
     VQW_LAUNCH_CHECK("conv_wgrad_up");
     if (dbias) {
         int rc = reduce_rows(bpart, dbias, Cout, nsb * 4 * 2, st, acc);
@@ -1066,15 +1187,17 @@ int conv_up2_wgrad(const float* xlow, const float* dy, float* dw, float* dbias, 
 // 4x4 stride-2 pad-1 weight gradient (PatchGAN): dW[co][ky][kx][ci] = sum dYlow[y, x][co] * Xhigh[2y + ky - 1, 2x + kx - 1][ci]
 // is the G matrix set of the kernel above with the roles swapped (Xhigh in the "dY" slot, dYlow in the "Xlow" slot):
 // slab[split][py][ci][px*4 + a*2 + b][co] with ky = 3 - py - 2a, kx = 3 - px - 2b.
+// The 3x3 stride-2 weight gradient behind a bottom / right pad (ks = 3) is the same sum without the top / left pad: its
+// tap (ky, kx) is the 4x4 form's (ky + 1, kx + 1), and the seven G matrices of a 4x4 tap with ky = 0 or kx = 0 are not computed.
 __global__ void __launch_bounds__(256) k_reduce_wg_k4s2(const float* __restrict__ part, float* __restrict__ dw, int Cout, int Cin,
-                                                         int nsplits, int acc) {
-    const long n = (long)Cout * 16 * Cin;
+                                                         int nsplits, int acc, int ks) {
+    const long n = (long)Cout * ks * ks * Cin;
     long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int ci = (int)(i % Cin);
         const long r = i / Cin;
-        const int t = (int)(r % 16), co = (int)(r / 16);
-        const int ky = t >> 2, kx = t & 3;
+        const int t = (int)(r % (ks * ks)), co = (int)(r / (ks * ks));
+        const int ky = t / ks + 4 - ks, kx = t % ks + 4 - ks;
         const int py = (ky & 1) ? 0 : 1, a = ky >= 2 ? 0 : 1;
         const int px = (kx & 1) ? 0 : 1, b = kx >= 2 ? 0 : 1;
         float v = 0.f;
@@ -1084,19 +1207,24 @@ __global__ void __launch_bounds__(256) k_reduce_wg_k4s2(const float* __restrict_
 }
 bool conv_k4s2_wgrad_ok(int Cin, int Cout, int N, int h, int w) { return conv_up2_wgrad_ok(Cout, Cin, N, h, w); }
 size_t conv_k4s2_wgrad_ws_floats(int Cin, int Cout, int N, int h, int w) { return wgup_ws_floats(Cout, Cin, N, h, w); }
-int conv_k4s2_wgrad(const float* x_high, const float* gy_low, float* dw, float* ws, int N, int h, int w, int Cin, int Cout, int acc,
-                    hipStream_t st) {
+template <int KS>
+static int k4s2_wgrad_launch(const float* x_high, const float* gy_low, float* dw, float* ws, int N, int h, int w, int Cin, int Cout, int acc,
+                             hipStream_t st) {
     const long Plow = (long)N * h * w;
     const int cin_r = Cout, cout_r = Cin;                 // roles inside k_conv_wgrad_up
     const int n_ci_t = ceil_div(cin_r, 32), ntiles = ceil_div(cout_r, 32) * n_ci_t;
     const int nsb = wgup_split_blocks(cin_r, cout_r, Plow);
     const unsigned nbx = (unsigned)(Plow * cin_r * 4), nbd = (unsigned)(4 * Plow * cout_r * 4);
-    k_conv_wgrad_up<<<ntiles * 2 * nsb, 256, 0, st>>>(gy_low, x_high, ws, nullptr, N, h, w, cin_r, cout_r, n_ci_t, ntiles, nsb, nbx, nbd);
+    k_conv_wgrad_up<KS == 3><<<ntiles * 2 * nsb, 256, 0, st>>>(gy_low, x_high, ws, nullptr, N, h, w, cin_r, cout_r, n_ci_t, ntiles, nsb, nbx, nbd);
     VQW_LAUNCH_CHECK("conv_wgrad_up(k4s2)");
-    const long n = (long)Cout * 16 * Cin;
-    k_reduce_wg_k4s2<<<stream_grid(n, 256), 256, 0, st>>>(ws, dw, Cout, Cin, nsb * 4, acc);
+    const long n = (long)Cout * KS * KS * Cin;
+    k_reduce_wg_k4s2<<<stream_grid(n, 256), 256, 0, st>>>(ws, dw, Cout, Cin, nsb * 4, acc, KS);
     VQW_LAUNCH_CHECK("reduce_wg_k4s2");
     return VQW_OK;
+}
+int conv_k4s2_wgrad(const float* x_high, const float* gy_low, float* dw, float* ws, int N, int h, int w, int Cin, int Cout, int acc,
+                    hipStream_t st) {
+    return k4s2_wgrad_launch<4>(x_high, gy_low, dw, ws, N, h, w, Cin, Cout, acc, st);
 }
 // 4x4 stride-1 weight gradient on a common N x H x W grid (dy zero-padded to the grid by the caller)
 int conv_k4s1_wgrad_grid(const float* x, const float* dy_grid, float* dw, float* ws, int N, int H, int W, int Cin, int Cout, int acc,
@@ -1136,7 +1264,7 @@ size_t conv_mfma_wgrad_ws_floats(int Cin, int Cout, int ks, long P) {
     return a > b ? a : b;
 }
 
-template <int BM, int BN, int KP>
+template <int BM, int BN, int KP, bool S2 = false>
 static int launch_wgrad(const ConvIn& in, const float* dy, float* dw, float* ws, int N, int H, int W, int Cout, int ks, int dil,
                         hipStream_t st, int acc, int tap0 = -1) {
     if (tap0 < 0) tap0 = ks >> 1;
@@ -1150,7 +1278,7 @@ static int launch_wgrad(const ConvIn& in, const float* dy, float* dw, float* ws,
     const int ntm = ceil_div(Cout, BM), ntn = ceil_div(Cin, BN);
     const long nout = (long)Cout * ks * ks * Cin;
     float* part = (splits > 1 || acc) ? ws : dw;
-    k_conv_mfma_wgrad<BM, BN, WM, WN, KP><<<ntm * ntn * ks * ks * splits, NT, 0, st>>>(in, dy, part, N, H, W, Cout, ks, dil,
+    k_conv_mfma_wgrad<BM, BN, WM, WN, KP, S2><<<ntm * ntn * ks * ks * splits, NT, 0, st>>>(in, dy, part, N, H, W, Cout, ks, dil,
                                                                                          ntm, ntn, per, tap0);
     VQW_LAUNCH_CHECK("conv_mfma_wgrad");
     if (splits > 1 || acc) return reduce_rows(ws, dw, nout, splits, st, acc);
@@ -1285,5 +1413,34 @@ int conv_k4s1_wgrad_grid(const float* x, const float* dy_grid, float* dw, float*
     WG_CASE(128, 128, 32);
 #undef WG_CASE
     vqw_set_error("conv_k4s1_wgrad_grid: no tile configuration");
+    return VQW_ERR_ARG;
+}
+
+// 3x3 stride-2 weight gradient behind a bottom / right pad: dW[co][ky][kx][ci] = sum dYlow[y, x][co] * Xhigh[2y + ky, 2x + kx][ci].
+// Maps whose low-resolution width is a multiple of 16 take the nine G matrices of k_conv_wgrad_up; any other even size takes
+// the per-tap kernel with the stride-2 source.
+static inline bool k3s2_wgrad_rows(int Cin, int Cout, int N, int h, int w) { return conv_k4s2_wgrad_ok(Cin, Cout, N, h, w); }
+size_t conv_k3s2_wgrad_ws_floats(int Cin, int Cout, int N, int h, int w) {
+    if (k3s2_wgrad_rows(Cin, Cout, N, h, w)) return conv_k4s2_wgrad_ws_floats(Cin, Cout, N, h, w);
+    return (size_t)wgrad_splits(Cin, Cout, 3, (long)N * h * w) * Cout * 9 * Cin;
+}
+int conv_k3s2_wgrad(const float* x_high, const float* gy_low, float* dw, float* ws, int N, int h, int w, int Cin, int Cout, int acc,
+                    hipStream_t st) {
+    if (k3s2_wgrad_rows(Cin, Cout, N, h, w)) return k4s2_wgrad_launch<3>(x_high, gy_low, dw, ws, N, h, w, Cin, Cout, acc, st);
+    ConvIn in{x_high, nullptr, Cin, 0, 0};
+    const int bm = wg_tile(Cout), bn = wg_tile(Cin);
+#define WG_CASE(M_, N_, K_) \
+    if (bm == M_ && bn == N_) return launch_wgrad<M_, N_, K_, true>(in, gy_low, dw, ws, N, h, w, Cout, 3, 1, st, acc, 0)
+    WG_CASE(32, 32, 32);
+    WG_CASE(32, 64, 32);
+    WG_CASE(64, 32, 32);
+    WG_CASE(64, 64, 32);
+    WG_CASE(32, 128, 32);
+    WG_CASE(128, 32, 32);
+    WG_CASE(64, 128, 32);
+    WG_CASE(128, 64, 32);
+    WG_CASE(128, 128, 32);
+#undef WG_CASE
+    vqw_set_error("conv_k3s2_wgrad: no tile configuration");
     return VQW_ERR_ARG;
 }

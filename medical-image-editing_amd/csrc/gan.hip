@@ -486,6 +486,46 @@ extern "C" int vqw_sconv_wgrad(const float* x, const float* gy, float* dw_ohwi, 
     return reduce_rows(part, dw_ohwi, (long)Cout * ks * ks * Cin, nsplit, st, accumulate);
 }
 
+// ---- 3x3 stride-2 convolution behind a bottom / right pad (the VQGAN Downsample) on the MFMA kernels of conv_mfma.hip
+static int check_conv3s2(const char* who, int N, int H, int W, int Cin, int Cout) {
+    VQW_CHECK(N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "%s: N=%d H=%d W=%d: H and W must be even", who, N, H, W);
+    VQW_CHECK(Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0, "%s: Cin=%d Cout=%d must be multiples of 32", who, Cin, Cout);
+    VQW_CHECK(conv_k3s2_ok(Cin, Cout, N, H / 2, W / 2), "%s: tensors of 4 GiB or more are not supported", who);
+    return VQW_OK;
+}
+extern "C" int vqw_conv3s2_fwd(const float* x, const float* w_ohwi, const float* bias, float* y, int N, int H, int W, int Cin,
+                               int Cout, void* stream) {
+    if (int rc = check_conv3s2("vqw_conv3s2_fwd", N, H, W, Cin, Cout)) return rc;
+    VQW_CHECK(x && w_ohwi && y, "vqw_conv3s2_fwd: null pointer");
+    return conv_k3s2_fwd(x, w_ohwi, bias, y, N, H / 2, W / 2, Cin, Cout, (hipStream_t)stream);
+}
+extern "C" size_t vqw_conv3s2_dgrad_ws_bytes(int Cin, int Cout) {
+    return (Cin <= 0 || Cout <= 0) ? 0 : conv_k3s2_dgrad_ws_floats(Cin, Cout) * sizeof(float);
+}
+extern "C" int vqw_conv3s2_dgrad(const float* gy, const float* w_ohwi, float* gx, void* ws, size_t ws_bytes, int N, int H, int W,
+                                 int Cin, int Cout, void* stream) {
+    if (int rc = check_conv3s2("vqw_conv3s2_dgrad", N, H, W, Cin, Cout)) return rc;
+    VQW_CHECK(gy && w_ohwi && gx && ws, "vqw_conv3s2_dgrad: null pointer");
+    VQW_CHECK(ws_bytes >= vqw_conv3s2_dgrad_ws_bytes(Cin, Cout), "vqw_conv3s2_dgrad: workspace too small");
+    return conv_k3s2_dgrad(gy, w_ohwi, (float*)ws, gx, N, H / 2, W / 2, Cin, Cout, (hipStream_t)stream);
+}
+extern "C" size_t vqw_conv3s2_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout) {
+    if (N <= 0 || H < 2 || W < 2 || Cin <= 0 || Cout <= 0) return 0;
+    return (bias_grad_ws_floats(Cout) + conv_k3s2_wgrad_ws_floats(Cin, Cout, N, H / 2, W / 2)) * sizeof(float);
+}
+extern "C" int vqw_conv3s2_wgrad(const float* x, const float* gy, float* dw_ohwi, float* dbias, void* ws, size_t ws_bytes, int N,
+                                 int H, int W, int Cin, int Cout, int accumulate, void* stream) {
+    if (int rc = check_conv3s2("vqw_conv3s2_wgrad", N, H, W, Cin, Cout)) return rc;
+    VQW_CHECK(x && gy && dw_ohwi && ws, "vqw_conv3s2_wgrad: null pointer");
+    VQW_CHECK(ws_bytes >= vqw_conv3s2_wgrad_ws_bytes(N, H, W, Cin, Cout), "vqw_conv3s2_wgrad: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    float* wsf = (float*)ws;
+    if (dbias) {
+        if (int rc = bias_grad(gy, dbias, wsf, (long)N * (H / 2) * (W / 2), Cout, st, accumulate)) return rc;
+    }
+    return conv_k3s2_wgrad(x, gy, dw_ohwi, wsf + bias_grad_ws_floats(Cout), N, H / 2, W / 2, Cin, Cout, accumulate, st);
+}
+
 extern "C" int vqw_leaky_relu_bwd(const float* y, const float* gy, float* gx, float slope, long n, void* stream) {
     VQW_CHECK(y && gy && gx && n > 0, "vqw_leaky_relu_bwd: bad arguments");
     k_leaky_bwd<<<stream_grid(n, 256), 256, 0, (hipStream_t)stream>>>(y, gy, gx, slope, n);

@@ -429,7 +429,8 @@ extern "C" int vqw_swish_bwd(const float* x, const float* gy, float* gx, long n,
 #define AT_KC 128          // channels per staged chunk
 #define AT_LD (AT_KC + 4)  // LDS row stride of a staged chunk: ds_read_b128 of 32 consecutive rows conflict-free
 #define AT_LDS (AT_BN + 4) // LDS row stride of a score tile
-#define AT_MAX_C 512
+#define AT_MAX_C 512        // widest value / output column window one workgroup keeps in registers
+#define AT_MAX_C2 1024      // two such windows: the grid's z dimension
 
 // LDS carve-up (floats).  A: staged 32-row operand chunk; B: staged 64-row operand chunk; T0 / T1: two score tiles as two
 // half-sums each; P0 / P1: the element-wise stage's results (the A operand of attn_gemm_pv); row vectors.
@@ -457,11 +458,14 @@ __device__ __forceinline__ void attn_stage(float* dst, const float* __restrict__
 // T[32][64] = A[a0 .. a0+32) . B[b0 .. b0+64)^T over all C channels, left in LDS as two half-sums T[0], T[1] ([32][AT_LDS]
 // each; the consumer adds them): wave w takes the 32 columns (w & 1) and half (w >> 1) of every chunk's channels.
 // Lane l feeds row / column l % 32; its four consecutive channels 8 s + 4 (l / 32) + {0..3} go to four MFMAs.
+// FOLD (the kernels above 512 channels): every chunk's sum is added to a second accumulator, so that no chain of dependent roundings is longer than
+// at 128 channels (a single chain over 1024 channels left lse twice as far from float64 as torch's fp32 bmm is).
+template <bool FOLD>
 __device__ __forceinline__ void attn_gemm_nt(float* lds, float* T, const float* __restrict__ A, int a0, int na, const float* __restrict__ B,
                                              int b0, int nb, int C) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, kb = wv & 1, hf = wv >> 1;
     const int lr = lane & 31, lh = lane >> 5;
-    f32x16 acc = {0};
+    f32x16 acc = {0}, tot = {0};
     for (int c0 = 0; c0 < C; c0 += AT_KC) {
         const int wt = imin_d(AT_KC, C - c0);
         __syncthreads();                      // the previous users of the staging buffers are done
@@ -478,21 +482,31 @@ __device__ __forceinline__ void attn_gemm_nt(float* lds, float* T, const float* 
             acc = MFMA32(a.z, b.z, acc);
             acc = MFMA32(a.w, b.w, acc);
         }
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { tot[r] += acc[r]; acc[r] = 0.f; }
+        }
     }
+    if constexpr (FOLD) acc = tot;
     float* t = T + hf * (AT_BM * AT_LDS) + kb * 32 + lr;
 #pragma unroll
     for (int r = 0; r < 16; ++r) t[((r & 3) + 8 * (r >> 2) + 4 * lh) * AT_LDS] = acc[r];
     __syncthreads();
 }
 
-// acc[t] (the 32 x 32 block of columns 128 t + 32 w of wave w) += P[32][64] . B[b0 .. b0+64)[C]
+// The value / output side works on a window of Cw = C / gridDim.z columns starting at column blockIdx.z Cw of rows of C floats
+// (one window = the whole row up to 512 channels, two halves above): the callers offset the pointers by attn_col0.
+__device__ __forceinline__ int attn_col0(int C) { return (int)blockIdx.z * (C / (int)gridDim.z); }
+
+// acc[t] (the 32 x 32 block of columns 128 t + 32 w of wave w) += P[32][64] . B[b0 .. b0+64)[window of row stride C]
 template <int CT>
 __device__ __forceinline__ void attn_gemm_pv(float* lds, const float* P, const float* __restrict__ B, int b0, int nb, int C, f32x16 (&acc)[CT]) {
+    const int Cw = C / (int)gridDim.z;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int lr = lane & 31, lh = lane >> 5;
 #pragma unroll
     for (int t = 0; t < CT; ++t) {
-        const int c0 = t * AT_KC, wt = imin_d(AT_KC, C - c0);
+        const int c0 = t * AT_KC, wt = imin_d(AT_KC, Cw - c0);
         __syncthreads();
         attn_stage(lds + AT_OFF_B, B, b0, nb, AT_BN, c0, wt, C);
         __syncthreads();
@@ -511,15 +525,16 @@ __device__ __forceinline__ void attn_gemm_pv(float* lds, const float* P, const f
     }
 }
 
-// out[row0 + row][128 t + 32 w + lane % 32] = acc * f(row) for the valid rows
+// out[row0 + row][128 t + 32 w + lane % 32] = acc * f(row) for the valid rows (columns of the window, rows of C floats)
 template <int CT, class RowScale>
 __device__ __forceinline__ void attn_store(float* __restrict__ out, int row0, int n_rows, int C, const f32x16 (&acc)[CT], RowScale rs) {
+    const int Cw = C / (int)gridDim.z;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int lr = lane & 31, lh = lane >> 5;
 #pragma unroll
     for (int t = 0; t < CT; ++t) {
         const int c = t * AT_KC + wv * 32;
-        if (c < C) {
+        if (c < Cw) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -541,13 +556,13 @@ __device__ __forceinline__ float attn_row8_sum(float v) {       // fixed butterf
     return v;
 }
 
-// grid (ceil(N / 32), B).  Online softmax: running row maximum m and sum l live in the row's eight threads.
-template <int CT>
+// grid (ceil(N / 32), B, column windows).  Online softmax: running row maximum m and sum l live in the row's eight threads.
+template <int CT, bool WIDE>
 __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                   float* __restrict__ o, float* __restrict__ lse, int N, int C, float scale) {
     extern __shared__ __align__(16) float lds[];
     const long boff = (long)blockIdx.y * N * C;
-    q += boff; k += boff; v += boff; o += boff;
+    q += boff; k += boff; v += boff + attn_col0(C); o += boff + attn_col0(C);
     const int i0 = blockIdx.x * AT_BM;
     float* T = lds + AT_OFF_T0;
     float* P = lds + AT_OFF_P0;
@@ -558,7 +573,7 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ q, c
     float m = -INFINITY, l = 0.f;
     const int row = AT_EW_ROW;
     for (int j0 = 0; j0 < N; j0 += AT_BN) {
-        attn_gemm_nt(lds, T, q, i0, N, k, j0, N, C);
+        attn_gemm_nt<WIDE>(lds, T, q, i0, N, k, j0, N, C);
         float s[8], mt = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -595,7 +610,7 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ q, c
     float* rinv = lds + AT_OFF_V + AT_BN;
     if ((threadIdx.x & 7) == 0) {
         rinv[row] = 1.f / l;
-        if (i0 + row < N) lse[(long)blockIdx.y * N + i0 + row] = m + logf(l);
+        if (i0 + row < N && blockIdx.z == 0) lse[(long)blockIdx.y * N + i0 + row] = m + logf(l);
     }
     __syncthreads();
     attn_store<CT>(o, i0, N, C, acc, [&](int r) { return rinv[r]; });
@@ -639,13 +654,13 @@ __device__ __forceinline__ void attn_bwd_stage(float* lds, const float* vec, int
 }
 
 // grid (ceil(N / 32), B): dQ = scale (P o (dO v^T - D)) k for a tile of 32 queries, walking the keys
-template <int CT>
+template <int CT, bool WIDE>
 __global__ void __launch_bounds__(256) k_attn_dq(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                  const float* __restrict__ go, const float* __restrict__ lse, const float* __restrict__ D,
                                                  float* __restrict__ gq, int N, int C, float scale) {
     extern __shared__ __align__(16) float lds[];
     const long boff = (long)blockIdx.y * N * C;
-    q += boff; k += boff; v += boff; go += boff; gq += boff;
+    q += boff; k += boff; v += boff; go += boff; gq += boff + attn_col0(C);
     lse += (long)blockIdx.y * N; D += (long)blockIdx.y * N;
     const int i0 = blockIdx.x * AT_BM;
     float* vec = lds + AT_OFF_V;
@@ -658,22 +673,22 @@ __global__ void __launch_bounds__(256) k_attn_dq(const float* __restrict__ q, co
 #pragma unroll
     for (int t = 0; t < CT; ++t) acc[t] = (f32x16){0};
     for (int j0 = 0; j0 < N; j0 += AT_BN) {
-        attn_gemm_nt(lds, lds + AT_OFF_T0, q, i0, N, k, j0, N, C);
-        attn_gemm_nt(lds, lds + AT_OFF_T1, go, i0, N, v, j0, N, C);
+        attn_gemm_nt<WIDE>(lds, lds + AT_OFF_T0, q, i0, N, k, j0, N, C);
+        attn_gemm_nt<WIDE>(lds, lds + AT_OFF_T1, go, i0, N, v, j0, N, C);
         attn_bwd_stage<true>(lds, vec, i0, j0, N, scale, false);
-        attn_gemm_pv<CT>(lds, lds + AT_OFF_P1, k, j0, N, C, acc);
+        attn_gemm_pv<CT>(lds, lds + AT_OFF_P1, k + attn_col0(C), j0, N, C, acc);
     }
     attn_store<CT>(gq, i0, N, C, acc, [](int) { return 1.f; });
 }
 
 // grid (ceil(N / 32), B): dK = scale (P o (dO v^T - D))^T q and dV = P^T dO for a tile of 32 keys, walking the queries
-template <int CT>
+template <int CT, bool WIDE>
 __global__ void __launch_bounds__(256) k_attn_dkdv(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                    const float* __restrict__ go, const float* __restrict__ lse, const float* __restrict__ D,
                                                    float* __restrict__ gk, float* __restrict__ gv, int N, int C, float scale) {
     extern __shared__ __align__(16) float lds[];
     const long boff = (long)blockIdx.y * N * C;
-    q += boff; k += boff; v += boff; go += boff; gk += boff; gv += boff;
+    q += boff; k += boff; v += boff; go += boff; gk += boff + attn_col0(C); gv += boff + attn_col0(C);
     lse += (long)blockIdx.y * N; D += (long)blockIdx.y * N;
     const int j0 = blockIdx.x * AT_BM;
     float* vec = lds + AT_OFF_V;
@@ -687,11 +702,11 @@ __global__ void __launch_bounds__(256) k_attn_dkdv(const float* __restrict__ q, 
             vec[threadIdx.x] = ok ? lse[i0 + threadIdx.x] : 0.f;
             vec[AT_BN + threadIdx.x] = ok ? D[i0 + threadIdx.x] : 0.f;
         }
-        attn_gemm_nt(lds, lds + AT_OFF_T0, k, j0, N, q, i0, N, C);
-        attn_gemm_nt(lds, lds + AT_OFF_T1, v, j0, N, go, i0, N, C);
+        attn_gemm_nt<WIDE>(lds, lds + AT_OFF_T0, k, j0, N, q, i0, N, C);
+        attn_gemm_nt<WIDE>(lds, lds + AT_OFF_T1, v, j0, N, go, i0, N, C);
         attn_bwd_stage<false>(lds, vec, j0, i0, N, scale, true);
-        attn_gemm_pv<CT>(lds, lds + AT_OFF_P0, go, i0, N, C, av);
-        attn_gemm_pv<CT>(lds, lds + AT_OFF_P1, q, i0, N, C, ak);
+        attn_gemm_pv<CT>(lds, lds + AT_OFF_P0, go + attn_col0(C), i0, N, C, av);
+        attn_gemm_pv<CT>(lds, lds + AT_OFF_P1, q + attn_col0(C), i0, N, C, ak);
     }
     attn_store<CT>(gk, j0, N, C, ak, [](int) { return 1.f; });
     attn_store<CT>(gv, j0, N, C, av, [](int) { return 1.f; });
@@ -699,24 +714,28 @@ __global__ void __launch_bounds__(256) k_attn_dkdv(const float* __restrict__ q, 
 
 static int attn_check(const char* name, int B, int N, int C) {
     VQW_CHECK(B >= 1 && B <= 65535 && N >= 1 && N <= (1 << 20), "%s: bad shape B=%d N=%d", name, B, N);
-    VQW_CHECK(C >= 32 && C % 32 == 0 && C <= AT_MAX_C, "%s: C=%d must be a multiple of 32, at most %d", name, C, AT_MAX_C);
+    VQW_CHECK(C >= 32 && ((C % 32 == 0 && C <= AT_MAX_C) || (C % 64 == 0 && C <= AT_MAX_C2)),
+              "%s: C=%d must be a multiple of 32 up to %d or a multiple of 64 up to %d", name, C, AT_MAX_C, AT_MAX_C2);
     return VQW_OK;
 }
+// column windows of the value / output side (the grid's z dimension), and the 128-channel blocks of one window
+static inline int attn_windows(int C) { return C > AT_MAX_C ? 2 : 1; }
+static inline int attn_ct(int C) { return ceil_div(C / attn_windows(C), AT_KC); }
 
-template <int CT>
+template <int CT, bool WIDE = false>
 static int attn_fwd_launch(const float* q, const float* k, const float* v, float* o, float* lse, int B, int N, int C, float scale, hipStream_t st) {
-    if (int rc = lds_opt_in<k_attn_fwd<CT>>(AT_LDS_BYTES, "vqw_attention_fwd")) return rc;
-    hipLaunchKernelGGL((k_attn_fwd<CT>), dim3(ceil_div(N, AT_BM), B), dim3(256), AT_LDS_BYTES, st, q, k, v, o, lse, N, C, scale);
+    if (int rc = lds_opt_in<k_attn_fwd<CT, WIDE>>(AT_LDS_BYTES, "vqw_attention_fwd")) return rc;
+    hipLaunchKernelGGL((k_attn_fwd<CT, WIDE>), dim3(ceil_div(N, AT_BM), B, attn_windows(C)), dim3(256), AT_LDS_BYTES, st, q, k, v, o, lse, N, C, scale);
     return VQW_OK;
 }
-template <int CT>
+template <int CT, bool WIDE = false>
 static int attn_bwd_launch(const float* q, const float* k, const float* v, const float* go, const float* lse, const float* D, float* gq,
                            float* gk, float* gv, int B, int N, int C, float scale, hipStream_t st) {
-    if (int rc = lds_opt_in<k_attn_dq<CT>>(AT_LDS_BYTES, "vqw_attention_bwd")) return rc;
-    if (int rc = lds_opt_in<k_attn_dkdv<CT>>(AT_LDS_BYTES, "vqw_attention_bwd")) return rc;
-    const dim3 grid(ceil_div(N, AT_BM), B);
-    hipLaunchKernelGGL((k_attn_dq<CT>), grid, dim3(256), AT_LDS_BYTES, st, q, k, v, go, lse, D, gq, N, C, scale);
-    hipLaunchKernelGGL((k_attn_dkdv<CT>), grid, dim3(256), AT_LDS_BYTES, st, q, k, v, go, lse, D, gk, gv, N, C, scale);
+    if (int rc = lds_opt_in<k_attn_dq<CT, WIDE>>(AT_LDS_BYTES, "vqw_attention_bwd")) return rc;
+    if (int rc = lds_opt_in<k_attn_dkdv<CT, WIDE>>(AT_LDS_BYTES, "vqw_attention_bwd")) return rc;
+    const dim3 grid(ceil_div(N, AT_BM), B, attn_windows(C));
+    hipLaunchKernelGGL((k_attn_dq<CT, WIDE>), grid, dim3(256), AT_LDS_BYTES, st, q, k, v, go, lse, D, gq, N, C, scale);
+    hipLaunchKernelGGL((k_attn_dkdv<CT, WIDE>), grid, dim3(256), AT_LDS_BYTES, st, q, k, v, go, lse, D, gk, gv, N, C, scale);
     return VQW_OK;
 }
 
@@ -727,7 +746,9 @@ extern "C" int vqw_attention_fwd(const float* q, const float* k, const float* v,
     VQW_CHECK(gn_al16(q) && gn_al16(k) && gn_al16(v), "vqw_attention_fwd: tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    switch (ceil_div(C, AT_KC)) {
+    if (attn_windows(C) == 2) {          // 576 ... 1024 channels: windows of 288 ... 512, three or four 128-channel blocks
+        rc = attn_ct(C) == 3 ? attn_fwd_launch<3, true>(q, k, v, o, lse, B, N, C, scale, st) : attn_fwd_launch<4, true>(q, k, v, o, lse, B, N, C, scale, st);
+    } else switch (attn_ct(C)) {
         case 1: rc = attn_fwd_launch<1>(q, k, v, o, lse, B, N, C, scale, st); break;
         case 2: rc = attn_fwd_launch<2>(q, k, v, o, lse, B, N, C, scale, st); break;
         case 3: rc = attn_fwd_launch<3>(q, k, v, o, lse, B, N, C, scale, st); break;
@@ -747,7 +768,10 @@ extern "C" int vqw_attention_bwd(const float* q, const float* k, const float* v,
     const long rows = (long)B * N;
     hipLaunchKernelGGL(k_attn_rowdot, dim3(ceil_div(rows, 4)), dim3(256), 0, st, go, o, d_ws, rows, C);
     int rc;
-    switch (ceil_div(C, AT_KC)) {
+    if (attn_windows(C) == 2) {
+        rc = attn_ct(C) == 3 ? attn_bwd_launch<3, true>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st)
+                             : attn_bwd_launch<4, true>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st);
+    } else switch (attn_ct(C)) {
         case 1: rc = attn_bwd_launch<1>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st); break;
         case 2: rc = attn_bwd_launch<2>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st); break;
         case 3: rc = attn_bwd_launch<3>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st); break;

@@ -883,14 +883,13 @@ extern "C" int vqw_vq_fwd(const float* x, const float* embed, int64_t* ids, int 
 
 // EMA (vq_module.py:132-136,195-196) + Laplace-smoothed renormalisation (:198-200).  One workgroup per 32 (d) x 32 (k)
 // tile of embed_avg; every workgroup derives n = sum_k cluster_size_new[k] itself from the OLD cluster sizes and the
-// counts (same order everywhere), k_vq_ema_cs then writes the new cluster sizes.
+// counts (same order everywhere), k_vq_ema_cs then writes the new cluster sizes.  om: the weight of the new statistics.
 __global__ void __launch_bounds__(256) k_vq_ema(const double* __restrict__ stats, float* __restrict__ embed, const float* __restrict__ cs,
-                                                float* __restrict__ ea, float m, float eps, float sum_scale, int D, int K) {
+                                                float* __restrict__ ea, float m, float om, float eps, float sum_scale, int D, int K) {
     __shared__ double s_red[4];
     __shared__ float s_n;
     __shared__ float s_t[32][33];
     const int t = threadIdx.x;
-    const float om = 1.f - m;
     double part = 0.0;
     for (int k = t; k < K; k += 256) part += (double)(cs[k] * m + om * (float)stats[k]);
     part = wave_sum_d(part);
@@ -921,18 +920,25 @@ __global__ void __launch_bounds__(256) k_vq_ema(const double* __restrict__ stats
         if (d < D && k < K) embed[(long)k * D + d] = s_t[tx][ty + 8 * r];
     }
 }
-__global__ void k_vq_ema_cs(const double* __restrict__ stats, float* __restrict__ cs, float m, int K) {
+__global__ void k_vq_ema_cs(const double* __restrict__ stats, float* __restrict__ cs, float m, float om, int K) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < K) cs[k] = cs[k] * m + (1.f - m) * (float)stats[k];
+    if (k < K) cs[k] = cs[k] * m + om * (float)stats[k];
+}
+// new_weight: what the new statistics are multiplied by.  torch's base.mul_(m).add_(update, alpha=1 - m) forms 1 - m in double
+// and rounds it once (0.0099999998 at m = 0.99); 1.f - (float)m is 0.0099999905, 9.5e-7 apart.
+extern "C" int vqw_vq_ema_update_w(const double* stats, float* embed, float* cluster_size, float* embed_avg, float momentum,
+                                   float new_weight, float eps, float sum_scale, int D, int K, void* stream) {
+    VQW_CHECK(stats && embed && cluster_size && embed_avg && D > 0 && K > 0, "vqw_vq_ema_update: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    k_vq_ema<<<ceil_div(D, 32) * ceil_div(K, 32), 256, 0, st>>>(stats, embed, cluster_size, embed_avg, momentum, new_weight, eps,
+                                                                 sum_scale, D, K);
+    k_vq_ema_cs<<<ceil_div(K, 256), 256, 0, st>>>(stats, cluster_size, momentum, new_weight, K);
+    VQW_LAUNCH_CHECK("vqw_vq_ema_update");
+    return VQW_OK;
 }
 extern "C" int vqw_vq_ema_update(const double* stats, float* embed, float* cluster_size, float* embed_avg, float momentum,
                                  float eps, float sum_scale, int D, int K, void* stream) {
-    VQW_CHECK(stats && embed && cluster_size && embed_avg && D > 0 && K > 0, "vqw_vq_ema_update: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    k_vq_ema<<<ceil_div(D, 32) * ceil_div(K, 32), 256, 0, st>>>(stats, embed, cluster_size, embed_avg, momentum, eps, sum_scale, D, K);
-    k_vq_ema_cs<<<ceil_div(K, 256), 256, 0, st>>>(stats, cluster_size, momentum, K);
-    VQW_LAUNCH_CHECK("vqw_vq_ema_update");
-    return VQW_OK;
+    return vqw_vq_ema_update_w(stats, embed, cluster_size, embed_avg, momentum, 1.f - momentum, eps, sum_scale, D, K, stream);
 }
 
 // One Lloyd update of the k-means codebook initialisation (unet_encoder.py:66-91; kmeans_pytorch's loop): centre k

@@ -2433,7 +2433,7 @@ def weighted_sum(terms, weights):
 # ----------------------------------------------------------------------------------------------
 class _VQ(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, embed, cluster_size, embed_avg, training, momentum, eps, dist_mode, id_base):
+    def forward(ctx, x, embed, cluster_size, embed_avg, training, momentum, eps, dist_mode, id_base, torch_ema_weight):
         _dev(x, embed, cluster_size, embed_avg)
         x = nhwc(x)
         N, D, H, W = x.shape
@@ -2463,7 +2463,10 @@ class _VQ(torch.autograd.Function):
                     scale = 1.0 / dist.get_world_size()
                 else:
                     raise RuntimeError("unknown VQ dist_mode %r" % dist_mode)
-            L.vqw_vq_ema_update(stats, embed, cluster_size, embed_avg, momentum, eps, scale, D, K)
+            if torch_ema_weight:         # the double 1 - momentum, rounded once by the call: torch's add_(update, alpha=1 - momentum)
+                L.vqw_vq_ema_update_w(stats, embed, cluster_size, embed_avg, momentum, 1.0 - momentum, eps, scale, D, K)
+            else:
+                L.vqw_vq_ema_update(stats, embed, cluster_size, embed_avg, momentum, eps, scale, D, K)
         _order_end(embed, cur)
         ctx.save_for_backward(x, q)
         ctx.mark_non_differentiable(ids)
@@ -2473,18 +2476,21 @@ class _VQ(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gq, gcommit, _gids):
         if gq is None and gcommit is None:
-            return (None,) * 9
+            return (None,) * 10
         x, q = ctx.saved_tensors
         gq = nhwc(gq) if gq is not None else None
         gc = gcommit.contiguous() if gcommit is not None else None
         gx = torch.empty_like(x, memory_format=CL)
         _L().vqw_vq_bwd(x, q, gq, gc, gx, x.numel())
-        return gx, None, None, None, None, None, None, None, None
+        return gx, None, None, None, None, None, None, None, None, None
 
 
-def vq_quantize(x, embed, cluster_size, embed_avg, training, momentum, eps, dist_mode="global", id_base=0):
-    """-> (quantized with straight-through gradient, commit loss, ids (N,H,W) int64 = code + id_base, per pixel)."""
-    return _VQ.apply(x, embed, cluster_size, embed_avg, bool(training), float(momentum), float(eps), dist_mode, int(id_base))
+def vq_quantize(x, embed, cluster_size, embed_avg, training, momentum, eps, dist_mode="global", id_base=0, torch_ema_weight=False):
+    """-> (quantized with straight-through gradient, commit loss, ids (N,H,W) int64 = code + id_base, per pixel).
+    torch_ema_weight: the EMA weighs the new statistics with the double 1 - momentum rounded once, as torch does, instead of
+    1.f - momentum formed in float32 (the default, which the U-Net models' recorded steps were taken with)."""
+    return _VQ.apply(x, embed, cluster_size, embed_avg, bool(training), float(momentum), float(eps), dist_mode, int(id_base),
+                     bool(torch_ema_weight))
 
 
 def kmeans_codebook(features, dict_size, seed=0, tol=1e-4, max_iter=100, return_ids=False):
@@ -2736,6 +2742,49 @@ class _SConv(torch.autograd.Function):
 def sconv2d(x, weight, bias=None, stride=1, padding=0, slope=1.0):
     """nn.Conv2d(k, stride in {1,2}, padding) with an optional LeakyReLU(slope) epilogue."""
     return _SConv.apply(x, weight, bias, int(stride), int(padding), float(slope))
+
+
+class _ConvDown2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _dev(x, weight, bias)
+        x, w = nhwc(x), nhwc(weight)
+        Cout, Cin, kh, kw = weight.shape
+        N, _, H, W = x.shape
+        if (kh, kw) != (3, 3) or x.shape[1] != Cin:
+            raise RuntimeError("conv2d_down2: a 3x3 weight over the input's %d channels is expected, got %s" % (x.shape[1], tuple(weight.shape)))
+        if bias is not None:
+            bias = _flat(bias)
+        y = empty_nhwc(N, Cout, H // 2, W // 2, x)
+        _L().vqw_conv3s2_fwd(x, w, bias, y, N, H, W, Cin, Cout)        # refuses odd H / W and channel counts off 32
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        L = _L()
+        gy = nhwc(gy)
+        Cout, Cin = w.shape[:2]
+        N, _, H, W = x.shape
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x, memory_format=CL)
+            ws = _ws(L.vqw_conv3s2_dgrad_ws_bytes(Cin, Cout), gy)
+            L.vqw_conv3s2_dgrad(gy, w, gx, ws, ws.numel(), N, H, W, Cin, Cout)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gw = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=gy.device, memory_format=CL)
+            gb = torch.empty(Cout, dtype=torch.float32, device=gy.device) if ctx.has_bias else None
+            ws = _ws(L.vqw_conv3s2_wgrad_ws_bytes(N, H, W, Cin, Cout), gy)
+            L.vqw_conv3s2_wgrad(x, gy, gw, gb, ws, ws.numel(), N, H, W, Cin, Cout, 0)
+        return gx, gw, gb
+
+
+def conv2d_down2(x, weight, bias=None):
+    """nn.Conv2d(C, C', 3, stride=2, padding=0) behind F.pad(x, (0, 1, 0, 1)): the VQGAN Downsample (vqgan.py:40-58).
+    H and W even, both channel counts multiples of 32."""
+    return _ConvDown2.apply(x, weight, bias)
 
 
 class _BnLrelu(torch.autograd.Function):

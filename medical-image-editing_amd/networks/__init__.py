@@ -10,3 +10,4 @@ from .random_transform import RandomTransform  # noqa: F401
 from .discriminator import NLayerDiscriminator  # noqa: F401
 from .unet_discriminator import UNetDiscriminator  # noqa: F401
 from .vqgan import Normalize, nonlinearity, Upsample, ResnetBlock, AttnBlock, Decoder  # noqa: F401
+from .vqgan_model import Downsample, Encoder, VQGAN  # noqa: F401

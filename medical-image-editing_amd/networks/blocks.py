@@ -17,18 +17,22 @@ from hipops import ops
 
 class Conv2d(nn.Conv2d):
     """nn.Conv2d parameter holder (same init, same state_dict entries) whose forward is the HIP
-    implicit-GEMM convolution.  'same' padding, stride 1, kernel 1 or 3 only — all the path uses."""
+    implicit-GEMM convolution.  'same' padding, stride 1, kernel 1 or 3 — and kernel 3, stride 2, padding 0, which is
+    evaluated behind a bottom / right zero pad of one pixel (the VQGAN Downsample): all the path uses."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias=bias)
         k, d = self.kernel_size[0], self.dilation[0]
-        if self.kernel_size[0] != self.kernel_size[1] or k not in (1, 3) or self.stride != (1, 1) \
-                or self.padding != (d * (k // 2),) * 2 or self.dilation[0] != self.dilation[1]:
-            raise NotImplementedError("HIP conv supports kernel 1/3, stride 1, padding = dilation*(k//2)")
+        self.down2 = (self.kernel_size, self.stride, self.padding, self.dilation) == ((3, 3), (2, 2), (0, 0), (1, 1))
+        if not self.down2 and (self.kernel_size[0] != self.kernel_size[1] or k not in (1, 3) or self.stride != (1, 1)
+                               or self.padding != (d * (k // 2),) * 2 or self.dilation[0] != self.dilation[1]):
+            raise NotImplementedError("HIP conv supports kernel 1/3, stride 1, padding = dilation*(k//2), or kernel 3, stride 2, padding 0")
         # OHWI storage (channels_last); logical shape / state_dict unchanged
         self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
 
     def forward(self, x, up2x=False, skip=None, relu=False, want_stats=False, grad_group=None, norm_input=False):
+        if self.down2:
+            return ops.conv2d_down2(x, self.weight, self.bias)
         return ops.conv2d(x, self.weight, self.bias, self.dilation[0], up2x=up2x, skip=skip, relu=relu, want_stats=want_stats,
                           grad_group=grad_group, norm_input=norm_input)
 

@@ -18,6 +18,10 @@ class VQModule(nn.Module):
     # multi-GPU EMA statistics: 'global' = counts and sums over the global batch (equals a single-process run on
     # the concatenated batch); 'reference' = the upstream quirk (rank-mean sums, local counts); 'local' = no exchange
     dist_mode = "global"
+    # EMA weight of the new statistics: False = 1.f - momentum formed in float32 (what the U-Net models' recorded steps were
+    # taken with), True = the double 1 - momentum rounded once, torch's add_(update, alpha=1 - momentum); 9.5e-7 apart at 0.99.
+    # networks.VQGAN sets it on its quantiser.
+    torch_ema_weight = False
 
     def __init__(self, emb_dim: int, dict_size: int, momentum: float, eps: float, knn_backend: Optional[str]) -> None:
         super().__init__()
@@ -41,7 +45,8 @@ class VQModule(nn.Module):
         if input.size(2) != input.size(3):
             raise RuntimeError("VQ expects square maps (the reference's flatten order is only consistent for H == W)")
         q, commit, ids = ops.vq_quantize(input, self.embed, self.cluster_size, self.embed_avg, self.training,
-                                         self.momentum, self.eps, dist_mode=self.dist_mode, id_base=id_base)
+                                         self.momentum, self.eps, dist_mode=self.dist_mode, id_base=id_base,
+                                         torch_ema_weight=self.torch_ema_weight)
         return q, commit, ids.transpose(1, 2)
 
     def lookup(self, ids: torch.Tensor) -> torch.Tensor:

@@ -6,7 +6,7 @@ gives the reference's initial values and a reference checkpoint loads with stric
 GroupNorm(+swish) is one pass of its own (ops.group_norm), the attention is ops.self_attention (the HW x HW score matrix is
 never materialised), the convolutions are ops.conv2d - Upsample's with up2x=True, so the up-sampled tensor is never written.
 
-The reference's Encoder, Downsample (a stride-2 convolution behind an asymmetric pad) and VQGAN are not part of this module.
+The reference's Encoder, Downsample (a stride-2 convolution behind an asymmetric pad) and VQGAN are in networks/vqgan_model.py.
 """
 import torch.nn as nn
 

@@ -82,6 +82,17 @@ def configure_models(config):
 _UNET_DIS_KEYS = ("D_ch", "D_wide", "D_attn", "resolution")
 
 
+def configure_vqgan(config):
+    """The VQGAN autoencoder of config.model.vqgan (reference: trainers/base.py:204-222, the same fourteen keys)."""
+    from networks import VQGAN
+    c = config.model.vqgan
+    return VQGAN(in_channels=c.in_channels, mid_channels=c.mid_channels, out_channels=c.out_channels, emb_dim=c.emb_dim,
+                 dict_size=c.dict_size, enc_ch_multiplier=c.enc_ch_multiplier, dec_ch_multiplier=c.dec_ch_multiplier,
+                 num_res_blocks=c.num_res_blocks, enc_attn_resolutions=c.enc_attn_resolutions,
+                 dec_attn_resolutions=c.dec_attn_resolutions, resolution=c.resolution, p_dropout=c.p_dropout,
+                 resamp_with_conv=c.resamp_with_conv, knn_backend=c.knn_backend)
+
+
 def configure_discriminator(config):
     """-> the discriminator as base.py:239-259 builds it.  PatchGAN: NLayerDiscriminator over config.model.dis, with spectral
     normalisation on its convolutions when dis.apply_spectral_norm is set.  model_name 'UNetDiscriminator': the U-Net
