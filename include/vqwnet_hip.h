@@ -623,7 +623,8 @@ int vqw_lpips_dist_bwd(const float* f, const float* lw, const float* gin, float*
 
 /* ---- 8-bit export (the validation mosaic, the inference export and test-mode pictures: what the reference's to_image /
  *      save_image do on the host, single_window_trainer.py:563-638, 716-779).  Added functions only; the ABI stays 9.
- * Both kernels read every input element once, take B * H * W < 2^31 and B <= 65535, and flip rows top to bottom with flip = 1.
+ * The kernels read every input element once (vqw_export_grey_auto: twice), take B * H * W < 2^31 and B <= 65535, and flip rows
+ * top to bottom with flip = 1.
  * vqw_export_grey: x [B][H][W] float (a (B,1,H,W) tensor in either memory format), win [nwin][6] device floats
  * (alpha, beta, lo, hi, vmin, vmax - vmin), nwin <= 8; out [nwin][B][H][W] bytes,
  *   u8 = min(255, floor(256 * clamp((clamp(alpha * x + beta, lo, hi) - vmin) / (vmax - vmin), 0, 1)))
@@ -635,6 +636,17 @@ int vqw_lpips_dist_bwd(const float* f, const float* lw, const float* gin, float*
 int vqw_export_grey(const float* x, const float* win, uint8_t* out, int nwin, int B, int H, int W, int flip, void* stream);
 int vqw_export_labels(const int64_t* ids, const uint8_t* palette, void* index_out, uint8_t* rgb, int32_t* counts, int32_t* err,
                       int B, int H, int W, int K, int flip, void* stream);
+/* vqw_export_grey_auto: every image through its own range (what matplotlib's imshow does with vmin = vmax = None: the
+ * discriminator maps of the VQGAN trainer's validation picture).  x [B][H][W] float, out [B][H][W] bytes,
+ *   u8 = min(255, floor(256 * clamp((x - vmin_b) / (vmax_b - vmin_b), 0, 1)))
+ * with vmin_b / vmax_b the minimum / maximum over the FINITE values of image b, one float32 rounding per operation.  A
+ * non-finite value exports as 0, and so does every pixel of a constant image and of an image without a finite value.
+ * range (nullable): [B][2] = (vmin_b, vmax_b); (+inf, -inf) for an image without a finite value.  Two passes: per-workgroup
+ * partial minima / maxima into ws (vqw_export_auto_ws_bytes(B) bytes), then each workgroup of the export pass folds its image's
+ * partials: x is read twice, out written once, no floating-point atomics.  Same limits and flip as vqw_export_grey. */
+size_t vqw_export_auto_ws_bytes(int B);
+int vqw_export_grey_auto(const float* x, uint8_t* out, float* range, float* ws, size_t ws_bytes, int B, int H, int W, int flip,
+                         void* stream);
 
 /* ---- preprocessing: NIfTI volumes -> per-slice datasets (the reference's src/preprocess/preprocess_crc.py,
  *      make_crc_testing_dataset.py, preprocess_brats.py).  Added functions only; the ABI stays 9.

@@ -2,7 +2,7 @@
 // counts.  What a validation mosaic, the inference export and a test-mode run copy to the host is then 1 byte (grey), 1-2
 // bytes (index) or 3 bytes (RGB) per pixel instead of float32 images and int64 ids.
 //
-// Both kernels stream: a thread takes four consecutive pixels of one plane (one 16-byte load of floats, two of ids), and
+// The kernels stream: a thread takes four consecutive pixels of one plane (one 16-byte load of floats, two of ids), and
 // stores four bytes per output plane as one dword.  Index arithmetic is 32-bit (B * H * W < 2^31 is checked on entry); the
 // only divisions are the 32-bit row lookups a flipped store needs.  A plane size that is not a multiple of four (planes
 // then start unaligned) and a flipped plane whose rows are not (a group of four then crosses rows) take the one-pixel forms
@@ -206,6 +206,130 @@ __global__ void __launch_bounds__(kBlock) k_export_labels(const int64_t* __restr
     }
 }
 
+// ---- per-image auto-ranged export: a range pass (per-workgroup partial minima / maxima of the finite values), then an export
+// pass whose workgroups each fold their image's partials.  x is read twice, out written once; no floating-point atomics.
+constexpr int kMaxRangeGroups = 64;      // partials per image: one wave folds them
+
+__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }      // false for NaN
+
+__device__ __forceinline__ void take_range(float v, float& lo, float& hi) {
+    if (finite_f(v)) {
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+}
+
+__device__ __forceinline__ void wave_range(float& lo, float& hi) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, o, 64));
+        hi = fmaxf(hi, __shfl_xor(hi, o, 64));
+    }
+}
+
+// workgroups per image of both passes (at most kMaxRangeGroups; fewer for many images)
+int auto_groups(unsigned work, int B) {
+    return imax(1, imin(imin(stream_grid(work, kBlock), kMaxRangeGroups), 2048 / imin(B, 2048)));
+}
+
+// x: [B][HW] floats; part: [B][gridDim.x][2] = this workgroup's (min, max) over the finite values it saw, (+inf, -inf) when
+// it saw none.  grid.y = image.
+template <bool VEC>
+__global__ void __launch_bounds__(kBlock) k_export_range(const float* __restrict__ x, float* __restrict__ part, unsigned HW) {
+    __shared__ float red[2][kBlock / 64];
+    const unsigned b = blockIdx.y;
+    const float* xp = x + (size_t)b * HW;
+    const unsigned step = gridDim.x * kBlock;
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    if (VEC) {
+        const unsigned groups = HW >> 2;
+        for (unsigned g = blockIdx.x * kBlock + threadIdx.x; g < groups; g += step) {
+            const float4_t v = *reinterpret_cast<const float4_t*>(xp + (g << 2));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) take_range(v[j], lo, hi);
+        }
+    } else {
+        for (unsigned p = blockIdx.x * kBlock + threadIdx.x; p < HW; p += step) take_range(xp[p], lo, hi);
+    }
+    wave_range(lo, hi);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = lo;
+        red[1][threadIdx.x >> 6] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 1; i < kBlock / 64; ++i) {
+            lo = fminf(lo, red[0][i]);
+            hi = fmaxf(hi, red[1][i]);
+        }
+        float* o = part + ((size_t)b * gridDim.x + blockIdx.x) * 2;
+        o[0] = lo;
+        o[1] = hi;
+    }
+}
+
+// u8 = min(255, floor(256 * clamp((x - vmin) / (vmax - vmin), 0, 1))): grey_level with the identity window and the image's own
+// (vmin, vmax - vmin); 0 for a non-finite x and for an image whose range is empty or a single value
+__device__ __forceinline__ unsigned auto_level(float x, float vmin, float d) {
+    if (!finite_f(x) || !(d > 0.f)) return 0u;
+    float q = __fdiv_rn(__fsub_rn(x, vmin), d);
+    q = fminf(fmaxf(q, 0.f), 1.f);
+    float l = floorf(__fmul_rn(256.f, q));
+    return (unsigned)fminf(l, 255.f);
+}
+
+// part: [B][nparts][2] from k_export_range; out: [B][HW] bytes; range (nullable): [B][2] = (vmin, vmax).  grid.y = image.
+template <bool VEC>
+__global__ void __launch_bounds__(kBlock) k_export_grey_auto(const float* __restrict__ x, const float* __restrict__ part,
+                                                             uint8_t* __restrict__ out, float* __restrict__ range, int nparts,
+                                                             unsigned H, unsigned W, int flip, int vec_store) {
+    __shared__ float rng[2];
+    const unsigned b = blockIdx.y;
+    if (threadIdx.x < 64) {
+        float lo = __builtin_inff(), hi = -__builtin_inff();
+        if ((int)threadIdx.x < nparts) {
+            const float* q = part + ((size_t)b * nparts + threadIdx.x) * 2;
+            lo = q[0];
+            hi = q[1];
+        }
+        wave_range(lo, hi);
+        if (threadIdx.x == 0) {
+            rng[0] = lo;
+            rng[1] = hi;
+            if (range && blockIdx.x == 0) {
+                range[2 * b] = lo;
+                range[2 * b + 1] = hi;
+            }
+        }
+    }
+    __syncthreads();
+    const float vmin = rng[0];
+    const float d = __fsub_rn(rng[1], vmin);
+    const unsigned HW = H * W;
+    const float* xp = x + (size_t)b * HW;
+    uint8_t* op = out + (size_t)b * HW;
+    const unsigned step = gridDim.x * kBlock;
+    if (VEC) {
+        const unsigned groups = HW >> 2;
+        for (unsigned g = blockIdx.x * kBlock + threadIdx.x; g < groups; g += step) {
+            const unsigned p = g << 2;
+            const float4_t v = *reinterpret_cast<const float4_t*>(xp + p);
+            if (vec_store) {
+                const unsigned dst = flip ? flipped(p, H, W) : p;
+                *reinterpret_cast<unsigned*>(op + dst) = auto_level(v[0], vmin, d) | (auto_level(v[1], vmin, d) << 8) |
+                                                         (auto_level(v[2], vmin, d) << 16) | (auto_level(v[3], vmin, d) << 24);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) op[flipped(p + j, H, W)] = (uint8_t)auto_level(v[j], vmin, d);
+            }
+        }
+    } else {
+        for (unsigned p = blockIdx.x * kBlock + threadIdx.x; p < HW; p += step)
+            op[flip ? flipped(p, H, W) : p] = (uint8_t)auto_level(xp[p], vmin, d);
+    }
+}
+
 int plane_checks(const char* name, int B, int H, int W) {
     VQW_CHECK(B > 0 && H > 0 && W > 0, "%s: B, H, W must be positive (got %d, %d, %d)", name, B, H, W);
     VQW_CHECK((long)B * H * W < (1L << 31), "%s: B * H * W = %ld does not fit 32-bit indices", name, (long)B * H * W);
@@ -228,6 +352,30 @@ extern "C" int vqw_export_grey(const float* x, const float* win, uint8_t* out, i
     if (vec) k_export_grey<true><<<grid, kBlock, 0, s>>>(x, win, out, nwin, B, H, W, flip, vec_store);
     else k_export_grey<false><<<grid, kBlock, 0, s>>>(x, win, out, nwin, B, H, W, flip, 0);
     VQW_LAUNCH_CHECK("vqw_export_grey");
+    return VQW_OK;
+}
+
+extern "C" size_t vqw_export_auto_ws_bytes(int B) { return sizeof(float) * 2 * kMaxRangeGroups * (size_t)imax(B, 1); }
+
+extern "C" int vqw_export_grey_auto(const float* x, uint8_t* out, float* range, float* ws, size_t ws_bytes, int B, int H, int W,
+                                    int flip, void* stream) {
+    VQW_CHECK(x && out && ws, "vqw_export_grey_auto: null pointer");
+    if (int rc = plane_checks("vqw_export_grey_auto", B, H, W)) return rc;
+    VQW_CHECK(ws_bytes >= vqw_export_auto_ws_bytes(B), "vqw_export_grey_auto: workspace of %zu bytes, %zu needed", ws_bytes,
+              vqw_export_auto_ws_bytes(B));
+    const unsigned HW = (unsigned)H * W;
+    const bool vec_load = HW % 4 == 0 && ((uintptr_t)x % 16) == 0;
+    const bool vec = vec_load && ((uintptr_t)out % 4) == 0;
+    const int vec_store = !flip || W % 4 == 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int nparts = auto_groups(vec_load ? HW / 4 : HW, B);
+    if (vec_load) k_export_range<true><<<dim3(nparts, B), kBlock, 0, s>>>(x, ws, HW);
+    else k_export_range<false><<<dim3(nparts, B), kBlock, 0, s>>>(x, ws, HW);
+    VQW_LAUNCH_CHECK("vqw_export_grey_auto (range)");
+    dim3 grid(imax(1, imin(stream_grid(vec ? HW / 4 : HW, kBlock), 2048 / imin(B, 2048))), B);
+    if (vec) k_export_grey_auto<true><<<grid, kBlock, 0, s>>>(x, ws, out, range, nparts, H, W, flip, vec_store);
+    else k_export_grey_auto<false><<<grid, kBlock, 0, s>>>(x, ws, out, range, nparts, H, W, flip, 0);
+    VQW_LAUNCH_CHECK("vqw_export_grey_auto");
     return VQW_OK;
 }
 

@@ -3440,6 +3440,30 @@ def export_grey(x, windows=(None,), vmin=-1.0, vmax=1.0, flip=False):
     return out
 
 
+def export_grey_auto(x, flip=False, return_range=False):
+    """(B, 1, H, W) fp32 images (either memory format) -> (B, H, W) uint8 tiles, each image over its own range (imshow with
+    vmin = vmax = None): u8 = min(255, floor(256 * clamp((x - vmin_b) / (vmax_b - vmin_b), 0, 1))) with vmin_b / vmax_b the
+    minimum / maximum over the finite values of image b; one float32 rounding per operation.  Non-finite values, a constant
+    image and an image without a finite value export as 0.  flip=True writes the rows bottom to top.  return_range=True ->
+    (tiles, (B, 2) fp32 (vmin_b, vmax_b); (+inf, -inf) where an image has no finite value)."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise RuntimeError("export_grey_auto: expected an fp32 tensor (got %s)" % (getattr(x, "dtype", type(x)),))
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise RuntimeError("export_grey_auto: expected a (B, 1, H, W) tensor, got shape %s" % (tuple(x.shape),))
+    if x.numel() == 0:
+        raise RuntimeError("export_grey_auto: empty input")
+    _dev(x)
+    x = x.detach()
+    B, _, H, W = x.shape
+    x = x.reshape(B, H, W).contiguous()                # one channel: NCHW and NHWC hold the same bytes, no copy
+    L = _L()
+    out = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
+    rng = torch.empty((B, 2), dtype=torch.float32, device=x.device) if return_range else None
+    ws = _ws(L.vqw_export_auto_ws_bytes(B), x)
+    L.vqw_export_grey_auto(x, out, rng, ws, ws.numel(), B, H, W, int(bool(flip)))
+    return (out, rng) if return_range else out
+
+
 class LabelExport:
     """Result of ops.export_labels: device tensors `index` (B, H, W) uint8 / uint16, `rgb` (B, H, W, 3) uint8 and `counts`
     (B, K + 1) int32 (each None when not asked for).  check() reads the error flag (one small device-to-host copy) and

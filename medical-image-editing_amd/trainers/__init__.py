@@ -3,7 +3,8 @@ from .data_parallel import GradientAllReducer  # noqa: F401
 from .second_step import SecondStepTrainer, GanLossWeights  # noqa: F401
 from .second_step_unet import UNetSecondStepTrainer, UNetGanLossWeights, draw_cutmix_box  # noqa: F401
 from .second_step_unet_mw import UNetMultiWindowSecondStepTrainer  # noqa: F401
-from .config import (build_first_step_trainer, build_second_step_trainer, configure_discriminator, configure_vqgan, gan_loss_weights, unet_gan_loss_weights, configure_models, configure_optimizers, configure_losses, configure_frequency_loss,  # noqa: F401
+from .vqgan_unet_dis import VQGANUNetDisTrainer, VQGANLossWeights  # noqa: F401
+from .config import (build_first_step_trainer, build_second_step_trainer, build_vqgan_trainer, check_vqgan_config, vqgan_loss_weights, configure_discriminator, configure_vqgan, gan_loss_weights, unet_gan_loss_weights, configure_models, configure_optimizers, configure_losses, configure_frequency_loss,  # noqa: F401
                      configure_perceptual_loss,
                      loss_weights, set_transform, build_evaluator)
 from .evaluation import Evaluator, write_result_csv  # noqa: F401

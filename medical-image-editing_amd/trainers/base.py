@@ -35,8 +35,9 @@ class StepThrottle:
 
 
 class TrainerBase:
-    """A subclass supplies modules() and optimizers() ({name: module / optimiser}, in the reference's order, with an
-    'encoder' and a 'decoder' among the modules) and sets `dict_size`."""
+    """A subclass supplies modules() and optimizers() ({name: module / optimiser}, in the reference's order, with a
+    'decoder' and - every trainer but the VQGAN's, whose 'decoder' is the whole autoencoder - an 'encoder' among the modules)
+    and sets `dict_size`."""
 
     def __init__(self, device):
         self.device = torch.device(device)
@@ -54,7 +55,9 @@ class TrainerBase:
         optimiser state dicts do not hold and a bit-exact continuation needs: the views' generators, the DropBlock
         schedule's position and the encoder's codebook-initialised flag."""
         mods = self.modules()
-        extra = {"init_embed": bool(mods["encoder"].init_embed)}
+        extra = {}
+        if "encoder" in mods:
+            extra["init_embed"] = bool(mods["encoder"].init_embed)
         views = getattr(self, "views", None)
         if hasattr(views, "state_dict"):
             extra["views"] = views.state_dict()
@@ -73,7 +76,7 @@ class TrainerBase:
             if k in state.get("optimizers", {}):
                 o.load_state_dict(state["optimizers"][k])
         extra = state.get("extra") or {}
-        if "init_embed" in extra:
+        if "init_embed" in extra and "encoder" in mods:
             mods["encoder"].init_embed = bool(extra["init_embed"])
         views = getattr(self, "views", None)
         if "views" in extra and hasattr(views, "load_state_dict"):
@@ -87,6 +90,8 @@ class TrainerBase:
         """The reference's test step (single_window_trainer.py:781-827): {'NMSE', 'SSIM', 'PSNR', 'Entropy'} of one batch
         through trainers.evaluation.Evaluator (eval mode, no gradients; training state untouched)."""
         mods = self.modules()
+        if "encoder" not in mods:
+            raise NotImplementedError("%s has no test step (the reference defines none for it)" % type(self).__name__)
         return Evaluator(mods["encoder"], mods["decoder"], self.dict_size).test_step(batch)
 
     @staticmethod

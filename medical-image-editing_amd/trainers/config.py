@@ -35,12 +35,13 @@ from functions import EmbeddingLoss, FocalFrequencyLoss, LPIPSLoss, VGGLoss
 from hipops import Adam
 from networks import UNetEncoder, UNetDecoder, RandomTransform, NLayerDiscriminator, UNetDiscriminator
 from utils import apply_spectral_norm
-from utils.checkpoint import load_first_stage_from_ckpt, load_discriminator_from_ckpt
+from utils.checkpoint import load_first_stage_from_ckpt, load_discriminator_from_ckpt, load_vqgan_from_ckpt
 
 from .first_step import FirstStepTrainer, FlipViews, RandomTransformViews, LossWeights
 from .second_step import SecondStepTrainer, GanLossWeights
 from .second_step_unet import UNetSecondStepTrainer, UNetGanLossWeights
 from .second_step_unet_mw import UNetMultiWindowSecondStepTrainer
+from .vqgan_unet_dis import VQGANUNetDisTrainer, VQGANLossWeights
 from .evaluation import Evaluator
 
 
@@ -52,7 +53,8 @@ def configure_models(config):
     """-> (UNetEncoder, UNetDecoder) exactly as base.py:189-237 calls the constructors (`init_embed = not use_init_embed`)."""
     g = config.model.vqmodel
     if _get(g, "model_name") == "VQGAN":
-        raise NotImplementedError("model_name 'VQGAN' (transformer-stage decoder) is outside the hot path this build covers")
+        raise NotImplementedError("model_name 'VQGAN': configure_models builds the U-Net encoder / decoder pair; the VQGAN and "
+                                  "its trainer are built by trainers.build_vqgan_trainer (run_vqwnet.py -v)")
     encoder = UNetEncoder(
         in_channels=g.in_channels,
         filters=list(g.enc_filters),
@@ -80,6 +82,21 @@ def configure_models(config):
 
 
 _UNET_DIS_KEYS = ("D_ch", "D_wide", "D_attn", "resolution")
+VQGAN_KEYS = ("in_channels", "mid_channels", "out_channels", "emb_dim", "dict_size", "enc_ch_multiplier", "dec_ch_multiplier",
+              "num_res_blocks", "enc_attn_resolutions", "dec_attn_resolutions", "resolution", "p_dropout", "resamp_with_conv",
+              "knn_backend")
+
+
+def check_vqgan_config(config):
+    """NotImplementedError unless the config describes the VQGAN trainer's model: model.vqmodel.model_name 'VQGAN' and the
+    fourteen keys of model.vqgan (no device work: the launcher calls it before anything else)."""
+    name = _get(_get(config.model, "vqmodel"), "model_name")
+    section = _get(config.model, "vqgan")
+    missing = [k for k in VQGAN_KEYS if section is None or not hasattr(section, k)]
+    if name != "VQGAN" or missing:
+        raise NotImplementedError("the VQGAN trainer (run_vqwnet.py -v, trainers.build_vqgan_trainer) needs model.vqmodel.model_name "
+                                  "'VQGAN' (got %r) and model.vqgan.{%s}, as the reference's constructor call does (base.py:204-222); "
+                                  "missing: %s" % (name, ", ".join(VQGAN_KEYS), ", ".join(missing) or "none"))
 
 
 def configure_vqgan(config):
@@ -132,6 +149,12 @@ def unet_gan_loss_weights(config):
     """-> UNetGanLossWeights from config.loss.loss_weight.{recon, gen, dis, freq, perceptual, unet_perceptual, cutmix,
     consistency}; an absent key keeps the namedtuple's default."""
     return _weights(UNetGanLossWeights, config)
+
+
+def vqgan_loss_weights(config):
+    """-> VQGANLossWeights from config.loss.loss_weight.{recon, freq, perceptual, commit, gen, unet_perceptual, dis, cutmix,
+    consistency}; an absent key keeps the namedtuple's default."""
+    return _weights(VQGANLossWeights, config)
 
 
 def _adam_kwargs(o):
@@ -322,3 +345,36 @@ def build_second_step_trainer(config, device="cuda", data_parallel=None, first_s
                                                     percep_weights=percep_weights, clamp_windows=clamp, **kw)
         return UNetSecondStepTrainer(encoder, decoder, **kw)
     return SecondStepTrainer(encoder, decoder, loss_weight=gan_loss_weights(config), **kw)
+
+
+def build_vqgan_trainer(config, device="cuda", data_parallel=None, first_stage_ckpt_path=None, discriminator_ckpt_path=None):
+    """config -> VQGANUNetDisTrainer (run_vqwnet.py -v; reference trainers/vqgan_unet_dis.py): the VQGAN of model.vqgan trained
+    against the U-Net discriminator of model.dis, whatever run.training_mode says (the reference's step has no mode dispatch).
+    first_stage_ckpt_path (argument, else run.first_stage_ckpt_path) loads a checkpoint's `decoder.*` keys into the VQGAN
+    non-strictly, discriminator_ckpt_path its `dis.*` keys into the discriminator, as TrainerBase.__init__ does (base.py:79-83)."""
+    import torch.distributed as dist
+    check_vqgan_config(config)
+    c = config.loss
+    loss_type = _get(c, "dis_loss_type") or "hinge_d_loss"
+    if loss_type != "hinge_d_loss":
+        raise NotImplementedError("loss.dis_loss_type %r: only 'hinge_d_loss' is built (vqgan_unet_dis.py:85)" % (loss_type,))
+    frequency_loss, perceptual_loss = configure_frequency_loss(config), configure_perceptual_loss(config)
+    vqgan = configure_vqgan(config)
+    dis = configure_discriminator(config)
+    if not isinstance(dis, UNetDiscriminator):
+        raise NotImplementedError("the VQGAN trainer trains against the U-Net discriminator (model.dis.model_name "
+                                  "'UNetDiscriminator'): its step unpacks three outputs of its discriminator "
+                                  "(vqgan_unet_dis.py:59); with the PatchGAN it is not built")
+    first = first_stage_ckpt_path or _get(config.run, "first_stage_ckpt_path")
+    if first:
+        load_vqgan_from_ckpt(first, vqgan)
+    dck = discriminator_ckpt_path or _get(config.run, "discriminator_ckpt_path")
+    if dck:
+        load_discriminator_from_ckpt(dck, dis)
+    if data_parallel is None:
+        data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    return VQGANUNetDisTrainer(vqgan, dis, loss_weight=vqgan_loss_weights(config), n_inner_loops=int(_get(c, "n_inner_loops") or 1),
+                               device=device, data_parallel=data_parallel, frequency_loss=frequency_loss,
+                               perceptual_loss=perceptual_loss, dec_optim=_adam_kwargs(config.dec_optim),
+                               dis_optim=_adam_kwargs(config.dis_optim), use_recon_loss=bool(_get(c, "use_recon_loss", True)),
+                               use_unet_perceptual_loss=bool(_get(c, "use_unet_perceptual_loss")))

@@ -28,6 +28,7 @@ from .base import TrainerBase
 from .config import configure_models
 from .first_step import FlipViews, LUNG_WINDOW, MEDIASTINAL_WINDOW, LossWeights
 from .evaluation import Evaluator
+from .vqgan_unet_dis import VQGANUNetDisTrainer
 
 LIMIT_VAL_BATCHES = 2              # run_vqwnet.py:127
 SANITY_VAL_BATCHES = 2             # run_vqwnet.py:125
@@ -86,7 +87,7 @@ def _first_step_row(v, w):
 
 
 def _second_step_terms(out):
-    names = ("gen_total", "dis_total", "recon", "gen", "freq", "perceptual", "unet_perceptual", "dis", "cutmix", "consistency")
+    names = ("gen_total", "dis_total", "recon", "gen", "freq", "perceptual", "commit", "unet_perceptual", "dis", "cutmix", "consistency")
     return [(n, out[n]) for n in names if out.get(n) is not None]
 
 
@@ -94,11 +95,12 @@ _SWITCHED_OFF_IS_ZERO = ("recon", "freq", "perceptual", "unet_perceptual")      
 
 
 def _second_step_row(v, w):
-    """The row of either second step, from the fields its loss weights have (U-Net: single_window_trainer.py:361-374)."""
+    """The row of a second step or of the VQGAN step, from the fields its loss weights have (U-Net: single_window_trainer.py:361-374;
+    VQGAN: vqgan_unet_dis.py:121-136, the only one with `commit`)."""
     f = np.float32
     term = lambda k: f(getattr(w, k)) * f(v.get(k, 0.0) if k in _SWITCHED_OFF_IS_ZERO else v[k])  # noqa: E731
     row = {"total": f(v["gen_total"]) + f(v["dis_total"]), "gen_total": v["gen_total"]}
-    row.update((k, term(k)) for k in ("recon", "freq", "perceptual", "gen", "unet_perceptual") if k in w._fields)
+    row.update((k, term(k)) for k in ("recon", "freq", "perceptual", "commit", "gen", "unet_perceptual") if k in w._fields)
     row["dis_total"] = v["dis_total"]
     if "cutmix" in w._fields:
         row.update((k, term(k)) for k in ("dis", "cutmix", "consistency"))
@@ -228,7 +230,12 @@ class Fit:
         self.do_validate, self.do_save = validate, save_checkpoints
         self.print = log
         self.mode = _get(config.run, "training_mode", "first_step")
-        self.dict_size = config.model.vqmodel.dict_size
+        # the VQGAN trainer (-v) has one step, a generator half and a discriminator half, whatever training_mode names
+        # (vqgan_unet_dis.py has no mode dispatch): the loop and the log treat it as a second step
+        self.vqgan = isinstance(trainer, VQGANUNetDisTrainer)
+        if self.vqgan:
+            self.mode = "second_step"
+        self.dict_size = trainer.dict_size if self.vqgan else config.model.vqmodel.dict_size
         self.n_epochs = int(_get(config.run, "n_epochs", 1))
         self.log_every = int(_get(config.run, "log_every_n_steps", DEFAULT_LOG_EVERY_N_STEPS))
         self.noise_std = float(_get(config.run, "noise_std", DEFAULT_NOISE_STD))
@@ -399,9 +406,37 @@ class Fit:
         rows = [np.concatenate([t[i] for t in tiles], axis=1) for i in range(n_rows)]
         return np.concatenate(rows, axis=0), counts
 
+    @torch.no_grad()
+    def _vqgan_eval_forward(self, image):
+        """-> (recon, r_map, f_map) of vqgan_unet_dis.py:191-196 with the VQGAN and the discriminator in eval mode (no EMA update
+        of the codebook, no u0 step of the spectral norms); their training modes are put back."""
+        vqgan, dis = self.trainer.vqgan, self.trainer.dis
+        modes = (vqgan.training, dis.training)
+        vqgan.eval()
+        dis.eval()
+        try:
+            recon = vqgan(image)[0]
+            r_map = dis(image)[0]
+            f_map = dis(recon)[0]
+        finally:
+            vqgan.train(modes[0])
+            dis.train(modes[1])
+        return recon, r_map, f_map
+
+    def vqgan_mosaic(self, image, recon, r_map, f_map, n_rows):
+        """-> (n_rows * H, 4 * W, 3) uint8 picture: one row per image - image, recon (grey over [-1, 1]), r_map, f_map (each
+        image's map over its own range, the reference's vmin = vmax = None; vqgan_unet_dis.py:212-221) - for every dataset."""
+        if n_rows <= 0:
+            return None
+        grey = [ops.export_grey(image[:n_rows])[0], ops.export_grey(recon[:n_rows])[0],
+                ops.export_grey_auto(r_map[:n_rows]), ops.export_grey_auto(f_map[:n_rows])]
+        tiles = [np.repeat(g.cpu().numpy()[..., None], 3, axis=3) for g in grey]
+        return np.concatenate([np.concatenate([t[i] for t in tiles], axis=1) for i in range(n_rows)], axis=0)
+
     def validate(self, epoch, limit=LIMIT_VAL_BATCHES):
         """At most `limit` validation batches in eval mode without gradients (rank 0): prints every batch's id histogram and
-        writes <run dir>/<epoch:06d>.png from the last one (the reference saves each batch's figure to the same path)."""
+        writes <run dir>/<epoch:06d>.png from the last one (the reference saves each batch's figure to the same path).  The
+        VQGAN trainer's picture has the discriminator's maps in place of the ids, and no histogram is printed."""
         if self.rank != 0:
             return None
         n_save = int(_get(self.config.save, "n_save_images", 0) or 0)
@@ -410,6 +445,10 @@ class Fit:
             if i >= limit:
                 break
             image = self._to_device(batch)
+            if self.vqgan:
+                recon, r_map, f_map = self._vqgan_eval_forward(image)
+                picture = self.vqgan_mosaic(image, recon, r_map, f_map, min(n_save, image.shape[0]))
+                continue
             recon, ids = self._eval_forward(image)
             picture, counts = self.mosaic(image, recon, ids, min(n_save, image.shape[0]))
             self.print("IDs: ", counts.sum(axis=0))
@@ -431,6 +470,8 @@ class Fit:
 
     def test(self):
         """`-m test` for the training modes: Evaluator over the test loader -> result.csv in the run directory."""
+        if self.vqgan:
+            raise ValueError("the VQGAN trainer has no test step (the reference defines none)")
         self._load_weights_for_test()
         if self.rank != 0:
             return None
@@ -444,6 +485,8 @@ class Fit:
         <save_dir>/<study_name>/<patient_id>/: image_%04d / recon_%04d / label_%04d as .png (the export kernels' bytes: grey
         over [-1, 1], ids through the palette) and as .nii.gz (float32 image / recon, int32 label; to_nifti orientation).
         NCCLungDataset: image and recon through the lung window first; CRCDataset: all three flipped upside down."""
+        if self.vqgan:
+            raise ValueError("the VQGAN trainer has no inference export (the reference defines none)")
         self._load_weights_for_test()
         if self.rank != 0:
             return []

@@ -27,16 +27,20 @@ GanLossWeights = namedtuple("GanLossWeights", "recon gen dis freq perceptual", d
 class SecondStepBase(TrainerBase):
     """A subclass sets `Weights` (its loss-weight namedtuple) and `dis_keys` (the names of what discriminator_update returns)
     and supplies generator_terms() and discriminator_update(); a multi-window step also overrides shared_terms() and
-    discriminator_inputs().  training_step is the one step body of all of them."""
+    discriminator_inputs().  reconstruct() is the generator itself: the frozen encoder and the trained decoder here; a trainer
+    whose generator is one module (the VQGAN's) passes encoder=None and overrides it.  training_step is the one step body of
+    all of them."""
 
     def __init__(self, encoder, decoder, dis=None, loss_weight=None, n_inner_loops=1, lr=1e-4, betas=(0.5, 0.999),
                  weight_decay=0.0, device="cuda", data_parallel=False, frequency_loss=None,
                  perceptual_loss=None, dec_optim=None, dis_optim=None, use_recon_loss=True):
         super().__init__(device)
-        self.encoder = encoder.to(self.device)
+        if encoder is not None:
+            self.encoder = encoder.to(self.device)
         self.decoder = decoder.to(self.device).train()
         self.dis = (dis if dis is not None else NLayerDiscriminator()).to(self.device).train()
-        self.dict_size = encoder.dict_size
+        if encoder is not None:
+            self.dict_size = encoder.dict_size
         self.w = loss_weight if loss_weight is not None else self.Weights()
         self.n_inner_loops = int(n_inner_loops)
         self.frequency_loss = frequency_loss          # functions.FocalFrequencyLoss or None (use_frequency_loss)
@@ -65,6 +69,14 @@ class SecondStepBase(TrainerBase):
         """The discriminator's parameters whose gradients a data-parallel run all-reduces."""
         return [p for p in self.dis.parameters() if p.requires_grad]
 
+    def reconstruct(self, image):
+        """image -> (recon with the generator's tape, ids, [(name, term, weight)] further entries of the generator total that
+        come out of the generator's own forward).  Here: the frozen encoder (eval mode, no tape), then the decoder."""
+        self.encoder.eval()
+        with torch.no_grad():
+            embed, _, ids = self.encoder(image)
+        return self.decoder(embed.detach()), ids, []
+
     def shared_terms(self, image, recon):
         """-> the ("recon", "freq", "perceptual") entries (name, term or None, weight) of the generator total: the terms that
         do not depend on the discriminator."""
@@ -81,7 +93,7 @@ class SecondStepBase(TrainerBase):
     def generator_terms(self, image, recon, shared):
         """-> [(name, term or None, weight)] of the generator total in the order ops.weighted_sum adds them (the order is
         part of the total's bits), the discriminator's forward on `recon` included; `shared`: the (recon, freq, perceptual)
-        entries.  Runs with the discriminator's parameters frozen."""
+        entries, followed by reconstruct()'s own.  Runs with the discriminator's parameters frozen."""
         raise NotImplementedError
 
     def discriminator_update(self, image, recon):
@@ -94,11 +106,8 @@ class SecondStepBase(TrainerBase):
         ops.begin_step()
         if self.dec_reducer is not None:
             ops.reset_pending(self.dec_optim.param_groups[0]["params"])
-        self.encoder.eval()
-        with torch.no_grad():
-            embed, _, ids = self.encoder(image)
-        recon = self.decoder(embed.detach())
-        shared = self.shared_terms(image, recon)
+        recon, ids, own = self.reconstruct(image)
+        shared = self.shared_terms(image, recon) + own
         d_image, d_recon = self.discriminator_inputs(image, recon)
         # The reference lets autograd fill the discriminator's parameter gradients in this pass and discards them
         # (dis_optim.zero_grad() in the discriminator half); they are not computed here.  Same decoder gradients, same

@@ -43,21 +43,12 @@ def draw_cutmix_box(height, width):
     return span(centre["y"], height), span(centre["x"], width)
 
 
-class UNetSecondStepTrainer(SecondStepBase):
-    Weights = UNetGanLossWeights
+class UNetDisHalves:
+    """What training against the U-Net discriminator adds to SecondStepBase, whatever the generator is: the generator pass on
+    D(recon) (and D(image)), the three discriminator passes with their CutMix draw, the discriminator's update.  Mixed in in
+    front of SecondStepBase by UNetSecondStepTrainer and VQGANUNetDisTrainer; it reads self.dis, self.w, self.dis_optim,
+    self.dis_reducer, self.use_unet_perceptual_loss and self.cutmix_box."""
     dis_keys = ("dis_total", "dis", "cutmix", "consistency")
-
-    def __init__(self, encoder, decoder, dis, loss_weight=None, n_inner_loops=1, lr=1e-4, betas=(0.5, 0.999), weight_decay=0.0,
-                 device="cuda", data_parallel=False, frequency_loss=None, perceptual_loss=None, dec_optim=None, dis_optim=None,
-                 use_recon_loss=True, use_unet_perceptual_loss=False, use_l1_loss=False, cutmix_box=None):
-        if use_l1_loss:
-            raise NotImplementedError("loss.use_l1_loss: the L1 reconstruction loss is not built (MSE is)")
-        if not isinstance(dis, UNetDiscriminator):
-            raise TypeError("UNetSecondStepTrainer trains a networks.UNetDiscriminator (SecondStepTrainer the PatchGAN)")
-        super().__init__(encoder, decoder, dis, loss_weight, n_inner_loops, lr, betas, weight_decay, device, data_parallel,
-                         frequency_loss, perceptual_loss, dec_optim, dis_optim, use_recon_loss)
-        self.use_unet_perceptual_loss = bool(use_unet_perceptual_loss)
-        self.cutmix_box = cutmix_box
 
     def reduced_dis_params(self):
         unused = {id(p) for p in self.dis.linear.parameters()}       # `linear` is never used: it never has a gradient
@@ -79,10 +70,6 @@ class UNetSecondStepTrainer(SecondStepBase):
             l_unet = ops.weighted_sum([ops.mse_loss(f, r) for f, r in zip(f_feat, r_feat)], [1.0] * len(f_feat))
         return l_gen, l_unet
 
-    def generator_terms(self, image, recon, shared):
-        l_gen, l_unet = self.generator_pass(image, recon)
-        return [("gen", l_gen, self.w.gen), *shared, ("unet_perceptual", l_unet, self.w.unet_perceptual)]
-
     def discriminator_pass(self, image, recon):
         """D(image), D(recon), one CutMix draw, D(cutmix_images) (single_window_trainer.py:319-349) -> (l_dis, l_cutmix, l_consistency)"""
         r_map, r_bottle, _ = self.dis(image.detach())
@@ -103,3 +90,23 @@ class UNetSecondStepTrainer(SecondStepBase):
         """One inner loop of the discriminator half (single_window_trainer.py:319-357): the three passes and their losses, one
         Adam step.  -> (l_dis_total, l_dis, l_cutmix, l_consistency)"""
         return self.discriminator_step(*self.discriminator_pass(image, recon))
+
+
+class UNetSecondStepTrainer(UNetDisHalves, SecondStepBase):
+    Weights = UNetGanLossWeights
+
+    def __init__(self, encoder, decoder, dis, loss_weight=None, n_inner_loops=1, lr=1e-4, betas=(0.5, 0.999), weight_decay=0.0,
+                 device="cuda", data_parallel=False, frequency_loss=None, perceptual_loss=None, dec_optim=None, dis_optim=None,
+                 use_recon_loss=True, use_unet_perceptual_loss=False, use_l1_loss=False, cutmix_box=None):
+        if use_l1_loss:
+            raise NotImplementedError("loss.use_l1_loss: the L1 reconstruction loss is not built (MSE is)")
+        if not isinstance(dis, UNetDiscriminator):
+            raise TypeError("UNetSecondStepTrainer trains a networks.UNetDiscriminator (SecondStepTrainer the PatchGAN)")
+        super().__init__(encoder, decoder, dis, loss_weight, n_inner_loops, lr, betas, weight_decay, device, data_parallel,
+                         frequency_loss, perceptual_loss, dec_optim, dis_optim, use_recon_loss)
+        self.use_unet_perceptual_loss = bool(use_unet_perceptual_loss)
+        self.cutmix_box = cutmix_box
+
+    def generator_terms(self, image, recon, shared):
+        l_gen, l_unet = self.generator_pass(image, recon)
+        return [("gen", l_gen, self.w.gen), *shared, ("unet_perceptual", l_unet, self.w.unet_perceptual)]

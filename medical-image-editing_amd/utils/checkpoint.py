@@ -19,6 +19,13 @@ def load_first_stage_from_ckpt(path, encoder, decoder=None, load_only_enc=False)
     return encoder, decoder
 
 
+def load_vqgan_from_ckpt(path, vqgan):
+    """The VQGAN trainer's first-stage load (base.py:85-102 with the VQGAN as `decoder`): the `decoder.*` keys, strict=False."""
+    sd = _state_dict(path)
+    vqgan.load_state_dict({k[len('decoder.'):]: v for k, v in sd.items() if k.startswith('decoder.')}, strict=False)
+    return vqgan
+
+
 def load_discriminator_from_ckpt(path, dis):
     """base.py:104-113"""
     sd = _state_dict(path)
