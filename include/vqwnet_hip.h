@@ -706,6 +706,37 @@ int vqw_attention_fwd(const float* q, const float* k, const float* v, float* o, 
 int vqw_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
                       float* d_ws, float* gq, float* gk, float* gv, int B, int N, int C, float scale, void* stream);
 
+/* ---- minGPT blocks (networks/mingpt.py:34-119 CausalSelfAttention / Block).  Added functions only; the ABI stays 9.
+ * LayerNorm(C, eps, affine) over the rows of x [rows][C]: y = gamma (x - mean_r) rstd_r + beta, biased variance from the centred
+ * values of the row, which is read once and held in registers.  C a multiple of 4 with 4 <= C <= 4096; anything else is refused
+ * by the argument check.  mean, rstd [rows] are what the backward needs besides x.  Backward: gx = rstd (gamma gy - mean_c(gamma
+ * gy) - xhat mean_c(gamma gy xhat)); dgamma = sum_r gy xhat and dbeta = sum_r gy are per-workgroup partials (32 rows each) in ws
+ * (vqw_layernorm_ws_bytes() bytes) that a second kernel folds in index order: no atomics, the same bits every run.  dgamma,
+ * dbeta [C] are overwritten. */
+size_t vqw_layernorm_ws_bytes(long rows, int C);
+int vqw_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long rows, int C,
+                      float eps, void* stream);
+int vqw_layernorm_bwd(const float* x, const float* gamma, const float* mean, const float* rstd, const float* gy, float* gx,
+                      float* dgamma, float* dbeta, void* ws, size_t ws_bytes, long rows, int C, void* stream);
+/* nn.GELU() in its exact form, y = 0.5 x (1 + erf(x / sqrt 2)), and its gradient gx = gy (Phi(x) + x phi(x)): n >= 1 elements,
+ * in fp32 with the device erff / expf */
+int vqw_gelu_fwd(const float* x, float* y, long n, void* stream);
+int vqw_gelu_bwd(const float* x, const float* gy, float* gx, long n, void* stream);
+/* Multi-head attention with a causal mask and an unmasked prefix: q, o [B][Tq][E], k, v [B][Tk][E], E = n_head hs, head h in the
+ * columns [h hs, (h + 1) hs) of a row of E floats (the layout three nn.Linear projections leave: no transpose pass);
+ * lse [B][n_head][Tq] = the row log-sum-exp of the visible scale q k^T.  hs a multiple of 32 with 32 <= hs <= 128, 1 <= Tq, Tk
+ * <= 65536, B n_head <= 65535, tensors 16-byte aligned; anything else is refused with a message that names the constraint.
+ * causal = 1 needs Tq == Tk = T and 0 <= n_unmasked <= T: query i sees key j iff j <= (i < n_unmasked ? n_unmasked - 1 : i),
+ * i.e. tril with mask[:n_unmasked, :n_unmasked] = 1.  causal = 0 (n_unmasked = 0): no mask, Tq != Tk allowed, forward only (the
+ * layer_past route).  Key steps wholly above a query tile's limit are not walked.  Backward (Tq == Tk): d_ws [B][n_head][T]
+ * receives D_i = sum_c go o over the head; P = exp(scale S - lse) is recomputed; gq per query tile, gk and gv per key tile.  No
+ * atomics; the same bits every run. */
+int vqw_causal_attention_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int Tq, int Tk,
+                             int n_head, int hs, float scale, int causal, int n_unmasked, void* stream);
+int vqw_causal_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
+                             float* d_ws, float* gq, float* gk, float* gv, int B, int Tq, int Tk, int n_head, int hs, float scale,
+                             int causal, int n_unmasked, void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

@@ -1576,6 +1576,131 @@ def self_attention_lse(q, k, v, scale):
     return o, lse
 
 
+# ----------------------------------------------------------------------------------------------
+# minGPT blocks (networks/mingpt.py): LayerNorm, exact GELU, nn.Linear, multi-head causal attention on (B, T, C) tensors
+# ----------------------------------------------------------------------------------------------
+class _LayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        _dev(x, weight, bias)
+        x, weight, bias = _flat(x), _flat(weight), _flat(bias)
+        C = x.shape[-1] if x.dim() >= 1 else 0
+        if weight.numel() != C or bias.numel() != C:
+            raise RuntimeError("layer_norm: weight / bias of %d / %d elements for a trailing dimension of %d" % (weight.numel(), bias.numel(), C))
+        rows = x.numel() // max(C, 1)
+        y = torch.empty_like(x)
+        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        _L().vqw_layernorm_fwd(x, weight, bias, y, mean, rstd, rows, C, eps)
+        ctx.save_for_backward(x, weight, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, mean, rstd = ctx.saved_tensors
+        C, rows = x.shape[-1], mean.numel()
+        L = _L()
+        gy = _flat(gy)
+        gx = torch.empty_like(x)
+        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws = _ws(L.vqw_layernorm_ws_bytes(rows, C), x)
+        L.vqw_layernorm_bwd(x, weight, mean, rstd, gy, gx, dgamma, dbeta, ws, ws.numel(), rows, C)
+        return gx, dgamma, dbeta, None
+
+
+def layer_norm(x, weight, bias, eps=1e-5):
+    """nn.LayerNorm(C, eps, elementwise_affine=True)(x) over the last axis of any tensor whose trailing dimension is C."""
+    return _LayerNorm.apply(x, weight, bias, float(eps))
+
+
+class _Gelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        _dev(x)
+        x = _flat(x)
+        y = torch.empty_like(x)
+        _L().vqw_gelu_fwd(x, y, x.numel())
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        _L().vqw_gelu_bwd(x, _flat(gy), gx, x.numel())
+        return gx
+
+
+def gelu(x):
+    """nn.GELU() in its exact form, 0.5 x (1 + erf(x / sqrt 2))."""
+    return _Gelu.apply(x)
+
+
+def linear(x, weight, bias=None):
+    """F.linear(x, weight, bias) on a (B, T, C) tensor: the 1 x 1 convolution ops.conv2d serves, on the channels-last view
+    (B, C, T, 1) of x (the same memory) with the 2-D weight viewed as (out, in, 1, 1).  The parameter stays nn.Linear's 2-D
+    weight: the 4-D view is no leaf, so the weight and bias gradients flow through autograd (never the out-of-band route, which
+    writes into the .grad of the tensor it is handed) and arrive in weight.grad / bias.grad with the parameters' own shapes."""
+    if x.dim() != 3 or weight.dim() != 2:
+        raise RuntimeError("linear: expected x (B, T, C) and a 2-D weight, got %s and %s" % (tuple(x.shape), tuple(weight.shape)))
+    y = conv2d(x.transpose(1, 2).unsqueeze(-1), weight.view(weight.shape[0], weight.shape[1], 1, 1), bias)
+    return y.squeeze(-1).transpose(1, 2)                 # (B, T, out), dense: the convolution's NHWC output
+
+
+def _heads(q, k, v, n_head, n_unmasked, causal):
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise RuntimeError("causal_attention: q (B, Tq, E) and k, v (B, Tk, E) expected, got %s, %s, %s" % (
+            tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    B, Tq, E = q.shape
+    if n_head < 1 or E % n_head != 0:
+        raise RuntimeError("causal_attention: E=%d is not divisible by n_head=%d" % (E, n_head))
+    return B, Tq, k.shape[1], E // n_head, 1.0 / float(E // n_head) ** 0.5, int(bool(causal)), int(n_unmasked)
+
+
+def _causal_attention_fwd(q, k, v, n_head, n_unmasked, causal):
+    _dev(q, k, v)
+    q, k, v = _flat(q), _flat(k), _flat(v)
+    B, Tq, Tk, hs, scale, causal, nu = _heads(q, k, v, n_head, n_unmasked, causal)
+    o = torch.empty_like(q)
+    lse = torch.empty(B, n_head, Tq, dtype=torch.float32, device=q.device)
+    _L().vqw_causal_attention_fwd(q, k, v, o, lse, B, Tq, Tk, n_head, hs, scale, causal, nu)
+    return q, k, v, o, lse, (B, Tq, Tk, hs, scale, causal, nu)
+
+
+class _CausalAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, n_head, n_unmasked, causal):
+        q, k, v, o, lse, ctx.cfg = _causal_attention_fwd(q, k, v, n_head, n_unmasked, causal)
+        ctx.n_head = n_head
+        ctx.save_for_backward(q, k, v, o, lse)          # the backward recomputes nothing but the scores
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, o, lse = ctx.saved_tensors
+        B, Tq, Tk, hs, scale, causal, nu = ctx.cfg
+        go = _flat(go)
+        gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        d = torch.empty_like(lse)
+        _L().vqw_causal_attention_bwd(q, k, v, o, lse, go, d, gq, gk, gv, B, Tq, Tk, ctx.n_head, hs, scale, causal, nu)
+        return gq, gk, gv, None, None, None
+
+
+def causal_attention(q, k, v, n_head, n_unmasked=0, causal=True):
+    """softmax(q k^T / sqrt(hs)) v per head on q (B, Tq, E), k, v (B, Tk, E), E = n_head hs, the heads side by side in the last
+    axis (what three nn.Linear projections leave); returns (B, Tq, E).  causal=True (Tq == Tk): query i sees key j iff
+    j <= (i < n_unmasked ? n_unmasked - 1 : i) - the reference's tril mask with an all-ones n_unmasked x n_unmasked corner
+    (mingpt.py:53-56).  causal=False: no mask, Tq != Tk allowed, forward only (the layer_past route, mingpt.py:71-80)."""
+    return _CausalAttention.apply(q, k, v, int(n_head), int(n_unmasked), bool(causal))
+
+
+def causal_attention_lse(q, k, v, n_head, n_unmasked=0, causal=True):
+    """(output, row log-sum-exp [B, n_head, Tq]) of causal_attention without a tape: for tests and measurement."""
+    _, _, _, o, lse, _ = _causal_attention_fwd(q, k, v, int(n_head), int(n_unmasked), bool(causal))
+    return o, lse
+
+
 class _MaxPool2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
