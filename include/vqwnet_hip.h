@@ -737,6 +737,41 @@ int vqw_causal_attention_bwd(const float* q, const float* k, const float* v, con
                              float* d_ws, float* gq, float* gk, float* gv, int B, int Tq, int Tk, int n_head, int hs, float scale,
                              int causal, int n_unmasked, void* stream);
 
+/* ---- the GPT code prior around the blocks (networks/mingpt.py:122-224 GPT).  Added functions only; the ABI stays 9.  fp32, dense,
+ * no float atomics: every sum has a fixed order, the same bits every run.
+ * Embedding: x[b][t] = (t < Te ? prefix[b][t] : tok[idx[b][t - Te]]) + pos[t0 + t], T = Te + Ti.  idx [B][Ti] (torch.long),
+ * tok [V][E], pos [block_size][E], prefix [B][Te][E] or null with Te = 0 (the reference's `embeddings=`), x [B][T][E]; t0 is
+ * the position offset (past_length on the cached route).  E a multiple of 4 with 4 <= E <= 4096, V >= 1, Ti >= 0, B >= 1,
+ * T >= 1, t0 + T <= block_size, tensors 16-byte aligned; anything else is refused with a message that names the constraint.
+ * An index outside [0, V) reads nothing: its row of x is NaN and the backward skips it.  Backward, from gx [B][T][E], both
+ * overwritten: gpos[t0 + t] = sum_b gx[b][t] with b ascending, 0 in the rows of pos outside [t0, t0 + T); gtok[v] = the sum of
+ * gx[b][Te + t] over the (b, t) with idx[b][t] == v in ascending (b, t) order (a wave owns a row and walks the B Ti indices),
+ * exactly 0 for a row no token uses.  The prefix's gradient is gx[:, :Te]: no kernel. */
+int vqw_embed_fwd(const long* idx, const float* tok, const float* pos, const float* prefix, float* x, int B, int Ti, int Te, int E,
+                  int V, int block_size, int t0, void* stream);
+int vqw_embed_bwd(const long* idx, const float* gx, float* gtok, float* gpos, int B, int Ti, int Te, int E, int V, int block_size,
+                  int t0, void* stream);
+/* Cross-entropy over the last axis of z [rows][V] against target [rows] (torch.long): lse_r = log sum_c exp(z_rc) with the row
+ * maximum subtracted first, loss_r = lse_r - z[r][target_r]; loss, lse [rows].  mean [1] (may be null; then ws is not needed)
+ * receives the mean of loss: per-workgroup partial sums (32 rows each) in double in ws (vqw_xent_ws_bytes() bytes, 8-byte
+ * aligned), folded in index order in double and rounded once.  1 <= V <= 65536, rows >= 1; up to V = 1024 a row is read once
+ * into registers, above it is walked with an online maximum and sum.  A target outside [0, V) reads nothing: loss_r and the
+ * row of gz are NaN.  Backward: gz[r][c] = (exp(z_rc - lse_r) - [c == target_r]) w_r with w_r = gw[0] / rows (mean = 1: gw is
+ * the device scalar d loss, read by the kernel) or gw[r] (mean = 0: gw [rows], reduction 'none'). */
+size_t vqw_xent_ws_bytes(long rows);
+int vqw_xent_fwd(const float* z, const long* target, float* loss, float* lse, float* mean, void* ws, size_t ws_bytes, long rows, int V,
+                 void* stream);
+int vqw_xent_bwd(const float* z, const long* target, const float* lse, const float* gw, float* gz, long rows, int V, int mean,
+                 void* stream);
+/* Top-k sampling, one token per row of logits [B][V] (taming-transformers' top_k_logits, softmax, inverse CDF): s = z /
+ * temperature; thr = the top_k-th largest s (top_k = 0 or >= V: no filter); every entry >= thr is kept, ties at the threshold
+ * included; p_c = exp(s_c - max) over the kept entries; out[b] = the first kept index, in index order, whose running sum of p
+ * exceeds u[b] total, or the last kept index if rounding leaves none - never an index outside the kept set.  u [B] are uniforms
+ * in [0, 1) from the caller: the kernel has no random numbers of its own, a seed reproduces a sample bit for bit.  out [B]
+ * (torch.long).  1 <= V <= 65536, B >= 1, temperature > 0, top_k >= 0.  A NaN logit makes the result unspecified (some index
+ * in [0, V)). */
+int vqw_sample_topk(const float* logits, const float* u, long* out, int B, int V, float temperature, int top_k, void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

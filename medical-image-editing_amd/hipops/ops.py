@@ -1701,6 +1701,117 @@ def causal_attention_lse(q, k, v, n_head, n_unmasked=0, causal=True):
     return o, lse
 
 
+# ----------------------------------------------------------------------------------------------
+# the GPT code prior around the blocks (networks/gpt.py): embedding, cross-entropy, top-k sampling
+# ----------------------------------------------------------------------------------------------
+def _long(t, what):
+    if t.dtype != torch.long:
+        raise RuntimeError("%s must be torch.long (got %s)" % (what, t.dtype))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+class _Embedding(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, idx, tok, pos, prefix, t0):
+        _dev(idx, tok, pos, prefix)
+        if prefix is not None and prefix.dim() == 3 and prefix.shape[1] == 0:
+            prefix = None
+        idx, tok, pos = _long(idx, "embedding: idx"), _flat(tok), _flat(pos)
+        if idx.dim() != 2 or tok.dim() != 2 or pos.dim() < 2 or pos.shape[-1] != tok.shape[1] or pos.numel() != pos.shape[-2] * pos.shape[-1]:
+            raise RuntimeError("embedding: idx (B, Ti), tok (V, E) and pos ([1,] block_size, E) expected, got %s, %s, %s" % (
+                tuple(idx.shape), tuple(tok.shape), tuple(pos.shape)))
+        (B, Ti), (V, E), block_size, Te = idx.shape, tok.shape, pos.shape[-2], 0
+        if prefix is not None:
+            prefix = _flat(prefix)
+            if prefix.dim() != 3 or prefix.shape[0] != B or prefix.shape[2] != E:
+                raise RuntimeError("embedding: prefix (B, Te, E) = (%d, Te, %d) expected, got %s" % (B, E, tuple(prefix.shape)))
+            Te = prefix.shape[1]
+        x = torch.empty(B, Te + Ti, E, dtype=torch.float32, device=tok.device)
+        _L().vqw_embed_fwd(idx, tok, pos, prefix, x, B, Ti, Te, E, V, block_size, t0)
+        ctx.save_for_backward(idx)
+        ctx.cfg = (B, Ti, Te, E, V, block_size, t0, tuple(pos.shape))
+        return x
+
+    @staticmethod
+    def backward(ctx, gx):
+        (idx,) = ctx.saved_tensors
+        B, Ti, Te, E, V, block_size, t0, pos_shape = ctx.cfg
+        gx = _flat(gx)
+        gtok = torch.empty(V, E, dtype=torch.float32, device=gx.device)
+        gpos = torch.empty(pos_shape, dtype=torch.float32, device=gx.device)
+        _L().vqw_embed_bwd(idx, gx, gtok, gpos, B, Ti, Te, E, V, block_size, t0)
+        return None, gtok, gpos, (gx[:, :Te] if Te > 0 and ctx.needs_input_grad[3] else None), None
+
+
+def embedding(idx, tok, pos, prefix=None, t0=0):
+    """x[b, t] = (prefix[b, t] if t < Te else tok[idx[b, t - Te]]) + pos[t0 + t]: the input stem of GPT (mingpt.py:177-189) on idx
+    (B, Ti) torch.long, tok (V, E), pos (block_size, E) or (1, block_size, E), prefix (B, Te, E) or None (the reference's
+    `embeddings=`); returns (B, Te + Ti, E).  t0 is the position offset of the first row (past_length on the cached route).
+    Gradients go to tok, pos and prefix.  An index outside [0, V) gives a NaN row and no gradient."""
+    return _Embedding.apply(idx, tok, pos, prefix, int(t0))
+
+
+def _xent_fwd(logits, target, want_mean):
+    _dev(logits, target)
+    z = _flat(logits)
+    if z.dim() < 1 or tuple(target.shape) != tuple(z.shape[:-1]):
+        raise RuntimeError("cross_entropy: logits (..., V) and target (...) expected, got %s and %s" % (tuple(logits.shape), tuple(target.shape)))
+    target = _long(target, "cross_entropy: target")
+    V = z.shape[-1]
+    rows = z.numel() // max(V, 1)
+    L = _L()
+    loss = torch.empty(z.shape[:-1], dtype=torch.float32, device=z.device)
+    lse = torch.empty(z.shape[:-1], dtype=torch.float32, device=z.device)
+    mean = torch.empty((), dtype=torch.float32, device=z.device) if want_mean else None
+    ws = _ws(L.vqw_xent_ws_bytes(rows), z) if want_mean else None
+    L.vqw_xent_fwd(z, target, loss, lse, mean, ws, ws.numel() if want_mean else 0, rows, V)
+    return z, target, loss, lse, mean
+
+
+class _CrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, want_mean):
+        z, target, loss, lse, mean = _xent_fwd(logits, target, want_mean)
+        ctx.save_for_backward(z, target, lse)
+        ctx.want_mean = want_mean
+        return mean if want_mean else loss
+
+    @staticmethod
+    def backward(ctx, g):
+        z, target, lse = ctx.saved_tensors
+        V = z.shape[-1]
+        gz = torch.empty_like(z)
+        _L().vqw_xent_bwd(z, target, lse, _flat(g), gz, z.numel() // V, V, int(ctx.want_mean))      # g stays on the device
+        return gz, None, None
+
+
+def cross_entropy(logits, target, reduction="mean"):
+    """F.cross_entropy over the last axis: logits (..., V), target (...) torch.long -> the mean over all rows (a 0-dim tensor) or,
+    reduction='none', the loss per row with the leading shape.  A target outside [0, V) gives NaN in its row (and in the mean)."""
+    if reduction not in ("mean", "none"):
+        raise ValueError("cross_entropy: reduction must be 'mean' or 'none' (got %r)" % (reduction,))
+    return _CrossEntropy.apply(logits, target, reduction == "mean")
+
+
+def cross_entropy_lse(logits, target):
+    """(loss per row, row log-sum-exp), both with the leading shape of logits, without a tape: for tests and measurement."""
+    _, _, loss, lse, _ = _xent_fwd(logits, target, False)
+    return loss, lse
+
+
+def sample_topk(logits, u, temperature=1.0, top_k=0):
+    """One token per row of logits (B, V): top_k_logits (keep every entry >= the top_k-th largest of logits / temperature; 0, None
+    or >= V: no filter), softmax, inverse-CDF sampling with the caller's uniforms u (B,) in [0, 1) - torch.rand with a generator.
+    Returns (B,) torch.long.  No random numbers are drawn here: the same u gives the same tokens."""
+    _dev(logits, u)
+    logits, u = _flat(logits), _flat(u)
+    if logits.dim() != 2 or u.dim() != 1 or u.shape[0] != logits.shape[0]:
+        raise RuntimeError("sample_topk: logits (B, V) and u (B,) expected, got %s and %s" % (tuple(logits.shape), tuple(u.shape)))
+    out = torch.empty(logits.shape[0], dtype=torch.long, device=logits.device)
+    _L().vqw_sample_topk(logits, u, out, logits.shape[0], logits.shape[1], float(temperature), int(top_k or 0))
+    return out
+
+
 class _MaxPool2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -15,7 +15,7 @@ than the stored one.
 Dropout: the three nn.Dropout members exist (the trees match); at p = 0 or in eval mode they are the identity.  A training
 forward with any p > 0 raises NotImplementedError - GPTConfig's class defaults of 0.1 included; there is no dropout kernel.
 
-The GPT class itself (embeddings, ln_f, head, sampling) is not built yet.
+The model over these blocks, the reference's GPT class (mingpt.py:122-224), is networks/gpt.py (networks.GPT).
 """
 import torch
 import torch.nn as nn
@@ -171,3 +171,4 @@ class Block(nn.Module):
             return x, present
 
         return x
+
