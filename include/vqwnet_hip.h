@@ -772,6 +772,46 @@ int vqw_xent_bwd(const float* z, const long* target, const float* lse, const flo
  * in [0, V)). */
 int vqw_sample_topk(const float* logits, const float* u, long* out, int B, int V, float temperature, int top_k, void* stream);
 
+/* ---- cached generation for the GPT code prior (networks/gpt.py GPT.prefill / decode_step / generate).  Added functions only; the
+ * ABI stays 9.  fp32 in, fp32 out, fp32 accumulation, no float atomics: every sum has a fixed order, the same bits every run.
+ * Forward only.
+ * Skinny fused linear: y[m][y_col + n] = act(sum_k LN?(x[m])[k] w[n][k] + bias[n]) (+ residual[m][n]) for x [M][K] (M: the batch of
+ * a decode step), w [N][K] as nn.Linear stores it, y with the row stride ldy >= y_col + N (elements outside the N columns and M
+ * rows are not touched).  Optional, each chosen by a non-null pointer or flag: the LayerNorm of the input row with ln_gamma,
+ * ln_beta [K] and eps (both or neither; K <= 4096; biased variance from the centred values, vqw_layernorm_fwd's formulas); bias
+ * [N]; gelu != 0: the exact erf GELU, vqw_gelu_fwd's formula; residual [M][N], dense - y may be the residual itself (then ldy ==
+ * N, y_col == 0), never x.  K a multiple of 4 with 4 <= K <= 16384, N >= 1, 1 <= M <= 524280; x, w, ln_gamma, ln_beta 16-byte
+ * aligned.  A wave owns an output column and reads its weight row once for the rows of a group of 8: up to M = 8 every weight
+ * element is read once per launch. */
+int vqw_dec_linear(const float* x, const float* w, const float* bias, const float* ln_gamma, const float* ln_beta, const float* residual,
+                   float* y, int M, int K, int N, long ldy, long y_col, int gelu, float eps, void* stream);
+/* Decode attention: o[b] = softmax(scale q[b] k[b][:Tk]^T) v[b][:Tk] per head for ONE query row per batch row, q, o [B][E], k, v
+ * [B][capacity][E] (a plane of the cache below), E = n_head hs, head h in the columns [h hs, (h + 1) hs).  No mask (the layer_past
+ * route, as vqw_causal_attention_fwd with causal = 0).  Rows at or beyond Tk are never read.  hs a multiple of 32 with 32 <= hs <=
+ * 128, B n_head <= 65535 (vqw_causal_attention_fwd's limits), 1 <= Tk <= capacity <= 65536, tensors 16-byte aligned.  One
+ * workgroup per (b, head); measured up to Tk = 256. */
+int vqw_dec_attention(const float* q, const float* k, const float* v, float* o, int B, int Tk, int capacity, int n_head, int hs,
+                      float scale, void* stream);
+/* One decode step of the GPT: ONE host call per token, 2 + 5 n_layer launches, no allocation, synchronisation or host read.
+ * idx [B] (torch.long, on the device): the token of each row at position t; tok [V][E], pos [block_size][E]: the model's embedding
+ * tables.  kv: the cache, [n_layer][2][B][capacity][E] (k-plane, v-plane per layer; the heads side by side in the last axis - the
+ * (B, T, E) layout vqw_causal_attention_fwd takes); its rows [0, t) hold the past, row t is written, the attention runs over the
+ * rows [0, t].  logits [B][V].  ws: vqw_gpt_decode_ws_bytes(B, E, V) bytes (the x, q, att [B][E] and h [B][4E] buffers).
+ * packed: vqw_gpt_decode_pack_floats(n_layer, E, V) floats, the model's weights in one buffer with the fixed layout
+ *     per layer l (12 E E + 13 E floats):  ln1.weight [E] | ln1.bias [E] | W_q | W_k | W_v as one [3E][E] | b_q | b_k | b_v [3E] |
+ *                                          W_proj [E][E] | b_proj [E] | ln2.weight [E] | ln2.bias [E] | W_fc1 [4E][E] | b_fc1 [4E] |
+ *                                          W_fc2 [E][4E] | b_fc2 [E]
+ *     then:                                ln_f.weight [E] | ln_f.bias [E] | W_head [V][E]
+ * filled by plain copies of the parameters.  Refused before any device work, with a message that names the constraint: a null
+ * pointer, E no multiple of 4 or outside [4, 4096], E not divisible by n_head, a head size outside vqw_dec_attention's limits,
+ * t < 0, t >= capacity, t >= block_size, a short workspace, pointers not 16-byte aligned.  The two size queries return 0 for a
+ * non-positive argument. */
+long vqw_gpt_decode_pack_floats(int n_layer, int E, int V);
+size_t vqw_gpt_decode_ws_bytes(int B, int E, int V);
+int vqw_gpt_decode_step(const float* packed, const float* tok, const float* pos, const long* idx, float* kv, float* logits, void* ws,
+                        size_t ws_bytes, int B, int t, int capacity, int n_layer, int n_head, int E, int V, int block_size, float eps,
+                        void* stream);
+
 /* ---- deferred split-K folds of the weight gradients (ABI 8).  Every conv weight-gradient entry point ends in one or two
  * short fold launches (dW and dbias slabs -> the gradient).  With vqw_fold_defer(1) those folds are only recorded - the
  * caller must then keep the `ws` buffers of the weight-gradient calls alive - and vqw_fold_flush_host() folds everything

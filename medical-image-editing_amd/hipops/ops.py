@@ -1812,6 +1812,103 @@ def sample_topk(logits, u, temperature=1.0, top_k=0):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# cached generation (networks/gpt.py GPT.decode_step / generate): the decode kernels.  Forward only.
+# ----------------------------------------------------------------------------------------------
+def _no_grad(name, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError("%s is forward only: call it under torch.no_grad() (an argument requires a gradient)" % name)
+
+
+def dec_linear(x, weight, bias=None, ln=None, gelu=False, residual=None, out=None, out_col=0):
+    """act(LN?(x) weight^T + bias) (+ residual) on x (M, K) - M the batch of a decode step - with nn.Linear's weight (N, K), in one
+    weight-bandwidth-bound launch.  ln: (gamma, beta, eps) of a LayerNorm applied to the rows of x first, or None; gelu: the exact
+    erf GELU; residual (M, N), which may be `out` itself.  Returns (M, N); with out= (M, ld), rows contiguous, the result goes
+    to out[:, out_col:out_col + N] - nothing else of `out` is touched - and `out` is returned.  Forward only."""
+    gamma, beta, eps = ln if ln is not None else (None, None, 1e-5)
+    _dev(x, weight, bias, gamma, beta, residual, out)
+    _no_grad("dec_linear", x, weight, bias, gamma, beta, residual)
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
+        raise RuntimeError("dec_linear: x (M, K) and weight (N, K) expected, got %s and %s" % (tuple(x.shape), tuple(weight.shape)))
+    (M, K), N = x.shape, weight.shape[0]
+    x, weight = _flat(x.detach()), _flat(weight.detach())
+    bias, gamma, beta, residual = (None if t is None else t.detach() for t in (bias, gamma, beta, residual))
+    for t, n, what in ((bias, N, "bias (N,)"), (gamma, K, "ln gamma (K,)"), (beta, K, "ln beta (K,)")):
+        if t is not None and (t.dim() != 1 or t.shape[0] != n or not t.is_contiguous()):
+            raise RuntimeError("dec_linear: a contiguous %s expected, got %s" % (what, tuple(t.shape)))
+    if residual is not None and (tuple(residual.shape) != (M, N) or not residual.is_contiguous()):
+        raise RuntimeError("dec_linear: a contiguous residual (M, N) = (%d, %d) expected, got %s" % (M, N, tuple(residual.shape)))
+    if out is None:
+        out, out_col = torch.empty(M, N, dtype=torch.float32, device=x.device), 0
+    elif out.dim() != 2 or out.shape[0] != M or out.stride(1) != 1 or out_col < 0 or out_col + N > out.shape[1] or out.dtype != torch.float32:
+        raise RuntimeError("dec_linear: out (M, ld) fp32 with contiguous rows and out_col + N <= ld expected, got %s (strides %s), out_col=%d, N=%d" % (
+            tuple(out.shape), out.stride(), out_col, N))
+    _L().vqw_dec_linear(x, weight, bias, gamma, beta, residual, out, M, K, N, out.stride(0) if M > 1 else max(out.stride(0), out.shape[1]),
+                        int(out_col), int(bool(gelu)), float(eps))
+    return out
+
+
+def dec_attention(q, k_cache, v_cache, Tk, n_head):
+    """softmax(q k^T / sqrt(hs)) v per head for ONE query row per batch row: q (B, E), k_cache, v_cache (B, capacity, E) contiguous -
+    a plane of the KV cache, the heads side by side in the last axis - against the cache rows [0, Tk); no mask (the layer_past
+    route).  Rows at or beyond Tk are never read.  Returns (B, E).  Forward only."""
+    _dev(q, k_cache, v_cache)
+    _no_grad("dec_attention", q, k_cache, v_cache)
+    if q.dim() != 2 or k_cache.dim() != 3 or k_cache.shape != v_cache.shape or k_cache.shape[0] != q.shape[0] or k_cache.shape[2] != q.shape[1]:
+        raise RuntimeError("dec_attention: q (B, E) and k_cache, v_cache (B, capacity, E) expected, got %s, %s, %s" % (
+            tuple(q.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise RuntimeError("dec_attention: the cache planes must be contiguous")
+    (B, E), capacity = q.shape, k_cache.shape[1]
+    if n_head < 1 or E % n_head != 0:
+        raise RuntimeError("dec_attention: E=%d is not divisible by n_head=%d" % (E, n_head))
+    hs = E // n_head
+    q = _flat(q.detach())
+    o = torch.empty_like(q)
+    _L().vqw_dec_attention(q, k_cache.detach(), v_cache.detach(), o, B, int(Tk), capacity, int(n_head), hs, 1.0 / float(hs) ** 0.5)
+    return o
+
+
+def gpt_decode_pack_floats(n_layer, E, V):
+    """Floats of the packed-weights buffer of gpt_decode_step (the layout is in include/vqwnet_hip.h)."""
+    return int(_L().vqw_gpt_decode_pack_floats(int(n_layer), int(E), int(V)))
+
+
+def gpt_decode_ws_floats(B, E, V):
+    """Floats of the activations workspace of gpt_decode_step."""
+    return int(_L().vqw_gpt_decode_ws_bytes(int(B), int(E), int(V))) // 4
+
+
+def gpt_decode_step(packed, tok, pos, idx, kv, logits, ws, t, n_head, eps=1e-5):
+    """One decode step of the GPT in one host call (2 + 5 n_layer launches from C): the token idx (B,) torch.long of every row at
+    position t, behind the cache kv (n_layer, 2, B, capacity, E) whose rows [0, t) hold the past; row t of every plane is written,
+    logits (B, V) are written and returned.  packed: the weights (networks.gpt.pack_decode_weights), tok (V, E), pos ([1,]
+    block_size, E): the embedding tables, ws: gpt_decode_ws_floats(B, E, V) floats.  Forward only."""
+    _dev(packed, tok, pos, idx, kv, logits, ws)
+    _no_grad("gpt_decode_step", packed, tok, pos)
+    if kv.dim() != 5 or kv.shape[1] != 2 or tok.dim() != 2 or tuple(logits.shape) != (kv.shape[2], tok.shape[0]) or kv.shape[4] != tok.shape[1]:
+        raise RuntimeError("gpt_decode_step: kv (n_layer, 2, B, capacity, E), tok (V, E) and logits (B, V) expected, got %s, %s, %s" % (
+            tuple(kv.shape), tuple(tok.shape), tuple(logits.shape)))
+    n_layer, _, B, capacity, E = kv.shape
+    V = tok.shape[0]
+    idx = _long(idx, "gpt_decode_step: idx")
+    if idx.numel() != B:
+        raise RuntimeError("gpt_decode_step: one token per row expected, idx of shape %s for B=%d" % (tuple(idx.shape), B))
+    if pos.dim() < 2 or pos.shape[-1] != E or pos.numel() != pos.shape[-2] * E:
+        raise RuntimeError("gpt_decode_step: pos ([1,] block_size, E) expected, got %s" % (tuple(pos.shape),))
+    for t_, what in ((packed, "packed"), (kv, "kv"), (logits, "logits"), (ws, "ws"), (tok, "tok"), (pos, "pos")):
+        if t_.dtype != torch.float32 or not t_.is_contiguous():
+            raise RuntimeError("gpt_decode_step: %s must be a contiguous fp32 tensor" % what)
+    if n_head < 1 or E % n_head != 0:
+        raise RuntimeError("gpt_decode_step: E=%d is not divisible by n_head=%d" % (E, n_head))
+    need = gpt_decode_pack_floats(n_layer, E, V)
+    if packed.numel() < need:
+        raise RuntimeError("gpt_decode_step: packed weights of %d floats, %d needed" % (packed.numel(), need))
+    _L().vqw_gpt_decode_step(packed, tok.detach(), pos.detach(), idx, kv, logits, ws, ws.numel() * 4, B, int(t), capacity, n_layer, int(n_head), E,
+                             V, pos.shape[-2], float(eps))
+    return logits
+
+
 class _MaxPool2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

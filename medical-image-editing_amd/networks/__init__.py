@@ -12,4 +12,4 @@ from .unet_discriminator import UNetDiscriminator  # noqa: F401
 from .vqgan import Normalize, nonlinearity, Upsample, ResnetBlock, AttnBlock, Decoder  # noqa: F401
 from .vqgan_model import Downsample, Encoder, VQGAN  # noqa: F401
 from .mingpt import GPTConfig, GPT1Config, CausalSelfAttention, Block  # noqa: F401
-from .gpt import GPT  # noqa: F401
+from .gpt import GPT, KVCache  # noqa: F401

@@ -15,6 +15,13 @@ past the reference adds pos_embed[:, past_length, :] - ONE position - to every n
 anything but exactly one new token (idx and `embeddings` rows together) behind a past raises ValueError, and past_length + 1 >
 block_size raises RuntimeError.  The cached route concatenates the past per step, as the reference does; it applies no mask
 (mingpt.py:79-80), so with n_unmasked > 0 it equals the full forward only when the first call carries at least n_unmasked tokens.
+
+Cached generation.  GPT.generate is sample() on a preallocated KV cache: GPT.new_cache builds a KVCache (the kv tensor, its length
+and capacity, the model's weights packed into one buffer, the step's workspace), GPT.prefill runs the prompt through the
+full-sequence kernels and copies every layer's k and v into the cache, GPT.decode_step is ONE ops.gpt_decode_step call per token:
+the whole step - embedding, per layer ln1 + q|k|v (k and v written straight into the cache row), attention over the cache, proj +
+residual, ln2 + fc1 + GELU, fc2 + residual, then ln_f + head - is 2 + 5 n_layer launches issued from C, with no copy of the past,
+no allocation and no synchronisation.  sample() stays as it is: the yardstick of the new path.  Neither has dropout (eval mode).
 """
 import torch
 import torch.nn as nn
@@ -135,3 +142,167 @@ class GPT(nn.Module):
         finally:
             self.train(was_training)
         return idx
+
+    # ---- cached generation: a preallocated KV cache and one host call per token (module docstring, "Cached generation")
+    def new_cache(self, batch_size, capacity=None):
+        """A KVCache for `batch_size` rows and `capacity` positions (default: block_size) on the model's device, with the weights
+        packed as they are now."""
+        capacity = self.block_size if capacity is None else int(capacity)
+        if batch_size < 1 or capacity < 1:
+            raise ValueError("GPT.new_cache: batch_size=%d and capacity=%d must be at least 1" % (batch_size, capacity))
+        return KVCache(self, int(batch_size), capacity)
+
+    def _check_cache(self, what, cache, B):
+        if self.training:
+            raise RuntimeError("GPT.%s: inference only, the model is in training mode (call .eval())" % what)
+        if cache.batch_size != B:
+            raise RuntimeError("GPT.%s: the cache was built for batch size %d, got %d rows" % (what, cache.batch_size, B))
+
+    @torch.no_grad()
+    def prefill(self, idx, cache, embeddings=None):
+        """The whole prompt idx (B, Tp) (behind `embeddings`, if given) through the full-sequence kernels - forward_with_past's first
+        call - with every layer's k and v copied into the cache rows [0, T) (one copy_ per layer); sets cache.length = T and returns
+        the logits (B, T, V).  Under the model's causal mask; the steps behind it apply none (forward_with_past's caveat): with
+        n_unmasked > 0 the prompt must carry at least n_unmasked tokens for the route to equal the full forward."""
+        self._check_cache("prefill", cache, idx.shape[0])
+        t = self._new_tokens(idx, embeddings)
+        if t < 1 or t > self.block_size or t > cache.capacity:
+            raise RuntimeError("GPT.prefill: a prompt of T=%d tokens; 1 <= T <= block_size=%d and T <= the cache's capacity=%d are needed" % (
+                t, self.block_size, cache.capacity))
+        nh = self.config.n_head
+        x = ops.embedding(idx, self.tok_embed.weight, self.pos_embed, embeddings)
+        for i, block in enumerate(self.blocks):
+            x, present = block(x, return_present=True)                                  # (2, B, nh, T, hs)
+            cache.kv[i][:, :, :t].unflatten(-1, (nh, -1)).copy_(present.transpose(2, 3))     # -> (2, B, T, nh, hs): the heads side by side
+        cache.length = t
+        return self._head(x)
+
+    @torch.no_grad()
+    def decode_step(self, idx, cache):
+        """One token per row, idx (B,) or (B, 1) torch.long on the device, behind the cache: ONE ops.gpt_decode_step call - the whole
+        step is launched from C, nothing is allocated but the logits, nothing synchronises.  Writes row cache.length of every
+        plane, advances cache.length and returns the logits (B, V) of the new position.  No mask (the layer_past route)."""
+        self._check_cache("decode_step", cache, idx.shape[0])
+        if idx.numel() != idx.shape[0]:
+            raise ValueError("GPT.decode_step: one token per row expected, got idx of shape %s" % (tuple(idx.shape),))
+        if cache.length >= cache.capacity:
+            raise RuntimeError("GPT.decode_step: the cache is full (length = capacity = %d)" % cache.capacity)
+        if cache.length + 1 > self.block_size:
+            raise RuntimeError("GPT.decode_step: length + 1 = %d exceeds block_size=%d" % (cache.length + 1, self.block_size))
+        logits = torch.empty(cache.batch_size, self.config.vocab_size, dtype=torch.float32, device=cache.kv.device)
+        ops.gpt_decode_step(cache.packed, self.tok_embed.weight, self.pos_embed, idx.reshape(-1), cache.kv, logits, cache.ws, cache.length,
+                            self.config.n_head, self.ln_f.eps)
+        cache.length += 1
+        return logits
+
+    @torch.no_grad()
+    def generate(self, idx, steps, temperature=1.0, top_k=None, generator=None, embeddings=None, uniforms=None):
+        """sample() on the cached route: idx (B, Tp) with `steps` sampled tokens appended, in eval mode.  The prompt goes through
+        prefill once, then every step is ops.sample_topk on the last logits and one decode_step.  Without `uniforms` each step draws
+        torch.rand(B, generator=...) on the device exactly as sample() does - a seed means the same stream in both; with `uniforms`
+        (steps, B) nothing is drawn and step k uses uniforms[k]."""
+        t = self._new_tokens(idx, embeddings)
+        if steps < 0 or t + steps > self.block_size:
+            raise RuntimeError("GPT.generate: prompt of %d tokens + %d steps exceeds block_size=%d" % (t, steps, self.block_size))
+        if not temperature > 0:
+            raise ValueError("GPT.generate: temperature=%r must be positive" % (temperature,))
+        B = idx.shape[0]
+        if uniforms is not None and tuple(uniforms.shape) != (steps, B):
+            raise ValueError("GPT.generate: uniforms of shape %s, (steps, B) = (%d, %d) expected" % (tuple(uniforms.shape), steps, B))
+        if steps == 0:
+            return idx
+        was_training = self.training
+        self.eval()
+        try:
+            cache = self.new_cache(B, capacity=t + steps - 1)          # the last sampled token is never fed back
+            if uniforms is not None:
+                uniforms = uniforms.to(device=cache.kv.device, dtype=torch.float32)
+            logits = self.prefill(idx, cache, embeddings)[:, -1, :]
+            out = [idx]
+            for k in range(steps):
+                u = uniforms[k] if uniforms is not None else torch.rand(B, generator=generator, device=logits.device)
+                new = ops.sample_topk(logits, u, temperature, top_k)
+                out.append(new.unsqueeze(1))
+                if k + 1 < steps:
+                    logits = self.decode_step(new, cache)
+        finally:
+            self.train(was_training)
+        return torch.cat(out, dim=1)
+
+
+def decode_pack_layout(n_layer, n_embed, vocab_size):
+    """[(state_dict key or tuple of keys stacked along the rows, offset in floats, shape)] of the packed-weights buffer
+    ops.gpt_decode_step reads - the layout documented in include/vqwnet_hip.h - and its size in floats."""
+    E, layout, off = n_embed, [], 0
+
+    def put(keys, shape):
+        nonlocal off
+        layout.append((keys, off, shape))
+        off += shape[0] * (shape[1] if len(shape) > 1 else 1)
+
+    for i in range(n_layer):
+        b = "blocks.%d." % i
+        put(b + "ln1.weight", (E,))
+        put(b + "ln1.bias", (E,))
+        put((b + "att.q.weight", b + "att.k.weight", b + "att.v.weight"), (3 * E, E))
+        put((b + "att.q.bias", b + "att.k.bias", b + "att.v.bias"), (3 * E,))
+        put(b + "att.proj.weight", (E, E))
+        put(b + "att.proj.bias", (E,))
+        put(b + "ln2.weight", (E,))
+        put(b + "ln2.bias", (E,))
+        put(b + "mlp.0.weight", (4 * E, E))
+        put(b + "mlp.0.bias", (4 * E,))
+        put(b + "mlp.2.weight", (E, 4 * E))
+        put(b + "mlp.2.bias", (E,))
+    put("ln_f.weight", (E,))
+    put("ln_f.bias", (E,))
+    put("head.weight", (vocab_size, E))
+    return layout, off
+
+
+@torch.no_grad()
+def pack_decode_weights(model, out=None):
+    """The model's weights in one contiguous buffer with decode_pack_layout's layout, by plain copy_ of the parameters; `out`: a
+    buffer of the right size to refill (the parameters may have changed), else a new one on the model's device."""
+    c = model.config
+    layout, n = decode_pack_layout(c.n_layer, c.n_embed, c.vocab_size)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=model.head.weight.device)
+    if out.numel() != n or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("pack_decode_weights: a contiguous fp32 buffer of %d floats expected, got %s of %s" % (n, tuple(out.shape), out.dtype))
+    params, flat = dict(model.named_parameters()), out.view(-1)
+    for keys, off, shape in layout:
+        for key in ((keys,) if isinstance(keys, str) else keys):
+            p = params[key]
+            flat[off:off + p.numel()].view(p.shape).copy_(p)
+            off += p.numel()
+    return out
+
+
+class KVCache:
+    """What GPT.decode_step works on, built by GPT.new_cache:
+
+        kv          (n_layer, 2, B, capacity, E) fp32: per layer a k-plane and a v-plane, the heads side by side in the last axis -
+                    the (B, T, E) layout ops.causal_attention takes, so kv[l, 0] can be handed to it unchanged
+        length      the rows [0, length) of every plane are valid (set by GPT.prefill, advanced by GPT.decode_step; setting it back
+                    rewinds the sequence)
+        capacity    rows of a plane
+        batch_size  B
+        packed      the model's weights as ops.gpt_decode_step reads them (pack_decode_weights): a snapshot taken at construction -
+                    call pack(model) after the parameters changed
+        ws          the step's activations workspace
+    """
+
+    def __init__(self, model, batch_size, capacity):
+        c, dev = model.config, model.head.weight.device
+        self.batch_size, self.capacity, self.length = batch_size, capacity, 0
+        self.kv = torch.empty(c.n_layer, 2, batch_size, capacity, c.n_embed, dtype=torch.float32, device=dev)
+        self.ws = torch.empty(ops.gpt_decode_ws_floats(batch_size, c.n_embed, c.vocab_size), dtype=torch.float32, device=dev)
+        if ops.gpt_decode_pack_floats(c.n_layer, c.n_embed, c.vocab_size) != decode_pack_layout(c.n_layer, c.n_embed, c.vocab_size)[1]:
+            raise RuntimeError("KVCache: the library's packed-weights size differs from decode_pack_layout's")
+        self.packed = pack_decode_weights(model)
+
+    def pack(self, model):
+        """Refill the packed weights from the model's parameters."""
+        pack_decode_weights(model, self.packed)
+        return self
