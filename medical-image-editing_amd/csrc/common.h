@@ -47,6 +47,7 @@ static inline int lds_opt_in(int bytes, const char* name) {
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int imin(int a, int b) { return a < b ? a : b; }
 static inline int imax(int a, int b) { return a > b ? a : b; }
+static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // Memory-bound grid sizing rule: cap at ~8 blocks per CU and grid-stride the rest.
 static inline int stream_grid(long work_items, int block) {

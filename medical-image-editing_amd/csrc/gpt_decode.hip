@@ -27,7 +27,6 @@
 #include "common.h"
 #include "../../include/vqwnet_hip.h"
 
-static inline bool gd_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 __device__ __forceinline__ float gd_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -163,7 +162,7 @@ extern "C" int vqw_dec_linear(const float* x, const float* w, const float* bias,
     VQW_CHECK(x && w && y, "vqw_dec_linear: null pointer");
     VQW_CHECK((ln_gamma != nullptr) == (ln_beta != nullptr), "vqw_dec_linear: ln_gamma and ln_beta must be given together");
     VQW_CHECK(y_col >= 0 && ldy >= y_col + N, "vqw_dec_linear: the output columns [%ld, %ld) do not fit the row stride ldy=%ld", y_col, y_col + N, ldy);
-    VQW_CHECK(gd_al16(x) && gd_al16(w) && gd_al16(ln_gamma) && gd_al16(ln_beta), "vqw_dec_linear: x, w and the LayerNorm parameters must be 16-byte aligned");
+    VQW_CHECK(al16(x) && al16(w) && al16(ln_gamma) && al16(ln_beta), "vqw_dec_linear: x, w and the LayerNorm parameters must be 16-byte aligned");
     VQW_CHECK((((uintptr_t)y) & 3) == 0 && (((uintptr_t)bias) & 3) == 0 && (((uintptr_t)residual) & 3) == 0,
               "vqw_dec_linear: y, bias and residual must be 4-byte aligned");
     VQW_CHECK((const float*)y != x, "vqw_dec_linear: y must not be x (y may be residual: the add is in place)");
@@ -299,7 +298,7 @@ extern "C" int vqw_dec_attention(const float* q, const float* k, const float* v,
                                  float scale, void* stream) {
     if (int rc = dec_attention_check("vqw_dec_attention", B, Tk, capacity, n_head, hs)) return rc;
     VQW_CHECK(q && k && v && o, "vqw_dec_attention: null pointer");
-    VQW_CHECK(gd_al16(q) && gd_al16(k) && gd_al16(v) && gd_al16(o), "vqw_dec_attention: tensors must be 16-byte aligned");
+    VQW_CHECK(al16(q) && al16(k) && al16(v) && al16(o), "vqw_dec_attention: tensors must be 16-byte aligned");
     dec_attention_launch(q, k, v, o, B, Tk, capacity, n_head, hs, scale, (hipStream_t)stream);
     VQW_LAUNCH_CHECK("vqw_dec_attention");
     return VQW_OK;
@@ -353,7 +352,7 @@ extern "C" int vqw_gpt_decode_step(const float* packed, const float* tok, const 
     VQW_CHECK(t < capacity, "%s: t=%d: the cache of capacity=%d rows is full", name, t, capacity);
     VQW_CHECK(block_size >= 1 && t < block_size, "%s: t + 1 = %d exceeds block_size=%d", name, t + 1, block_size);
     VQW_CHECK(ws_bytes >= vqw_gpt_decode_ws_bytes(B, E, V), "%s: workspace of %zu bytes, %zu needed", name, ws_bytes, vqw_gpt_decode_ws_bytes(B, E, V));
-    VQW_CHECK(gd_al16(packed) && gd_al16(tok) && gd_al16(pos) && gd_al16(kv) && gd_al16(logits) && gd_al16(ws), "%s: tensors must be 16-byte aligned", name);
+    VQW_CHECK(al16(packed) && al16(tok) && al16(pos) && al16(kv) && al16(logits) && al16(ws), "%s: tensors must be 16-byte aligned", name);
     VQW_CHECK((((uintptr_t)idx) & 7) == 0, "%s: idx must be 8-byte aligned", name);
     if (int rc = dec_linear_check(name, B, 4 * E, V, false)) return rc;
 

@@ -25,7 +25,6 @@
 #include "common.h"
 #include "../../include/vqwnet_hip.h"
 
-static inline bool gh_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 __device__ __forceinline__ float wave_max_f(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -134,7 +133,7 @@ extern "C" int vqw_embed_fwd(const long* idx, const float* tok, const float* pos
     if (int rc = em_check("vqw_embed_fwd", B, Ti, Te, E, V, block_size, t0)) return rc;
     VQW_CHECK(tok && pos && x && (idx || Ti == 0), "vqw_embed_fwd: null pointer");
     VQW_CHECK((prefix != nullptr) == (Te > 0), "vqw_embed_fwd: prefix must be given exactly when Te=%d is positive", Te);
-    VQW_CHECK(gh_al16(tok) && gh_al16(pos) && gh_al16(prefix) && gh_al16(x), "vqw_embed_fwd: tensors must be 16-byte aligned");
+    VQW_CHECK(al16(tok) && al16(pos) && al16(prefix) && al16(x), "vqw_embed_fwd: tensors must be 16-byte aligned");
     const long rows = (long)B * (Te + Ti);
     hipLaunchKernelGGL(k_embed_fwd, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, idx, tok, pos, prefix, x, rows, Ti, Te, E, V, t0);
     VQW_LAUNCH_CHECK("vqw_embed_fwd");
@@ -145,7 +144,7 @@ extern "C" int vqw_embed_bwd(const long* idx, const float* gx, float* gtok, floa
                              int t0, void* stream) {
     if (int rc = em_check("vqw_embed_bwd", B, Ti, Te, E, V, block_size, t0)) return rc;
     VQW_CHECK(gx && gtok && gpos && (idx || Ti == 0), "vqw_embed_bwd: null pointer");
-    VQW_CHECK(gh_al16(gx) && gh_al16(gtok) && gh_al16(gpos), "vqw_embed_bwd: tensors must be 16-byte aligned");
+    VQW_CHECK(al16(gx) && al16(gtok) && al16(gpos), "vqw_embed_bwd: tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_embed_gpos, dim3(stream_grid((long)block_size * (E >> 2), 256)), dim3(256), 0, st, gx, gpos, B, Te + Ti, E, block_size, t0);
     if (E <= EM_SMALL_E) hipLaunchKernelGGL((k_embed_gtok<EM_SMALL_E / 256>), dim3(ceil_div(V, 4)), dim3(256), 0, st, idx, gx, gtok, B, Ti, Te, E, V);

@@ -1,5 +1,5 @@
-// GroupNorm(32 groups, affine)(+swish) and single-head self-attention over a feature map: the two kernel families of the
-// VQGAN decoder blocks (networks/vqgan.py: Normalize / nonlinearity :10-19, AttnBlock :125-180).  NHWC fp32.
+// GroupNorm(32 groups, affine)(+swish) and swish on its own: the normalisation of the VQGAN blocks (networks/vqgan.py:
+// Normalize / nonlinearity :10-19).  NHWC fp32.  The blocks' self-attention is in attention.hip.
 //
 // GroupNorm.  A thread owns one float4 column (four channels) of the tensor and walks pixels, so gamma, beta and the
 // statistics of its channels are loaded once.  Every reduction is two-stage and deterministic: per-thread double sums, a
@@ -8,14 +8,6 @@
 // from channel sums, so any channel count that is a multiple of 32 works - a group of 3 channels (C = 96) does not have to be a
 // float4 multiple.  A plane of at most GN_ONE_WG_ELEMS elements per image takes one workgroup that finalises in its own tail; a
 // larger one is split.
-//
-// Attention.  o = softmax(scale q k^T) v per batch element, q, k, v [B][N][C].  All five matrix products (q k^T and p v
-// forward; recomputed q k^T, dO v^T, dS k, dS^T q and p^T dO backward) are one of two forms on the exact-fp32 32x32x2 MFMA:
-//   attn_gemm_nt: T[32][64] = A[32 rows][C] . B[64 rows][C]^T   (operands staged in LDS in chunks of <= 128 channels)
-//   attn_gemm_pv: acc[32][C] += P[32][64] (LDS) . B[64 rows][C]  (each wave owns the 32-column blocks w, w + 4, ...)
-// A workgroup owns 32 "tile rows" (queries forward and for dQ; keys for dK / dV, where the transposed score tile is computed
-// directly as k q^T - no transposed LDS reads) and walks the other axis in tiles of 64.  The N x N matrix never leaves LDS.
-// No atomics anywhere: every output element is written by one thread, sums run in a fixed order.
 #include <type_traits>
 #include "common.h"
 #include "mfma_util.h"
@@ -335,8 +327,6 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(const float* __restrict__ 
     });
 }
 
-static inline bool gn_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // the tier choice, written once: one workgroup per image that finalises in its tail, or split + finalise pass
 template <class F>
 static void gn_launch_reduce(F f, double* part, double* tot, int N, int HW, int C, hipStream_t st) {
@@ -367,7 +357,7 @@ extern "C" int vqw_groupnorm_fwd(const float* x, const float* gamma, const float
                                  size_t ws_bytes, int N, int HW, int C, float eps, int swish, void* stream) {
     VQW_CHECK(x && gamma && beta && y && mean && rstd && ws, "vqw_groupnorm_fwd: null pointer");
     if (int rc = gn_check("vqw_groupnorm_fwd", N, HW, C, ws_bytes)) return rc;
-    VQW_CHECK(gn_al16(x) && gn_al16(y) && gn_al16(ws), "vqw_groupnorm_fwd: tensors must be 16-byte aligned");
+    VQW_CHECK(al16(x) && al16(y) && al16(ws), "vqw_groupnorm_fwd: tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     FGnStats f{x, mean, rstd, eps};
     gn_launch_reduce(f, (double*)ws, (double*)((char*)ws + gn_part_bytes(N, HW, C)), N, HW, C, st);
@@ -383,7 +373,7 @@ extern "C" int vqw_groupnorm_bwd(const float* x, const float* gamma, const float
                                  int C, int swish, void* stream) {
     VQW_CHECK(x && gamma && beta && mean && rstd && gy && gx && dgamma && dbeta && ws, "vqw_groupnorm_bwd: null pointer");
     if (int rc = gn_check("vqw_groupnorm_bwd", N, HW, C, ws_bytes)) return rc;
-    VQW_CHECK(gn_al16(x) && gn_al16(gy) && gn_al16(gx) && gn_al16(ws), "vqw_groupnorm_bwd: tensors must be 16-byte aligned");
+    VQW_CHECK(al16(x) && al16(gy) && al16(gx) && al16(ws), "vqw_groupnorm_bwd: tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     double* part = (double*)ws;
     double* tot = (double*)((char*)ws + gn_part_bytes(N, HW, C));
@@ -420,364 +410,5 @@ extern "C" int vqw_swish_bwd(const float* x, const float* gy, float* gx, long n,
     VQW_CHECK(x && gy && gx && n > 0, "vqw_swish_bwd: bad arguments");
     hipLaunchKernelGGL(k_swish_bwd, dim3(stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, x, gy, gx, n);
     VQW_LAUNCH_CHECK("vqw_swish_bwd");
-    return VQW_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------- attention
-#define AT_BM 32           // tile rows a workgroup owns
-#define AT_BN 64           // tile columns per step of the walk
-#define AT_KC 128          // channels per staged chunk
-#define AT_LD (AT_KC + 4)  // LDS row stride of a staged chunk: ds_read_b128 of 32 consecutive rows conflict-free
-#define AT_LDS (AT_BN + 4) // LDS row stride of a score tile
-#define AT_MAX_C 512        // widest value / output column window one workgroup keeps in registers
-#define AT_MAX_C2 1024      // two such windows: the grid's z dimension
-
-// LDS carve-up (floats).  A: staged 32-row operand chunk; B: staged 64-row operand chunk; T0 / T1: two score tiles as two
-// half-sums each; P0 / P1: the element-wise stage's results (the A operand of attn_gemm_pv); row vectors.
-#define AT_OFF_A 0
-#define AT_OFF_B (AT_OFF_A + AT_BM * AT_LD)
-#define AT_OFF_T0 (AT_OFF_B + AT_BN * AT_LD)
-#define AT_OFF_T1 (AT_OFF_T0 + 2 * AT_BM * AT_LDS)
-#define AT_OFF_P0 (AT_OFF_T1 + 2 * AT_BM * AT_LDS)
-#define AT_OFF_P1 (AT_OFF_P0 + AT_BM * AT_LDS)
-#define AT_OFF_V (AT_OFF_P1 + AT_BM * AT_LDS)         // 4 x 64 floats of row / column vectors
-#define AT_LDS_FLOATS (AT_OFF_V + 4 * AT_BN)
-#define AT_LDS_BYTES (AT_LDS_FLOATS * 4)
-
-// rows [row0, row0 + R) x channels [c0, c0 + wt) of src [n_rows][C] -> dst [R][AT_LD]; rows at or past n_rows are zeros
-__device__ __forceinline__ void attn_stage(float* dst, const float* __restrict__ src, int row0, int n_rows, int R, int c0, int wt, int C) {
-    const int w4 = wt >> 2;
-    for (int i = threadIdx.x; i < R * w4; i += 256) {
-        const int r = i / w4, c4 = i - r * w4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row0 + r < n_rows) v = *(const float4*)(src + (long)(row0 + r) * C + c0 + c4 * 4);
-        *(float4*)(dst + r * AT_LD + c4 * 4) = v;
-    }
-}
-
-// T[32][64] = A[a0 .. a0+32) . B[b0 .. b0+64)^T over all C channels, left in LDS as two half-sums T[0], T[1] ([32][AT_LDS]
-// each; the consumer adds them): wave w takes the 32 columns (w & 1) and half (w >> 1) of every chunk's channels.
-// Lane l feeds row / column l % 32; its four consecutive channels 8 s + 4 (l / 32) + {0..3} go to four MFMAs.
-// FOLD (the kernels above 512 channels): every chunk's sum is added to a second accumulator, so that no chain of dependent roundings is longer than
-// at 128 channels (a single chain over 1024 channels left lse twice as far from float64 as torch's fp32 bmm is).
-template <bool FOLD>
-__device__ __forceinline__ void attn_gemm_nt(float* lds, float* T, const float* __restrict__ A, int a0, int na, const float* __restrict__ B,
-                                             int b0, int nb, int C) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, kb = wv & 1, hf = wv >> 1;
-    const int lr = lane & 31, lh = lane >> 5;
-    f32x16 acc = {0}, tot = {0};
-    for (int c0 = 0; c0 < C; c0 += AT_KC) {
-        const int wt = imin_d(AT_KC, C - c0);
-        __syncthreads();                      // the previous users of the staging buffers are done
-        attn_stage(lds + AT_OFF_A, A, a0, na, AT_BM, c0, wt, C);
-        attn_stage(lds + AT_OFF_B, B, b0, nb, AT_BN, c0, wt, C);
-        __syncthreads();
-        const int half = wt >> 1;             // a multiple of 16
-        const float* pa = lds + AT_OFF_A + lr * AT_LD + hf * half + lh * 4;
-        const float* pb = lds + AT_OFF_B + (kb * 32 + lr) * AT_LD + hf * half + lh * 4;
-        for (int s = 0; s < half; s += 8) {
-            const float4 a = *(const float4*)(pa + s), b = *(const float4*)(pb + s);
-            acc = MFMA32(a.x, b.x, acc);
-            acc = MFMA32(a.y, b.y, acc);
-            acc = MFMA32(a.z, b.z, acc);
-            acc = MFMA32(a.w, b.w, acc);
-        }
-        if constexpr (FOLD) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { tot[r] += acc[r]; acc[r] = 0.f; }
-        }
-    }
-    if constexpr (FOLD) acc = tot;
-    float* t = T + hf * (AT_BM * AT_LDS) + kb * 32 + lr;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t[((r & 3) + 8 * (r >> 2) + 4 * lh) * AT_LDS] = acc[r];
-    __syncthreads();
-}
-
-// The value / output side works on a window of Cw = C / gridDim.z columns starting at column blockIdx.z Cw of rows of C floats
-// (one window = the whole row up to 512 channels, two halves above): the callers offset the pointers by attn_col0.
-__device__ __forceinline__ int attn_col0(int C) { return (int)blockIdx.z * (C / (int)gridDim.z); }
-
-// acc[t] (the 32 x 32 block of columns 128 t + 32 w of wave w) += P[32][64] . B[b0 .. b0+64)[window of row stride C]
-template <int CT>
-__device__ __forceinline__ void attn_gemm_pv(float* lds, const float* P, const float* __restrict__ B, int b0, int nb, int C, f32x16 (&acc)[CT]) {
-    const int Cw = C / (int)gridDim.z;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int lr = lane & 31, lh = lane >> 5;
-#pragma unroll
-    for (int t = 0; t < CT; ++t) {
-        const int c0 = t * AT_KC, wt = imin_d(AT_KC, Cw - c0);
-        __syncthreads();
-        attn_stage(lds + AT_OFF_B, B, b0, nb, AT_BN, c0, wt, C);
-        __syncthreads();
-        if (wv * 32 < wt) {
-            const float* pa = P + lr * AT_LDS + lh * 4;
-            const float* pb = lds + AT_OFF_B + (lh * 4) * AT_LD + wv * 32 + lr;
-#pragma unroll
-            for (int s = 0; s < AT_BN; s += 8) {
-                const float4 a = *(const float4*)(pa + s);
-                acc[t] = MFMA32(a.x, pb[(s + 0) * AT_LD], acc[t]);
-                acc[t] = MFMA32(a.y, pb[(s + 1) * AT_LD], acc[t]);
-                acc[t] = MFMA32(a.z, pb[(s + 2) * AT_LD], acc[t]);
-                acc[t] = MFMA32(a.w, pb[(s + 3) * AT_LD], acc[t]);
-            }
-        }
-    }
-}
-
-// out[row0 + row][128 t + 32 w + lane % 32] = acc * f(row) for the valid rows (columns of the window, rows of C floats)
-template <int CT, class RowScale>
-__device__ __forceinline__ void attn_store(float* __restrict__ out, int row0, int n_rows, int C, const f32x16 (&acc)[CT], RowScale rs) {
-    const int Cw = C / (int)gridDim.z;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int lr = lane & 31, lh = lane >> 5;
-#pragma unroll
-    for (int t = 0; t < CT; ++t) {
-        const int c = t * AT_KC + wv * 32;
-        if (c < Cw) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (row0 + row < n_rows) out[(long)(row0 + row) * C + c + lr] = acc[t][r] * rs(row);
-            }
-        }
-    }
-}
-
-// element-wise stage: thread -> row tid / 8, columns tid % 8 + 8 e (e = 0..7): the eight threads of a row are neighbours
-#define AT_EW_ROW (threadIdx.x >> 3)
-#define AT_EW_COL(e) ((threadIdx.x & 7) + 8 * (e))
-__device__ __forceinline__ float attn_row8_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64));
-    return v;
-}
-__device__ __forceinline__ float attn_row8_sum(float v) {       // fixed butterfly: the same bits in all eight lanes, every run
-    v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-    return v;
-}
-
-// grid (ceil(N / 32), B, column windows).  Online softmax: running row maximum m and sum l live in the row's eight threads.
-template <int CT, bool WIDE>
-__global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                  float* __restrict__ o, float* __restrict__ lse, int N, int C, float scale) {
-    extern __shared__ __align__(16) float lds[];
-    const long boff = (long)blockIdx.y * N * C;
-    q += boff; k += boff; v += boff + attn_col0(C); o += boff + attn_col0(C);
-    const int i0 = blockIdx.x * AT_BM;
-    float* T = lds + AT_OFF_T0;
-    float* P = lds + AT_OFF_P0;
-    float* alpha = lds + AT_OFF_V;          // [32] this step's rescale of the accumulated rows
-    f32x16 acc[CT];
-#pragma unroll
-    for (int t = 0; t < CT; ++t) acc[t] = (f32x16){0};
-    float m = -INFINITY, l = 0.f;
-    const int row = AT_EW_ROW;
-    for (int j0 = 0; j0 < N; j0 += AT_BN) {
-        attn_gemm_nt<WIDE>(lds, T, q, i0, N, k, j0, N, C);
-        float s[8], mt = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int col = AT_EW_COL(e);
-            s[e] = (j0 + col < N) ? scale * (T[row * AT_LDS + col] + T[AT_BM * AT_LDS + row * AT_LDS + col]) : -INFINITY;
-            mt = fmaxf(mt, s[e]);
-        }
-        const float mn = fmaxf(m, attn_row8_max(mt));       // finite: every tile holds at least one key
-        float ps = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float p = expf(s[e] - mn);
-            P[row * AT_LDS + AT_EW_COL(e)] = p;
-            ps += p;
-        }
-        const float a = expf(m - mn);
-        l = fmaf(l, a, attn_row8_sum(ps));
-        m = mn;
-        if ((threadIdx.x & 7) == 0) alpha[row] = a;
-        __syncthreads();
-        {
-            const int lh = (threadIdx.x & 63) >> 5;
-            float ar[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) ar[r] = alpha[(r & 3) + 8 * (r >> 2) + 4 * lh];
-#pragma unroll
-            for (int t = 0; t < CT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[t][r] *= ar[r];
-        }
-        attn_gemm_pv<CT>(lds, P, v, j0, N, C, acc);
-    }
-    __syncthreads();
-    float* rinv = lds + AT_OFF_V + AT_BN;
-    if ((threadIdx.x & 7) == 0) {
-        rinv[row] = 1.f / l;
-        if (i0 + row < N && blockIdx.z == 0) lse[(long)blockIdx.y * N + i0 + row] = m + logf(l);
-    }
-    __syncthreads();
-    attn_store<CT>(o, i0, N, C, acc, [&](int r) { return rinv[r]; });
-}
-
-// D[b][i] = sum_c dO O: one wave per row, fixed butterfly
-__global__ void __launch_bounds__(256) k_attn_rowdot(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ d, long rows, int C) {
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const int lane = threadIdx.x & 63;
-    float s = 0.f;
-    for (int c = lane * 4; c < C; c += 256) {
-        const float4 x = *(const float4*)(a + r * C + c), y = *(const float4*)(b + r * C + c);
-        s = fmaf(x.x, y.x, s); s = fmaf(x.y, y.y, s); s = fmaf(x.z, y.z, s); s = fmaf(x.w, y.w, s);
-    }
-    s = wave_sum_f(s);
-    if (lane == 0) d[r] = s;
-}
-
-// The backward's element-wise stage on the two tiles T0 = (q k^T or k q^T) and T1 = (dO v^T or v dO^T): P = exp(scale S - lse),
-// dS = scale P (dP - D), with lse / D indexed by the QUERY: the tile row (ROWS_ARE_QUERIES) or the tile column.  Entries whose
-// row or column lies past N are zero.  vec: lse at [0, 64), D at [64, 128) of the tile's query range.
-template <bool ROWS_ARE_QUERIES>
-__device__ __forceinline__ void attn_bwd_stage(float* lds, const float* vec, int r0, int c0, int N, float scale, bool want_p) {
-    const float* T0 = lds + AT_OFF_T0;
-    const float* T1 = lds + AT_OFF_T1;
-    float* P = lds + AT_OFF_P0;
-    float* dS = lds + AT_OFF_P1;
-    const int row = AT_EW_ROW;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int col = AT_EW_COL(e), qi = ROWS_ARE_QUERIES ? row : col;
-        const bool ok = (r0 + row < N) && (c0 + col < N);
-        const float sc = scale * (T0[row * AT_LDS + col] + T0[AT_BM * AT_LDS + row * AT_LDS + col]);
-        const float dp = T1[row * AT_LDS + col] + T1[AT_BM * AT_LDS + row * AT_LDS + col];
-        const float p = ok ? expf(sc - vec[qi]) : 0.f;
-        if (want_p) P[row * AT_LDS + col] = p;
-        dS[row * AT_LDS + col] = scale * p * (dp - vec[AT_BN + qi]);
-    }
-    __syncthreads();
-}
-
-// grid (ceil(N / 32), B): dQ = scale (P o (dO v^T - D)) k for a tile of 32 queries, walking the keys
-template <int CT, bool WIDE>
-__global__ void __launch_bounds__(256) k_attn_dq(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                 const float* __restrict__ go, const float* __restrict__ lse, const float* __restrict__ D,
-                                                 float* __restrict__ gq, int N, int C, float scale) {
-    extern __shared__ __align__(16) float lds[];
-    const long boff = (long)blockIdx.y * N * C;
-    q += boff; k += boff; v += boff; go += boff; gq += boff + attn_col0(C);
-    lse += (long)blockIdx.y * N; D += (long)blockIdx.y * N;
-    const int i0 = blockIdx.x * AT_BM;
-    float* vec = lds + AT_OFF_V;
-    if (threadIdx.x < AT_BM) {
-        const bool ok = i0 + threadIdx.x < N;
-        vec[threadIdx.x] = ok ? lse[i0 + threadIdx.x] : 0.f;
-        vec[AT_BN + threadIdx.x] = ok ? D[i0 + threadIdx.x] : 0.f;
-    }
-    f32x16 acc[CT];
-#pragma unroll
-    for (int t = 0; t < CT; ++t) acc[t] = (f32x16){0};
-    for (int j0 = 0; j0 < N; j0 += AT_BN) {
-        attn_gemm_nt<WIDE>(lds, lds + AT_OFF_T0, q, i0, N, k, j0, N, C);
-        attn_gemm_nt<WIDE>(lds, lds + AT_OFF_T1, go, i0, N, v, j0, N, C);
-        attn_bwd_stage<true>(lds, vec, i0, j0, N, scale, false);
-        attn_gemm_pv<CT>(lds, lds + AT_OFF_P1, k + attn_col0(C), j0, N, C, acc);
-    }
-    attn_store<CT>(gq, i0, N, C, acc, [](int) { return 1.f; });
-}
-
-// grid (ceil(N / 32), B): dK = scale (P o (dO v^T - D))^T q and dV = P^T dO for a tile of 32 keys, walking the queries
-template <int CT, bool WIDE>
-__global__ void __launch_bounds__(256) k_attn_dkdv(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                   const float* __restrict__ go, const float* __restrict__ lse, const float* __restrict__ D,
-                                                   float* __restrict__ gk, float* __restrict__ gv, int N, int C, float scale) {
-    extern __shared__ __align__(16) float lds[];
-    const long boff = (long)blockIdx.y * N * C;
-    q += boff; k += boff; v += boff; go += boff; gk += boff + attn_col0(C); gv += boff + attn_col0(C);
-    lse += (long)blockIdx.y * N; D += (long)blockIdx.y * N;
-    const int j0 = blockIdx.x * AT_BM;
-    float* vec = lds + AT_OFF_V;
-    f32x16 ak[CT], av[CT];
-#pragma unroll
-    for (int t = 0; t < CT; ++t) { ak[t] = (f32x16){0}; av[t] = (f32x16){0}; }
-    for (int i0 = 0; i0 < N; i0 += AT_BN) {
-        __syncthreads();                      // the previous step's readers of vec are done
-        if (threadIdx.x < AT_BN) {
-            const bool ok = i0 + threadIdx.x < N;
-            vec[threadIdx.x] = ok ? lse[i0 + threadIdx.x] : 0.f;
-            vec[AT_BN + threadIdx.x] = ok ? D[i0 + threadIdx.x] : 0.f;
-        }
-        attn_gemm_nt<WIDE>(lds, lds + AT_OFF_T0, k, j0, N, q, i0, N, C);
-        attn_gemm_nt<WIDE>(lds, lds + AT_OFF_T1, v, j0, N, go, i0, N, C);
-        attn_bwd_stage<false>(lds, vec, j0, i0, N, scale, true);
-        attn_gemm_pv<CT>(lds, lds + AT_OFF_P0, go + attn_col0(C), i0, N, C, av);
-        attn_gemm_pv<CT>(lds, lds + AT_OFF_P1, q + attn_col0(C), i0, N, C, ak);
-    }
-    attn_store<CT>(gk, j0, N, C, ak, [](int) { return 1.f; });
-    attn_store<CT>(gv, j0, N, C, av, [](int) { return 1.f; });
-}
-
-static int attn_check(const char* name, int B, int N, int C) {
-    VQW_CHECK(B >= 1 && B <= 65535 && N >= 1 && N <= (1 << 20), "%s: bad shape B=%d N=%d", name, B, N);
-    VQW_CHECK(C >= 32 && ((C % 32 == 0 && C <= AT_MAX_C) || (C % 64 == 0 && C <= AT_MAX_C2)),
-              "%s: C=%d must be a multiple of 32 up to %d or a multiple of 64 up to %d", name, C, AT_MAX_C, AT_MAX_C2);
-    return VQW_OK;
-}
-// column windows of the value / output side (the grid's z dimension), and the 128-channel blocks of one window
-static inline int attn_windows(int C) { return C > AT_MAX_C ? 2 : 1; }
-static inline int attn_ct(int C) { return ceil_div(C / attn_windows(C), AT_KC); }
-
-template <int CT, bool WIDE = false>
-static int attn_fwd_launch(const float* q, const float* k, const float* v, float* o, float* lse, int B, int N, int C, float scale, hipStream_t st) {
-    if (int rc = lds_opt_in<k_attn_fwd<CT, WIDE>>(AT_LDS_BYTES, "vqw_attention_fwd")) return rc;
-    hipLaunchKernelGGL((k_attn_fwd<CT, WIDE>), dim3(ceil_div(N, AT_BM), B, attn_windows(C)), dim3(256), AT_LDS_BYTES, st, q, k, v, o, lse, N, C, scale);
-    return VQW_OK;
-}
-template <int CT, bool WIDE = false>
-static int attn_bwd_launch(const float* q, const float* k, const float* v, const float* go, const float* lse, const float* D, float* gq,
-                           float* gk, float* gv, int B, int N, int C, float scale, hipStream_t st) {
-    if (int rc = lds_opt_in<k_attn_dq<CT, WIDE>>(AT_LDS_BYTES, "vqw_attention_bwd")) return rc;
-    if (int rc = lds_opt_in<k_attn_dkdv<CT, WIDE>>(AT_LDS_BYTES, "vqw_attention_bwd")) return rc;
-    const dim3 grid(ceil_div(N, AT_BM), B, attn_windows(C));
-    hipLaunchKernelGGL((k_attn_dq<CT, WIDE>), grid, dim3(256), AT_LDS_BYTES, st, q, k, v, go, lse, D, gq, N, C, scale);
-    hipLaunchKernelGGL((k_attn_dkdv<CT, WIDE>), grid, dim3(256), AT_LDS_BYTES, st, q, k, v, go, lse, D, gk, gv, N, C, scale);
-    return VQW_OK;
-}
-
-extern "C" int vqw_attention_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int N, int C, float scale,
-                                 void* stream) {
-    VQW_CHECK(q && k && v && o && lse, "vqw_attention_fwd: null pointer");
-    if (int rc = attn_check("vqw_attention_fwd", B, N, C)) return rc;
-    VQW_CHECK(gn_al16(q) && gn_al16(k) && gn_al16(v), "vqw_attention_fwd: tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (attn_windows(C) == 2) {          // 576 ... 1024 channels: windows of 288 ... 512, three or four 128-channel blocks
-        rc = attn_ct(C) == 3 ? attn_fwd_launch<3, true>(q, k, v, o, lse, B, N, C, scale, st) : attn_fwd_launch<4, true>(q, k, v, o, lse, B, N, C, scale, st);
-    } else switch (attn_ct(C)) {
-        case 1: rc = attn_fwd_launch<1>(q, k, v, o, lse, B, N, C, scale, st); break;
-        case 2: rc = attn_fwd_launch<2>(q, k, v, o, lse, B, N, C, scale, st); break;
-        case 3: rc = attn_fwd_launch<3>(q, k, v, o, lse, B, N, C, scale, st); break;
-        default: rc = attn_fwd_launch<4>(q, k, v, o, lse, B, N, C, scale, st); break;
-    }
-    if (rc) return rc;
-    VQW_LAUNCH_CHECK("vqw_attention_fwd");
-    return VQW_OK;
-}
-
-extern "C" int vqw_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
-                                 float* d_ws, float* gq, float* gk, float* gv, int B, int N, int C, float scale, void* stream) {
-    VQW_CHECK(q && k && v && o && lse && go && d_ws && gq && gk && gv, "vqw_attention_bwd: null pointer");
-    if (int rc = attn_check("vqw_attention_bwd", B, N, C)) return rc;
-    VQW_CHECK(gn_al16(q) && gn_al16(k) && gn_al16(v) && gn_al16(o) && gn_al16(go), "vqw_attention_bwd: tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const long rows = (long)B * N;
-    hipLaunchKernelGGL(k_attn_rowdot, dim3(ceil_div(rows, 4)), dim3(256), 0, st, go, o, d_ws, rows, C);
-    int rc;
-    if (attn_windows(C) == 2) {
-        rc = attn_ct(C) == 3 ? attn_bwd_launch<3, true>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st)
-                             : attn_bwd_launch<4, true>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st);
-    } else switch (attn_ct(C)) {
-        case 1: rc = attn_bwd_launch<1>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st); break;
-        case 2: rc = attn_bwd_launch<2>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st); break;
-        case 3: rc = attn_bwd_launch<3>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st); break;
-        default: rc = attn_bwd_launch<4>(q, k, v, go, lse, d_ws, gq, gk, gv, B, N, C, scale, st); break;
-    }
-    if (rc) return rc;
-    VQW_LAUNCH_CHECK("vqw_attention_bwd");
     return VQW_OK;
 }

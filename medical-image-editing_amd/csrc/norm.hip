@@ -684,7 +684,6 @@ __global__ void k_inorm_bwd_pair_apply4(const float4* __restrict__ xa, const flo
 // Tiers of an element-wise map: scalar flat index; float4 flat index (C % 4 == 0, every channel stride and offset % 4 == 0,
 // every tensor 16-byte aligned); float4 division-free walk (additionally C / 4 a power of two <= 256, see below).  A reduction
 // on the float4 tiers is k_plane_reduce4 / k_plane_reduce4p (launch_plane_reduce4 picks by the same walk_ok).
-static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static inline int ilog2_exact(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
 static inline bool walk_ok(int C4) { return C4 >= 1 && C4 <= 256 && ilog2_exact(C4) >= 0; }
 enum Tier { TIER_SCALAR, TIER_FLAT4, TIER_WALK4 };

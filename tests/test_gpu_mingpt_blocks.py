@@ -45,7 +45,7 @@ def _gate(got, truth, ref32, what):
 
 
 # ------------------------------------------------------------------------------------------------ causal_attention
-# Tiles: a workgroup owns 32 rows and walks the other axis in steps of 64 (CA_BM, CA_BN in csrc/mingpt.hip).
+# Tiles: a workgroup owns 32 rows and walks the other axis in steps of 64 (AT_BM, AT_BN in csrc/attention.hip).
 ATTN_CASES = [(2, 1, 2, 32, 0), (2, 40, 2, 32, 5), (2, 70, 3, 32, 0), (1, 96, 1, 96, 0), (1, 129, 2, 64, 40), (1, 129, 1, 128, 129)]
 
 

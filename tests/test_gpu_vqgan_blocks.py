@@ -20,7 +20,7 @@ DEV = "cuda"
 CL = torch.channels_last
 
 # vqw_groupnorm_splits: a plane of at most this many elements (H W C per image) is reduced and finalised by one workgroup,
-# a larger one is split across workgroups with a finalise pass (GN_ONE_WG_ELEMS in csrc/groupnorm_attn.hip)
+# a larger one is split across workgroups with a finalise pass (GN_ONE_WG_ELEMS in csrc/groupnorm.hip)
 GN_ONE_WG_ELEMS = 16384
 SMALLEST_SPLIT_PLANE = (19, 27)          # 513 pixels x 32 channels = 16416 elements: the smallest C = 32 plane that is split
 
@@ -121,10 +121,12 @@ def test_swish_operator():
 
 
 # ------------------------------------------------------------------------------------------------ self_attention
-# Tiles: a workgroup owns 32 rows and walks the other axis in steps of 64 (AT_BM, AT_BN in csrc/groupnorm_attn.hip).  12 x 12 =
+# Tiles: a workgroup owns 32 rows and walks the other axis in steps of 64 (AT_BM, AT_BN in csrc/attention.hip).  12 x 12 =
 # 144 = 4 x 32 + 16 = 2 x 64 + 16: ragged on both axes, three steps.  40 x 40 = 1600 = 25 x 64 would leave no ragged last key
-# tile, so that case runs at 41 x 41 = 1681 = 52 x 32 + 17 = 26 x 64 + 17.
-ATTN_CASES = [(2, 4, 4, 32), (1, 12, 12, 64), (1, 41, 41, 128), (2, 16, 16, 512)]
+# tile, so that case runs at 41 x 41 = 1681 = 52 x 32 + 17 = 26 x 64 + 17.  The last two cases reach the unsplit route's two- and
+# three-block column windows (C = 256, 384): 5 x 7 = 35 is one ragged key step and a ragged second row tile, 9 x 9 = 81 two key
+# steps with both axes ragged.
+ATTN_CASES = [(2, 4, 4, 32), (1, 12, 12, 64), (1, 41, 41, 128), (2, 16, 16, 512), (1, 5, 7, 256), (1, 9, 9, 384)]
 
 
 def _attn_inputs(B, H, W, C, seed, qscale=1.0):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The two kernel families of the VQGAN decoder blocks (csrc/groupnorm_attn.hip) alone on one GPU, one JSON line per
-measurement, HIP events on the launch stream around --reps launches, --windows windows after --warmup launches:
+"""The two kernel families of the VQGAN decoder blocks (csrc/groupnorm.hip, csrc/attention.hip) alone on one GPU, one JSON
+line per measurement, HIP events on the launch stream around --reps launches, --windows windows after --warmup launches:
 
   group_norm      forward (statistics + apply) and backward (reduce + apply) with swish at 4x512x512x32, 4x256x256x64 and
                   4x32x32x512: ms and achieved bytes/s, bytes = the tensor passes the launches make (forward: x twice, y once;
