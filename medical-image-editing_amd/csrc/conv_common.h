@@ -26,6 +26,14 @@ inline int conv_slab_split(int nsp, int nblk, int max_slabs, int* kt_out) {
     if (kt_out) *kt_out = kt;
     return (nsp + kt - 1) / kt;
 }
+// Regions per run (kt) of a forward / input-gradient Winograd kernel whose workgroups each own one of ntn cout tiles and a run
+// of consecutive regions: as many runs as fill the GPU once (wg_per_cu workgroups per CU), the nsp regions spread evenly.
+inline int conv_region_runs(int nsp, int ntn, int wg_per_cu) {
+    int groups = conv_max_blocks() * wg_per_cu / ntn;
+    if (groups < 1) groups = 1;
+    const int even = (nsp + groups - 1) / groups;
+    return even < 1 ? 1 : even;
+}
 
 // Virtual conv input: channel-concat of src0 (C0 channels; up0=1 -> nearest x2 up-sampled from H/2 x W/2)
 // and src1 (C1 channels at full resolution; C1 == 0 -> absent).

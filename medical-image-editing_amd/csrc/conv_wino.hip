@@ -25,10 +25,13 @@
 //
 // Rounding: the products differ from the direct form's (sums of four inputs times sums of weights), the result agrees
 // with it to a few fp32 ulps of the accumulated magnitude - the same class of difference as a changed summation order.
+//
+// The item cursor, the hidden +1 / -1 constants and the transforms' vocabulary are shared with conv_wino64.hip and
+// conv_wino_up.hip (wino_common.h); the three-buffer ring and its per-item addresses are this kernel's own.
 #include "common.h"
 #include "conv_common.h"
 #include "mfma_util.h"
-#include <type_traits>
+#include "wino_common.h"
 
 int g_wino_mode = 0;     // 0 auto, 1 off
 
@@ -43,30 +46,20 @@ __global__ void k_wino_weights(const float* __restrict__ w, float* __restrict__ 
     const long n = (long)Cout * Cin;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
         const int co = (int)(e / Cin), ci = (int)(e % Cin);
-        double g[3][3], t[4][3];
+        double g[3][3], uu[4][4];
         for (int ky = 0; ky < 3; ++ky)
             for (int kx = 0; kx < 3; ++kx)
                 g[ky][kx] = transposed ? (double)w[(((long)ci * 3 + (2 - ky)) * 3 + (2 - kx)) * Cout + co]
                                        : (double)w[(((long)co * 3 + ky) * 3 + kx) * Cin + ci];
-        for (int kx = 0; kx < 3; ++kx) {
-            t[0][kx] = g[0][kx];
-            t[1][kx] = 0.5 * (g[0][kx] + g[1][kx] + g[2][kx]);
-            t[2][kx] = 0.5 * (g[0][kx] - g[1][kx] + g[2][kx]);
-            t[3][kx] = g[2][kx];
-        }
-        for (int i = 0; i < 4; ++i) {
-            const double r0 = t[i][0], r1 = 0.5 * (t[i][0] + t[i][1] + t[i][2]), r2 = 0.5 * (t[i][0] - t[i][1] + t[i][2]), r3 = t[i][2];
-            const double rr[4] = {r0, r1, r2, r3};
+        wino::weight_transform(g, uu);
+        for (int i = 0; i < 4; ++i)
             for (int j = 0; j < 4; ++j) {
                 const long xi = i * 4 + j;
                 const long at = chunked ? ((((long)(ci >> 3) * 16 + xi) * Cout + co) * 8 + (ci & 7)) : ((xi * Cout + co) * Cin + ci);
-                u[at] = (float)rr[j];
+                u[at] = (float)uu[i][j];
             }
-        }
     }
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct WinoArgs {
     const float* x;
@@ -118,14 +111,10 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
     const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
     const __amdgpu_buffer_rsrc_t rsx = make_rsrc(a.x, a.nbx), rsu = make_rsrc(a.u, a.nbu), rsy = make_rsrc(a.y, a.nby);
 
-    const int ntn = a.ntn, nch = a.nch;
-    const int lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_n = lb % ntn;
-    const int sp0 = (lb / ntn) * a.kt;
-    const int co_base = tile_n * 32;
-    const int my_tiles = min(a.kt, a.nsp - sp0);
-    const int nitems = my_tiles * nch;
-    const int per_img = a.tilesY * a.tilesX;
+    const int nch = a.nch;
+    const wino::RegionRun run = wino::region_run(a.ntn, a.kt, a.nsp);
+    const int co_base = run.tile_n * 32;
+    const int nitems = run.my_tiles * nch;
     if (nitems <= 0) return;           // uniform per workgroup
 
     // loader slots (fixed for the whole kernel): halo float4 f -> pixel f / 2, channel quad f % 2
@@ -181,31 +170,11 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
     };
     auto commit_u = [&](int j, int buf) { *(float4*)&Us[buf * UBUF + u_lds[j]] = ru[j]; };
 
-    // item cursors: (image, strip, region row, chunk) of items i, i+1, i+2
-    int cn, ctx, cty, ch = 0;
-    {
-        cn = sp0 / per_img;
-        const int rem = sp0 - cn * per_img;
-        ctx = rem / a.tilesY;
-        cty = rem - ctx * a.tilesY;
-    }
-    auto advance = [&](int& n, int& tx, int& ty, int& c) {     // the item after (n, tx, ty, c)
-        const int adv = c + 1 == nch ? 1 : 0;
-        c = adv ? 0 : c + 1;
-        const int ty1 = ty + adv, wy = ty1 == a.tilesY ? 1 : 0;
-        ty = wy ? 0 : ty1;
-        const int tx1 = tx + wy, wx = tx1 == a.tilesX ? 1 : 0;
-        tx = wx ? 0 : tx1;
-        n += wx;
-    };
-    int n1 = cn, tx1 = ctx, ty1 = cty, ch1 = 0;
-    advance(n1, tx1, ty1, ch1);
-    int n2 = n1, tx2 = tx1, ty2 = ty1, ch2 = ch1;
-    advance(n2, tx2, ty2, ch2);
+    wino::ItemCursor it(a, run.sp0);   // items i, i+1, i+2
 
     // prologue: halo of items 0 and 1 into halo buffers 0 and 1, U chunk of item 0 into U buffer 0.  (Items past the
     // workgroup's share read another region or nothing - out-of-range offsets return 0 - and are never consumed.)
-    issue_setup(cn, ctx, cty, 0);
+    issue_setup(it.cn, it.ctx, it.cty, 0);
 #pragma unroll
     for (int j = 0; j < LH; ++j) issue_h(j);
 #pragma unroll
@@ -214,7 +183,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
     for (int j = 0; j < LH; ++j) commit_h(j, 0);
 #pragma unroll
     for (int j = 0; j < LW; ++j) commit_u(j, 0);
-    issue_setup(n1, tx1, ty1, ch1);
+    issue_setup(it.n1, it.tx1, it.ty1, it.ch1);
 #pragma unroll
     for (int j = 0; j < LH; ++j) issue_h(j);
 #pragma unroll
@@ -258,17 +227,8 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
 
     // V = B^T d B of the lane's tile at its two channels.  The 64 add / sub of an item's transform are single VALU
     // instructions placed two per MFMA in the second half of the PREVIOUS item, column by column as the patch columns arrive
-    // from LDS, then row by row.  They are written as fma with +1 / -1 held in registers the compiler cannot see through:
-    // x + 1 * y and x - 1 * y round exactly like the add / sub they stand for, the vector combiner cannot pair them into
-    // v_pk_add_f32 over the two channels of a ds_read_b64 (which holds the vector issue port 2-3 times as long beside MFMAs),
-    // and - unlike the inline-asm v_add / v_sub this kernel used before - they are ordinary instructions to the compiler's
-    // hazard recogniser (a VALU write inside inline asm followed closely by the MFMA that reads it gave a stale operand in
-    // the weight-gradient kernel below).
-    float pone, mone;
-    { float c = 1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(pone) : "v"(c)); }
-    { float c = -1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(mone) : "v"(c)); }
-    auto fadd = [&](float x, float y) { return __builtin_fmaf(pone, y, x); };
-    auto fsub = [&](float x, float y) { return __builtin_fmaf(mone, y, x); };
+    // from LDS, then row by row, as fma with the hidden constants +1 / -1 (see opaque_f).
+    const float pone = opaque_f(1.f), mone = opaque_f(-1.f);
     f32x2 dcol[2][4];                  // two patch columns in flight
     float e[2][4][4];                  // [channel][row][column] after the column pass
     float v[2][2][16];                 // [parity of the item][channel of the pair][xi]
@@ -289,12 +249,12 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
     auto col_op = [&](int c, int k) {          // k = 0..7: channel k / 4, output row k % 4 of column c
         const int t = k >> 2, rr = k & 3;
         const float d0 = dcol[c & 1][0][t], d1 = dcol[c & 1][1][t], d2 = dcol[c & 1][2][t], d3 = dcol[c & 1][3][t];
-        e[t][rr][c] = rr == 0 ? fsub(d0, d2) : rr == 1 ? fadd(d1, d2) : rr == 2 ? fsub(d2, d1) : fsub(d1, d3);
+        e[t][rr][c] = wino::bt_row(rr, d0, d1, d2, d3, pone, mone);
     };
     auto row_op = [&](int par, int r, int k) { // k = 0..7: channel k / 4, output column k % 4 of row r
         const int t = k >> 2, cc = k & 3;
         const float e0 = e[t][r][0], e1 = e[t][r][1], e2 = e[t][r][2], e3 = e[t][r][3];
-        v[par][t][r * 4 + cc] = cc == 0 ? fsub(e0, e2) : cc == 1 ? fadd(e1, e2) : cc == 2 ? fsub(e2, e1) : fsub(e1, e3);
+        v[par][t][r * 4 + cc] = wino::bt_row(cc, e0, e1, e2, e3, pone, mone);
     };
     {   // item 0: nothing to hide behind yet
 #pragma unroll
@@ -317,7 +277,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
     auto body = [&](auto PAR, auto FIRST) {
         constexpr int par = decltype(PAR)::value;
         constexpr bool first = decltype(FIRST)::value;      // first chunk of a region: the accumulators start from 0
-        if (!first && ch == 0) {
+        if (!first && it.ch == 0) {
 #pragma unroll
             for (int xi = 0; xi < 16; ++xi)
 #pragma unroll
@@ -333,9 +293,9 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
         };
         auto slot = [&](int p) {       // p = 0..63: MFMA position (compile-time after unrolling)
             // loads (address arithmetic included) behind the first MFMAs: halo of item i+2, U chunk of item i+1
-            if (p == 0) issue_setup(n2, tx2, ty2, ch2);
+            if (p == 0) issue_setup(it.n2, it.tx2, it.ty2, it.ch2);
             if (p >= 1 && p < 1 + LH) issue_h(p - 1);
-            if (p == 1 + LH) i_cc4 = (unsigned)(ch1 * WN_KC) * 4u;
+            if (p == 1 + LH) i_cc4 = (unsigned)(it.ch1 * WN_KC) * 4u;
             if (p >= 2 + LH && p < 2 + LH + LW) issue_u(p - 2 - LH);
             if (p >= WN_CP && p < WN_CP + LH) commit_h(p - WN_CP, hC);
             if (p >= WN_CP + 4 && p < WN_CP + 4 + LW) commit_u(p - WN_CP - 4, ucur ^ 1);
@@ -369,12 +329,12 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
             slot(4 * xi + 3); __builtin_amdgcn_sched_barrier(0);
         }
 
-        if (ch == nch - 1) {
+        if (it.ch == nch - 1) {
             // Y = A^T M A per (tile, cout) entry: lane-local over the 16 xi; then bias / ReLU, statistics, stores
             // C/D rows of a lane = tiles 4 q + r: RW = 32: tile row wv, columns 4 q + r; RW = 16: tile row 2 wv + (q >> 1),
             // columns 4 (q & 1) + r
-            const int yrow0 = cty * WN_TR + (RW == 32 ? 2 * wv : 2 * (2 * wv + (q >> 1)));
-            const int xcol0 = ctx * RW + (RW == 32 ? 8 * q : 8 * (q & 1));
+            const int yrow0 = it.cty * WN_TR + (RW == 32 ? 2 * wv : 2 * (2 * wv + (q >> 1)));
+            const int xcol0 = it.ctx * RW + (RW == 32 ? 8 * q : 8 * (q & 1));
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 float yv[16];      // [r][a][b]
@@ -398,7 +358,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
                 for (int aa = 0; aa < 2; ++aa) {
                     const int yy = yrow0 + aa;
                     const bool ok = (co_off[nb] != 0xFFFFFFFFu) & (yy < H);
-                    const unsigned base = (((unsigned)cn * H + (unsigned)yy) * W + (unsigned)xcol0) * (unsigned)Cout + co_off[nb];
+                    const unsigned base = (((unsigned)it.cn * H + (unsigned)yy) * W + (unsigned)xcol0) * (unsigned)Cout + co_off[nb];
                     const int voff = (int)sel_u32(ok, base * 4u, a.nby);
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -418,18 +378,16 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino(WinoArgs a) {
                     }
                 }
             }
-            if (a.stats) fold_t = (cn * a.tilesX + ctx) * a.tilesY + cty;
+            if (a.stats) fold_t = (it.cn * a.tilesX + it.ctx) * a.tilesY + it.cty;
         }
-        cn = n1; ctx = tx1; cty = ty1; ch = ch1;
-        n1 = n2; tx1 = tx2; ty1 = ty2; ch1 = ch2;
-        advance(n2, tx2, ty2, ch2);
+        it.shift();
         __syncthreads();               // publishes the halo of item i+2 and the U chunk of item i+1
         const int t = hA; hA = hB; hB = hC; hC = t;
         ucur ^= 1;
         fold_stats();
     };
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
+    using wino::P0;
+    using wino::P1;
     for (int item = 0; item < nitems; item += 2) {      // every branch is uniform per workgroup
         body(P0{}, std::false_type{});
         if (item + 1 < nitems) body(P1{}, std::false_type{});
@@ -496,10 +454,7 @@ int conv_wino_fwd(const float* x, const float* u, const float* bias, float* y, i
     a.nbx = (unsigned)(P * Cin * 4);
     a.nbu = (unsigned)(16L * Cout * Cin * 4);
     a.nby = (unsigned)(P * Cout * 4);
-    int groups = conv_max_blocks() / a.ntn;
-    if (groups < 1) groups = 1;
-    const int even = ceil_div(a.nsp, groups);
-    a.kt = even < 1 ? 1 : even;
+    a.kt = conv_region_runs(a.nsp, a.ntn, 1);
     if (wide) k_conv_wino<32><<<ceil_div(a.nsp, a.kt) * a.ntn, 512, lds, st>>>(a);
     else k_conv_wino<16><<<ceil_div(a.nsp, a.kt) * a.ntn, 512, lds, st>>>(a);
     VQW_LAUNCH_CHECK("conv_wino");
@@ -561,7 +516,6 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad(WinoWgArgs a) {
     const int co_base = (blk / a.n_ci_b) * 32, ci_base = (blk % a.n_ci_b) * 16;
     const int sp0 = sblk * a.kt;
     const int my_tiles = min(a.kt, a.nsp - sp0);
-    const int per_img = a.tilesY * a.tilesX;
     // the 16-channel ci block of the workgroup lies in one of the two sources (C0 % 16 == 0 whenever there are two)
     const bool x_from0 = ci_base < a.C0;
     const unsigned xC = x_from0 ? (unsigned)a.C0 : (unsigned)a.C1;
@@ -617,12 +571,8 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad(WinoWgArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[xi][mb][r] = 0.f;
 
-    int cn = sp0 / per_img, ctx, cty;
-    {
-        const int rem = sp0 - cn * per_img;
-        ctx = rem / a.tilesY;
-        cty = rem - ctx * a.tilesY;
-    }
+    int cn, ctx, cty;
+    region_start(sp0, a.tilesY, a.tilesX, cn, ctx, cty);
     if (my_tiles > 0) {
         issue_setup(cn, ctx, cty);
 #pragma unroll
@@ -648,11 +598,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad(WinoWgArgs a) {
     float once = 0.f;
     for (int t = 0; t < my_tiles; ++t) {
         {   // next region (past the last one the loads read another region or nothing; their LDS copy is never consumed)
-            const int ty1 = cty + 1, wy = ty1 == a.tilesY ? 1 : 0;
-            cty = wy ? 0 : ty1;
-            const int tx1 = ctx + wy, wx = tx1 == a.tilesX ? 1 : 0;
-            ctx = wx ? 0 : tx1;
-            cn += wx;
+            region_next(a.tilesY, a.tilesX, cn, ctx, cty);
             issue_setup(cn, ctx, cty);
             once = t + 1 < my_tiles ? 1.f : 0.f;
         }

@@ -24,16 +24,17 @@
 //
 // Halo ring: two buffers suffice - the patch of item i+1 is read (and transformed) during item i, so the buffer of
 // item i is dead from the barrier that ends item i-1 and receives the halo of item i+2 during item i.
+//
+// The walk over a workgroup's run of regions, the halo stager and the transform vocabulary are shared with conv_wino.hip and
+// conv_wino_up.hip: wino_common.h, DESIGN section 6v (which also says what this kernel keeps a copy of, and why).
 #include "common.h"
 #include "conv_common.h"
 #include "mfma_util.h"
-#include <type_traits>
+#include "wino_common.h"
 
 extern int g_wino_mode;
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct W64Args {
     const float* x;
@@ -70,7 +71,7 @@ struct W64Args {
     int n_sh, n_m;
 };
 
-constexpr int W6_KPH = 10;                 // floats per halo pixel in LDS (8 channels + 2: conflict-free ds_read_b64 patches)
+constexpr int W6_KPH = wino::KPH;          // floats per halo pixel in LDS
 // Workgroup shapes.  MBW = M blocks (of 16 tiles) per wave, NBW = 4 / MBW N blocks (of 16 couts) per wave:
 //   MBW = 1: 64 tiles x 64 couts (Cout % 64 == 0): 32 transform VALU per 64 MFMAs;
 //   MBW = 2: 128 tiles x 32 couts (Cout % 32 == 0, widths that are multiples of 32): 64 per 64 MFMAs - what a 32-cout
@@ -111,11 +112,9 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
     using G = W64Geo<RW, MBW, NW>;
     constexpr int NT = 64 * NW, NMB = G::NMB, NBW = G::NBW, NCO = G::NCO;
     constexpr int HWS = G::HWS, HWV = G::HWV, HBUF = G::HBUF, UBUF = G::UBUF;
-    constexpr int HPIX = G::HR * HWV;          // 340 / 324 / 612 halo pixels
-    constexpr int HF = HPIX * 2;               // float4 per halo chunk: 680 / 648 / 1224
-    constexpr int LH = (HF + NT - 1) / NT;     // 2 / 2 / 3 halo slots per thread
+    using Halo = wino::HaloStager<NT, G::HR, HWV, HWS, wino::PitchedPix>;     // 340 / 324 / 612 halo pixels = 680 / 648 / 1224 float4
+    constexpr int LH = Halo::LH;               // 2 / 2 / 3 halo slots per thread
     constexpr int LU = 512 * NBW / NT;         // U slots per thread: 512 NBW float4 per chunk
-    static_assert(HF > (LH - 1) * NT && HF >= NT, "every halo slot but the last is full");
     // All slots in the first half of an item where they fit; otherwise the second half of the U slots forms a second phase
     // (issued from position W6_PB on, committed from W6_CB on) that re-uses the registers of the first.
     constexpr int CP = MBW == 1 ? W6_CP1 : W6_CP;
@@ -140,50 +139,18 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
     const __amdgpu_buffer_rsrc_t rsr = make_rsrc(EPI == 3 ? a.mr : a.y, EPI == 3 ? (unsigned)((size_t)a.N * a.Cout * 8) : a.nby);
     const __amdgpu_buffer_rsrc_t rsy2 = make_rsrc(EPI == 4 ? a.y2 : a.y, EPI == 4 ? a.nby2 : a.nby);
 
-    const int ntn = a.ntn, nch = a.nch;
-    const int lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_n = lb % ntn;
-    const int sp0 = (lb / ntn) * a.kt;
-    const int co_base = tile_n * NCO;
-    const int my_tiles = min(a.kt, a.nsp - sp0);
-    const int per_img = a.tilesY * a.tilesX;
+    const int nch = a.nch;
+    const wino::RegionRun run = wino::region_run(a.ntn, a.kt, a.nsp);
+    const int co_base = run.tile_n * NCO;
+    const int my_tiles = run.my_tiles;
     if (my_tiles <= 0) return;             // uniform per workgroup
 
-    // ---- loader slots (fixed per thread) ----
-    // halo float4 f -> halo pixel f / 2, channel quad f % 2; the last slot of the threads past the end repeats another
-    // thread's slot (same address, same data: a benign duplicate instead of a masked store)
+    // ---- loader slots (fixed per thread): the halo through the shared stager, pixels through the pitch fields ----
     const int c4 = tid & 1;
-    auto halo_pixel = [&](int j, int& hy, int& hx) {       // (recomputed where needed: a division by a constant, no register held)
-        int f = tid + j * NT;
-        if (f >= HF) f -= HF;
-        const int hp = f >> 1;
-        hy = hp / HWV;
-        hx = hp - hy * HWV;
-    };
-    int h_lds[LH];
-#pragma unroll
-    for (int j = 0; j < LH; ++j) {
-        int hy, hx;
-        halo_pixel(j, hy, hx);
-        h_lds[j] = (hy * HWS + hx) * W6_KPH + c4 * 4;
-    }
-    unsigned h_voff[LH];                   // byte offsets of the slots in the region whose halo is fetched next
-    auto basepix = [&](int n) {                // (scalar: n is uniform)
-        return (unsigned)(n >> a.n_sh) * a.img_px + (unsigned)((n >> 1) & a.n_m) * a.rowb_px + (unsigned)(n & a.n_m);
-    };
-    auto region_offsets = [&](int n, int tx, int ty) {
-        const int y0 = ty * G::TR - 1, x0 = tx * RW - 1;
-        const unsigned nb = basepix(n);
-#pragma unroll
-        for (int j = 0; j < LH; ++j) {
-            int hy, hx;
-            halo_pixel(j, hy, hx);
-            const int yy = y0 + hy, xx = x0 + hx;
-            const bool ok = ((unsigned)yy < (unsigned)H) & ((unsigned)xx < (unsigned)W);
-            const unsigned pix = nb + (unsigned)yy * a.rpx + (unsigned)xx * a.ppx;
-            h_voff[j] = sel_u32(ok, pix * (unsigned)Cin * 4u + (unsigned)c4 * 16u, 0xFFFFFFFFu);
-        }
-    };
+    const wino::PitchedPix pixel = {a.img_px, a.rowb_px, a.rpx, a.ppx, a.n_sh, a.n_m};
+    Halo hs;
+    hs.init(tid, pixel);
+    auto region_offsets = [&](int n, int tx, int ty) { hs.region_offsets(n, ty * G::TR - 1, tx * RW - 1, H, W, Cin); };
     // U float4 f = tid + NT j -> row = xi * NCO + n = (tid >> 1) + NT / 2 j, channel quad tid & 1
     // (a wave's slot = 32 couts x 32 bytes = 1 KB in a row of the chunked layout [Cin / 8][16 xi][Cout][8])
     const int u_n = (tid >> 1) & (NCO - 1);
@@ -192,48 +159,36 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
     const unsigned u_cstride = 16u * Cout * 32u;                           // per 8-channel chunk
     const int u_lds = (tid >> 1) * 8 + ((c4 ^ ((u_n >> 3) & 1)) * 4);      // + j * NT * 4 floats
 
-    float4 rh[LH], ru[LUA];
-    auto issue_h = [&](int j, int chunk) {
-        u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsx, (int)h_voff[j], chunk * 32, 0);
-        unsigned a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];
-        rh[j].x = __uint_as_float(a0); rh[j].y = __uint_as_float(a1); rh[j].z = __uint_as_float(a2); rh[j].w = __uint_as_float(a3);
-    };
+    float4 ru[LUA];
+    auto issue_h = [&](int j, int chunk) { hs.issue_h(rsx, j, chunk); };
+    auto commit_h = [&](int j, float* Hb) { hs.commit_h(j, Hb); };
     auto issue_u = [&](int j, int chunk) {
         u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsu, (int)u_voff, (int)(chunk * u_cstride + j * u_jstride), 0);
         unsigned a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];
         float4& r = ru[j % LUA];
         r.x = __uint_as_float(a0); r.y = __uint_as_float(a1); r.z = __uint_as_float(a2); r.w = __uint_as_float(a3);
     };
-    auto commit_h = [&](int j, float* Hb) {    // a halo pixel is 40 bytes: two 8-byte-aligned halves
-        float* p = Hb + h_lds[j];
-        f32x2 lo, hi;
-        lo.x = rh[j].x; lo.y = rh[j].y; hi.x = rh[j].z; hi.y = rh[j].w;
-        *(f32x2*)p = lo;
-        *(f32x2*)(p + 2) = hi;
-    };
     auto commit_u = [&](int j, float* Ub) { *(float4*)&Ub[u_lds + j * (NT * 4)] = ru[j % LUA]; };
 
-    // ---- item cursors: (image, strip, region row, chunk) of items i, i+1, i+2 ----
+    // ---- item cursors: (image, strip, region row, chunk) of items i, i+1, i+2.  This kernel keeps its own copy of
+    // wino::ItemCursor and of wino::region_loop (same code, see there): through the shared ones some of its fifteen
+    // instantiations took one or two more VGPRs (DESIGN section 6v has the table) ----
     int cn, ctx, cty, ch = 0;
-    {
-        cn = sp0 / per_img;
-        const int rem = sp0 - cn * per_img;
-        ctx = rem / a.tilesY;
-        cty = rem - ctx * a.tilesY;
-    }
+    region_start(run.sp0, a.tilesY, a.tilesX, cn, ctx, cty);
     auto advance = [&](int& n, int& tx, int& ty, int& c) {     // the item after (n, tx, ty, c)
         const int adv = c + 1 == nch ? 1 : 0;
         c = adv ? 0 : c + 1;
-        const int ty1 = ty + adv, wy = ty1 == a.tilesY ? 1 : 0;
-        ty = wy ? 0 : ty1;
-        const int tx1 = tx + wy, wx = tx1 == a.tilesX ? 1 : 0;
-        tx = wx ? 0 : tx1;
-        n += wx;
+        region_step(adv, a.tilesY, a.tilesX, n, tx, ty);
     };
     int n1 = cn, tx1 = ctx, ty1 = cty, ch1 = 0;
     advance(n1, tx1, ty1, ch1);
     int n2 = n1, tx2 = tx1, ty2 = ty1, ch2 = ch1;
     advance(n2, tx2, ty2, ch2);
+    auto shift = [&]() {               // item i+1 becomes the current item
+        cn = n1; ctx = tx1; cty = ty1; ch = ch1;
+        n1 = n2; tx1 = tx2; ty1 = ty2; ch1 = ch2;
+        advance(n2, tx2, ty2, ch2);
+    };
 
     // ---- fragment bases: lane (tile m = lane & 15, channel pair q = lane >> 4) ----
     const int m = lane & 15, q = lane >> 4;
@@ -253,12 +208,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
     const int b_swz = ((q >> 1) ^ (m >> 3)) * 4 + (q & 1) * 2;
     const int b_0 = opaque(((h ? 3 : 0) * 4 * NCO + m) * 8 + b_swz);       // + (cc * NCO + nb * 16) * 8
     const int b_1 = opaque(((h ? 2 : 1) * 4 * NCO + m) * 8 + b_swz);
-    // sg, mone live in VGPRs the compiler cannot see through: an SGPR operand costs 1.5 x, and a literal -1 would turn the
-    // fma back into a subtraction that the vector combiner pairs into v_pk_add_f32 over the two channels of a ds_read_b64
-    // (10-15 pipe cycles instead of 2 x 4.4)
-    float sg, mone;
-    { float s = h ? -1.f : 1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(sg) : "v"(s)); }
-    { float s = -1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(mone) : "v"(s)); }
+    const float sg = opaque_f(h ? -1.f : 1.f), mone = opaque_f(-1.f);      // hidden constants of the column pass (see opaque_f)
 
     f32x4 acc[8][MBW][NBW];
     f32x2 bf[2][NBW];                  // B fragments: xi l in bf[l & 1]; those of an item's last xi cross the barrier
@@ -283,7 +233,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
         } else {
             const int k = o - 16, lr = k >> 3, t = (k >> 2) & 1, cc = k & 3;
             const float e0 = e[t][lr][0], e1 = e[t][lr][1], e2 = e[t][lr][2], e3 = e[t][lr][3];
-            v[par][w][t][lr * 4 + cc] = cc == 0 ? e0 - e2 : cc == 1 ? e1 + e2 : cc == 2 ? e2 - e1 : e1 - e3;
+            v[par][w][t][lr * 4 + cc] = wino::bt_row_plain(cc, e0, e1, e2, e3);
         }
     };
     // what the transform does beside MFMA position p of an item (reads three positions ahead of a column's first operation);
@@ -467,7 +417,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
 #pragma unroll
                 for (int aa = 0; aa < 2; ++aa) {
                     const int yy = yrow0 + aa;
-                    const unsigned base = (basepix(cn) + (unsigned)yy * a.rpx + (unsigned)xcol0 * a.ppx) * cs + cc;
+                    const unsigned base = (pixel.base(cn) + (unsigned)yy * a.rpx + (unsigned)xcol0 * a.ppx) * cs + cc;
                     voffs[aa] = (int)sel_u32(yy < H, base * 4u, 0xFFFFFFFFu);
                 }
                 float mk[16];
@@ -580,16 +530,9 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
         spar ^= 1;
     };
 
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    auto shift = [&]() {               // item i+1 becomes the current item
-        cn = n1; ctx = tx1; cty = ty1; ch = ch1;
-        n1 = n2; tx1 = tx2; ty1 = ty2; ch1 = ch2;
-        advance(n2, tx2, ty2, ch2);
-    };
-    // nch is even: a region is nch / 2 (even, odd) item pairs; the first pair starts the accumulators from the MFMA's inline 0.
-    // (Explicit region / pair loops rather than one item loop with an `if (first)` diamond: with 128 accumulators live the
-    // diamond's PHIs cost register copies and spills.)  Every branch is uniform per workgroup.
+    using wino::P0;
+    using wino::P1;
+    // (wino::region_loop, written out: see the cursor above)
     for (int reg = 0; reg < my_tiles; ++reg) {
         body(P0{}, std::true_type{});
         __syncthreads();             // publishes the halo of item i+2 and the U chunk of item i+1
@@ -643,10 +586,7 @@ static int launch_wino64(W64Args& a, hipStream_t st) {
     if (int rc = lds_opt_in<k_conv_wino64<RW, MBW, EPI, NW>>((int)lds, "conv_wino64")) return rc;
     a.tilesY = ceil_div(a.H, G::TR); a.tilesX = a.W / RW; a.nsp = a.N * a.tilesY * a.tilesX;
     a.ntn = a.Cout / G::NCO;
-    int groups = conv_max_blocks() * (8 / NW) / a.ntn;
-    if (groups < 1) groups = 1;
-    const int even = ceil_div(a.nsp, groups);
-    a.kt = even < 1 ? 1 : even;
+    a.kt = conv_region_runs(a.nsp, a.ntn, 8 / NW);
     k_conv_wino64<RW, MBW, EPI, NW><<<ceil_div(a.nsp, a.kt) * a.ntn, 64 * NW, lds, st>>>(a);
     VQW_LAUNCH_CHECK("conv_wino64");
     return VQW_OK;
@@ -886,9 +826,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_wgrad_blk(W64WgArgs a) {
     // (MB = 4: the X buffers start 72 KB into the LDS, beyond the 64 KB immediate of a ds_read: their offset lives in the base register)
     const int x_A = opaque(2 * DBUF + ((2 * trow0 + iA) * XW + 2 * k) * WG_XP + idx);       // + s-part, + column * WG_XP, + nbk * 16
     const int x_B = opaque(2 * DBUF + ((2 * trow0 + iB) * XW + 2 * k) * WG_XP + idx);
-    float sA, sB;
-    { float s = (r == 1) ? 1.f : (r == 2) ? -1.f : 0.f; asm volatile("v_mov_b32 %0, %1" : "=v"(sA) : "v"(s)); }
-    { float s = (r == 1) ? 1.f : -1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(sB) : "v"(s)); }
+    const float sA = opaque_f((r == 1) ? 1.f : (r == 2) ? -1.f : 0.f), sB = opaque_f((r == 1) ? 1.f : -1.f);      // (see opaque_f)
     // pixel offset of k-step s inside the region's dY tile / X halo
     auto s_px_d = [](int s) { return RW == 32 ? 8 * s : 2 * (s >> 1) * 16 + 8 * (s & 1); };
     auto s_px_x = [](int s) { return RW == 32 ? 8 * s : 2 * (s >> 1) * XW + 8 * (s & 1); };

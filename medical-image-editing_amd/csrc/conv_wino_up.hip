@@ -13,14 +13,14 @@
 //   * weight gradient: dU[xi] = sum_tiles dM[xi]^T V[xi] is zero wherever V[xi] is.
 // Built like conv_wino64.hip (see there for the accounting): beside fp32 MFMAs every VALU instruction costs 4.4 matrix-pipe
 // cycles, LDS / SALU instructions nothing - per-region load offsets, scalar chunk offsets, immediates everywhere else.
+// The region-run cursor, the region loop and the halo stager of the input gradient are the shared ones of wino_common.h
+// (DESIGN section 6v).
 #include "common.h"
 #include "conv_common.h"
 #include "mfma_util.h"
-#include <type_traits>
+#include "wino_common.h"
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // the nine positions: (i, j) with i, j in {0, 1, 3}
 __device__ __host__ constexpr int up_row(int s) { return s == 2 ? 3 : s; }       // s = 0, 1, 2 -> Winograd index 0, 1, 3
@@ -41,20 +41,10 @@ __global__ void k_wino_up_weights(const float* __restrict__ w, float* __restrict
         for (int ky = 0; ky < 3; ++ky)
             for (int kx = 0; kx < 3; ++kx) g[ky][kx] = (double)w[(((long)co * 3 + ky) * 3 + kx) * Cin + ci];
         for (int flip = 0; flip < 2; ++flip) {
-            double t[4][3], u[4][4];
-            for (int kx = 0; kx < 3; ++kx) {
-                const double g0 = flip ? g[2][2 - kx] : g[0][kx], g1 = flip ? g[1][2 - kx] : g[1][kx], g2 = flip ? g[0][2 - kx] : g[2][kx];
-                t[0][kx] = g0;
-                t[1][kx] = 0.5 * (g0 + g1 + g2);
-                t[2][kx] = 0.5 * (g0 - g1 + g2);
-                t[3][kx] = g2;
-            }
-            for (int i = 0; i < 4; ++i) {
-                u[i][0] = t[i][0];
-                u[i][1] = 0.5 * (t[i][0] + t[i][1] + t[i][2]);
-                u[i][2] = 0.5 * (t[i][0] - t[i][1] + t[i][2]);
-                u[i][3] = t[i][2];
-            }
+            double gf[3][3], u[4][4];
+            for (int ky = 0; ky < 3; ++ky)
+                for (int kx = 0; kx < 3; ++kx) gf[ky][kx] = flip ? g[2 - ky][2 - kx] : g[ky][kx];
+            wino::weight_transform(gf, u);
             for (int si = 0; si < 3; ++si)
                 for (int sj = 0; sj < 3; ++sj) {
                     const int i = up_row(si), j = up_row(sj), xi = si * 3 + sj;
@@ -92,8 +82,8 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
     constexpr int RW = 32, TR = 16, HR = TR + 2, HWV = RW + 2, HWS = 34;
     constexpr int HBUF = HR * HWS * WU_KPH;            // 6120 floats
     constexpr int UBUF = 9 * NCO * 8;
-    constexpr int HF = HR * HWV * 2;                   // 1224 float4
-    constexpr int LH = (HF + NT - 1) / NT;             // 3
+    using Halo = wino::HaloStager<NT, HR, HWV, HWS, wino::DensePix>;      // 1224 float4
+    constexpr int LH = Halo::LH;                       // 3
     constexpr int UF = 9 * NCO * 2;                    // float4 per U chunk: 2304 / 1152
     constexpr int LU = (UF + NT - 1) / NT;             // 5 / 3
     constexpr int NPOS = 18 * NBW;                     // MFMAs per item and wave: 144 / 72
@@ -111,44 +101,17 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
     const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
     const __amdgpu_buffer_rsrc_t rsd = make_rsrc(a.dy, a.nbd), rsu = make_rsrc(a.u, a.nbu), rsg = make_rsrc(a.g, a.nbg);
 
-    const int ntn = a.ntn, nch = a.nch;
-    const int lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_n = lb % ntn;
-    const int sp0 = (lb / ntn) * a.kt;
-    const int co_base = tile_n * NCO;                  // first input channel (N dimension) of the workgroup
-    const int my_tiles = min(a.kt, a.nsp - sp0);
-    const int per_img = a.tilesY * a.tilesX;
+    const int nch = a.nch;
+    const wino::RegionRun run = wino::region_run(a.ntn, a.kt, a.nsp);
+    const int co_base = run.tile_n * NCO;              // first input channel (N dimension) of the workgroup
+    const int my_tiles = run.my_tiles;
     if (my_tiles <= 0) return;
 
-    // ---- loader slots ----
+    // ---- loader slots: the halo of dY through the shared stager (dense pixels) ----
     const int c4 = tid & 1;
-    auto halo_pixel = [&](int j, int& hy, int& hx) {
-        int f = tid + j * NT;
-        if (f >= HF) f -= HF;
-        const int hp = f >> 1;
-        hy = hp / HWV;
-        hx = hp - hy * HWV;
-    };
-    int h_lds[LH];
-#pragma unroll
-    for (int j = 0; j < LH; ++j) {
-        int hy, hx;
-        halo_pixel(j, hy, hx);
-        h_lds[j] = (hy * HWS + hx) * WU_KPH + c4 * 4;
-    }
-    unsigned h_voff[LH];
-    auto region_offsets = [&](int n, int tx, int ty) {
-        const int y0 = ty * TR - 1, x0 = tx * RW - 1;
-#pragma unroll
-        for (int j = 0; j < LH; ++j) {
-            int hy, hx;
-            halo_pixel(j, hy, hx);
-            const int yy = y0 + hy, xx = x0 + hx;
-            const bool ok = ((unsigned)yy < (unsigned)H) & ((unsigned)xx < (unsigned)W);
-            const unsigned pix = ((unsigned)n * H + (unsigned)yy) * W + (unsigned)xx;
-            h_voff[j] = sel_u32(ok, pix * (unsigned)Cout * 4u + (unsigned)c4 * 16u, 0xFFFFFFFFu);
-        }
-    };
+    Halo hs;
+    hs.init(tid, wino::DensePix{(unsigned)H, (unsigned)W});
+    auto region_offsets = [&](int n, int tx, int ty) { hs.region_offsets(n, ty * TR - 1, tx * RW - 1, H, W, Cout); };
     // U float4 f -> row f / 2 = xi * NCO + n, channel quad f % 2; the last slot wraps (duplicates)
     unsigned u_voff[LU];
     int u_lds[LU];
@@ -162,40 +125,14 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
     }
     const unsigned u_cstride = 9u * Cin * 32u;         // per 8-channel chunk
 
-    float4 rh[LH], ru[LU];
-    auto issue_h = [&](int j, int chunk) { rh[j] = buf_ld4(rsd, h_voff[j], chunk * 32); };
+    float4 ru[LU];
+    auto issue_h = [&](int j, int chunk) { hs.issue_h(rsd, j, chunk); };
     // (readfirstlane: left alone the compiler multiplies in a VGPR and wraps the load in a waterfall loop)
     auto issue_u = [&](int j, int chunk) { ru[j] = buf_ld4(rsu, u_voff[j], __builtin_amdgcn_readfirstlane(chunk * u_cstride)); };
-    auto commit_h = [&](int j, int buf) {
-        float* p = smem + buf * HBUF + h_lds[j];
-        f32x2 lo, hi;
-        lo.x = rh[j].x; lo.y = rh[j].y; hi.x = rh[j].z; hi.y = rh[j].w;
-        *(f32x2*)p = lo;
-        *(f32x2*)(p + 2) = hi;
-    };
+    auto commit_h = [&](int j, int buf) { hs.commit_h(j, smem + buf * HBUF); };
     auto commit_u = [&](int j, int buf) { *(float4*)&smem[u_lds[j] + buf * UBUF] = ru[j]; };
 
-    // ---- item cursors ----
-    int cn, ctx, cty, ch = 0;
-    {
-        cn = sp0 / per_img;
-        const int rem = sp0 - cn * per_img;
-        ctx = rem / a.tilesY;
-        cty = rem - ctx * a.tilesY;
-    }
-    auto advance = [&](int& n, int& tx, int& ty, int& c) {
-        const int adv = c + 1 == nch ? 1 : 0;
-        c = adv ? 0 : c + 1;
-        const int ty1 = ty + adv, wy = ty1 == a.tilesY ? 1 : 0;
-        ty = wy ? 0 : ty1;
-        const int tx1 = tx + wy, wx = tx1 == a.tilesX ? 1 : 0;
-        tx = wx ? 0 : tx1;
-        n += wx;
-    };
-    int n1 = cn, tx1 = ctx, ty1 = cty, ch1 = 0;
-    advance(n1, tx1, ty1, ch1);
-    int n2 = n1, tx2 = tx1, ty2 = ty1, ch2 = ch1;
-    advance(n2, tx2, ty2, ch2);
+    wino::ItemCursor it(a, run.sp0);   // items i, i+1, i+2
 
     // ---- fragments: lane (tile m = lane & 15, channel pair q = lane >> 4); wave = tile row ----
     const int m = lane & 15, q = lane >> 4;
@@ -206,9 +143,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
     // (indices in units of f32x2: a float index that went through `opaque` carries no alignment and the 8-byte fragment read
     // would be split into ds_read2_b32 with a VALU add each)
     const int b_u0 = opaque((2 * HBUF + m * 8 + b_swz) / 2), b_u1 = opaque((2 * HBUF + UBUF + m * 8 + b_swz) / 2);      // + (xi * NCO + nb * 16) * 4
-    float mone, pone;                  // -1 / +1 the compiler cannot see through: x + pone * y rounds like x + y and is never paired into v_pk_add_f32
-    { float s = -1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(mone) : "v"(s)); }
-    { float s = 1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(pone) : "v"(s)); }
+    const float mone = opaque_f(-1.f), pone = opaque_f(1.f);      // hidden constants of the transform (see opaque_f)
 
     f32x4 acc[NBW];
     f32x2 bf[2][NBW];
@@ -226,11 +161,11 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
         if (o < 24) {
             const int c = o / 6, t = (o % 6) / 3, s = o % 3;
             const float d0 = dcol[c & 1][0][t], d1 = dcol[c & 1][1][t], d2 = dcol[c & 1][2][t], d3 = dcol[c & 1][3][t];
-            e[t][s][c] = s == 0 ? __builtin_fmaf(mone, d2, d0) : s == 1 ? __builtin_fmaf(pone, d2, d1) : __builtin_fmaf(mone, d3, d1);
+            e[t][s][c] = wino::bt_row(up_row(s), d0, d1, d2, d3, pone, mone);
         } else {
             const int k = o - 24, t = k / 9, s = (k % 9) / 3, sj = k % 3;
             const float e0 = e[t][s][0], e1 = e[t][s][1], e2 = e[t][s][2], e3 = e[t][s][3];
-            v[par][t][s * 3 + sj] = sj == 0 ? __builtin_fmaf(mone, e2, e0) : sj == 1 ? __builtin_fmaf(pone, e2, e1) : __builtin_fmaf(mone, e3, e1);
+            v[par][t][s * 3 + sj] = wino::bt_row(up_row(sj), e0, e1, e2, e3, pone, mone);
         }
     };
     auto op_pos = [](int o) { return T0 + (o * OPSTEP2) / 2; };
@@ -243,7 +178,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
     };
 
     // ---- prologue ----
-    region_offsets(cn, ctx, cty);
+    region_offsets(it.cn, it.ctx, it.cty);
 #pragma unroll
     for (int j = 0; j < LH; ++j) issue_h(j, 0);
 #pragma unroll
@@ -252,9 +187,9 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
     for (int j = 0; j < LH; ++j) commit_h(j, 0);
 #pragma unroll
     for (int j = 0; j < LU; ++j) commit_u(j, 0);
-    region_offsets(n1, tx1, ty1);
+    region_offsets(it.n1, it.tx1, it.ty1);
 #pragma unroll
-    for (int j = 0; j < LH; ++j) issue_h(j, ch1);
+    for (int j = 0; j < LH; ++j) issue_h(j, it.ch1);
 #pragma unroll
     for (int j = 0; j < LH; ++j) commit_h(j, 1);
     __syncthreads();
@@ -264,7 +199,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
         xform_op(0, o);
     }
     __syncthreads();
-    region_offsets(n2, tx2, ty2);
+    region_offsets(it.n2, it.tx2, it.ty2);
 
     // One item of parity PAR: operands v[PAR], U chunk in U buffer PAR, the next item's halo in halo buffer PAR ^ 1; the halo
     // of item i+2 goes to halo buffer PAR, the U chunk of item i+1 to U buffer PAR ^ 1.
@@ -275,8 +210,8 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
             bf[xi & 1][nb] = ((const f32x2*)smem)[(par ? b_u1 : b_u0) + (xi * NCO + nb * 16) * 4];
         };
         auto slot = [&](int p) {
-            if (p >= 1 && p < 1 + 2 * LH && (p & 1)) issue_h((p - 1) >> 1, ch2);
-            if (p >= 1 + 2 * LH && p < 1 + 2 * (LH + LU) && (p & 1)) issue_u((p - 1 - 2 * LH) >> 1, ch1);
+            if (p >= 1 && p < 1 + 2 * LH && (p & 1)) issue_h((p - 1) >> 1, it.ch2);
+            if (p >= 1 + 2 * LH && p < 1 + 2 * (LH + LU) && (p & 1)) issue_u((p - 1 - 2 * LH) >> 1, it.ch1);
             if (p >= CP && p < CP + LH) commit_h(p - CP, par);
             if (p >= CP + LH && p < CP + LH + LU) commit_u(p - CP - LH, par ^ 1);
             xform_slot(par ^ 1, par ^ 1, p);
@@ -299,8 +234,8 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
     };
     // C/D layout (16x16): col = lane & 15 (channel of the N block), row = 4 (lane >> 4) + r (tile = low-resolution column)
     auto epilogue = [&]() {
-        const int ylow = cty * (TR / 2) + wv, xlow0 = ctx * (RW / 2) + 4 * q;
-        const unsigned base = (((unsigned)cn * (H >> 1) + (unsigned)ylow) * (W >> 1) + (unsigned)xlow0) * (unsigned)Cin + co_base + m;
+        const int ylow = it.cty * (TR / 2) + wv, xlow0 = it.ctx * (RW / 2) + 4 * q;
+        const unsigned base = (((unsigned)it.cn * (H >> 1) + (unsigned)ylow) * (W >> 1) + (unsigned)xlow0) * (unsigned)Cin + co_base + m;
         const int voff = (int)sel_u32(ylow < (H >> 1), base * 4u, 0xFFFFFFFFu);
         if (ACC) {
             float old[NBW][4];
@@ -320,32 +255,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_dgrad(WUpDgArgs a) {
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[nb][r]), rsg, voff, r * Cin * 4 + nb * 64, 0);
     };
 
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    auto shift = [&]() {
-        cn = n1; ctx = tx1; cty = ty1; ch = ch1;
-        n1 = n2; tx1 = tx2; ty1 = ty2; ch1 = ch2;
-        advance(n2, tx2, ty2, ch2);
-    };
-    for (int reg = 0; reg < my_tiles; ++reg) {     // nch is even: a region is nch / 2 (even, odd) item pairs
-        body(P0{}, std::true_type{});
-        __syncthreads();
-        shift();
-        body(P1{}, std::false_type{});
-        __syncthreads();
-        for (int c = 2; c < nch; c += 2) {
-            shift();
-            if (ch2 == 0) region_offsets(n2, tx2, ty2);
-            body(P0{}, std::false_type{});
-            __syncthreads();
-            shift();
-            body(P1{}, std::false_type{});
-            __syncthreads();
-        }
-        epilogue();
-        shift();
-        if (ch2 == 0) region_offsets(n2, tx2, ty2);
-    }
+    wino::region_loop(my_tiles, nch, it, body, region_offsets, epilogue);
 }
 
 
@@ -397,16 +307,13 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
     const __amdgpu_buffer_rsrc_t rsy2 = make_rsrc(split ? a.y2 : a.y, a.nby);
     const int Cst = split ? 32 : a.Cout;                   // channels per output pixel as stored
 
-    const int ntn = a.ntn, nch = a.nch;
-    const int lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_n = lb % ntn;
-    const int sp0 = (lb / ntn) * a.kt;
-    const int co_base = tile_n * NCO;
-    const int my_tiles = min(a.kt, a.nsp - sp0);
-    const int per_img = a.tilesY * a.tilesX;
+    const int nch = a.nch;
+    const wino::RegionRun run = wino::region_run(a.ntn, a.kt, a.nsp);
+    const int co_base = run.tile_n * NCO;
+    const int my_tiles = run.my_tiles;
     if (my_tiles <= 0) return;
 
-    // ---- loader slots: one halo slot (threads past the 360 float4 repeat another thread's), three U slots ----
+    // ---- loader slots (this kernel's own: a float4 pixel, a single slot): one halo slot (threads past the 360 float4 repeat another thread's), three U slots ----
     const int c4 = tid & 1;
     const int hf = tid < HF ? tid : tid - HF;
     const int h_hy = (hf >> 1) / LWV, h_hx = (hf >> 1) - h_hy * LWV;
@@ -436,27 +343,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
     auto commit_h = [&](int buf) { *(float4*)&smem[buf * HBUF + h_lds] = rh; };
     auto commit_u = [&](int j, int buf) { *(float4*)&smem[u_lds[j] + buf * UBUF] = ru[j]; };
 
-    // ---- item cursors ----
-    int cn, ctx, cty, ch = 0;
-    {
-        cn = sp0 / per_img;
-        const int rem = sp0 - cn * per_img;
-        ctx = rem / a.tilesY;
-        cty = rem - ctx * a.tilesY;
-    }
-    auto advance = [&](int& n, int& tx, int& ty, int& c) {
-        const int adv = c + 1 == nch ? 1 : 0;
-        c = adv ? 0 : c + 1;
-        const int ty1 = ty + adv, wy = ty1 == a.tilesY ? 1 : 0;
-        ty = wy ? 0 : ty1;
-        const int tx1 = tx + wy, wx = tx1 == a.tilesX ? 1 : 0;
-        tx = wx ? 0 : tx1;
-        n += wx;
-    };
-    int n1 = cn, tx1 = ctx, ty1 = cty, ch1 = 0;
-    advance(n1, tx1, ty1, ch1);
-    int n2 = n1, tx2 = tx1, ty2 = ty1, ch2 = ch1;
-    advance(n2, tx2, ty2, ch2);
+    wino::ItemCursor it(a, run.sp0);   // items i, i+1, i+2
 
     // ---- fragments: lane (tile m = lane & 15 = low-resolution column, channel pair q = lane >> 4); wave = tile row ----
     const int m = lane & 15, q = lane >> 4;
@@ -465,9 +352,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
     for (int r = 0; r < 3; ++r) a_row[r] = opaque((((wv + r) * LWS + m) * WF_KPH + 2 * q) / 2);
     const int b_swz = ((q >> 1) ^ (m >> 3)) * 4 + (q & 1) * 2;
     const int b_u0 = opaque((2 * HBUF + m * 8 + b_swz) / 2), b_u1 = opaque((2 * HBUF + UBUF + m * 8 + b_swz) / 2);
-    float mone, pone;                  // -1 / +1 the compiler cannot see through: x + pone * y rounds like x + y and is never paired into v_pk_add_f32
-    { float s = -1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(mone) : "v"(s)); }
-    { float s = 1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(pone) : "v"(s)); }
+    const float mone = opaque_f(-1.f);      // hidden constant of the transform (see opaque_f)
 
     f32x4 acc[9][NBW];
     f32x2 bf[2][NBW];
@@ -504,15 +389,15 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
     };
 
     // ---- prologue ----
-    region_offsets(cn, ctx, cty);
+    region_offsets(it.cn, it.ctx, it.cty);
     issue_h(0);
 #pragma unroll
     for (int j = 0; j < LU; ++j) issue_u(j, 0);
     commit_h(0);
 #pragma unroll
     for (int j = 0; j < LU; ++j) commit_u(j, 0);
-    region_offsets(n1, tx1, ty1);
-    issue_h(ch1);
+    region_offsets(it.n1, it.tx1, it.ty1);
+    issue_h(it.ch1);
     commit_h(1);
     __syncthreads();
 #pragma unroll
@@ -521,7 +406,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
         xform_op(0, o);
     }
     __syncthreads();
-    region_offsets(n2, tx2, ty2);
+    region_offsets(it.n2, it.tx2, it.ty2);
 
     float bvv[NBW];
 #pragma unroll
@@ -536,8 +421,8 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
             bf[xi & 1][nb] = ((const f32x2*)smem)[(par ? b_u1 : b_u0) + (xi * NCO + nb * 16) * 4];
         };
         auto slot = [&](int p) {
-            if (p == 1) issue_h(ch2);
-            if (p >= 3 && p < 3 + 2 * LU && (p & 1)) issue_u((p - 3) >> 1, ch1);
+            if (p == 1) issue_h(it.ch2);
+            if (p >= 3 && p < 3 + 2 * LU && (p & 1)) issue_u((p - 3) >> 1, it.ch1);
             if (p == CP) commit_h(par);
             if (p > CP && p <= CP + LU) commit_u(p - CP - 1, par ^ 1);
             xform_slot(par ^ 1, par ^ 1, p);
@@ -560,7 +445,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
     // Y = A^T M A over the nine M of a (tile, cout) entry: T0[j] = M0j + M1j, T1[j] = M1j - M3j; Y[a][0] = Ta[0] + Ta[1],
     // Y[a][1] = Ta[1] - Ta[3].  C/D layout (16x16): col = lane & 15 (cout), row = 4 (lane >> 4) + r (tile column).
     auto epilogue = [&]() {
-        const int yrow0 = cty * 16 + 2 * wv, xcol0 = ctx * 32 + 8 * q;
+        const int yrow0 = it.cty * 16 + 2 * wv, xcol0 = it.ctx * 32 + 8 * q;
         const int H = 2 * h, W = 2 * w;
 #pragma unroll
         for (int nb = 0; nb < NBW; ++nb) {
@@ -584,7 +469,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
 #pragma unroll
             for (int aa = 0; aa < 2; ++aa) {
                 const int yy = yrow0 + aa;
-                const unsigned base = (((unsigned)cn * H + (unsigned)yy) * W + (unsigned)xcol0) * (unsigned)Cst + co;
+                const unsigned base = (((unsigned)it.cn * H + (unsigned)yy) * W + (unsigned)xcol0) * (unsigned)Cst + co;
                 const int voff = (int)sel_u32(yy < H, base * 4u, 0xFFFFFFFFu);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -611,7 +496,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
                 float s1 = R[0], s2 = R[1];              // the eight tile rows of 64 pixels, merged in order
 #pragma unroll
                 for (int r = 1; r < 8; ++r) stat_merge(s1, s2, 64.f * r, R[r * NCO * 2], R[r * NCO * 2 + 1], 64.f);
-                const int t = (cn * a.tilesX + ctx) * a.tilesY + cty;
+                const int t = (it.cn * a.tilesX + it.ctx) * a.tilesY + it.cty;
                 float* o = split ? (tid < 32 ? a.stats : a.stats2) + ((size_t)t * 32 + (tid & 31)) * 2
                                  : a.stats + ((size_t)t * Cout + co_base + tid) * 2;
                 o[0] = s1;
@@ -621,32 +506,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_fwd(WUpFwArgs a) {
         }
     };
 
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    auto shift = [&]() {
-        cn = n1; ctx = tx1; cty = ty1; ch = ch1;
-        n1 = n2; tx1 = tx2; ty1 = ty2; ch1 = ch2;
-        advance(n2, tx2, ty2, ch2);
-    };
-    for (int reg = 0; reg < my_tiles; ++reg) {     // nch is even
-        body(P0{}, std::true_type{});
-        __syncthreads();
-        shift();
-        body(P1{}, std::false_type{});
-        __syncthreads();
-        for (int c = 2; c < nch; c += 2) {
-            shift();
-            if (ch2 == 0) region_offsets(n2, tx2, ty2);
-            body(P0{}, std::false_type{});
-            __syncthreads();
-            shift();
-            body(P1{}, std::false_type{});
-            __syncthreads();
-        }
-        epilogue();
-        shift();
-        if (ch2 == 0) region_offsets(n2, tx2, ty2);
-    }
+    wino::region_loop(my_tiles, nch, it, body, region_offsets, epilogue);
 }
 
 
@@ -751,9 +611,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wino_up_wgrad(WUpWgArgs a) {
     int x_r[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) x_r[r] = opaque(2 * DBUF + ((trow + r) * XW + 8 * thalf + k) * WW_XP + idx);      // + s * 4 px, + column px, + nbk * 16
-    float mone, pone;                  // -1 / +1 the compiler cannot see through: x + pone * y rounds like x + y and is never paired into v_pk_add_f32
-    { float s = -1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(mone) : "v"(s)); }
-    { float s = 1.f; asm volatile("v_mov_b32 %0, %1" : "=v"(pone) : "v"(s)); }
+    const float mone = opaque_f(-1.f);      // hidden constant of the transform (see opaque_f)
 
     f32x4 acc[9][2][2];                // [xi][co block][ci block]
 #pragma unroll
@@ -963,10 +821,7 @@ static int launch_up_dgrad(WUpDgArgs& a, hipStream_t st) {
     static_assert(lds <= 160 * 1024, "buffers do not fit the 160 KB LDS");
     if (int rc = lds_opt_in<k_conv_wino_up_dgrad<NBW, ACC>>(160 * 1024, "conv_wino_up_dgrad")) return rc;
     a.ntn = a.Cin / (16 * NBW);
-    int groups = conv_max_blocks() / a.ntn;
-    if (groups < 1) groups = 1;
-    const int even = ceil_div(a.nsp, groups);
-    a.kt = even < 1 ? 1 : even;
+    a.kt = conv_region_runs(a.nsp, a.ntn, 1);
     k_conv_wino_up_dgrad<NBW, ACC><<<ceil_div(a.nsp, a.kt) * a.ntn, 512, lds, st>>>(a);
     VQW_LAUNCH_CHECK("conv_wino_up_dgrad");
     return VQW_OK;
@@ -1011,10 +866,7 @@ int conv_wino_up_fwd(const float* x_low, const float* ws, const float* bias, flo
     a.nbx = (unsigned)(Pl * Cin * 4);
     a.nbu = (unsigned)(9L * Cout * Cin * 4);
     a.nby = (unsigned)(4 * Pl * (y2 ? 32 : Cout) * 4);
-    int groups = conv_max_blocks() / a.ntn;
-    if (groups < 1) groups = 1;
-    const int even = ceil_div(a.nsp, groups);
-    a.kt = even < 1 ? 1 : even;
+    a.kt = conv_region_runs(a.nsp, a.ntn, 1);
     k_conv_wino_up_fwd<<<ceil_div(a.nsp, a.kt) * a.ntn, 512, lds, st>>>(a);
     VQW_LAUNCH_CHECK("conv_wino_up_fwd");
     return VQW_OK;

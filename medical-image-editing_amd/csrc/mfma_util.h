@@ -4,6 +4,7 @@
 
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // Bijective XCD-aware remap: workgroups are dealt round-robin over the 8 XCDs, so give each XCD a contiguous run
@@ -39,6 +40,14 @@ __device__ __forceinline__ void buf_st4(__amdgpu_buffer_rsrc_t r, unsigned byte_
 // A value the compiler cannot see through: LDS base addresses kept in registers of their own (no ds_read2 merging, no
 // re-derivation from a common base inside an MFMA loop).
 __device__ __forceinline__ int opaque(int x) { asm volatile("" : "+v"(x)); return x; }
+// Its float twin: a constant (+1, -1, a wave's sign) held in a VGPR the compiler cannot see through.  The Winograd transforms
+// write their add / sub as fma with such a constant: x + 1 * y and x - 1 * y round exactly like the add / sub they stand
+// for, but the vector combiner cannot pair them into v_pk_add_f32 over the two channels of a ds_read_b64 (which holds the
+// vector issue port 2-3 times as long beside MFMAs: 10-15 matrix-pipe cycles instead of 2 x 4.4), an SGPR operand would cost
+// 1.5 x, and - unlike v_add / v_sub written in inline asm - the fma is an ordinary instruction to the compiler's hazard
+// recogniser (a VALU write inside inline asm followed closely by the MFMA that reads it gave a stale operand in the
+// weight-gradient kernel of conv_wino.hip).  The v_mov is the whole asm: nothing that feeds an MFMA is computed in it.
+__device__ __forceinline__ float opaque_f(float x) { float r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(x)); return r; }
 
 // Walk over the regions of a tensor in the order (image, region column, region row): the cursor of region number sp, and its
 // successor.  tilesY / tilesX = regions per image column / row.
@@ -49,13 +58,15 @@ __device__ __forceinline__ void region_start(int sp, int tilesY, int tilesX, int
     tx = rem / tilesY;
     ty = rem - tx * tilesY;
 }
-__device__ __forceinline__ void region_next(int tilesY, int tilesX, int& n, int& tx, int& ty) {
-    const int ty1 = ty + 1, wy = ty1 == tilesY ? 1 : 0;
+// (step = 0 / 1: stay / move on - selects, no branch: see sel_u32)
+__device__ __forceinline__ void region_step(int step, int tilesY, int tilesX, int& n, int& tx, int& ty) {
+    const int ty1 = ty + step, wy = ty1 == tilesY ? 1 : 0;
     ty = wy ? 0 : ty1;
     const int tx1 = tx + wy, wx = tx1 == tilesX ? 1 : 0;
     tx = wx ? 0 : tx1;
     n += wx;
 }
+__device__ __forceinline__ void region_next(int tilesY, int tilesX, int& n, int& tx, int& ty) { region_step(1, tilesY, tilesX, n, tx, ty); }
 
 // A select between two values that are both evaluated.  Written as `c ? f(x) : k` the address arithmetic of f lands in
 // an exec-masked block of its own; basic-block boundaries inside an MFMA loop keep the scheduler from spreading the

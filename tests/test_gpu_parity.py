@@ -164,6 +164,16 @@ CONV_CASES = [
     (3, 208, 212, 32, 0, False, 64, 1, 1, False, False),
     (8, 128, 128, 64, 0, False, 64, 1, 1, False, False),
     (4, 192, 192, 16, 0, False, 128, 1, 1, False, False),
+    # The item cursor's wraps INSIDE one workgroup's run of regions (region-row wrap, column-strip wrap, step to the next image):
+    # with the default 256 workgroups (VQW_CONV_MAX_BLOCKS unset) the launchers give kt = ceil(nsp / (256 [x 2] / ntn)) = 2
+    # regions per run; tilesY = 3 is odd, so runs straddle the region-row wrap, and tilesY x tilesX is odd, so one straddles the
+    # image step.  Forward rows run under the winograd_forward fixture.
+    (5, 20, 288, 16, 0, False, 128, 3, 1, True, False),    # k_conv_wino64<32,1>: 8-row regions, 3 x 9 per image, nsp 135, ntn 2 -> groups 128, kt 2
+    (5, 20, 416, 16, 0, False, 96, 3, 1, True, False),     # k_conv_wino64<32,2,.,4>: 3 x 13, nsp 195, ntn 3, two workgroups per CU -> groups 170, kt 2
+    (8, 40, 48, 16, 0, False, 256, 3, 1, True, False),     # k_conv_wino64<16,1>: 16 x 16 regions, 3 x 3, nsp 72, ntn 4 -> groups 64, kt 2
+    (4, 40, 160, 24, 0, False, 160, 3, 1, True, False),    # k_conv_wino (Cin % 16 != 0): 16 x 32 regions, 3 x 5, nsp 60, ntn 5 -> groups 51, kt 2
+    (6, 40, 160, 16, 0, True, 192, 3, 1, True, False),     # k_conv_wino_up_fwd: 3 x 5 (low-res 8 x 16), nsp 90, ntn 3 -> groups 85, kt 2
+    (6, 40, 160, 192, 0, True, 16, 3, 1, True, False),     # k_conv_wino_up_dgrad<4>: 3 x 5, nsp 90, ntn 192 / 64 = 3 -> groups 85, kt 2
 ]
 
 
