@@ -836,6 +836,34 @@ int vqw_adam_step(float* p, const float* g, float* m, float* v, long n, float lr
 int vqw_adam_multi(const void* chunks_dev, int n_chunks, float lr, float beta1, float beta2, float eps,
                    float weight_decay, float bias_corr1, float bias_corr2, void* stream);
 
+/* ---- training the GPT code prior (trainers/prior.py; minGPT's and taming-transformers' recipe).  Added functions only; the ABI
+ * stays 9.  fp32 in, fp32 out, no float atomics: every sum has a fixed order, the same bits every run.  No host synchronisation.
+ * Global gradient norm: the L2 norm over the g tensors of vqw_adam_multi's chunk table (p, m, v are not touched).  Stage one, a
+ * workgroup per record, leaves the sum of g g of its chunk, in double, in ws (vqw_grad_norm_ws_bytes(n_chunks) bytes, 8-byte
+ * aligned; 0 for n_chunks < 1); stage two, one workgroup, folds the partials in index order in double and writes norm_out[0] =
+ * (float)sqrt(sum) and norm_out[1] = the clip coefficient min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s
+ * formula in fp32; max_norm <= 0: the coefficient is 1.  A NaN norm gives a NaN coefficient and an infinite norm the coefficient
+ * 0 (then 0 inf = NaN in the update), both as torch's clamp leaves them: a non-finite gradient poisons the step, nothing hides it. */
+size_t vqw_grad_norm_ws_bytes(int n_chunks);
+int vqw_grad_norm_multi(const void* chunks_dev, int n_chunks, float max_norm, void* ws, size_t ws_bytes, float* norm_out, void* stream);
+/* torch.optim.AdamW (decoupled decay): p *= 1 - lr wd; m = b1 m + (1 - b1) g'; v = b2 v + (1 - b2) g'^2; p -= (lr / bias_corr1)
+ * m / (sqrt(v) / sqrt(bias_corr2) + eps), with g' = clip[0] g.  clip: a device scalar - norm_out + 1 of vqw_grad_norm_multi - or
+ * null, which means 1.  The gradient tensors are NOT rewritten: after a clipped step p.grad still holds the unclipped values,
+ * unlike torch's in-place clip_grad_norm_.  Argument order, chunk table and walk as vqw_adam_multi / vqw_adam_step; the scalars
+ * are doubles: 1 - lr wd, 1 - beta, lr / bias_corr1 and sqrt(bias_corr2) are formed in double and rounded once, as torch forms
+ * them before its fp32 tensor operations (an fp32 beta2 = 0.95 would leave 1 - beta2 2.4e-7 off in every element). */
+int vqw_adamw_multi(const void* chunks_dev, int n_chunks, double lr, double beta1, double beta2, double eps, double weight_decay,
+                    double bias_corr1, double bias_corr2, const float* clip, void* stream);
+int vqw_adamw_step(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2, double eps,
+                   double weight_decay, double bias_corr1, double bias_corr2, const float* clip, void* stream);
+/* The transformer's input from a batch of code sequences ids [B][T] (torch.long): inp[b][0] = sos, inp[b][t] = corrupted[b][t - 1]
+ * with corrupted[b][t] = ids[b][t] if u_keep[b][t] < pkeep, else min(V - 1, (long)floorf(u_rand[b][t] V)) - taming-transformers'
+ * pkeep corruption behind a start token; the target stays ids.  u_keep, u_rand [B][T] are uniforms in [0, 1) from the caller: the
+ * kernel has no random numbers of its own (vqw_sample_topk's rule).  pkeep >= 1 reads neither, both may be null.  An ids entry
+ * outside [0, V) is passed through unchanged (vqw_embed_fwd defines what follows).  B, T, V >= 1. */
+int vqw_prior_tokens(const long* ids, const float* u_keep, const float* u_rand, long* inp, int B, int T, int V, long sos, float pkeep,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

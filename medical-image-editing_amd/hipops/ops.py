@@ -1812,6 +1812,30 @@ def sample_topk(logits, u, temperature=1.0, top_k=0):
     return out
 
 
+def prior_tokens(ids, sos, pkeep, vocab_size, u_keep=None, u_rand=None):
+    """The transformer's input of a training step of the prior, from the code sequences ids (B, T) torch.long: the start token
+    `sos` in front of the sequence shifted right by one (teacher forcing; the target stays `ids`), with taming-transformers'
+    pkeep corruption: an entry whose u_keep is not below pkeep is replaced by the uniform code min(V - 1, floor(u_rand V)).
+    u_keep, u_rand (B, T) fp32 in [0, 1) - torch.rand with a generator; no random numbers are drawn here.  pkeep >= 1 reads
+    neither (both may be None).  Returns (B, T) torch.long.  An entry of ids outside [0, V) is passed through."""
+    _dev(ids, u_keep, u_rand)
+    ids = _long(ids, "prior_tokens: ids")
+    if ids.dim() != 2 or ids.shape[0] < 1 or ids.shape[1] < 1:
+        raise RuntimeError("prior_tokens: ids (B, T) expected, got %s" % (tuple(ids.shape),))
+    if pkeep < 1:
+        if u_keep is None or u_rand is None:
+            raise RuntimeError("prior_tokens: pkeep=%g below 1 needs u_keep and u_rand" % pkeep)
+        u_keep, u_rand = _flat(u_keep), _flat(u_rand)
+        if tuple(u_keep.shape) != tuple(ids.shape) or tuple(u_rand.shape) != tuple(ids.shape):
+            raise RuntimeError("prior_tokens: u_keep and u_rand of shape %s expected, got %s and %s" % (
+                tuple(ids.shape), tuple(u_keep.shape), tuple(u_rand.shape)))
+    else:
+        u_keep = u_rand = None
+    inp = torch.empty_like(ids)
+    _L().vqw_prior_tokens(ids, u_keep, u_rand, inp, ids.shape[0], ids.shape[1], int(vocab_size), int(sos), float(pkeep))
+    return inp
+
+
 # ----------------------------------------------------------------------------------------------
 # cached generation (networks/gpt.py GPT.decode_step / generate): the decode kernels.  Forward only.
 # ----------------------------------------------------------------------------------------------

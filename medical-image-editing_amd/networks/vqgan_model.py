@@ -6,6 +6,7 @@ reference checkpoint loads with strict=True.  Downsample's convolution - 3x3, st
 ops.conv2d_down2 (the pad is index arithmetic in the kernel's loader, the padded tensor is never written); the quantiser is
 networks.vq.VQ.
 """
+import torch
 import torch.nn as nn
 
 from .blocks import Conv2d
@@ -111,3 +112,36 @@ class VQGAN(nn.Module):
         x = self.vq.lookup(ids)
         x = x.transpose(3, 1)                            # (B, A, C, D) -> (B, D, C, A): the reference's layout, vqgan.py:441-446
         return self.decoder(x)
+
+    # ---- the code side: what the GPT prior trains on and samples into (trainers/prior.py).  Raster order - row-major over the
+    # latent's h, then w, the order taming-transformers trains its prior in - while VQ.forward's ids and generate_image_from_ids
+    # use the reference's transposed (B, W, H) view; the two methods below are the only place that converts.
+    @staticmethod
+    def raster_from_vq_ids(ids):
+        """VQ.forward's ids (B, W, H) -> (B, h * w) in raster order: out[b, r * w + c] is the code of latent pixel (r, c)."""
+        return ids.transpose(1, 2).reshape(ids.shape[0], -1)
+
+    @staticmethod
+    def vq_ids_from_raster(seq, h, w):
+        """(B, h * w) in raster order -> the (B, W, H) view generate_image_from_ids takes."""
+        if seq.dim() != 2 or seq.shape[1] != h * w:
+            raise ValueError("decode_from_ids: seq of shape (B, h * w) = (B, %d) expected, got %s" % (h * w, tuple(seq.shape)))
+        return seq.reshape(seq.shape[0], h, w).transpose(1, 2)
+
+    def _eval_only(self):
+        if self.training:
+            raise RuntimeError("encode_to_ids: eval mode only")
+
+    @torch.no_grad()
+    def encode_to_ids(self, x):
+        """x (B, C, H, W) -> (B, h * w) torch.long, the codes of the latent in raster order.  Eval mode only (no EMA update of the
+        codebook), no gradients."""
+        self._eval_only()
+        _, _, ids = self.vq(self.encoder(x))
+        return self.raster_from_vq_ids(ids).contiguous()
+
+    @torch.no_grad()
+    def decode_from_ids(self, seq, h, w):
+        """seq (B, h * w) torch.long in raster order -> the decoder's picture of those codes.  Eval mode only, no gradients."""
+        self._eval_only()
+        return self.generate_image_from_ids(self.vq_ids_from_raster(seq, h, w))

@@ -1,13 +1,17 @@
 """Launcher: train, validate, test and export a VQ-W-Net from a config (the reference's run_vqwnet.py:61-155 command line).
 
-    python run_vqwnet.py -c CONFIG [-m train|test] [-w] [-v]
+    python run_vqwnet.py -c CONFIG [-m train|test] [-w] [-v | -p]
 
 run.training_mode picks the work: `first_step` / `second_step` train (-m train) or are scored (-m test: result.csv in the
 run directory); `inference` (-m test only) exports PNG and NIfTI files per slice.  -w selects the multi-window step and
 needs loss.recon_weights and dataset.window_width / window_center / window_scale.  -v trains the VQGAN of model.vqgan against
 the U-Net discriminator (trainers/vqgan_unet_dis.py) whatever -w and run.training_mode say - the reference's step has no mode
 dispatch - and needs model.vqmodel.model_name 'VQGAN' and the model.vqgan section; that trainer has no test step, so -v with
--m test or with training_mode 'inference' is refused.
+-m test or with training_mode 'inference' is refused.  -p trains the GPT code prior of model.prior on the codes of the frozen VQGAN
+of model.vqgan (trainers/prior.py; run.first_stage_ckpt_path names the -v checkpoint the VQGAN's weights come from): it needs the
+model.vqgan, model.prior and prior_optim sections, validates (cross-entropy and perplexity), writes a picture and a checkpoint per
+epoch and resumes from run.resume_checkpoint.  -p is refused with -v, with -m test, with training_mode 'inference' and with
+run.num_gpus > 1 (data-parallel prior training is not built).
 
 One process per GPU.  With run.num_gpus == 1 this process is the worker.  With more, this process never touches the GPU:
 it starts num_gpus fresh interpreters of this file (`--rank r`, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their
@@ -36,6 +40,7 @@ def build_parser():
     parser.add_argument("-m", "--mode", default="train", help="train (default) or test")
     parser.add_argument("-w", "--multiwindow", action="store_true", help="multi-window training step")
     parser.add_argument("-v", "--vqgan", action="store_true", help="train the VQGAN (model.vqgan) with the U-Net discriminator; overrides -w")
+    parser.add_argument("-p", "--prior", action="store_true", help="train the GPT code prior (model.prior) on the codes of the VQGAN (model.vqgan)")
     parser.add_argument('--rank', type=int, default=None, help='set by the launcher for its worker processes')
     parser.add_argument('--seed', type=int, default=None, help='set by the launcher: the seed all workers share')
     return parser
@@ -57,9 +62,15 @@ def _lookup(config, dotted):
 
 def check_arguments(config, args):
     """Everything that can be refused before a device is touched or a process started."""
+    prior = bool(getattr(args, "prior", False))
+    if prior and args.vqgan:
+        raise ValueError("-p with -v: one run trains the VQGAN (-v) or the prior on its codes (-p), not both")
     if args.vqgan:
         from trainers.config import check_vqgan_config
         check_vqgan_config(config)              # NotImplementedError naming the VQGAN trainer and the missing keys
+    if prior:
+        from trainers.config import check_prior_config
+        check_prior_config(config)              # NotImplementedError naming the prior trainer and the missing keys
     if args.mode not in ("train", "test"):
         raise ValueError("-m %r: the mode is 'train' or 'test'" % (args.mode,))
     mode = _get(config.run, "training_mode", "first_step")
@@ -68,9 +79,15 @@ def check_arguments(config, args):
     if args.vqgan and (args.mode == "test" or mode == "inference"):
         raise ValueError("-v: the VQGAN trainer has no test step and no inference export (the reference defines neither); "
                          "it trains with -m train and run.training_mode first_step or second_step")
+    if prior and (args.mode == "test" or mode == "inference"):
+        raise ValueError("-p: the prior trainer has no test step and no inference export; it trains with -m train and "
+                         "run.training_mode first_step or second_step")
+    if prior and int(_get(config.run, "num_gpus", 1)) > 1:
+        raise ValueError("-p with run.num_gpus = %d: data-parallel training of the prior is not built (out of scope); "
+                         "set run.num_gpus to 1" % int(_get(config.run, "num_gpus", 1)))
     if mode == "inference" and args.mode != "test":
         raise ValueError("run.training_mode 'inference' exports with -m test; it cannot be trained (-m %s)" % args.mode)
-    if args.multiwindow and not args.vqgan:         # -v overrides -w
+    if args.multiwindow and not args.vqgan and not prior:         # -v and -p override -w
         missing = [k for k in WINDOW_KEYS if _lookup(config, k) is None]
         if missing:
             raise ValueError("-w (multi-window) needs the config keys %s; missing: %s" % (", ".join(WINDOW_KEYS), ", ".join(missing)))
@@ -91,7 +108,7 @@ def launch(args, num_gpus, seed, child_command=None, poll_seconds=0.2, grace_sec
     """Start one worker per GPU and wait -> exit status (0, or the first failing worker's).  This process creates no GPU
     context.  child_command: the command line up to the per-rank arguments (default: this file under this interpreter)."""
     base = list(child_command) if child_command is not None else [sys.executable, os.path.abspath(__file__)]
-    common = ["-c", args.config, "-m", args.mode, "--seed", str(seed)] + (["-w"] if args.multiwindow else []) + (["-v"] if args.vqgan else [])
+    common = ["-c", args.config, "-m", args.mode, "--seed", str(seed)] + (["-w"] if args.multiwindow else []) + (["-v"] if args.vqgan else []) + (["-p"] if getattr(args, "prior", False) else [])
     env = dict(os.environ, WORLD_SIZE=str(num_gpus), MASTER_ADDR=os.environ.get("MASTER_ADDR", "127.0.0.1"),
                MASTER_PORT=os.environ.get("MASTER_PORT") or str(_free_port()))
     procs = []
@@ -151,7 +168,7 @@ def _digest(trainer, fit, path, rank):
 def worker(config, args, training_mode, rank, world_size, seed):
     import torch
     import torch.distributed as dist
-    from trainers import Fit, InferenceModels, build_first_step_trainer, build_second_step_trainer, build_vqgan_trainer
+    from trainers import Fit, InferenceModels, build_first_step_trainer, build_second_step_trainer, build_vqgan_trainer, build_prior_trainer
     from utils.logger import Logger
 
     seed_everything(seed)                       # shared by all ranks: the replicas start from the same weights
@@ -166,7 +183,9 @@ def worker(config, args, training_mode, rank, world_size, seed):
         torch.cuda.set_device(torch.device(device))
         dist.init_process_group("gloo" if one_device else "nccl", rank=rank, world_size=world_size)
     try:
-        if args.vqgan:
+        if getattr(args, "prior", False):
+            trainer = build_prior_trainer(config, device=device)
+        elif args.vqgan:
             trainer = build_vqgan_trainer(config, device=device, data_parallel=distributed)
         elif training_mode == "first_step":
             trainer = build_first_step_trainer(config, device=device, data_parallel=distributed,

@@ -18,6 +18,9 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
                  (multi-window runs, -w); config.loss.clamp_windows (second_step, a key of this project: absent -> true, see
                  trainers/second_step_unet_mw.py)
     config.loss.{perceptual_loss_type, conv_index, perceptual_weights, lpips_weights}   (with use_perceptual_loss)
+    config.model.prior.{n_layer, n_head, n_embed, n_unmasked, pkeep, sos_token}, config.prior_optim.{lr, b1, b2, weight_decay,
+                 grad_norm_clip, warmup_steps, decay_steps}    (the GPT code prior, -p: keys of this project, the reference has
+                 no trainer for its GPT; trainers/prior.py)
 
 The focal frequency loss (use_frequency_loss) is functions.FocalFrequencyLoss, built on HIP kernels in place of the
 third-party focal-frequency-loss package.  The perceptual loss (use_perceptual_loss with perceptual_loss_type 'vgg', the
@@ -108,6 +111,58 @@ def configure_vqgan(config):
                  num_res_blocks=c.num_res_blocks, enc_attn_resolutions=c.enc_attn_resolutions,
                  dec_attn_resolutions=c.dec_attn_resolutions, resolution=c.resolution, p_dropout=c.p_dropout,
                  resamp_with_conv=c.resamp_with_conv, knn_backend=c.knn_backend)
+
+
+PRIOR_KEYS = ("n_layer", "n_head", "n_embed", "n_unmasked", "pkeep", "sos_token")
+PRIOR_OPTIM_KEYS = ("lr", "b1", "b2", "weight_decay", "grad_norm_clip", "warmup_steps", "decay_steps")
+
+
+def check_prior_config(config):
+    """NotImplementedError unless the config describes the prior trainer's models and optimiser: check_vqgan_config's keys (the
+    first stage whose codes are modelled), the six keys of model.prior and the seven of prior_optim (no device work: the launcher
+    calls it before anything else)."""
+    check_vqgan_config(config)
+    for where, section, keys in (("model.prior", _get(config.model, "prior"), PRIOR_KEYS),
+                                 ("prior_optim", _get(config, "prior_optim"), PRIOR_OPTIM_KEYS)):
+        missing = [k for k in keys if section is None or not hasattr(section, k)]
+        if missing:
+            raise NotImplementedError("the prior trainer (run_vqwnet.py -p, trainers.build_prior_trainer) needs %s.{%s}; missing: %s"
+                                      % (where, ", ".join(keys), ", ".join(missing)))
+
+
+def latent_size(config):
+    """Side of the VQGAN's latent map: resolution halved once per encoder level but the first."""
+    c = config.model.vqgan
+    return int(c.resolution) // 2 ** (len(c.enc_ch_multiplier) - 1)
+
+
+def configure_prior(config):
+    """The GPT of config.model.prior over the codes of config.model.vqgan: vocab_size = the VQGAN's dict_size, block_size = the
+    latent's h w (model.prior.block_size, if given, overrides it), every dropout probability 0 (a JSON `false` / absent
+    n_unmasked, like 0, means the plain causal mask)."""
+    from networks import GPT
+    p = config.model.prior
+    side = latent_size(config)
+    return GPT(vocab_size=config.model.vqgan.dict_size, block_size=int(_get(p, "block_size") or side * side), n_layer=p.n_layer,
+               n_head=p.n_head, n_embed=p.n_embed, n_unmasked=int(p.n_unmasked or 0))
+
+
+def build_prior_trainer(config, device="cuda", first_stage_ckpt_path=None):
+    """config -> PriorTrainer (run_vqwnet.py -p): the GPT of model.prior trained on the codes of the frozen VQGAN of model.vqgan.
+    first_stage_ckpt_path (argument, else run.first_stage_ckpt_path) loads a -v checkpoint's `decoder.*` keys into the VQGAN, as
+    build_vqgan_trainer does.  A JSON `false` for pkeep, sos_token, warmup_steps or decay_steps arrives as None: pkeep then means
+    1 (no corruption), the others 0."""
+    from .prior import PriorTrainer
+    check_prior_config(config)
+    vqgan, gpt = configure_vqgan(config), configure_prior(config)
+    first = first_stage_ckpt_path or _get(config.run, "first_stage_ckpt_path")
+    if first:
+        load_vqgan_from_ckpt(first, vqgan)
+    p, o = config.model.prior, config.prior_optim
+    return PriorTrainer(vqgan, gpt, pkeep=1.0 if p.pkeep is None else p.pkeep, sos_token=int(p.sos_token or 0), lr=o.lr,
+                        betas=(o.b1, o.b2), weight_decay=o.weight_decay or 0.0, grad_norm_clip=o.grad_norm_clip or None,
+                        warmup_steps=int(o.warmup_steps or 0), decay_steps=int(o.decay_steps or 0),
+                        seed=int(_get(config.run, "seed", 0) or 0), device=device)
 
 
 def configure_discriminator(config):

@@ -2,7 +2,8 @@
 export (reference: run_vqwnet.py:61-129, trainers/base.py:116-187, single_window_trainer.py:541-644, 716-779), as a plain
 class over the trainers of this package - no PyTorch-Lightning.
 
-    Fit(config, trainer, logger).fit()            train run.n_epochs epochs (from run.resume_checkpoint when set)
+    Fit(config, trainer, logger).fit()            train run.n_epochs epochs (from run.resume_checkpoint when set); with a
+                                                  trainers.PriorTrainer (-p): the same loop, validate_prior per epoch
     Fit(config, trainer, logger).test()           result.csv of trainers.evaluation.Evaluator over the test loader
     Fit(config, trainer, logger).export()         training_mode 'inference': PNG + NIfTI of image, recon, label per slice
 
@@ -29,6 +30,7 @@ from .config import configure_models
 from .first_step import FlipViews, LUNG_WINDOW, MEDIASTINAL_WINDOW, LossWeights
 from .evaluation import Evaluator
 from .vqgan_unet_dis import VQGANUNetDisTrainer
+from .prior import PriorTrainer
 
 LIMIT_VAL_BATCHES = 2              # run_vqwnet.py:127
 SANITY_VAL_BATCHES = 2             # run_vqwnet.py:125
@@ -235,7 +237,12 @@ class Fit:
         self.vqgan = isinstance(trainer, VQGANUNetDisTrainer)
         if self.vqgan:
             self.mode = "second_step"
-        self.dict_size = trainer.dict_size if self.vqgan else config.model.vqmodel.dict_size
+        # the prior trainer (-p) has a step, a validation and a picture of its own (PriorTrainer's methods); the loop, the
+        # lagged log, the checkpoints and the resume are the ones of every run
+        self.prior = isinstance(trainer, PriorTrainer)
+        if self.prior:
+            self.mode = "prior"
+        self.dict_size = trainer.dict_size if self.vqgan or self.prior else config.model.vqmodel.dict_size
         self.n_epochs = int(_get(config.run, "n_epochs", 1))
         self.log_every = int(_get(config.run, "log_every_n_steps", DEFAULT_LOG_EVERY_N_STEPS))
         self.noise_std = float(_get(config.run, "noise_std", DEFAULT_NOISE_STD))
@@ -300,8 +307,11 @@ class Fit:
 
     # ---------------------------------------------------------------- logging
     def _emit_row(self, meta, values):
-        w = self.trainer.w
-        row = _first_step_row(values, w) if isinstance(w, LossWeights) else _second_step_row(values, w)
+        if self.prior:
+            row = dict(values)            # loss, grad_norm, lr: logged as the step returns them
+        else:
+            w = self.trainer.w
+            row = _first_step_row(values, w) if isinstance(w, LossWeights) else _second_step_row(values, w)
         row = {k: float(v) for k, v in row.items()}
         row.update(epoch=meta[0], iteration=meta[1])
         if self.rank == 0 and self.logger is not None:
@@ -309,14 +319,17 @@ class Fit:
 
     def _log_step(self, out):
         if (self.global_step + 1) % self.log_every == 0:
-            terms = _first_step_terms(out) if self.mode == "first_step" else _second_step_terms(out)
+            if self.prior:
+                terms = [(n, out[n]) for n in ("loss", "grad_norm", "lr") if out.get(n) is not None]
+            else:
+                terms = _first_step_terms(out) if self.mode == "first_step" else _second_step_terms(out)
             self.queue.push((self.epoch, self.global_step), terms)
         self.queue.step()
 
     # ---------------------------------------------------------------- training
     def fit(self):
         cfg = self.config
-        if self.mode not in ("first_step", "second_step"):
+        if self.mode not in ("first_step", "second_step", "prior"):
             raise ValueError("training_mode %r cannot be trained (inference runs with -m test)" % (self.mode,))
         start_epoch = 0
         resume = _get(cfg.run, "resume_checkpoint")
@@ -439,6 +452,8 @@ class Fit:
         VQGAN trainer's picture has the discriminator's maps in place of the ids, and no histogram is printed."""
         if self.rank != 0:
             return None
+        if self.prior:
+            return self.validate_prior(epoch, limit)
         n_save = int(_get(self.config.save, "n_save_images", 0) or 0)
         picture = None
         for i, batch in enumerate(self.loader("val")):
@@ -459,6 +474,43 @@ class Fit:
             return path
         return None
 
+    def validate_prior(self, epoch, limit=LIMIT_VAL_BATCHES):
+        """The prior's validation: the mean cross-entropy of at most `limit` validation batches (PriorTrainer.validation_step:
+        no corruption, eval mode) and its exponential, printed and logged as `val_loss` and `ppl`; and <run dir>/<epoch:06d>.png
+        from the last batch: top row the slices, middle row their reconstructions from their own codes, bottom row as many
+        draws of the prior (model.prior.{temperature, top_k}, absent: 1.0 and no filter) from a generator of their own, seeded
+        from (seed, epoch) - the training's random streams are not touched."""
+        tr = self.trainer
+        n_save = int(_get(self.config.save, "n_save_images", 0) or 0)
+        losses, image, ids = [], None, None
+        for i, batch in enumerate(self.loader("val")):
+            if i >= limit:
+                break
+            image = self._to_device(batch)
+            out = tr.validation_step({"image": image})
+            losses.append(out["loss"])
+            ids = out["ids"]
+        if not losses:
+            return None
+        val_loss = float(torch.stack(losses).mean())
+        ppl = float(np.exp(val_loss))
+        self.print("epoch %d: validation cross-entropy %.4f, perplexity %.2f" % (epoch, val_loss, ppl))
+        if self.logger is not None:
+            self.logger.log_metrics({"epoch": epoch, "iteration": self.global_step, "val_loss": val_loss, "ppl": ppl})
+        n = min(n_save, image.shape[0])
+        if n <= 0 or self.logger is None:
+            return None
+        p = self.config.model.prior
+        gen = torch.Generator(device=self.device).manual_seed(self.seed * 1000003 + epoch)
+        recon = tr.vqgan.decode_from_ids(ids[:n], tr.h, tr.w)
+        draws = tr.sample_images(n, temperature=float(_get(p, "temperature", 1.0)), top_k=_get(p, "top_k"), generator=gen)
+        rows = [ops.export_grey(t)[0].cpu().numpy() for t in (image[:n], recon, draws)]
+        picture = np.concatenate([np.concatenate(list(r), axis=1) for r in rows], axis=0)
+        os.makedirs(self.logger.log_dir, exist_ok=True)
+        path = os.path.join(self.logger.log_dir, "%06d.png" % epoch)
+        png.save(path, picture)
+        return path
+
     # ---------------------------------------------------------------- -m test
     def _load_weights_for_test(self):
         resume = _get(self.config.run, "resume_checkpoint")
@@ -470,6 +522,8 @@ class Fit:
 
     def test(self):
         """`-m test` for the training modes: Evaluator over the test loader -> result.csv in the run directory."""
+        if self.prior:
+            raise ValueError("the prior trainer has no test step")
         if self.vqgan:
             raise ValueError("the VQGAN trainer has no test step (the reference defines none)")
         self._load_weights_for_test()
@@ -485,6 +539,8 @@ class Fit:
         <save_dir>/<study_name>/<patient_id>/: image_%04d / recon_%04d / label_%04d as .png (the export kernels' bytes: grey
         over [-1, 1], ids through the palette) and as .nii.gz (float32 image / recon, int32 label; to_nifti orientation).
         NCCLungDataset: image and recon through the lung window first; CRCDataset: all three flipped upside down."""
+        if self.prior:
+            raise ValueError("the prior trainer has no inference export")
         if self.vqgan:
             raise ValueError("the VQGAN trainer has no inference export (the reference defines none)")
         self._load_weights_for_test()

@@ -72,8 +72,10 @@ def save_lightning_style_ckpt(path, encoder=None, decoder=None, dis=None, extra=
 # ----------------------------------------------------------------------------------------------------
 # checkpoints of this build's own runs (trainers/fit.py): the reference's wire format plus one project-own key
 # ----------------------------------------------------------------------------------------------------
-OPTIMIZER_ORDER = ("enc", "dec", "dis")          # configure_optimizers' list, trainers/base.py:164-183
-MODULE_ORDER = ("encoder", "decoder", "dis")
+# configure_optimizers' list, trainers/base.py:164-183; behind it what the reference does not have: the GPT prior's optimiser
+# and module (trainers/prior.py) - a checkpoint of the other trainers is unchanged by the longer lists
+OPTIMIZER_ORDER = ("enc", "dec", "dis", "prior_optim")
+MODULE_ORDER = ("encoder", "decoder", "dis", "transformer")
 RUN_STATE_KEY = "vqw_run_state"                  # not a key of the reference: everything a bit-exact continuation needs
 
 
