@@ -771,6 +771,27 @@ int vqw_xent_bwd(const float* z, const long* target, const float* lse, const flo
  * (torch.long).  1 <= V <= 65536, B >= 1, temperature > 0, top_k >= 0.  A NaN logit makes the result unspecified (some index
  * in [0, V)). */
 int vqw_sample_topk(const float* logits, const float* u, long* out, int B, int V, float temperature, int top_k, void* stream);
+/* Sample or force, with top-k, top-p and the log-probability (GPT.generate_masked's step), one row of logits [B][V] per workgroup.
+ * Filter: s = z / temperature; K1 = vqw_sample_topk's kept set (every entry >= the top_k-th largest, ties included; top_k = 0 or
+ * >= V keeps all); the nucleus is taken over K1: with p_c = exp(s_c - max) / sum_{K1}, entry c stays iff the mass of the entries
+ * of K1 STRICTLY GREATER than it is <= top_p (top_k_top_p_filtering's rule; tied entries share one fate, so no sort order
+ * enters; the largest entry always stays).  The masses are 2^-40 fixed point in 64-bit integers (p <= 1, V <= 2^16: the sums
+ * fit; integer addition has no order): the threshold is exact for the fp32 values of p up to V 2^-41 of the total.  top_p >= 1:
+ * no nucleus filter, and no code for it runs.  Draw: vqw_sample_topk's inverse CDF in index order over the kept set from u[b];
+ * no random numbers of the kernel's own; never an index outside the kept set.  forced [B] (torch.long; may be null): forced[b]
+ * in [0, V) gives out[b] = forced[b] and u[b] is not read; forced[b] < 0 draws; forced[b] >= V draws as well and sets logp[b]
+ * to NaN.  logp [B] (may be null): z[out] - logsumexp(z) under the model's own distribution - temperature 1, unfiltered,
+ * whatever the filter was: fp32 terms exp(z - max), summed in double in a fixed order, rounded once (vqw_xent_fwd's rule).
+ * No float atomics; the same bits every run.  With forced = null and top_p >= 1, out has the bits of vqw_sample_topk on the same
+ * inputs.  1 <= V <= 65536, B >= 1, temperature > 0, top_k >= 0, top_p > 0; logits, u and out must not be null. */
+int vqw_sample_filtered(const float* logits, const float* u, const long* forced, long* out, float* logp, int B, int V,
+                        float temperature, int top_k, float top_p, void* stream);
+/* The composite of an edit: out[b][y][x][c] = cellmask[b][y / fy][x / fx] ? edit[b][y][x][c] : image[b][y][x][c] on NHWC
+ * tensors [N][H][W][C]; cellmask [N][h][w] bytes (non-zero: the edit), fy = H / h, fx = W / w; H % h == 0 and W % w == 0.  One
+ * streaming kernel, 16-byte accesses when a cell's row (fx C floats) is a multiple of 4 floats and the tensors are 16-byte
+ * aligned, else one float per thread.  N H W C < 2^31.  No gradient. */
+int vqw_paste_cells(const float* image, const float* edit, const uint8_t* cellmask, float* out, int N, int H, int W, int C, int h,
+                    int w, void* stream);
 
 /* ---- cached generation for the GPT code prior (networks/gpt.py GPT.prefill / decode_step / generate).  Added functions only; the
  * ABI stays 9.  fp32 in, fp32 out, fp32 accumulation, no float atomics: every sum has a fixed order, the same bits every run.

@@ -1,5 +1,5 @@
-// The three kernel families around the minGPT blocks that make the code prior (networks/mingpt.py GPT :122-224): the token /
-// position embedding, the cross-entropy over the last axis, and top-k sampling.  fp32, dense, no float atomics: every sum has a
+// The kernel families around the minGPT blocks that make the code prior (networks/mingpt.py GPT :122-224): the token /
+// position embedding, the cross-entropy over the last axis, top-k sampling, and the sample-or-force step of masked resampling.  fp32, dense, no float atomics: every sum has a
 // fixed order, two runs give the same bits.
 //
 // Embedding.  x[b][t] = (t < Te ? prefix[b][t] : tok[idx[b][t - Te]]) + pos[t0 + t]: one wave per row, one add per element.  An
@@ -22,6 +22,11 @@
 // not depend on order); every entry at or above it is kept, ties included.  p = exp(s - max) over the kept entries; thread t sums
 // the contiguous chunk t of the row, thread 0 adds the 256 chunk sums in order, finds the first chunk whose running sum exceeds
 // u total and walks it serially.  The row is read from global memory on every pass (L2-resident at these sizes).
+//
+// Sample or force (k_sample_filtered, the step of GPT.generate_masked).  The same row maximum, select and draw, plus a nucleus
+// threshold found by the same radix walk on integer MASSES per bin, a forced token per row in place of the draw, and the token's
+// log-probability under the unfiltered distribution at temperature 1 (the cross-entropy's rule: fp32 terms, a double sum in a
+// fixed order, rounded once).  Details above the kernel.
 #include "common.h"
 #include "../../include/vqwnet_hip.h"
 
@@ -383,5 +388,202 @@ extern "C" int vqw_sample_topk(const float* logits, const float* u, long* out, i
     VQW_CHECK(logits && u && out, "vqw_sample_topk: null pointer");
     hipLaunchKernelGGL(k_sample_topk, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, u, out, V, temperature, top_k);
     VQW_LAUNCH_CHECK("vqw_sample_topk");
+    return VQW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------- sample or force
+// k_sample_topk's row maximum, radix select and draw, operation for operation (with forced = null and top_p >= 1 the two give the
+// same bits), plus: a forced row skips the filter and the draw; the nucleus threshold; the row's log-probability.
+//
+// Nucleus.  Entry c of K1 (the top-k kept set) stays iff G(c) = the mass of the entries of K1 strictly greater than it is
+// <= top_p total.  G falls as the key rises, so the kept set is {key >= thr2} and thr2 is found like the k-th largest entry: byte
+// by byte from the top, on a histogram of MASSES per bin.  The masses are p = exp(s - max) in 2^-40 fixed point (p <= 1 and
+// V <= 2^16: a 64-bit sum cannot overflow; p 2^40 is exact in fp32, the conversion truncates below 2^-40): integer additions have
+// no order, so the LDS atomics leave the same bits every run.  The bins are walked downwards while the mass above the next
+// bin stays within the limit (wave 0, four bins a lane); the bin the walk stops in holds thr2 and is refined by the next byte.  An empty bin may be chosen: thr2
+// need not be a key of the row.
+#define SF_FIX 0x1p40f
+
+template <bool NUCLEUS>
+__global__ void __launch_bounds__(256) k_sample_filtered(const float* __restrict__ logits, const float* __restrict__ u,
+                                                         const long* __restrict__ forced, long* __restrict__ out, float* __restrict__ logp,
+                                                         int V, float temperature, int top_k, float top_p) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned long long mass[256];
+    __shared__ float csum[256];
+    __shared__ int clast[256];
+    __shared__ float wmax[4], wzmax[4];
+    __shared__ double wsum[4];
+    __shared__ unsigned sel[2];
+    __shared__ unsigned long long sabove;
+    const int tid = threadIdx.x;
+    const float* z = logits + (long)blockIdx.x * V;
+    const long f = forced ? forced[blockIdx.x] : -1;
+    const bool force = f >= 0 && f < V;             // the same for the whole workgroup
+
+    float m = -INFINITY, zm = -INFINITY;            // the maxima of s = z / temperature and of z
+    for (int c = tid; c < V; c += 256) {
+        const float x = z[c];
+        zm = fmaxf(zm, x);
+        m = fmaxf(m, x / temperature);
+    }
+    m = wave_max_f(m);
+    zm = wave_max_f(zm);
+    if ((tid & 63) == 0) { wmax[tid >> 6] = m; wzmax[tid >> 6] = zm; }
+    __syncthreads();
+    m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    zm = fmaxf(fmaxf(wzmax[0], wzmax[1]), fmaxf(wzmax[2], wzmax[3]));
+
+    // sum_c exp(z_c - max z): fp32 terms, thread t the columns t, t + 256, ... in double, a butterfly per wave, the four waves in order
+    if (logp) {
+        double s = 0.0;
+        for (int c = tid; c < V; c += 256) s += (double)expf(z[c] - zm);
+        s = wave_sum_d(s);
+        if ((tid & 63) == 0) wsum[tid >> 6] = s;
+    }
+
+    int pick = (int)f;
+    if (!force) {
+        // the key of the k-th largest entry: k_sample_topk's select
+        unsigned thr = 0;
+        if (top_k > 0 && top_k < V) {
+            unsigned prefix = 0, pmask = 0, kk = (unsigned)top_k;
+            for (int shift = 24; shift >= 0; shift -= 8) {
+                hist[tid] = 0;
+                __syncthreads();
+                for (int c = tid; c < V; c += 256) {
+                    const unsigned key = st_key(z[c] / temperature);
+                    if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    int bin = 255;
+                    for (; bin > 0; --bin) {
+                        const unsigned cnt = hist[bin];
+                        if (cnt >= kk) break;
+                        kk -= cnt;
+                    }
+                    sel[0] = prefix | ((unsigned)bin << shift);
+                    sel[1] = kk;
+                }
+                __syncthreads();
+                prefix = sel[0];
+                kk = sel[1];
+                pmask |= 0xffu << shift;
+                __syncthreads();
+            }
+            thr = prefix;
+        }
+
+        if (NUCLEUS) {
+            unsigned prefix = 0, pmask = 0;
+            unsigned long long above = 0, limit = 0;          // wave 0's: the mass above the chosen bin, floor(top_p total)
+            for (int shift = 24; shift >= 0; shift -= 8) {
+                mass[tid] = 0;
+                __syncthreads();
+                for (int c = tid; c < V; c += 256) {
+                    const float x = z[c] / temperature;
+                    const unsigned key = st_key(x);
+                    if (key >= thr && (key & pmask) == prefix)
+                        atomicAdd(&mass[(key >> shift) & 255u], (unsigned long long)(expf(x - m) * SF_FIX));
+                }
+                __syncthreads();
+                // the walk "bin = 255; while (bin > 0 && above + mass[bin] <= limit) above += mass[bin--]" by wave 0: lane l owns
+                // the bins 255 - 4 l ... 252 - 4 l, an integer scan over the lanes finds the lane the walk stops in
+                if (tid < 64) {
+                    const int hi = 255 - 4 * tid;
+                    unsigned long long mb[4], own = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { mb[j] = mass[hi - j]; own += mb[j]; }
+                    unsigned long long inc = own;
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const unsigned long long t = __shfl_up(inc, o, 64);
+                        if (tid >= o) inc += t;
+                    }
+                    if (shift == 24) limit = (unsigned long long)((double)top_p * (double)__shfl(inc, 63, 64));
+                    const unsigned long long over = __ballot(above + inc > limit);
+                    const int stop = over ? __ffsll((long long)over) - 1 : 63;
+                    if (tid == stop) {
+                        unsigned long long a = above + (inc - own);
+                        int bin = hi;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (bin == hi - j && bin > 0 && a + mb[j] <= limit) { a += mb[j]; --bin; }
+                        sel[0] = prefix | ((unsigned)bin << shift);
+                        sabove = a;
+                    }
+                }
+                __syncthreads();
+                prefix = sel[0];
+                above = sabove;
+                pmask |= 0xffu << shift;
+                __syncthreads();
+            }
+            if (prefix > thr) thr = prefix;
+        }
+
+        // k_sample_topk's draw: chunk sums of p = exp(s - max) over the kept entries, and each chunk's last kept index
+        const int chunk = (V + 255) / 256, c0 = tid * chunk, c1 = c0 + chunk < V ? c0 + chunk : V;
+        float s = 0.f;
+        int last = -1;
+        for (int c = c0; c < c1; ++c) {
+            const float x = z[c] / temperature;
+            if (st_key(x) >= thr) { s += expf(x - m); last = c; }
+        }
+        csum[tid] = s;
+        clast[tid] = last;
+        __syncthreads();
+        if (tid == 0) {
+            float total = 0.f;
+            for (int t = 0; t < 256; ++t) total += csum[t];
+            const float goal = u[blockIdx.x] * total;
+            float run = 0.f;
+            int t = 0;
+            pick = -1;
+            for (; t < 256; ++t) {
+                const float nx = run + csum[t];
+                if (nx > goal) break;
+                run = nx;
+            }
+            if (t < 256) {
+                const int e = (t + 1) * chunk < V ? (t + 1) * chunk : V;
+                for (int c = t * chunk; c < e; ++c) {
+                    const float x = z[c] / temperature;
+                    if (st_key(x) >= thr) {
+                        run += expf(x - m);
+                        if (run > goal) { pick = c; break; }
+                    }
+                }
+                if (pick < 0) pick = clast[t];              // rounding: the chunk's own sum crossed, the running sum did not
+            } else {
+                for (t = 255; t >= 0 && pick < 0; --t) pick = clast[t];      // rounding left no such index: the last kept one
+            }
+            if (pick < 0) pick = 0;                         // only with NaN logits
+        }
+    } else {
+        __syncthreads();                                    // wsum
+    }
+    if (tid == 0) {
+        out[blockIdx.x] = pick;
+        if (logp) {                                         // k_xe_fwd's form: the difference first, then the logarithm, rounded once
+            const double ls = log(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+            logp[blockIdx.x] = f >= V ? __uint_as_float(0x7fc00000u) : -(float)(((double)zm - (double)z[pick]) + ls);
+        }
+    }
+}
+
+extern "C" int vqw_sample_filtered(const float* logits, const float* u, const long* forced, long* out, float* logp, int B, int V,
+                                   float temperature, int top_k, float top_p, void* stream) {
+    VQW_CHECK(V >= 1 && V <= ST_MAX_V, "vqw_sample_filtered: V=%d must satisfy 1 <= V <= %d", V, ST_MAX_V);
+    VQW_CHECK(B >= 1, "vqw_sample_filtered: B=%d must be at least 1", B);
+    VQW_CHECK(temperature > 0.f, "vqw_sample_filtered: temperature=%g must be positive", (double)temperature);
+    VQW_CHECK(top_k >= 0, "vqw_sample_filtered: top_k=%d must not be negative (0: no filter)", top_k);
+    VQW_CHECK(top_p > 0.f, "vqw_sample_filtered: top_p=%g must be positive (>= 1: no filter)", (double)top_p);
+    VQW_CHECK(logits && u && out, "vqw_sample_filtered: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (top_p < 1.f) hipLaunchKernelGGL(k_sample_filtered<true>, dim3(B), dim3(256), 0, st, logits, u, forced, out, logp, V, temperature, top_k, top_p);
+    else hipLaunchKernelGGL(k_sample_filtered<false>, dim3(B), dim3(256), 0, st, logits, u, forced, out, logp, V, temperature, top_k, top_p);
+    VQW_LAUNCH_CHECK("vqw_sample_filtered");
     return VQW_OK;
 }

@@ -1812,6 +1812,48 @@ def sample_topk(logits, u, temperature=1.0, top_k=0):
     return out
 
 
+def sample_filtered(logits, u, forced=None, temperature=1.0, top_k=0, top_p=None, return_logp=True):
+    """One token per row of logits (B, V), sampled or forced -> (tokens (B,) torch.long, logp (B,) fp32 or None).
+    Filter: sample_topk's top-k (0, None or >= V: none), then the nucleus over what it kept: an entry stays iff the mass of the
+    kept entries strictly greater than it is <= top_p (top_k_top_p_filtering's rule; ties share one fate; None or >= 1: no
+    filter).  Draw: sample_topk's inverse CDF with the caller's uniforms u (B,).  forced (B,) torch.long or None: a row whose entry
+    lies in [0, V) takes it (u is not read there), a negative entry draws, an entry >= V draws and makes logp NaN.  logp is the
+    token's log-probability under the model's own distribution (temperature 1, no filter).  With forced None and no top_p the
+    tokens have sample_topk's bits."""
+    _dev(logits, u, forced)
+    logits, u = _flat(logits), _flat(u)
+    if logits.dim() != 2 or u.dim() != 1 or u.shape[0] != logits.shape[0]:
+        raise RuntimeError("sample_filtered: logits (B, V) and u (B,) expected, got %s and %s" % (tuple(logits.shape), tuple(u.shape)))
+    if forced is not None:
+        forced = _long(forced, "sample_filtered: forced")
+        if tuple(forced.shape) != tuple(u.shape):
+            raise RuntimeError("sample_filtered: forced (B,) = %s expected, got %s" % (tuple(u.shape), tuple(forced.shape)))
+    B, V = logits.shape
+    out = torch.empty(B, dtype=torch.long, device=logits.device)
+    logp = torch.empty(B, dtype=torch.float32, device=logits.device) if return_logp else None
+    _L().vqw_sample_filtered(logits, u, forced, out, logp, B, V, float(temperature), int(top_k or 0), 1.0 if top_p is None else float(top_p))
+    return out, logp
+
+
+def paste_cells(image, edit, cellmask):
+    """The composite of an edit: out = edit where the latent cell of the pixel is set in cellmask (B, h, w) torch.uint8, else
+    image; image and edit (B, C, H, W) fp32 in either memory format, H and W multiples of h and w.  Returns a channels_last
+    tensor.  No gradient."""
+    _dev(image, edit, cellmask)
+    image, edit = nhwc(image.detach()), nhwc(edit.detach())
+    if image.shape != edit.shape:
+        raise RuntimeError("paste_cells: shape mismatch %s vs %s" % (tuple(image.shape), tuple(edit.shape)))
+    N, C, H, W = image.shape
+    if cellmask.dtype != torch.uint8 or cellmask.dim() != 3 or cellmask.shape[0] != N:
+        raise RuntimeError("paste_cells: cellmask (B, h, w) torch.uint8 with B = %d expected, got %s of %s" % (N, tuple(cellmask.shape), cellmask.dtype))
+    h, w = cellmask.shape[1:]
+    if h < 1 or w < 1 or H % h or W % w:
+        raise RuntimeError("paste_cells: H = %d and W = %d must be multiples of the cell grid %d x %d" % (H, W, h, w))
+    out = torch.empty_like(image, memory_format=CL)
+    _L().vqw_paste_cells(image, edit, cellmask.contiguous(), out, N, H, W, C, h, w)
+    return out
+
+
 def prior_tokens(ids, sos, pkeep, vocab_size, u_keep=None, u_rand=None):
     """The transformer's input of a training step of the prior, from the code sequences ids (B, T) torch.long: the start token
     `sos` in front of the sequence shifted right by one (teacher forcing; the target stays `ids`), with taming-transformers'

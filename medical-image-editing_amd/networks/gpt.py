@@ -22,7 +22,13 @@ full-sequence kernels and copies every layer's k and v into the cache, GPT.decod
 the whole step - embedding, per layer ln1 + q|k|v (k and v written straight into the cache row), attention over the cache, proj +
 residual, ln2 + fc1 + GELU, fc2 + residual, then ln_f + head - is 2 + 5 n_layer launches issued from C, with no copy of the past,
 no allocation and no synchronisation.  sample() stays as it is: the yardstick of the new path.  Neither has dropout (eval mode).
+
+Masked resampling.  GPT.generate_masked redraws some positions of a sequence and keeps the others, on the same cache: one prefill over
+the prompt and the kept codes in front of the first redrawn position, then per position ONE ops.sample_filtered launch - a draw
+(top-k, then top-p) or the kept token, and the log-probability of whichever stands there - and one decode_step.  The resample mask is a
+host array: the plan is made without a synchronisation.  The sum of the log-probabilities scores a candidate (trainers/prior.py).
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -228,6 +234,71 @@ class GPT(nn.Module):
         finally:
             self.train(was_training)
         return torch.cat(out, dim=1)
+
+    @torch.no_grad()
+    def generate_masked(self, idx, known, resample, temperature=1.0, top_k=None, top_p=None, generator=None, uniforms=None,
+                        embeddings=None):
+        """Redraw some positions of a sequence and keep the others: behind the prompt idx (B, Tp) (and `embeddings`), position k
+        of the S new ones takes known[:, k] where resample is false and a draw - top-k, then top-p, ops.sample_filtered - where it
+        is true.  Either way the token goes into the cache: what follows is conditioned on what was kept and on what was drawn.
+        known (B, S) torch.long on the device; resample a HOST bool array (S,) or (B, S) - the plan below is made from it without
+        a synchronisation.  Returns (tokens (B, S) torch.long, logp (B, S) fp32), logp[:, k] the model's log-probability
+        (temperature 1, unfiltered) of the token that stands at k.
+
+        With j0 the first column in which any row resamples, the prompt and known[:, :j0] go through prefill once (their logp:
+        minus the cross-entropy of the prefill logits); from j0 on each position is one ops.sample_filtered launch - forced to
+        that column of where(resample, -1, known) - and one decode_step; the last token is not fed back.  Nothing resampled: one
+        prefill and nothing else.  uniforms (S - j0, B), or a generator, as in generate().  Refused before any kernel: training
+        mode, Tp + S - 1 > block_size, n_unmasked > Tp + j0 (the decode steps apply no mask: prefill's caveat), shapes, top_p
+        outside (0, 1]."""
+        if self.training:
+            raise RuntimeError("GPT.generate_masked: inference only, the model is in training mode (call .eval())")
+        t = self._new_tokens(idx, embeddings)
+        if known.dim() != 2 or known.shape[0] != idx.shape[0] or known.shape[1] < 1 or known.dtype != torch.long:
+            raise ValueError("GPT.generate_masked: known (B, S) torch.long with B = %d and S >= 1 expected, got %s of %s" % (
+                idx.shape[0], tuple(known.shape), known.dtype))
+        B, S = known.shape
+        mask = np.asarray(resample)
+        if mask.dtype != np.bool_ or mask.shape not in ((S,), (B, S)):
+            raise ValueError("GPT.generate_masked: resample must be a host bool array of shape (S,) = (%d,) or (B, S) = (%d, %d), got %s of %s" % (
+                S, B, S, mask.shape, mask.dtype))
+        mask = np.broadcast_to(mask, (B, S)).copy()
+        if t < 1 or t + S - 1 > self.block_size:
+            raise RuntimeError("GPT.generate_masked: a prompt of %d tokens + %d positions - 1 exceeds block_size=%d" % (t, S, self.block_size))
+        if not temperature > 0:
+            raise ValueError("GPT.generate_masked: temperature=%r must be positive" % (temperature,))
+        if top_p is not None and not 0 < top_p <= 1:
+            raise ValueError("GPT.generate_masked: top_p=%r must lie in (0, 1]" % (top_p,))
+        cols = np.flatnonzero(mask.any(axis=0))
+        j0 = int(cols[0]) if cols.size else S
+        if self.config.n_unmasked > t + j0:
+            raise RuntimeError("GPT.generate_masked: n_unmasked=%d exceeds the %d tokens of the prefill (prompt %d + kept prefix %d); the "
+                               "decode steps apply no mask" % (self.config.n_unmasked, t + j0, t, j0))
+        if uniforms is not None and tuple(uniforms.shape) != (S - j0, B):
+            raise ValueError("GPT.generate_masked: uniforms of shape %s, (S - j0, B) = (%d, %d) expected" % (tuple(uniforms.shape), S - j0, B))
+
+        n_pre = min(j0, S - 1)                         # known columns behind the prompt in the prefill
+        cache = self.new_cache(B, capacity=t + S - 1)
+        dev = cache.kv.device
+        logits = self.prefill(torch.cat((idx, known[:, :n_pre]), dim=1), cache, embeddings)
+        tokens = torch.empty(B, S, dtype=torch.long, device=dev)
+        logp = torch.empty(B, S, dtype=torch.float32, device=dev)
+        n_xe = n_pre if j0 < S else S                  # positions whose log-probability the prefill logits give
+        if n_xe:
+            tokens[:, :n_xe] = known[:, :n_xe]
+            logp[:, :n_xe] = -ops.cross_entropy(logits[:, t - 1:t - 1 + n_xe], known[:, :n_xe], reduction="none")
+        if j0 < S:
+            if uniforms is not None:
+                uniforms = uniforms.to(device=dev, dtype=torch.float32)
+            forced = torch.where(torch.from_numpy(mask).to(dev), torch.full_like(known, -1), known).t().contiguous()      # (S, B)
+            step_logits = logits[:, -1, :]
+            for k in range(j0, S):
+                u = uniforms[k - j0] if uniforms is not None else torch.rand(B, generator=generator, device=dev)
+                new, lp = ops.sample_filtered(step_logits, u, forced[k], temperature, top_k, top_p)
+                tokens[:, k], logp[:, k] = new, lp
+                if k + 1 < S:
+                    step_logits = self.decode_step(new, cache)
+        return tokens, logp
 
 
 def decode_pack_layout(n_layer, n_embed, vocab_size):

@@ -1,6 +1,7 @@
 """Launcher: train, validate, test and export a VQ-W-Net from a config (the reference's run_vqwnet.py:61-155 command line).
 
     python run_vqwnet.py -c CONFIG [-m train|test] [-w] [-v | -p]
+    python run_vqwnet.py -c CONFIG -p -m edit
 
 run.training_mode picks the work: `first_step` / `second_step` train (-m train) or are scored (-m test: result.csv in the
 run directory); `inference` (-m test only) exports PNG and NIfTI files per slice.  -w selects the multi-window step and
@@ -11,7 +12,10 @@ dispatch - and needs model.vqmodel.model_name 'VQGAN' and the model.vqgan sectio
 of model.vqgan (trainers/prior.py; run.first_stage_ckpt_path names the -v checkpoint the VQGAN's weights come from): it needs the
 model.vqgan, model.prior and prior_optim sections, validates (cross-entropy and perplexity), writes a picture and a checkpoint per
 epoch and resumes from run.resume_checkpoint.  -p is refused with -v, with -m test, with training_mode 'inference' and with
-run.num_gpus > 1 (data-parallel prior training is not built).
+run.num_gpus > 1 (data-parallel prior training is not built).  -p -m edit edits slices with a trained prior (Fit.edit): the
+prior of run.resume_checkpoint redraws the codes of the region the `edit` section selects (box, mask_path or nll_threshold) in the
+first edit.n_slices test slices, edit.n_candidates times each, and keeps the likeliest; pictures, codes and scores go to
+<run dir>/edit/.  -m edit without -p is refused.
 
 One process per GPU.  With run.num_gpus == 1 this process is the worker.  With more, this process never touches the GPU:
 it starts num_gpus fresh interpreters of this file (`--rank r`, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their
@@ -37,7 +41,7 @@ TRAINING_MODES = ("first_step", "second_step", "inference")
 def build_parser():
     parser = argparse.ArgumentParser(description="Train, score or export a VQ-W-Net from a JSON config")
     parser.add_argument("-c", "--config", required=True, help="path of the JSON config")
-    parser.add_argument("-m", "--mode", default="train", help="train (default) or test")
+    parser.add_argument("-m", "--mode", default="train", help="train (default), test, or edit (with -p)")
     parser.add_argument("-w", "--multiwindow", action="store_true", help="multi-window training step")
     parser.add_argument("-v", "--vqgan", action="store_true", help="train the VQGAN (model.vqgan) with the U-Net discriminator; overrides -w")
     parser.add_argument("-p", "--prior", action="store_true", help="train the GPT code prior (model.prior) on the codes of the VQGAN (model.vqgan)")
@@ -71,8 +75,13 @@ def check_arguments(config, args):
     if prior:
         from trainers.config import check_prior_config
         check_prior_config(config)              # NotImplementedError naming the prior trainer and the missing keys
-    if args.mode not in ("train", "test"):
-        raise ValueError("-m %r: the mode is 'train' or 'test'" % (args.mode,))
+    if args.mode == "edit":
+        if not prior:
+            raise ValueError("-m edit: editing redraws the codes of a region with the code prior and needs -p")
+        from trainers.config import check_edit_config
+        check_edit_config(config)               # NotImplementedError naming the missing keys of the `edit` section
+    elif args.mode not in ("train", "test"):
+        raise ValueError("-m %r: the mode is 'train' or 'test' (or, with -p, 'edit')" % (args.mode,))
     mode = _get(config.run, "training_mode", "first_step")
     if mode not in TRAINING_MODES:
         raise ValueError("run.training_mode %r: one of %s" % (mode, ", ".join(TRAINING_MODES)))
@@ -212,6 +221,8 @@ def worker(config, args, training_mode, rank, world_size, seed):
                   data_seed=seed)
         if training_mode == "inference":
             fit.export()
+        elif args.mode == "edit":
+            fit.edit()
         elif args.mode == "train":
             fit.fit()
         else:

@@ -21,6 +21,8 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
     config.model.prior.{n_layer, n_head, n_embed, n_unmasked, pkeep, sos_token}, config.prior_optim.{lr, b1, b2, weight_decay,
                  grad_norm_clip, warmup_steps, decay_steps}    (the GPT code prior, -p: keys of this project, the reference has
                  no trainer for its GPT; trainers/prior.py)
+    config.edit.{n_slices, n_candidates, temperature, top_k, top_p, seed} and one of edit.{box, mask_path, nll_threshold},
+                 config.run.resume_checkpoint    (editing with the prior, -p -m edit: keys of this project; Fit.edit)
 
 The focal frequency loss (use_frequency_loss) is functions.FocalFrequencyLoss, built on HIP kernels in place of the
 third-party focal-frequency-loss package.  The perceptual loss (use_perceptual_loss with perceptual_loss_type 'vgg', the
@@ -128,6 +130,29 @@ def check_prior_config(config):
         if missing:
             raise NotImplementedError("the prior trainer (run_vqwnet.py -p, trainers.build_prior_trainer) needs %s.{%s}; missing: %s"
                                       % (where, ", ".join(keys), ", ".join(missing)))
+
+
+EDIT_KEYS = ("n_slices", "n_candidates", "temperature", "top_k", "top_p", "seed")
+EDIT_SELECTORS = ("box", "mask_path", "nll_threshold")
+
+
+def check_edit_config(config):
+    """NotImplementedError unless the config describes an editing run (run_vqwnet.py -p -m edit): check_prior_config's keys,
+    run.resume_checkpoint (the -p checkpoint whose prior edits), the six keys of the `edit` section and exactly one selector
+    among edit.{box, mask_path, nll_threshold} (a JSON `false` is no selector).  No device work."""
+    check_prior_config(config)
+    if not _get(config.run, "resume_checkpoint"):
+        raise NotImplementedError("editing with the prior (run_vqwnet.py -p -m edit) needs run.resume_checkpoint, the -p checkpoint "
+                                  "of the prior; missing: run.resume_checkpoint")
+    section = _get(config, "edit")
+    missing = [k for k in EDIT_KEYS if section is None or not hasattr(section, k)]
+    if missing:
+        raise NotImplementedError("editing with the prior (run_vqwnet.py -p -m edit) needs edit.{%s}; missing: %s"
+                                  % (", ".join(EDIT_KEYS), ", ".join(missing)))
+    given = [k for k in EDIT_SELECTORS if _get(section, k) is not None]
+    if len(given) != 1:
+        raise NotImplementedError("editing with the prior (run_vqwnet.py -p -m edit) needs exactly one of edit.{%s}; given: %s"
+                                  % (", ".join(EDIT_SELECTORS), ", ".join(given) or "none"))
 
 
 def latent_size(config):

@@ -6,6 +6,7 @@ class over the trainers of this package - no PyTorch-Lightning.
                                                   trainers.PriorTrainer (-p): the same loop, validate_prior per epoch
     Fit(config, trainer, logger).test()           result.csv of trainers.evaluation.Evaluator over the test loader
     Fit(config, trainer, logger).export()         training_mode 'inference': PNG + NIfTI of image, recon, label per slice
+    Fit(config, trainer, logger).edit()           -p -m edit: PriorTrainer.edit over the first test slices -> pictures, codes, scores
 
 Nothing here reads a scalar from the device inside a step: the logged losses of a step go to the host in one small
 copy that is looked at two steps later (after that step's StepThrottle event), so the loop adds host work only.
@@ -510,6 +511,57 @@ class Fit:
         path = os.path.join(self.logger.log_dir, "%06d.png" % epoch)
         png.save(path, picture)
         return path
+
+    # ---------------------------------------------------------------- -p -m edit
+    def edit(self):
+        """`-p -m edit`: PriorTrainer.edit over the first edit.n_slices slices of the test split with the prior of
+        run.resume_checkpoint; the region is edit.box (y0, y1, x0, x1 in pixels), edit.mask_path (a .npy mask at pixel or code
+        resolution) or edit.nll_threshold.  Under <run dir>/edit/: slice_<i>.png - four grey tiles side by side: the slice, its
+        reconstruction from its own codes, the best edit, the composite; codes_<i>.npy - (3, h, w) int64: the codes before,
+        after, and the cell mask; edit.csv - slice, candidate, score, rank (0: the best), n_resampled.  All draws come from one
+        generator seeded with edit.seed: a seed reproduces every file byte for byte."""
+        if not self.prior:
+            raise ValueError("editing needs the prior trainer (-p)")
+        self._load_weights_for_test()
+        if self.rank != 0:
+            return []
+        e, tr = self.config.edit, self.trainer
+        n_slices = int(e.n_slices)
+        selector = {}
+        if _get(e, "box") is not None:
+            selector["box"] = tuple(int(v) for v in e.box)
+        elif _get(e, "mask_path") is not None:
+            selector["mask"] = np.load(e.mask_path)
+        else:
+            selector["nll_threshold"] = float(e.nll_threshold)
+        gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
+        out_dir = os.path.join(self.logger.log_dir, "edit")
+        os.makedirs(out_dir, exist_ok=True)
+        rows, written, done = ["slice,candidate,score,rank,n_resampled"], [], 0
+        for batch in self.loader("test"):
+            if done >= n_slices:
+                break
+            image = self._to_device(batch)[:n_slices - done]
+            out = tr.edit({"image": image}, n_candidates=int(e.n_candidates), temperature=float(e.temperature or 1.0),
+                          top_k=e.top_k or None, top_p=e.top_p or None, generator=gen, **selector)
+            tiles = [ops.export_grey(t)[0].cpu().numpy() for t in (image, out["recon"], out["edit"], out["composite"])]
+            scores, cells = out["scores"].cpu().numpy(), out["cellmask"].cpu().numpy()
+            before = out["source_ids"].cpu().numpy().reshape(cells.shape)
+            after = out["ids"].cpu().numpy().reshape(cells.shape)
+            for b in range(image.shape[0]):
+                i = done + b
+                path = os.path.join(out_dir, "slice_%04d.png" % i)
+                png.save(path, np.concatenate([t[b] for t in tiles], axis=1))
+                np.save(os.path.join(out_dir, "codes_%04d.npy" % i), np.stack([before[b], after[b], cells[b].astype(np.int64)]))
+                rank = np.argsort(np.argsort(-scores[b], kind="stable"), kind="stable")
+                for c in range(scores.shape[1]):
+                    rows.append("%d,%d,%.17g,%d,%d" % (i, c, scores[b, c], rank[c], int(cells[b].sum())))
+                written.append(path)
+            done += image.shape[0]
+        with open(os.path.join(out_dir, "edit.csv"), "w") as f:
+            f.write("\n".join(rows) + "\n")
+        self.print("Edited slices are saved: {}".format(out_dir))
+        return written
 
     # ---------------------------------------------------------------- -m test
     def _load_weights_for_test(self):

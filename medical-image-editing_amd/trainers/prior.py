@@ -13,9 +13,15 @@ Nothing is read back: the step returns {'loss', 'grad_norm', 'lr', 'ids'} with t
 `modules()` is {'decoder': vqgan, 'transformer': gpt}: a -v checkpoint's decoder.* keys load into the frozen first stage
 (run.first_stage_ckpt_path), and a prior checkpoint carries both.  `extra` holds the generator's state and the step counter
 the learning rate is computed from, so a resumed run continues bit for bit.
+
+Editing (the launcher's -p -m edit).  token_nll(batch) is the prior's opinion of a slice code by code, -log p(code | the codes
+before it) as an (h, w) map.  edit(batch, mask | box | nll_threshold) redraws the selected codes n_candidates times with
+GPT.generate_masked, keeps every other code, scores each candidate by the log-probability of its whole sequence and pastes the best
+one back into the slice cell by cell (ops.paste_cells).
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -203,3 +209,104 @@ class PriorTrainer(TrainerBase):
     def sample_images(self, n, temperature=1.0, top_k=None, generator=None):
         """n pictures: sample_ids, then VQGAN.decode_from_ids."""
         return self.vqgan.decode_from_ids(self.sample_ids(n, temperature, top_k, generator), self.h, self.w)
+
+    # ---------------------------------------------------------------- editing
+    @torch.no_grad()
+    def _token_nll(self, ids):
+        was_training = self.gpt.training
+        self.gpt.eval()
+        try:
+            nll = ops.cross_entropy(self.gpt(self._inputs(ids, 1.0)), ids, reduction="none")
+        finally:
+            self.gpt.train(was_training)
+        return nll
+
+    def token_nll(self, batch):
+        """What the prior thinks of a slice, code by code: -log p(code | the codes before it) as a map (B, h, w) fp32 in raster
+        order - one full forward in eval mode without corruption (pkeep = 1) and ops.cross_entropy(reduction='none').  Its mean
+        is validation_step's loss; a high value marks a code the prior did not expect (the anomaly map of a code prior)."""
+        ids = self.codes(batch)
+        if ids.shape[1] != self.h * self.w:
+            raise ValueError("PriorTrainer.token_nll: sequences of h w = %d codes expected, got %d" % (self.h * self.w, ids.shape[1]))
+        return self._token_nll(ids).reshape(-1, self.h, self.w)
+
+    def cell_mask(self, B, mask=None, box=None, image_size=None):
+        """The host bool array (B, h, w) of the codes a user's selection touches.  mask: a host array at pixel resolution (H, W)
+        or (B, H, W), or at code resolution (h, w) or (B, h, w); box = (y0, y1, x0, x1) in pixels.  A code is selected iff any
+        pixel of its cell is set.  H, W: image_size, else the VQGAN's resolution."""
+        h, w = self.h, self.w
+        H, W = image_size if image_size is not None else (int(self.vqgan.encoder.resolution),) * 2
+        if H % h or W % w:
+            raise ValueError("PriorTrainer.edit: the picture's %d x %d is no multiple of the latent's %d x %d" % (H, W, h, w))
+        if box is not None:
+            y0, y1, x0, x1 = (int(v) for v in box)
+            if not (0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W):
+                raise ValueError("PriorTrainer.edit: box [%d, %d) x [%d, %d) outside %d x %d" % (y0, y1, x0, x1, H, W))
+            mask = np.zeros((H, W), dtype=bool)
+            mask[y0:y1, x0:x1] = True
+        mask = np.asarray(mask) != 0
+        if mask.ndim == 2:
+            mask = mask[None]
+        if mask.ndim != 3 or mask.shape[0] not in (1, B) or mask.shape[1:] not in ((H, W), (h, w)):
+            raise ValueError("PriorTrainer.edit: a mask of shape (H, W) = (%d, %d), (h, w) = (%d, %d) or either behind B = %d expected, got %s" % (
+                H, W, h, w, B, mask.shape))
+        if mask.shape[1:] != (h, w):
+            mask = mask.reshape(mask.shape[0], h, H // h, w, W // w).any(axis=(2, 4))
+        return np.broadcast_to(mask, (B, h, w)).copy()
+
+    @torch.no_grad()
+    def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None,
+             generator=None):
+        """Redraw the codes of a region of every slice with the prior and keep the rest.  Exactly one selector: `mask` (a host
+        array at pixel or code resolution, cell_mask), `box` = (y0, y1, x0, x1) in pixels, or `nll_threshold`, which selects the
+        codes whose token_nll exceeds it - the prior picks the region itself; this costs one device-to-host read of the map.
+
+        Every slice is repeated n_candidates times in the batch and ONE GPT.generate_masked call behind the start token draws all
+        B n_candidates rows (the uniforms are drawn per candidate from `generator`, candidate 0 first, so a seed gives candidate 0
+        the same codes whatever n_candidates is); a candidate's score is the sum of logp over the whole sequence (in double) - the kept codes behind
+        the region included, scored given the drawn ones, which is how a raster-order prior prefers what fits the codes that
+        follow.  One device-to-host read ranks them.  A slice with no code selected comes back unchanged, with its own score.
+
+        Returns a dict: ids (B, T) the best candidate (source_ids: the slice's own codes); candidates (B, n, T) and scores (B, n) float64 in draw order; best (B,);
+        cellmask (B, h, w) uint8; recon and edit, the slice's own codes and the best candidate's through decode_from_ids; and
+        composite = ops.paste_cells(image, edit, cellmask).  A {'ids'} batch has no image and no composite."""
+        if (mask is not None) + (box is not None) + (nll_threshold is not None) != 1:
+            raise ValueError("PriorTrainer.edit: exactly one of mask, box and nll_threshold selects the region")
+        n = int(n_candidates)
+        if n < 1:
+            raise ValueError("PriorTrainer.edit: n_candidates=%r must be at least 1" % (n_candidates,))
+        has_image = not (isinstance(batch, dict) and batch.get("ids") is not None)
+        image = (batch["image"] if isinstance(batch, dict) else batch).to(self.device) if has_image else None
+        ids = self.codes({"image": image} if has_image else batch)
+        B, T = ids.shape
+        if T != self.h * self.w:
+            raise ValueError("PriorTrainer.edit: sequences of h w = %d codes expected, got %d" % (self.h * self.w, T))
+        if nll_threshold is not None:
+            cells = (self._token_nll(ids).reshape(B, self.h, self.w) > float(nll_threshold)).cpu().numpy()      # the one read of the selector
+        else:
+            cells = self.cell_mask(B, mask, box, tuple(image.shape[-2:]) if has_image else None)
+        resample = np.repeat(cells.reshape(B, T), n, axis=0)
+        known = ids.repeat_interleave(n, dim=0)
+        start = torch.full((B * n, 1), self.sos_token, dtype=torch.long, device=self.device)
+        # one torch.rand call per candidate, candidate 0 first: its uniforms - and so its codes - do not depend on n_candidates
+        cols = np.flatnonzero(resample.any(axis=0))
+        steps = T - int(cols[0]) if cols.size else 0
+        uniforms = torch.stack([torch.rand(steps, B, generator=generator, device=self.device) for _ in range(n)])      # (n, steps, B)
+        uniforms = uniforms.permute(1, 2, 0).reshape(steps, B * n)
+        was_training = self.gpt.training
+        self.gpt.eval()
+        try:
+            tokens, logp = self.gpt.generate_masked(start, known, resample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                                    uniforms=uniforms)
+        finally:
+            self.gpt.train(was_training)
+        scores = logp.double().sum(1).reshape(B, n)
+        best = torch.from_numpy(np.argmax(scores.cpu().numpy(), axis=1)).to(self.device)      # the read of the ranking; first maximum
+        candidates = tokens.reshape(B, n, T)
+        best_ids = candidates[torch.arange(B, device=self.device), best]
+        cellmask = torch.from_numpy(cells.astype(np.uint8)).to(self.device)
+        out = {"ids": best_ids, "source_ids": ids, "candidates": candidates, "scores": scores, "best": best, "cellmask": cellmask,
+               "recon": self.vqgan.decode_from_ids(ids, self.h, self.w), "edit": self.vqgan.decode_from_ids(best_ids, self.h, self.w)}
+        if has_image:
+            out["composite"] = ops.paste_cells(image, out["edit"], cellmask)
+        return out
