@@ -737,6 +737,33 @@ int vqw_causal_attention_bwd(const float* q, const float* k, const float* v, con
                              float* d_ws, float* gq, float* gk, float* gv, int B, int Tq, int Tk, int n_head, int hs, float scale,
                              int causal, int n_unmasked, void* stream);
 
+/* ---- dropout of the GPT prior (networks/mingpt.py:83, :88, :104, :189).  Added functions only; the ABI stays 9.
+ * Counter-based: whether an element is kept is a pure integer function of (seed, call, site, element index) - csrc/dropout.h
+ * holds it, tests/dropout_ref.py restates it - generated in registers where it is used and never stored; a kept element is
+ * multiplied by float32(1 / (1 - p)), keep iff the element's 32-bit draw >= round(p 2^32).  0 <= p < 1, anything else is refused.
+ * The element index of these sites is the linear index into the dense tensor.  n >= 1, tensors 16-byte aligned.
+ * vqw_dropout: y = drop(x); its backward is the same call on the gradient.  vqw_add_dropout: y = a + drop(b) in one pass; the
+ * gradient of a is gy, that of b is vqw_dropout(gy) under the same key.  y may be x (or a, or b). */
+int vqw_dropout(const float* x, float* y, long n, float p, long seed, long call, int site, void* stream);
+int vqw_add_dropout(const float* a, const float* b, float* y, long n, float p, long seed, long call, int site, void* stream);
+/* The keep masks themselves as bytes (1 = kept), through the same device function: out [n] of an element-wise site, out
+ * [B][n_head][Tq][Tk] of an attention site (element (b n_head + h, i, j)).  For tests and for looking at a mask: nothing on the
+ * training path calls them. */
+int vqw_dropout_mask(unsigned char* out, long n, float p, long seed, long call, int site, void* stream);
+int vqw_attention_dropout_mask(unsigned char* out, int B, int n_head, int Tq, int Tk, float p, long seed, long call, int site,
+                               void* stream);
+/* vqw_causal_attention_fwd / _bwd with dropout on the probabilities (mingpt.py:83): o = (softmax(.) o M) v with M = keep / (1 - p)
+ * of element (b n_head + h, i, j), the mask regenerated in the forward and in both backward kernels from the logical position.
+ * Same contract and argument checks as the functions above; in addition Tq == Tk is needed with causal = 0 too (the layer_past
+ * route is inference only) and 0 <= p < 1.  lse is that of the undropped probabilities: the same bits as without dropout.
+ * Backward: D = sum_c go o as before; gv = (P o M)^T go, dS = scale P o (M o (go v^T) - D). */
+int vqw_causal_attention_drop_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int Tq, int Tk,
+                                  int n_head, int hs, float scale, int causal, int n_unmasked, float p, long seed, long call, int site,
+                                  void* stream);
+int vqw_causal_attention_drop_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
+                                  float* d_ws, float* gq, float* gk, float* gv, int B, int Tq, int Tk, int n_head, int hs, float scale,
+                                  int causal, int n_unmasked, float p, long seed, long call, int site, void* stream);
+
 /* ---- the GPT code prior around the blocks (networks/mingpt.py:122-224 GPT).  Added functions only; the ABI stays 9.  fp32, dense,
  * no float atomics: every sum has a fixed order, the same bits every run.
  * Embedding: x[b][t] = (t < Te ? prefix[b][t] : tok[idx[b][t - Te]]) + pos[t0 + t], T = Te + Ti.  idx [B][Ti] (torch.long),

@@ -1,7 +1,8 @@
 // Softmax attention, forward and backward, for the two layouts of the library: the VQGAN's single-head self-attention over a
 // feature map (networks/vqgan.py: AttnBlock :125-180) and the minGPT's multi-head attention with a causal mask and an unmasked
 // prefix (networks/mingpt.py: CausalSelfAttention :34-90).  fp32.  One tile engine serves both; what differs between them is
-// held by two compile-time policies (below), never by a run-time branch on the caller.
+// held by two compile-time policies (below), never by a run-time branch on the caller.  A third policy adds dropout on the
+// probabilities (mingpt.py:83) to the causal kernels: the instantiations without it are the code they were before it existed.
 //
 // o = softmax(scale q k^T) v.  All five matrix products (q k^T and p v forward; recomputed q k^T, dO v^T, dS k, dS^T q and
 // p^T dO backward) are one of two forms on the exact-fp32 32x32x2 MFMA:
@@ -22,6 +23,7 @@
 #include <type_traits>
 #include "common.h"
 #include "mfma_util.h"
+#include "dropout.h"
 #include "../../include/vqwnet_hip.h"
 
 #define AT_BM 32           // tile rows a workgroup owns
@@ -113,6 +115,32 @@ struct AtCausal {
     }
 };
 
+// --------------------------------------------------------------------------------------------------------- dropout policies
+// Dropout on the probabilities, between the softmax and the P . V product: o = (P o M) v with M = keep / (1 - p).  The mask is the
+// counter-based one of dropout.h at the LOGICAL position of a probability - index hi = (b n_head + h) Tq + i, lo = j - so that
+// the three kernels, which meet an element in different tile orientations, regenerate the same mask and nothing is stored.
+// A query row's two key words are made once per row: by the row's thread (forward) or into the row / column vector in LDS
+// beside lse and D (backward); an element then costs the nine vector instructions dropout.h counts and the multiply by M.
+// AtNoDrop is empty and every use of a policy sits behind `if constexpr (DP::ON)`: no run-time flag reaches the element-wise
+// stage (at_gemm_nt's comment says what one costs).  A kernel takes the policy as a trailing parameter PACK: without dropout the
+// pack is empty and the kernel's argument list - its kernarg segment and the loads in front of its body - is the one it had.
+struct AtNoDrop {
+    static constexpr bool ON = false;
+};
+struct AtDrop {
+    static constexpr bool ON = true;
+    DropKey key;
+    __device__ __forceinline__ void row(int Tq, int i, uint32_t& r0, uint32_t& r1) const {
+        dk_row(key, dk_attn_hi(blockIdx.y, (uint32_t)Tq, (uint32_t)i), r0, r1);
+    }
+    // M of key j in the row of (r0, r1)
+    __device__ __forceinline__ float m(uint32_t r0, uint32_t r1, int j) const { return dk_keep_row(key, r0, r1, (uint32_t)j) ? key.scale : 0.f; }
+};
+__device__ __forceinline__ AtNoDrop at_policy() { return {}; }
+__device__ __forceinline__ const AtDrop& at_policy(const AtDrop& dp) { return dp; }
+#define AT_VEC_R0 (2 * AT_BN)          // the backward's vector: lse, D, then the queries' two key words (drop policy only)
+#define AT_VEC_R1 (3 * AT_BN)
+
 // --------------------------------------------------------------------------------------------------------- the tile engine
 // rows [row0, row0 + R) x columns [c0, c0 + wt) of src (row stride ld) -> dst [R][sld]; rows at or past n_rows are zeros
 template <class G>
@@ -190,7 +218,10 @@ __device__ __forceinline__ float at_score(const float* T, int row, int col) {   
 // eight threads; P0 = exp(s - m); returns this step's rescale of what the row has accumulated.  Every row - a padding row of
 // the last tile too - sees key 0, so m is finite after the first step, and a masked entry (s = -inf) gives exp(-inf - m) = 0
 // exactly.  (Selecting the constant 0 for it instead gives the same bits and cost every forward about 1 %, measured.)
-__device__ __forceinline__ float at_softmax_step(const AtLds& L, int j0, int lim, float scale, float& m, float& l) {
+// Drop policy: m and l come from the undropped p - lse does not know of the dropout - and P0 = p M, the row's key words in (r0, r1).
+template <class DP>
+__device__ __forceinline__ float at_softmax_step(const AtLds& L, int j0, int lim, float scale, float& m, float& l, const DP& dp, uint32_t r0,
+                                                 uint32_t r1) {
     const int row = AT_EW_ROW;
     float s[8], mt = -INFINITY;
 #pragma unroll
@@ -203,7 +234,8 @@ __device__ __forceinline__ float at_softmax_step(const AtLds& L, int j0, int lim
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const float p = expf(s[e] - mn);
-        L.P0[row * AT_LDS + AT_EW_COL(e)] = p;
+        if constexpr (DP::ON) L.P0[row * AT_LDS + AT_EW_COL(e)] = p * dp.m(r0, r1, j0 + AT_EW_COL(e));
+        else L.P0[row * AT_LDS + AT_EW_COL(e)] = p;
         ps += p;
     }
     const float a = expf(m - mn);
@@ -215,8 +247,10 @@ __device__ __forceinline__ float at_softmax_step(const AtLds& L, int j0, int lim
 // The backward's element-wise stage on T0 = (q k^T or k q^T) and T1 = (dO v^T or v dO^T): P = exp(scale S - lse) -> P0 (if
 // wanted), dS = scale P (dP - D) -> P1 where the query exists and sees the key, 0 elsewhere.  lse / D are indexed by the QUERY:
 // the tile row (ROWS_ARE_QUERIES) or column.  vec: lse at [0, 64), D at [64, 128) of the tile's query range.
-template <bool ROWS_ARE_QUERIES, class G>
-__device__ __forceinline__ void at_bwd_stage(const AtLds& L, const float* vec, int r0, int c0, const G& g, float scale, bool want_p) {
+// Drop policy, M the mask of (query, key) from the query's key words at [128, 256) of vec: P0 = P o M (what dV multiplies),
+// dS = scale P (M dP - D).
+template <bool ROWS_ARE_QUERIES, class G, class DP>
+__device__ __forceinline__ void at_bwd_stage(const AtLds& L, const float* vec, int r0, int c0, const G& g, float scale, bool want_p, const DP& dp) {
     const int row = AT_EW_ROW;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -224,20 +258,32 @@ __device__ __forceinline__ void at_bwd_stage(const AtLds& L, const float* vec, i
         const int iq = ROWS_ARE_QUERIES ? r0 + row : c0 + col, jk = ROWS_ARE_QUERIES ? c0 + col : r0 + row;
         const bool ok = iq < g.Tq() && jk <= g.limit(iq);
         const float sc = scale * at_score(L.T0, row, col);
-        const float dp = at_score(L.T1, row, col);
+        const float dpv = at_score(L.T1, row, col);
         const float p = ok ? expf(sc - vec[qi]) : 0.f;
-        if (want_p) L.P0[row * AT_LDS + col] = p;
-        L.P1[row * AT_LDS + col] = ok ? scale * p * (dp - vec[AT_BN + qi]) : 0.f;
+        if constexpr (DP::ON) {
+            const uint32_t* kw = (const uint32_t*)vec;
+            const float mk = dp.m(kw[AT_VEC_R0 + qi], kw[AT_VEC_R1 + qi], jk);
+            if (want_p) L.P0[row * AT_LDS + col] = p * mk;
+            L.P1[row * AT_LDS + col] = ok ? scale * p * (mk * dpv - vec[AT_BN + qi]) : 0.f;
+        } else {
+            if (want_p) L.P0[row * AT_LDS + col] = p;
+            L.P1[row * AT_LDS + col] = ok ? scale * p * (dpv - vec[AT_BN + qi]) : 0.f;
+        }
     }
     __syncthreads();
 }
 
-// vec <- lse | D of the n queries from i0 (zeros past T)
-__device__ __forceinline__ void at_load_vec(float* vec, const float* __restrict__ lse, const float* __restrict__ D, int i0, int n, int T) {
+// vec <- lse | D of the n queries from i0 (zeros past T); drop policy: and the queries' key words
+template <class DP>
+__device__ __forceinline__ void at_load_vec(float* vec, const float* __restrict__ lse, const float* __restrict__ D, int i0, int n, int T, const DP& dp) {
     if (threadIdx.x < n) {
         const bool ok = i0 + threadIdx.x < T;
         vec[threadIdx.x] = ok ? lse[i0 + threadIdx.x] : 0.f;
         vec[AT_BN + threadIdx.x] = ok ? D[i0 + threadIdx.x] : 0.f;
+        if constexpr (DP::ON) {
+            uint32_t* kw = (uint32_t*)vec;
+            dp.row(T, i0 + threadIdx.x, kw[AT_VEC_R0 + threadIdx.x], kw[AT_VEC_R1 + threadIdx.x]);
+        }
     }
 }
 
@@ -368,10 +414,12 @@ struct AtKeySplits {
 // ------------------------------------------------------------------------------------------------------------- the kernels
 // grid (ceil(Tq / 32), batch x heads, column windows).  o and lse [batch x heads][Tq] of a tile of 32 queries, over the key
 // steps up to the tile's largest limit.  A single-chunk geometry re-uses the staged q tile after the first step.
-template <class G, class VO>
+template <class G, class VO, class... DPs>
 __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                  float* __restrict__ o, float* __restrict__ lse, G g, float scale) {
+                                                  float* __restrict__ o, float* __restrict__ lse, G g, float scale, DPs... dps) {
     extern __shared__ __align__(16) float lds[];
+    const auto dp = at_policy(dps...);
+    using DP = std::remove_cv_t<decltype(dp)>;
     const AtLds L(lds, g.lds_ld());
     const int Tq = g.Tq(), Tk = g.Tk(), W = g.width(), ld = g.ld();
     q += g.base(Tq); o += g.base(Tq); k += g.base(Tk); v += g.base(Tk);
@@ -382,9 +430,11 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ q, c
     float m = -INFINITY, l = 0.f;
     const int row = AT_EW_ROW;
     const int lim = g.limit(i0 + row), jmax = g.last_key(i0);
+    uint32_t r0 = 0, r1 = 0;     // drop policy: the key words of this thread's query row
+    if constexpr (DP::ON) dp.row(Tq, i0 + row, r0, r1);
     for (int j0 = 0; j0 <= jmax; j0 += AT_BN) {
         at_gemm_nt<G>(L, L.T0, q, i0, Tq, k, j0, Tk, W, ld, j0 == 0);
-        const float a = at_softmax_step(L, j0, lim, scale, m, l);
+        const float a = at_softmax_step(L, j0, lim, scale, m, l, dp, r0, r1);
         if ((threadIdx.x & 7) == 0) alpha[row] = a;
         __syncthreads();
         acc.rescale(alpha);
@@ -416,11 +466,12 @@ __global__ void __launch_bounds__(256) k_attn_rowdot(const float* __restrict__ a
 }
 
 // same grid: dQ = scale (P o (dO v^T - D)) k for a tile of 32 queries, over the key steps the forward walked
-template <class G, class VO>
+template <class G, class VO, class... DPs>
 __global__ void __launch_bounds__(256) k_attn_dq(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                  const float* __restrict__ go, const float* __restrict__ lse, const float* __restrict__ D,
-                                                 float* __restrict__ gq, G g, float scale) {
+                                                 float* __restrict__ gq, G g, float scale, DPs... dps) {
     extern __shared__ __align__(16) float lds[];
+    const auto dp = at_policy(dps...);
     const AtLds L(lds, g.lds_ld());
     const int T = g.Tq(), W = g.width(), ld = g.ld();
     const long off = g.base(T);
@@ -428,14 +479,14 @@ __global__ void __launch_bounds__(256) k_attn_dq(const float* __restrict__ q, co
     lse += (long)blockIdx.y * T; D += (long)blockIdx.y * T;
     const int i0 = blockIdx.x * AT_BM;
     float* vec = L.V;
-    at_load_vec(vec, lse, D, i0, AT_BM, T);
+    at_load_vec(vec, lse, D, i0, AT_BM, T, dp);
     VO acc;
     acc.zero();
     const int jmax = g.last_key(i0);
     for (int j0 = 0; j0 <= jmax; j0 += AT_BN) {
         at_gemm_nt<G>(L, L.T0, q, i0, T, k, j0, T, W, ld, true);
         at_gemm_nt<G>(L, L.T1, go, i0, T, v, j0, T, W, ld, true);
-        at_bwd_stage<true>(L, vec, i0, j0, g, scale, false);
+        at_bwd_stage<true>(L, vec, i0, j0, g, scale, false, dp);
         acc.template pv<G>(L, L.P1, k, j0, T, W, ld);
     }
     acc.store(L, gq, i0, T, W, ld, [](int) { return 1.f; });
@@ -443,11 +494,12 @@ __global__ void __launch_bounds__(256) k_attn_dq(const float* __restrict__ q, co
 
 // same grid: dK = scale (P o (dO v^T - D))^T q and dV = P^T dO for a tile of 32 keys, over the query steps from the first one
 // that sees one of its keys
-template <class G, class VO>
+template <class G, class VO, class... DPs>
 __global__ void __launch_bounds__(256) k_attn_dkdv(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                    const float* __restrict__ go, const float* __restrict__ lse, const float* __restrict__ D,
-                                                   float* __restrict__ gk, float* __restrict__ gv, G g, float scale) {
+                                                   float* __restrict__ gk, float* __restrict__ gv, G g, float scale, DPs... dps) {
     extern __shared__ __align__(16) float lds[];
+    const auto dp = at_policy(dps...);
     const AtLds L(lds, g.lds_ld());
     const int T = g.Tq(), W = g.width(), ld = g.ld();
     const long off = g.base(T);
@@ -460,10 +512,10 @@ __global__ void __launch_bounds__(256) k_attn_dkdv(const float* __restrict__ q, 
     av.zero();
     for (int i0 = g.first_query(j0); i0 < T; i0 += AT_BN) {
         __syncthreads();                      // the previous step's readers of vec are done
-        at_load_vec(vec, lse, D, i0, AT_BN, T);
+        at_load_vec(vec, lse, D, i0, AT_BN, T, dp);
         at_gemm_nt<G>(L, L.T0, k, j0, T, q, i0, T, W, ld, true);
         at_gemm_nt<G>(L, L.T1, v, j0, T, go, i0, T, W, ld, true);
-        at_bwd_stage<false>(L, vec, j0, i0, g, scale, true);
+        at_bwd_stage<false>(L, vec, j0, i0, g, scale, true, dp);
         av.template pv<G>(L, L.P0, go, i0, T, W, ld);
         ak.template pv<G>(L, L.P1, q, i0, T, W, ld);
     }
@@ -473,22 +525,22 @@ __global__ void __launch_bounds__(256) k_attn_dkdv(const float* __restrict__ q, 
 
 // ---------------------------------------------------------------------------------------------------------------- the host
 // lds_max: the largest request of this instantiation (the opt-in is made once), lds: this launch's
-template <class G, class VO>
+template <class G, class VO, class... DPs>
 static int at_fwd_launch(const char* name, const G& g, dim3 grid, int lds_max, int lds, const float* q, const float* k, const float* v, float* o,
-                         float* lse, float scale, hipStream_t st) {
-    if (int rc = lds_opt_in<k_attn_fwd<G, VO>>(lds_max, name)) return rc;
-    hipLaunchKernelGGL((k_attn_fwd<G, VO>), grid, dim3(256), lds, st, q, k, v, o, lse, g, scale);
+                         float* lse, float scale, hipStream_t st, DPs... dps) {
+    if (int rc = lds_opt_in<k_attn_fwd<G, VO, DPs...>>(lds_max, name)) return rc;
+    hipLaunchKernelGGL((k_attn_fwd<G, VO, DPs...>), grid, dim3(256), lds, st, q, k, v, o, lse, g, scale, dps...);
     return VQW_OK;
 }
-template <class G, class VO>
+template <class G, class VO, class... DPs>
 static int at_bwd_launch(const char* name, const G& g, dim3 grid, int lds_max, int lds, long segments, const float* q, const float* k,
                          const float* v, const float* o, const float* go, const float* lse, float* D, float* gq, float* gk, float* gv, float scale,
-                         hipStream_t st) {
-    if (int rc = lds_opt_in<k_attn_dq<G, VO>>(lds_max, name)) return rc;
-    if (int rc = lds_opt_in<k_attn_dkdv<G, VO>>(lds_max, name)) return rc;
+                         hipStream_t st, DPs... dps) {
+    if (int rc = lds_opt_in<k_attn_dq<G, VO, DPs...>>(lds_max, name)) return rc;
+    if (int rc = lds_opt_in<k_attn_dkdv<G, VO, DPs...>>(lds_max, name)) return rc;
     hipLaunchKernelGGL((k_attn_rowdot<typename G::RowDot>), dim3(ceil_div(segments, 4)), dim3(256), 0, st, go, o, D, segments, g.rowdot());
-    hipLaunchKernelGGL((k_attn_dq<G, VO>), grid, dim3(256), lds, st, q, k, v, go, lse, D, gq, g, scale);
-    hipLaunchKernelGGL((k_attn_dkdv<G, VO>), grid, dim3(256), lds, st, q, k, v, go, lse, D, gk, gv, g, scale);
+    hipLaunchKernelGGL((k_attn_dq<G, VO, DPs...>), grid, dim3(256), lds, st, q, k, v, go, lse, D, gq, g, scale, dps...);
+    hipLaunchKernelGGL((k_attn_dkdv<G, VO, DPs...>), grid, dim3(256), lds, st, q, k, v, go, lse, D, gk, gv, g, scale, dps...);
     return VQW_OK;
 }
 
@@ -587,5 +639,46 @@ extern "C" int vqw_causal_attention_bwd(const float* q, const float* k, const fl
                                                       lse, d_ws, gq, gk, gv, scale, (hipStream_t)stream))
         return rc;
     VQW_LAUNCH_CHECK("vqw_causal_attention_bwd");
+    return VQW_OK;
+}
+
+// ---- the same two passes with dropout on the probabilities (the drop policy): the contract and the checks of the functions above
+static int at_drop_check(const char* name, int Tq, int Tk, float p) {
+    VQW_CHECK(Tq == Tk, "%s: dropout needs Tq == Tk (got Tq=%d, Tk=%d): the layer_past route is inference only", name, Tq, Tk);
+    VQW_CHECK(p >= 0.f && p < 1.f, "%s: p=%g must lie in [0, 1)", name, (double)p);
+    return VQW_OK;
+}
+
+extern "C" int vqw_causal_attention_drop_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int Tq, int Tk,
+                                             int n_head, int hs, float scale, int causal, int n_unmasked, float p, long seed, long call,
+                                             int site, void* stream) {
+    if (int rc = at_causal_check("vqw_causal_attention_drop_fwd", B, Tq, Tk, n_head, hs, causal, n_unmasked)) return rc;
+    if (int rc = at_drop_check("vqw_causal_attention_drop_fwd", Tq, Tk, p)) return rc;
+    VQW_CHECK(q && k && v && o && lse, "vqw_causal_attention_drop_fwd: null pointer");
+    VQW_CHECK(al16(q) && al16(k) && al16(v) && al16(o), "vqw_causal_attention_drop_fwd: tensors must be 16-byte aligned");
+    const AtCausal g{Tq, Tk, n_head, hs, causal ? 1 : 0, n_unmasked};
+    if (int rc = at_fwd_launch<AtCausal, AtKeySplits, AtDrop>("vqw_causal_attention_drop_fwd", g, dim3(ceil_div(Tq, AT_BM), B * n_head),
+                                                              at_lds_bytes(AT_KC + 4, false), at_lds_bytes(hs + 4, false), q, k, v, o, lse, scale,
+                                                              (hipStream_t)stream, AtDrop{dk_make(p, seed, call, site)}))
+        return rc;
+    VQW_LAUNCH_CHECK("vqw_causal_attention_drop_fwd");
+    return VQW_OK;
+}
+
+extern "C" int vqw_causal_attention_drop_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
+                                             float* d_ws, float* gq, float* gk, float* gv, int B, int Tq, int Tk, int n_head, int hs, float scale,
+                                             int causal, int n_unmasked, float p, long seed, long call, int site, void* stream) {
+    if (int rc = at_causal_check("vqw_causal_attention_drop_bwd", B, Tq, Tk, n_head, hs, causal, n_unmasked)) return rc;
+    if (int rc = at_drop_check("vqw_causal_attention_drop_bwd", Tq, Tk, p)) return rc;
+    VQW_CHECK(q && k && v && o && lse && go && d_ws && gq && gk && gv, "vqw_causal_attention_drop_bwd: null pointer");
+    VQW_CHECK(al16(q) && al16(k) && al16(v) && al16(o) && al16(go) && al16(gq) && al16(gk) && al16(gv),
+              "vqw_causal_attention_drop_bwd: tensors must be 16-byte aligned");
+    const AtCausal g{Tq, Tk, n_head, hs, causal ? 1 : 0, n_unmasked};
+    if (int rc = at_bwd_launch<AtCausal, AtKeySplits, AtDrop>("vqw_causal_attention_drop_bwd", g, dim3(ceil_div(Tq, AT_BM), B * n_head),
+                                                              at_lds_bytes(AT_KC + 4, true), at_lds_bytes(hs + 4, true), (long)B * Tq * n_head, q, k, v,
+                                                              o, go, lse, d_ws, gq, gk, gv, scale, (hipStream_t)stream,
+                                                              AtDrop{dk_make(p, seed, call, site)}))
+        return rc;
+    VQW_LAUNCH_CHECK("vqw_causal_attention_drop_bwd");
     return VQW_OK;
 }

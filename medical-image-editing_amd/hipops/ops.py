@@ -1687,18 +1687,134 @@ class _CausalAttention(torch.autograd.Function):
         return gq, gk, gv, None, None, None
 
 
-def causal_attention(q, k, v, n_head, n_unmasked=0, causal=True):
+class _CausalAttentionDrop(torch.autograd.Function):
+    """_CausalAttention with dropout on the probabilities: the same five tensors saved, the mask regenerated from (p, key)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, n_head, n_unmasked, causal, p, key):
+        _dev(q, k, v)
+        q, k, v = _flat(q), _flat(k), _flat(v)
+        B, Tq, Tk, hs, scale, causal, nu = ctx.cfg = _heads(q, k, v, n_head, n_unmasked, causal)
+        o = torch.empty_like(q)
+        lse = torch.empty(B, n_head, Tq, dtype=torch.float32, device=q.device)
+        _L().vqw_causal_attention_drop_fwd(q, k, v, o, lse, B, Tq, Tk, n_head, hs, scale, causal, nu, p, *key)
+        ctx.n_head, ctx.p, ctx.key = n_head, p, key
+        ctx.save_for_backward(q, k, v, o, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, o, lse = ctx.saved_tensors
+        B, Tq, Tk, hs, scale, causal, nu = ctx.cfg
+        go = _flat(go)
+        gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        d = torch.empty_like(lse)
+        _L().vqw_causal_attention_drop_bwd(q, k, v, o, lse, go, d, gq, gk, gv, B, Tq, Tk, ctx.n_head, hs, scale, causal, nu, ctx.p, *ctx.key)
+        return gq, gk, gv, None, None, None, None, None
+
+
+def causal_attention(q, k, v, n_head, n_unmasked=0, causal=True, dropout_p=0.0, dropout_key=None):
     """softmax(q k^T / sqrt(hs)) v per head on q (B, Tq, E), k, v (B, Tk, E), E = n_head hs, the heads side by side in the last
     axis (what three nn.Linear projections leave); returns (B, Tq, E).  causal=True (Tq == Tk): query i sees key j iff
     j <= (i < n_unmasked ? n_unmasked - 1 : i) - the reference's tril mask with an all-ones n_unmasked x n_unmasked corner
-    (mingpt.py:53-56).  causal=False: no mask, Tq != Tk allowed, forward only (the layer_past route, mingpt.py:71-80)."""
-    return _CausalAttention.apply(q, k, v, int(n_head), int(n_unmasked), bool(causal))
+    (mingpt.py:53-56).  causal=False: no mask, Tq != Tk allowed, forward only (the layer_past route, mingpt.py:71-80).
+    dropout_p > 0 with dropout_key = (seed, call, site): dropout on the probabilities (mingpt.py:83) inside the kernels, the mask
+    of element (b n_head + h, i, j) regenerated in the backward (Tq == Tk); dropout_p == 0 or no key: the path without it."""
+    if dropout_key is None or dropout_p == 0:
+        return _CausalAttention.apply(q, k, v, int(n_head), int(n_unmasked), bool(causal))
+    return _CausalAttentionDrop.apply(q, k, v, int(n_head), int(n_unmasked), bool(causal), _drop_p(dropout_p), _drop_key(dropout_key))
 
 
 def causal_attention_lse(q, k, v, n_head, n_unmasked=0, causal=True):
     """(output, row log-sum-exp [B, n_head, Tq]) of causal_attention without a tape: for tests and measurement."""
     _, _, _, o, lse, _ = _causal_attention_fwd(q, k, v, int(n_head), int(n_unmasked), bool(causal))
     return o, lse
+
+
+# ----------------------------------------------------------------------------------------------
+# dropout of the GPT prior: counter-based masks (csrc/dropout.h), key = (seed, call, site), nothing saved but the key
+# ----------------------------------------------------------------------------------------------
+def _drop_p(p):
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout: p=%r must lie in [0, 1)" % (p,))
+    return p
+
+
+def _drop_key(key):
+    seed, call, site = (int(v) for v in key)
+    if not (-2 ** 63 <= seed < 2 ** 63 and -2 ** 63 <= call < 2 ** 63 and -2 ** 31 <= site < 2 ** 31):
+        raise ValueError("dropout: key (seed, call, site) = %r does not fit (long, long, int)" % ((seed, call, site),))
+    return seed, call, site
+
+
+class _Dropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, key):
+        _dev(x)
+        x = _flat(x)
+        y = torch.empty_like(x)
+        _L().vqw_dropout(x, y, x.numel(), p, *key)
+        ctx.p, ctx.key = p, key
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        gy = _flat(gy)
+        gx = torch.empty_like(gy)
+        _L().vqw_dropout(gy, gx, gy.numel(), ctx.p, *ctx.key)          # dropout is linear: the same launch on the gradient
+        return gx, None, None
+
+
+class _AddDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, p, key):
+        _dev(a, b)
+        a, b = _flat(a), _flat(b)
+        if a.shape != b.shape:
+            raise RuntimeError("add_dropout: shape mismatch %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+        y = torch.empty_like(a)
+        _L().vqw_add_dropout(a, b, y, a.numel(), p, *key)
+        ctx.p, ctx.key = p, key
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        gb = None
+        if ctx.needs_input_grad[1]:
+            gy = _flat(gy)
+            gb = torch.empty_like(gy)
+            _L().vqw_dropout(gy, gb, gy.numel(), ctx.p, *ctx.key)
+        return gy, gb, None, None
+
+
+def dropout(x, p, key):
+    """Training-mode nn.Dropout(p)(x) on a dense fp32 tensor under key = (seed, call, site) (Python ints): element e (the linear
+    index) is kept iff its draw of csrc/dropout.h is >= round(p 2^32), a kept element is multiplied by float32(1 / (1 - p)).  The
+    backward regenerates the mask from the key: nothing is saved."""
+    return _Dropout.apply(x, _drop_p(p), _drop_key(key))
+
+
+def add_dropout(a, b, p, key):
+    """a + dropout(b, p, key) in one pass over dense fp32 tensors of one shape."""
+    return _AddDropout.apply(a, b, _drop_p(p), _drop_key(key))
+
+
+def dropout_keep_mask(n, p, key, device="cuda"):
+    """The keep mask (n,) torch.bool of an element-wise site, written by the device function the kernels use: for tests and for
+    looking at a mask."""
+    out = torch.empty(int(n), dtype=torch.uint8, device=device)
+    _dev(out)
+    _L().vqw_dropout_mask(out, int(n), _drop_p(p), *_drop_key(key))
+    return out.bool()
+
+
+def attention_keep_mask(B, n_head, Tq, Tk, p, key, device="cuda"):
+    """The keep mask (B, n_head, Tq, Tk) torch.bool of an attention site (ops.causal_attention's dropout_key)."""
+    out = torch.empty(int(B), int(n_head), int(Tq), int(Tk), dtype=torch.uint8, device=device)
+    _dev(out)
+    _L().vqw_attention_dropout_mask(out, int(B), int(n_head), int(Tq), int(Tk), _drop_p(p), *_drop_key(key))
+    return out.bool()
 
 
 # ----------------------------------------------------------------------------------------------

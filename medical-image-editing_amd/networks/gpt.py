@@ -6,8 +6,12 @@ a seed gives the reference's initial values and a reference checkpoint loads wit
 position embedding, with the reference's optional `embeddings=` prefix), the blocks, ops.layer_norm and ops.linear without bias; the
 loss of the prior is ops.cross_entropy, a token is drawn by ops.sample_topk.
 
-Dropout: `drop` exists (the trees match); at p = 0 or in eval mode it is the identity.  A training forward with emb_pdrop,
-res_pdrop or att_pdrop above 0 raises NotImplementedError before any kernel runs; there is no dropout kernel.
+Dropout: `drop` exists (the trees match); at p = 0 or in eval mode it is the identity.  GPT.seed_dropout(seed, call=0) numbers the
+sites of the tree - 0 is `drop`, then per block att_drop, att.res_drop, mlp[3] - and stores seed and call; a training forward of a
+seeded model runs ops.dropout behind the embedding, the attention kernels' dropout policy and ops.add_dropout in the residual
+adds under (seed, call, site) and then advances call by one; GPT.set_dropout_call(n) sets it (networks/mingpt.py, csrc/dropout.h:
+counter-based masks, nothing stored).  A training forward with emb_pdrop, res_pdrop or att_pdrop above 0 on a model that has not
+been seeded raises NotImplementedError before any kernel runs.
 
 GPT.forward_with_past.  The reference's body cannot run (`present.append(present)`, mingpt.py:219); what it evidently means is
 built: `presents.append(present)`, returning (logits, torch.stack(presents)) of shape (n_layer, 2, B, n_head, T, hs).  With a
@@ -34,10 +38,10 @@ import torch.nn as nn
 
 from hipops import ops
 
-from .mingpt import Block, GPTConfig, _no_dropout
+from .mingpt import Block, GPTConfig, SeededDropout, _no_dropout
 
 
-class GPT(nn.Module):
+class GPT(SeededDropout, nn.Module):
     """Token + position embedding, n_layer Blocks, a final LayerNorm and a bias-free head onto the vocabulary; block_size is the
     longest sequence it can see.  Submodules and parameters are created in the reference's order (mingpt.py:149-158): tok_embed,
     pos_embed, drop, blocks, ln_f, head - the random stream of a seed and the state_dict order depend on it."""
@@ -49,7 +53,7 @@ class GPT(nn.Module):
                            res_pdrop=res_pdrop, att_pdrop=att_pdrop, n_unmasked=n_unmasked)
         self.tok_embed = nn.Embedding(vocab_size, n_embed)
         self.pos_embed = nn.Parameter(torch.zeros(1, block_size, n_embed))
-        self.drop = nn.Dropout(emb_pdrop)          # identity at p = 0 or in eval mode; anything else raises in forward
+        self.drop = nn.Dropout(emb_pdrop)          # identity at p = 0 or in eval mode; in training mode the p of site 0 (seed_dropout)
         self.blocks = nn.Sequential(*(Block(config) for _ in range(n_layer)))
         self.ln_f = nn.LayerNorm(n_embed)
         self.head = nn.Linear(n_embed, vocab_size, bias=False)
@@ -79,6 +83,13 @@ class GPT(nn.Module):
             block.att._check_dropout()
             _no_dropout(block, block.mlp[3], "res_pdrop")
 
+    def _seed_sites(self, seed, site):
+        self.dropout_seed, self.dropout_site = seed, site          # `drop`
+        site += 1
+        for block in self.blocks:
+            site = block._seed_sites(seed, site)
+        return site
+
     @staticmethod
     def _new_tokens(idx, embeddings):
         return idx.shape[1] + (embeddings.shape[1] if embeddings is not None else 0)
@@ -92,10 +103,16 @@ class GPT(nn.Module):
         t = self._new_tokens(idx, embeddings)
         if t > self.block_size:
             raise RuntimeError("GPT: cannot forward T=%d tokens, the model's block_size=%d is exhausted" % (t, self.block_size))
+        call = self._dropout_call()
         x = ops.embedding(idx, self.tok_embed.weight, self.pos_embed, embeddings)          # token (or given) + position embedding
+        if call is not None and self.drop.p > 0:
+            x = ops.dropout(x, self.drop.p, self._key(call, self.dropout_site))
         for block in self.blocks:
-            x = block(x)
-        return self._head(x)
+            x = block._forward(x, None, call)[0]
+        x = self._head(x)
+        if call is not None:
+            self.set_dropout_call(call + 1)
+        return x
 
     def forward_with_past(self, idx, embeddings=None, past=None, past_length=None):
         # inference only

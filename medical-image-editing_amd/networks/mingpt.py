@@ -12,8 +12,14 @@ i)) and never reads the buffer.  n_unmasked comes from the config at constructio
 state is loaded; a loaded mask that is no tril with an all-ones u x u corner raises - nothing is computed under another mask
 than the stored one.
 
-Dropout: the three nn.Dropout members exist (the trees match); at p = 0 or in eval mode they are the identity.  A training
-forward with any p > 0 raises NotImplementedError - GPTConfig's class defaults of 0.1 included; there is no dropout kernel.
+Dropout: the three nn.Dropout members exist (the trees match) and hold the probabilities; at p = 0 or in eval mode they are the
+identity.  The masks are counter-based (csrc/dropout.h): whether an element is kept is a pure integer function of (seed, call,
+site, element index), generated inside the kernels - ops.causal_attention's dropout on the probabilities, ops.add_dropout for the
+two residual adds - and never stored.  So dropout is opt-in by seed: seed_dropout(seed, call=0) numbers the module's sites
+(att_drop, att.res_drop, mlp[3] in module-tree order) and stores seed and call; every training forward uses (seed, call, site)
+and then advances call by one, so a seed reproduces a run bit for bit and a resumed run needs nothing but the call it stopped
+at (set_dropout_call).  A training forward with any p > 0 on a module that has NOT been seeded raises NotImplementedError before
+any kernel runs - GPTConfig's class defaults of 0.1 included: an unseeded, irreproducible mask has no kernel here.
 
 The model over these blocks, the reference's GPT class (mingpt.py:122-224), is networks/gpt.py (networks.GPT).
 """
@@ -64,12 +70,43 @@ def n_unmasked_of(mask):
 
 
 def _no_dropout(module, drop, what):
-    if module.training and drop.p > 0:
+    if module.training and drop.p > 0 and getattr(module, "dropout_seed", None) is None:
         raise NotImplementedError("%s: dropout with p = %g in training mode has no kernel; build the config with %s = 0.0 "
-                                  "or call .eval()" % (type(module).__name__, drop.p, what))
+                                  "or call .eval(), or seed the dropout: seed_dropout(seed)" % (type(module).__name__, drop.p, what))
 
 
-class CausalSelfAttention(nn.Module):
+class SeededDropout:
+    """The dropout state of a module: the seed (None: not seeded), the call counter and the number of the module's first site."""
+    dropout_seed = None
+    dropout_call = 0
+    dropout_site = 0
+
+    def seed_dropout(self, seed, call=0):
+        """Seed every dropout site of this module's tree, numbered from 0 in module-tree order, and set the call counter."""
+        self._seed_sites(int(seed), 0)
+        self.set_dropout_call(call)
+        return self
+
+    def _seed_sites(self, seed, site):
+        """-> the first site number behind this module's"""
+        raise NotImplementedError
+
+    def set_dropout_call(self, n):
+        """The call the next training forward uses (a training forward advances it by one)."""
+        for m in self.modules():
+            if isinstance(m, SeededDropout):
+                m.dropout_call = int(n)
+        return self
+
+    def _dropout_call(self):
+        """The call of this forward, or None: eval mode or not seeded (then every p is 0, or _no_dropout has raised)"""
+        return self.dropout_call if self.training and self.dropout_seed is not None else None
+
+    def _key(self, call, site):
+        return (self.dropout_seed, call, site)
+
+
+class CausalSelfAttention(SeededDropout, nn.Module):
 
     def __init__(self, config):
         super().__init__()
@@ -80,7 +117,7 @@ class CausalSelfAttention(nn.Module):
         self.q = nn.Linear(config.n_embed, config.n_embed)
         self.v = nn.Linear(config.n_embed, config.n_embed)
 
-        # identity at p = 0 or in eval mode; anything else raises in forward
+        # identity at p = 0 or in eval mode; in training mode they give the probabilities of the seeded kernels (seed_dropout)
         self.att_drop = nn.Dropout(config.att_pdrop)
         self.res_drop = nn.Dropout(config.res_pdrop)
 
@@ -106,8 +143,24 @@ class CausalSelfAttention(nn.Module):
         _no_dropout(self, self.att_drop, "att_pdrop")
         _no_dropout(self, self.res_drop, "res_pdrop")
 
+    def _seed_sites(self, seed, site):
+        self.dropout_seed, self.dropout_site = seed, site          # att_drop: site, res_drop: site + 1
+        return site + 2
+
     def forward(self, x, layer_past=None):
+        """-> (res_drop(proj(attention)), present)"""
         self._check_dropout()
+        call = self._dropout_call()
+        y, present = self._attend(x, layer_past, call)
+        if call is not None:
+            if self.res_drop.p > 0:
+                y = ops.dropout(y, self.res_drop.p, self._key(call, self.dropout_site + 1))
+            self.dropout_call = call + 1
+        return y, present
+
+    def _attend(self, x, layer_past, call):
+        """(proj(attention), present) in front of res_drop - a Block applies that inside its residual add; call: the dropout call
+        of this forward or None"""
         B, T, C = x.size()
         if layer_past is None and T > self.mask.shape[-1]:
             raise RuntimeError("CausalSelfAttention: T=%d exceeds block_size=%d" % (T, self.mask.shape[-1]))
@@ -119,20 +172,23 @@ class CausalSelfAttention(nn.Module):
 
         present = torch.stack((k.view(B, T, nh, hs).transpose(1, 2), v.view(B, T, nh, hs).transpose(1, 2)))   # (2, B, nh, T, hs)
 
+        drop = dict(dropout_p=self.att_drop.p, dropout_key=self._key(call, self.dropout_site)) if call is not None else {}
         if layer_past is not None:
+            if drop and self.att_drop.p > 0:
+                raise RuntimeError("CausalSelfAttention: the layer_past route is inference only, it has no dropout (call .eval())")
             past_k, past_v = layer_past                        # (B, nh, Tp, hs) each
             k = torch.cat((past_k.transpose(1, 2).reshape(B, -1, C), k), dim=1)
             v = torch.cat((past_v.transpose(1, 2).reshape(B, -1, C), v), dim=1)
             y = ops.causal_attention(q, k, v, nh, causal=False)          # no mask on this route (mingpt.py:79-80)
         else:
             # the mask's top-left T x T window: tril with a corner of min(n_unmasked, T)
-            y = ops.causal_attention(q, k, v, nh, n_unmasked=min(self.n_unmasked, T), causal=True)
+            y = ops.causal_attention(q, k, v, nh, n_unmasked=min(self.n_unmasked, T), causal=True, **drop)
 
         y = ops.linear(y, self.proj.weight, self.proj.bias)
         return y, present
 
 
-class Block(nn.Module):
+class Block(SeededDropout, nn.Module):
     """x + att(ln1(x)), then x + mlp(ln2(x))."""
     def __init__(self, config):
         super().__init__()
@@ -156,19 +212,33 @@ class Block(nn.Module):
         """a + b through ops.add, on the (B, C, T, 1) channels-last view of the two (B, T, C) tensors: the same memory."""
         return ops.add(a.transpose(1, 2).unsqueeze(-1), b.transpose(1, 2).unsqueeze(-1)).squeeze(-1).transpose(1, 2)
 
+    def _seed_sites(self, seed, site):
+        self.dropout_seed = seed
+        self.dropout_site = self.att._seed_sites(seed, site)          # mlp[3]: the site behind the attention's two
+        return self.dropout_site + 1
+
+    def _add_drop(self, a, b, p, call, site):
+        """a + dropout(b): one pass, as _add is"""
+        if call is None or p == 0:
+            return self._add(a, b)
+        return ops.add_dropout(a, b, p, self._key(call, site))
+
     def forward(self, x, layer_past=None, return_present=False):
         if return_present:
             assert not self.training
         self.att._check_dropout()                       # before any kernel runs
         _no_dropout(self, self.mlp[3], "res_pdrop")
+        call = self._dropout_call()
+        out = self._forward(x, layer_past, call)
+        if call is not None:
+            self.set_dropout_call(call + 1)
+        return out if layer_past is not None or return_present else out[0]
 
-        att, present = self.att(ops.layer_norm(x, self.ln1.weight, self.ln1.bias, self.ln1.eps), layer_past=layer_past)
+    def _forward(self, x, layer_past, call):
+        """-> (x, present); call: the dropout call of this forward (the block's own or the model's) or None"""
+        att, present = self.att._attend(ops.layer_norm(x, self.ln1.weight, self.ln1.bias, self.ln1.eps), layer_past, call)
 
-        x = self._add(x, att)
-        x = self._add(x, self._mlp(ops.layer_norm(x, self.ln2.weight, self.ln2.bias, self.ln2.eps)))
-
-        if layer_past is not None or return_present:
-            return x, present
-
-        return x
+        x = self._add_drop(x, att, self.att.res_drop.p, call, self.att.dropout_site + 1)
+        x = self._add_drop(x, self._mlp(ops.layer_norm(x, self.ln2.weight, self.ln2.bias, self.ln2.eps)), self.mlp[3].p, call, self.dropout_site)
+        return x, present
 

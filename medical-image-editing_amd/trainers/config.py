@@ -163,20 +163,22 @@ def latent_size(config):
 
 def configure_prior(config):
     """The GPT of config.model.prior over the codes of config.model.vqgan: vocab_size = the VQGAN's dict_size, block_size = the
-    latent's h w (model.prior.block_size, if given, overrides it), every dropout probability 0 (a JSON `false` / absent
-    n_unmasked, like 0, means the plain causal mask)."""
+    latent's h w (model.prior.block_size, if given, overrides it); the optional model.prior.{emb_pdrop, res_pdrop, att_pdrop} are
+    the dropout probabilities, absent or `false` meaning 0 (a JSON `false` / absent n_unmasked, like 0, means the plain causal
+    mask).  build_prior_trainer seeds the dropout from run.seed."""
     from networks import GPT
     p = config.model.prior
     side = latent_size(config)
     return GPT(vocab_size=config.model.vqgan.dict_size, block_size=int(_get(p, "block_size") or side * side), n_layer=p.n_layer,
-               n_head=p.n_head, n_embed=p.n_embed, n_unmasked=int(p.n_unmasked or 0))
+               n_head=p.n_head, n_embed=p.n_embed, n_unmasked=int(p.n_unmasked or 0),
+               **{k: float(_get(p, k) or 0.0) for k in ("emb_pdrop", "res_pdrop", "att_pdrop")})
 
 
 def build_prior_trainer(config, device="cuda", first_stage_ckpt_path=None):
     """config -> PriorTrainer (run_vqwnet.py -p): the GPT of model.prior trained on the codes of the frozen VQGAN of model.vqgan.
     first_stage_ckpt_path (argument, else run.first_stage_ckpt_path) loads a -v checkpoint's `decoder.*` keys into the VQGAN, as
     build_vqgan_trainer does.  A JSON `false` for pkeep, sos_token, warmup_steps or decay_steps arrives as None: pkeep then means
-    1 (no corruption), the others 0."""
+    1 (no corruption), the others 0.  run.seed seeds the trainer's generator and the prior's dropout (model.prior.*_pdrop)."""
     from .prior import PriorTrainer
     check_prior_config(config)
     vqgan, gpt = configure_vqgan(config), configure_prior(config)
@@ -187,7 +189,7 @@ def build_prior_trainer(config, device="cuda", first_stage_ckpt_path=None):
     return PriorTrainer(vqgan, gpt, pkeep=1.0 if p.pkeep is None else p.pkeep, sos_token=int(p.sos_token or 0), lr=o.lr,
                         betas=(o.b1, o.b2), weight_decay=o.weight_decay or 0.0, grad_norm_clip=o.grad_norm_clip or None,
                         warmup_steps=int(o.warmup_steps or 0), decay_steps=int(o.decay_steps or 0),
-                        seed=int(_get(config.run, "seed", 0) or 0), device=device)
+                        seed=int(_get(config.run, "seed", 0) or 0), dropout_seed=int(_get(config.run, "seed", 0) or 0), device=device)
 
 
 def configure_discriminator(config):

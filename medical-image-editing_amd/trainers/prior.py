@@ -1,18 +1,23 @@
 """Training the GPT code prior on the codes of a frozen VQGAN (the launcher's -p).  The reference has no trainer for its
 networks.GPT; the recipe is minGPT's and taming-transformers': AdamW over decay / no-decay parameter groups, gradient clipping by
 the global norm, linear warm-up and cosine decay of the learning rate, teacher forcing behind a start token, and `pkeep` token
-corruption as the regulariser (training-mode dropout has no kernel: a GPT with a dropout probability above 0 is refused here).
+corruption and, when asked for, dropout as the regularisers.  Dropout is opt-in by seed: `dropout_seed` seeds the GPT's
+counter-based masks (GPT.seed_dropout) and every step sets the dropout call to the step counter, so the masks of step n are a
+function of (dropout_seed, n) alone and a resumed run needs no further state; a GPT with a dropout probability above 0 and no
+dropout_seed is refused here.
 
 One step, from {'image'} (encoded by the frozen VQGAN, VQGAN.encode_to_ids: raster order) or {'ids': (B, T) long}:
     inp    = ops.prior_tokens(ids, sos, pkeep, V, u_keep, u_rand)      uniforms from the trainer's own device generator
+    gpt.set_dropout_call(step)                                         with a dropout_seed
     logits = gpt(inp)
     loss   = ops.cross_entropy(logits, ids)                            mean over B T
     TrainerBase.update(loss, [optim])                                  hipops.AdamW: norm, clip and update on the device
 Nothing is read back: the step returns {'loss', 'grad_norm', 'lr', 'ids'} with the scalars on the device (lr is a host float).
 
 `modules()` is {'decoder': vqgan, 'transformer': gpt}: a -v checkpoint's decoder.* keys load into the frozen first stage
-(run.first_stage_ckpt_path), and a prior checkpoint carries both.  `extra` holds the generator's state and the step counter
-the learning rate is computed from, so a resumed run continues bit for bit.
+(run.first_stage_ckpt_path), and a prior checkpoint carries both.  `extra` holds the generator's state, the step counter the
+learning rate and the dropout call are computed from, and the dropout seed (a resumed run verifies it), so a resumed run
+continues bit for bit.
 
 Editing (the launcher's -p -m edit).  token_nll(batch) is the prior's opinion of a slice code by code, -log p(code | the codes
 before it) as an (h, w) map.  edit(batch, mask | box | nll_threshold) redraws the selected codes n_candidates times with
@@ -74,7 +79,7 @@ def parameter_groups(gpt, weight_decay):
 
 class PriorTrainer(TrainerBase):
     def __init__(self, vqgan, gpt, pkeep=1.0, sos_token=0, lr=4.5e-4, betas=(0.9, 0.95), weight_decay=0.01, grad_norm_clip=1.0,
-                 warmup_steps=0, decay_steps=0, seed=0, device="cuda"):
+                 warmup_steps=0, decay_steps=0, seed=0, device="cuda", dropout_seed=None):
         if not isinstance(vqgan, VQGAN):
             raise TypeError("PriorTrainer trains on the codes of a networks.VQGAN")
         if not isinstance(gpt, GPT):
@@ -94,7 +99,10 @@ class PriorTrainer(TrainerBase):
         if warmup_steps < 0 or decay_steps < 0 or (decay_steps and decay_steps < warmup_steps):
             raise ValueError("PriorTrainer: warmup_steps=%r and decay_steps=%r: non-negative, decay_steps 0 or >= warmup_steps" % (warmup_steps, decay_steps))
         gpt.train()
-        gpt._check_dropout()             # NotImplementedError for a dropout probability above 0, before any kernel runs
+        self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
+        if self.dropout_seed is not None:
+            gpt.seed_dropout(self.dropout_seed)
+        gpt._check_dropout()             # NotImplementedError for a dropout probability above 0 without a seed, before any kernel runs
         self.vqgan = vqgan.to(self.device).eval().requires_grad_(False)          # frozen: never stepped, never in train mode
         self.gpt = gpt.to(self.device)
         self.pkeep, self.sos_token = float(pkeep), int(sos_token)
@@ -112,12 +120,16 @@ class PriorTrainer(TrainerBase):
 
     def state_dict(self):
         state = super().state_dict()
-        state["extra"].update(prior_generator=self.generator.get_state(), prior_step=int(self.step_count))
+        state["extra"].update(prior_generator=self.generator.get_state(), prior_step=int(self.step_count), prior_dropout_seed=self.dropout_seed)
         return state
 
     def load_state_dict(self, state):
-        super().load_state_dict(state)
         extra = state.get("extra") or {}
+        has_dropout = any(m.p > 0 for m in self.gpt.modules() if isinstance(m, nn.Dropout))
+        if has_dropout and extra.get("prior_dropout_seed", self.dropout_seed) != self.dropout_seed:
+            raise ValueError("PriorTrainer: the checkpoint was trained with dropout_seed=%r, this trainer has %r: the run would not "
+                             "continue with the same masks" % (extra["prior_dropout_seed"], self.dropout_seed))
+        super().load_state_dict(state)
         if "prior_generator" in extra:
             self.generator.set_state(extra["prior_generator"].cpu())
         if "prior_step" in extra:
@@ -150,6 +162,8 @@ class PriorTrainer(TrainerBase):
         ids = self.codes(batch)
         self.gpt.train()
         inp = self._inputs(ids, self.pkeep)
+        if self.dropout_seed is not None:
+            self.gpt.set_dropout_call(self.step_count)          # the masks of a step: a function of (dropout_seed, step) alone
         loss = ops.cross_entropy(self.gpt(inp), ids)
         lr = self.current_lr()
         for group in self.optim.param_groups:
