@@ -61,15 +61,15 @@ typedef float float4_t __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// wave64 butterfly sum
-__device__ __forceinline__ float wave_sum(float v) {
+// wave64 butterflies: a fixed order, the same bits every run, the result in every lane
+__device__ __forceinline__ float wave_sum_f(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-__device__ __forceinline__ float wave_sum_f(float v) {       // fixed butterfly: the same bits every run
+__device__ __forceinline__ float wave_max_f(float v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
 __device__ __forceinline__ double wave_sum_d(double v) {

@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(256) k_conv_direct_wgrad(ConvIn in, const floa
         }
         acc = fmaf(dy[p * Cout + co], v, acc);
     }
-    acc = wave_sum(acc);
+    acc = wave_sum_f(acc);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) part[(long)s * gridDim.x + o] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);

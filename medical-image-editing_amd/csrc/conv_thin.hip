@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(256) k_stem_wgrad(const float* __restrict__ x,
     for (int c = 0; c < CO; ++c)
 #pragma unroll
         for (int t = 0; t < NA; ++t) {
-            float s = wave_sum(acc[c][t]);
+            float s = wave_sum_f(acc[c][t]);
             if (lane == 0) sred[wv][c * NA + t] = s;
         }
     __syncthreads();

@@ -8,10 +8,10 @@
 // workgroup is four waves = four columns.  Rows are tiled in groups of DEC_ROWS (grid.y): the rows of a group sit in LDS as
 // [DEC_ROWS][chunk], chunk = min(K, DEC_KC), staged once per workgroup (rows past M as zeros) and read as ds_read_b128 at
 // consecutive lanes.  With M <= DEC_ROWS every weight element is read exactly once per launch.  Optional LayerNorm of the input
-// row: K <= DEC_KC, so the whole row is in LDS; wave w normalises the rows w, w + 4, ... in place with k_ln_fwd's formulas (the
-// mean plus the mean of the residuals, the variance from the centred values, fixed butterflies).  The 64 lane partials of a
-// column are folded by one fixed butterfly per row; lane m then owns row m: bias, the exact erf GELU (k_gelu_fwd's formula),
-// residual, one store.  The output is addressed through up to three column segments (pointer, row stride): one launch over the
+// row: K <= DEC_KC, so the whole row is in LDS; wave w normalises the rows w, w + 4, ... in place by the steps k_ln_fwd takes on
+// registers, gpt_math.h's (the mean plus the mean of the residuals, the variance from the centred values, fixed butterflies).
+// The 64 lane partials of a column are folded by one fixed butterfly per row; lane m then owns row m: bias, the exact erf GELU
+// (gelu_y), residual, one store.  The output is addressed through up to three column segments (pointer, row stride): one launch over the
 // packed [3E][E] weight writes q to a buffer and k, v into row t of the cache planes.
 //
 // Decode attention.  One query row per (b, head) against the cache rows [0, Tk): one workgroup per (b, head), no mask (the
@@ -21,19 +21,12 @@
 // The (m, l, acc) partials are merged through LDS in (wave, key group) order.  A lane whose key index is at or beyond Tk issues no
 // load: rows past Tk are never read.
 //
-// The step.  vqw_gpt_decode_step: embedding of idx[b] at position t, per layer ln1 + q|k|v (k, v into cache row t), attention over
-// the rows [0, t], proj + residual, ln2 + fc1 + GELU, fc2 + residual, then ln_f + head: 2 + 5 n_layer launches, no allocation, no
-// synchronisation, no host read.
+// The step.  vqw_gpt_decode_step: embedding of idx[b] at position t (vqw_embed_fwd with Ti = 1, t0 = t), per layer ln1 + q|k|v
+// (k, v into cache row t), attention over the rows [0, t], proj + residual, ln2 + fc1 + GELU, fc2 + residual, then ln_f + head:
+// 2 + 5 n_layer launches, no allocation, no synchronisation, no host read.
 #include "common.h"
+#include "gpt_math.h"
 #include "../../include/vqwnet_hip.h"
-
-__device__ __forceinline__ float gd_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float gd_sum4(const float4& v) { return (v.x + v.y) + (v.z + v.w); }
-__device__ __forceinline__ float gd_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 
 // ---------------------------------------------------------------------------------------------------------- skinny fused linear
 #define DEC_ROWS 8          // rows of x a workgroup serves: one row group
@@ -78,28 +71,26 @@ __global__ void __launch_bounds__(256) k_dec_linear(const float* __restrict__ x,
             for (int m = wv; m < rows; m += 4) {
                 float* xr = xs + m * kc;
                 float s = 0.f;
-                for (int c4 = lane; c4 < kn4; c4 += 64) s += gd_sum4(*(const float4*)(xr + 4 * c4));
+                for (int c4 = lane; c4 < kn4; c4 += 64) s += sum4(*(const float4*)(xr + 4 * c4));
                 const float mu0 = wave_sum_f(s) / (float)K;
                 float s0 = 0.f;
                 for (int c4 = lane; c4 < kn4; c4 += 64) {
                     float4 v = *(const float4*)(xr + 4 * c4);
-                    v.x -= mu0; v.y -= mu0; v.z -= mu0; v.w -= mu0;
-                    s0 += gd_sum4(v);
+                    ln_centre(v, mu0);
+                    s0 += sum4(v);
                 }
                 const float delta = wave_sum_f(s0) / (float)K;
                 float m2 = 0.f;
                 for (int c4 = lane; c4 < kn4; c4 += 64) {
                     float4 v = *(const float4*)(xr + 4 * c4);
-                    v.x = (v.x - mu0) - delta; v.y = (v.y - mu0) - delta; v.z = (v.z - mu0) - delta; v.w = (v.w - mu0) - delta;
-                    m2 = fmaf(v.x, v.x, m2); m2 = fmaf(v.y, v.y, m2); m2 = fmaf(v.z, v.z, m2); m2 = fmaf(v.w, v.w, m2);
+                    ln_centre(v, mu0); ln_centre(v, delta);
+                    m2 = ln_m2(v, m2);
                 }
                 const float rs = 1.f / sqrtf(wave_sum_f(m2) / (float)K + eps);
                 for (int c4 = lane; c4 < kn4; c4 += 64) {          // a lane rewrites only what it read itself
                     float4 v = *(const float4*)(xr + 4 * c4);
-                    const float4 g = *(const float4*)(gamma + 4 * c4), b = *(const float4*)(beta + 4 * c4);
-                    v.x = (v.x - mu0) - delta; v.y = (v.y - mu0) - delta; v.z = (v.z - mu0) - delta; v.w = (v.w - mu0) - delta;
-                    *(float4*)(xr + 4 * c4) = make_float4(fmaf(v.x * rs, g.x, b.x), fmaf(v.y * rs, g.y, b.y), fmaf(v.z * rs, g.z, b.z),
-                                                          fmaf(v.w * rs, g.w, b.w));
+                    ln_centre(v, mu0); ln_centre(v, delta);
+                    *(float4*)(xr + 4 * c4) = ln_affine(v, rs, *(const float4*)(gamma + 4 * c4), *(const float4*)(beta + 4 * c4));
                 }
             }
             __syncthreads();
@@ -127,7 +118,7 @@ __global__ void __launch_bounds__(256) k_dec_linear(const float* __restrict__ x,
     if (lane < rows) {          // lane m owns row m0 + m of column n
         const long row = m0 + lane;
         if (bias) r += bias[n];
-        if (gelu) r = gd_gelu(r);
+        if (gelu) r = gelu_y(r);
         if (residual) r += residual[row * N + n];
         const int s = n / out.seg_n;
         out.p[s][row * out.ld[s] + (n - s * out.seg_n)] = r;
@@ -216,9 +207,9 @@ __global__ void __launch_bounds__(256) k_dec_attention(const float* __restrict__
                     const float4 kk = *(const float4*)(kr + 4 * c), qq = *(const float4*)(qs + 4 * c);
                     d.x = fmaf(qq.x, kk.x, d.x); d.y = fmaf(qq.y, kk.y, d.y); d.z = fmaf(qq.z, kk.z, d.z); d.w = fmaf(qq.w, kk.w, d.w);
                 }
-                s = scale * gd_sum4(d);
+                s = scale * sum4(d);
             }
-            const float mn = fmaxf(m, gd_wave_max(s));          // finite: the chunk has a key
+            const float mn = fmaxf(m, wave_max_f(s));          // finite: the chunk has a key
             const float p = lane < nk ? expf(s - mn) : 0.f;
             a = expf(m - mn);                                    // 0 on the wave's first chunk (m = -inf)
             l = fmaf(l, a, wave_sum_f(p));
@@ -305,24 +296,6 @@ extern "C" int vqw_dec_attention(const float* q, const float* k, const float* v,
 }
 
 // ---------------------------------------------------------------------------------------------------------- the step
-// grid ceil(B / 4): wave w of workgroup g writes x[4 g + w] = tok[idx[4 g + w]] + pos[t] (k_embed_fwd for one token per row); an
-// index outside [0, V) reads nothing and writes a NaN row
-__global__ void __launch_bounds__(256) k_dec_embed(const long* __restrict__ idx, const float* __restrict__ tok, const float* __restrict__ pos,
-                                                   float* __restrict__ x, int B, int E, int V, int t) {
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= B) return;
-    const int lane = threadIdx.x & 63, E4 = E >> 2;
-    const long id = idx[b];
-    const bool ok = id >= 0 && id < V;
-    const float* src = tok + (ok ? id : 0) * E;
-    const float* pp = pos + (long)t * E;
-    const float nan = __uint_as_float(0x7fc00000u);
-    for (int c4 = lane; c4 < E4; c4 += 64) {
-        const float4 a = *(const float4*)(src + 4 * c4), p = *(const float4*)(pp + 4 * c4);
-        *(float4*)(x + (long)b * E + 4 * c4) = ok ? make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w) : make_float4(nan, nan, nan, nan);
-    }
-}
-
 // floats of one layer in the packed buffer: ln1 (2E), W_qkv (3E E), b_qkv (3E), W_proj (E E), b_proj (E), ln2 (2E), W_fc1 (4E E),
 // b_fc1 (4E), W_fc2 (E 4E), b_fc2 (E)
 static inline long dec_layer_floats(long E) { return 12 * E * E + 13 * E; }
@@ -371,7 +344,8 @@ extern "C" int vqw_gpt_decode_step(const float* packed, const float* tok, const 
         return o;
     };
 
-    hipLaunchKernelGGL(k_dec_embed, dim3(ceil_div(B, 4)), dim3(256), 0, st, idx, tok, pos, x, B, E, V, t);
+    // x[b] = tok[idx[b]] + pos[t]: the embedding's own launch with one token per row (what it checks has been checked above)
+    if (int rc = vqw_embed_fwd(idx, tok, pos, nullptr, x, B, 1, 0, E, V, block_size, t, stream)) return rc;
     const float* p = packed;
     for (int l = 0; l < n_layer; ++l, p += dec_layer_floats(e)) {
         const float *ln1w = p, *ln1b = ln1w + e, *wqkv = ln1b + e, *bqkv = wqkv + 3 * e * e, *wproj = bqkv + 3 * e, *bproj = wproj + e * e;

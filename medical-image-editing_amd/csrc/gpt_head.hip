@@ -23,18 +23,13 @@
 // the contiguous chunk t of the row, thread 0 adds the 256 chunk sums in order, finds the first chunk whose running sum exceeds
 // u total and walks it serially.  The row is read from global memory on every pass (L2-resident at these sizes).
 //
-// Sample or force (k_sample_filtered, the step of GPT.generate_masked).  The same row maximum, select and draw, plus a nucleus
-// threshold found by the same radix walk on integer MASSES per bin, a forced token per row in place of the draw, and the token's
-// log-probability under the unfiltered distribution at temperature 1 (the cross-entropy's rule: fp32 terms, a double sum in a
-// fixed order, rounded once).  Details above the kernel.
+// Sample or force (vqw_sample_filtered, the step of GPT.generate_masked).  The same kernel, k_sample, with what vqw_sample_topk
+// leaves off: a nucleus threshold found by the same radix walk on integer MASSES per bin, a forced token per row in place of the
+// draw, and the token's log-probability under the unfiltered distribution at temperature 1 (the cross-entropy's rule: fp32
+// terms, a double sum in a fixed order, rounded once).  Details above the kernel.
 #include "common.h"
+#include "gpt_math.h"
 #include "../../include/vqwnet_hip.h"
-
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------- embedding
 #define EM_MIN_E 4
@@ -60,7 +55,7 @@ __global__ void __launch_bounds__(256) k_embed_fwd(const long* __restrict__ idx,
     }
     const float* pp = pos + (long)(t0 + t) * E;
     float* xr = x + r * E;
-    const float nan = __uint_as_float(0x7fc00000u);
+    const float nan = quiet_nan();
     for (int c4 = lane; c4 < E4; c4 += 64) {
         const float4 a = *(const float4*)(src + 4 * c4), p = *(const float4*)(pp + 4 * c4);
         *(float4*)(xr + 4 * c4) = ok ? make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w) : make_float4(nan, nan, nan, nan);
@@ -208,7 +203,7 @@ __global__ void __launch_bounds__(256) k_xe_fwd(const float* __restrict__ z, con
         const long t = target[r];
         const bool ok = t >= 0 && t < V;
         const double ls = log(s);
-        const float l = ok ? (float)(((double)m - (double)zr[ok ? t : 0]) + ls) : __uint_as_float(0x7fc00000u);
+        const float l = ok ? (float)(((double)m - (double)zr[ok ? t : 0]) + ls) : quiet_nan();
         if (lane == 0) { lse[r] = (float)((double)m + ls); loss[r] = l; }
         acc += (double)l;
     }
@@ -246,7 +241,7 @@ __global__ void __launch_bounds__(256) k_xe_bwd(const float* __restrict__ z, con
     float* gr = gz + r * V;
     for (int c = lane; c < V; c += 64) {
         const float p = expf(zr[c] - L);
-        gr[c] = ok ? (c == t ? p - 1.f : p) * w : __uint_as_float(0x7fc00000u);
+        gr[c] = ok ? (c == t ? p - 1.f : p) * w : quiet_nan();
     }
 }
 
@@ -282,132 +277,27 @@ extern "C" int vqw_xent_bwd(const float* z, const long* target, const float* lse
     return VQW_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------- top-k sampling
+// ---------------------------------------------------------------------------------------------------------- sampling
 #define ST_MAX_V 65536
 
-// the order-preserving integer image of a float: a < b iff key(a) < key(b); -0 and +0 share a key
-__device__ __forceinline__ unsigned st_key(float x) {
-    if (x == 0.f) x = 0.f;
-    const unsigned u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// grid B, 256 threads: one row each
-__global__ void __launch_bounds__(256) k_sample_topk(const float* __restrict__ logits, const float* __restrict__ u, long* __restrict__ out, int V,
-                                                     float temperature, int top_k) {
-    __shared__ unsigned hist[256];
-    __shared__ float csum[256];
-    __shared__ int clast[256];
-    __shared__ float wmax[4];
-    __shared__ unsigned sel[2];
-    const int tid = threadIdx.x;
-    const float* z = logits + (long)blockIdx.x * V;
-
-    float m = -INFINITY;
-    for (int c = tid; c < V; c += 256) m = fmaxf(m, z[c] / temperature);
-    m = wave_max_f(m);
-    if ((tid & 63) == 0) wmax[tid >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-
-    // the key of the k-th largest entry: byte by byte from the top, among the entries that share the bytes chosen so far
-    unsigned thr = 0;
-    if (top_k > 0 && top_k < V) {
-        unsigned prefix = 0, pmask = 0, kk = (unsigned)top_k;
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            hist[tid] = 0;
-            __syncthreads();
-            for (int c = tid; c < V; c += 256) {
-                const unsigned key = st_key(z[c] / temperature);
-                if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int bin = 255;
-                for (; bin > 0; --bin) {
-                    const unsigned cnt = hist[bin];
-                    if (cnt >= kk) break;
-                    kk -= cnt;
-                }
-                sel[0] = prefix | ((unsigned)bin << shift);
-                sel[1] = kk;
-            }
-            __syncthreads();
-            prefix = sel[0];
-            kk = sel[1];
-            pmask |= 0xffu << shift;
-            __syncthreads();
-        }
-        thr = prefix;
-    }
-
-    // chunk sums of p = exp(s - max) over the kept entries, and each chunk's last kept index
-    const int chunk = (V + 255) / 256, c0 = tid * chunk, c1 = c0 + chunk < V ? c0 + chunk : V;
-    float s = 0.f;
-    int last = -1;
-    for (int c = c0; c < c1; ++c) {
-        const float x = z[c] / temperature;
-        if (st_key(x) >= thr) { s += expf(x - m); last = c; }
-    }
-    csum[tid] = s;
-    clast[tid] = last;
-    __syncthreads();
-    if (tid == 0) {
-        float total = 0.f;
-        for (int t = 0; t < 256; ++t) total += csum[t];
-        const float goal = u[blockIdx.x] * total;
-        float run = 0.f;
-        int t = 0, pick = -1;
-        for (; t < 256; ++t) {
-            const float nx = run + csum[t];
-            if (nx > goal) break;
-            run = nx;
-        }
-        if (t < 256) {
-            const int e = (t + 1) * chunk < V ? (t + 1) * chunk : V;
-            for (int c = t * chunk; c < e; ++c) {
-                const float x = z[c] / temperature;
-                if (st_key(x) >= thr) {
-                    run += expf(x - m);
-                    if (run > goal) { pick = c; break; }
-                }
-            }
-            if (pick < 0) pick = clast[t];              // rounding: the chunk's own sum crossed, the running sum did not
-        } else {
-            for (t = 255; t >= 0 && pick < 0; --t) pick = clast[t];      // rounding left no such index: the last kept one
-        }
-        out[blockIdx.x] = pick < 0 ? 0 : pick;          // pick < 0 only with NaN logits
-    }
-}
-
-extern "C" int vqw_sample_topk(const float* logits, const float* u, long* out, int B, int V, float temperature, int top_k, void* stream) {
-    VQW_CHECK(V >= 1 && V <= ST_MAX_V, "vqw_sample_topk: V=%d must satisfy 1 <= V <= %d", V, ST_MAX_V);
-    VQW_CHECK(B >= 1, "vqw_sample_topk: B=%d must be at least 1", B);
-    VQW_CHECK(temperature > 0.f, "vqw_sample_topk: temperature=%g must be positive", (double)temperature);
-    VQW_CHECK(top_k >= 0, "vqw_sample_topk: top_k=%d must not be negative (0: no filter)", top_k);
-    VQW_CHECK(logits && u && out, "vqw_sample_topk: null pointer");
-    hipLaunchKernelGGL(k_sample_topk, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, u, out, V, temperature, top_k);
-    VQW_LAUNCH_CHECK("vqw_sample_topk");
-    return VQW_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------- sample or force
-// k_sample_topk's row maximum, radix select and draw, operation for operation (with forced = null and top_p >= 1 the two give the
-// same bits), plus: a forced row skips the filter and the draw; the nucleus threshold; the row's log-probability.
+// One kernel draws for vqw_sample_topk (forced = logp = null, top_p = 1) and vqw_sample_filtered.  The row maximum of s, the radix
+// select of the k-th largest key and the chunked inverse-CDF draw are as the file's header describes; a forced row skips the
+// filter and the draw; the row's log-probability (and the maximum of z it needs) is taken only where logp is given.
 //
 // Nucleus.  Entry c of K1 (the top-k kept set) stays iff G(c) = the mass of the entries of K1 strictly greater than it is
 // <= top_p total.  G falls as the key rises, so the kept set is {key >= thr2} and thr2 is found like the k-th largest entry: byte
 // by byte from the top, on a histogram of MASSES per bin.  The masses are p = exp(s - max) in 2^-40 fixed point (p <= 1 and
 // V <= 2^16: a 64-bit sum cannot overflow; p 2^40 is exact in fp32, the conversion truncates below 2^-40): integer additions have
 // no order, so the LDS atomics leave the same bits every run.  The bins are walked downwards while the mass above the next
-// bin stays within the limit (wave 0, four bins a lane); the bin the walk stops in holds thr2 and is refined by the next byte.  An empty bin may be chosen: thr2
-// need not be a key of the row.
+// bin stays within the limit (wave 0, four bins a lane); the bin the walk stops in holds thr2 and is refined by the next byte.
+// An empty bin may be chosen: thr2 need not be a key of the row.
 #define SF_FIX 0x1p40f
 
+// grid B, 256 threads: one row each
 template <bool NUCLEUS>
-__global__ void __launch_bounds__(256) k_sample_filtered(const float* __restrict__ logits, const float* __restrict__ u,
-                                                         const long* __restrict__ forced, long* __restrict__ out, float* __restrict__ logp,
-                                                         int V, float temperature, int top_k, float top_p) {
+__global__ void __launch_bounds__(256) k_sample(const float* __restrict__ logits, const float* __restrict__ u, const long* __restrict__ forced,
+                                                long* __restrict__ out, float* __restrict__ logp, int V, float temperature, int top_k,
+                                                float top_p) {
     __shared__ unsigned hist[256];
     __shared__ unsigned long long mass[256];
     __shared__ float csum[256];
@@ -421,21 +311,21 @@ __global__ void __launch_bounds__(256) k_sample_filtered(const float* __restrict
     const long f = forced ? forced[blockIdx.x] : -1;
     const bool force = f >= 0 && f < V;             // the same for the whole workgroup
 
-    float m = -INFINITY, zm = -INFINITY;            // the maxima of s = z / temperature and of z
+    float m = -INFINITY, zm = -INFINITY;            // the maxima of s = z / temperature and, for logp, of z
     for (int c = tid; c < V; c += 256) {
         const float x = z[c];
-        zm = fmaxf(zm, x);
+        if (logp) zm = fmaxf(zm, x);                // the same for the whole workgroup
         m = fmaxf(m, x / temperature);
     }
     m = wave_max_f(m);
-    zm = wave_max_f(zm);
+    if (logp) zm = wave_max_f(zm);
     if ((tid & 63) == 0) { wmax[tid >> 6] = m; wzmax[tid >> 6] = zm; }
     __syncthreads();
     m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-    zm = fmaxf(fmaxf(wzmax[0], wzmax[1]), fmaxf(wzmax[2], wzmax[3]));
 
     // sum_c exp(z_c - max z): fp32 terms, thread t the columns t, t + 256, ... in double, a butterfly per wave, the four waves in order
     if (logp) {
+        zm = fmaxf(fmaxf(wzmax[0], wzmax[1]), fmaxf(wzmax[2], wzmax[3]));
         double s = 0.0;
         for (int c = tid; c < V; c += 256) s += (double)expf(z[c] - zm);
         s = wave_sum_d(s);
@@ -444,7 +334,7 @@ __global__ void __launch_bounds__(256) k_sample_filtered(const float* __restrict
 
     int pick = (int)f;
     if (!force) {
-        // the key of the k-th largest entry: k_sample_topk's select
+        // the key of the k-th largest entry: byte by byte from the top, among the entries that share the bytes chosen so far
         unsigned thr = 0;
         if (top_k > 0 && top_k < V) {
             unsigned prefix = 0, pmask = 0, kk = (unsigned)top_k;
@@ -523,7 +413,7 @@ __global__ void __launch_bounds__(256) k_sample_filtered(const float* __restrict
             if (prefix > thr) thr = prefix;
         }
 
-        // k_sample_topk's draw: chunk sums of p = exp(s - max) over the kept entries, and each chunk's last kept index
+        // the draw: chunk sums of p = exp(s - max) over the kept entries, and each chunk's last kept index
         const int chunk = (V + 255) / 256, c0 = tid * chunk, c1 = c0 + chunk < V ? c0 + chunk : V;
         float s = 0.f;
         int last = -1;
@@ -568,7 +458,7 @@ __global__ void __launch_bounds__(256) k_sample_filtered(const float* __restrict
         out[blockIdx.x] = pick;
         if (logp) {                                         // k_xe_fwd's form: the difference first, then the logarithm, rounded once
             const double ls = log(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
-            logp[blockIdx.x] = f >= V ? __uint_as_float(0x7fc00000u) : -(float)(((double)zm - (double)z[pick]) + ls);
+            logp[blockIdx.x] = f >= V ? quiet_nan() : -(float)(((double)zm - (double)z[pick]) + ls);
         }
     }
 }
@@ -582,8 +472,20 @@ extern "C" int vqw_sample_filtered(const float* logits, const float* u, const lo
     VQW_CHECK(top_p > 0.f, "vqw_sample_filtered: top_p=%g must be positive (>= 1: no filter)", (double)top_p);
     VQW_CHECK(logits && u && out, "vqw_sample_filtered: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (top_p < 1.f) hipLaunchKernelGGL(k_sample_filtered<true>, dim3(B), dim3(256), 0, st, logits, u, forced, out, logp, V, temperature, top_k, top_p);
-    else hipLaunchKernelGGL(k_sample_filtered<false>, dim3(B), dim3(256), 0, st, logits, u, forced, out, logp, V, temperature, top_k, top_p);
+    if (top_p < 1.f) hipLaunchKernelGGL(k_sample<true>, dim3(B), dim3(256), 0, st, logits, u, forced, out, logp, V, temperature, top_k, top_p);
+    else hipLaunchKernelGGL(k_sample<false>, dim3(B), dim3(256), 0, st, logits, u, forced, out, logp, V, temperature, top_k, top_p);
     VQW_LAUNCH_CHECK("vqw_sample_filtered");
+    return VQW_OK;
+}
+
+extern "C" int vqw_sample_topk(const float* logits, const float* u, long* out, int B, int V, float temperature, int top_k, void* stream) {
+    VQW_CHECK(V >= 1 && V <= ST_MAX_V, "vqw_sample_topk: V=%d must satisfy 1 <= V <= %d", V, ST_MAX_V);
+    VQW_CHECK(B >= 1, "vqw_sample_topk: B=%d must be at least 1", B);
+    VQW_CHECK(temperature > 0.f, "vqw_sample_topk: temperature=%g must be positive", (double)temperature);
+    VQW_CHECK(top_k >= 0, "vqw_sample_topk: top_k=%d must not be negative (0: no filter)", top_k);
+    VQW_CHECK(logits && u && out, "vqw_sample_topk: null pointer");
+    hipLaunchKernelGGL(k_sample<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, u, (const long*)nullptr, out, (float*)nullptr, V,
+                       temperature, top_k, 1.f);
+    VQW_LAUNCH_CHECK("vqw_sample_topk");
     return VQW_OK;
 }

@@ -98,11 +98,6 @@ __device__ __forceinline__ float wave_min(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
     return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 template <bool VEC>
@@ -138,7 +133,7 @@ __global__ __launch_bounds__(MT_BLOCK) void k_mt_stats(MtArgs a) {
             const double d = (double)p - t;
             sse += d * d;
         }
-        pmn = wave_min(pmn); pmx = wave_max(pmx); tmn = wave_min(tmn); tmx = wave_max(tmx);
+        pmn = wave_min(pmn); pmx = wave_max_f(pmx); tmn = wave_min(tmn); tmx = wave_max_f(tmx);
         sse = wave_sum_d(sse);
         if (lane == 0) { smm[0][w] = pmn; smm[1][w] = pmx; smm[2][w] = tmn; smm[3][w] = tmx; ssq[w] = sse; }
         __syncthreads();
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(MT_FOLD) void k_mt_fold(MtArgs a) {
             tmn = fminf(tmn, (float)o[2]); tmx = fmaxf(tmx, (float)o[3]);
             sse += o[4];
         }
-        pmn = wave_min(pmn); pmx = wave_max(pmx); tmn = wave_min(tmn); tmx = wave_max(tmx);
+        pmn = wave_min(pmn); pmx = wave_max_f(pmx); tmn = wave_min(tmn); tmx = wave_max_f(tmx);
         if (lane == 0) { smm[0][w] = pmn; smm[1][w] = pmx; smm[2][w] = tmn; smm[3][w] = tmx; }
         sse = block_sum_d<MT_FOLD>(sse, sh);        // its barriers also publish smm
         if (tid == 0) {

@@ -3,12 +3,14 @@
 //
 // LayerNorm.  One wave owns a row of [rows][C]: lane l holds the float4 columns l, l + 64, ... in registers, the row is read
 // once.  mean = sum / C plus the mean of the residuals, then the variance from the centred values (never E[x^2] - mean^2,
-// mfma_util.h:65-67); every sum is one fixed butterfly.  Backward: a workgroup owns LN_WG_ROWS consecutive rows, wave w the rows
+// mfma_util.h:65-67); every sum is one fixed butterfly.  The steps are gpt_math.h's, shared with the decode step's fused
+// LayerNorm.  Backward: a workgroup owns LN_WG_ROWS consecutive rows, wave w the rows
 // w, w + 4, ... of them; dgamma / dbeta are summed per lane over the wave's rows, the four waves are folded in wave order in LDS,
 // the workgroup's partial goes to the workspace and a second kernel folds the partials in index order (in double).  No atomics.
 //
 // GELU.  0.5 x (1 + erf(x / sqrt 2)) and its gradient Phi(x) + x phi(x) with the device erff / expf in fp32.
 #include "common.h"
+#include "gpt_math.h"
 #include "mfma_util.h"
 #include "../../include/vqwnet_hip.h"
 
@@ -26,7 +28,6 @@ extern "C" size_t vqw_layernorm_ws_bytes(long rows, int C) {
 __device__ __forceinline__ float4 ln_ld(const float* p, int c4, int C4) {
     return c4 < C4 ? *(const float4*)(p + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
-__device__ __forceinline__ float ln_sum4(const float4& v) { return (v.x + v.y) + (v.z + v.w); }
 
 // grid ceil(rows / 4): wave w of workgroup g normalises row 4 g + w
 template <int NV>
@@ -40,37 +41,25 @@ __global__ void __launch_bounds__(256) k_ln_fwd(const float* __restrict__ x, con
     float4 v[NV];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) { v[i] = ln_ld(xr, lane + 64 * i, C4); s += ln_sum4(v[i]); }
-    // mean = mu0 + delta with delta the mean of x - mu0: on a row that sits far off zero x - mu0 is exact and delta carries what
-    // the fp32 sum lost, so the centred values do not inherit the rounding of the mean
+    for (int i = 0; i < NV; ++i) { v[i] = ln_ld(xr, lane + 64 * i, C4); s += sum4(v[i]); }
     const float mu0 = wave_sum_f(s) / (float)C;
     float s0 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        if (lane + 64 * i < C4) {
-            v[i].x -= mu0; v[i].y -= mu0; v[i].z -= mu0; v[i].w -= mu0;
-            s0 += ln_sum4(v[i]);
-        }
+        if (lane + 64 * i < C4) { ln_centre(v[i], mu0); s0 += sum4(v[i]); }
     }
     const float delta = wave_sum_f(s0) / (float)C, mu = mu0 + delta;
     float m2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        if (lane + 64 * i < C4) {
-            v[i].x -= delta; v[i].y -= delta; v[i].z -= delta; v[i].w -= delta;
-            m2 = fmaf(v[i].x, v[i].x, m2); m2 = fmaf(v[i].y, v[i].y, m2); m2 = fmaf(v[i].z, v[i].z, m2); m2 = fmaf(v[i].w, v[i].w, m2);
-        }
+        if (lane + 64 * i < C4) { ln_centre(v[i], delta); m2 = ln_m2(v[i], m2); }
     }
     const float rs = 1.f / sqrtf(wave_sum_f(m2) / (float)C + eps);
     float* yr = y + r * C;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c4 = lane + 64 * i;
-        if (c4 < C4) {
-            const float4 g = *(const float4*)(gamma + 4 * c4), b = *(const float4*)(beta + 4 * c4);
-            *(float4*)(yr + 4 * c4) = make_float4(fmaf(v[i].x * rs, g.x, b.x), fmaf(v[i].y * rs, g.y, b.y), fmaf(v[i].z * rs, g.z, b.z),
-                                                  fmaf(v[i].w * rs, g.w, b.w));
-        }
+        if (c4 < C4) *(float4*)(yr + 4 * c4) = ln_affine(v[i], rs, *(const float4*)(gamma + 4 * c4), *(const float4*)(beta + 4 * c4));
     }
     if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
 }
@@ -105,7 +94,7 @@ __global__ void __launch_bounds__(256) k_ln_bwd(const float* __restrict__ x, con
         for (int i = 0; i < NV; ++i) {
             xh[i].x = (xh[i].x - mu) * rs; xh[i].y = (xh[i].y - mu) * rs; xh[i].z = (xh[i].z - mu) * rs; xh[i].w = (xh[i].w - mu) * rs;
             const float4 a = make_float4(gm[i].x * g[i].x, gm[i].y * g[i].y, gm[i].z * g[i].z, gm[i].w * g[i].w);
-            s1 += ln_sum4(a);
+            s1 += sum4(a);
             s2 += (a.x * xh[i].x + a.y * xh[i].y) + (a.z * xh[i].z + a.w * xh[i].w);
             db[i].x += g[i].x; db[i].y += g[i].y; db[i].z += g[i].z; db[i].w += g[i].w;
             dg[i].x = fmaf(g[i].x, xh[i].x, dg[i].x); dg[i].y = fmaf(g[i].y, xh[i].y, dg[i].y);
@@ -203,15 +192,7 @@ extern "C" int vqw_layernorm_bwd(const float* x, const float* gamma, const float
 }
 
 // ---------------------------------------------------------------------------------------------------------- GELU
-// The fp32 form with the device erff / expf: it passes the accuracy gate on every case (within 1.11 of the host's fp32 error) at
-// 2.3 times the speed of an evaluation in double, which was measured too.
-__device__ __forceinline__ float gelu_y(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float gelu_dx(float x, float gy) {
-    const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
-    const float pdf = expf(-0.5f * x * x) * 0.39894228040143267794f;
-    return gy * fmaf(x, pdf, cdf);
-}
-
+// gelu_y and gelu_dx: gpt_math.h
 __global__ void __launch_bounds__(256) k_gelu_fwd(const float* __restrict__ x, float* __restrict__ y, long n) {
     const long n4 = n >> 2, step = (long)gridDim.x * blockDim.x, t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     for (long i = t; i < n4; i += step) {

@@ -1658,21 +1658,25 @@ def _heads(q, k, v, n_head, n_unmasked, causal):
     return B, Tq, k.shape[1], E // n_head, 1.0 / float(E // n_head) ** 0.5, int(bool(causal)), int(n_unmasked)
 
 
-def _causal_attention_fwd(q, k, v, n_head, n_unmasked, causal):
+def _causal_attention_fwd(q, k, v, n_head, n_unmasked, causal, drop=()):
+    """drop: () or (p, seed, call, site), the dropout kernels' trailing arguments."""
     _dev(q, k, v)
     q, k, v = _flat(q), _flat(k), _flat(v)
     B, Tq, Tk, hs, scale, causal, nu = _heads(q, k, v, n_head, n_unmasked, causal)
     o = torch.empty_like(q)
     lse = torch.empty(B, n_head, Tq, dtype=torch.float32, device=q.device)
-    _L().vqw_causal_attention_fwd(q, k, v, o, lse, B, Tq, Tk, n_head, hs, scale, causal, nu)
+    fwd = _L().vqw_causal_attention_drop_fwd if drop else _L().vqw_causal_attention_fwd
+    fwd(q, k, v, o, lse, B, Tq, Tk, n_head, hs, scale, causal, nu, *drop)
     return q, k, v, o, lse, (B, Tq, Tk, hs, scale, causal, nu)
 
 
 class _CausalAttention(torch.autograd.Function):
+    """drop = (p, seed, call, site): dropout on the probabilities, the mask regenerated from it in the backward; (): none."""
+
     @staticmethod
-    def forward(ctx, q, k, v, n_head, n_unmasked, causal):
-        q, k, v, o, lse, ctx.cfg = _causal_attention_fwd(q, k, v, n_head, n_unmasked, causal)
-        ctx.n_head = n_head
+    def forward(ctx, q, k, v, n_head, n_unmasked, causal, drop):
+        q, k, v, o, lse, ctx.cfg = _causal_attention_fwd(q, k, v, n_head, n_unmasked, causal, drop)
+        ctx.n_head, ctx.drop = n_head, drop
         ctx.save_for_backward(q, k, v, o, lse)          # the backward recomputes nothing but the scores
         return o
 
@@ -1683,34 +1687,9 @@ class _CausalAttention(torch.autograd.Function):
         go = _flat(go)
         gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         d = torch.empty_like(lse)
-        _L().vqw_causal_attention_bwd(q, k, v, o, lse, go, d, gq, gk, gv, B, Tq, Tk, ctx.n_head, hs, scale, causal, nu)
-        return gq, gk, gv, None, None, None
-
-
-class _CausalAttentionDrop(torch.autograd.Function):
-    """_CausalAttention with dropout on the probabilities: the same five tensors saved, the mask regenerated from (p, key)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, n_head, n_unmasked, causal, p, key):
-        _dev(q, k, v)
-        q, k, v = _flat(q), _flat(k), _flat(v)
-        B, Tq, Tk, hs, scale, causal, nu = ctx.cfg = _heads(q, k, v, n_head, n_unmasked, causal)
-        o = torch.empty_like(q)
-        lse = torch.empty(B, n_head, Tq, dtype=torch.float32, device=q.device)
-        _L().vqw_causal_attention_drop_fwd(q, k, v, o, lse, B, Tq, Tk, n_head, hs, scale, causal, nu, p, *key)
-        ctx.n_head, ctx.p, ctx.key = n_head, p, key
-        ctx.save_for_backward(q, k, v, o, lse)
-        return o
-
-    @staticmethod
-    def backward(ctx, go):
-        q, k, v, o, lse = ctx.saved_tensors
-        B, Tq, Tk, hs, scale, causal, nu = ctx.cfg
-        go = _flat(go)
-        gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        d = torch.empty_like(lse)
-        _L().vqw_causal_attention_drop_bwd(q, k, v, o, lse, go, d, gq, gk, gv, B, Tq, Tk, ctx.n_head, hs, scale, causal, nu, ctx.p, *ctx.key)
-        return gq, gk, gv, None, None, None, None, None
+        bwd = _L().vqw_causal_attention_drop_bwd if ctx.drop else _L().vqw_causal_attention_bwd
+        bwd(q, k, v, o, lse, go, d, gq, gk, gv, B, Tq, Tk, ctx.n_head, hs, scale, causal, nu, *ctx.drop)
+        return gq, gk, gv, None, None, None, None
 
 
 def causal_attention(q, k, v, n_head, n_unmasked=0, causal=True, dropout_p=0.0, dropout_key=None):
@@ -1720,9 +1699,8 @@ def causal_attention(q, k, v, n_head, n_unmasked=0, causal=True, dropout_p=0.0, 
     (mingpt.py:53-56).  causal=False: no mask, Tq != Tk allowed, forward only (the layer_past route, mingpt.py:71-80).
     dropout_p > 0 with dropout_key = (seed, call, site): dropout on the probabilities (mingpt.py:83) inside the kernels, the mask
     of element (b n_head + h, i, j) regenerated in the backward (Tq == Tk); dropout_p == 0 or no key: the path without it."""
-    if dropout_key is None or dropout_p == 0:
-        return _CausalAttention.apply(q, k, v, int(n_head), int(n_unmasked), bool(causal))
-    return _CausalAttentionDrop.apply(q, k, v, int(n_head), int(n_unmasked), bool(causal), _drop_p(dropout_p), _drop_key(dropout_key))
+    drop = () if dropout_key is None or dropout_p == 0 else (_drop_p(dropout_p),) + _drop_key(dropout_key)
+    return _CausalAttention.apply(q, k, v, int(n_head), int(n_unmasked), bool(causal), drop)
 
 
 def causal_attention_lse(q, k, v, n_head, n_unmasked=0, causal=True):
@@ -1915,15 +1893,19 @@ def cross_entropy_lse(logits, target):
     return loss, lse
 
 
+def _sample_args(name, logits, u):
+    _dev(logits, u)
+    logits, u = _flat(logits), _flat(u)
+    if logits.dim() != 2 or u.dim() != 1 or u.shape[0] != logits.shape[0]:
+        raise RuntimeError("%s: logits (B, V) and u (B,) expected, got %s and %s" % (name, tuple(logits.shape), tuple(u.shape)))
+    return logits, u, torch.empty(logits.shape[0], dtype=torch.long, device=logits.device)
+
+
 def sample_topk(logits, u, temperature=1.0, top_k=0):
     """One token per row of logits (B, V): top_k_logits (keep every entry >= the top_k-th largest of logits / temperature; 0, None
     or >= V: no filter), softmax, inverse-CDF sampling with the caller's uniforms u (B,) in [0, 1) - torch.rand with a generator.
     Returns (B,) torch.long.  No random numbers are drawn here: the same u gives the same tokens."""
-    _dev(logits, u)
-    logits, u = _flat(logits), _flat(u)
-    if logits.dim() != 2 or u.dim() != 1 or u.shape[0] != logits.shape[0]:
-        raise RuntimeError("sample_topk: logits (B, V) and u (B,) expected, got %s and %s" % (tuple(logits.shape), tuple(u.shape)))
-    out = torch.empty(logits.shape[0], dtype=torch.long, device=logits.device)
+    logits, u, out = _sample_args("sample_topk", logits, u)
     _L().vqw_sample_topk(logits, u, out, logits.shape[0], logits.shape[1], float(temperature), int(top_k or 0))
     return out
 
@@ -1935,17 +1917,14 @@ def sample_filtered(logits, u, forced=None, temperature=1.0, top_k=0, top_p=None
     filter).  Draw: sample_topk's inverse CDF with the caller's uniforms u (B,).  forced (B,) torch.long or None: a row whose entry
     lies in [0, V) takes it (u is not read there), a negative entry draws, an entry >= V draws and makes logp NaN.  logp is the
     token's log-probability under the model's own distribution (temperature 1, no filter).  With forced None and no top_p the
-    tokens have sample_topk's bits."""
-    _dev(logits, u, forced)
-    logits, u = _flat(logits), _flat(u)
-    if logits.dim() != 2 or u.dim() != 1 or u.shape[0] != logits.shape[0]:
-        raise RuntimeError("sample_filtered: logits (B, V) and u (B,) expected, got %s and %s" % (tuple(logits.shape), tuple(u.shape)))
+    tokens have sample_topk's bits: the two are one kernel."""
+    _dev(forced)
+    logits, u, out = _sample_args("sample_filtered", logits, u)
     if forced is not None:
         forced = _long(forced, "sample_filtered: forced")
         if tuple(forced.shape) != tuple(u.shape):
             raise RuntimeError("sample_filtered: forced (B,) = %s expected, got %s" % (tuple(u.shape), tuple(forced.shape)))
     B, V = logits.shape
-    out = torch.empty(B, dtype=torch.long, device=logits.device)
     logp = torch.empty(B, dtype=torch.float32, device=logits.device) if return_logp else None
     _L().vqw_sample_filtered(logits, u, forced, out, logp, B, V, float(temperature), int(top_k or 0), 1.0 if top_p is None else float(top_p))
     return out, logp

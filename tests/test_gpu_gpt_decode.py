@@ -1,6 +1,7 @@
 """GPU tests of the cached generation of the GPT code prior: the skinny fused linear and the decode attention against the float64
 restatement (tests/gpt_decode_ref.py) at the smallest shapes that can go wrong, run-to-run bit-identity, and the model - prefill,
-decode_step token by token, the cache's contents, generate() - on the reference's fixtures (tests/golden/mingpt_gpt_*.npz).  Run with
+decode_step token by token, the cache's contents, generate() - on the reference's fixtures (tests/golden/mingpt_gpt_*.npz); one
+decode_step against the same step rebuilt from its pieces, bit for bit, and a token outside the vocabulary.  Run with
 `pytest -m gpu` on an MI355X.
 
 Tolerances.  Kernel cases: the relative L2 distance of the kernel's result from the float64 restatement may be at most twice the
@@ -265,6 +266,79 @@ def test_decode_step_rewound_repeats_its_bits_and_repack_sees_new_weights(golden
     assert torch.equal(m.decode_step(tokens[:, 6], cache), a), "the packed weights are a snapshot"
     cache.pack(m).length = 6
     assert not torch.equal(m.decode_step(tokens[:, 6], cache), a)
+
+
+def _step_from_pieces(m, idx, cache):
+    """decode_step's 2 + 5 n_layer launches as one ops call each (q, k and v as three: a wave owns a column, so the bits do not
+    depend on the packing) on row cache.length of the cache -> the logits"""
+    from hipops import ops
+    t, nh, eps = cache.length, m.config.n_head, m.ln_f.eps
+    x = ops.embedding(idx[:, None], m.tok_embed.weight, m.pos_embed, t0=t)[:, 0]
+    for i, blk in enumerate(m.blocks):
+        ln1, ln2 = (blk.ln1.weight, blk.ln1.bias, eps), (blk.ln2.weight, blk.ln2.bias, eps)
+        q = ops.dec_linear(x, blk.att.q.weight, blk.att.q.bias, ln=ln1)
+        for plane, lin in ((0, blk.att.k), (1, blk.att.v)):
+            cache.kv[i, plane, :, t] = ops.dec_linear(x, lin.weight, lin.bias, ln=ln1)
+        att = ops.dec_attention(q, cache.kv[i, 0], cache.kv[i, 1], t + 1, nh)
+        ops.dec_linear(att, blk.att.proj.weight, blk.att.proj.bias, residual=x, out=x)
+        h = ops.dec_linear(x, blk.mlp[0].weight, blk.mlp[0].bias, ln=ln2, gelu=True)
+        ops.dec_linear(h, blk.mlp[2].weight, blk.mlp[2].bias, residual=x, out=x)
+    cache.length += 1
+    return ops.dec_linear(x, m.head.weight, ln=(m.ln_f.weight, m.ln_f.bias, eps))
+
+
+def test_decode_step_equals_its_pieces_bit_for_bit(golden):
+    name, n0 = "gpt64", 3
+    g, state, idx, prefix, refs = _fixture(golden, name)
+    V, bs, nl, nh, E, nu, B, Ti, Te = G.CASES[name]
+    assert nl == 2 and prefix is None
+    m = _model(name, state).eval()
+    tokens = idx.to(DEV)
+    one, two = m.new_cache(B), m.new_cache(B)
+    with torch.no_grad():
+        for cache in (one, two):
+            cache.kv.fill_(SENTINEL)
+            m.prefill(tokens[:, :n0], cache)
+        assert torch.equal(one.kv, two.kv)
+        step = m.decode_step(tokens[:, n0], one)
+        pieces = _step_from_pieces(m, tokens[:, n0], two)
+    torch.cuda.synchronize()
+    assert one.length == two.length == n0 + 1 and step.shape == pieces.shape == (B, V) and bool(torch.isfinite(step).all())
+    assert torch.equal(step, pieces), "logits: %.3e apart" % rel_err(step, pieces)
+    for layer in range(nl):
+        for plane in range(2):
+            assert torch.equal(one.kv[layer, plane, :, n0], two.kv[layer, plane, :, n0]), "layer %d plane %d row %d" % (layer, plane, n0)
+    assert torch.equal(one.kv, two.kv) and bool((one.kv[:, :, :, n0 + 1:] == SENTINEL).all())
+
+
+def test_decode_step_token_outside_the_vocabulary_gives_nan_rows_and_touches_no_other():
+    """B = 5: the fifth row sits in the second workgroup of the embedding launch (four rows a workgroup)."""
+    import networks
+    V, bs, E, B, bad = 8, 4, 32, 5, (1, 4)
+    torch.manual_seed(23)
+    m = networks.GPT(vocab_size=V, block_size=bs, n_layer=1, n_head=1, n_embed=E)
+    with torch.no_grad():
+        for p in m.parameters():          # LayerNorm weights and every bias off their initial 1 and 0
+            p.add_(0.1 * torch.randn(p.shape))
+    m = m.to(DEV).eval()
+    first = torch.tensor([3, 0, 7, 5, 2], device=DEV)
+    valid = torch.tensor([6, 1, 0, 7, 4], device=DEV)
+    tokens = valid.clone()
+    tokens[bad[0]], tokens[bad[1]] = V, -1
+    got, want = m.new_cache(B), m.new_cache(B)
+    for cache in (got, want):
+        cache.kv.fill_(SENTINEL)
+        m.prefill(first[:, None], cache)
+    logits, ref = m.decode_step(tokens, got), m.decode_step(valid, want)
+    torch.cuda.synchronize()
+    assert got.length == 2 and logits.shape == (B, V) and bool(torch.isfinite(ref).all()) and bool(torch.isfinite(want.kv[:, :, :, :2]).all())
+    good = [b for b in range(B) if b not in bad]
+    for b in bad:
+        assert bool(torch.isnan(logits[b]).all()), "logits row %d" % b
+        assert bool(torch.isnan(got.kv[0, :, b, 1]).all()), "cache row 1 of batch row %d" % b
+    assert torch.equal(logits[good], ref[good]) and torch.equal(got.kv[0, :, good, 1], want.kv[0, :, good, 1])
+    assert torch.equal(got.kv[:, :, :, 0], want.kv[:, :, :, 0]), "the prefilled row"
+    assert bool((got.kv[:, :, :, 2:] == SENTINEL).all()), "rows at or beyond length must keep their sentinel"
 
 
 # ------------------------------------------------------------------------------------------------ generate
