@@ -912,6 +912,46 @@ int vqw_adamw_step(float* p, const float* g, float* m, float* v, long n, double 
 int vqw_prior_tokens(const long* ids, const float* u_keep, const float* u_rand, long* inp, int B, int T, int V, long sos, float pkeep,
                      void* stream);
 
+/* ---- anomaly detection with the code prior (trainers/prior.py PriorTrainer.detect, trainers/fit.py Fit.detect; the reference has
+ * nothing like it).  Added functions only; the ABI stays 9.  fp32 in, no float atomics, the same bits every run; every refusal below
+ * arrives with a message before any launch.
+ * The map of a restoration: map = G(r o U(m)) on NHWC a, b [N][H][W][C] -> map [N][H][W].  r[y][x] = (sum_c |a - b|) / C, c
+ * ascending.  m = float(cellmask != 0), cellmask [N][h][w] bytes with H = fy h, W = fx w for integers fy, fx; U is bilinear
+ * up-sampling with half-pixel centres and clamped edges, the values of F.interpolate(mode='bilinear', align_corners=False): source
+ * coordinate max(0, (y + 0.5) h / H - 0.5), its floor and the next cell (clamped to h - 1), weights from the fraction.  cellmask
+ * null: m is all ones, U is skipped and h, w are not read.  G is the separable filter of the K = 2 R + 1 taps [K] (the caller's
+ * normalised Gaussian; device, fp32) with clamped (replicate) borders, rows first, then columns, each sum over the taps in
+ * ascending order from 0; K = 1 with the tap 1 is no blur.  ONE kernel: a workgroup owns a 32 x 64 tile, computes r o U(m) for the
+ * tile and its halo of R pixels into LDS, runs both passes there and writes the tile - a and b are read once (plus the halo), the
+ * map is written once, nothing else touches memory.  Refused: K even, K < 1 or K > 33 (R <= 16 is the halo the tile geometry
+ * holds: sigma <= 5.33 under K = 2 ceil(3 sigma) + 1); H or W no multiple of h, w; an empty tensor (N, H, W or C < 1); N > 65535;
+ * a, b, taps or map null or not 16-byte aligned. */
+int vqw_anomaly_map(const float* a, const float* b, const uint8_t* cellmask, const float* taps, float* map, int N, int H, int W, int C,
+                    int h, int w, int K, void* stream);
+/* The histogram of scores [n] by an order-preserving key, ACCUMULATED into hist [2][65536] (torch.long; hist[0]: the negatives,
+ * labels[i] == 0, hist[1]: the positives): the key of a finite score s >= 0 is bits(s) >> 15 - 8 exponent and 8 mantissa bits,
+ * monotone non-decreasing in s, relative resolution 2^-8; -0 counts as 0.  A NaN, an infinity or a negative score is not binned and
+ * adds 1 to err[0] (torch.long, accumulated too).  labels [n] bytes.  Integer atomics: the counts are exact and do not depend on the
+ * order.  A workgroup keeps 32-bit counters for a window of 24 exponents x 256 keys per label in LDS - the window ends one exponent
+ * above the largest key of the workgroup's first chunk - and for key 0 (the exact zeros of untouched pixels), and adds the non-zero
+ * ones to hist once; any other key outside the window goes to hist at once; before any add a wave merges the lanes that share
+ * the key of its first lane into one add per label, so a constant map costs two adds per wave-instruction.  16 bytes of scores and 4 of labels per load when scores is 16-byte and
+ * labels 4-byte aligned, else one score per load.  Refused: a null pointer, n < 1 (an empty tensor), n > 2^40, scores not 4-byte
+ * or hist, err not 8-byte aligned. */
+int vqw_score_histogram(const float* scores, const uint8_t* labels, long* hist, long* err, long n, void* stream);
+/* The detection scores of a histogram, out [8] doubles on the device, one launch, one workgroup.  With P_b = hist[1][b], N_b =
+ * hist[0][b], P = sum P_b, N = sum N_b, TP_b = sum_{b' >= b} P_b', FP_b = sum_{b' >= b} N_b' (64-bit integer scans over the bins
+ * in descending order):
+ *   out[0] auroc          = sum_b P_b (N_{<b} + N_b / 2) / (P N)                      (Mann-Whitney; ties inside a bin count half)
+ *   out[1] ap             = sum_{b non-empty} (P_b / P) TP_b / (TP_b + FP_b)           (one threshold per distinct key)
+ *   out[2] best_dice      = max over the non-empty bins of 2 TP_b / (TP_b + FP_b + P)  (= 2 TP / (2 TP + FP + FN))
+ *   out[3] best_threshold = the float whose bits are b << 15 for the bin of best_dice; a tie goes to the highest bin (the Dice
+ *                           values are compared exactly, as fractions)
+ *   out[4] P, out[5] N, out[6] 1 if err is null or err[0] == 0 else 0, out[7] 0.
+ * Every term is formed in double from the exact integers (no integer product) and summed in a fixed order.  With P = 0 or N = 0
+ * out[0..3] are NaN: that is the definition, not an error.  Refused: hist or out null, a pointer not 8-byte aligned. */
+int vqw_detection_scores(const long* hist, const long* err, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,10 +59,18 @@ class _Compose:
 
 def get_data_loader(mode, dataset_name, root_dir_path, batch_size, num_workers, modality=None, augmentations=None,
                     drop_last=False, window_width=None, window_center=None, window_scale=None, sampler=None, generator=None,
-                    image_size=None, n_samples=None, seed=0):
+                    image_size=None, n_samples=None, seed=0, label_modality=None, lesions=None):
     """sampler (e.g. a DistributedSampler; replaces the loader's own shuffling) and generator (the torch.Generator the
     shuffling and the workers' seeds are drawn from, so that a run can save and restore it) are passed to the DataLoader;
-    image_size / n_samples / seed describe the generated 'synthetic' dataset."""
+    image_size / n_samples / seed describe the generated 'synthetic' dataset.  Labels (anomaly detection, Fit.detect) are opt-in
+    and leave every other key of a sample as it is: label_modality names the MICCAIBraTSDataset sibling files
+    `<x>_<label_modality>_<slice>.npy` (preprocess_brats.py's 'seg') loaded as sample['label'], (1, H, W) uint8, 1 where the file
+    is non-zero; lesions = {n, radius, contrast} adds dataio.synthetic_lesions to the 'synthetic' slices, with their mask as the
+    label.  Any other combination raises."""
+    if label_modality is not None and dataset_name != 'MICCAIBraTSDataset':
+        raise NotImplementedError("label_modality=%r: only MICCAIBraTSDataset has label files (got %s)" % (label_modality, dataset_name))
+    if lesions is not None and dataset_name != 'synthetic':
+        raise NotImplementedError("lesions are generated for the 'synthetic' dataset only (got %s)" % (dataset_name,))
     assert mode in {'train', 'val', 'test'}
     assert dataset_name in {'MICCAIBraTSDataset', 'NCCLungDataset', 'CRCDataset', 'synthetic'}
     intensity = [] if dataset_name == 'NCCLungDataset' else [NormalizeIntensity()]      # CT slices are windowed by the dataset
@@ -74,9 +82,10 @@ def get_data_loader(mode, dataset_name, root_dir_path, batch_size, num_workers, 
         assert augmentations is None
         transform, shuffle = _Compose([ToTensor()] + intensity), mode == 'val'
     if dataset_name == 'synthetic':         # generated in [-1, 1] as (1, H, W) tensors: no transform chain
-        dataset = SyntheticSliceDataset(mode, image_size or 256, n_samples or (256 if mode == 'train' else 64), seed)
+        dataset = SyntheticSliceDataset(mode, image_size or 256, n_samples or (256 if mode == 'train' else 64), seed,
+                                        lesions=lesions)
     elif dataset_name == 'MICCAIBraTSDataset':
-        dataset = MICCAIBraTSDataset(root_dir_path, modality, transform)
+        dataset = MICCAIBraTSDataset(root_dir_path, modality, transform, label_modality=label_modality)
     elif dataset_name == 'CRCDataset':
         dataset = CRCDataset(root_dir_path, transform)
     else:

@@ -5,6 +5,7 @@ import os
 import random
 
 import numpy as np
+import torch
 from torch.utils import data
 
 
@@ -48,10 +49,11 @@ class MICCAIBraTSDataset(data.Dataset):
     """dataio/miccai_dataset.py:15-68: `<patient>/<x>_<modality>_<slice>.npy` MR slices (intensities 0..255; the loader's
     NormalizeIntensity maps them to [-1, 1]); the file list keeps directory order (no shuffle at construction, as upstream)."""
 
-    def __init__(self, root_dir_path, modality, transform=None):
+    def __init__(self, root_dir_path, modality, transform=None, label_modality=None):
         super().__init__()
         assert modality in {'t1', 't1ce', 't2', 'flair'}
         self.root_dir_path, self.modality, self.transform = str(root_dir_path), modality, transform
+        self.label_modality = label_modality          # e.g. 'seg': the sibling `<x>_<label_modality>_<slice>.npy` -> sample['label']
         self.files = []
         for patient_id in os.listdir(self.root_dir_path):
             for path in sorted(glob.glob(os.path.join(self.root_dir_path, patient_id, '*_{}_*'.format(modality)))):
@@ -65,7 +67,13 @@ class MICCAIBraTSDataset(data.Dataset):
     def __getitem__(self, index):
         sample = dict(self.files[index])
         sample['image'] = np.load(sample['image_path']).astype(np.float32)
-        return self.transform(sample) if self.transform else sample
+        sample = self.transform(sample) if self.transform else sample
+        if self.label_modality is not None:          # after the transform chain: a label is never normalised
+            folder, name = os.path.split(sample['image_path'])
+            head, _, tail = name.rpartition('_{}_'.format(self.modality))
+            label = np.load(os.path.join(folder, '{}_{}_{}'.format(head, self.label_modality, tail)))
+            sample['label'] = torch.from_numpy((label != 0).astype(np.uint8)).reshape((1,) + label.shape[-2:])
+        return sample
 
 
 class CRCDataset(data.Dataset):

@@ -1949,6 +1949,98 @@ def paste_cells(image, edit, cellmask):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# anomaly detection with the code prior (csrc/detect.hip): forward only, no gradient
+# ----------------------------------------------------------------------------------------------
+SCORE_BINS = 65536
+DETECTION_SCORES = ("auroc", "ap", "best_dice", "best_threshold", "P", "N", "err_free", "reserved")
+
+
+def gauss_taps(sigma):
+    """The K = 2 ceil(3 sigma) + 1 taps exp(-d^2 / 2 sigma^2) of anomaly_map's Gaussian, normalised to sum 1 in double and
+    rounded to fp32 (a host tensor); sigma = 0: the single tap 1 (no blur)."""
+    import math
+    sigma = float(sigma)
+    if not sigma >= 0 or math.isinf(sigma):
+        raise ValueError("gauss_taps: sigma=%r must be a finite number >= 0" % (sigma,))
+    if sigma == 0:
+        return torch.ones(1, dtype=torch.float32)
+    R = int(math.ceil(3.0 * sigma))
+    d = torch.arange(-R, R + 1, dtype=torch.float64)
+    t = torch.exp(-d * d / (2.0 * sigma * sigma))
+    return (t / t.sum()).float()
+
+
+_device_taps = {}
+
+
+def _taps_on_device(sigma, device):
+    """gauss_taps(sigma) on the device, copied once per (sigma, device): a call of anomaly_map then has no host-to-device copy."""
+    key = (sigma, str(device))
+    if key not in _device_taps:
+        _device_taps[key] = gauss_taps(sigma).to(device)
+    return _device_taps[key]
+
+
+def anomaly_map(a, b, cellmask=None, sigma=2.0):
+    """map = G_sigma(r o U(m)) -> (N, H, W) fp32: r = mean_c |a - b| of a, b (N, C, H, W) fp32 in either memory format; m =
+    float(cellmask != 0) for cellmask (N, h, w) torch.uint8 with H, W integer multiples of h, w, U its bilinear up-sampling
+    (F.interpolate(mode='bilinear', align_corners=False)); cellmask None: no weight.  G_sigma: the separable Gaussian of
+    gauss_taps(sigma) with replicate borders; sigma = 0: no blur.  One kernel; refused by its argument check: a sigma whose
+    K = 2 ceil(3 sigma) + 1 exceeds 33 taps, non-integer factors, empty tensors.  No gradient."""
+    _dev(a, b, cellmask)
+    a, b = nhwc(a.detach()), nhwc(b.detach())
+    if a.shape != b.shape:
+        raise RuntimeError("anomaly_map: shape mismatch %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    N, C, H, W = a.shape
+    h = w = 1
+    if cellmask is not None:
+        if cellmask.dtype != torch.uint8 or cellmask.dim() != 3 or cellmask.shape[0] != N:
+            raise RuntimeError("anomaly_map: cellmask (N, h, w) torch.uint8 with N = %d expected, got %s of %s" % (N, tuple(cellmask.shape), cellmask.dtype))
+        cellmask = cellmask.contiguous()
+        h, w = cellmask.shape[1:]
+    taps = _taps_on_device(float(sigma), a.device)
+    out = torch.empty((N, H, W), dtype=torch.float32, device=a.device)
+    _L().vqw_anomaly_map(a, b, cellmask, taps, out, N, H, W, C, h, w, taps.numel())
+    return out
+
+
+def new_score_histogram(device):
+    """(hist (2, 65536) torch.long, err (1,) torch.long), zeroed, for score_histogram to accumulate into."""
+    return torch.zeros((2, SCORE_BINS), dtype=torch.long, device=device), torch.zeros(1, dtype=torch.long, device=device)
+
+
+def score_histogram(scores, labels, hist, err):
+    """Adds the scores (any shape, fp32) to hist (2, 65536) torch.long IN PLACE - hist[0] the pixels whose label is 0, hist[1] the
+    others - by the key bits(s) >> 15 of a finite s >= 0 (-0 is 0); a NaN, an infinity or a negative score is not binned and
+    adds 1 to err (1,) torch.long.  labels: torch.uint8 (or torch.bool) with as many elements.  Returns None."""
+    _dev(scores, labels, hist, err)
+    scores = _flat(scores.detach()).reshape(-1)
+    if labels.dtype == torch.bool:
+        labels = labels.view(torch.uint8) if labels.is_contiguous() else labels.contiguous().view(torch.uint8)
+    if labels.dtype != torch.uint8 or labels.numel() != scores.numel():
+        raise RuntimeError("score_histogram: labels torch.uint8 with %d elements expected, got %s of %s" % (scores.numel(), tuple(labels.shape), labels.dtype))
+    if hist.dtype != torch.long or tuple(hist.shape) != (2, SCORE_BINS) or not hist.is_contiguous():
+        raise RuntimeError("score_histogram: hist (2, %d) torch.long, contiguous, expected, got %s of %s" % (SCORE_BINS, tuple(hist.shape), hist.dtype))
+    if err.dtype != torch.long or err.numel() != 1:
+        raise RuntimeError("score_histogram: err (1,) torch.long expected, got %s of %s" % (tuple(err.shape), err.dtype))
+    _L().vqw_score_histogram(scores, labels.contiguous().reshape(-1), hist, err, scores.numel())
+
+
+def detection_scores(hist, err=None):
+    """(8,) float64 on the device from a score histogram: [auroc, ap, best_dice, best_threshold, P, N, err-free flag, 0]
+    (DETECTION_SCORES names them; the definitions are vqw_detection_scores' in include/vqwnet_hip.h).  With no positive or no
+    negative pixel the first four are NaN.  err: score_histogram's counter (None: the flag is 1).  One launch, no host read."""
+    _dev(hist, err)
+    if hist.dtype != torch.long or tuple(hist.shape) != (2, SCORE_BINS) or not hist.is_contiguous():
+        raise RuntimeError("detection_scores: hist (2, %d) torch.long, contiguous, expected, got %s of %s" % (SCORE_BINS, tuple(hist.shape), hist.dtype))
+    if err is not None and (err.dtype != torch.long or err.numel() != 1):
+        raise RuntimeError("detection_scores: err (1,) torch.long expected, got %s of %s" % (tuple(err.shape), err.dtype))
+    out = torch.empty(8, dtype=torch.float64, device=hist.device)
+    _L().vqw_detection_scores(hist, err, out)
+    return out
+
+
 def prior_tokens(ids, sos, pkeep, vocab_size, u_keep=None, u_rand=None):
     """The transformer's input of a training step of the prior, from the code sequences ids (B, T) torch.long: the start token
     `sos` in front of the sequence shifted right by one (teacher forcing; the target stays `ids`), with taming-transformers'

@@ -2,6 +2,7 @@
 
     python run_vqwnet.py -c CONFIG [-m train|test] [-w] [-v | -p]
     python run_vqwnet.py -c CONFIG -p -m edit
+    python run_vqwnet.py -c CONFIG -p -m detect
 
 run.training_mode picks the work: `first_step` / `second_step` train (-m train) or are scored (-m test: result.csv in the
 run directory); `inference` (-m test only) exports PNG and NIfTI files per slice.  -w selects the multi-window step and
@@ -15,7 +16,11 @@ epoch and resumes from run.resume_checkpoint.  -p is refused with -v, with -m te
 run.num_gpus > 1 (data-parallel prior training is not built).  -p -m edit edits slices with a trained prior (Fit.edit): the
 prior of run.resume_checkpoint redraws the codes of the region the `edit` section selects (box, mask_path or nll_threshold) in the
 first edit.n_slices test slices, edit.n_candidates times each, and keeps the likeliest; pictures, codes and scores go to
-<run dir>/edit/.  -m edit without -p is refused.
+<run dir>/edit/.  -m edit without -p is refused.  -p -m detect localises anomalies with a trained prior (Fit.detect): the prior
+of run.resume_checkpoint restores the codes whose token_nll exceeds detect.nll_threshold, the smoothed pixel residual is the
+anomaly map of a slice (ops.anomaly_map), and with detect.labels the maps are scored against the lesion labels - AUROC, average
+precision and the best Dice over all pixels (detect_result.csv beside detect.csv and the pictures in the run directory).  -m detect
+without -p, or with -v, is refused.
 
 One process per GPU.  With run.num_gpus == 1 this process is the worker.  With more, this process never touches the GPU:
 it starts num_gpus fresh interpreters of this file (`--rank r`, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their
@@ -41,7 +46,7 @@ TRAINING_MODES = ("first_step", "second_step", "inference")
 def build_parser():
     parser = argparse.ArgumentParser(description="Train, score or export a VQ-W-Net from a JSON config")
     parser.add_argument("-c", "--config", required=True, help="path of the JSON config")
-    parser.add_argument("-m", "--mode", default="train", help="train (default), test, or edit (with -p)")
+    parser.add_argument("-m", "--mode", default="train", help="train (default), test, or edit / detect (with -p)")
     parser.add_argument("-w", "--multiwindow", action="store_true", help="multi-window training step")
     parser.add_argument("-v", "--vqgan", action="store_true", help="train the VQGAN (model.vqgan) with the U-Net discriminator; overrides -w")
     parser.add_argument("-p", "--prior", action="store_true", help="train the GPT code prior (model.prior) on the codes of the VQGAN (model.vqgan)")
@@ -80,8 +85,13 @@ def check_arguments(config, args):
             raise ValueError("-m edit: editing redraws the codes of a region with the code prior and needs -p")
         from trainers.config import check_edit_config
         check_edit_config(config)               # NotImplementedError naming the missing keys of the `edit` section
+    elif args.mode == "detect":
+        if not prior:
+            raise ValueError("-m detect: detection restores the unlikely codes with the code prior and needs -p")
+        from trainers.config import check_detect_config
+        check_detect_config(config)             # NotImplementedError naming the missing keys of the `detect` section
     elif args.mode not in ("train", "test"):
-        raise ValueError("-m %r: the mode is 'train' or 'test' (or, with -p, 'edit')" % (args.mode,))
+        raise ValueError("-m %r: the mode is 'train' or 'test' (or, with -p, 'edit' or 'detect')" % (args.mode,))
     mode = _get(config.run, "training_mode", "first_step")
     if mode not in TRAINING_MODES:
         raise ValueError("run.training_mode %r: one of %s" % (mode, ", ".join(TRAINING_MODES)))
@@ -223,6 +233,8 @@ def worker(config, args, training_mode, rank, world_size, seed):
             fit.export()
         elif args.mode == "edit":
             fit.edit()
+        elif args.mode == "detect":
+            fit.detect()
         elif args.mode == "train":
             fit.fit()
         else:

@@ -7,7 +7,7 @@ from .vqgan_unet_dis import VQGANUNetDisTrainer, VQGANLossWeights  # noqa: F401
 from .config import (build_first_step_trainer, build_second_step_trainer, build_vqgan_trainer, check_vqgan_config, vqgan_loss_weights, configure_discriminator, configure_vqgan, gan_loss_weights, unet_gan_loss_weights, configure_models, configure_optimizers, configure_losses, configure_frequency_loss,  # noqa: F401
                      configure_perceptual_loss,
                      loss_weights, set_transform, build_evaluator)
-from .config import build_prior_trainer, check_prior_config, check_edit_config, configure_prior  # noqa: F401
+from .config import build_prior_trainer, check_prior_config, check_edit_config, check_detect_config, configure_prior  # noqa: F401
 from .prior import PriorTrainer, learning_rate, parameter_groups  # noqa: F401
 from .evaluation import Evaluator, write_result_csv  # noqa: F401
 from .fit import Fit, InferenceModels, build_loader  # noqa: F401

@@ -23,6 +23,8 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
                  no trainer for its GPT; trainers/prior.py)
     config.edit.{n_slices, n_candidates, temperature, top_k, top_p, seed} and one of edit.{box, mask_path, nll_threshold},
                  config.run.resume_checkpoint    (editing with the prior, -p -m edit: keys of this project; Fit.edit)
+    config.detect.{n_slices, n_candidates, temperature, top_k, top_p, seed, nll_threshold, sigma, against, weight, labels},
+                 config.run.resume_checkpoint    (anomaly detection with the prior, -p -m detect: keys of this project; Fit.detect)
 
 The focal frequency loss (use_frequency_loss) is functions.FocalFrequencyLoss, built on HIP kernels in place of the
 third-party focal-frequency-loss package.  The perceptual loss (use_perceptual_loss with perceptual_loss_type 'vgg', the
@@ -153,6 +155,52 @@ def check_edit_config(config):
     if len(given) != 1:
         raise NotImplementedError("editing with the prior (run_vqwnet.py -p -m edit) needs exactly one of edit.{%s}; given: %s"
                                   % (", ".join(EDIT_SELECTORS), ", ".join(given) or "none"))
+
+
+DETECT_KEYS = ("n_slices", "n_candidates", "temperature", "top_k", "top_p", "seed", "nll_threshold", "sigma", "against", "weight",
+               "labels")
+DETECT_AGAINST, DETECT_WEIGHT = ("image", "reconstruction"), ("mask", "none")
+DETECT_LESION_KEYS = ("n", "radius", "contrast")
+
+
+def detect_labels(config):
+    """config.detect.labels -> (label_modality or None, synthetic lesions {n, radius, contrast} or None): `false` (no labels), a
+    modality name (MICCAIBraTSDataset's sibling files), or {"synthetic": {n, radius, contrast}}."""
+    labels = _get(config.detect, "labels")
+    if labels is None or labels is False:
+        return None, None
+    if isinstance(labels, str):
+        return labels, None
+    lesions = _get(labels, "synthetic")
+    missing = [k for k in DETECT_LESION_KEYS if lesions is None or not hasattr(lesions, k)]
+    if missing:
+        raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect): detect.labels is false, a modality name or "
+                                  "{\"synthetic\": {%s}}; missing: %s" % (", ".join(DETECT_LESION_KEYS), ", ".join("detect.labels.synthetic." + k for k in missing)))
+    return None, {k: getattr(lesions, k) for k in DETECT_LESION_KEYS}
+
+
+def check_detect_config(config):
+    """NotImplementedError unless the config describes a detection run (run_vqwnet.py -p -m detect): check_prior_config's keys,
+    run.resume_checkpoint (the -p checkpoint whose prior restores), and the eleven keys of the `detect` section - n_slices (0: the
+    whole test split), n_candidates, temperature, top_k, top_p, seed, nll_threshold (a number), sigma, against ('image' or
+    'reconstruction'), weight ('mask' or 'none'), labels (detect_labels).  No device work."""
+    check_prior_config(config)
+    if not _get(config.run, "resume_checkpoint"):
+        raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect) needs run.resume_checkpoint, the -p checkpoint "
+                                  "of the prior; missing: run.resume_checkpoint")
+    section = _get(config, "detect")
+    missing = [k for k in DETECT_KEYS if section is None or not hasattr(section, k)]
+    if missing:
+        raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect) needs detect.{%s}; missing: %s"
+                                  % (", ".join(DETECT_KEYS), ", ".join(missing)))
+    if section.nll_threshold is None or isinstance(section.nll_threshold, bool):
+        raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect) needs a number for detect.nll_threshold, the "
+                                  "token_nll above which a code is restored; missing: detect.nll_threshold")
+    for key, allowed in (("against", DETECT_AGAINST), ("weight", DETECT_WEIGHT)):
+        if getattr(section, key) not in allowed:
+            raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect): detect.%s is one of %s (got %r)"
+                                      % (key, ", ".join(repr(a) for a in allowed), getattr(section, key)))
+    detect_labels(config)
 
 
 def latent_size(config):

@@ -7,6 +7,7 @@ class over the trainers of this package - no PyTorch-Lightning.
     Fit(config, trainer, logger).test()           result.csv of trainers.evaluation.Evaluator over the test loader
     Fit(config, trainer, logger).export()         training_mode 'inference': PNG + NIfTI of image, recon, label per slice
     Fit(config, trainer, logger).edit()           -p -m edit: PriorTrainer.edit over the first test slices -> pictures, codes, scores
+    Fit(config, trainer, logger).detect()         -p -m detect: PriorTrainer.detect over the test slices -> anomaly maps, AUROC / AP / Dice
 
 Nothing here reads a scalar from the device inside a step: the logged losses of a step go to the host in one small
 copy that is looked at two steps later (after that step's StepThrottle event), so the loop adds host work only.
@@ -52,10 +53,11 @@ def dataset_window(config):
     return None
 
 
-def build_loader(config, mode, seed=0, sampler=None, generator=None):
+def build_loader(config, mode, seed=0, sampler=None, generator=None, label_modality=None, lesions=None):
     """The reference's train / val / test loader (base.py:116-162) from config.dataset.  The file datasets shuffle their
     file list once at construction with Python's `random`: it is seeded from (seed, mode) around the construction - and
-    put back - so the list is the same in every process and run that names the same seed."""
+    put back - so the list is the same in every process and run that names the same seed.  label_modality / lesions: the opt-in
+    labels of get_data_loader (Fit.detect)."""
     d = config.dataset
     state = random.getstate()
     random.seed(int(seed) * 3 + ("train", "val", "test").index(mode))
@@ -66,7 +68,7 @@ def build_loader(config, mode, seed=0, sampler=None, generator=None):
             augmentations=_get(d, "augmentations") if mode == "train" else None, drop_last=mode == "train",
             window_width=_get(d, "window_width"), window_center=_get(d, "window_center"), window_scale=_get(d, "window_scale"),
             sampler=sampler, generator=generator, image_size=_get(d, "image_size"), n_samples=_get(d, "n_samples_" + mode),
-            seed=seed)
+            seed=seed, label_modality=label_modality, lesions=lesions)
     finally:
         random.setstate(state)
 
@@ -562,6 +564,74 @@ class Fit:
             f.write("\n".join(rows) + "\n")
         self.print("Edited slices are saved: {}".format(out_dir))
         return written
+
+    # ---------------------------------------------------------------- -p -m detect
+    def detect(self):
+        """`-p -m detect`: PriorTrainer.detect over the first detect.n_slices slices of the test split (0: all of it) with the prior
+        of run.resume_checkpoint.  Into the run directory: detect_<i>.png for the first save.n_save_images slices - three grey tiles
+        side by side: the slice, the restored slice, and the map over its own range; detect.csv - per slice: n_resampled, the mean
+        token_nll, the largest value of the map, the winner's score and, with labels, the slice's positive pixels;
+        with labels detect_result.csv - the eight values of ops.detection_scores over all scored pixels: the maps go into ONE
+        histogram on the device (ops.score_histogram per batch), read once at the end.  All draws come from one generator seeded
+        with detect.seed: a seed reproduces every file byte for byte."""
+        from .config import detect_labels
+        if not self.prior:
+            raise ValueError("detecting needs the prior trainer (-p)")
+        self._load_weights_for_test()
+        if self.rank != 0:
+            return None
+        e, tr = self.config.detect, self.trainer
+        n_slices = int(e.n_slices or 0)
+        label_modality, lesions = detect_labels(self.config)
+        labelled = label_modality is not None or lesions is not None
+        loader = build_loader(self.config, "test", self.data_seed, label_modality=label_modality, lesions=lesions)
+        n_save = int(_get(_get(self.config, "save"), "n_save_images", 0) or 0)
+        gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
+        out_dir = self.logger.log_dir
+        os.makedirs(out_dir, exist_ok=True)
+        hist, err = ops.new_score_histogram(self.device)
+        per_slice, done = [], 0                          # device tensors per batch: read once, after the loop
+        for batch in loader:
+            if n_slices and done >= n_slices:
+                break
+            take = n_slices - done if n_slices else None
+            image = self._to_device(batch)[:take]
+            out = tr.detect({"image": image}, nll_threshold=float(e.nll_threshold), n_candidates=int(e.n_candidates),
+                            temperature=float(e.temperature or 1.0), top_k=e.top_k or None, top_p=e.top_p or None,
+                            sigma=float(e.sigma or 0.0), against=e.against, weight=e.weight, generator=gen)
+            B = image.shape[0]
+            stats = [out["n_resampled"].double(), out["nll"].double().mean((1, 2)), out["map"].reshape(B, -1).max(1).values.double(),
+                     out["score"].double()]
+            if labelled:
+                label = batch["label"][:take].to(self.device).reshape(B, -1)
+                if label.shape[1] != out["map"][0].numel():
+                    raise ValueError("detect: a label of %d pixels per slice for a map of %d" % (label.shape[1], out["map"][0].numel()))
+                label = (label != 0).to(torch.uint8)
+                ops.score_histogram(out["map"], label, hist, err)
+                stats.append(label.sum(1, dtype=torch.long).double())
+            per_slice.append(torch.stack(stats, dim=1))
+            if done < n_save:
+                k = min(B, n_save - done)
+                tiles = [ops.export_grey(t[:k])[0].cpu().numpy() for t in (image, out["restored"])]
+                tiles.append(ops.export_grey_auto(out["map"][:k, None]).cpu().numpy())
+                for b in range(k):
+                    png.save(os.path.join(out_dir, "detect_%04d.png" % (done + b)), np.concatenate([t[b] for t in tiles], axis=1))
+            done += B
+        table = torch.cat(per_slice).cpu().numpy() if per_slice else np.zeros((0, 5 if labelled else 4))
+        with open(os.path.join(out_dir, "detect.csv"), "w") as f:
+            f.write("slice,n_resampled,mean_nll,max_map,score" + (",positives" if labelled else "") + "\n")
+            for i, row in enumerate(table):
+                f.write("%d,%d,%.9g,%.9g,%.17g" % (i, int(row[0]), row[1], row[2], row[3]) + (",%d" % int(row[4]) if labelled else "") + "\n")
+        result = None
+        if labelled:
+            result = dict(zip(ops.DETECTION_SCORES[:7], ops.detection_scores(hist, err).cpu().tolist()))      # the one read of the scores
+            result["err"] = int(err.cpu())
+            with open(os.path.join(out_dir, "detect_result.csv"), "w") as f:
+                f.write("auroc,ap,best_dice,best_threshold,P,N,err_free,err\n")
+                f.write("%.17g,%.17g,%.17g,%.9g,%d,%d,%d,%d\n" % (result["auroc"], result["ap"], result["best_dice"], result["best_threshold"],
+                                                               int(result["P"]), int(result["N"]), int(result["err_free"]), result["err"]))
+        self.print("Detection results are saved: {}".format(out_dir))
+        return result
 
     # ---------------------------------------------------------------- -m test
     def _load_weights_for_test(self):

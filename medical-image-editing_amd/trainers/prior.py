@@ -23,6 +23,10 @@ Editing (the launcher's -p -m edit).  token_nll(batch) is the prior's opinion of
 before it) as an (h, w) map.  edit(batch, mask | box | nll_threshold) redraws the selected codes n_candidates times with
 GPT.generate_masked, keeps every other code, scores each candidate by the log-probability of its whole sequence and pastes the best
 one back into the slice cell by cell (ops.paste_cells).
+
+Detecting (the launcher's -p -m detect).  detect(batch, nll_threshold) is one edit(nll_threshold=...) - the prior restores the codes
+it finds unlikely - and ops.anomaly_map of what was there against what the prior put there: the smoothed pixel residual, the
+anomaly map of a slice (Fit.detect scores it against lesion labels with ops.score_histogram / ops.detection_scores).
 """
 import math
 
@@ -284,6 +288,11 @@ class PriorTrainer(TrainerBase):
         Returns a dict: ids (B, T) the best candidate (source_ids: the slice's own codes); candidates (B, n, T) and scores (B, n) float64 in draw order; best (B,);
         cellmask (B, h, w) uint8; recon and edit, the slice's own codes and the best candidate's through decode_from_ids; and
         composite = ops.paste_cells(image, edit, cellmask).  A {'ids'} batch has no image and no composite."""
+        return self._edit(batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator)[0]
+
+    def _edit(self, batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator):
+        """edit()'s work -> (edit()'s dict, the token_nll map (B, h, w) the nll_threshold selector computed, else None): what edit
+        and detect share."""
         if (mask is not None) + (box is not None) + (nll_threshold is not None) != 1:
             raise ValueError("PriorTrainer.edit: exactly one of mask, box and nll_threshold selects the region")
         n = int(n_candidates)
@@ -295,8 +304,10 @@ class PriorTrainer(TrainerBase):
         B, T = ids.shape
         if T != self.h * self.w:
             raise ValueError("PriorTrainer.edit: sequences of h w = %d codes expected, got %d" % (self.h * self.w, T))
+        nll = None
         if nll_threshold is not None:
-            cells = (self._token_nll(ids).reshape(B, self.h, self.w) > float(nll_threshold)).cpu().numpy()      # the one read of the selector
+            nll = self._token_nll(ids).reshape(B, self.h, self.w)
+            cells = (nll > float(nll_threshold)).cpu().numpy()      # the one read of the selector
         else:
             cells = self.cell_mask(B, mask, box, tuple(image.shape[-2:]) if has_image else None)
         resample = np.repeat(cells.reshape(B, T), n, axis=0)
@@ -323,4 +334,41 @@ class PriorTrainer(TrainerBase):
                "recon": self.vqgan.decode_from_ids(ids, self.h, self.w), "edit": self.vqgan.decode_from_ids(best_ids, self.h, self.w)}
         if has_image:
             out["composite"] = ops.paste_cells(image, out["edit"], cellmask)
-        return out
+        return out, nll
+
+    # ---------------------------------------------------------------- anomaly detection
+    @torch.no_grad()
+    def detect(self, batch, nll_threshold, n_candidates=4, temperature=1.0, top_k=None, top_p=None, sigma=2.0, against="image",
+               weight="mask", generator=None):
+        """Unsupervised anomaly localisation: restore the codes the prior finds unlikely - ONE edit(nll_threshold=...), the same
+        draws under the same generator - and smooth the pixel residual between what was there and what the prior put there into a
+        map, ops.anomaly_map(a, b, cellmask, sigma) = G_sigma(mean_c |a - b| o U(cellmask)).
+
+        against='image': a = the slice, b = the composite (the winner pasted into the slice cell by cell); outside the restored
+        cells the residual is exactly 0, so a slice with no code above the threshold gets an all-zero map.
+        against='reconstruction': a = decode(the slice's own codes), b = decode(the winner's codes) - the VQGAN's own
+        reconstruction error cancels; a {'ids'} batch has this mode only.
+        weight='mask': the residual is weighted by the bilinearly up-sampled cell mask; weight='none': no cell mask is passed.
+
+        Returns a dict: map (B, H, W) fp32; restored (B, C, H, W) = b; nll (B, h, w), token_nll of the slice; cellmask (B, h, w)
+        uint8; score (B,) float64, the winner's log-probability; n_resampled (B,) long, the restored codes per slice."""
+        if nll_threshold is None:
+            raise ValueError("PriorTrainer.detect: nll_threshold selects the codes to restore and is required")
+        if against not in ("image", "reconstruction"):
+            raise ValueError("PriorTrainer.detect: against=%r must be 'image' or 'reconstruction'" % (against,))
+        if weight not in ("mask", "none"):
+            raise ValueError("PriorTrainer.detect: weight=%r must be 'mask' or 'none'" % (weight,))
+        ops.gauss_taps(sigma)                # a bad sigma is refused before any device work
+        if against == "image" and isinstance(batch, dict) and batch.get("ids") is not None:
+            raise ValueError("PriorTrainer.detect: against='image' needs a batch with an image ({'ids'} has none)")
+        out, nll = self._edit(batch, None, None, nll_threshold, n_candidates, temperature, top_k, top_p, generator)
+        if against == "image":
+            image = batch["image"] if isinstance(batch, dict) else batch
+            a, b = image.to(self.device), out["composite"]
+        else:
+            a, b = out["recon"], out["edit"]
+        cellmask = out["cellmask"]
+        amap = ops.anomaly_map(a, b, cellmask if weight == "mask" else None, sigma)
+        rows = torch.arange(cellmask.shape[0], device=self.device)
+        return {"map": amap, "restored": b, "nll": nll, "cellmask": cellmask, "score": out["scores"][rows, out["best"]],
+                "n_resampled": cellmask.reshape(cellmask.shape[0], -1).sum(1, dtype=torch.long)}
