@@ -25,6 +25,19 @@
 // Halo ring: two buffers suffice - the patch of item i+1 is read (and transformed) during item i, so the buffer of
 // item i is dead from the barrier that ends item i-1 and receives the halo of item i+2 during item i.
 //
+// Loader.  The weights (U) never pass through registers: k_wino_weights leaves them chunked as [Cin / 8][16 xi][Cout][8], so a
+// wave's load is 1 KB in a row and the LDS image of a chunk is lane-linear - one buffer_load_dwordx4 ... lds per slot writes
+// the wave's piece of U buffer PAR ^ 1 (wino::buf_ld4_lds).  The only irregularity of the image, the swap of a row's two
+// float4 halves by cout bit 3 (conflict-free B fragments), sits in the per-lane SOURCE address.  An item issues its U pieces
+// first (positions 1, 3, 5, 7: L2 hits, nothing held for them), the halo loads - the ones that come from HBM - behind them
+// (9, 13, 17) and commits the halo at positions 48..50, 33-39 MFMA positions after its loads (19-25 while four U register
+// sets shared the item with it).  The data is read behind the end-of-item wait + barrier; U buffer 1 doubles as the region
+// epilogue's exchange area, which is safe because a region's last item has odd parity and loads into buffer 0.  Against the
+// register-staged loader this form replaced (16 VGPRs of U, four ds_write_b128 per item and thread, a second U phase in the
+// four-wave form): the serialised kernel sum of a training step 30.2 -> 29.2 ms, 32->32 @256 input gradient 0.241 -> 0.225 ms,
+// the shapes with Cin >= 256 unchanged.  The halo keeps its registers: its 10-float padded pixel is not
+// lane-linear.
+//
 // The walk over a workgroup's run of regions, the halo stager and the transform vocabulary are shared with conv_wino.hip and
 // conv_wino_up.hip: wino_common.h, DESIGN section 6v (which also says what this kernel keeps a copy of, and why).
 #include "common.h"
@@ -100,11 +113,11 @@ template <int RW, int MBW, int NW = 8> struct W64Geo {
     static_assert(EXF >= UBUF, "U buffer 1 lives in the exchange area");
     static constexpr size_t LDS_FLOATS = 2 * HBUF + UBUF + EXF + 2 * NMB * NCO * 2;
 };
-constexpr int W6_LS = 4;                   // MFMA positions between two prefetch loads (a burst of 48 wave-loads stalls their issue;
+constexpr int W6_LS = 4;                   // MFMA positions between two halo loads (a burst of wave-loads stalls their issue;
                                            // 2 -> 4: 32->64 @256 dgrad 0.447 -> 0.425 ms, 64->128 @128 0.318 -> 0.306, nothing slower)
-constexpr int W6_CP = 26;                  // MFMA position of the first LDS commit of the prefetched data
-constexpr int W6_CP1 = 26;                 // ... of the 64-cout shape (MBW = 1), which has registers to hold the loads longer
-constexpr int W6_PB = 33, W6_CB = 58;      // second phase of U slots (four-wave workgroups): first issue, first commit
+constexpr int W6_ULS = 2;                  // ... between two direct U loads (L2 hits, no register behind them; 4: the same times)
+constexpr int W6_CP = 48;                  // MFMA position of the first LDS commit of the halo (26 while the U slots shared the
+                                           // item with it; 40 / 48 / 56 measure alike on the 64-cout shape, 40 loses 2 % on 32->32 @256)
 
 template <int RW, int MBW, int EPI, int NW = 8>
 __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
@@ -115,14 +128,10 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
     using Halo = wino::HaloStager<NT, G::HR, HWV, HWS, wino::PitchedPix>;     // 340 / 324 / 612 halo pixels = 680 / 648 / 1224 float4
     constexpr int LH = Halo::LH;               // 2 / 2 / 3 halo slots per thread
     constexpr int LU = 512 * NBW / NT;         // U slots per thread: 512 NBW float4 per chunk
-    // All slots in the first half of an item where they fit; otherwise the second half of the U slots forms a second phase
-    // (issued from position W6_PB on, committed from W6_CB on) that re-uses the registers of the first.
-    constexpr int CP = MBW == 1 ? W6_CP1 : W6_CP;
-    constexpr int CPMAX = MBW == 1 ? 64 : 32;
-    constexpr bool ONE_PHASE = 1 + (LH + LU) * W6_LS <= CP && CP + LH + LU <= CPMAX;
-    constexpr int LUA = ONE_PHASE ? LU : LU / 2;
-    static_assert(1 + (LH + LUA) * W6_LS <= CP && CP + LH + LUA <= CPMAX, "prefetch slots fit the first half of an item");
-    static_assert(ONE_PHASE || (LU == 2 * LUA && W6_PB + LUA * W6_LS <= W6_CB && W6_CB + LUA <= 64), "second U phase fits the second half");
+    // Slots of an item: the U pieces first (direct loads: nothing to hold), the halo loads behind them, the halo commits late.
+    // A halo commit waits for its load and so - loads return in order - for every U piece as well.
+    constexpr int HP0 = 1 + LU * W6_ULS;       // position of the first halo load
+    static_assert(HP0 + (LH - 1) * W6_LS < W6_CP && W6_CP + LH <= 64, "prefetch slots fit the item");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Hs = smem;                      // [2][HBUF]
@@ -154,21 +163,19 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
     // U float4 f = tid + NT j -> row = xi * NCO + n = (tid >> 1) + NT / 2 j, channel quad tid & 1
     // (a wave's slot = 32 couts x 32 bytes = 1 KB in a row of the chunked layout [Cin / 8][16 xi][Cout][8])
     const int u_n = (tid >> 1) & (NCO - 1);
-    const unsigned u_voff = (((unsigned)(tid >> 1) / NCO * Cout + co_base + u_n) * 8u + c4 * 4) * 4u;
+    const int u_swz = (u_n >> 3) & 1;                      // the float4 halves of a row are swapped in LDS for couts 8..15 of an N block
+    const int u_c4 = c4 ^ u_swz;                           // the lane's LDS slot is half c4 of its row (lane-linear), so the SOURCE half swaps
+    const unsigned u_voff = (((unsigned)(tid >> 1) / NCO * Cout + co_base + u_n) * 8u + u_c4 * 4) * 4u;
     const unsigned u_jstride = (unsigned)(NT / 2 / NCO) * Cout * 32u;      // NT / 2 rows = NT / 2 / NCO xi further per slot
     const unsigned u_cstride = 16u * Cout * 32u;                           // per 8-channel chunk
-    const int u_lds = (tid >> 1) * 8 + ((c4 ^ ((u_n >> 3) & 1)) * 4);      // + j * NT * 4 floats
+    const int u_wave = wv * 256;                           // the wave's 1 KB piece of a slot, in floats (+ lane * 16 bytes by the hardware)
 
-    float4 ru[LUA];
     auto issue_h = [&](int j, int chunk) { hs.issue_h(rsx, j, chunk); };
     auto commit_h = [&](int j, float* Hb) { hs.commit_h(j, Hb); };
-    auto issue_u = [&](int j, int chunk) {
-        u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsu, (int)u_voff, (int)(chunk * u_cstride + j * u_jstride), 0);
-        unsigned a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];
-        float4& r = ru[j % LUA];
-        r.x = __uint_as_float(a0); r.y = __uint_as_float(a1); r.z = __uint_as_float(a2); r.w = __uint_as_float(a3);
+    // U slot j of a chunk straight into U buffer Ub: no register, no commit (wino::buf_ld4_lds has the rules for reading it)
+    auto issue_u = [&](int j, int chunk, float* Ub) {
+        wino::buf_ld4_lds(rsu, Ub + u_wave + j * (NT * 4), u_voff, chunk * u_cstride + j * u_jstride);
     };
-    auto commit_u = [&](int j, float* Ub) { *(float4*)&Ub[u_lds + j * (NT * 4)] = ru[j % LUA]; };
 
     // ---- item cursors: (image, strip, region row, chunk) of items i, i+1, i+2.  This kernel keeps its own copy of
     // wino::ItemCursor and of wino::region_loop (same code, see there): through the shared ones some of its fifteen
@@ -258,20 +265,15 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
 #pragma unroll
     for (int j = 0; j < LH; ++j) issue_h(j, 0);
 #pragma unroll
-    for (int j = 0; j < LUA; ++j) issue_u(j, 0);
+    for (int j = 0; j < LU; ++j) issue_u(j, 0, Us);
 #pragma unroll
     for (int j = 0; j < LH; ++j) commit_h(j, Hs);
-#pragma unroll
-    for (int j = 0; j < LUA; ++j) commit_u(j, Us);
-#pragma unroll
-    for (int j = LUA; j < LU; ++j) issue_u(j, 0);
-#pragma unroll
-    for (int j = LUA; j < LU; ++j) commit_u(j, Us);
     region_offsets(n1, tx1, ty1);
 #pragma unroll
     for (int j = 0; j < LH; ++j) issue_h(j, ch1);
 #pragma unroll
     for (int j = 0; j < LH; ++j) commit_h(j, Hs + HBUF);
+    wino::dma_wait();                  // U chunk 0 has landed in this wave's piece; the barrier publishes every wave's
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < MBW; ++w)
@@ -302,15 +304,11 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
         auto ldb = [&](int l, int nb) {
             bf[l & 1][nb] = *(const f32x2*)&Uc[(l < 4 ? b_0 : b_1) + ((l & 3) * NCO + nb * 16) * 8];
         };
+        static_assert(par == 0 || (par ^ 1) == 0, "a region's last item (odd) loads U into buffer 0: buffer 1 is the epilogue's exchange area");
         auto slot = [&](int p) {       // p = 0..63: MFMA position (compile-time after unrolling)
-            if (p >= 1 && p < 1 + LH * W6_LS && (p - 1) % W6_LS == 0) issue_h((p - 1) / W6_LS, ch2);
-            if (p >= CP && p < CP + LH) commit_h(p - CP, Hw);
-            if (p >= 1 + LH * W6_LS && p < 1 + (LH + LUA) * W6_LS && (p - 1) % W6_LS == 0) issue_u((p - 1) / W6_LS - LH, ch1);
-            if (p >= CP + LH && p < CP + LH + LUA) commit_u(p - CP - LH, Uw);
-            if (!ONE_PHASE) {
-                if (p >= W6_PB && p < W6_PB + LUA * W6_LS && (p - W6_PB) % W6_LS == 0) issue_u(LUA + (p - W6_PB) / W6_LS, ch1);
-                if (p >= W6_CB && p < W6_CB + LUA) commit_u(LUA + p - W6_CB, Uw);
-            }
+            if (p >= 1 && p < HP0 && (p - 1) % W6_ULS == 0) issue_u((p - 1) / W6_ULS, ch1, Uw);
+            if (p >= HP0 && p < HP0 + LH * W6_LS && (p - HP0) % W6_LS == 0) issue_h((p - HP0) / W6_LS, ch2);
+            if (p >= W6_CP && p < W6_CP + LH) commit_h(p - W6_CP, Hw);
             xform_slot(Hn, par ^ 1, p);
         };
         // The item's first B fragments are requested right behind the barrier; the eight MFMAs of the PREVIOUS item's last xi
@@ -533,20 +531,27 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) k_conv_wino64(W64Args a) {
     using wino::P0;
     using wino::P1;
     // (wino::region_loop, written out: see the cursor above)
+    // End of an item: publishes the halo of item i+2 and the U chunk of item i+1.  Every wave first waits for its own U pieces
+    // (the halo commits have already waited for them: the wait is free and does not lean on the issue order), the barrier
+    // then covers the workgroup's.
+    auto item_end = [&]() {
+        wino::dma_wait();
+        __syncthreads();
+    };
     for (int reg = 0; reg < my_tiles; ++reg) {
         body(P0{}, std::true_type{});
-        __syncthreads();             // publishes the halo of item i+2 and the U chunk of item i+1
+        item_end();
         shift();
         body(P1{}, std::false_type{});
-        __syncthreads();
+        item_end();
         for (int c = 2; c < nch; c += 2) {
             shift();
             if (ch2 == 0) region_offsets(n2, tx2, ty2);   // item i+2 opens a region: its halo offsets
             body(P0{}, std::false_type{});
-            __syncthreads();
+            item_end();
             shift();
             body(P1{}, std::false_type{});
-            __syncthreads();
+            item_end();
         }
         // region (cn, ctx, cty) is complete
         flush();

@@ -1,6 +1,7 @@
 // Device code shared by the Winograd convolution kernels (conv_wino.hip, conv_wino64.hip, conv_wino_up.hip): the walk of a
-// workgroup over its run of regions, the halo stager of the 10-float LDS pixel and the transforms.  DESIGN section 6v is the
-// description; the kernels keep what distinguishes them (tile geometry, slot positions, operand builds, epilogues).
+// workgroup over its run of regions, the halo stager of the 10-float LDS pixel, the direct global -> LDS load and the
+// transforms.  DESIGN section 6v is the description; the kernels keep what distinguishes them (tile geometry, slot positions,
+// operand builds, epilogues).
 #pragma once
 #include "mfma_util.h"
 #include <type_traits>
@@ -151,6 +152,18 @@ struct HaloStager {
         *(f32x2*)(p + 2) = hi;
     }
 };
+
+// ---- direct global -> LDS load ------------------------------------------------------------------------------------------
+// 16 bytes per lane straight into LDS (buffer_load_dwordx4 ... offen lds): no VGPR destination, no ds_write.  The wave's
+// 64 x 16 bytes land in a row at lds_wave (wave-uniform; the hardware adds lane * 16): a layout that is not lane-linear is
+// reached through the per-lane SOURCE offset.  byte_off is range-checked like buf_ld4's (an out-of-range lane writes 0), soff
+// is not.  The load counts on vmcnt like any other; its data may be read only behind a wait that covers it (dma_wait) AND
+// the barrier behind that wait.
+__device__ __forceinline__ void buf_ld4_lds(__amdgpu_buffer_rsrc_t r, float* lds_wave, unsigned byte_off, unsigned soff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave, 16, (int)byte_off, (int)soff, 0, 0);
+}
+// s_waitcnt vmcnt(0) alone (gfx9 encoding: vmcnt in bits 3:0 and 15:14; expcnt 6:4 and lgkmcnt 11:8 stay at their maxima)
+__device__ __forceinline__ void dma_wait() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
 // ---- transforms -------------------------------------------------------------------------------------------------------
 // Row r of B^T d = (d0 - d2, d1 + d2, d2 - d1, d1 - d3); r is a constant after unrolling, so a call is one instruction.
