@@ -912,6 +912,25 @@ int vqw_adamw_step(float* p, const float* g, float* m, float* v, long n, double 
 int vqw_prior_tokens(const long* ids, const float* u_keep, const float* u_rand, long* inp, int B, int T, int V, long sos, float pkeep,
                      void* stream);
 
+/* ---- conditioning the code prior on label maps (csrc/cond.hip; networks.LabelCondition, trainers.ConditionalPriorTrainer;
+ * taming-transformers' recipe: one conditioning token per latent cell).  Added functions only; the ABI stays 9.  Integer counts, no
+ * float atomics: the same bits every run.  Every refusal arrives with a message before any launch.
+ * Cell labels: label [B][H][W] of elem_bytes = 1 (unsigned, torch.uint8), 4 or 8 (signed) byte integers, fy = H / h, fx = W / w
+ * with H % h == 0 and W % w == 0.  tokens[b][cy][cx] (torch.long) = the label in [0, n_labels) that most pixels of the cell carry;
+ * a tie goes to the smallest label; a pixel outside [0, n_labels) counts for nothing; a cell with no counted pixel gets -1.
+ * purity [B][h][w] (may be null) = float(the winner's count) / float(fy fx), one fp32 division; 0 for the -1 cell.  A workgroup
+ * takes one row of cells of one image (fewer cells where n_labels counters per cell would exceed 32 KB of LDS or the grid would be
+ * small), reads the image rows in 16-byte units at aligned addresses and counts with integer LDS atomics.  1 <= n_labels <= 256,
+ * B and h <= 65535, fy fx <= 2^24, label aligned to its element size.
+ * Cells changed: out[b][cy][cx] (bytes) = 1 iff any pixel of the cell differs between a and b, two maps of one shape and element
+ * size; the same walk, 16-byte units where the two pointers agree modulo 16.
+ * Table lookup: out[r] = table[idx[r]] for idx [rows] (torch.long), table [L][E], out [rows][E]; an index outside [0, L) writes a
+ * NaN row.  E a multiple of 4 with 4 <= E <= 4096, table and out 16-byte aligned.  Its gradient is vqw_embed_bwd's gtok. */
+int vqw_cell_labels(const void* label, long* tokens, float* purity, int B, int H, int W, int h, int w, int n_labels, int elem_bytes,
+                    void* stream);
+int vqw_cells_changed(const void* a, const void* b, uint8_t* out, int B, int H, int W, int h, int w, int elem_bytes, void* stream);
+int vqw_embed_lookup(const long* idx, const float* table, float* out, long rows, int E, int L, void* stream);
+
 /* ---- anomaly detection with the code prior (trainers/prior.py PriorTrainer.detect, trainers/fit.py Fit.detect; the reference has
  * nothing like it).  Added functions only; the ABI stays 9.  fp32 in, no float atomics, the same bits every run; every refusal below
  * arrives with a message before any launch.

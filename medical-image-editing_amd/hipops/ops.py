@@ -2066,6 +2066,94 @@ def prior_tokens(ids, sos, pkeep, vocab_size, u_keep=None, u_rand=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# conditioning the code prior on label maps (csrc/cond.hip): label tokens per latent cell, changed cells, the table lookup
+# ----------------------------------------------------------------------------------------------
+_LABEL_DTYPES = {torch.uint8: 1, torch.int32: 4, torch.long: 8}
+
+
+def _label_map(name, label, h, w):
+    """A label map (B, H, W) or (B, 1, H, W), contiguous, of a dtype in _LABEL_DTYPES -> (B, H, W, element size)."""
+    _dev(label)
+    if label.dtype not in _LABEL_DTYPES:
+        raise RuntimeError("%s: a label map of torch.uint8, torch.int32 or torch.long expected, got %s" % (name, label.dtype))
+    if label.dim() == 4 and label.shape[1] == 1:
+        shape = (label.shape[0],) + tuple(label.shape[2:])
+    elif label.dim() == 3:
+        shape = tuple(label.shape)
+    else:
+        raise RuntimeError("%s: a label map (B, H, W) or (B, 1, H, W) expected, got %s" % (name, tuple(label.shape)))
+    if not label.is_contiguous():
+        raise RuntimeError("%s: the label map must be contiguous" % name)
+    B, H, W = shape
+    if h < 1 or w < 1 or B < 1 or H < 1 or W < 1 or H % h or W % w:
+        raise RuntimeError("%s: H = %d and W = %d must be multiples of the cell grid %d x %d" % (name, H, W, h, w))
+    return B, H, W, _LABEL_DTYPES[label.dtype]
+
+
+def cell_labels(label, h, w, n_labels, want_purity=False):
+    """One conditioning token per latent cell: tokens (B, h, w) torch.long, the label in [0, n_labels) that most pixels of the cell
+    carry, from label (B, H, W) or (B, 1, H, W) torch.uint8 / int32 / long, contiguous, H % h == 0 and W % w == 0, 1 <= n_labels
+    <= 256.  A tie goes to the smallest label; a pixel outside [0, n_labels) counts for nothing; a cell with no counted pixel gets
+    -1 (a NaN row downstream).  want_purity: also (B, h, w) fp32 = float(the winner's count) / float(pixels per cell), 0 for the -1
+    cell.  Integer counts: the same bits every run.  No gradient."""
+    h, w, n_labels = int(h), int(w), int(n_labels)
+    B, H, W, es = _label_map("cell_labels", label, h, w)
+    if not 1 <= n_labels <= 256:
+        raise RuntimeError("cell_labels: n_labels=%d must lie in [1, 256]" % n_labels)
+    tokens = torch.empty((B, h, w), dtype=torch.long, device=label.device)
+    purity = torch.empty((B, h, w), dtype=torch.float32, device=label.device) if want_purity else None
+    _L().vqw_cell_labels(label, tokens, purity, B, H, W, h, w, n_labels, es)
+    return (tokens, purity) if want_purity else tokens
+
+
+def cells_changed(a, b, h, w):
+    """(B, h, w) torch.uint8: 1 iff any pixel of the latent cell differs between the label maps a and b (one dtype, one shape;
+    cell_labels' layouts).  No gradient."""
+    h, w = int(h), int(w)
+    B, H, W, es = _label_map("cells_changed", a, h, w)
+    _dev(b)
+    if b.dtype != a.dtype or tuple(b.shape) != tuple(a.shape) or not b.is_contiguous():
+        raise RuntimeError("cells_changed: two contiguous label maps of one dtype and shape expected, got %s of %s and %s of %s" % (
+            tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
+    out = torch.empty((B, h, w), dtype=torch.uint8, device=a.device)
+    _L().vqw_cells_changed(a, b, out, B, H, W, h, w, es)
+    return out
+
+
+class _EmbeddingLookup(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, idx, table):
+        _dev(idx, table)
+        idx, table = _long(idx, "embedding_lookup: idx"), _flat(table)
+        if idx.dim() != 2 or table.dim() != 2 or idx.numel() < 1:
+            raise RuntimeError("embedding_lookup: idx (B, T) and table (L, E) expected, got %s and %s" % (tuple(idx.shape), tuple(table.shape)))
+        (B, T), (L, E) = idx.shape, table.shape
+        out = torch.empty(B, T, E, dtype=torch.float32, device=table.device)
+        _L().vqw_embed_lookup(idx, table, out, B * T, E, L)
+        ctx.save_for_backward(idx)
+        ctx.cfg = (B, T, E, L)
+        return out
+
+    @staticmethod
+    def backward(ctx, gx):
+        # the one embedding gradient (vqw_embed_bwd: a wave owns a table row, ascending (b, t), no sort, no atomics) with no prefix
+        # and T positions; the position sums it writes beside the table's gradient are not used
+        (idx,) = ctx.saved_tensors
+        B, T, E, L = ctx.cfg
+        gx = _flat(gx)
+        gtable = torch.empty(L, E, dtype=torch.float32, device=gx.device)
+        gpos = torch.empty(T, E, dtype=torch.float32, device=gx.device)
+        _L().vqw_embed_bwd(idx, gx, gtable, gpos, B, T, 0, E, L, T, 0)
+        return None, gtable
+
+
+def embedding_lookup(idx, table):
+    """table[idx]: idx (B, T) torch.long, table (L, E) fp32 -> (B, T, E), a plain gather with a gradient to table - ops.embedding's
+    deterministic one.  An index outside [0, L) gives a NaN row and no gradient."""
+    return _EmbeddingLookup.apply(idx, table)
+
+
+# ----------------------------------------------------------------------------------------------
 # cached generation (networks/gpt.py GPT.decode_step / generate): the decode kernels.  Forward only.
 # ----------------------------------------------------------------------------------------------
 def _no_grad(name, *ts):

@@ -13,3 +13,4 @@ from .vqgan import Normalize, nonlinearity, Upsample, ResnetBlock, AttnBlock, De
 from .vqgan_model import Downsample, Encoder, VQGAN  # noqa: F401
 from .mingpt import GPTConfig, GPT1Config, CausalSelfAttention, Block  # noqa: F401
 from .gpt import GPT, KVCache  # noqa: F401
+from .label_condition import LabelCondition  # noqa: F401

@@ -6,6 +6,9 @@ a seed gives the reference's initial values and a reference checkpoint loads wit
 position embedding, with the reference's optional `embeddings=` prefix), the blocks, ops.layer_norm and ops.linear without bias; the
 loss of the prior is ops.cross_entropy, a token is drawn by ops.sample_topk.
 
+GPT.forward_tail(idx, embeddings, n_tail) is forward() with ln_f and the head on the last n_tail positions only: behind a conditioning
+prefix (trainers/cond_prior.py) the prefix's rows of the head and of the logits are never computed.
+
 Dropout: `drop` exists (the trees match); at p = 0 or in eval mode it is the identity.  GPT.seed_dropout(seed, call=0) numbers the
 sites of the tree - 0 is `drop`, then per block att_drop, att.res_drop, mlp[3] - and stores seed and call; a training forward of a
 seeded model runs ops.dropout behind the embedding, the attention kernels' dropout policy and ops.add_dropout in the residual
@@ -110,6 +113,35 @@ class GPT(SeededDropout, nn.Module):
         for block in self.blocks:
             x = block._forward(x, None, call)[0]
         x = self._head(x)
+        if call is not None:
+            self.set_dropout_call(call + 1)
+        return x
+
+    def _trunk(self, idx, embeddings):
+        """Everything of a training or evaluation forward in front of ln_f: embedding, its dropout, the blocks -> (x, the dropout call
+        or None).  forward() has the same lines in place (it is the reference's method and stays as it was)."""
+        call = self._dropout_call()
+        x = ops.embedding(idx, self.tok_embed.weight, self.pos_embed, embeddings)
+        if call is not None and self.drop.p > 0:
+            x = ops.dropout(x, self.drop.p, self._key(call, self.dropout_site))
+        for block in self.blocks:
+            x = block._forward(x, None, call)[0]
+        return x, call
+
+    def forward_tail(self, idx, embeddings=None, n_tail=None):
+        """forward() up to the last block, then ln_f and head on the last n_tail positions only -> (B, n_tail, V): behind a
+        conditioning prefix (`embeddings`) the prefix's rows of the head and of the logits are never computed.  n_tail None:
+        idx's own positions.  With n_tail = every position it is forward() bit for bit.  Dropout bookkeeping is forward()'s: the
+        same sites under the same call, which it advances by one."""
+        self._check_dropout()
+        t = self._new_tokens(idx, embeddings)
+        n_tail = idx.shape[1] if n_tail is None else int(n_tail)
+        if t > self.block_size:
+            raise RuntimeError("GPT: cannot forward T=%d tokens, the model's block_size=%d is exhausted" % (t, self.block_size))
+        if not 1 <= n_tail <= t:
+            raise ValueError("GPT.forward_tail: n_tail=%d must lie in [1, T = %d]" % (n_tail, t))
+        x, call = self._trunk(idx, embeddings)
+        x = self._head(x[:, t - n_tail:])
         if call is not None:
             self.set_dropout_call(call + 1)
         return x

@@ -1,0 +1,37 @@
+"""The condition of a conditional code prior (trainers/cond_prior.py): a label map becomes one conditioning token per latent cell
+and the tokens are embedded by a table of their own - taming-transformers' recipe for a segmentation-conditioned transformer,
+restated.  The table lives outside the GPT, whose state_dict keys stay the reference's; the embedded tokens go in front of the
+code sequence through the GPT's `embeddings=` prefix.
+"""
+import torch
+import torch.nn as nn
+
+from hipops import ops
+
+
+class LabelCondition(nn.Module):
+    """tokens(label): (B, H, W) or (B, 1, H, W) integer label map -> (B, h w) torch.long in raster order, ops.cell_labels (the
+    majority label of each cell; -1 for a cell with no pixel in [0, n_labels)).  forward(tokens): (B, h w) -> (B, h w, n_embed),
+    ops.embedding_lookup in `embed.weight` (n_labels, n_embed), the module's one parameter, drawn N(0, 0.02) like the GPT's."""
+
+    def __init__(self, n_labels, n_embed, h, w):
+        super().__init__()
+        n_labels, n_embed, h, w = int(n_labels), int(n_embed), int(h), int(w)
+        if not 1 <= n_labels <= 256:
+            raise ValueError("LabelCondition: n_labels=%d must lie in [1, 256]" % n_labels)
+        if n_embed < 4 or n_embed % 4:
+            raise ValueError("LabelCondition: n_embed=%d must be a positive multiple of 4" % n_embed)
+        if h < 1 or w < 1:
+            raise ValueError("LabelCondition: the latent grid h=%d, w=%d must be positive" % (h, w))
+        self.n_labels, self.n_embed, self.h, self.w = n_labels, n_embed, h, w
+        self.embed = nn.Embedding(n_labels, n_embed)
+        nn.init.normal_(self.embed.weight, mean=0.0, std=0.02)
+
+    @torch.no_grad()
+    def tokens(self, label):
+        return ops.cell_labels(label, self.h, self.w, self.n_labels).reshape(label.shape[0], self.h * self.w)
+
+    def forward(self, tokens):
+        if tokens.dim() != 2 or tokens.shape[1] != self.h * self.w:
+            raise ValueError("LabelCondition: tokens (B, h w) = (B, %d) expected, got %s" % (self.h * self.w, tuple(tokens.shape)))
+        return ops.embedding_lookup(tokens, self.embed.weight)

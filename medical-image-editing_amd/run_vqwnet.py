@@ -3,6 +3,7 @@
     python run_vqwnet.py -c CONFIG [-m train|test] [-w] [-v | -p]
     python run_vqwnet.py -c CONFIG -p -m edit
     python run_vqwnet.py -c CONFIG -p -m detect
+    python run_vqwnet.py -c CONFIG -p -m synth
 
 run.training_mode picks the work: `first_step` / `second_step` train (-m train) or are scored (-m test: result.csv in the
 run directory); `inference` (-m test only) exports PNG and NIfTI files per slice.  -w selects the multi-window step and
@@ -20,7 +21,11 @@ first edit.n_slices test slices, edit.n_candidates times each, and keeps the lik
 of run.resume_checkpoint restores the codes whose token_nll exceeds detect.nll_threshold, the smoothed pixel residual is the
 anomaly map of a slice (ops.anomaly_map), and with detect.labels the maps are scored against the lesion labels - AUROC, average
 precision and the best Dice over all pixels (detect_result.csv beside detect.csv and the pictures in the run directory).  -m detect
-without -p, or with -v, is refused.
+without -p, or with -v, is refused.  With model.prior.cond the prior is conditioned on the label maps the loaders deliver
+(trainers/cond_prior.py: one conditioning token per latent cell in front of the codes); -p -m synth (Fit.synth) then draws slices
+from the label maps of the first synth.n_slices test slices and, with synth.discs, edits each slice through its label map -
+pictures and synth.csv under <run dir>/synth/.  -m synth without -p, without model.prior.cond or without run.resume_checkpoint is
+refused, and so is -m detect with model.prior.cond.
 
 One process per GPU.  With run.num_gpus == 1 this process is the worker.  With more, this process never touches the GPU:
 it starts num_gpus fresh interpreters of this file (`--rank r`, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their
@@ -46,7 +51,7 @@ TRAINING_MODES = ("first_step", "second_step", "inference")
 def build_parser():
     parser = argparse.ArgumentParser(description="Train, score or export a VQ-W-Net from a JSON config")
     parser.add_argument("-c", "--config", required=True, help="path of the JSON config")
-    parser.add_argument("-m", "--mode", default="train", help="train (default), test, or edit / detect (with -p)")
+    parser.add_argument("-m", "--mode", default="train", help="train (default), test, or edit / detect / synth (with -p)")
     parser.add_argument("-w", "--multiwindow", action="store_true", help="multi-window training step")
     parser.add_argument("-v", "--vqgan", action="store_true", help="train the VQGAN (model.vqgan) with the U-Net discriminator; overrides -w")
     parser.add_argument("-p", "--prior", action="store_true", help="train the GPT code prior (model.prior) on the codes of the VQGAN (model.vqgan)")
@@ -90,8 +95,17 @@ def check_arguments(config, args):
             raise ValueError("-m detect: detection restores the unlikely codes with the code prior and needs -p")
         from trainers.config import check_detect_config
         check_detect_config(config)             # NotImplementedError naming the missing keys of the `detect` section
+        from trainers.config import prior_condition
+        if prior_condition(config) is not None:
+            raise NotImplementedError("-m detect with model.prior.cond: a prior conditioned on the lesion labels is told where the lesion "
+                                      "is; detection needs the unconditional prior")
+    elif args.mode == "synth":
+        if not prior:
+            raise ValueError("-m synth: synthesis draws slices from label maps with the conditional code prior and needs -p")
+        from trainers.config import check_synth_config
+        check_synth_config(config)              # NotImplementedError naming the missing part
     elif args.mode not in ("train", "test"):
-        raise ValueError("-m %r: the mode is 'train' or 'test' (or, with -p, 'edit' or 'detect')" % (args.mode,))
+        raise ValueError("-m %r: the mode is 'train' or 'test' (or, with -p, 'edit', 'detect' or 'synth')" % (args.mode,))
     mode = _get(config.run, "training_mode", "first_step")
     if mode not in TRAINING_MODES:
         raise ValueError("run.training_mode %r: one of %s" % (mode, ", ".join(TRAINING_MODES)))
@@ -235,6 +249,8 @@ def worker(config, args, training_mode, rank, world_size, seed):
             fit.edit()
         elif args.mode == "detect":
             fit.detect()
+        elif args.mode == "synth":
+            fit.synth()
         elif args.mode == "train":
             fit.fit()
         else:

@@ -1,0 +1,163 @@
+"""The code prior conditioned on a label map (the launcher's -p with model.prior.cond): p(codes | label tokens), taming-transformers'
+recipe for a segmentation-conditioned transformer restated on this project's kernels.
+
+A label map becomes one conditioning token per latent cell (networks.LabelCondition.tokens, ops.cell_labels: the majority label of
+the cell) and the Tc = h w tokens, embedded by a table of their own, stand in front of the code sequence as a fully visible prefix:
+the GPT runs with n_unmasked = Tc on [cond embeddings | sos, code 0 .. code T - 2] and GPT.forward_tail leaves the prefix's rows
+out of ln_f, the head and the loss.  Positions: Tc + T <= block_size.  The start token and the pkeep corruption are the
+unconditional trainer's, on the codes only.  The table's one parameter joins the undecayed group of the fused AdamW: the global
+gradient norm and the clip cover it.
+
+Batches: {'image', 'label'} (codes from the frozen VQGAN, tokens from the label map) or {'ids', 'cond'} with cond (B, Tc)
+torch.long; 'cond', where a batch has it, is the prefix.
+
+synthesize(label | cond) draws every code from the label alone; edit(batch, new_label=...) redraws the cells whose label changed
+under the new label's prefix and keeps every other code.  detect is refused: lesion labels as a condition would leak the answer.
+"""
+import numpy as np
+import torch
+
+from hipops import AdamW, ops
+from networks.label_condition import LabelCondition
+
+from .prior import PriorTrainer, parameter_groups
+
+
+class ConditionalPriorTrainer(PriorTrainer):
+    def __init__(self, vqgan, gpt, cond, pkeep=1.0, sos_token=0, lr=4.5e-4, betas=(0.9, 0.95), weight_decay=0.01, grad_norm_clip=1.0,
+                 warmup_steps=0, decay_steps=0, seed=0, device="cuda", dropout_seed=None):
+        if not isinstance(cond, LabelCondition):
+            raise TypeError("ConditionalPriorTrainer conditions on a networks.LabelCondition")
+        self._cond_grid = (cond.h, cond.w)          # read by _latent_grid inside the parent's constructor
+        super().__init__(vqgan, gpt, pkeep=pkeep, sos_token=sos_token, lr=lr, betas=betas, weight_decay=weight_decay,
+                         grad_norm_clip=grad_norm_clip, warmup_steps=warmup_steps, decay_steps=decay_steps, seed=seed, device=device,
+                         dropout_seed=dropout_seed)
+        T = self.h * self.w
+        if cond.n_embed != gpt.config.n_embed:
+            raise ValueError("ConditionalPriorTrainer: the condition's n_embed=%d must equal the GPT's n_embed=%d" % (cond.n_embed, gpt.config.n_embed))
+        if gpt.block_size < 2 * T:
+            raise ValueError("ConditionalPriorTrainer: the GPT's block_size=%d must be at least Tc + T = 2 h w = %d" % (gpt.block_size, 2 * T))
+        if gpt.config.n_unmasked != T:
+            raise ValueError("ConditionalPriorTrainer: the GPT's n_unmasked=%d must be Tc = h w = %d, the fully visible conditioning prefix" % (
+                gpt.config.n_unmasked, T))
+        self.cond = cond.to(self.device).train()
+        self.Tc = T
+        groups, self.group_names = parameter_groups(self.gpt, weight_decay)
+        groups[1]["params"].append(self.cond.embed.weight)          # an embedding table: undecayed, as the GPT's own
+        self.optim = AdamW(groups, lr=lr, betas=tuple(betas), weight_decay=weight_decay, max_grad_norm=grad_norm_clip)
+
+    def _latent_grid(self, vqgan):
+        """The condition's grid: the square one of the VQGAN's own resolution, or that of the pictures a run feeds the (fully
+        convolutional) VQGAN; codes() holds every batch to it."""
+        return self._cond_grid
+
+    def modules(self):
+        return {"decoder": self.vqgan, "transformer": self.gpt, "cond": self.cond}
+
+    def codes(self, batch):
+        ids = super().codes(batch)
+        if ids.shape[1] != self.h * self.w:
+            raise ValueError("ConditionalPriorTrainer: sequences of h w = %d x %d = %d codes expected, got %d" % (self.h, self.w, self.h * self.w, ids.shape[1]))
+        return ids
+
+    # ---------------------------------------------------------------- the prefix
+    def cond_tokens(self, batch):
+        """The conditioning tokens (B, Tc) torch.long of a batch: its 'cond', else LabelCondition.tokens of its 'label'."""
+        if not isinstance(batch, dict) or (batch.get("cond") is None and batch.get("label") is None):
+            has_ids = isinstance(batch, dict) and batch.get("ids") is not None
+            raise ValueError("ConditionalPriorTrainer: the batch has no '%s'" % ("cond" if has_ids else "label"))
+        if batch.get("cond") is not None:
+            tokens = batch["cond"].to(self.device)
+        else:
+            tokens = self.cond.tokens(self._label(batch["label"]))
+        if tokens.dim() != 2 or tokens.shape[1] != self.Tc or tokens.dtype != torch.long:
+            raise ValueError("ConditionalPriorTrainer: cond (B, Tc) = (B, %d) torch.long expected, got %s of %s" % (self.Tc, tuple(tokens.shape), tokens.dtype))
+        return tokens
+
+    def _label(self, label):
+        return label.to(self.device).contiguous()
+
+    def _prefix(self, batch):
+        return self.cond(self.cond_tokens(batch))
+
+    def _logits(self, inp, prefix):
+        return self.gpt.forward_tail(inp, prefix, n_tail=inp.shape[1])
+
+    # ---------------------------------------------------------------- sampling
+    def sample_ids(self, n, temperature=1.0, top_k=None, generator=None):
+        raise NotImplementedError("ConditionalPriorTrainer: sampling needs a condition: synthesize(label=...) or synthesize(cond=...)")
+
+    @torch.no_grad()
+    def synthesize(self, label=None, cond=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None, generator=None, uniforms=None):
+        """Slices from label maps alone: every code is drawn.  label (B, H, W) or (B, 1, H, W), or cond (B, Tc) torch.long - exactly
+        one.  ONE GPT.generate_masked call behind the prompt [cond prefix | sos] draws all B n_candidates rows with every position
+        resampled (the uniforms per candidate, candidate 0 first, as edit draws them); a candidate's score is the sum of its logp in
+        double and the first maximum wins.  uniforms (n_candidates, T, B): the draws, in place of the generator.  Returns a dict: ids (B, T) the winner, candidates (B, n, T), scores (B, n) float64, best
+        (B,), cond (B, Tc) and image, the winner through decode_from_ids."""
+        if (label is None) == (cond is None):
+            raise ValueError("ConditionalPriorTrainer.synthesize: exactly one of label and cond gives the condition")
+        n = int(n_candidates)
+        if n < 1:
+            raise ValueError("ConditionalPriorTrainer.synthesize: n_candidates=%r must be at least 1" % (n_candidates,))
+        tokens = self.cond_tokens({"cond": cond} if cond is not None else {"label": label})
+        B, T = tokens.shape[0], self.h * self.w
+        start = torch.full((B * n, 1), self.sos_token, dtype=torch.long, device=self.device)
+        known = torch.zeros((B * n, T), dtype=torch.long, device=self.device)
+        if uniforms is None:
+            uniforms = torch.stack([torch.rand(T, B, generator=generator, device=self.device) for _ in range(n)])
+        elif tuple(uniforms.shape) != (n, T, B):
+            raise ValueError("ConditionalPriorTrainer.synthesize: uniforms of shape %s, (n_candidates, T, B) = (%d, %d, %d) expected" % (
+                tuple(uniforms.shape), n, T, B))
+        uniforms = uniforms.to(device=self.device, dtype=torch.float32).permute(1, 2, 0).reshape(T, B * n)
+        was_training = self.gpt.training
+        self.gpt.eval()
+        try:
+            drawn, logp = self.gpt.generate_masked(start, known, np.ones(T, dtype=bool), temperature=temperature, top_k=top_k, top_p=top_p,
+                                                   uniforms=uniforms, embeddings=self.cond(tokens).repeat_interleave(n, dim=0))
+        finally:
+            self.gpt.train(was_training)
+        scores = logp.double().sum(1).reshape(B, n)
+        best = torch.from_numpy(np.argmax(scores.cpu().numpy(), axis=1)).to(self.device)      # the read of the ranking; first maximum
+        candidates = drawn.reshape(B, n, T)
+        ids = candidates[torch.arange(B, device=self.device), best]
+        return {"ids": ids, "candidates": candidates, "scores": scores, "best": best, "cond": tokens,
+                "image": self.vqgan.decode_from_ids(ids, self.h, self.w)}
+
+    # ---------------------------------------------------------------- editing
+    @torch.no_grad()
+    def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None,
+             generator=None, new_label=None):
+        """PriorTrainer.edit under a condition, with a fourth selector: exactly one of mask, box, nll_threshold and new_label.
+        With mask, box or nll_threshold the prefix is the batch's own condition.  new_label (the batch's 'label' with the user's
+        changes drawn in; same dtype and shape): the prefix comes from new_label, the redrawn cells are those in which any pixel of
+        the label changed (ops.cells_changed; one device-to-host read) and every other code is kept.  Returns the parent's dict plus
+        cond (B, Tc), the tokens of the prefix, and label_cells (B, h, w), the same tokens as a map over the latent."""
+        if (mask is not None) + (box is not None) + (nll_threshold is not None) + (new_label is not None) != 1:
+            raise ValueError("ConditionalPriorTrainer.edit: exactly one of mask, box, nll_threshold and new_label selects the region")
+        cells = None
+        has_label = isinstance(batch, dict) and batch.get("label") is not None
+        label_size = tuple(batch["label"].shape[-2:]) if has_label else None          # what a mask or box of an {'ids'} batch refers to
+        if new_label is not None:
+            if not isinstance(batch, dict) or batch.get("label") is None:
+                raise ValueError("ConditionalPriorTrainer.edit: new_label needs the batch's own 'label' to compare against")
+            changed = ops.cells_changed(self._label(batch["label"]), self._label(new_label), self.h, self.w)
+            cells = changed.cpu().numpy() != 0                         # the one read of the selector
+            tokens = self.cond.tokens(self._label(new_label))
+        else:
+            tokens = self.cond_tokens(batch)
+        out = self._edit(dict(batch, cond=tokens), mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator, cells=cells,
+                         image_size=label_size)[0]
+        out["cond"], out["label_cells"] = tokens, tokens.reshape(-1, self.h, self.w)
+        return out
+
+    def cell_mask(self, B, mask=None, box=None, image_size=None):
+        """The parent's; without image_size: the VQGAN's resolution where the latent grid divides it, else the grid itself (a mask
+        at code resolution, a box in cells)."""
+        if image_size is None:
+            res = int(self.vqgan.encoder.resolution)
+            image_size = (res, res) if res % self.h == 0 and res % self.w == 0 else (self.h, self.w)
+        return super().cell_mask(B, mask, box, image_size)
+
+    def detect(self, *args, **kwargs):
+        raise NotImplementedError("ConditionalPriorTrainer.detect: a prior conditioned on the labels would be told where the lesion is; "
+                                  "anomaly detection needs the unconditional PriorTrainer")

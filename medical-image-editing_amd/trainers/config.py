@@ -21,6 +21,9 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
     config.model.prior.{n_layer, n_head, n_embed, n_unmasked, pkeep, sos_token}, config.prior_optim.{lr, b1, b2, weight_decay,
                  grad_norm_clip, warmup_steps, decay_steps}    (the GPT code prior, -p: keys of this project, the reference has
                  no trainer for its GPT; trainers/prior.py)
+    config.model.prior.cond.{source, n_labels, labels} (optional: the prior conditioned on label maps, trainers/cond_prior.py) and
+                 config.synth.{n_slices, n_candidates, temperature, top_k, top_p, seed, discs}, config.run.resume_checkpoint
+                 (synthesis from label maps, -p -m synth: keys of this project; Fit.synth)
     config.edit.{n_slices, n_candidates, temperature, top_k, top_p, seed} and one of edit.{box, mask_path, nll_threshold},
                  config.run.resume_checkpoint    (editing with the prior, -p -m edit: keys of this project; Fit.edit)
     config.detect.{n_slices, n_candidates, temperature, top_k, top_p, seed, nll_threshold, sigma, against, weight, labels},
@@ -163,10 +166,9 @@ DETECT_AGAINST, DETECT_WEIGHT = ("image", "reconstruction"), ("mask", "none")
 DETECT_LESION_KEYS = ("n", "radius", "contrast")
 
 
-def detect_labels(config):
-    """config.detect.labels -> (label_modality or None, synthetic lesions {n, radius, contrast} or None): `false` (no labels), a
+def _labels(labels, what, where):
+    """A `labels` entry -> (label_modality or None, synthetic lesions {n, radius, contrast} or None): `false` (no labels), a
     modality name (MICCAIBraTSDataset's sibling files), or {"synthetic": {n, radius, contrast}}."""
-    labels = _get(config.detect, "labels")
     if labels is None or labels is False:
         return None, None
     if isinstance(labels, str):
@@ -174,9 +176,66 @@ def detect_labels(config):
     lesions = _get(labels, "synthetic")
     missing = [k for k in DETECT_LESION_KEYS if lesions is None or not hasattr(lesions, k)]
     if missing:
-        raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect): detect.labels is false, a modality name or "
-                                  "{\"synthetic\": {%s}}; missing: %s" % (", ".join(DETECT_LESION_KEYS), ", ".join("detect.labels.synthetic." + k for k in missing)))
+        raise NotImplementedError("%s: %s is false, a modality name or "
+                                  "{\"synthetic\": {%s}}; missing: %s" % (what, where, ", ".join(DETECT_LESION_KEYS), ", ".join("%s.synthetic.%s" % (where, k) for k in missing)))
     return None, {k: getattr(lesions, k) for k in DETECT_LESION_KEYS}
+
+
+def detect_labels(config):
+    """config.detect.labels -> (label_modality or None, synthetic lesions {n, radius, contrast} or None): `false` (no labels), a
+    modality name (MICCAIBraTSDataset's sibling files), or {"synthetic": {n, radius, contrast}}."""
+    return _labels(_get(config.detect, "labels"), "detecting with the prior (run_vqwnet.py -p -m detect)", "detect.labels")
+
+
+COND_KEYS = ("source", "n_labels", "labels")
+
+
+def prior_condition(config):
+    """The optional model.prior.cond = {"source": "label", "n_labels": N, "labels": ...} -> None (absent or `false`: the
+    unconditional prior) or {n_labels, label_modality, lesions}: the label maps the loaders deliver beside the slices (`labels` in
+    detect.labels' two forms) become one conditioning token per latent cell (trainers/cond_prior.py)."""
+    cond = _get(_get(config.model, "prior"), "cond")
+    if cond is None or cond is False:
+        return None
+    what = "the conditional prior (run_vqwnet.py -p with model.prior.cond)"
+    missing = [k for k in COND_KEYS if not hasattr(cond, k)]
+    if missing:
+        raise NotImplementedError("%s needs model.prior.cond.{%s}; missing: %s" % (what, ", ".join(COND_KEYS), ", ".join(missing)))
+    if cond.source != "label":
+        raise NotImplementedError("%s: model.prior.cond.source is 'label', one token per latent cell from a label map (got %r); other "
+                                  "conditions are not built" % (what, cond.source))
+    if isinstance(cond.n_labels, bool) or not isinstance(cond.n_labels, int) or not 1 <= cond.n_labels <= 256:
+        raise ValueError("%s: model.prior.cond.n_labels=%r must be an integer in [1, 256]" % (what, cond.n_labels))
+    label_modality, lesions = _labels(cond.labels, what, "model.prior.cond.labels")
+    if label_modality is None and lesions is None:
+        raise NotImplementedError("%s needs label maps: model.prior.cond.labels is a modality name or {\"synthetic\": {%s}}; missing: "
+                                  "model.prior.cond.labels" % (what, ", ".join(DETECT_LESION_KEYS)))
+    return {"n_labels": int(cond.n_labels), "label_modality": label_modality, "lesions": lesions}
+
+
+SYNTH_KEYS = ("n_slices", "n_candidates", "temperature", "top_k", "top_p", "seed", "discs")
+
+
+def check_synth_config(config):
+    """NotImplementedError unless the config describes a synthesis run (run_vqwnet.py -p -m synth): check_prior_config's keys,
+    model.prior.cond, run.resume_checkpoint (the -p checkpoint of the conditional prior) and the seven keys of the `synth` section;
+    synth.discs is `false` or a list of [cy, cx, radius, value] drawn into the label map for edit(new_label=...).  No device work."""
+    check_prior_config(config)
+    if prior_condition(config) is None:
+        raise NotImplementedError("synthesising from label maps (run_vqwnet.py -p -m synth) needs a conditional prior; missing: "
+                                  "model.prior.cond")
+    if not _get(config.run, "resume_checkpoint"):
+        raise NotImplementedError("synthesising from label maps (run_vqwnet.py -p -m synth) needs run.resume_checkpoint, the -p checkpoint "
+                                  "of the conditional prior; missing: run.resume_checkpoint")
+    section = _get(config, "synth")
+    missing = [k for k in SYNTH_KEYS if section is None or not hasattr(section, k)]
+    if missing:
+        raise NotImplementedError("synthesising from label maps (run_vqwnet.py -p -m synth) needs synth.{%s}; missing: %s"
+                                  % (", ".join(SYNTH_KEYS), ", ".join("synth." + k for k in missing)))
+    discs = section.discs
+    if discs is not None and discs is not False:
+        if not isinstance(discs, (list, tuple)) or any(not isinstance(d, (list, tuple)) or len(d) != 4 for d in discs):
+            raise ValueError("synth.discs is false or a list of [cy, cx, radius, value] (got %r)" % (discs,))
 
 
 def check_detect_config(config):
@@ -217,13 +276,20 @@ def configure_prior(config):
     from networks import GPT
     p = config.model.prior
     side = latent_size(config)
-    return GPT(vocab_size=config.model.vqgan.dict_size, block_size=int(_get(p, "block_size") or side * side), n_layer=p.n_layer,
-               n_head=p.n_head, n_embed=p.n_embed, n_unmasked=int(p.n_unmasked or 0),
+    positions, n_unmasked = side * side, int(p.n_unmasked or 0)
+    if prior_condition(config) is not None:          # [h w conditioning tokens | h w codes], the prefix fully visible
+        if n_unmasked not in (0, side * side):
+            raise ValueError("model.prior.n_unmasked=%d with model.prior.cond: the conditioning prefix is the latent's h w = %d tokens "
+                             "(0 or `false` leaves it to the condition)" % (n_unmasked, side * side))
+        positions, n_unmasked = 2 * side * side, side * side
+    return GPT(vocab_size=config.model.vqgan.dict_size, block_size=int(_get(p, "block_size") or positions), n_layer=p.n_layer,
+               n_head=p.n_head, n_embed=p.n_embed, n_unmasked=n_unmasked,
                **{k: float(_get(p, k) or 0.0) for k in ("emb_pdrop", "res_pdrop", "att_pdrop")})
 
 
 def build_prior_trainer(config, device="cuda", first_stage_ckpt_path=None):
-    """config -> PriorTrainer (run_vqwnet.py -p): the GPT of model.prior trained on the codes of the frozen VQGAN of model.vqgan.
+    """config -> PriorTrainer (run_vqwnet.py -p): the GPT of model.prior trained on the codes of the frozen VQGAN of model.vqgan;
+    with model.prior.cond (prior_condition) the ConditionalPriorTrainer and its LabelCondition.
     first_stage_ckpt_path (argument, else run.first_stage_ckpt_path) loads a -v checkpoint's `decoder.*` keys into the VQGAN, as
     build_vqgan_trainer does.  A JSON `false` for pkeep, sos_token, warmup_steps or decay_steps arrives as None: pkeep then means
     1 (no corruption), the others 0.  run.seed seeds the trainer's generator and the prior's dropout (model.prior.*_pdrop)."""
@@ -234,10 +300,16 @@ def build_prior_trainer(config, device="cuda", first_stage_ckpt_path=None):
     if first:
         load_vqgan_from_ckpt(first, vqgan)
     p, o = config.model.prior, config.prior_optim
-    return PriorTrainer(vqgan, gpt, pkeep=1.0 if p.pkeep is None else p.pkeep, sos_token=int(p.sos_token or 0), lr=o.lr,
+    cls, extra, cond = PriorTrainer, {}, prior_condition(config)
+    if cond is not None:
+        from networks import LabelCondition
+        from .cond_prior import ConditionalPriorTrainer
+        side = latent_size(config)
+        cls, extra = ConditionalPriorTrainer, {"cond": LabelCondition(cond["n_labels"], p.n_embed, side, side)}
+    return cls(vqgan, gpt, pkeep=1.0 if p.pkeep is None else p.pkeep, sos_token=int(p.sos_token or 0), lr=o.lr,
                         betas=(o.b1, o.b2), weight_decay=o.weight_decay or 0.0, grad_norm_clip=o.grad_norm_clip or None,
                         warmup_steps=int(o.warmup_steps or 0), decay_steps=int(o.decay_steps or 0),
-                        seed=int(_get(config.run, "seed", 0) or 0), dropout_seed=int(_get(config.run, "seed", 0) or 0), device=device)
+                        seed=int(_get(config.run, "seed", 0) or 0), dropout_seed=int(_get(config.run, "seed", 0) or 0), device=device, **extra)
 
 
 def configure_discriminator(config):

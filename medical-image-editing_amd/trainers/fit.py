@@ -33,6 +33,7 @@ from .first_step import FlipViews, LUNG_WINDOW, MEDIASTINAL_WINDOW, LossWeights
 from .evaluation import Evaluator
 from .vqgan_unet_dis import VQGANUNetDisTrainer
 from .prior import PriorTrainer
+from .cond_prior import ConditionalPriorTrainer
 
 LIMIT_VAL_BATCHES = 2              # run_vqwnet.py:127
 SANITY_VAL_BATCHES = 2             # run_vqwnet.py:125
@@ -245,6 +246,11 @@ class Fit:
         self.prior = isinstance(trainer, PriorTrainer)
         if self.prior:
             self.mode = "prior"
+        # the conditional prior (model.prior.cond): every loader delivers the label maps beside the slices
+        self.cond = None
+        if isinstance(trainer, ConditionalPriorTrainer):
+            from .config import prior_condition
+            self.cond = prior_condition(config)
         self.dict_size = trainer.dict_size if self.vqgan or self.prior else config.model.vqmodel.dict_size
         self.n_epochs = int(_get(config.run, "n_epochs", 1))
         self.log_every = int(_get(config.run, "log_every_n_steps", DEFAULT_LOG_EVERY_N_STEPS))
@@ -263,7 +269,10 @@ class Fit:
     # ---------------------------------------------------------------- data
     def loader(self, mode):
         if mode not in self._loaders:
-            if mode == "train":
+            if self.cond is not None:
+                self._loaders[mode] = build_loader(self.config, mode, self.data_seed, generator={"train": self.train_gen, "val": self.val_gen}.get(mode),
+                                                   label_modality=self.cond["label_modality"], lesions=self.cond["lesions"])
+            elif mode == "train":
                 if self.world_size > 1:
                     probe = build_loader(self.config, "train", self.data_seed)
                     self.sampler = _RecordingSampler(probe.dataset, num_replicas=self.world_size, rank=self.rank,
@@ -282,6 +291,12 @@ class Fit:
     def _to_device(self, batch):
         image = batch["image"] if isinstance(batch, dict) else batch
         return image.to(self.device, non_blocking=True)
+
+    def _step_batch(self, batch, image, take=None):
+        """What a step of the trainer takes: the slices and, for the conditional prior, their label maps."""
+        if self.cond is None:
+            return {"image": image}
+        return {"image": image, "label": batch["label"][:take].to(self.device, non_blocking=True).contiguous()}
 
     # ---------------------------------------------------------------- state
     def run_state(self):
@@ -372,7 +387,7 @@ class Fit:
                             noise = ops.affine_(noise, self.noise_std, 0.0)
                         out = self.trainer.training_step({"image": image}, noise=noise)
                     else:
-                        out = self.trainer.training_step({"image": image})
+                        out = self.trainer.training_step(self._step_batch(batch, image))
                     self._log_step(out)
                     self.global_step += 1
                 self.queue.flush()
@@ -490,7 +505,8 @@ class Fit:
             if i >= limit:
                 break
             image = self._to_device(batch)
-            out = tr.validation_step({"image": image})
+            last = self._step_batch(batch, image)
+            out = tr.validation_step(last)
             losses.append(out["loss"])
             ids = out["ids"]
         if not losses:
@@ -506,7 +522,11 @@ class Fit:
         p = self.config.model.prior
         gen = torch.Generator(device=self.device).manual_seed(self.seed * 1000003 + epoch)
         recon = tr.vqgan.decode_from_ids(ids[:n], tr.h, tr.w)
-        draws = tr.sample_images(n, temperature=float(_get(p, "temperature", 1.0)), top_k=_get(p, "top_k"), generator=gen)
+        if self.cond is None:
+            draws = tr.sample_images(n, temperature=float(_get(p, "temperature", 1.0)), top_k=_get(p, "top_k"), generator=gen)
+        else:          # the bottom row: one draw per slice from its own label map
+            draws = tr.synthesize(label=last["label"][:n], n_candidates=1, temperature=float(_get(p, "temperature", 1.0)),
+                                  top_k=_get(p, "top_k"), generator=gen)["image"]
         rows = [ops.export_grey(t)[0].cpu().numpy() for t in (image[:n], recon, draws)]
         picture = np.concatenate([np.concatenate(list(r), axis=1) for r in rows], axis=0)
         os.makedirs(self.logger.log_dir, exist_ok=True)
@@ -544,7 +564,7 @@ class Fit:
             if done >= n_slices:
                 break
             image = self._to_device(batch)[:n_slices - done]
-            out = tr.edit({"image": image}, n_candidates=int(e.n_candidates), temperature=float(e.temperature or 1.0),
+            out = tr.edit(self._step_batch(batch, image, n_slices - done), n_candidates=int(e.n_candidates), temperature=float(e.temperature or 1.0),
                           top_k=e.top_k or None, top_p=e.top_p or None, generator=gen, **selector)
             tiles = [ops.export_grey(t)[0].cpu().numpy() for t in (image, out["recon"], out["edit"], out["composite"])]
             scores, cells = out["scores"].cpu().numpy(), out["cellmask"].cpu().numpy()
@@ -563,6 +583,58 @@ class Fit:
         with open(os.path.join(out_dir, "edit.csv"), "w") as f:
             f.write("\n".join(rows) + "\n")
         self.print("Edited slices are saved: {}".format(out_dir))
+        return written
+
+    # ---------------------------------------------------------------- -p -m synth
+    def synth(self):
+        """`-p -m synth`: the conditional prior of run.resume_checkpoint over the first synth.n_slices slices of the test split.
+        Under <run dir>/synth/: slice_<i>.png - tiles side by side: the label map (grey over its own range), the slice, the
+        synthesis from the label map alone (ConditionalPriorTrainer.synthesize) and, with synth.discs, the label map with the
+        discs [cy, cx, radius, value] drawn in and the composite of edit(new_label=...); synth.csv - slice, the winner among the
+        candidates, its score, the cells the edit redrew (0 without discs).  All draws come from one generator seeded with
+        synth.seed: a seed reproduces every file byte for byte."""
+        if self.cond is None:
+            raise ValueError("synthesising needs the conditional prior trainer (-p with model.prior.cond)")
+        self._load_weights_for_test()
+        if self.rank != 0:
+            return []
+        e, tr = self.config.synth, self.trainer
+        n_slices = int(e.n_slices)
+        discs = e.discs if e.discs else []
+        kw = dict(n_candidates=int(e.n_candidates), temperature=float(e.temperature or 1.0), top_k=e.top_k or None, top_p=e.top_p or None)
+        gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
+        out_dir = os.path.join(self.logger.log_dir, "synth")
+        os.makedirs(out_dir, exist_ok=True)
+        rows, written, done = ["slice,winner,score,cells_redrawn"], [], 0
+        for batch in self.loader("test"):
+            if done >= n_slices:
+                break
+            image = self._to_device(batch)[:n_slices - done]
+            step = self._step_batch(batch, image, n_slices - done)
+            label = step["label"]
+            B = image.shape[0]
+            out = tr.synthesize(label=label, generator=gen, **kw)
+            grey_of = lambda lab: ops.export_grey_auto(lab.reshape(B, 1, *lab.shape[-2:]).float()).cpu().numpy()  # noqa: E731
+            tiles = [grey_of(label)] + [ops.export_grey(t)[0].cpu().numpy() for t in (image, out["image"])]
+            redrawn = np.zeros(B, dtype=np.int64)
+            if discs:
+                new = label.clone()
+                yy, xx = torch.meshgrid(torch.arange(new.shape[-2], device=self.device), torch.arange(new.shape[-1], device=self.device), indexing="ij")
+                for cy, cx, radius, value in discs:
+                    new.reshape(B, *new.shape[-2:])[:, (yy - int(cy)) ** 2 + (xx - int(cx)) ** 2 <= int(radius) ** 2] = int(value)
+                edited = tr.edit(step, new_label=new, generator=gen, **kw)
+                tiles += [grey_of(new), ops.export_grey(edited["composite"])[0].cpu().numpy()]
+                redrawn = edited["cellmask"].reshape(B, -1).sum(1).cpu().numpy()
+            best, scores = out["best"].cpu().numpy(), out["scores"].cpu().numpy()
+            for b in range(B):
+                path = os.path.join(out_dir, "slice_%04d.png" % (done + b))
+                png.save(path, np.concatenate([t[b] for t in tiles], axis=1))
+                rows.append("%d,%d,%.17g,%d" % (done + b, best[b], scores[b, best[b]], int(redrawn[b])))
+                written.append(path)
+            done += B
+        with open(os.path.join(out_dir, "synth.csv"), "w") as f:
+            f.write("\n".join(rows) + "\n")
+        self.print("Synthesised slices are saved: {}".format(out_dir))
         return written
 
     # ---------------------------------------------------------------- -p -m detect

@@ -19,6 +19,10 @@ Nothing is read back: the step returns {'loss', 'grad_norm', 'lr', 'ids'} with t
 learning rate and the dropout call are computed from, and the dropout seed (a resumed run verifies it), so a resumed run
 continues bit for bit.
 
+Two hooks make room for a conditional prior (trainers/cond_prior.py): _prefix(batch), the embeddings that stand in front of the
+prompt (None here), and _logits(inp, prefix), the logits of the code positions (gpt(inp) here); the step, the validation, token_nll
+and _edit go through them.
+
 Editing (the launcher's -p -m edit).  token_nll(batch) is the prior's opinion of a slice code by code, -log p(code | the codes
 before it) as an (h, w) map.  edit(batch, mask | box | nll_threshold) redraws the selected codes n_candidates times with
 GPT.generate_masked, keeps every other code, scores each candidate by the log-probability of its whole sequence and pastes the best
@@ -89,8 +93,7 @@ class PriorTrainer(TrainerBase):
         if not isinstance(gpt, GPT):
             raise TypeError("PriorTrainer trains a networks.GPT")
         super().__init__(device)
-        enc = vqgan.encoder
-        self.h = self.w = int(enc.resolution) // 2 ** (int(enc.num_resolutions) - 1)
+        self.h, self.w = self._latent_grid(vqgan)
         self.dict_size = int(vqgan.vq.dict_size)
         if gpt.config.vocab_size != self.dict_size:
             raise ValueError("PriorTrainer: the GPT's vocab_size=%d must equal the VQGAN's dict_size=%d" % (gpt.config.vocab_size, self.dict_size))
@@ -115,6 +118,12 @@ class PriorTrainer(TrainerBase):
         self.optim = AdamW(groups, lr=lr, betas=tuple(betas), weight_decay=weight_decay, max_grad_norm=grad_norm_clip)
         self.generator = torch.Generator(device=self.device).manual_seed(int(seed))
         self.step_count = 0
+
+    def _latent_grid(self, vqgan):
+        """(h, w) of the code sequences: the latent of the VQGAN at its own resolution (the conditional trainer: its condition's)."""
+        enc = vqgan.encoder
+        side = int(enc.resolution) // 2 ** (int(enc.num_resolutions) - 1)
+        return side, side
 
     def modules(self):
         return {"decoder": self.vqgan, "transformer": self.gpt}
@@ -161,6 +170,15 @@ class PriorTrainer(TrainerBase):
             u_rand = torch.rand(ids.shape, generator=self.generator, device=self.device)
         return ops.prior_tokens(ids, self.sos_token, pkeep, self.dict_size, u_keep, u_rand)
 
+    # the two hooks of a conditional prior (trainers/cond_prior.py); here: no prefix, the logits of every position
+    def _prefix(self, batch):
+        """The embeddings (B, Tc, E) that stand in front of the prompt as a fully visible prefix, or None."""
+        return None
+
+    def _logits(self, inp, prefix):
+        """The logits (B, T, V) of the code positions of inp (B, T) behind `prefix`."""
+        return self.gpt(inp)
+
     def training_step(self, batch, mark=None):
         self.throttle.begin()
         ids = self.codes(batch)
@@ -168,7 +186,7 @@ class PriorTrainer(TrainerBase):
         inp = self._inputs(ids, self.pkeep)
         if self.dropout_seed is not None:
             self.gpt.set_dropout_call(self.step_count)          # the masks of a step: a function of (dropout_seed, step) alone
-        loss = ops.cross_entropy(self.gpt(inp), ids)
+        loss = ops.cross_entropy(self._logits(inp, self._prefix(batch)), ids)
         lr = self.current_lr()
         for group in self.optim.param_groups:
             group["lr"] = lr
@@ -184,7 +202,7 @@ class PriorTrainer(TrainerBase):
         was_training = self.gpt.training
         self.gpt.eval()
         try:
-            loss = ops.cross_entropy(self.gpt(self._inputs(ids, 1.0)), ids)
+            loss = ops.cross_entropy(self._logits(self._inputs(ids, 1.0), self._prefix(batch)), ids)
         finally:
             self.gpt.train(was_training)
         return {"loss": loss, "ids": ids}
@@ -230,11 +248,11 @@ class PriorTrainer(TrainerBase):
 
     # ---------------------------------------------------------------- editing
     @torch.no_grad()
-    def _token_nll(self, ids):
+    def _token_nll(self, ids, prefix=None):
         was_training = self.gpt.training
         self.gpt.eval()
         try:
-            nll = ops.cross_entropy(self.gpt(self._inputs(ids, 1.0)), ids, reduction="none")
+            nll = ops.cross_entropy(self._logits(self._inputs(ids, 1.0), prefix), ids, reduction="none")
         finally:
             self.gpt.train(was_training)
         return nll
@@ -246,7 +264,7 @@ class PriorTrainer(TrainerBase):
         ids = self.codes(batch)
         if ids.shape[1] != self.h * self.w:
             raise ValueError("PriorTrainer.token_nll: sequences of h w = %d codes expected, got %d" % (self.h * self.w, ids.shape[1]))
-        return self._token_nll(ids).reshape(-1, self.h, self.w)
+        return self._token_nll(ids, self._prefix(batch)).reshape(-1, self.h, self.w)
 
     def cell_mask(self, B, mask=None, box=None, image_size=None):
         """The host bool array (B, h, w) of the codes a user's selection touches.  mask: a host array at pixel resolution (H, W)
@@ -290,10 +308,11 @@ class PriorTrainer(TrainerBase):
         composite = ops.paste_cells(image, edit, cellmask).  A {'ids'} batch has no image and no composite."""
         return self._edit(batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator)[0]
 
-    def _edit(self, batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator):
+    def _edit(self, batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator, cells=None, image_size=None):
         """edit()'s work -> (edit()'s dict, the token_nll map (B, h, w) the nll_threshold selector computed, else None): what edit
-        and detect share."""
-        if (mask is not None) + (box is not None) + (nll_threshold is not None) != 1:
+        and detect share.  cells: a host bool array (B, h, w) in place of the three selectors (the conditional trainer's fourth);
+        image_size: the (H, W) a mask or box of a batch without a picture refers to (cell_mask's default otherwise)."""
+        if cells is None and (mask is not None) + (box is not None) + (nll_threshold is not None) != 1:
             raise ValueError("PriorTrainer.edit: exactly one of mask, box and nll_threshold selects the region")
         n = int(n_candidates)
         if n < 1:
@@ -304,12 +323,13 @@ class PriorTrainer(TrainerBase):
         B, T = ids.shape
         if T != self.h * self.w:
             raise ValueError("PriorTrainer.edit: sequences of h w = %d codes expected, got %d" % (self.h * self.w, T))
+        prefix = self._prefix(batch)
         nll = None
-        if nll_threshold is not None:
-            nll = self._token_nll(ids).reshape(B, self.h, self.w)
+        if cells is None and nll_threshold is not None:
+            nll = self._token_nll(ids, prefix).reshape(B, self.h, self.w)
             cells = (nll > float(nll_threshold)).cpu().numpy()      # the one read of the selector
-        else:
-            cells = self.cell_mask(B, mask, box, tuple(image.shape[-2:]) if has_image else None)
+        elif cells is None:
+            cells = self.cell_mask(B, mask, box, tuple(image.shape[-2:]) if has_image else image_size)
         resample = np.repeat(cells.reshape(B, T), n, axis=0)
         known = ids.repeat_interleave(n, dim=0)
         start = torch.full((B * n, 1), self.sos_token, dtype=torch.long, device=self.device)
@@ -322,7 +342,8 @@ class PriorTrainer(TrainerBase):
         self.gpt.eval()
         try:
             tokens, logp = self.gpt.generate_masked(start, known, resample, temperature=temperature, top_k=top_k, top_p=top_p,
-                                                    uniforms=uniforms)
+                                                    uniforms=uniforms,
+                                                    embeddings=None if prefix is None else prefix.repeat_interleave(n, dim=0))
         finally:
             self.gpt.train(was_training)
         scores = logp.double().sum(1).reshape(B, n)

@@ -75,7 +75,7 @@ def save_lightning_style_ckpt(path, encoder=None, decoder=None, dis=None, extra=
 # configure_optimizers' list, trainers/base.py:164-183; behind it what the reference does not have: the GPT prior's optimiser
 # and module (trainers/prior.py) - a checkpoint of the other trainers is unchanged by the longer lists
 OPTIMIZER_ORDER = ("enc", "dec", "dis", "prior_optim")
-MODULE_ORDER = ("encoder", "decoder", "dis", "transformer")
+MODULE_ORDER = ("encoder", "decoder", "dis", "transformer", "cond")          # cond: the conditional prior's label table (trainers/cond_prior.py)
 RUN_STATE_KEY = "vqw_run_state"                  # not a key of the reference: everything a bit-exact continuation needs
 
 
