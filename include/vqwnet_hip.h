@@ -813,6 +813,17 @@ int vqw_sample_topk(const float* logits, const float* u, long* out, int B, int V
  * inputs.  1 <= V <= 65536, B >= 1, temperature > 0, top_k >= 0, top_p > 0; logits, u and out must not be null. */
 int vqw_sample_filtered(const float* logits, const float* u, const long* forced, long* out, float* logp, int B, int V,
                         float temperature, int top_k, float top_p, void* stream);
+/* Classifier-free guidance inside the same sampler (GPT.generate_masked's guided step).  Added function only; the ABI stays 9.
+ * logits [2B][V]: the rows [0, B) are the conditional rows z_c, the rows [B, 2B) the unconditional rows z_u of the same samples.
+ * The mixed logit z[c] = fmaf(scale, z_c[c] - z_u[c], z_u[c]) - one fp32 subtraction, one fused multiply-add, the same bits in
+ * every pass of the kernel - takes the place of vqw_sample_filtered's row: temperature, top-k, top-p, forced and the draw apply to
+ * it word for word, with u, forced [B].  No [B][V] intermediate is written; each pass reads both rows.  out [2B]: out[b] = out[B + b]
+ * = the token, so the decode step of the next position takes out as its idx for both halves.  logp [B] (may be null): the token's
+ * log-probability under the CONDITIONAL row - temperature 1, unfiltered: what vqw_sample_filtered returns for z_c with that token
+ * forced; logp_u [B] (may be null): the same under z_u.  forced[b] >= V sets both to NaN.  scale must be finite and >= 0 (0: z_u,
+ * 1: z_c up to the rounding of the mix); otherwise vqw_sample_filtered's constraints. */
+int vqw_sample_guided(const float* logits, const float* u, const long* forced, long* out, float* logp, float* logp_u, int B, int V,
+                      float scale, float temperature, int top_k, float top_p, void* stream);
 /* The composite of an edit: out[b][y][x][c] = cellmask[b][y / fy][x / fx] ? edit[b][y][x][c] : image[b][y][x][c] on NHWC
  * tensors [N][H][W][C]; cellmask [N][h][w] bytes (non-zero: the edit), fy = H / h, fx = W / w; H % h == 0 and W % w == 0.  One
  * streaming kernel, 16-byte accesses when a cell's row (fx C floats) is a multiple of 4 floats and the tensors are 16-byte
@@ -930,6 +941,14 @@ int vqw_cell_labels(const void* label, long* tokens, float* purity, int B, int H
                     void* stream);
 int vqw_cells_changed(const void* a, const void* b, uint8_t* out, int B, int H, int W, int h, int w, int elem_bytes, void* stream);
 int vqw_embed_lookup(const long* idx, const float* table, float* out, long rows, int E, int L, void* stream);
+/* The lookup with the condition dropped per SAMPLE (the training side of classifier-free guidance).  Added function only; the ABI
+ * stays 9.  Sample b = r / rows_per_sample is dropped iff the draw of csrc/dropout.h for element b under (seed, call) and the site
+ * COND_DROP_SITE (-1: outside the sites GPT.seed_dropout numbers from 0) is below round(p 2^32); every row of a dropped sample reads
+ * table[null_index].  eff [rows] (torch.long) receives the index actually read: the gradient is vqw_embed_bwd's gtok over eff.  No
+ * mask tensor, no host read, the same bits every run; at p = 0 out has vqw_embed_lookup's bits.  rows a multiple of
+ * rows_per_sample >= 1, 0 <= null_index < L, 0 <= p < 1, otherwise vqw_embed_lookup's constraints. */
+int vqw_embed_lookup_drop(const long* idx, const float* table, float* out, long* eff, long rows, int rows_per_sample, int E, int L,
+                          long null_index, float p, long seed, long call, void* stream);
 
 /* ---- anomaly detection with the code prior (trainers/prior.py PriorTrainer.detect, trainers/fit.py Fit.detect; the reference has
  * nothing like it).  Added functions only; the ABI stays 9.  fp32 in, no float atomics, the same bits every run; every refusal below

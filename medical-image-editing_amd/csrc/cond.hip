@@ -17,8 +17,14 @@
 //
 // Table lookup.  out[r] = table[idx[r]], a wave per row; an index outside [0, L) writes a NaN row (vqw_embed_fwd's rule).  Its
 // gradient is vqw_embed_bwd's: nothing here.
+//
+// Table lookup with the condition dropped per sample (classifier-free guidance's training side).  Sample b = r / rows_per_sample is
+// dropped iff the draw of dropout.h for element b of the site COND_DROP_SITE under (seed, call) falls below round(p 2^32) - the mask
+// is never stored, the same bits every run - and every row of a dropped sample reads table[null_index].  eff[r] is the index read:
+// the gradient is vqw_embed_bwd's gtok over eff.
 #include "common.h"
 #include "gpt_math.h"
+#include "dropout.h"
 #include "../../include/vqwnet_hip.h"
 
 #define CL_MAX_LABELS 256
@@ -158,6 +164,26 @@ __global__ void __launch_bounds__(256) k_embed_lookup(const long* __restrict__ i
         *(float4*)(out + r * E + 4 * c4) = ok ? *(const float4*)(src + 4 * c4) : make_float4(nan, nan, nan, nan);
 }
 
+// The dropout site of the condition drop: GPT.seed_dropout numbers its sites upwards from 0, so a negative site is never one of them.
+#define COND_DROP_SITE (-1)
+
+// grid ceil(rows / 4): wave w of workgroup g writes row 4 g + w
+__global__ void __launch_bounds__(256) k_embed_lookup_drop(const long* __restrict__ idx, const float* __restrict__ table, float* __restrict__ out,
+                                                           long* __restrict__ eff, long rows, int rows_per_sample, int E, int L, long null_index,
+                                                           DropKey key) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63, E4 = E >> 2;
+    const bool keep = dk_keep(key, (uint64_t)(r / rows_per_sample));          // the same for every row of a sample
+    const long id = keep ? idx[r] : null_index;
+    const bool ok = id >= 0 && id < L;
+    const float* src = table + (ok ? id : 0) * E;
+    const float nan = quiet_nan();
+    if (lane == 0) eff[r] = id;
+    for (int c4 = lane; c4 < E4; c4 += 64)
+        *(float4*)(out + r * E + 4 * c4) = ok ? *(const float4*)(src + 4 * c4) : make_float4(nan, nan, nan, nan);
+}
+
 static int cell_check(const char* name, int B, int H, int W, int h, int w, int elem_bytes) {
     VQW_CHECK(B >= 1 && H >= 1 && W >= 1, "%s: B=%d, H=%d, W=%d must be positive", name, B, H, W);
     VQW_CHECK(h >= 1 && w >= 1 && H % h == 0 && W % w == 0, "%s: H=%d, W=%d must be multiples of the cell grid h=%d, w=%d", name, H, W, h, w);
@@ -221,5 +247,22 @@ extern "C" int vqw_embed_lookup(const long* idx, const float* table, float* out,
     VQW_CHECK(al16(table) && al16(out), "vqw_embed_lookup: tensors must be 16-byte aligned");
     hipLaunchKernelGGL(k_embed_lookup, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, idx, table, out, rows, E, L);
     VQW_LAUNCH_CHECK("vqw_embed_lookup");
+    return VQW_OK;
+}
+
+extern "C" int vqw_embed_lookup_drop(const long* idx, const float* table, float* out, long* eff, long rows, int rows_per_sample, int E, int L,
+                                     long null_index, float p, long seed, long call, void* stream) {
+    VQW_CHECK(rows >= 1 && rows <= (1L << 31) - 4, "vqw_embed_lookup_drop: rows=%ld must lie in [1, 2^31 - 4]", rows);
+    VQW_CHECK(rows_per_sample >= 1 && rows % rows_per_sample == 0, "vqw_embed_lookup_drop: rows=%ld must be a multiple of rows_per_sample=%d >= 1", rows,
+              rows_per_sample);
+    VQW_CHECK(E % 4 == 0 && E >= 4 && E <= 4096, "vqw_embed_lookup_drop: E=%d must be a multiple of 4 with 4 <= E <= 4096", E);
+    VQW_CHECK(L >= 1, "vqw_embed_lookup_drop: L=%d must be at least 1", L);
+    VQW_CHECK(null_index >= 0 && null_index < L, "vqw_embed_lookup_drop: null_index=%ld must be a row of the table, [0, L = %d)", null_index, L);
+    VQW_CHECK(p >= 0.f && p < 1.f, "vqw_embed_lookup_drop: p=%g must lie in [0, 1)", (double)p);
+    VQW_CHECK(idx && table && out && eff, "vqw_embed_lookup_drop: null pointer");
+    VQW_CHECK(al16(table) && al16(out), "vqw_embed_lookup_drop: tensors must be 16-byte aligned");
+    hipLaunchKernelGGL(k_embed_lookup_drop, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, idx, table, out, eff, rows, rows_per_sample, E, L,
+                       null_index, dk_make(p, seed, call, COND_DROP_SITE));
+    VQW_LAUNCH_CHECK("vqw_embed_lookup_drop");
     return VQW_OK;
 }

@@ -27,6 +27,10 @@
 // leaves off: a nucleus threshold found by the same radix walk on integer MASSES per bin, a forced token per row in place of the
 // draw, and the token's log-probability under the unfiltered distribution at temperature 1 (the cross-entropy's rule: fp32
 // terms, a double sum in a fixed order, rounded once).  Details above the kernel.
+//
+// Guided sampling (vqw_sample_guided, the guided step of GPT.generate_masked).  Still the same kernel: k_sample takes its logits
+// source as a template parameter, and the guided source mixes the conditional and the unconditional row of a sample entry by entry,
+// z = fmaf(scale, z_c - z_u, z_u), in every pass - nothing of the size of the logits is written.  Details above the two sources.
 #include "common.h"
 #include "gpt_math.h"
 #include "../../include/vqwnet_hip.h"
@@ -293,33 +297,81 @@ extern "C" int vqw_xent_bwd(const float* z, const long* target, const float* lse
 // An empty bin may be chosen: thr2 need not be a key of the row.
 #define SF_FIX 0x1p40f
 
-// grid B, 256 threads: one row each
-template <bool NUCLEUS>
-__global__ void __launch_bounds__(256) k_sample(const float* __restrict__ logits, const float* __restrict__ u, const long* __restrict__ forced,
+// The logits source of k_sample, a template parameter: what entry c of the row of workgroup b is.
+//   PlainLogits   logits [B][V]: the entry itself; the log-probability is that of the same row.
+//   GuidedLogits  logits [2B][V], classifier-free guidance: row b is the conditional z_c, row B + b the unconditional z_u of the same
+//                 sample, and the entry is sg_mix(z_c, z_u, scale) = z_u + scale (z_c - z_u): one fp32 subtraction and one EXPLICIT
+//                 fused multiply-add (the file is built with -ffp-contract=fast: a + s * d would leave the fusing to the back end).
+//                 ONE function for every pass - the maximum, the radix select, the mass histogram, the chunk sums and the walk see
+//                 the same bits for an entry, so tied entries share one fate.  Nothing [B][V] is written: each pass reads both rows
+//                 again (L2-resident at these sizes).  The log-probabilities are those of the two rows themselves: logp under z_c,
+//                 logp_u under z_u, each in the plain kernel's form.
+__device__ __forceinline__ float sg_mix(float zc, float zu, float scale) { return fmaf(scale, zc - zu, zu); }
+
+struct PlainLogits {
+    static constexpr bool GUIDED = false;
+    const float* __restrict__ logits;
+    struct Row {
+        const float* __restrict__ z;
+        __device__ __forceinline__ float operator()(int c) const { return z[c]; }
+        __device__ __forceinline__ float cond(int c) const { return z[c]; }
+        __device__ __forceinline__ float uncond(int c) const { return z[c]; }
+    };
+    __device__ __forceinline__ Row row(unsigned b, unsigned B, int V) const { return Row{logits + (long)b * V}; }
+    __device__ __forceinline__ float* logp_uncond() const { return nullptr; }
+};
+
+struct GuidedLogits {
+    static constexpr bool GUIDED = true;
+    const float* __restrict__ logits;
+    float* __restrict__ logp_u;
+    float scale;
+    struct Row {
+        const float* __restrict__ zc;
+        const float* __restrict__ zu;
+        float scale;
+        __device__ __forceinline__ float operator()(int c) const { return sg_mix(zc[c], zu[c], scale); }
+        __device__ __forceinline__ float cond(int c) const { return zc[c]; }
+        __device__ __forceinline__ float uncond(int c) const { return zu[c]; }
+    };
+    __device__ __forceinline__ Row row(unsigned b, unsigned B, int V) const { return Row{logits + (long)b * V, logits + ((long)B + b) * V, scale}; }
+    __device__ __forceinline__ float* logp_uncond() const { return logp_u; }
+};
+
+// grid B, 256 threads: one row (GuidedLogits: one pair of rows) each; out [B], GuidedLogits: [2B] with out[B + b] = out[b]
+template <bool NUCLEUS, class SRC>
+__global__ void __launch_bounds__(256) k_sample(const SRC src, const float* __restrict__ u, const long* __restrict__ forced,
                                                 long* __restrict__ out, float* __restrict__ logp, int V, float temperature, int top_k,
                                                 float top_p) {
     __shared__ unsigned hist[256];
     __shared__ unsigned long long mass[256];
     __shared__ float csum[256];
     __shared__ int clast[256];
-    __shared__ float wmax[4], wzmax[4];
-    __shared__ double wsum[4];
+    __shared__ float wmax[4], wzmax[4], wzmaxu[4];
+    __shared__ double wsum[4], wsumu[4];
     __shared__ unsigned sel[2];
     __shared__ unsigned long long sabove;
     const int tid = threadIdx.x;
-    const float* z = logits + (long)blockIdx.x * V;
+    const typename SRC::Row z = src.row(blockIdx.x, gridDim.x, V);
+    float* const logp_u = src.logp_uncond();        // GuidedLogits only: null otherwise
     const long f = forced ? forced[blockIdx.x] : -1;
     const bool force = f >= 0 && f < V;             // the same for the whole workgroup
 
-    float m = -INFINITY, zm = -INFINITY;            // the maxima of s = z / temperature and, for logp, of z
+    float m = -INFINITY, zm = -INFINITY, zmu = -INFINITY;      // the maxima of s = z / temperature and, for logp (logp_u), of z_c (z_u)
     for (int c = tid; c < V; c += 256) {
-        const float x = z[c];
-        if (logp) zm = fmaxf(zm, x);                // the same for the whole workgroup
+        const float x = z(c);
+        if (logp) zm = fmaxf(zm, SRC::GUIDED ? z.cond(c) : x);      // the same for the whole workgroup
+        if (SRC::GUIDED && logp_u) zmu = fmaxf(zmu, z.uncond(c));
         m = fmaxf(m, x / temperature);
     }
     m = wave_max_f(m);
     if (logp) zm = wave_max_f(zm);
-    if ((tid & 63) == 0) { wmax[tid >> 6] = m; wzmax[tid >> 6] = zm; }
+    if (SRC::GUIDED && logp_u) zmu = wave_max_f(zmu);
+    if ((tid & 63) == 0) {
+        wmax[tid >> 6] = m;
+        wzmax[tid >> 6] = zm;
+        if (SRC::GUIDED) wzmaxu[tid >> 6] = zmu;
+    }
     __syncthreads();
     m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
 
@@ -327,9 +379,16 @@ __global__ void __launch_bounds__(256) k_sample(const float* __restrict__ logits
     if (logp) {
         zm = fmaxf(fmaxf(wzmax[0], wzmax[1]), fmaxf(wzmax[2], wzmax[3]));
         double s = 0.0;
-        for (int c = tid; c < V; c += 256) s += (double)expf(z[c] - zm);
+        for (int c = tid; c < V; c += 256) s += (double)expf(z.cond(c) - zm);
         s = wave_sum_d(s);
         if ((tid & 63) == 0) wsum[tid >> 6] = s;
+    }
+    if (SRC::GUIDED && logp_u) {
+        zmu = fmaxf(fmaxf(wzmaxu[0], wzmaxu[1]), fmaxf(wzmaxu[2], wzmaxu[3]));
+        double s = 0.0;
+        for (int c = tid; c < V; c += 256) s += (double)expf(z.uncond(c) - zmu);
+        s = wave_sum_d(s);
+        if ((tid & 63) == 0) wsumu[tid >> 6] = s;
     }
 
     int pick = (int)f;
@@ -342,7 +401,7 @@ __global__ void __launch_bounds__(256) k_sample(const float* __restrict__ logits
                 hist[tid] = 0;
                 __syncthreads();
                 for (int c = tid; c < V; c += 256) {
-                    const unsigned key = st_key(z[c] / temperature);
+                    const unsigned key = st_key(z(c) / temperature);
                     if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
                 }
                 __syncthreads();
@@ -372,7 +431,7 @@ __global__ void __launch_bounds__(256) k_sample(const float* __restrict__ logits
                 mass[tid] = 0;
                 __syncthreads();
                 for (int c = tid; c < V; c += 256) {
-                    const float x = z[c] / temperature;
+                    const float x = z(c) / temperature;
                     const unsigned key = st_key(x);
                     if (key >= thr && (key & pmask) == prefix)
                         atomicAdd(&mass[(key >> shift) & 255u], (unsigned long long)(expf(x - m) * SF_FIX));
@@ -418,7 +477,7 @@ __global__ void __launch_bounds__(256) k_sample(const float* __restrict__ logits
         float s = 0.f;
         int last = -1;
         for (int c = c0; c < c1; ++c) {
-            const float x = z[c] / temperature;
+            const float x = z(c) / temperature;
             if (st_key(x) >= thr) { s += expf(x - m); last = c; }
         }
         csum[tid] = s;
@@ -439,7 +498,7 @@ __global__ void __launch_bounds__(256) k_sample(const float* __restrict__ logits
             if (t < 256) {
                 const int e = (t + 1) * chunk < V ? (t + 1) * chunk : V;
                 for (int c = t * chunk; c < e; ++c) {
-                    const float x = z[c] / temperature;
+                    const float x = z(c) / temperature;
                     if (st_key(x) >= thr) {
                         run += expf(x - m);
                         if (run > goal) { pick = c; break; }
@@ -456,9 +515,14 @@ __global__ void __launch_bounds__(256) k_sample(const float* __restrict__ logits
     }
     if (tid == 0) {
         out[blockIdx.x] = pick;
+        if (SRC::GUIDED) out[gridDim.x + blockIdx.x] = pick;      // the next decode step's idx for both halves
         if (logp) {                                         // k_xe_fwd's form: the difference first, then the logarithm, rounded once
             const double ls = log(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
-            logp[blockIdx.x] = f >= V ? quiet_nan() : -(float)(((double)zm - (double)z[pick]) + ls);
+            logp[blockIdx.x] = f >= V ? quiet_nan() : -(float)(((double)zm - (double)z.cond(pick)) + ls);
+        }
+        if (SRC::GUIDED && logp_u) {
+            const double ls = log(((wsumu[0] + wsumu[1]) + wsumu[2]) + wsumu[3]);
+            logp_u[blockIdx.x] = f >= V ? quiet_nan() : -(float)(((double)zmu - (double)z.uncond(pick)) + ls);
         }
     }
 }
@@ -472,9 +536,27 @@ extern "C" int vqw_sample_filtered(const float* logits, const float* u, const lo
     VQW_CHECK(top_p > 0.f, "vqw_sample_filtered: top_p=%g must be positive (>= 1: no filter)", (double)top_p);
     VQW_CHECK(logits && u && out, "vqw_sample_filtered: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (top_p < 1.f) hipLaunchKernelGGL(k_sample<true>, dim3(B), dim3(256), 0, st, logits, u, forced, out, logp, V, temperature, top_k, top_p);
-    else hipLaunchKernelGGL(k_sample<false>, dim3(B), dim3(256), 0, st, logits, u, forced, out, logp, V, temperature, top_k, top_p);
+    const PlainLogits src{logits};
+    if (top_p < 1.f) hipLaunchKernelGGL((k_sample<true, PlainLogits>), dim3(B), dim3(256), 0, st, src, u, forced, out, logp, V, temperature, top_k, top_p);
+    else hipLaunchKernelGGL((k_sample<false, PlainLogits>), dim3(B), dim3(256), 0, st, src, u, forced, out, logp, V, temperature, top_k, top_p);
     VQW_LAUNCH_CHECK("vqw_sample_filtered");
+    return VQW_OK;
+}
+
+extern "C" int vqw_sample_guided(const float* logits, const float* u, const long* forced, long* out, float* logp, float* logp_u, int B, int V,
+                                 float scale, float temperature, int top_k, float top_p, void* stream) {
+    VQW_CHECK(V >= 1 && V <= ST_MAX_V, "vqw_sample_guided: V=%d must satisfy 1 <= V <= %d", V, ST_MAX_V);
+    VQW_CHECK(B >= 1 && B <= (1 << 30), "vqw_sample_guided: B=%d must lie in [1, 2^30] (logits has 2 B rows)", B);
+    VQW_CHECK(temperature > 0.f, "vqw_sample_guided: temperature=%g must be positive", (double)temperature);
+    VQW_CHECK(top_k >= 0, "vqw_sample_guided: top_k=%d must not be negative (0: no filter)", top_k);
+    VQW_CHECK(top_p > 0.f, "vqw_sample_guided: top_p=%g must be positive (>= 1: no filter)", (double)top_p);
+    VQW_CHECK(scale >= 0.f && scale < INFINITY, "vqw_sample_guided: scale=%g must be finite and not negative", (double)scale);
+    VQW_CHECK(logits && u && out, "vqw_sample_guided: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const GuidedLogits src{logits, logp_u, scale};
+    if (top_p < 1.f) hipLaunchKernelGGL((k_sample<true, GuidedLogits>), dim3(B), dim3(256), 0, st, src, u, forced, out, logp, V, temperature, top_k, top_p);
+    else hipLaunchKernelGGL((k_sample<false, GuidedLogits>), dim3(B), dim3(256), 0, st, src, u, forced, out, logp, V, temperature, top_k, top_p);
+    VQW_LAUNCH_CHECK("vqw_sample_guided");
     return VQW_OK;
 }
 
@@ -484,8 +566,8 @@ extern "C" int vqw_sample_topk(const float* logits, const float* u, long* out, i
     VQW_CHECK(temperature > 0.f, "vqw_sample_topk: temperature=%g must be positive", (double)temperature);
     VQW_CHECK(top_k >= 0, "vqw_sample_topk: top_k=%d must not be negative (0: no filter)", top_k);
     VQW_CHECK(logits && u && out, "vqw_sample_topk: null pointer");
-    hipLaunchKernelGGL(k_sample<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, u, (const long*)nullptr, out, (float*)nullptr, V,
-                       temperature, top_k, 1.f);
+    hipLaunchKernelGGL((k_sample<false, PlainLogits>), dim3(B), dim3(256), 0, (hipStream_t)stream, PlainLogits{logits}, u, (const long*)nullptr, out,
+                       (float*)nullptr, V, temperature, top_k, 1.f);
     VQW_LAUNCH_CHECK("vqw_sample_topk");
     return VQW_OK;
 }

@@ -10,6 +10,7 @@ Conv weights are logically OIHW and physically OHWI (channels_last too).
 """
 import contextlib
 import ctypes
+import math
 import os
 
 import torch
@@ -1930,6 +1931,40 @@ def sample_filtered(logits, u, forced=None, temperature=1.0, top_k=0, top_p=None
     return out, logp
 
 
+def _guidance_scale(name, scale):
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale >= 0.0):
+        raise ValueError("%s: guidance_scale=%r must be finite and not negative" % (name, scale))
+    return scale
+
+
+def sample_guided(logits, u, scale, forced=None, temperature=1.0, top_k=0, top_p=None, out=None):
+    """sample_filtered under classifier-free guidance, in the same kernel: logits (2B, V) - the rows [0, B) conditional (z_c), the
+    rows [B, 2B) unconditional (z_u) - u (B,), forced (B,) or None -> (tokens (2B,) torch.long with tokens[B:] == tokens[:B], logp
+    (B,), logp_u (B,)).  The filter and the draw see z = fmaf(scale, z_c - z_u, z_u), never written to memory; logp and logp_u are
+    the token's log-probabilities under z_c and under z_u (temperature 1, unfiltered): what sample_filtered returns for that row
+    with the token forced.  scale: finite, >= 0.  `out`: a (2B,) torch.long buffer to write the tokens into."""
+    _dev(logits, u, forced)
+    scale = _guidance_scale("sample_guided", scale)
+    logits, u = _flat(logits), _flat(u)
+    if logits.dim() != 2 or u.dim() != 1 or logits.shape[0] != 2 * u.shape[0] or u.shape[0] < 1:
+        raise RuntimeError("sample_guided: logits (2B, V) and u (B,) expected, got %s and %s" % (tuple(logits.shape), tuple(u.shape)))
+    B, V = u.shape[0], logits.shape[1]
+    if forced is not None:
+        forced = _long(forced, "sample_guided: forced")
+        if tuple(forced.shape) != (B,):
+            raise RuntimeError("sample_guided: forced (B,) = (%d,) expected, got %s" % (B, tuple(forced.shape)))
+    if out is None:
+        out = torch.empty(2 * B, dtype=torch.long, device=logits.device)
+    elif out.dtype != torch.long or tuple(out.shape) != (2 * B,) or not out.is_contiguous() or out.device != logits.device:
+        raise RuntimeError("sample_guided: out must be a contiguous (2B,) = (%d,) torch.long tensor on the logits' device" % (2 * B))
+    logp = torch.empty(B, dtype=torch.float32, device=logits.device)
+    logp_u = torch.empty(B, dtype=torch.float32, device=logits.device)
+    _L().vqw_sample_guided(logits, u, forced, out, logp, logp_u, B, V, scale, float(temperature), int(top_k or 0),
+                           1.0 if top_p is None else float(top_p))
+    return out, logp, logp_u
+
+
 def paste_cells(image, edit, cellmask):
     """The composite of an edit: out = edit where the latent cell of the pixel is set in cellmask (B, h, w) torch.uint8, else
     image; image and edit (B, C, H, W) fp32 in either memory format, H and W multiples of h and w.  Returns a channels_last
@@ -2151,6 +2186,50 @@ def embedding_lookup(idx, table):
     """table[idx]: idx (B, T) torch.long, table (L, E) fp32 -> (B, T, E), a plain gather with a gradient to table - ops.embedding's
     deterministic one.  An index outside [0, L) gives a NaN row and no gradient."""
     return _EmbeddingLookup.apply(idx, table)
+
+
+COND_DROP_SITE = -1          # csrc/cond.hip: the dropout site of the condition drop, outside the sites GPT.seed_dropout numbers from 0
+
+
+class _EmbeddingLookupDrop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, idx, table, null_index, p, seed, call):
+        _dev(idx, table)
+        idx, table = _long(idx, "embedding_lookup_drop: idx"), _flat(table)
+        if idx.dim() != 2 or table.dim() != 2 or idx.numel() < 1:
+            raise RuntimeError("embedding_lookup_drop: idx (B, T) and table (L, E) expected, got %s and %s" % (tuple(idx.shape), tuple(table.shape)))
+        (B, T), (L, E) = idx.shape, table.shape
+        out = torch.empty(B, T, E, dtype=torch.float32, device=table.device)
+        eff = torch.empty(B, T, dtype=torch.long, device=table.device)
+        _L().vqw_embed_lookup_drop(idx, table, out, eff, B * T, T, E, L, null_index, p, seed, call)
+        ctx.save_for_backward(eff)
+        ctx.cfg = (B, T, E, L)
+        ctx.mark_non_differentiable(eff)
+        return out, eff
+
+    @staticmethod
+    def backward(ctx, gx, _geff):
+        # embedding_lookup's gradient over the indices actually read: a dropped sample's rows add to the null row
+        (eff,) = ctx.saved_tensors
+        B, T, E, L = ctx.cfg
+        gx = _flat(gx)
+        gtable = torch.empty(L, E, dtype=torch.float32, device=gx.device)
+        gpos = torch.empty(T, E, dtype=torch.float32, device=gx.device)
+        _L().vqw_embed_bwd(eff, gx, gtable, gpos, B, T, 0, E, L, T, 0)
+        return None, gtable, None, None, None, None
+
+
+def embedding_lookup_drop(idx, table, null_index, p, seed, call, return_eff=False):
+    """embedding_lookup with the condition dropped per sample: sample b of idx (B, T) reads table[null_index] in all its T rows
+    iff the draw of csrc/dropout.h for element b under (seed, call, COND_DROP_SITE) falls below round(p 2^32) - no mask tensor, no
+    host read, the same bits every run; p = 0 drops nobody and has embedding_lookup's bits.  The table's gradient runs over the
+    indices actually read (return_eff: also returned, (B, T) torch.long).  0 <= p < 1, 0 <= null_index < L."""
+    seed, call, _ = _drop_key((seed, call, COND_DROP_SITE))
+    null_index = int(null_index)
+    if not 0 <= null_index < table.shape[0]:
+        raise ValueError("embedding_lookup_drop: null_index=%d must be a row of the table (L = %d)" % (null_index, table.shape[0]))
+    out, eff = _EmbeddingLookupDrop.apply(idx, table, null_index, _drop_p(p), seed, call)
+    return (out, eff) if return_eff else out
 
 
 # ----------------------------------------------------------------------------------------------

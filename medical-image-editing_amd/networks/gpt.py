@@ -34,6 +34,9 @@ Masked resampling.  GPT.generate_masked redraws some positions of a sequence and
 the prompt and the kept codes in front of the first redrawn position, then per position ONE ops.sample_filtered launch - a draw
 (top-k, then top-p) or the kept token, and the log-probability of whichever stands there - and one decode_step.  The resample mask is a
 host array: the plan is made without a synchronisation.  The sum of the log-probabilities scores a candidate (trainers/prior.py).
+With guidance_scale (classifier-free guidance, trainers/cond_prior.py) the same loop runs on ONE cache of 2B rows - the condition's
+prefix in front of the first B, the null condition's in front of the others - and ops.sample_guided draws from z_u + s (z_c - z_u)
+inside the sampler: still one sampler launch and one decode_step per position.
 """
 import numpy as np
 import torch
@@ -286,7 +289,7 @@ class GPT(SeededDropout, nn.Module):
 
     @torch.no_grad()
     def generate_masked(self, idx, known, resample, temperature=1.0, top_k=None, top_p=None, generator=None, uniforms=None,
-                        embeddings=None):
+                        embeddings=None, uncond_embeddings=None, guidance_scale=None):
         """Redraw some positions of a sequence and keep the others: behind the prompt idx (B, Tp) (and `embeddings`), position k
         of the S new ones takes known[:, k] where resample is false and a draw - top-k, then top-p, ops.sample_filtered - where it
         is true.  Either way the token goes into the cache: what follows is conditioned on what was kept and on what was drawn.
@@ -299,7 +302,28 @@ class GPT(SeededDropout, nn.Module):
         that column of where(resample, -1, known) - and one decode_step; the last token is not fed back.  Nothing resampled: one
         prefill and nothing else.  uniforms (S - j0, B), or a generator, as in generate().  Refused before any kernel: training
         mode, Tp + S - 1 > block_size, n_unmasked > Tp + j0 (the decode steps apply no mask: prefill's caveat), shapes, top_p
-        outside (0, 1]."""
+        outside (0, 1].
+
+        Classifier-free guidance.  guidance_scale None or 1.0: the route above, bit for bit; no unconditional row is computed.
+        Otherwise `embeddings` and `uncond_embeddings` (one shape: the condition's prefix and the null condition's) are needed and
+        every draw is made from z = z_u + guidance_scale (z_c - z_u): ONE cache of 2B rows - the rows [0, B) behind `embeddings`,
+        the rows [B, 2B) behind `uncond_embeddings` - ONE prefill over cat(embeddings, uncond_embeddings) with the prompt and the
+        kept prefix repeated, then per position ONE ops.sample_guided launch (the mix is made inside the sampler; its (2B,) output
+        is the next step's idx for both halves) and ONE decode_step at 2B rows: the launch count of the unguided route.  Returns
+        (tokens (B, S), logp (B, S), logp_u (B, S)): the log-probabilities of the tokens under the conditional and under the
+        unconditional rows.  Refused before any kernel as well: guidance without uncond_embeddings (or without embeddings), a shape
+        mismatch between the two, a guidance_scale that is negative or not finite."""
+        guided = guidance_scale is not None and float(guidance_scale) != 1.0
+        if guided:
+            guidance_scale = float(guidance_scale)
+            if not (np.isfinite(guidance_scale) and guidance_scale >= 0.0):
+                raise ValueError("GPT.generate_masked: guidance_scale=%r must be finite and not negative" % (guidance_scale,))
+            if embeddings is None or uncond_embeddings is None:
+                raise ValueError("GPT.generate_masked: guidance_scale=%r needs embeddings and uncond_embeddings, the prefixes of the "
+                                 "condition and of the null condition" % (guidance_scale,))
+            if tuple(uncond_embeddings.shape) != tuple(embeddings.shape):
+                raise ValueError("GPT.generate_masked: uncond_embeddings of shape %s, the shape of embeddings %s expected" % (
+                    tuple(uncond_embeddings.shape), tuple(embeddings.shape)))
         if self.training:
             raise RuntimeError("GPT.generate_masked: inference only, the model is in training mode (call .eval())")
         t = self._new_tokens(idx, embeddings)
@@ -326,6 +350,9 @@ class GPT(SeededDropout, nn.Module):
         if uniforms is not None and tuple(uniforms.shape) != (S - j0, B):
             raise ValueError("GPT.generate_masked: uniforms of shape %s, (S - j0, B) = (%d, %d) expected" % (tuple(uniforms.shape), S - j0, B))
 
+        if guided:
+            return self._generate_guided(idx, known, mask, j0, t, temperature, top_k, top_p, generator, uniforms, embeddings,
+                                         uncond_embeddings, guidance_scale)
         n_pre = min(j0, S - 1)                         # known columns behind the prompt in the prefill
         cache = self.new_cache(B, capacity=t + S - 1)
         dev = cache.kv.device
@@ -348,6 +375,37 @@ class GPT(SeededDropout, nn.Module):
                 if k + 1 < S:
                     step_logits = self.decode_step(new, cache)
         return tokens, logp
+
+    def _generate_guided(self, idx, known, mask, j0, t, temperature, top_k, top_p, generator, uniforms, embeddings, uncond_embeddings,
+                         scale):
+        """generate_masked's guided route behind its checks: the unguided body on 2B rows, ops.sample_guided in place of
+        ops.sample_filtered."""
+        B, S = known.shape
+        n_pre = min(j0, S - 1)
+        cache = self.new_cache(2 * B, capacity=t + S - 1)
+        dev = cache.kv.device
+        prompt = torch.cat((idx, known[:, :n_pre]), dim=1)
+        logits = self.prefill(prompt.repeat(2, 1), cache, torch.cat((embeddings, uncond_embeddings), dim=0))      # (2B, T, V)
+        tokens = torch.empty(B, S, dtype=torch.long, device=dev)
+        logp = torch.empty(B, S, dtype=torch.float32, device=dev)
+        logp_u = torch.empty(B, S, dtype=torch.float32, device=dev)
+        n_xe = n_pre if j0 < S else S
+        if n_xe:
+            tokens[:, :n_xe] = known[:, :n_xe]
+            lp = -ops.cross_entropy(logits[:, t - 1:t - 1 + n_xe], known[:, :n_xe].repeat(2, 1), reduction="none")
+            logp[:, :n_xe], logp_u[:, :n_xe] = lp[:B], lp[B:]
+        if j0 < S:
+            if uniforms is not None:
+                uniforms = uniforms.to(device=dev, dtype=torch.float32)
+            forced = torch.where(torch.from_numpy(mask).to(dev), torch.full_like(known, -1), known).t().contiguous()      # (S, B)
+            step_logits = logits[:, -1, :]
+            for k in range(j0, S):
+                u = uniforms[k - j0] if uniforms is not None else torch.rand(B, generator=generator, device=dev)
+                new, lp, lpu = ops.sample_guided(step_logits, u, scale, forced[k], temperature, top_k, top_p)
+                tokens[:, k], logp[:, k], logp_u[:, k] = new[:B], lp, lpu
+                if k + 1 < S:
+                    step_logits = self.decode_step(new, cache)
+        return tokens, logp, logp_u
 
 
 def decode_pack_layout(n_layer, n_embed, vocab_size):

@@ -25,7 +25,9 @@ without -p, or with -v, is refused.  With model.prior.cond the prior is conditio
 (trainers/cond_prior.py: one conditioning token per latent cell in front of the codes); -p -m synth (Fit.synth) then draws slices
 from the label maps of the first synth.n_slices test slices and, with synth.discs, edits each slice through its label map -
 pictures and synth.csv under <run dir>/synth/.  -m synth without -p, without model.prior.cond or without run.resume_checkpoint is
-refused, and so is -m detect with model.prior.cond.
+refused, and so is -m detect with model.prior.cond.  Classifier-free guidance is opt-in by keys: model.prior.cond.{null_token,
+p_uncond, drop_seed} train the prior with the condition dropped onto a null embedding some of the time, and
+synth.{guidance_scale, rank} (edit.{guidance_scale, rank}) draw from z_u + scale (z_c - z_u); absent keys mean off.
 
 One process per GPU.  With run.num_gpus == 1 this process is the worker.  With more, this process never touches the GPU:
 it starts num_gpus fresh interpreters of this file (`--rank r`, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their

@@ -8,7 +8,7 @@ from .config import (build_first_step_trainer, build_second_step_trainer, build_
                      configure_perceptual_loss,
                      loss_weights, set_transform, build_evaluator)
 from .config import build_prior_trainer, check_prior_config, check_edit_config, check_detect_config, configure_prior  # noqa: F401
-from .config import check_synth_config, prior_condition  # noqa: F401
+from .config import check_synth_config, guidance, prior_cond_drop, prior_condition  # noqa: F401
 from .prior import PriorTrainer, learning_rate, parameter_groups  # noqa: F401
 from .cond_prior import ConditionalPriorTrainer  # noqa: F401
 from .evaluation import Evaluator, write_result_csv  # noqa: F401

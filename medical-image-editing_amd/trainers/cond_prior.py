@@ -13,6 +13,14 @@ torch.long; 'cond', where a batch has it, is the prefix.
 
 synthesize(label | cond) draws every code from the label alone; edit(batch, new_label=...) redraws the cells whose label changed
 under the new label's prefix and keeps every other code.  detect is refused: lesion labels as a condition would leak the answer.
+
+Classifier-free guidance.  Training (p_uncond > 0, a condition built with null_token=True, a cond_drop_seed): the prefix of step n
+is LabelCondition.forward(tokens, drop=(p_uncond, cond_drop_seed, n)) - whole samples read the null embedding, decided by the
+counter-based draw of csrc/dropout.h, a function of (cond_drop_seed, n) alone, so a resumed run continues bit for bit with no new
+checkpoint state; the seed goes into the checkpoint's `extra` and a mismatch on load raises.  validation_step also returns
+loss_uncond, the cross-entropy under the null prefix.  Sampling (synthesize / edit with guidance_scale other than None or 1): the
+null prefix runs beside the label's in GPT.generate_masked's guided route; the result gains scores_uncond and rank='gain' picks the
+candidate whose sum(logp - logp_u) is largest - how much the label explains it - in place of rank='cond', the conditional score.
 """
 import numpy as np
 import torch
@@ -25,9 +33,19 @@ from .prior import PriorTrainer, parameter_groups
 
 class ConditionalPriorTrainer(PriorTrainer):
     def __init__(self, vqgan, gpt, cond, pkeep=1.0, sos_token=0, lr=4.5e-4, betas=(0.9, 0.95), weight_decay=0.01, grad_norm_clip=1.0,
-                 warmup_steps=0, decay_steps=0, seed=0, device="cuda", dropout_seed=None):
+                 warmup_steps=0, decay_steps=0, seed=0, device="cuda", dropout_seed=None, p_uncond=0.0, cond_drop_seed=None):
         if not isinstance(cond, LabelCondition):
             raise TypeError("ConditionalPriorTrainer conditions on a networks.LabelCondition")
+        p_uncond = float(p_uncond)
+        if not 0.0 <= p_uncond < 1.0:
+            raise ValueError("ConditionalPriorTrainer: p_uncond=%r must lie in [0, 1)" % (p_uncond,))
+        if p_uncond > 0 and cond.null_index is None:
+            raise ValueError("ConditionalPriorTrainer: p_uncond=%g needs a condition with the null embedding, LabelCondition(..., "
+                             "null_token=True) (model.prior.cond.null_token)" % p_uncond)
+        if p_uncond > 0 and cond_drop_seed is None:
+            raise ValueError("ConditionalPriorTrainer: p_uncond=%g needs cond_drop_seed (model.prior.cond.drop_seed): the drop of a step "
+                             "is a function of (cond_drop_seed, step)" % p_uncond)
+        self.p_uncond, self.cond_drop_seed = p_uncond, None if cond_drop_seed is None else int(cond_drop_seed)
         self._cond_grid = (cond.h, cond.w)          # read by _latent_grid inside the parent's constructor
         super().__init__(vqgan, gpt, pkeep=pkeep, sos_token=sos_token, lr=lr, betas=betas, weight_decay=weight_decay,
                          grad_norm_clip=grad_norm_clip, warmup_steps=warmup_steps, decay_steps=decay_steps, seed=seed, device=device,
@@ -80,6 +98,70 @@ class ConditionalPriorTrainer(PriorTrainer):
     def _prefix(self, batch):
         return self.cond(self.cond_tokens(batch))
 
+    def _null_prefix(self, B):
+        return self.cond.null_prefix(B)
+
+    def _train_prefix(self, batch):
+        """The prefix of training step step_count: with p_uncond > 0 whole samples are dropped onto the null embedding."""
+        if self.p_uncond > 0:
+            return self.cond(self.cond_tokens(batch), drop=(self.p_uncond, self.cond_drop_seed, self.step_count))
+        return self._prefix(batch)
+
+    def state_dict(self):
+        state = super().state_dict()
+        if self.p_uncond > 0:          # off: the checkpoint's extra is what it was
+            state["extra"].update(cond_drop_seed=self.cond_drop_seed)
+        return state
+
+    def load_state_dict(self, state):
+        extra = state.get("extra") or {}
+        if self.p_uncond > 0 and extra.get("cond_drop_seed", self.cond_drop_seed) != self.cond_drop_seed:
+            raise ValueError("ConditionalPriorTrainer: the checkpoint was trained with cond_drop_seed=%r, this trainer has %r: the run "
+                             "would not continue with the same dropped samples" % (extra["cond_drop_seed"], self.cond_drop_seed))
+        super().load_state_dict(state)
+
+    @torch.no_grad()
+    def validation_step(self, batch):
+        """The parent's; with a null embedding also loss_uncond, the cross-entropy of the same codes under the null prefix (eval
+        mode, no corruption): how much the label is worth is loss_uncond - loss."""
+        out = super().validation_step(batch)
+        if self.cond.null_index is not None:
+            ids = out["ids"]
+            was_training = self.gpt.training
+            self.gpt.eval()
+            try:
+                out["loss_uncond"] = ops.cross_entropy(self._logits(self._inputs(ids, 1.0), self.cond.null_prefix(ids.shape[0])), ids)
+            finally:
+                self.gpt.train(was_training)
+        return out
+
+    def _guidance(self, what, guidance_scale, rank):
+        """(guided?, scale) of a synthesize / edit call, refused before any kernel."""
+        if rank not in ("cond", "gain"):
+            raise ValueError("ConditionalPriorTrainer.%s: rank=%r must be 'cond' or 'gain'" % (what, rank))
+        guided = guidance_scale is not None and float(guidance_scale) != 1.0
+        if guided:
+            scale = float(guidance_scale)
+            if not (np.isfinite(scale) and scale >= 0.0):
+                raise ValueError("ConditionalPriorTrainer.%s: guidance_scale=%r must be finite and not negative" % (what, guidance_scale))
+            if self.cond.null_index is None:
+                raise ValueError("ConditionalPriorTrainer.%s: guidance_scale=%r needs a prior trained with the null embedding "
+                                 "(model.prior.cond.null_token)" % (what, guidance_scale))
+        elif rank == "gain":
+            raise ValueError("ConditionalPriorTrainer.%s: rank='gain' compares the conditional and the unconditional score and needs "
+                             "guidance (guidance_scale other than 1)" % what)
+        return guided, (float(guidance_scale) if guided else None)
+
+    @staticmethod
+    def _rank(logp, logp_u, B, n, rank):
+        """(scores (B, n), scores_uncond or None, the ranking key): sums in double; rank 'gain': sum(logp - logp_u)."""
+        scores = logp.double().sum(1).reshape(B, n)
+        if logp_u is None:
+            return scores, None, scores
+        scores_u = logp_u.double().sum(1).reshape(B, n)
+        key = (logp.double() - logp_u.double()).sum(1).reshape(B, n) if rank == "gain" else scores
+        return scores, scores_u, key
+
     def _logits(self, inp, prefix):
         return self.gpt.forward_tail(inp, prefix, n_tail=inp.shape[1])
 
@@ -88,12 +170,19 @@ class ConditionalPriorTrainer(PriorTrainer):
         raise NotImplementedError("ConditionalPriorTrainer: sampling needs a condition: synthesize(label=...) or synthesize(cond=...)")
 
     @torch.no_grad()
-    def synthesize(self, label=None, cond=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None, generator=None, uniforms=None):
+    def synthesize(self, label=None, cond=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None, generator=None, uniforms=None,
+                   guidance_scale=None, rank="cond"):
         """Slices from label maps alone: every code is drawn.  label (B, H, W) or (B, 1, H, W), or cond (B, Tc) torch.long - exactly
         one.  ONE GPT.generate_masked call behind the prompt [cond prefix | sos] draws all B n_candidates rows with every position
         resampled (the uniforms per candidate, candidate 0 first, as edit draws them); a candidate's score is the sum of its logp in
         double and the first maximum wins.  uniforms (n_candidates, T, B): the draws, in place of the generator.  Returns a dict: ids (B, T) the winner, candidates (B, n, T), scores (B, n) float64, best
-        (B,), cond (B, Tc) and image, the winner through decode_from_ids."""
+        (B,), cond (B, Tc) and image, the winner through decode_from_ids.
+
+        guidance_scale other than None or 1: classifier-free guidance - the null prefix runs beside the label's (GPT.generate_masked's
+        guided route); scores stay the conditional log-probabilities, the dict gains scores_uncond (B, n) float64, the same under
+        the null prefix, and rank='gain' ranks by sum(logp - logp_u) in double (first maximum) in place of rank='cond', the
+        conditional score."""
+        guided, scale = self._guidance("synthesize", guidance_scale, rank)
         if (label is None) == (cond is None):
             raise ValueError("ConditionalPriorTrainer.synthesize: exactly one of label and cond gives the condition")
         n = int(n_candidates)
@@ -112,26 +201,33 @@ class ConditionalPriorTrainer(PriorTrainer):
         was_training = self.gpt.training
         self.gpt.eval()
         try:
-            drawn, logp = self.gpt.generate_masked(start, known, np.ones(T, dtype=bool), temperature=temperature, top_k=top_k, top_p=top_p,
-                                                   uniforms=uniforms, embeddings=self.cond(tokens).repeat_interleave(n, dim=0))
+            kw = dict(temperature=temperature, top_k=top_k, top_p=top_p, uniforms=uniforms, embeddings=self.cond(tokens).repeat_interleave(n, dim=0))
+            if guided:
+                kw.update(uncond_embeddings=self.cond.null_prefix(B * n), guidance_scale=scale)
+            drawn, logp, *rest = self.gpt.generate_masked(start, known, np.ones(T, dtype=bool), **kw)
         finally:
             self.gpt.train(was_training)
-        scores = logp.double().sum(1).reshape(B, n)
-        best = torch.from_numpy(np.argmax(scores.cpu().numpy(), axis=1)).to(self.device)      # the read of the ranking; first maximum
+        scores, scores_u, key = self._rank(logp, rest[0] if guided else None, B, n, rank)
+        best = torch.from_numpy(np.argmax(key.cpu().numpy(), axis=1)).to(self.device)      # the read of the ranking; first maximum
         candidates = drawn.reshape(B, n, T)
         ids = candidates[torch.arange(B, device=self.device), best]
-        return {"ids": ids, "candidates": candidates, "scores": scores, "best": best, "cond": tokens,
-                "image": self.vqgan.decode_from_ids(ids, self.h, self.w)}
+        out = {"ids": ids, "candidates": candidates, "scores": scores, "best": best, "cond": tokens,
+               "image": self.vqgan.decode_from_ids(ids, self.h, self.w)}
+        if guided:
+            out["scores_uncond"] = scores_u
+        return out
 
     # ---------------------------------------------------------------- editing
     @torch.no_grad()
     def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None,
-             generator=None, new_label=None):
+             generator=None, new_label=None, guidance_scale=None, rank="cond"):
         """PriorTrainer.edit under a condition, with a fourth selector: exactly one of mask, box, nll_threshold and new_label.
         With mask, box or nll_threshold the prefix is the batch's own condition.  new_label (the batch's 'label' with the user's
         changes drawn in; same dtype and shape): the prefix comes from new_label, the redrawn cells are those in which any pixel of
         the label changed (ops.cells_changed; one device-to-host read) and every other code is kept.  Returns the parent's dict plus
-        cond (B, Tc), the tokens of the prefix, and label_cells (B, h, w), the same tokens as a map over the latent."""
+        cond (B, Tc), the tokens of the prefix, and label_cells (B, h, w), the same tokens as a map over the latent.
+        guidance_scale and rank as in synthesize: under guidance the dict gains scores_uncond."""
+        guided, scale = self._guidance("edit", guidance_scale, rank)
         if (mask is not None) + (box is not None) + (nll_threshold is not None) + (new_label is not None) != 1:
             raise ValueError("ConditionalPriorTrainer.edit: exactly one of mask, box, nll_threshold and new_label selects the region")
         cells = None
@@ -146,7 +242,7 @@ class ConditionalPriorTrainer(PriorTrainer):
         else:
             tokens = self.cond_tokens(batch)
         out = self._edit(dict(batch, cond=tokens), mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator, cells=cells,
-                         image_size=label_size)[0]
+                         image_size=label_size, guidance=(scale, rank) if guided else None)[0]
         out["cond"], out["label_cells"] = tokens, tokens.reshape(-1, self.h, self.w)
         return out
 

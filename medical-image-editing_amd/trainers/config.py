@@ -21,7 +21,9 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
     config.model.prior.{n_layer, n_head, n_embed, n_unmasked, pkeep, sos_token}, config.prior_optim.{lr, b1, b2, weight_decay,
                  grad_norm_clip, warmup_steps, decay_steps}    (the GPT code prior, -p: keys of this project, the reference has
                  no trainer for its GPT; trainers/prior.py)
-    config.model.prior.cond.{source, n_labels, labels} (optional: the prior conditioned on label maps, trainers/cond_prior.py) and
+    config.model.prior.cond.{source, n_labels, labels} (optional: the prior conditioned on label maps, trainers/cond_prior.py; its
+                 optional {null_token, p_uncond, drop_seed} and synth.{guidance_scale, rank} / edit.{guidance_scale, rank}:
+                 classifier-free guidance, absent meaning off) and
                  config.synth.{n_slices, n_candidates, temperature, top_k, top_p, seed, discs}, config.run.resume_checkpoint
                  (synthesis from label maps, -p -m synth: keys of this project; Fit.synth)
     config.edit.{n_slices, n_candidates, temperature, top_k, top_p, seed} and one of edit.{box, mask_path, nll_threshold},
@@ -158,6 +160,7 @@ def check_edit_config(config):
     if len(given) != 1:
         raise NotImplementedError("editing with the prior (run_vqwnet.py -p -m edit) needs exactly one of edit.{%s}; given: %s"
                                   % (", ".join(EDIT_SELECTORS), ", ".join(given) or "none"))
+    guidance(config, "edit")          # the optional edit.{guidance_scale, rank}
 
 
 DETECT_KEYS = ("n_slices", "n_candidates", "temperature", "top_k", "top_p", "seed", "nll_threshold", "sigma", "against", "weight",
@@ -213,6 +216,53 @@ def prior_condition(config):
     return {"n_labels": int(cond.n_labels), "label_modality": label_modality, "lesions": lesions}
 
 
+def prior_cond_drop(config):
+    """The three optional classifier-free guidance keys of model.prior.cond -> {null_token, p_uncond, drop_seed}; absent (or
+    `false`) means off: no null embedding, p_uncond 0, no seed.  p_uncond > 0 needs null_token and drop_seed."""
+    cond = _get(_get(config.model, "prior"), "cond")
+    what = "the conditional prior (run_vqwnet.py -p with model.prior.cond)"
+    if cond is None or cond is False:
+        return {"null_token": False, "p_uncond": 0.0, "drop_seed": None}
+    null_token = bool(_get(cond, "null_token") or False)
+    p_uncond = _get(cond, "p_uncond")
+    p_uncond = 0.0 if p_uncond is None or p_uncond is False else p_uncond
+    if isinstance(p_uncond, bool) or not isinstance(p_uncond, (int, float)) or not 0.0 <= p_uncond < 1.0:
+        raise ValueError("%s: model.prior.cond.p_uncond=%r must be a number in [0, 1)" % (what, p_uncond))
+    drop_seed = _get(cond, "drop_seed")
+    drop_seed = None if drop_seed is None or drop_seed is False else drop_seed
+    if drop_seed is not None and (isinstance(drop_seed, bool) or not isinstance(drop_seed, int)):
+        raise ValueError("%s: model.prior.cond.drop_seed=%r must be an integer" % (what, drop_seed))
+    if p_uncond > 0 and not null_token:
+        raise ValueError("%s: model.prior.cond.p_uncond=%g drops the condition onto the null embedding and needs "
+                         "model.prior.cond.null_token: true" % (what, p_uncond))
+    if p_uncond > 0 and drop_seed is None:
+        raise ValueError("%s: model.prior.cond.p_uncond=%g needs model.prior.cond.drop_seed, the seed of the dropped samples" % (what, p_uncond))
+    return {"null_token": null_token, "p_uncond": float(p_uncond), "drop_seed": drop_seed}
+
+
+GUIDANCE_RANKS = ("cond", "gain")
+
+
+def guidance(config, name):
+    """The two optional guidance keys of the `synth` or `edit` section `name` -> (guidance_scale, rank); absent (or `false`) means
+    1.0 and 'cond': no guidance, the conditional score ranks.  A scale other than 1 needs model.prior.cond.null_token; rank 'gain'
+    needs a scale other than 1.  No device work."""
+    section = _get(config, name)
+    scale, rank = _get(section, "guidance_scale"), _get(section, "rank")
+    scale = 1.0 if scale is None or scale is False else scale
+    rank = "cond" if rank is None or rank is False else rank
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not (scale == scale and 0.0 <= scale < float("inf")):
+        raise ValueError("%s.guidance_scale=%r must be a finite number >= 0 (1: no guidance)" % (name, scale))
+    if rank not in GUIDANCE_RANKS:
+        raise ValueError("%s.rank=%r is one of %s" % (name, rank, ", ".join(repr(r) for r in GUIDANCE_RANKS)))
+    if float(scale) != 1.0:
+        if prior_condition(config) is None or not prior_cond_drop(config)["null_token"]:
+            raise ValueError("%s.guidance_scale=%g needs a prior trained with the null embedding: model.prior.cond.null_token: true" % (name, scale))
+    elif rank == "gain":
+        raise ValueError("%s.rank='gain' compares the conditional and the unconditional score and needs %s.guidance_scale other than 1" % (name, name))
+    return float(scale), rank
+
+
 SYNTH_KEYS = ("n_slices", "n_candidates", "temperature", "top_k", "top_p", "seed", "discs")
 
 
@@ -236,6 +286,7 @@ def check_synth_config(config):
     if discs is not None and discs is not False:
         if not isinstance(discs, (list, tuple)) or any(not isinstance(d, (list, tuple)) or len(d) != 4 for d in discs):
             raise ValueError("synth.discs is false or a list of [cy, cx, radius, value] (got %r)" % (discs,))
+    guidance(config, "synth")          # the optional synth.{guidance_scale, rank}
 
 
 def check_detect_config(config):
@@ -305,7 +356,10 @@ def build_prior_trainer(config, device="cuda", first_stage_ckpt_path=None):
         from networks import LabelCondition
         from .cond_prior import ConditionalPriorTrainer
         side = latent_size(config)
-        cls, extra = ConditionalPriorTrainer, {"cond": LabelCondition(cond["n_labels"], p.n_embed, side, side)}
+        drop = prior_cond_drop(config)
+        cls, extra = ConditionalPriorTrainer, {"cond": LabelCondition(cond["n_labels"], p.n_embed, side, side, null_token=drop["null_token"])}
+        if drop["p_uncond"] > 0:
+            extra.update(p_uncond=drop["p_uncond"], cond_drop_seed=drop["drop_seed"])
     return cls(vqgan, gpt, pkeep=1.0 if p.pkeep is None else p.pkeep, sos_token=int(p.sos_token or 0), lr=o.lr,
                         betas=(o.b1, o.b2), weight_decay=o.weight_decay or 0.0, grad_norm_clip=o.grad_norm_clip or None,
                         warmup_steps=int(o.warmup_steps or 0), decay_steps=int(o.decay_steps or 0),

@@ -500,7 +500,7 @@ class Fit:
         from (seed, epoch) - the training's random streams are not touched."""
         tr = self.trainer
         n_save = int(_get(self.config.save, "n_save_images", 0) or 0)
-        losses, image, ids = [], None, None
+        losses, uncond, image, ids = [], [], None, None
         for i, batch in enumerate(self.loader("val")):
             if i >= limit:
                 break
@@ -508,14 +508,20 @@ class Fit:
             last = self._step_batch(batch, image)
             out = tr.validation_step(last)
             losses.append(out["loss"])
+            if out.get("loss_uncond") is not None:          # a conditional prior with the null embedding: the same codes under it
+                uncond.append(out["loss_uncond"])
             ids = out["ids"]
         if not losses:
             return None
         val_loss = float(torch.stack(losses).mean())
         ppl = float(np.exp(val_loss))
         self.print("epoch %d: validation cross-entropy %.4f, perplexity %.2f" % (epoch, val_loss, ppl))
+        metrics = {"epoch": epoch, "iteration": self.global_step, "val_loss": val_loss, "ppl": ppl}
+        if uncond:
+            metrics["val_loss_uncond"] = float(torch.stack(uncond).mean())
+            self.print("epoch %d: validation cross-entropy under the null condition %.4f" % (epoch, metrics["val_loss_uncond"]))
         if self.logger is not None:
-            self.logger.log_metrics({"epoch": epoch, "iteration": self.global_step, "val_loss": val_loss, "ppl": ppl})
+            self.logger.log_metrics(metrics)
         n = min(n_save, image.shape[0])
         if n <= 0 or self.logger is None:
             return None
@@ -556,6 +562,10 @@ class Fit:
             selector["mask"] = np.load(e.mask_path)
         else:
             selector["nll_threshold"] = float(e.nll_threshold)
+        from .config import guidance
+        scale, rank = guidance(self.config, "edit")
+        if scale != 1.0:          # classifier-free guidance: the conditional trainer's keywords
+            selector.update(guidance_scale=scale, rank=rank)
         gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
         out_dir = os.path.join(self.logger.log_dir, "edit")
         os.makedirs(out_dir, exist_ok=True)
@@ -602,6 +612,10 @@ class Fit:
         n_slices = int(e.n_slices)
         discs = e.discs if e.discs else []
         kw = dict(n_candidates=int(e.n_candidates), temperature=float(e.temperature or 1.0), top_k=e.top_k or None, top_p=e.top_p or None)
+        from .config import guidance
+        scale, rank = guidance(self.config, "synth")
+        if scale != 1.0:          # classifier-free guidance, for the synthesis and for the edit through the label map
+            kw.update(guidance_scale=scale, rank=rank)
         gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
         out_dir = os.path.join(self.logger.log_dir, "synth")
         os.makedirs(out_dir, exist_ok=True)

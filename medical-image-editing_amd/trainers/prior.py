@@ -179,6 +179,14 @@ class PriorTrainer(TrainerBase):
         """The logits (B, T, V) of the code positions of inp (B, T) behind `prefix`."""
         return self.gpt(inp)
 
+    def _train_prefix(self, batch):
+        """The prefix of a training step: _prefix(batch) (the conditional trainer may drop the condition of some samples)."""
+        return self._prefix(batch)
+
+    def _null_prefix(self, B):
+        """The prefix of the null condition for B rows (the conditional trainer's, under guidance)."""
+        raise NotImplementedError("PriorTrainer: guidance needs a condition (trainers/cond_prior.py)")
+
     def training_step(self, batch, mark=None):
         self.throttle.begin()
         ids = self.codes(batch)
@@ -186,7 +194,7 @@ class PriorTrainer(TrainerBase):
         inp = self._inputs(ids, self.pkeep)
         if self.dropout_seed is not None:
             self.gpt.set_dropout_call(self.step_count)          # the masks of a step: a function of (dropout_seed, step) alone
-        loss = ops.cross_entropy(self._logits(inp, self._prefix(batch)), ids)
+        loss = ops.cross_entropy(self._logits(inp, self._train_prefix(batch)), ids)
         lr = self.current_lr()
         for group in self.optim.param_groups:
             group["lr"] = lr
@@ -308,10 +316,13 @@ class PriorTrainer(TrainerBase):
         composite = ops.paste_cells(image, edit, cellmask).  A {'ids'} batch has no image and no composite."""
         return self._edit(batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator)[0]
 
-    def _edit(self, batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator, cells=None, image_size=None):
+    def _edit(self, batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator, cells=None, image_size=None,
+              guidance=None):
         """edit()'s work -> (edit()'s dict, the token_nll map (B, h, w) the nll_threshold selector computed, else None): what edit
         and detect share.  cells: a host bool array (B, h, w) in place of the three selectors (the conditional trainer's fourth);
-        image_size: the (H, W) a mask or box of a batch without a picture refers to (cell_mask's default otherwise)."""
+        image_size: the (H, W) a mask or box of a batch without a picture refers to (cell_mask's default otherwise).  guidance:
+        None or (scale, rank) of the conditional trainer - the null prefix runs beside the batch's, the dict gains scores_uncond
+        and rank 'gain' ranks by sum(logp - logp_u)."""
         if cells is None and (mask is not None) + (box is not None) + (nll_threshold is not None) != 1:
             raise ValueError("PriorTrainer.edit: exactly one of mask, box and nll_threshold selects the region")
         n = int(n_candidates)
@@ -341,18 +352,25 @@ class PriorTrainer(TrainerBase):
         was_training = self.gpt.training
         self.gpt.eval()
         try:
-            tokens, logp = self.gpt.generate_masked(start, known, resample, temperature=temperature, top_k=top_k, top_p=top_p,
-                                                    uniforms=uniforms,
-                                                    embeddings=None if prefix is None else prefix.repeat_interleave(n, dim=0))
+            kw = dict(temperature=temperature, top_k=top_k, top_p=top_p, uniforms=uniforms,
+                      embeddings=None if prefix is None else prefix.repeat_interleave(n, dim=0))
+            if guidance is not None:
+                kw.update(uncond_embeddings=self._null_prefix(B * n), guidance_scale=guidance[0])
+            tokens, logp, *rest = self.gpt.generate_masked(start, known, resample, **kw)
         finally:
             self.gpt.train(was_training)
         scores = logp.double().sum(1).reshape(B, n)
-        best = torch.from_numpy(np.argmax(scores.cpu().numpy(), axis=1)).to(self.device)      # the read of the ranking; first maximum
+        key = scores
+        if guidance is not None and guidance[1] == "gain":
+            key = (logp.double() - rest[0].double()).sum(1).reshape(B, n)
+        best = torch.from_numpy(np.argmax(key.cpu().numpy(), axis=1)).to(self.device)      # the read of the ranking; first maximum
         candidates = tokens.reshape(B, n, T)
         best_ids = candidates[torch.arange(B, device=self.device), best]
         cellmask = torch.from_numpy(cells.astype(np.uint8)).to(self.device)
         out = {"ids": best_ids, "source_ids": ids, "candidates": candidates, "scores": scores, "best": best, "cellmask": cellmask,
                "recon": self.vqgan.decode_from_ids(ids, self.h, self.w), "edit": self.vqgan.decode_from_ids(best_ids, self.h, self.w)}
+        if guidance is not None:
+            out["scores_uncond"] = rest[0].double().sum(1).reshape(B, n)
         if has_image:
             out["composite"] = ops.paste_cells(image, out["edit"], cellmask)
         return out, nll

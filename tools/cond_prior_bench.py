@@ -15,7 +15,13 @@ around windows of calls, every side warmed up, the sides of a comparison alterna
   synthesize  ConditionalPriorTrainer.synthesize of ONE slice, 8 candidates, top-k 32, top-p 0.95 on the 16 x 16 latent (V = 1024;
               a small VQGAN decodes): ms per call
 
-    python tools/cond_prior_bench.py [--steps 10] [--warmup 3] [--windows 5] [--batch 32] [--hbm-tbs 8.0] [--out FILE]
+  --guidance  classifier-free guidance, in place of the measurements above: synthesize as above on a model with the null embedding
+              at guidance scale 1 (the unguided route: the code the model without a null embedding runs, measured beside it as
+              `plain`) and at scale 3 (one cache of 16 rows, one sampler launch and one decode step per position), with the
+              per-position time = ms / 256; and the two sampler launches alone at B = 8, V = 1024, top-k 32, top-p 0.95:
+              ops.sample_filtered on 8 rows against ops.sample_guided on 8 pairs of rows, microseconds per launch
+
+    python tools/cond_prior_bench.py [--steps 10] [--warmup 3] [--windows 5] [--batch 32] [--hbm-tbs 8.0] [--guidance] [--out FILE]
 """
 import argparse
 import json
@@ -112,6 +118,41 @@ def build_torch(state, ids, cond):
     return step
 
 
+def guidance_lines(args):
+    import torch
+    from hipops import ops
+    from networks import GPT, LabelCondition
+    from trainers import ConditionalPriorTrainer
+    trainers = {}
+    for name, null in (("plain", False), ("null", True)):
+        torch.manual_seed(0)
+        gpt = GPT(V, 2 * T, n_layer=N_LAYER, n_head=N_HEAD, n_embed=N_EMBED, n_unmasked=T)
+        trainers[name] = ConditionalPriorTrainer(small_vqgan(), gpt, LabelCondition(L, N_EMBED, 16, 16, null_token=null), device="cuda")
+    one = torch.randint(0, L, (1, T), device="cuda")
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    kw = dict(cond=one, n_candidates=8, top_k=32, top_p=0.95, generator=gen)
+    sides = {"plain": lambda: trainers["plain"].synthesize(**kw),
+             "scale1": lambda: trainers["null"].synthesize(guidance_scale=1.0, **kw),
+             "scale3": lambda: trainers["null"].synthesize(guidance_scale=3.0, **kw)}
+    rec = measure(sides, args, "synthesize one slice, 8 candidates, top-k 32, top-p 0.95, 16 x 16 latent: no null row / scale 1 / scale 3", steps=2)
+    for n in sides:
+        rec[n + "_per_position_us"] = round(1e3 * rec[n + "_ms"] / T, 3)
+    rec["scale1_over_plain"] = round(rec["scale1_ms"] / rec["plain_ms"], 4)
+    rec["scale3_over_scale1"] = round(rec["scale3_ms"] / rec["scale1_ms"], 4)
+    lines = [rec]
+    B = 8
+    z = torch.randn(2 * B, V, device="cuda")
+    zc = z[:B].contiguous()
+    u = torch.rand(B, device="cuda")
+    launches = {"sample_filtered": lambda: ops.sample_filtered(zc, u, None, 1.0, 32, 0.95),
+                "sample_guided": lambda: ops.sample_guided(z, u, 3.0, None, 1.0, 32, 0.95)}
+    rec = measure(launches, args, "one sampler launch, B=%d V=%d, top-k 32, top-p 0.95: 8 rows against 8 guided pairs" % (B, V), steps=200)
+    for n in launches:
+        rec[n + "_us"] = round(1e3 * rec[n + "_ms"], 3)
+    lines.append(rec)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--steps", type=int, default=10)
@@ -119,12 +160,23 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--hbm-tbs", type=float, default=8.0)
+    ap.add_argument("--guidance", action="store_true", help="measure classifier-free guidance in place of the default measurements")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
     from hipops import ops
     if not torch.cuda.is_available():
         raise SystemExit("cond_prior_bench.py measures on a GPU; none is available")
+    if args.guidance:
+        lines = guidance_lines(args)
+        for rec in lines:
+            print(json.dumps(rec))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                for rec in lines:
+                    f.write(json.dumps(rec) + "\n")
+        return
     lines = []
     sides, state, ids, cond, cond_tr = build_trainers(args.batch)
     sides["torch"] = build_torch(state, ids, cond)
