@@ -990,6 +990,39 @@ int vqw_score_histogram(const float* scores, const uint8_t* labels, long* hist, 
  * out[0..3] are NaN: that is the definition, not an error.  Refused: hist or out null, a pointer not 8-byte aligned. */
 int vqw_detection_scores(const long* hist, const long* err, double* out, void* stream);
 
+/* ---- the bidirectional masked code prior (csrc/masked_prior.hip; networks.MaskedGPT, trainers.MaskedPriorTrainer; MaskGIT's
+ * recipe: fill in masked codes, decode in a few parallel passes).  Added functions only; the ABI stays 9.  Integer LDS atomics only,
+ * no float atomics: the same bits every run.  One workgroup per sample; 1 <= B <= 65535, 1 <= T <= 65536, T a multiple of nothing.
+ * Every refusal arrives with a message that names the constraint, before any launch.
+ * The select: out[b][t] (bytes) = 1 for exactly min(max(n[b], 0), count_b) of the count_b eligible entries of row b - those with
+ * the smallest (key, position) - and 0 elsewhere.  keys [B][T] fp32, compared as unsigned integers under the order-preserving map
+ * of their bits (-0 < +0, the infinities order as numbers, a NaN with a clear sign bit lies above +inf); eligible [B][T] bytes,
+ * null: every entry; n [B] int32.  The n-th smallest key is found by a byte-wise radix walk on an LDS histogram; entries EQUAL to it
+ * are taken in ascending position (a workgroup prefix count), so ties do not depend on scheduling. */
+int vqw_select_lowest(const float* keys, const uint8_t* eligible, const int* n, uint8_t* out, int B, int T, void* stream);
+/* The corruption of a training step, from ids [B][T] (torch.long): sample b masks n[b] = clamp(ceil(r_b T), 1, T) positions (the
+ * product and the ceil in double), r_b = cos(pi/2 u_b) with u_b = draw / 2^32, the draw of csrc/dropout.h for element b under
+ * (seed, call) and the site MASK_RATIO_SITE = -2 (MaskGIT's cosine schedule); 0 < ratio <= 1 replaces r_b for every sample,
+ * ratio = 0 means the schedule.  The masked set: the n[b] positions with the smallest (draw of element b T + t under
+ * MASK_KEY_SITE = -3, t) - the select above over integer keys: exactly n[b], no Bernoulli draw.  inp [B][T] (torch.long) =
+ * mask_token where masked, else ids; masked [B][T] bytes; n [B] int32.  No mask tensor from the host, no host read: the output is
+ * a function of (seed, call) alone.  mask_token >= 0; ids and inp 8-byte, n 4-byte aligned. */
+int vqw_mask_tokens(const long* ids, long* inp, uint8_t* masked, int* n, int B, int T, long mask_token, double ratio, long seed,
+                    long call, void* stream);
+/* One iteration of parallel decoding, one launch.  tokens [B][T] (torch.long), logp [B][T]: vqw_sample_filtered's output over all
+ * B T rows, the known positions forced; masked [B][T] bytes; m0 [B] int32: the positions masked when decoding began.  Per sample,
+ * with cur the masked count now: n_keep = gamma <= 0 ? 0 : max(0, min(cur - 1, floor(gamma m0))), the product in double - every
+ * iteration fixes at least one code, gamma = 0 fixes all.  The confidence of a masked position is logp + tau g with g =
+ * -logf(-logf(clamp(u, 2^-24, 1 - 2^-24))), u [B][T] the caller's uniforms; tau = 0: logp itself, bit for bit, and u is not read
+ * (it may be null).  The n_keep masked positions of lowest (confidence, position) stay masked - the select above.  ids_out [B][T] =
+ * mask_token where still masked, else tokens; masked_out [B][T]; fixed_logp [B][T], in / out: written with logp only where a
+ * position turns from masked to fixed, untouched elsewhere; conf [B][T] (may be null): the confidence of the masked positions,
+ * +inf at the others.  A position that was not masked keeps its token and is never masked.  gamma and tau finite, tau >= 0,
+ * mask_token >= 0; masked_out and ids_out must not be masked and tokens themselves. */
+int vqw_unmask_step(const long* tokens, const float* logp, const uint8_t* masked, const float* u, const int* m0, long* ids_out,
+                    uint8_t* masked_out, float* fixed_logp, float* conf, int B, int T, double gamma, float tau, long mask_token,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

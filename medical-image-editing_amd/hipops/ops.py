@@ -2233,6 +2233,105 @@ def embedding_lookup_drop(idx, table, null_index, p, seed, call, return_eff=Fals
 
 
 # ----------------------------------------------------------------------------------------------
+# the bidirectional masked code prior (csrc/masked_prior.hip): the select, the corruption of a step, one decoding iteration.
+# No gradient.
+# ----------------------------------------------------------------------------------------------
+MASK_RATIO_SITE = -2         # csrc/masked_prior.hip: the dropout site of a sample's masking ratio
+MASK_KEY_SITE = -3           # and of the keys that order its positions
+
+
+def _rows(name, t, dtype, shape, what):
+    """A contiguous (B, T) tensor of `dtype` (and of `shape`, when given) on the device."""
+    if t.dtype != dtype or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError("%s: %s (B, T)%s of %s expected, got %s of %s" % (
+            name, what, "" if shape is None else " = %s" % (tuple(shape),), dtype, tuple(t.shape), t.dtype))
+    _dev(t)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _bytes(name, t, shape, what):
+    """A (B, T) mask as torch.uint8 (torch.bool is viewed, not copied)."""
+    if t.dtype == torch.bool:
+        t = (t if t.is_contiguous() else t.contiguous()).view(torch.uint8)
+    return _rows(name, t, torch.uint8, shape, what)
+
+
+def _counts(name, n, B, device, what):
+    """A per-sample count as (B,) torch.int32 on the device: a tensor of B integers, or one Python integer for every sample."""
+    if not torch.is_tensor(n):
+        return torch.full((B,), int(n), dtype=torch.int32, device=device)
+    _dev(n)
+    if n.dtype not in (torch.int32, torch.long) or tuple(n.shape) != (B,):
+        raise RuntimeError("%s: %s (B,) = (%d,) of torch.int32 expected, got %s of %s" % (name, what, B, tuple(n.shape), n.dtype))
+    return n.to(torch.int32).contiguous()
+
+
+def select_lowest(keys, n, eligible=None):
+    """(B, T) torch.uint8: 1 at exactly min(max(n[b], 0), count_b) of the eligible entries of row b of keys (B, T) fp32 - those with
+    the smallest (key, position) - and 0 elsewhere.  The keys are compared by the order-preserving integer image of their bits: -0
+    lies below +0, the infinities order as numbers.  n: (B,) torch.int32 (or one integer); eligible (B, T) torch.uint8 / bool or
+    None (every entry).  Equal keys are taken in ascending position; the same bytes every run."""
+    keys = _rows("select_lowest", _flat(keys), torch.float32, None, "keys")
+    B, T = keys.shape
+    if eligible is not None:
+        eligible = _bytes("select_lowest", eligible, keys.shape, "eligible")
+    n = _counts("select_lowest", n, B, keys.device, "n")
+    out = torch.empty((B, T), dtype=torch.uint8, device=keys.device)
+    _L().vqw_select_lowest(keys, eligible, n, out, B, T)
+    return out
+
+
+def mask_tokens(ids, mask_token, seed, call, ratio=None):
+    """The corruption of a training step of the masked prior: ids (B, T) torch.long -> (inp (B, T) torch.long with mask_token at
+    the masked positions, masked (B, T) torch.uint8, n (B,) torch.int32, the masked count per sample).  Sample b masks n_b =
+    clamp(ceil(cos(pi/2 u_b) T), 1, T) positions, u_b the draw of csrc/dropout.h for element b under (seed, call, MASK_RATIO_SITE)
+    over 2^32; the positions are the n_b smallest (draw of element b T + t under MASK_KEY_SITE, t): exactly n_b.  ratio in (0, 1]
+    replaces the cosine for every sample (validation).  No mask tensor, no host read: a function of (seed, call) alone."""
+    if ratio is not None and not 0.0 < float(ratio) <= 1.0:
+        raise ValueError("mask_tokens: ratio=%r must lie in (0, 1] (None: the cosine schedule)" % (ratio,))
+    seed, call, _ = _drop_key((seed, call, MASK_KEY_SITE))
+    ids = _rows("mask_tokens", ids, torch.long, None, "ids")
+    B, T = ids.shape
+    inp = torch.empty_like(ids)
+    masked = torch.empty((B, T), dtype=torch.uint8, device=ids.device)
+    n = torch.empty(B, dtype=torch.int32, device=ids.device)
+    _L().vqw_mask_tokens(ids, inp, masked, n, B, T, int(mask_token), 0.0 if ratio is None else float(ratio), seed, call)
+    return inp, masked, n
+
+
+def unmask_step(tokens, logp, masked, m0, gamma, tau, mask_token, u=None, fixed_logp=None, return_conf=False):
+    """One iteration of parallel decoding, one launch: tokens (B, T) torch.long and logp (B, T) fp32 - sample_filtered's output over
+    all B T rows, the known positions forced - masked (B, T) torch.uint8 / bool, m0 (B,) torch.int32: the masked count when
+    decoding began.  Per sample n_keep = 0 if gamma <= 0 else max(0, min(cur - 1, floor(gamma m0))) of the cur masked positions
+    stay masked: those of lowest (confidence, position), confidence = logp + tau g, g the Gumbel noise of u (B, T) fp32 in [0, 1);
+    tau = 0: logp itself and u may be None.  Returns (ids (B, T) with mask_token where still masked, masked (B, T) torch.uint8,
+    fixed_logp (B, T)) and, return_conf, the confidences (+inf where nothing was masked).  fixed_logp is updated IN PLACE when
+    given - logp where a position turns from masked to fixed, untouched elsewhere - else it starts from zeros."""
+    tokens = _rows("unmask_step", tokens, torch.long, None, "tokens")
+    B, T = tokens.shape
+    logp = _rows("unmask_step", _flat(logp), torch.float32, (B, T), "logp")
+    masked = _bytes("unmask_step", masked, (B, T), "masked")
+    gamma, tau = float(gamma), float(tau)
+    if u is not None:
+        u = _rows("unmask_step", _flat(u), torch.float32, (B, T), "u")
+    elif tau != 0.0:
+        raise RuntimeError("unmask_step: tau=%g needs the uniforms u (only tau = 0 reads none)" % tau)
+    m0 = _counts("unmask_step", m0, B, tokens.device, "m0")
+    if fixed_logp is None:
+        fixed_logp = torch.zeros((B, T), dtype=torch.float32, device=tokens.device)
+    else:
+        _dev(fixed_logp)
+        if fixed_logp.dtype != torch.float32 or tuple(fixed_logp.shape) != (B, T) or not fixed_logp.is_contiguous():
+            raise RuntimeError("unmask_step: fixed_logp (B, T) = %s fp32, contiguous, expected (it is updated in place), got %s of %s" % (
+                (B, T), tuple(fixed_logp.shape), fixed_logp.dtype))
+    ids_out = torch.empty_like(tokens)
+    masked_out = torch.empty((B, T), dtype=torch.uint8, device=tokens.device)
+    conf = torch.empty((B, T), dtype=torch.float32, device=tokens.device) if return_conf else None
+    _L().vqw_unmask_step(tokens, logp, masked, u, m0, ids_out, masked_out, fixed_logp, conf, B, T, gamma, tau, int(mask_token))
+    return (ids_out, masked_out, fixed_logp, conf) if return_conf else (ids_out, masked_out, fixed_logp)
+
+
+# ----------------------------------------------------------------------------------------------
 # cached generation (networks/gpt.py GPT.decode_step / generate): the decode kernels.  Forward only.
 # ----------------------------------------------------------------------------------------------
 def _no_grad(name, *ts):

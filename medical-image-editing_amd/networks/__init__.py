@@ -12,5 +12,5 @@ from .unet_discriminator import UNetDiscriminator  # noqa: F401
 from .vqgan import Normalize, nonlinearity, Upsample, ResnetBlock, AttnBlock, Decoder  # noqa: F401
 from .vqgan_model import Downsample, Encoder, VQGAN  # noqa: F401
 from .mingpt import GPTConfig, GPT1Config, CausalSelfAttention, Block  # noqa: F401
-from .gpt import GPT, KVCache  # noqa: F401
+from .gpt import GPT, KVCache, MaskedGPT, unmask_schedule  # noqa: F401
 from .label_condition import LabelCondition  # noqa: F401

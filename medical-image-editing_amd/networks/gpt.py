@@ -37,7 +37,15 @@ host array: the plan is made without a synchronisation.  The sum of the log-prob
 With guidance_scale (classifier-free guidance, trainers/cond_prior.py) the same loop runs on ONE cache of 2B rows - the condition's
 prefix in front of the first B, the null condition's in front of the others - and ops.sample_guided draws from z_u + s (z_c - z_u)
 inside the sampler: still one sampler launch and one decode_step per position.
+
+Bidirectional masked prior.  MaskedGPT is the same tree with n_unmasked = block_size - every position sees every position - a token
+table of vocab_size + 1 rows, the last one the mask token, and a head of vocab_size outputs, so the mask token can never be drawn.
+It is trained to fill in masked codes (trainers/masked_prior.py) and decoded in a few parallel passes, MaskedGPT.generate_parallel:
+per pass one forward, one ops.sample_filtered launch over all B T rows and one ops.unmask_step launch, which fixes the confident
+codes and masks the others again (MaskGIT).  A bidirectional model has no past: the cached routes raise NotImplementedError.
 """
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -406,6 +414,111 @@ class GPT(SeededDropout, nn.Module):
                 if k + 1 < S:
                     step_logits = self.decode_step(new, cache)
         return tokens, logp, logp_u
+
+
+def unmask_schedule(k, n_steps, choice_temperature):
+    """(gamma, tau) of iteration k of n_steps of MaskedGPT.generate_parallel: the share cos(pi/2 (k + 1) / n_steps) of the initially
+    masked positions that stays masked behind it - exactly 0 at the last iteration - and the temperature choice_temperature (1 -
+    (k + 1) / n_steps) of the Gumbel noise on the confidences."""
+    r = (k + 1) / n_steps
+    return (0.0 if k + 1 >= n_steps else math.cos(0.5 * math.pi * r)), float(choice_temperature) * (1.0 - r)
+
+
+class MaskedGPT(GPT):
+    """The bidirectional code prior: GPT's tree, parameter names and order, with tok_embed of vocab_size + 1 rows (row vocab_size is
+    the mask token), a head of vocab_size outputs and n_unmasked = block_size.  No start token.  forward() is GPT's; seeded dropout
+    works unchanged.  config.vocab_size stays the number of codes; mask_token = vocab_size."""
+
+    def __init__(self, vocab_size, block_size, n_layer=12, n_head=8, n_embed=256, emb_pdrop=0.0, res_pdrop=0.0, att_pdrop=0.0):
+        super().__init__(vocab_size, block_size, n_layer=n_layer, n_head=n_head, n_embed=n_embed, emb_pdrop=emb_pdrop,
+                         res_pdrop=res_pdrop, att_pdrop=att_pdrop, n_unmasked=block_size)
+        self.mask_token = int(vocab_size)
+        self.tok_embed = nn.Embedding(vocab_size + 1, n_embed)          # takes tok_embed's place in the tree: the order stays GPT's
+        self._init_weights(self.tok_embed)
+
+    def _no_past(self, what):
+        raise NotImplementedError("MaskedGPT.%s: a bidirectional model has no past - every position sees every position, so nothing "
+                                  "can be cached; use forward() or generate_parallel()" % what)
+
+    def new_cache(self, *args, **kwargs):
+        self._no_past("new_cache")
+
+    def prefill(self, *args, **kwargs):
+        self._no_past("prefill")
+
+    def decode_step(self, *args, **kwargs):
+        self._no_past("decode_step")
+
+    def generate(self, *args, **kwargs):
+        self._no_past("generate")
+
+    def generate_masked(self, *args, **kwargs):
+        self._no_past("generate_masked")
+
+    def sample(self, *args, **kwargs):
+        self._no_past("sample")
+
+    def forward_with_past(self, *args, **kwargs):
+        self._no_past("forward_with_past")
+
+    @torch.no_grad()
+    def generate_parallel(self, ids, masked, n_steps, temperature=1.0, top_k=None, top_p=None, choice_temperature=4.5, generator=None,
+                          uniforms=None):
+        """Fill in the masked positions of ids (B, T) torch.long in n_steps parallel passes, in eval mode: masked (B, T) torch.uint8 /
+        bool on the device (what ids holds there is not read).  Iteration k: one forward of the current ids (the mask token at the
+        masked positions), one ops.sample_filtered launch over the (B T, V) rows - forced to the code where it is known, a draw
+        (temperature, top-k, top-p) where it is masked - and one ops.unmask_step launch with unmask_schedule(k, n_steps,
+        choice_temperature): the floor(gamma m0) least confident draws are masked again, the others are fixed.  The last iteration
+        fixes everything.  m0, the masked count at the start, is a device tensor: no host read inside the loop.
+
+        Returns (ids (B, T), fixed_logp (B, T) fp32): a fixed position's log-probability (temperature 1, unfiltered) under the pass
+        that fixed it, 0 at the positions that were known.  A sample with nothing masked comes back unchanged.  Without `uniforms`
+        each iteration draws torch.rand(B T) for the sampler and then torch.rand(B, T) for the confidences from `generator`;
+        uniforms (n_steps, 2, B, T) replaces them: index 0 feeds the sampler, index 1 the confidences."""
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("MaskedGPT.generate_parallel: n_steps=%r must be at least 1" % (n_steps,))
+        if ids.dim() != 2 or ids.dtype != torch.long or ids.shape[1] < 1 or ids.shape[1] > self.block_size:
+            raise ValueError("MaskedGPT.generate_parallel: ids (B, T) torch.long with 1 <= T <= block_size=%d expected, got %s of %s" % (
+                self.block_size, tuple(ids.shape), ids.dtype))
+        B, T = ids.shape
+        if tuple(masked.shape) != (B, T) or masked.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("MaskedGPT.generate_parallel: masked (B, T) = (%d, %d) torch.uint8 or torch.bool expected, got %s of %s" % (
+                B, T, tuple(masked.shape), masked.dtype))
+        if not temperature > 0:
+            raise ValueError("MaskedGPT.generate_parallel: temperature=%r must be positive" % (temperature,))
+        if top_p is not None and not 0 < top_p <= 1:
+            raise ValueError("MaskedGPT.generate_parallel: top_p=%r must lie in (0, 1]" % (top_p,))
+        if not (math.isfinite(float(choice_temperature)) and choice_temperature >= 0):
+            raise ValueError("MaskedGPT.generate_parallel: choice_temperature=%r must be finite and not negative" % (choice_temperature,))
+        if uniforms is not None and tuple(uniforms.shape) != (n_steps, 2, B, T):
+            raise ValueError("MaskedGPT.generate_parallel: uniforms of shape %s, (n_steps, 2, B, T) = (%d, 2, %d, %d) expected" % (
+                tuple(uniforms.shape), n_steps, B, T))
+        dev, V = self.head.weight.device, self.config.vocab_size
+        was_training = self.training
+        self.eval()
+        try:
+            if uniforms is not None:
+                uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
+            masked = masked.to(dev).contiguous().view(torch.uint8)
+            m0 = masked.sum(1, dtype=torch.int32)
+            cur = torch.where(masked != 0, torch.full_like(ids, self.mask_token), ids.to(dev))
+            fixed_logp = torch.zeros(B, T, dtype=torch.float32, device=dev)
+            for k in range(n_steps):
+                gamma, tau = unmask_schedule(k, n_steps, choice_temperature)
+                logits = self(cur)
+                if uniforms is not None:
+                    u_draw, u_conf = uniforms[k, 0].reshape(-1), uniforms[k, 1]
+                else:
+                    u_draw = torch.rand(B * T, generator=generator, device=dev)
+                    u_conf = torch.rand(B, T, generator=generator, device=dev)
+                forced = torch.where(masked != 0, torch.full_like(cur, -1), cur).reshape(-1)
+                tokens, logp = ops.sample_filtered(logits.reshape(B * T, V), u_draw, forced, temperature, top_k, top_p)
+                cur, masked, fixed_logp = ops.unmask_step(tokens.view(B, T), logp.view(B, T), masked, m0, gamma, tau, self.mask_token,
+                                                          u=u_conf, fixed_logp=fixed_logp)
+        finally:
+            self.train(was_training)
+        return cur, fixed_logp
 
 
 def decode_pack_layout(n_layer, n_embed, vocab_size):

@@ -28,6 +28,10 @@ pictures and synth.csv under <run dir>/synth/.  -m synth without -p, without mod
 refused, and so is -m detect with model.prior.cond.  Classifier-free guidance is opt-in by keys: model.prior.cond.{null_token,
 p_uncond, drop_seed} train the prior with the condition dropped onto a null embedding some of the time, and
 synth.{guidance_scale, rank} (edit.{guidance_scale, rank}) draw from z_u + scale (z_c - z_u); absent keys mean off.
+With model.prior.masked = {n_steps, choice_temperature, mask_seed} -p trains the bidirectional masked prior instead
+(trainers/masked_prior.py: networks.MaskedGPT learns to fill in masked codes) and -p -m edit fills the region in again in
+edit.n_steps (default: masked.n_steps) parallel passes that see the kept codes on both sides; edit.nll_threshold, -m detect and
+model.prior.cond are refused with it.  Absent or `false`, every mode is what it was.
 
 One process per GPU.  With run.num_gpus == 1 this process is the worker.  With more, this process never touches the GPU:
 it starts num_gpus fresh interpreters of this file (`--rank r`, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their
@@ -101,6 +105,10 @@ def check_arguments(config, args):
         if prior_condition(config) is not None:
             raise NotImplementedError("-m detect with model.prior.cond: a prior conditioned on the lesion labels is told where the lesion "
                                       "is; detection needs the unconditional prior")
+        from trainers.config import prior_masked
+        if prior_masked(config) is not None:
+            raise NotImplementedError("-m detect with model.prior.masked: detection selects the codes to restore by a raster-order "
+                                      "likelihood, which the masked prior does not define; it needs the autoregressive prior")
     elif args.mode == "synth":
         if not prior:
             raise ValueError("-m synth: synthesis draws slices from label maps with the conditional code prior and needs -p")

@@ -26,6 +26,9 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
                  classifier-free guidance, absent meaning off) and
                  config.synth.{n_slices, n_candidates, temperature, top_k, top_p, seed, discs}, config.run.resume_checkpoint
                  (synthesis from label maps, -p -m synth: keys of this project; Fit.synth)
+    config.model.prior.masked.{n_steps, choice_temperature, mask_seed} (optional: the bidirectional masked prior decoded in n_steps
+                 parallel passes, trainers/masked_prior.py; absent or `false`: the autoregressive prior.  pkeep and sos_token are
+                 ignored with it, model.prior.cond beside it is refused; edit.n_steps overrides n_steps for -p -m edit)
     config.edit.{n_slices, n_candidates, temperature, top_k, top_p, seed} and one of edit.{box, mask_path, nll_threshold},
                  config.run.resume_checkpoint    (editing with the prior, -p -m edit: keys of this project; Fit.edit)
     config.detect.{n_slices, n_candidates, temperature, top_k, top_p, seed, nll_threshold, sigma, against, weight, labels},
@@ -137,6 +140,35 @@ def check_prior_config(config):
         if missing:
             raise NotImplementedError("the prior trainer (run_vqwnet.py -p, trainers.build_prior_trainer) needs %s.{%s}; missing: %s"
                                       % (where, ", ".join(keys), ", ".join(missing)))
+    prior_masked(config)          # the optional model.prior.masked: its keys and what it excludes
+
+
+MASKED_KEYS = ("n_steps", "choice_temperature", "mask_seed")
+
+
+def prior_masked(config):
+    """The optional model.prior.masked = {"n_steps", "choice_temperature", "mask_seed"} -> None (absent or `false`: the
+    autoregressive prior, exactly as without the key) or {n_steps, choice_temperature, mask_seed}: the bidirectional masked prior
+    (trainers/masked_prior.py).  model.prior.{pkeep, sos_token} are ignored with it; model.prior.cond beside it raises."""
+    masked = _get(_get(config.model, "prior"), "masked")
+    if masked is None or masked is False:
+        return None
+    what = "the masked prior (run_vqwnet.py -p with model.prior.masked)"
+    missing = [k for k in MASKED_KEYS if not hasattr(masked, k)]
+    if missing:
+        raise NotImplementedError("%s needs model.prior.masked.{%s}; missing: %s" % (what, ", ".join(MASKED_KEYS), ", ".join(missing)))
+    cond = _get(config.model.prior, "cond")
+    if cond is not None and cond is not False:
+        raise NotImplementedError("%s: model.prior.cond beside model.prior.masked - conditioning the masked prior on label maps is "
+                                  "not built (out of scope)" % what)
+    n_steps, tau, seed = masked.n_steps, masked.choice_temperature, masked.mask_seed
+    if isinstance(n_steps, bool) or not isinstance(n_steps, int) or n_steps < 1:
+        raise ValueError("%s: model.prior.masked.n_steps=%r must be an integer >= 1" % (what, n_steps))
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0 <= float(tau) < float("inf"):
+        raise ValueError("%s: model.prior.masked.choice_temperature=%r must be a finite number >= 0" % (what, tau))
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError("%s: model.prior.masked.mask_seed=%r must be an integer" % (what, seed))
+    return {"n_steps": n_steps, "choice_temperature": float(tau), "mask_seed": seed}
 
 
 EDIT_KEYS = ("n_slices", "n_candidates", "temperature", "top_k", "top_p", "seed")
@@ -161,6 +193,27 @@ def check_edit_config(config):
         raise NotImplementedError("editing with the prior (run_vqwnet.py -p -m edit) needs exactly one of edit.{%s}; given: %s"
                                   % (", ".join(EDIT_SELECTORS), ", ".join(given) or "none"))
     guidance(config, "edit")          # the optional edit.{guidance_scale, rank}
+    edit_n_steps(config)              # the optional edit.n_steps of the masked prior
+
+
+def edit_n_steps(config):
+    """The optional edit.n_steps -> None (absent or `false`: the trainer's model.prior.masked.n_steps) or the number of parallel
+    decoding passes of an edit with the masked prior.  It means nothing to the autoregressive prior, which refuses it; the masked
+    prior in turn has no likelihood map: edit.nll_threshold is refused with it."""
+    section, masked = _get(config, "edit"), prior_masked(config)
+    n_steps = _get(section, "n_steps")
+    if n_steps is not None and n_steps is not False:
+        if masked is None:
+            raise ValueError("edit.n_steps=%r is the number of decoding passes of the masked prior and needs model.prior.masked" % (n_steps,))
+        if isinstance(n_steps, bool) or not isinstance(n_steps, int) or n_steps < 1:
+            raise ValueError("edit.n_steps=%r must be an integer >= 1" % (n_steps,))
+    else:
+        n_steps = None
+    if masked is not None and _get(section, "nll_threshold") is not None:
+        raise NotImplementedError("editing with the masked prior (run_vqwnet.py -p -m edit with model.prior.masked): edit.nll_threshold "
+                                  "selects by a raster-order likelihood, which the masked prior does not define; use edit.box or "
+                                  "edit.mask_path")
+    return n_steps
 
 
 DETECT_KEYS = ("n_slices", "n_candidates", "temperature", "top_k", "top_p", "seed", "nll_threshold", "sigma", "against", "weight",
@@ -327,6 +380,10 @@ def configure_prior(config):
     from networks import GPT
     p = config.model.prior
     side = latent_size(config)
+    if prior_masked(config) is not None:          # the bidirectional masked prior: h w positions, every one sees every one
+        from networks import MaskedGPT
+        return MaskedGPT(vocab_size=config.model.vqgan.dict_size, block_size=side * side, n_layer=p.n_layer, n_head=p.n_head,
+                         n_embed=p.n_embed, **{k: float(_get(p, k) or 0.0) for k in ("emb_pdrop", "res_pdrop", "att_pdrop")})
     positions, n_unmasked = side * side, int(p.n_unmasked or 0)
     if prior_condition(config) is not None:          # [h w conditioning tokens | h w codes], the prefix fully visible
         if n_unmasked not in (0, side * side):
@@ -352,6 +409,10 @@ def build_prior_trainer(config, device="cuda", first_stage_ckpt_path=None):
         load_vqgan_from_ckpt(first, vqgan)
     p, o = config.model.prior, config.prior_optim
     cls, extra, cond = PriorTrainer, {}, prior_condition(config)
+    masked = prior_masked(config)
+    if masked is not None:
+        from .masked_prior import MaskedPriorTrainer
+        cls, extra = MaskedPriorTrainer, dict(masked)
     if cond is not None:
         from networks import LabelCondition
         from .cond_prior import ConditionalPriorTrainer

@@ -562,10 +562,13 @@ class Fit:
             selector["mask"] = np.load(e.mask_path)
         else:
             selector["nll_threshold"] = float(e.nll_threshold)
-        from .config import guidance
+        from .config import guidance, edit_n_steps
         scale, rank = guidance(self.config, "edit")
         if scale != 1.0:          # classifier-free guidance: the conditional trainer's keywords
             selector.update(guidance_scale=scale, rank=rank)
+        n_steps = edit_n_steps(self.config)
+        if n_steps is not None:   # the masked prior's keyword: the number of parallel decoding passes
+            selector.update(n_steps=n_steps)
         gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
         out_dir = os.path.join(self.logger.log_dir, "edit")
         os.makedirs(out_dir, exist_ok=True)

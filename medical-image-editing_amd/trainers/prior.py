@@ -363,17 +363,24 @@ class PriorTrainer(TrainerBase):
         key = scores
         if guidance is not None and guidance[1] == "gain":
             key = (logp.double() - rest[0].double()).sum(1).reshape(B, n)
+        out = self._edit_result(ids, tokens, scores, key, cells, image)
+        if guidance is not None:
+            out["scores_uncond"] = rest[0].double().sum(1).reshape(B, n)
+        return out, nll
+
+    def _edit_result(self, ids, tokens, scores, key, cells, image):
+        """edit()'s dict from the drawn candidates: tokens (B n, T) in draw order, scores and the ranking key (B, n) float64, cells
+        the host bool array (B, h, w), image the slices or None ({'ids'} batch: no composite).  One device-to-host read ranks."""
+        (B, T), n = ids.shape, scores.shape[1]
         best = torch.from_numpy(np.argmax(key.cpu().numpy(), axis=1)).to(self.device)      # the read of the ranking; first maximum
         candidates = tokens.reshape(B, n, T)
         best_ids = candidates[torch.arange(B, device=self.device), best]
         cellmask = torch.from_numpy(cells.astype(np.uint8)).to(self.device)
         out = {"ids": best_ids, "source_ids": ids, "candidates": candidates, "scores": scores, "best": best, "cellmask": cellmask,
                "recon": self.vqgan.decode_from_ids(ids, self.h, self.w), "edit": self.vqgan.decode_from_ids(best_ids, self.h, self.w)}
-        if guidance is not None:
-            out["scores_uncond"] = rest[0].double().sum(1).reshape(B, n)
-        if has_image:
+        if image is not None:
             out["composite"] = ops.paste_cells(image, out["edit"], cellmask)
-        return out, nll
+        return out
 
     # ---------------------------------------------------------------- anomaly detection
     @torch.no_grad()
