@@ -1023,6 +1023,34 @@ int vqw_unmask_step(const long* tokens, const float* logp, const uint8_t* masked
                     uint8_t* masked_out, float* fixed_logp, float* conf, int B, int T, double gamma, float tau, long mask_token,
                     void* stream);
 
+/* ---- scores of the prior's samples (csrc/sample_scores.hip; functions/sample_scores.py, PriorTrainer.score, Fit.score; the
+ * reference has nothing like it).  Added functions only; the ABI stays 9.  Feature rows x [N][D], fp32, dense, 1 <= D <= 2048, any
+ * N >= 1 up to 2^30; a row is used as y = fp32(x - shift), one fp32 subtraction per element while staging, shift [D] or null (0):
+ * the caller's centring, which keeps the Gram form below from cancelling on features far from the origin.  No float atomics; the
+ * same bits every run.  Every refusal arrives with a message that names the constraint, before any launch: D or k out of range,
+ * N < k + 1, a null or misaligned pointer (4 bytes for fp32 / int32, 8 for doubles), N or M above 2^30, a short workspace.
+ * Moments: sum [D] += sum_n y and outer [D][D] += sum_n y y^T, both double and ACCUMULATED (the caller clears them once), the
+ * products in double (exact for fp32 factors), plain double FMAs.  The rows are split over workgroups and each split is walked in
+ * row order; the splits are folded in index order; both triangles of outer are written from one folded value, so it stays exactly
+ * symmetric.  ws: vqw_feature_moments_ws_bytes(N, D) bytes, 8-byte aligned (0 for an argument out of range).
+ * Distances: d2(q, a) = max(0, |q|^2 + |a|^2 - 2 q.a) in fp32, the products on the exact-fp32 matrix cores, the squared norms
+ * through the same instruction in the same column order, so bit-identical rows have d2 exactly 0.  Centre tiles of 64 rows stream
+ * through LDS against a query tile of 64 rows; the row reduction runs in registers; the N x M distances are never written and the
+ * workspace holds the squared norms alone ((N + M) floats: vqw_knn_radius_ws_bytes(N), vqw_ball_counts_ws_bytes(M, N)).
+ * vqw_knn_radius: r2 [N], r2[i] = the k-th smallest d2(i, j) over j != i - self is excluded by index, not by value; 1 <= k <= 8,
+ * N >= k + 1.
+ * vqw_ball_counts: queries q [M][D], centres a [N][D], r2 [N].  cnt_q [M] (int32) = the number of i with d2(q, a_i) <= r2[i]
+ * (inclusive); hit_a [N] (int32) = the number of queries inside ball i, cleared by the call and counted with integer atomics
+ * (counts have no order).  A NaN r2[i] contains nobody. */
+size_t vqw_feature_moments_ws_bytes(long N, int D);
+int vqw_feature_moments(const float* x, const float* shift, double* sum, double* outer, void* ws, size_t ws_bytes, long N, int D,
+                        void* stream);
+size_t vqw_knn_radius_ws_bytes(long N);
+int vqw_knn_radius(const float* a, const float* shift, float* r2, void* ws, size_t ws_bytes, long N, int D, int k, void* stream);
+size_t vqw_ball_counts_ws_bytes(long M, long N);
+int vqw_ball_counts(const float* q, const float* a, const float* r2, const float* shift, int32_t* cnt_q, int32_t* hit_a, void* ws,
+                    size_t ws_bytes, long M, long N, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

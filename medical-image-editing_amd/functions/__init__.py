@@ -7,3 +7,4 @@ from .freq_loss import FocalFrequencyLoss  # noqa: F401
 from .perceptual_loss import VGGLoss  # noqa: F401
 from .lpips_loss import LPIPSLoss  # noqa: F401
 from .metrics import MeanSquaredError, StructuralSimilarityIndexMeasure, PeakSignalNoiseRatio, label_entropy  # noqa: F401
+from .sample_scores import FeatureStats, Moments, frechet_distance, manifold_scores, code_scores, sample_scores  # noqa: F401

@@ -2076,6 +2076,91 @@ def detection_scores(hist, err=None):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# scores of the prior's samples (csrc/sample_scores.hip): feature rows (N, D) fp32, used as fp32(x - shift)
+# ----------------------------------------------------------------------------------------------
+FEATURE_MAX_D = 2048
+KNN_MAX_K = 8
+
+
+def _feature_rows(name, x, what, D=None):
+    _dev(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise RuntimeError("%s: %s (N, D) fp32 with N, D >= 1 expected, got %s of %s" % (name, what, tuple(x.shape), x.dtype))
+    if not 1 <= x.shape[1] <= FEATURE_MAX_D:
+        raise RuntimeError("%s: D=%d out of [1, %d]" % (name, x.shape[1], FEATURE_MAX_D))
+    if D is not None and x.shape[1] != D:
+        raise RuntimeError("%s: %s has D=%d, expected %d" % (name, what, x.shape[1], D))
+    return x.detach().contiguous()
+
+
+def _feature_shift(name, shift, D, like):
+    if shift is None:
+        return None
+    _dev(shift)
+    if shift.dtype != torch.float32 or tuple(shift.shape) != (D,) or shift.device != like.device:
+        raise RuntimeError("%s: shift (%d,) fp32 on %s expected, got %s of %s" % (name, D, like.device, tuple(shift.shape), shift.dtype))
+    return shift.detach().contiguous()
+
+
+def feature_moments(x, sum, outer, shift=None):
+    """Adds the moments of the feature rows x (N, D) fp32 IN PLACE: sum (D,) float64 += sum_n y, outer (D, D) float64 += sum_n y
+    y^T with y = fp32(x - shift), the products and sums in double, in a fixed order (the same bytes every run), outer exactly
+    symmetric.  sum and outer are contiguous float64 tensors the caller zeroed once; shift (D,) fp32 or None.  Returns None.  No
+    gradient."""
+    x = _feature_rows("feature_moments", x, "x")
+    N, D = x.shape
+    _dev(sum, outer)
+    if sum.dtype != torch.float64 or tuple(sum.shape) != (D,) or not sum.is_contiguous():
+        raise RuntimeError("feature_moments: sum (%d,) float64, contiguous, expected, got %s of %s" % (D, tuple(sum.shape), sum.dtype))
+    if outer.dtype != torch.float64 or tuple(outer.shape) != (D, D) or not outer.is_contiguous():
+        raise RuntimeError("feature_moments: outer (%d, %d) float64, contiguous, expected, got %s of %s" % (D, D, tuple(outer.shape), outer.dtype))
+    shift = _feature_shift("feature_moments", shift, D, x)
+    L = _L()
+    ws = _ws(L.vqw_feature_moments_ws_bytes(N, D), x)
+    L.vqw_feature_moments(x, shift, sum, outer, ws, ws.numel(), N, D)
+
+
+def knn_radius(a, k, shift=None):
+    """(N,) fp32: r2[i] = the k-th smallest squared distance from row i of a (N, D) fp32 to the OTHER rows (self is excluded by
+    index, so a duplicate of row i counts, at distance exactly 0).  d2 = max(0, |q|^2 + |a|^2 - 2 q.a) over y = fp32(x - shift) on
+    the exact-fp32 matrix cores; the N x N distances are never written.  1 <= k <= 8, N >= k + 1.  No gradient."""
+    a = _feature_rows("knn_radius", a, "a")
+    N, D = a.shape
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError("knn_radius: k=%d out of [1, %d]" % (k, KNN_MAX_K))
+    if N < k + 1:
+        raise ValueError("knn_radius: N=%d must be at least k + 1 = %d (self is excluded)" % (N, k + 1))
+    shift = _feature_shift("knn_radius", shift, D, a)
+    r2 = torch.empty(N, dtype=torch.float32, device=a.device)
+    L = _L()
+    ws = _ws(L.vqw_knn_radius_ws_bytes(N), a)
+    L.vqw_knn_radius(a, shift, r2, ws, ws.numel(), N, D, k)
+    return r2
+
+
+def ball_counts(q, a, r2, shift=None):
+    """(cnt_q (M,), hit_a (N,)) torch.int32 for queries q (M, D), centres a (N, D) and squared radii r2 (N,), all fp32: cnt_q[m] =
+    the number of balls i with d2(q_m, a_i) <= r2[i] (inclusive), hit_a[i] = the number of queries inside ball i.  knn_radius's
+    distances; a NaN radius contains nobody.  The M x N distances are never written.  No gradient."""
+    q = _feature_rows("ball_counts", q, "q")
+    M, D = q.shape
+    a = _feature_rows("ball_counts", a, "a", D)
+    N = a.shape[0]
+    _dev(r2)
+    if r2.dtype != torch.float32 or tuple(r2.shape) != (N,) or r2.device != a.device or q.device != a.device:
+        raise RuntimeError("ball_counts: r2 (%d,) fp32 on the device of q and a expected, got %s of %s" % (N, tuple(r2.shape), r2.dtype))
+    r2 = r2.detach().contiguous()
+    shift = _feature_shift("ball_counts", shift, D, a)
+    cnt_q = torch.empty(M, dtype=torch.int32, device=a.device)
+    hit_a = torch.empty(N, dtype=torch.int32, device=a.device)
+    L = _L()
+    ws = _ws(L.vqw_ball_counts_ws_bytes(M, N), a)
+    L.vqw_ball_counts(q, a, r2, shift, cnt_q, hit_a, ws, ws.numel(), M, N, D)
+    return cnt_q, hit_a
+
+
 def prior_tokens(ids, sos, pkeep, vocab_size, u_keep=None, u_rand=None):
     """The transformer's input of a training step of the prior, from the code sequences ids (B, T) torch.long: the start token
     `sos` in front of the sequence shifted right by one (teacher forcing; the target stays `ids`), with taming-transformers'

@@ -4,6 +4,7 @@
     python run_vqwnet.py -c CONFIG -p -m edit
     python run_vqwnet.py -c CONFIG -p -m detect
     python run_vqwnet.py -c CONFIG -p -m synth
+    python run_vqwnet.py -c CONFIG -p -m score
 
 run.training_mode picks the work: `first_step` / `second_step` train (-m train) or are scored (-m test: result.csv in the
 run directory); `inference` (-m test only) exports PNG and NIfTI files per slice.  -w selects the multi-window step and
@@ -32,6 +33,10 @@ With model.prior.masked = {n_steps, choice_temperature, mask_seed} -p trains the
 (trainers/masked_prior.py: networks.MaskedGPT learns to fill in masked codes) and -p -m edit fills the region in again in
 edit.n_steps (default: masked.n_steps) parallel passes that see the kept codes on both sides; edit.nll_threshold, -m detect and
 model.prior.cond are refused with it.  Absent or `false`, every mode is what it was.
+-p -m score scores the samples of the prior of run.resume_checkpoint against the first score.n_slices test slices (Fit.score): the
+Frechet distance, precision / recall and density / coverage in the frozen first stage's own feature space and the divergence of the
+code histograms, each beside its floor - the same score between two halves of the real slices - in <run dir>/score/score.csv and
+score.json.  -m score without -p, without run.resume_checkpoint or with score.n_samples < score.k + 1 is refused.
 
 One process per GPU.  With run.num_gpus == 1 this process is the worker.  With more, this process never touches the GPU:
 it starts num_gpus fresh interpreters of this file (`--rank r`, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their
@@ -114,8 +119,13 @@ def check_arguments(config, args):
             raise ValueError("-m synth: synthesis draws slices from label maps with the conditional code prior and needs -p")
         from trainers.config import check_synth_config
         check_synth_config(config)              # NotImplementedError naming the missing part
+    elif args.mode == "score":
+        if not prior:
+            raise ValueError("-m score: scoring compares the code prior's samples with held-out slices and needs -p")
+        from trainers.config import check_score_config
+        check_score_config(config)              # NotImplementedError naming the missing part, ValueError for a value out of range
     elif args.mode not in ("train", "test"):
-        raise ValueError("-m %r: the mode is 'train' or 'test' (or, with -p, 'edit', 'detect' or 'synth')" % (args.mode,))
+        raise ValueError("-m %r: the mode is 'train' or 'test' (or, with -p, 'edit', 'detect', 'synth' or 'score')" % (args.mode,))
     mode = _get(config.run, "training_mode", "first_step")
     if mode not in TRAINING_MODES:
         raise ValueError("run.training_mode %r: one of %s" % (mode, ", ".join(TRAINING_MODES)))
@@ -261,6 +271,8 @@ def worker(config, args, training_mode, rank, world_size, seed):
             fit.detect()
         elif args.mode == "synth":
             fit.synth()
+        elif args.mode == "score":
+            fit.score()
         elif args.mode == "train":
             fit.fit()
         else:

@@ -217,6 +217,22 @@ class ConditionalPriorTrainer(PriorTrainer):
             out["scores_uncond"] = scores_u
         return out
 
+    # ---------------------------------------------------------------- scoring the samples
+    def _score_condition(self, batch):
+        return self.cond_tokens(batch)
+
+    def _score_draws(self, conditions, n_samples, batch_size, temperature, top_k, top_p, generator, guidance_scale=None):
+        """One sample per held-out slice, drawn from that slice's own label map (synthesize with one candidate): the score is then
+        paired with the condition distribution of the held-out split.  n_samples must be the number of held-out slices."""
+        n_real = sum(int(c.shape[0]) for c in conditions)
+        if n_samples != n_real:
+            raise ValueError("ConditionalPriorTrainer.score: one sample is drawn per held-out slice: n_samples=%d must equal the %d "
+                             "slices" % (n_samples, n_real))
+        tokens = torch.cat(conditions)
+        for i in range(0, n_real, batch_size):
+            yield self.synthesize(cond=tokens[i:i + batch_size], n_candidates=1, temperature=temperature, top_k=top_k, top_p=top_p,
+                                  generator=generator, guidance_scale=guidance_scale)["ids"]
+
     # ---------------------------------------------------------------- editing
     @torch.no_grad()
     def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None,

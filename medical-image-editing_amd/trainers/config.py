@@ -366,6 +366,62 @@ def check_detect_config(config):
     detect_labels(config)
 
 
+SCORE_KEYS = ("n_slices", "n_samples", "batch_size", "k", "temperature", "top_k", "top_p", "against", "seed", "guidance_scale")
+SCORE_AGAINST = ("image", "recon")
+
+
+def check_score_config(config):
+    """NotImplementedError unless the config describes a scoring run (run_vqwnet.py -p -m score): check_prior_config's keys,
+    run.resume_checkpoint (the -p checkpoint whose samples are scored) and the ten keys of the `score` section - n_slices (the
+    held-out test slices), n_samples (the draws; with model.prior.cond one per slice: equal to n_slices), batch_size, k (the
+    neighbour of the manifold scores, 1..8), temperature, top_k, top_p, against ('image' or 'recon'), seed, guidance_scale;
+    score.n_steps is added with model.prior.masked.  ValueError for a value out of range: n_samples < k + 1, n_slices < 2 (k + 1) -
+    the floor splits the slices into two halves.  Returns the keywords of PriorTrainer.score.  No device work."""
+    what = "scoring the prior's samples (run_vqwnet.py -p -m score)"
+    check_prior_config(config)
+    if not _get(config.run, "resume_checkpoint"):
+        raise NotImplementedError("%s needs run.resume_checkpoint, the -p checkpoint of the prior; missing: run.resume_checkpoint" % what)
+    section, masked, cond = _get(config, "score"), prior_masked(config), prior_condition(config)
+    keys = SCORE_KEYS + (("n_steps",) if masked is not None else ())
+    missing = [k for k in keys if section is None or not hasattr(section, k)]
+    if missing:
+        raise NotImplementedError("%s needs score.{%s}; missing: %s" % (what, ", ".join(keys), ", ".join("score." + k for k in missing)))
+    for key in ("n_slices", "n_samples", "batch_size", "k"):
+        v = getattr(section, key)
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError("%s: score.%s=%r must be an integer >= 1" % (what, key, v))
+    k = section.k
+    if k > 8:
+        raise ValueError("%s: score.k=%d out of [1, 8]" % (what, k))
+    if section.n_samples < k + 1:
+        raise ValueError("%s: score.n_samples=%d must be at least k + 1 = %d" % (what, section.n_samples, k + 1))
+    if section.n_slices < 2 * (k + 1):
+        raise ValueError("%s: score.n_slices=%d must be at least 2 (k + 1) = %d: the floor compares two halves of the real set"
+                         % (what, section.n_slices, 2 * (k + 1)))
+    if section.against not in SCORE_AGAINST:
+        raise ValueError("%s: score.against is one of %s (got %r)" % (what, ", ".join(repr(a) for a in SCORE_AGAINST), section.against))
+    kw = dict(n_samples=section.n_samples, batch_size=section.batch_size, k=k, temperature=float(section.temperature or 1.0),
+              top_k=section.top_k or None, top_p=section.top_p or None, against=section.against)
+    scale = section.guidance_scale
+    scale = 1.0 if scale is None or scale is False else scale
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not (scale == scale and 0.0 <= scale < float("inf")):
+        raise ValueError("score.guidance_scale=%r must be a finite number >= 0 (1: no guidance)" % (scale,))
+    if float(scale) != 1.0:
+        if cond is None or not prior_cond_drop(config)["null_token"]:
+            raise ValueError("score.guidance_scale=%g needs a prior trained with the null embedding: model.prior.cond.null_token: true" % scale)
+        kw["guidance_scale"] = float(scale)
+    if cond is not None and section.n_samples != section.n_slices:
+        raise ValueError("%s: with model.prior.cond one sample is drawn per held-out slice: score.n_samples=%d must equal "
+                         "score.n_slices=%d" % (what, section.n_samples, section.n_slices))
+    if masked is not None:
+        n_steps = section.n_steps
+        if n_steps is not None and n_steps is not False:
+            if isinstance(n_steps, bool) or not isinstance(n_steps, int) or n_steps < 1:
+                raise ValueError("score.n_steps=%r must be an integer >= 1 (false: model.prior.masked.n_steps)" % (n_steps,))
+            kw["n_steps"] = n_steps
+    return kw
+
+
 def latent_size(config):
     """Side of the VQGAN's latent map: resolution halved once per encoder level but the first."""
     c = config.model.vqgan

@@ -8,6 +8,7 @@ class over the trainers of this package - no PyTorch-Lightning.
     Fit(config, trainer, logger).export()         training_mode 'inference': PNG + NIfTI of image, recon, label per slice
     Fit(config, trainer, logger).edit()           -p -m edit: PriorTrainer.edit over the first test slices -> pictures, codes, scores
     Fit(config, trainer, logger).detect()         -p -m detect: PriorTrainer.detect over the test slices -> anomaly maps, AUROC / AP / Dice
+    Fit(config, trainer, logger).score()          -p -m score: PriorTrainer.score against the test slices -> score.csv, score.json
 
 Nothing here reads a scalar from the device inside a step: the logged losses of a step go to the host in one small
 copy that is looked at two steps later (after that step's StepThrottle event), so the loop adds host work only.
@@ -721,6 +722,53 @@ class Fit:
                                                                int(result["P"]), int(result["N"]), int(result["err_free"]), result["err"]))
         self.print("Detection results are saved: {}".format(out_dir))
         return result
+
+    # ---------------------------------------------------------------- -p -m score
+    def score(self):
+        """`-p -m score`: PriorTrainer.score of the prior of run.resume_checkpoint against the first score.n_slices slices of the
+        test split - Frechet distance, precision / recall, density / coverage in the first stage's own feature space, and the code
+        histograms - each beside its floor, the same score between the two halves of the real set.  Under <run dir>/score/:
+        score.csv - one row per score: score,value,floor; score.json - the same values plus the config keys used.  All draws come
+        from one generator seeded with score.seed: a seed reproduces both files byte for byte."""
+        import json
+        from .config import check_score_config
+        if not self.prior:
+            raise ValueError("scoring needs the prior trainer (-p)")
+        kw = check_score_config(self.config)
+        self._load_weights_for_test()
+        if self.rank != 0:
+            return None
+        e, tr = self.config.score, self.trainer
+        n_slices = int(e.n_slices)
+        n_test = len(self.loader("test").dataset)
+        if n_test < n_slices:
+            raise ValueError("scoring: score.n_slices=%d but the test split has %d slices" % (n_slices, n_test))
+
+        def held_out():
+            done = 0
+            for batch in self.loader("test"):
+                if done >= n_slices:
+                    return
+                image = self._to_device(batch)[:n_slices - done]
+                yield self._step_batch(batch, image, n_slices - done)
+                done += image.shape[0]
+
+        gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
+        res = tr.score(held_out(), generator=gen, **kw)
+        scores, floor = res["scores"], res["floor"]
+        out_dir = os.path.join(self.logger.log_dir, "score")
+        os.makedirs(out_dir, exist_ok=True)
+        fmt = lambda v: "%d" % v if isinstance(v, int) else "%.17g" % v  # noqa: E731
+        with open(os.path.join(out_dir, "score.csv"), "w") as f:
+            f.write("score,value,floor\n")
+            for key in scores:
+                f.write("%s,%s,%s\n" % (key, fmt(scores[key]), fmt(floor[key])))
+        used = dict(kw, n_slices=n_slices, seed=int(e.seed or 0))
+        with open(os.path.join(out_dir, "score.json"), "w") as f:
+            json.dump({"scores": scores, "floor": floor, "config": used}, f, indent=1, sort_keys=True)
+            f.write("\n")
+        self.print("Scores are saved: {}".format(out_dir))
+        return res
 
     # ---------------------------------------------------------------- -m test
     def _load_weights_for_test(self):

@@ -94,6 +94,10 @@ class MaskedPriorTrainer(PriorTrainer):
         return self.gpt.generate_parallel(ids, masked, self.n_steps if n_steps is None else n_steps, temperature=temperature, top_k=top_k,
                                           top_p=top_p, choice_temperature=self.choice_temperature, generator=generator)[0]
 
+    def _score_sample_ids(self, n, temperature, top_k, top_p, generator, n_steps=None):
+        """score()'s draws: this trainer's own sample_ids; n_steps and top_p are passed on."""
+        return self.sample_ids(n, temperature, top_k, generator, top_p=top_p, n_steps=n_steps)
+
     # ---------------------------------------------------------------- what needs a raster-order likelihood
     def token_nll(self, batch):
         self._no_likelihood("token_nll")

@@ -31,6 +31,11 @@ one back into the slice cell by cell (ops.paste_cells).
 Detecting (the launcher's -p -m detect).  detect(batch, nll_threshold) is one edit(nll_threshold=...) - the prior restores the codes
 it finds unlikely - and ops.anomaly_map of what was there against what the prior put there: the smoothed pixel residual, the
 anomaly map of a slice (Fit.detect scores it against lesion labels with ops.score_histogram / ops.detection_scores).
+
+Scoring (the launcher's -p -m score).  features(images) are the frozen first stage's pooled encoder outputs; score(batches,
+n_samples) compares the prior's samples with held-out slices there - Frechet distance, precision / recall, density / coverage and
+the code histograms (functions/sample_scores.py over csrc/sample_scores.hip) - and returns the same scores between the two halves of
+the real set beside them, the floor.
 """
 import math
 
@@ -253,6 +258,94 @@ class PriorTrainer(TrainerBase):
     def sample_images(self, n, temperature=1.0, top_k=None, generator=None):
         """n pictures: sample_ids, then VQGAN.decode_from_ids."""
         return self.vqgan.decode_from_ids(self.sample_ids(n, temperature, top_k, generator), self.h, self.w)
+
+    # ---------------------------------------------------------------- scoring the samples
+    @torch.no_grad()
+    def features(self, images):
+        """The feature rows the sample scores live in: the frozen first stage's encoder output, before quantisation, averaged over
+        the latent grid -> (B, emb_dim) fp32.  Eval mode (the first stage never leaves it), no gradients."""
+        return self._pool(self.vqgan.encoder(images.to(self.device)))
+
+    @staticmethod
+    def _pool(z):
+        return z.mean(dim=(2, 3)).contiguous()
+
+    def _score_condition(self, batch):
+        """What score() keeps of a held-out batch to draw its samples from (the conditional trainer: the conditioning tokens)."""
+        return None
+
+    def _score_draws(self, conditions, n_samples, batch_size, temperature, top_k, top_p, generator, **sample_kw):
+        """The code sequences score() scores, batch by batch: n_samples draws from the start token alone."""
+        done = 0
+        while done < n_samples:
+            n = min(batch_size, n_samples - done)
+            yield self._score_sample_ids(n, temperature, top_k, top_p, generator, **sample_kw)
+            done += n
+
+    def _score_sample_ids(self, n, temperature, top_k, top_p, generator):
+        if top_p is None:
+            return self.sample_ids(n, temperature, top_k, generator)
+        # top-p: the sampler of generate_masked with every position redrawn
+        T = self.h * self.w
+        start = torch.full((n, 1), self.sos_token, dtype=torch.long, device=self.device)
+        was_training = self.gpt.training
+        self.gpt.eval()
+        try:
+            return self.gpt.generate_masked(start, torch.zeros((n, T), dtype=torch.long, device=self.device), np.ones((n, T), dtype=bool),
+                                            temperature=temperature, top_k=top_k, top_p=top_p, generator=generator)[0]
+        finally:
+            self.gpt.train(was_training)
+
+    @torch.no_grad()
+    def score(self, batches, n_samples, batch_size=16, k=3, temperature=1.0, top_k=None, top_p=None, against="image", generator=None,
+              **sample_kw):
+        """Score the prior's samples against held-out slices in the first stage's own feature space (functions/sample_scores.py).
+
+        batches: the held-out slices, batch by batch ({'image'[, 'label']} or the images).  Real features: features(slice) with
+        against='image', features(decode(encode(slice))) with against='recon', which takes the first stage's own reconstruction
+        error out of the comparison.  Fake features: n_samples draws (_score_draws: sample_ids here) -> decode_from_ids ->
+        features.  Every feature is centred on the fp32 mean of the first real batch.  Returns {'scores', 'floor'}: two dicts of
+        sample_scores's keys - the samples against the real set, and the real set's even arrival indices against its odd ones:
+        the same scores between two halves of one distribution at half the n, without which nobody can tell a Frechet distance of 3
+        from sampling noise."""
+        from functions.sample_scores import FeatureStats, sample_scores
+        k, n_samples, batch_size = int(k), int(n_samples), int(batch_size)
+        if against not in ("image", "recon"):
+            raise ValueError("PriorTrainer.score: against=%r must be 'image' or 'recon'" % (against,))
+        if n_samples < k + 1:
+            raise ValueError("PriorTrainer.score: n_samples=%d must be at least k + 1 = %d" % (n_samples, k + 1))
+        if batch_size < 1:
+            raise ValueError("PriorTrainer.score: batch_size=%d must be at least 1" % batch_size)
+        real = halves = None
+        real_ids, conditions, seen = [], [], 0
+        for batch in batches:
+            image = (batch["image"] if isinstance(batch, dict) else batch).to(self.device)
+            z = self.vqgan.encoder(image)                # one encoder pass gives the slice's codes and, against='image', its features
+            ids = self.vqgan.raster_from_vq_ids(self.vqgan.vq(z)[2]).contiguous()
+            f = self._pool(z) if against == "image" else self.features(self.vqgan.decode_from_ids(ids, self.h, self.w))
+            if real is None:
+                shift = f.mean(dim=0)
+                real = FeatureStats(f.shape[1], shift, keep=2 ** 31)
+                halves = [FeatureStats(f.shape[1], shift, keep=2 ** 31) for _ in range(2)]
+            real.add(f)
+            first = seen % 2                             # the parity of this batch's first arrival index
+            halves[first].add(f[0::2])
+            halves[1 - first].add(f[1::2])
+            real_ids.append(ids)
+            conditions.append(self._score_condition(batch))
+            seen += int(f.shape[0])
+        if real is None or min(h.n for h in halves) < k + 1:
+            raise ValueError("PriorTrainer.score: %d held-out slices: each half of the real set needs at least k + 1 = %d" % (seen, k + 1))
+        fake = FeatureStats(real.D, real.shift, keep=2 ** 31)
+        fake_ids = []
+        for ids in self._score_draws(conditions, n_samples, batch_size, temperature, top_k, top_p, generator, **sample_kw):
+            image = self.vqgan.decode_from_ids(ids, self.h, self.w)
+            fake.add(self.features(image))
+            fake_ids.append(ids)
+        real_ids, fake_ids = torch.cat(real_ids), torch.cat(fake_ids)
+        scores = sample_scores(real, fake, k, real_ids, fake_ids, self.dict_size)
+        floor = sample_scores(halves[0], halves[1], k, real_ids[0::2], real_ids[1::2], self.dict_size)
+        return {"scores": scores, "floor": floor}
 
     # ---------------------------------------------------------------- editing
     @torch.no_grad()
