@@ -949,6 +949,19 @@ int vqw_embed_lookup(const long* idx, const float* table, float* out, long rows,
  * rows_per_sample >= 1, 0 <= null_index < L, 0 <= p < 1, otherwise vqw_embed_lookup's constraints. */
 int vqw_embed_lookup_drop(const long* idx, const float* table, float* out, long* eff, long rows, int rows_per_sample, int E, int L,
                           long null_index, float p, long seed, long call, void* stream);
+/* The conditioned embedding of the masked prior (networks.MaskedGPT.forward_conditioned): the label token of latent cell t is ADDED
+ * to the embedding of position t.  Added function only; the ABI stays 9.
+ *   x[b][t][:] = fp32(fp32(tok[idx[b][t]] + pos[t]) + ctab[e]),   e = cidx[b][t], or null_index when sample b is dropped
+ * - two fp32 additions in this order: the bits of vqw_embed_fwd's output plus vqw_embed_lookup_drop's, added in fp32.  idx, cidx
+ * [B][T] (torch.long), tok [V][E], pos [block_size][E], ctab [L][E], x [B][T][E]; eff [B][T] (torch.long, may be null) receives e.
+ * The drop is vqw_embed_lookup_drop's, decided by the same function: the draw of csrc/dropout.h for element b under (seed, call)
+ * and COND_DROP_SITE against round(p 2^32); p = 0 reads neither seed nor call and drops nobody.  An idx outside [0, V) or an e
+ * outside [0, L) (vqw_cell_labels' -1) writes a NaN row.  One streaming pass, a wave per row, 16-byte accesses, no intermediate of
+ * the size of x, no float atomics.  The gradients are vqw_embed_bwd's: gtok and gpos over idx with Te = 0, gctab the gtok walk
+ * over eff.  E a multiple of 4 with 4 <= E <= 4096, T <= block_size, tok, pos, ctab and x 16-byte aligned, 0 <= p < 1, and
+ * 0 <= null_index < L when p > 0. */
+int vqw_embed_cond_fwd(const long* idx, const float* tok, const float* pos, const long* cidx, const float* ctab, float* x, long* eff,
+                       int B, int T, int E, int V, int L, int block_size, long null_index, float p, long seed, long call, void* stream);
 
 /* ---- anomaly detection with the code prior (trainers/prior.py PriorTrainer.detect, trainers/fit.py Fit.detect; the reference has
  * nothing like it).  Added functions only; the ABI stays 9.  fp32 in, no float atomics, the same bits every run; every refusal below

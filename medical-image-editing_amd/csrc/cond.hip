@@ -22,6 +22,11 @@
 // dropped iff the draw of dropout.h for element b of the site COND_DROP_SITE under (seed, call) falls below round(p 2^32) - the mask
 // is never stored, the same bits every run - and every row of a dropped sample reads table[null_index].  eff[r] is the index read:
 // the gradient is vqw_embed_bwd's gtok over eff.
+//
+// Conditioned embedding (vqw_embed_cond_fwd, the input stem of the label-conditioned MaskedGPT).  The label token of cell t is ADDED
+// to the embedding of position t: x[b][t] = (tok[idx[b][t]] + pos[t]) + ctab[e], two fp32 additions in this order, e the effective
+// label of the row - cond_effective() below, the one place where the drop is decided, shared with the lookup above.  One streaming
+// pass, a wave per row, 16-byte accesses, every element of x written once; the looked-up condition is never stored.
 #include "common.h"
 #include "gpt_math.h"
 #include "dropout.h"
@@ -167,6 +172,12 @@ __global__ void __launch_bounds__(256) k_embed_lookup(const long* __restrict__ i
 // The dropout site of the condition drop: GPT.seed_dropout numbers its sites upwards from 0, so a negative site is never one of them.
 #define COND_DROP_SITE (-1)
 
+// The index row r of a conditioned lookup reads: its own, or null_index when its sample r / rows_per_sample is dropped - the same
+// for every row of a sample.
+__device__ __forceinline__ long cond_effective(const long* __restrict__ idx, long r, int rows_per_sample, long null_index, const DropKey& key) {
+    return dk_keep(key, (uint64_t)(r / rows_per_sample)) ? idx[r] : null_index;
+}
+
 // grid ceil(rows / 4): wave w of workgroup g writes row 4 g + w
 __global__ void __launch_bounds__(256) k_embed_lookup_drop(const long* __restrict__ idx, const float* __restrict__ table, float* __restrict__ out,
                                                            long* __restrict__ eff, long rows, int rows_per_sample, int E, int L, long null_index,
@@ -174,14 +185,36 @@ __global__ void __launch_bounds__(256) k_embed_lookup_drop(const long* __restric
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int lane = threadIdx.x & 63, E4 = E >> 2;
-    const bool keep = dk_keep(key, (uint64_t)(r / rows_per_sample));          // the same for every row of a sample
-    const long id = keep ? idx[r] : null_index;
+    const long id = cond_effective(idx, r, rows_per_sample, null_index, key);
     const bool ok = id >= 0 && id < L;
     const float* src = table + (ok ? id : 0) * E;
     const float nan = quiet_nan();
     if (lane == 0) eff[r] = id;
     for (int c4 = lane; c4 < E4; c4 += 64)
         *(float4*)(out + r * E + 4 * c4) = ok ? *(const float4*)(src + 4 * c4) : make_float4(nan, nan, nan, nan);
+}
+
+// grid ceil(B T / 4): wave w of workgroup g writes row 4 g + w.  A key with thr = 0 keeps every sample (p = 0).
+__global__ void __launch_bounds__(256) k_embed_cond_fwd(const long* __restrict__ idx, const float* __restrict__ tok, const float* __restrict__ pos,
+                                                        const long* __restrict__ cidx, const float* __restrict__ ctab, float* __restrict__ x,
+                                                        long* __restrict__ eff, long rows, int T, int E, int V, int L, long null_index, DropKey key) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63, E4 = E >> 2;
+    const int t = (int)(r % T);
+    const long id = idx[r], e = cond_effective(cidx, r, T, null_index, key);
+    const bool ok = id >= 0 && id < V && e >= 0 && e < L;
+    const float* ta = tok + (ok ? id : 0) * E;
+    const float* pp = pos + (long)t * E;
+    const float* cc = ctab + (ok ? e : 0) * E;
+    float* xr = x + r * E;
+    const float nan = quiet_nan();
+    if (eff && lane == 0) eff[r] = e;
+    for (int c4 = lane; c4 < E4; c4 += 64) {
+        const float4 a = *(const float4*)(ta + 4 * c4), p = *(const float4*)(pp + 4 * c4), c = *(const float4*)(cc + 4 * c4);
+        *(float4*)(xr + 4 * c4) = ok ? make_float4((a.x + p.x) + c.x, (a.y + p.y) + c.y, (a.z + p.z) + c.z, (a.w + p.w) + c.w)
+                                     : make_float4(nan, nan, nan, nan);
+    }
 }
 
 static int cell_check(const char* name, int B, int H, int W, int h, int w, int elem_bytes) {
@@ -264,5 +297,28 @@ extern "C" int vqw_embed_lookup_drop(const long* idx, const float* table, float*
     hipLaunchKernelGGL(k_embed_lookup_drop, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, idx, table, out, eff, rows, rows_per_sample, E, L,
                        null_index, dk_make(p, seed, call, COND_DROP_SITE));
     VQW_LAUNCH_CHECK("vqw_embed_lookup_drop");
+    return VQW_OK;
+}
+
+extern "C" int vqw_embed_cond_fwd(const long* idx, const float* tok, const float* pos, const long* cidx, const float* ctab, float* x, long* eff,
+                                  int B, int T, int E, int V, int L, int block_size, long null_index, float p, long seed, long call,
+                                  void* stream) {
+    VQW_CHECK(E % 4 == 0 && E >= 4 && E <= 4096, "vqw_embed_cond_fwd: E=%d must be a multiple of 4 with 4 <= E <= 4096", E);
+    VQW_CHECK(V >= 1, "vqw_embed_cond_fwd: V=%d must be at least 1", V);
+    VQW_CHECK(L >= 1, "vqw_embed_cond_fwd: L=%d must be at least 1", L);
+    VQW_CHECK(B >= 1 && T >= 1, "vqw_embed_cond_fwd: B=%d, T=%d must be at least 1", B, T);
+    VQW_CHECK(block_size >= 1 && T <= block_size, "vqw_embed_cond_fwd: T = %d exceeds block_size=%d", T, block_size);
+    VQW_CHECK((long)B * T <= (1L << 31) - 4, "vqw_embed_cond_fwd: B * T = %ld rows are too many", (long)B * T);
+    VQW_CHECK(p >= 0.f && p < 1.f, "vqw_embed_cond_fwd: p=%g must lie in [0, 1)", (double)p);
+    VQW_CHECK(p == 0.f || (null_index >= 0 && null_index < L), "vqw_embed_cond_fwd: null_index=%ld must be a row of the table, [0, L = %d), when p > 0",
+              null_index, L);
+    VQW_CHECK(idx && tok && pos && cidx && ctab && x, "vqw_embed_cond_fwd: null pointer");
+    VQW_CHECK(al16(tok) && al16(pos) && al16(ctab) && al16(x), "vqw_embed_cond_fwd: tensors must be 16-byte aligned");
+    const long rows = (long)B * T;
+    // p = 0 reads neither seed nor call: the key of (0, 0) with threshold 0 keeps every sample
+    const DropKey key = p > 0.f ? dk_make(p, seed, call, COND_DROP_SITE) : dk_make(0.f, 0, 0, COND_DROP_SITE);
+    hipLaunchKernelGGL(k_embed_cond_fwd, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, idx, tok, pos, cidx, ctab, x, eff, rows, T, E, V,
+                       L, null_index, key);
+    VQW_LAUNCH_CHECK("vqw_embed_cond_fwd");
     return VQW_OK;
 }

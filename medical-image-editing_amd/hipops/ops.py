@@ -2317,6 +2317,64 @@ def embedding_lookup_drop(idx, table, null_index, p, seed, call, return_eff=Fals
     return (out, eff) if return_eff else out
 
 
+class _EmbeddingCond(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, idx, tok, pos, cidx, ctab, null_index, p, seed, call):
+        _dev(idx, tok, pos, cidx, ctab)
+        idx, cidx = _long(idx, "embedding_cond: idx"), _long(cidx, "embedding_cond: cidx")
+        tok, pos, ctab = _flat(tok), _flat(pos), _flat(ctab)
+        if idx.dim() != 2 or tok.dim() != 2 or pos.dim() < 2 or pos.shape[-1] != tok.shape[1] or pos.numel() != pos.shape[-2] * pos.shape[-1]:
+            raise RuntimeError("embedding_cond: idx (B, T), tok (V, E) and pos ([1,] block_size, E) expected, got %s, %s, %s" % (
+                tuple(idx.shape), tuple(tok.shape), tuple(pos.shape)))
+        if tuple(cidx.shape) != tuple(idx.shape) or ctab.dim() != 2 or ctab.shape[1] != tok.shape[1]:
+            raise RuntimeError("embedding_cond: cidx (B, T) = %s and ctab (L, E) = (L, %d) expected, got %s and %s" % (
+                tuple(idx.shape), tok.shape[1], tuple(cidx.shape), tuple(ctab.shape)))
+        (B, T), (V, E), L, block_size = idx.shape, tok.shape, ctab.shape[0], pos.shape[-2]
+        x = torch.empty(B, T, E, dtype=torch.float32, device=tok.device)
+        eff = torch.empty(B, T, dtype=torch.long, device=tok.device)
+        _L().vqw_embed_cond_fwd(idx, tok, pos, cidx, ctab, x, eff, B, T, E, V, L, block_size, null_index, p, seed, call)
+        ctx.save_for_backward(idx, eff)
+        ctx.cfg = (B, T, E, V, L, block_size, tuple(pos.shape))
+        ctx.mark_non_differentiable(eff)
+        return x, eff
+
+    @staticmethod
+    def backward(ctx, gx, _geff):
+        # no kernel of its own: ops.embedding's gradient over idx (no prefix) for tok and pos, embedding_lookup_drop's - the same
+        # walk over the indices actually read - for the condition's table; its position sums are not used
+        idx, eff = ctx.saved_tensors
+        B, T, E, V, L, block_size, pos_shape = ctx.cfg
+        gx = _flat(gx)
+        gtok = gpos = gctab = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gtok = torch.empty(V, E, dtype=torch.float32, device=gx.device)
+            gpos = torch.empty(pos_shape, dtype=torch.float32, device=gx.device)
+            _L().vqw_embed_bwd(idx, gx, gtok, gpos, B, T, 0, E, V, block_size, 0)
+        if ctx.needs_input_grad[4]:
+            gctab = torch.empty(L, E, dtype=torch.float32, device=gx.device)
+            scratch = torch.empty(T, E, dtype=torch.float32, device=gx.device)
+            _L().vqw_embed_bwd(eff, gx, gctab, scratch, B, T, 0, E, L, T, 0)
+        return None, gtok, gpos, None, gctab, None, None, None, None
+
+
+def embedding_cond(idx, tok, pos, cidx, ctab, null_index=None, drop=None, return_eff=False):
+    """x[b, t] = (tok[idx[b, t]] + pos[t]) + ctab[e[b, t]]: ops.embedding with a second table's row ADDED position by position, in
+    one pass - the input stem of the label-conditioned MaskedGPT.  idx, cidx (B, T) torch.long, tok (V, E), pos (block_size, E) or
+    (1, block_size, E), ctab (L, E); returns (B, T, E).  Two fp32 additions in this order: the bits of ops.embedding(idx, tok, pos) +
+    ops.embedding_lookup(cidx, ctab).  drop = (p, seed, call): e is null_index in every row of a dropped sample, decided as
+    ops.embedding_lookup_drop decides it (the same function in csrc/cond.hip); None or p = 0 drops nobody and needs no null_index.
+    return_eff: also e, (B, T) torch.long.  Gradients go to tok, pos and ctab (ops.embedding's deterministic walks, ctab's over e).
+    An idx outside [0, V) or an e outside [0, L) gives a NaN row: that row adds to no row of the table it misses."""
+    p, seed, call = (0.0, 0, 0) if drop is None else drop
+    p = _drop_p(p)
+    seed, call, _ = _drop_key((seed, call, COND_DROP_SITE))
+    if p > 0:
+        if null_index is None or not 0 <= int(null_index) < ctab.shape[0]:
+            raise ValueError("embedding_cond: null_index=%r must be a row of the table (L = %d) when p > 0" % (null_index, ctab.shape[0]))
+    x, eff = _EmbeddingCond.apply(idx, tok, pos, cidx, ctab, 0 if null_index is None else int(null_index), p, seed, call)
+    return (x, eff) if return_eff else x
+
+
 # ----------------------------------------------------------------------------------------------
 # the bidirectional masked code prior (csrc/masked_prior.hip): the select, the corruption of a step, one decoding iteration.
 # No gradient.

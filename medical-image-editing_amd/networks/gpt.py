@@ -43,6 +43,9 @@ table of vocab_size + 1 rows, the last one the mask token, and a head of vocab_s
 It is trained to fill in masked codes (trainers/masked_prior.py) and decoded in a few parallel passes, MaskedGPT.generate_parallel:
 per pass one forward, one ops.sample_filtered launch over all B T rows and one ops.unmask_step launch, which fixes the confident
 codes and masks the others again (MaskGIT).  A bidirectional model has no past: the cached routes raise NotImplementedError.
+MaskedGPT.forward_conditioned adds one label token's embedding to every position (ops.embedding_cond: the latent grid and the
+label-token grid are the same grid, so the sequence stays h w long) and generate_parallel(cond=..., guidance_scale=...) decodes under
+it, with classifier-free guidance as one forward over 2B rows and one ops.sample_guided launch per pass.
 """
 import math
 
@@ -461,9 +464,30 @@ class MaskedGPT(GPT):
     def forward_with_past(self, *args, **kwargs):
         self._no_past("forward_with_past")
 
+    def forward_conditioned(self, idx, cond_tokens, cond_table, null_index=None, drop=None):
+        """forward(idx) with one conditioning token per position ADDED to the embedding: GPT.forward's lines with ops.embedding_cond
+        in place of ops.embedding.  cond_tokens (B, T) torch.long - the label token of every latent cell (LabelCondition.tokens) -
+        cond_table (L, n_embed), the condition's own table.  drop = (p, seed, call) with null_index: whole samples read
+        cond_table[null_index] (classifier-free guidance's training side, ops.embedding_cond).  The embedding dropout applies after
+        the sum, at forward()'s site and under forward()'s call bookkeeping.  The sequence stays T long."""
+        self._check_dropout()
+        t = idx.shape[1]
+        if t > self.block_size:
+            raise RuntimeError("GPT: cannot forward T=%d tokens, the model's block_size=%d is exhausted" % (t, self.block_size))
+        call = self._dropout_call()
+        x = ops.embedding_cond(idx, self.tok_embed.weight, self.pos_embed, cond_tokens, cond_table, null_index, drop)
+        if call is not None and self.drop.p > 0:
+            x = ops.dropout(x, self.drop.p, self._key(call, self.dropout_site))
+        for block in self.blocks:
+            x = block._forward(x, None, call)[0]
+        x = self._head(x)
+        if call is not None:
+            self.set_dropout_call(call + 1)
+        return x
+
     @torch.no_grad()
     def generate_parallel(self, ids, masked, n_steps, temperature=1.0, top_k=None, top_p=None, choice_temperature=4.5, generator=None,
-                          uniforms=None):
+                          uniforms=None, cond=None, guidance_scale=None):
         """Fill in the masked positions of ids (B, T) torch.long in n_steps parallel passes, in eval mode: masked (B, T) torch.uint8 /
         bool on the device (what ids holds there is not read).  Iteration k: one forward of the current ids (the mask token at the
         masked positions), one ops.sample_filtered launch over the (B T, V) rows - forced to the code where it is known, a draw
@@ -474,7 +498,16 @@ class MaskedGPT(GPT):
         Returns (ids (B, T), fixed_logp (B, T) fp32): a fixed position's log-probability (temperature 1, unfiltered) under the pass
         that fixed it, 0 at the positions that were known.  A sample with nothing masked comes back unchanged.  Without `uniforms`
         each iteration draws torch.rand(B T) for the sampler and then torch.rand(B, T) for the confidences from `generator`;
-        uniforms (n_steps, 2, B, T) replaces them: index 0 feeds the sampler, index 1 the confidences."""
+        uniforms (n_steps, 2, B, T) replaces them: index 0 feeds the sampler, index 1 the confidences.
+
+        cond = (tokens (B, T) torch.long, table (L, n_embed), null_index or None): every pass is forward_conditioned under the label
+        tokens in place of forward; nothing else changes.  With guidance_scale other than None or 1 (classifier-free guidance;
+        needs null_index) a pass is ONE forward_conditioned over 2B rows - the rows [0, B) under the label tokens, the rows [B, 2B)
+        under null_index at every position, both halves holding the current ids - ONE ops.sample_guided launch over the (2 B T, V)
+        logits, which draws from z_u + scale (z_c - z_u), and ONE ops.unmask_step on the conditional log-probabilities: the
+        confidence of a draw is its log-probability under the label.  The guided call returns (ids, fixed_logp, fixed_logp_u),
+        fixed_logp_u the null rows' log-probability of a position in the pass that fixed it, 0 where it was known.  uniforms stays
+        (n_steps, 2, B, T).  Without cond: the code path and the bits of the unconditional model; guidance without cond raises."""
         n_steps = int(n_steps)
         if n_steps < 1:
             raise ValueError("MaskedGPT.generate_parallel: n_steps=%r must be at least 1" % (n_steps,))
@@ -494,7 +527,24 @@ class MaskedGPT(GPT):
         if uniforms is not None and tuple(uniforms.shape) != (n_steps, 2, B, T):
             raise ValueError("MaskedGPT.generate_parallel: uniforms of shape %s, (n_steps, 2, B, T) = (%d, 2, %d, %d) expected" % (
                 tuple(uniforms.shape), n_steps, B, T))
+        guided = guidance_scale is not None and float(guidance_scale) != 1.0
+        if guided:
+            guidance_scale = float(guidance_scale)
+            if not (math.isfinite(guidance_scale) and guidance_scale >= 0.0):
+                raise ValueError("MaskedGPT.generate_parallel: guidance_scale=%r must be finite and not negative" % (guidance_scale,))
+            if cond is None or cond[2] is None:
+                raise ValueError("MaskedGPT.generate_parallel: guidance_scale=%r needs cond = (tokens, table, null_index) with a null "
+                                 "index, the condition of the unconditional rows" % (guidance_scale,))
         dev, V = self.head.weight.device, self.config.vocab_size
+        if cond is not None:
+            ctok, ctab, null_index = cond
+            if ctok.dtype != torch.long or tuple(ctok.shape) != (B, T):
+                raise ValueError("MaskedGPT.generate_parallel: cond tokens (B, T) = (%d, %d) torch.long expected, got %s of %s" % (
+                    B, T, tuple(ctok.shape), ctok.dtype))
+            ctok = ctok.to(dev).contiguous()
+            if guided:
+                return self._generate_parallel_guided(ids, masked, n_steps, temperature, top_k, top_p, choice_temperature, generator, uniforms,
+                                                      ctok, ctab, int(null_index), guidance_scale)
         was_training = self.training
         self.eval()
         try:
@@ -506,7 +556,7 @@ class MaskedGPT(GPT):
             fixed_logp = torch.zeros(B, T, dtype=torch.float32, device=dev)
             for k in range(n_steps):
                 gamma, tau = unmask_schedule(k, n_steps, choice_temperature)
-                logits = self(cur)
+                logits = self(cur) if cond is None else self.forward_conditioned(cur, ctok, ctab)
                 if uniforms is not None:
                     u_draw, u_conf = uniforms[k, 0].reshape(-1), uniforms[k, 1]
                 else:
@@ -519,6 +569,41 @@ class MaskedGPT(GPT):
         finally:
             self.train(was_training)
         return cur, fixed_logp
+
+    def _generate_parallel_guided(self, ids, masked, n_steps, temperature, top_k, top_p, choice_temperature, generator, uniforms, ctok, ctab,
+                                  null_index, scale):
+        """generate_parallel's guided route behind its checks: the unguided body with the forward on 2B rows and ops.sample_guided in
+        place of ops.sample_filtered."""
+        B, T = ids.shape
+        dev, V = self.head.weight.device, self.config.vocab_size
+        was_training = self.training
+        self.eval()
+        try:
+            if uniforms is not None:
+                uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
+            masked = masked.to(dev).contiguous().view(torch.uint8)
+            m0 = masked.sum(1, dtype=torch.int32)
+            cur = torch.where(masked != 0, torch.full_like(ids, self.mask_token), ids.to(dev))
+            ctok2 = torch.cat((ctok, torch.full_like(ctok, null_index)), dim=0)          # the label's rows, then the null rows
+            fixed_logp = torch.zeros(B, T, dtype=torch.float32, device=dev)
+            fixed_logp_u = torch.zeros(B, T, dtype=torch.float32, device=dev)
+            for k in range(n_steps):
+                gamma, tau = unmask_schedule(k, n_steps, choice_temperature)
+                logits = self.forward_conditioned(torch.cat((cur, cur), dim=0), ctok2, ctab)          # (2B, T, V)
+                if uniforms is not None:
+                    u_draw, u_conf = uniforms[k, 0].reshape(-1), uniforms[k, 1]
+                else:
+                    u_draw = torch.rand(B * T, generator=generator, device=dev)
+                    u_conf = torch.rand(B, T, generator=generator, device=dev)
+                forced = torch.where(masked != 0, torch.full_like(cur, -1), cur).reshape(-1)
+                tokens, logp, logp_u = ops.sample_guided(logits.reshape(2 * B * T, V), u_draw, scale, forced, temperature, top_k, top_p)
+                before = masked
+                cur, masked, fixed_logp = ops.unmask_step(tokens[:B * T].view(B, T), logp.view(B, T), masked, m0, gamma, tau, self.mask_token,
+                                                          u=u_conf, fixed_logp=fixed_logp)
+                fixed_logp_u = torch.where((before != 0) & (masked == 0), logp_u.view(B, T), fixed_logp_u)      # fixed in this pass
+        finally:
+            self.train(was_training)
+        return cur, fixed_logp, fixed_logp_u
 
 
 def decode_pack_layout(n_layer, n_embed, vocab_size):

@@ -33,6 +33,11 @@ With model.prior.masked = {n_steps, choice_temperature, mask_seed} -p trains the
 (trainers/masked_prior.py: networks.MaskedGPT learns to fill in masked codes) and -p -m edit fills the region in again in
 edit.n_steps (default: masked.n_steps) parallel passes that see the kept codes on both sides; edit.nll_threshold, -m detect and
 model.prior.cond are refused with it.  Absent or `false`, every mode is what it was.
+With model.prior.masked.cond (model.prior.cond's keys) the masked prior is conditioned on the label maps
+(trainers/masked_cond_prior.py: the label token of a latent cell is added to the embedding of its position, the sequence stays h w
+long): -p trains p(codes | label map), -p -m synth decodes slices from label maps alone in synth.n_steps (default: masked.n_steps)
+parallel passes and edits them through synth.discs, -p -m edit and -p -m score run under the slices' own label maps, and the guidance
+keys work as for model.prior.cond; -m detect stays refused.
 -p -m score scores the samples of the prior of run.resume_checkpoint against the first score.n_slices test slices (Fit.score): the
 Frechet distance, precision / recall and density / coverage in the frozen first stage's own feature space and the divergence of the
 code histograms, each beside its floor - the same score between two halves of the real slices - in <run dir>/score/score.csv and

@@ -26,27 +26,18 @@ import numpy as np
 import torch
 
 from hipops import AdamW, ops
-from networks.label_condition import LabelCondition
 
+from .label_cond import LabelConditionMixin
 from .prior import PriorTrainer, parameter_groups
 
 
-class ConditionalPriorTrainer(PriorTrainer):
+class ConditionalPriorTrainer(LabelConditionMixin, PriorTrainer):
+    """The batch -> tokens logic, the guidance checks, the ranking, the drop seed's place in the checkpoint and cell_mask's default
+    are LabelConditionMixin's (trainers/label_cond.py), shared with the conditional masked prior."""
+
     def __init__(self, vqgan, gpt, cond, pkeep=1.0, sos_token=0, lr=4.5e-4, betas=(0.9, 0.95), weight_decay=0.01, grad_norm_clip=1.0,
                  warmup_steps=0, decay_steps=0, seed=0, device="cuda", dropout_seed=None, p_uncond=0.0, cond_drop_seed=None):
-        if not isinstance(cond, LabelCondition):
-            raise TypeError("ConditionalPriorTrainer conditions on a networks.LabelCondition")
-        p_uncond = float(p_uncond)
-        if not 0.0 <= p_uncond < 1.0:
-            raise ValueError("ConditionalPriorTrainer: p_uncond=%r must lie in [0, 1)" % (p_uncond,))
-        if p_uncond > 0 and cond.null_index is None:
-            raise ValueError("ConditionalPriorTrainer: p_uncond=%g needs a condition with the null embedding, LabelCondition(..., "
-                             "null_token=True) (model.prior.cond.null_token)" % p_uncond)
-        if p_uncond > 0 and cond_drop_seed is None:
-            raise ValueError("ConditionalPriorTrainer: p_uncond=%g needs cond_drop_seed (model.prior.cond.drop_seed): the drop of a step "
-                             "is a function of (cond_drop_seed, step)" % p_uncond)
-        self.p_uncond, self.cond_drop_seed = p_uncond, None if cond_drop_seed is None else int(cond_drop_seed)
-        self._cond_grid = (cond.h, cond.w)          # read by _latent_grid inside the parent's constructor
+        self._init_condition(cond, p_uncond, cond_drop_seed)
         super().__init__(vqgan, gpt, pkeep=pkeep, sos_token=sos_token, lr=lr, betas=betas, weight_decay=weight_decay,
                          grad_norm_clip=grad_norm_clip, warmup_steps=warmup_steps, decay_steps=decay_steps, seed=seed, device=device,
                          dropout_seed=dropout_seed)
@@ -64,11 +55,6 @@ class ConditionalPriorTrainer(PriorTrainer):
         groups[1]["params"].append(self.cond.embed.weight)          # an embedding table: undecayed, as the GPT's own
         self.optim = AdamW(groups, lr=lr, betas=tuple(betas), weight_decay=weight_decay, max_grad_norm=grad_norm_clip)
 
-    def _latent_grid(self, vqgan):
-        """The condition's grid: the square one of the VQGAN's own resolution, or that of the pictures a run feeds the (fully
-        convolutional) VQGAN; codes() holds every batch to it."""
-        return self._cond_grid
-
     def modules(self):
         return {"decoder": self.vqgan, "transformer": self.gpt, "cond": self.cond}
 
@@ -79,22 +65,6 @@ class ConditionalPriorTrainer(PriorTrainer):
         return ids
 
     # ---------------------------------------------------------------- the prefix
-    def cond_tokens(self, batch):
-        """The conditioning tokens (B, Tc) torch.long of a batch: its 'cond', else LabelCondition.tokens of its 'label'."""
-        if not isinstance(batch, dict) or (batch.get("cond") is None and batch.get("label") is None):
-            has_ids = isinstance(batch, dict) and batch.get("ids") is not None
-            raise ValueError("ConditionalPriorTrainer: the batch has no '%s'" % ("cond" if has_ids else "label"))
-        if batch.get("cond") is not None:
-            tokens = batch["cond"].to(self.device)
-        else:
-            tokens = self.cond.tokens(self._label(batch["label"]))
-        if tokens.dim() != 2 or tokens.shape[1] != self.Tc or tokens.dtype != torch.long:
-            raise ValueError("ConditionalPriorTrainer: cond (B, Tc) = (B, %d) torch.long expected, got %s of %s" % (self.Tc, tuple(tokens.shape), tokens.dtype))
-        return tokens
-
-    def _label(self, label):
-        return label.to(self.device).contiguous()
-
     def _prefix(self, batch):
         return self.cond(self.cond_tokens(batch))
 
@@ -106,19 +76,6 @@ class ConditionalPriorTrainer(PriorTrainer):
         if self.p_uncond > 0:
             return self.cond(self.cond_tokens(batch), drop=(self.p_uncond, self.cond_drop_seed, self.step_count))
         return self._prefix(batch)
-
-    def state_dict(self):
-        state = super().state_dict()
-        if self.p_uncond > 0:          # off: the checkpoint's extra is what it was
-            state["extra"].update(cond_drop_seed=self.cond_drop_seed)
-        return state
-
-    def load_state_dict(self, state):
-        extra = state.get("extra") or {}
-        if self.p_uncond > 0 and extra.get("cond_drop_seed", self.cond_drop_seed) != self.cond_drop_seed:
-            raise ValueError("ConditionalPriorTrainer: the checkpoint was trained with cond_drop_seed=%r, this trainer has %r: the run "
-                             "would not continue with the same dropped samples" % (extra["cond_drop_seed"], self.cond_drop_seed))
-        super().load_state_dict(state)
 
     @torch.no_grad()
     def validation_step(self, batch):
@@ -135,40 +92,10 @@ class ConditionalPriorTrainer(PriorTrainer):
                 self.gpt.train(was_training)
         return out
 
-    def _guidance(self, what, guidance_scale, rank):
-        """(guided?, scale) of a synthesize / edit call, refused before any kernel."""
-        if rank not in ("cond", "gain"):
-            raise ValueError("ConditionalPriorTrainer.%s: rank=%r must be 'cond' or 'gain'" % (what, rank))
-        guided = guidance_scale is not None and float(guidance_scale) != 1.0
-        if guided:
-            scale = float(guidance_scale)
-            if not (np.isfinite(scale) and scale >= 0.0):
-                raise ValueError("ConditionalPriorTrainer.%s: guidance_scale=%r must be finite and not negative" % (what, guidance_scale))
-            if self.cond.null_index is None:
-                raise ValueError("ConditionalPriorTrainer.%s: guidance_scale=%r needs a prior trained with the null embedding "
-                                 "(model.prior.cond.null_token)" % (what, guidance_scale))
-        elif rank == "gain":
-            raise ValueError("ConditionalPriorTrainer.%s: rank='gain' compares the conditional and the unconditional score and needs "
-                             "guidance (guidance_scale other than 1)" % what)
-        return guided, (float(guidance_scale) if guided else None)
-
-    @staticmethod
-    def _rank(logp, logp_u, B, n, rank):
-        """(scores (B, n), scores_uncond or None, the ranking key): sums in double; rank 'gain': sum(logp - logp_u)."""
-        scores = logp.double().sum(1).reshape(B, n)
-        if logp_u is None:
-            return scores, None, scores
-        scores_u = logp_u.double().sum(1).reshape(B, n)
-        key = (logp.double() - logp_u.double()).sum(1).reshape(B, n) if rank == "gain" else scores
-        return scores, scores_u, key
-
     def _logits(self, inp, prefix):
         return self.gpt.forward_tail(inp, prefix, n_tail=inp.shape[1])
 
     # ---------------------------------------------------------------- sampling
-    def sample_ids(self, n, temperature=1.0, top_k=None, generator=None):
-        raise NotImplementedError("ConditionalPriorTrainer: sampling needs a condition: synthesize(label=...) or synthesize(cond=...)")
-
     @torch.no_grad()
     def synthesize(self, label=None, cond=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None, generator=None, uniforms=None,
                    guidance_scale=None, rank="cond"):
@@ -218,9 +145,6 @@ class ConditionalPriorTrainer(PriorTrainer):
         return out
 
     # ---------------------------------------------------------------- scoring the samples
-    def _score_condition(self, batch):
-        return self.cond_tokens(batch)
-
     def _score_draws(self, conditions, n_samples, batch_size, temperature, top_k, top_p, generator, guidance_scale=None):
         """One sample per held-out slice, drawn from that slice's own label map (synthesize with one candidate): the score is then
         paired with the condition distribution of the held-out split.  n_samples must be the number of held-out slices."""
@@ -261,14 +185,6 @@ class ConditionalPriorTrainer(PriorTrainer):
                          image_size=label_size, guidance=(scale, rank) if guided else None)[0]
         out["cond"], out["label_cells"] = tokens, tokens.reshape(-1, self.h, self.w)
         return out
-
-    def cell_mask(self, B, mask=None, box=None, image_size=None):
-        """The parent's; without image_size: the VQGAN's resolution where the latent grid divides it, else the grid itself (a mask
-        at code resolution, a box in cells)."""
-        if image_size is None:
-            res = int(self.vqgan.encoder.resolution)
-            image_size = (res, res) if res % self.h == 0 and res % self.w == 0 else (self.h, self.w)
-        return super().cell_mask(B, mask, box, image_size)
 
     def detect(self, *args, **kwargs):
         raise NotImplementedError("ConditionalPriorTrainer.detect: a prior conditioned on the labels would be told where the lesion is; "

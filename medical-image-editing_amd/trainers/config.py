@@ -29,6 +29,9 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
     config.model.prior.masked.{n_steps, choice_temperature, mask_seed} (optional: the bidirectional masked prior decoded in n_steps
                  parallel passes, trainers/masked_prior.py; absent or `false`: the autoregressive prior.  pkeep and sos_token are
                  ignored with it, model.prior.cond beside it is refused; edit.n_steps overrides n_steps for -p -m edit)
+    config.model.prior.masked.cond.{source, n_labels, labels} and its optional {null_token, p_uncond, drop_seed} (optional: the
+                 masked prior conditioned on label maps, trainers/masked_cond_prior.py - model.prior.cond's keys, read by
+                 prior_condition / prior_cond_drop in its place; synth.n_steps overrides n_steps for -p -m synth)
     config.edit.{n_slices, n_candidates, temperature, top_k, top_p, seed} and one of edit.{box, mask_path, nll_threshold},
                  config.run.resume_checkpoint    (editing with the prior, -p -m edit: keys of this project; Fit.edit)
     config.detect.{n_slices, n_candidates, temperature, top_k, top_p, seed, nll_threshold, sigma, against, weight, labels},
@@ -140,7 +143,9 @@ def check_prior_config(config):
         if missing:
             raise NotImplementedError("the prior trainer (run_vqwnet.py -p, trainers.build_prior_trainer) needs %s.{%s}; missing: %s"
                                       % (where, ", ".join(keys), ", ".join(missing)))
-    prior_masked(config)          # the optional model.prior.masked: its keys and what it excludes
+    if prior_masked(config) is not None:          # the optional model.prior.masked: its keys and what it excludes
+        prior_condition(config)                   # and its optional condition, model.prior.masked.cond: missing keys are named here
+        prior_cond_drop(config)
 
 
 MASKED_KEYS = ("n_steps", "choice_temperature", "mask_seed")
@@ -149,7 +154,8 @@ MASKED_KEYS = ("n_steps", "choice_temperature", "mask_seed")
 def prior_masked(config):
     """The optional model.prior.masked = {"n_steps", "choice_temperature", "mask_seed"} -> None (absent or `false`: the
     autoregressive prior, exactly as without the key) or {n_steps, choice_temperature, mask_seed}: the bidirectional masked prior
-    (trainers/masked_prior.py).  model.prior.{pkeep, sos_token} are ignored with it; model.prior.cond beside it raises."""
+    (trainers/masked_prior.py).  model.prior.{pkeep, sos_token} are ignored with it; model.prior.cond beside it raises: its
+    condition is the optional model.prior.masked.cond (prior_condition)."""
     masked = _get(_get(config.model, "prior"), "masked")
     if masked is None or masked is False:
         return None
@@ -159,8 +165,8 @@ def prior_masked(config):
         raise NotImplementedError("%s needs model.prior.masked.{%s}; missing: %s" % (what, ", ".join(MASKED_KEYS), ", ".join(missing)))
     cond = _get(config.model.prior, "cond")
     if cond is not None and cond is not False:
-        raise NotImplementedError("%s: model.prior.cond beside model.prior.masked - conditioning the masked prior on label maps is "
-                                  "not built (out of scope)" % what)
+        raise NotImplementedError("%s: model.prior.cond beside model.prior.masked - model.prior.cond is the autoregressive prior's "
+                                  "conditioning prefix; the masked prior is conditioned on label maps by model.prior.masked.cond" % what)
     n_steps, tau, seed = masked.n_steps, masked.choice_temperature, masked.mask_seed
     if isinstance(n_steps, bool) or not isinstance(n_steps, int) or n_steps < 1:
         raise ValueError("%s: model.prior.masked.n_steps=%r must be an integer >= 1" % (what, n_steps))
@@ -246,50 +252,62 @@ def detect_labels(config):
 COND_KEYS = ("source", "n_labels", "labels")
 
 
+def _cond_section(config):
+    """(the condition's section, its key): model.prior.masked.cond when model.prior.masked is set (the masked prior's condition,
+    trainers/masked_cond_prior.py), else model.prior.cond."""
+    prior = _get(config.model, "prior")
+    masked = _get(prior, "masked")
+    if masked is not None and masked is not False:
+        return _get(masked, "cond"), "model.prior.masked.cond"
+    return _get(prior, "cond"), "model.prior.cond"
+
+
 def prior_condition(config):
     """The optional model.prior.cond = {"source": "label", "n_labels": N, "labels": ...} -> None (absent or `false`: the
     unconditional prior) or {n_labels, label_modality, lesions}: the label maps the loaders deliver beside the slices (`labels` in
-    detect.labels' two forms) become one conditioning token per latent cell (trainers/cond_prior.py)."""
-    cond = _get(_get(config.model, "prior"), "cond")
+    detect.labels' two forms) become one conditioning token per latent cell (trainers/cond_prior.py).  With model.prior.masked the
+    section is model.prior.masked.cond, the same keys (trainers/masked_cond_prior.py)."""
+    cond, key = _cond_section(config)
     if cond is None or cond is False:
         return None
-    what = "the conditional prior (run_vqwnet.py -p with model.prior.cond)"
+    what = "the conditional prior (run_vqwnet.py -p with %s)" % key
     missing = [k for k in COND_KEYS if not hasattr(cond, k)]
     if missing:
-        raise NotImplementedError("%s needs model.prior.cond.{%s}; missing: %s" % (what, ", ".join(COND_KEYS), ", ".join(missing)))
+        raise NotImplementedError("%s needs %s.{%s}; missing: %s" % (what, key, ", ".join(COND_KEYS), ", ".join(missing)))
     if cond.source != "label":
-        raise NotImplementedError("%s: model.prior.cond.source is 'label', one token per latent cell from a label map (got %r); other "
-                                  "conditions are not built" % (what, cond.source))
+        raise NotImplementedError("%s: %s.source is 'label', one token per latent cell from a label map (got %r); other "
+                                  "conditions are not built" % (what, key, cond.source))
     if isinstance(cond.n_labels, bool) or not isinstance(cond.n_labels, int) or not 1 <= cond.n_labels <= 256:
-        raise ValueError("%s: model.prior.cond.n_labels=%r must be an integer in [1, 256]" % (what, cond.n_labels))
-    label_modality, lesions = _labels(cond.labels, what, "model.prior.cond.labels")
+        raise ValueError("%s: %s.n_labels=%r must be an integer in [1, 256]" % (what, key, cond.n_labels))
+    label_modality, lesions = _labels(cond.labels, what, key + ".labels")
     if label_modality is None and lesions is None:
-        raise NotImplementedError("%s needs label maps: model.prior.cond.labels is a modality name or {\"synthetic\": {%s}}; missing: "
-                                  "model.prior.cond.labels" % (what, ", ".join(DETECT_LESION_KEYS)))
+        raise NotImplementedError("%s needs label maps: %s.labels is a modality name or {\"synthetic\": {%s}}; missing: "
+                                  "%s.labels" % (what, key, ", ".join(DETECT_LESION_KEYS), key))
     return {"n_labels": int(cond.n_labels), "label_modality": label_modality, "lesions": lesions}
 
 
 def prior_cond_drop(config):
     """The three optional classifier-free guidance keys of model.prior.cond -> {null_token, p_uncond, drop_seed}; absent (or
-    `false`) means off: no null embedding, p_uncond 0, no seed.  p_uncond > 0 needs null_token and drop_seed."""
-    cond = _get(_get(config.model, "prior"), "cond")
-    what = "the conditional prior (run_vqwnet.py -p with model.prior.cond)"
+    `false`) means off: no null embedding, p_uncond 0, no seed.  p_uncond > 0 needs null_token and drop_seed.  With
+    model.prior.masked they are model.prior.masked.cond's."""
+    cond, key = _cond_section(config)
+    what = "the conditional prior (run_vqwnet.py -p with %s)" % key
     if cond is None or cond is False:
         return {"null_token": False, "p_uncond": 0.0, "drop_seed": None}
     null_token = bool(_get(cond, "null_token") or False)
     p_uncond = _get(cond, "p_uncond")
     p_uncond = 0.0 if p_uncond is None or p_uncond is False else p_uncond
     if isinstance(p_uncond, bool) or not isinstance(p_uncond, (int, float)) or not 0.0 <= p_uncond < 1.0:
-        raise ValueError("%s: model.prior.cond.p_uncond=%r must be a number in [0, 1)" % (what, p_uncond))
+        raise ValueError("%s: %s.p_uncond=%r must be a number in [0, 1)" % (what, key, p_uncond))
     drop_seed = _get(cond, "drop_seed")
     drop_seed = None if drop_seed is None or drop_seed is False else drop_seed
     if drop_seed is not None and (isinstance(drop_seed, bool) or not isinstance(drop_seed, int)):
-        raise ValueError("%s: model.prior.cond.drop_seed=%r must be an integer" % (what, drop_seed))
+        raise ValueError("%s: %s.drop_seed=%r must be an integer" % (what, key, drop_seed))
     if p_uncond > 0 and not null_token:
-        raise ValueError("%s: model.prior.cond.p_uncond=%g drops the condition onto the null embedding and needs "
-                         "model.prior.cond.null_token: true" % (what, p_uncond))
+        raise ValueError("%s: %s.p_uncond=%g drops the condition onto the null embedding and needs "
+                         "%s.null_token: true" % (what, key, p_uncond, key))
     if p_uncond > 0 and drop_seed is None:
-        raise ValueError("%s: model.prior.cond.p_uncond=%g needs model.prior.cond.drop_seed, the seed of the dropped samples" % (what, p_uncond))
+        raise ValueError("%s: %s.p_uncond=%g needs %s.drop_seed, the seed of the dropped samples" % (what, key, p_uncond, key))
     return {"null_token": null_token, "p_uncond": float(p_uncond), "drop_seed": drop_seed}
 
 
@@ -310,7 +328,8 @@ def guidance(config, name):
         raise ValueError("%s.rank=%r is one of %s" % (name, rank, ", ".join(repr(r) for r in GUIDANCE_RANKS)))
     if float(scale) != 1.0:
         if prior_condition(config) is None or not prior_cond_drop(config)["null_token"]:
-            raise ValueError("%s.guidance_scale=%g needs a prior trained with the null embedding: model.prior.cond.null_token: true" % (name, scale))
+            raise ValueError("%s.guidance_scale=%g needs a prior trained with the null embedding: %s.null_token: true" % (
+                name, scale, _cond_section(config)[1]))
     elif rank == "gain":
         raise ValueError("%s.rank='gain' compares the conditional and the unconditional score and needs %s.guidance_scale other than 1" % (name, name))
     return float(scale), rank
@@ -326,7 +345,7 @@ def check_synth_config(config):
     check_prior_config(config)
     if prior_condition(config) is None:
         raise NotImplementedError("synthesising from label maps (run_vqwnet.py -p -m synth) needs a conditional prior; missing: "
-                                  "model.prior.cond")
+                                  "%s" % _cond_section(config)[1])
     if not _get(config.run, "resume_checkpoint"):
         raise NotImplementedError("synthesising from label maps (run_vqwnet.py -p -m synth) needs run.resume_checkpoint, the -p checkpoint "
                                   "of the conditional prior; missing: run.resume_checkpoint")
@@ -340,6 +359,20 @@ def check_synth_config(config):
         if not isinstance(discs, (list, tuple)) or any(not isinstance(d, (list, tuple)) or len(d) != 4 for d in discs):
             raise ValueError("synth.discs is false or a list of [cy, cx, radius, value] (got %r)" % (discs,))
     guidance(config, "synth")          # the optional synth.{guidance_scale, rank}
+    synth_n_steps(config)              # the optional synth.n_steps of the masked prior
+
+
+def synth_n_steps(config):
+    """The optional synth.n_steps -> None (absent or `false`: the trainer's model.prior.masked.n_steps) or the number of parallel
+    decoding passes of a synthesis with the conditional masked prior; the autoregressive prior refuses it (edit_n_steps' rule)."""
+    n_steps = _get(_get(config, "synth"), "n_steps")
+    if n_steps is None or n_steps is False:
+        return None
+    if prior_masked(config) is None:
+        raise ValueError("synth.n_steps=%r is the number of decoding passes of the masked prior and needs model.prior.masked" % (n_steps,))
+    if isinstance(n_steps, bool) or not isinstance(n_steps, int) or n_steps < 1:
+        raise ValueError("synth.n_steps=%r must be an integer >= 1" % (n_steps,))
+    return n_steps
 
 
 def check_detect_config(config):
@@ -408,7 +441,8 @@ def check_score_config(config):
         raise ValueError("score.guidance_scale=%r must be a finite number >= 0 (1: no guidance)" % (scale,))
     if float(scale) != 1.0:
         if cond is None or not prior_cond_drop(config)["null_token"]:
-            raise ValueError("score.guidance_scale=%g needs a prior trained with the null embedding: model.prior.cond.null_token: true" % scale)
+            raise ValueError("score.guidance_scale=%g needs a prior trained with the null embedding: %s.null_token: true" % (
+                scale, _cond_section(config)[1]))
         kw["guidance_scale"] = float(scale)
     if cond is not None and section.n_samples != section.n_slices:
         raise ValueError("%s: with model.prior.cond one sample is drawn per held-out slice: score.n_samples=%d must equal "
@@ -453,7 +487,8 @@ def configure_prior(config):
 
 def build_prior_trainer(config, device="cuda", first_stage_ckpt_path=None):
     """config -> PriorTrainer (run_vqwnet.py -p): the GPT of model.prior trained on the codes of the frozen VQGAN of model.vqgan;
-    with model.prior.cond (prior_condition) the ConditionalPriorTrainer and its LabelCondition.
+    with model.prior.cond (prior_condition) the ConditionalPriorTrainer and its LabelCondition; with model.prior.masked the
+    MaskedPriorTrainer, and with model.prior.masked.cond the ConditionalMaskedPriorTrainer.
     first_stage_ckpt_path (argument, else run.first_stage_ckpt_path) loads a -v checkpoint's `decoder.*` keys into the VQGAN, as
     build_vqgan_trainer does.  A JSON `false` for pkeep, sos_token, warmup_steps or decay_steps arrives as None: pkeep then means
     1 (no corruption), the others 0.  run.seed seeds the trainer's generator and the prior's dropout (model.prior.*_pdrop)."""
@@ -469,7 +504,15 @@ def build_prior_trainer(config, device="cuda", first_stage_ckpt_path=None):
     if masked is not None:
         from .masked_prior import MaskedPriorTrainer
         cls, extra = MaskedPriorTrainer, dict(masked)
-    if cond is not None:
+        if cond is not None:          # model.prior.masked.cond: the condition is added to every position, the GPT stays h w long
+            from networks import LabelCondition
+            from .masked_cond_prior import ConditionalMaskedPriorTrainer
+            side, drop = latent_size(config), prior_cond_drop(config)
+            cls = ConditionalMaskedPriorTrainer
+            extra["cond"] = LabelCondition(cond["n_labels"], p.n_embed, side, side, null_token=drop["null_token"])
+            if drop["p_uncond"] > 0:
+                extra.update(p_uncond=drop["p_uncond"], cond_drop_seed=drop["drop_seed"])
+    elif cond is not None:
         from networks import LabelCondition
         from .cond_prior import ConditionalPriorTrainer
         side = latent_size(config)

@@ -34,7 +34,7 @@ from .first_step import FlipViews, LUNG_WINDOW, MEDIASTINAL_WINDOW, LossWeights
 from .evaluation import Evaluator
 from .vqgan_unet_dis import VQGANUNetDisTrainer
 from .prior import PriorTrainer
-from .cond_prior import ConditionalPriorTrainer
+from .label_cond import LabelConditionMixin
 
 LIMIT_VAL_BATCHES = 2              # run_vqwnet.py:127
 SANITY_VAL_BATCHES = 2             # run_vqwnet.py:125
@@ -247,9 +247,9 @@ class Fit:
         self.prior = isinstance(trainer, PriorTrainer)
         if self.prior:
             self.mode = "prior"
-        # the conditional prior (model.prior.cond): every loader delivers the label maps beside the slices
+        # the conditional priors (model.prior.cond, model.prior.masked.cond): every loader delivers the label maps beside the slices
         self.cond = None
-        if isinstance(trainer, ConditionalPriorTrainer):
+        if isinstance(trainer, LabelConditionMixin):
             from .config import prior_condition
             self.cond = prior_condition(config)
         self.dict_size = trainer.dict_size if self.vqgan or self.prior else config.model.vqmodel.dict_size
@@ -608,7 +608,7 @@ class Fit:
         candidates, its score, the cells the edit redrew (0 without discs).  All draws come from one generator seeded with
         synth.seed: a seed reproduces every file byte for byte."""
         if self.cond is None:
-            raise ValueError("synthesising needs the conditional prior trainer (-p with model.prior.cond)")
+            raise ValueError("synthesising needs the conditional prior trainer (-p with model.prior.cond or model.prior.masked.cond)")
         self._load_weights_for_test()
         if self.rank != 0:
             return []
@@ -616,10 +616,13 @@ class Fit:
         n_slices = int(e.n_slices)
         discs = e.discs if e.discs else []
         kw = dict(n_candidates=int(e.n_candidates), temperature=float(e.temperature or 1.0), top_k=e.top_k or None, top_p=e.top_p or None)
-        from .config import guidance
+        from .config import guidance, synth_n_steps
         scale, rank = guidance(self.config, "synth")
         if scale != 1.0:          # classifier-free guidance, for the synthesis and for the edit through the label map
             kw.update(guidance_scale=scale, rank=rank)
+        n_steps = synth_n_steps(self.config)
+        if n_steps is not None:   # the conditional masked prior's keyword: the number of parallel decoding passes
+            kw.update(n_steps=n_steps)
         gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
         out_dir = os.path.join(self.logger.log_dir, "synth")
         os.makedirs(out_dir, exist_ok=True)

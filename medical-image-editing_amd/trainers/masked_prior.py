@@ -17,7 +17,8 @@ MaskedGPT.generate_parallel, n_steps forwards of all B n rows whatever the size 
 contract and dict; a candidate's score is the sum of fixed_logp over the redrawn positions - each code's log-probability under the
 pass that fixed it, given both sides of the region.  It is a ranking among candidates of one region, not a likelihood: a
 raster-order likelihood is not defined for this model, so token_nll, the nll_threshold selector, detect and guidance raise
-NotImplementedError.
+NotImplementedError.  Conditioning on label maps, with guidance, is trainers/masked_cond_prior.py, through the hooks _forward_of /
+_train_forward and _edit_parallel.
 """
 import numpy as np
 import torch
@@ -49,12 +50,21 @@ class MaskedPriorTrainer(PriorTrainer):
                                   "(every code is predicted from both sides); use the autoregressive PriorTrainer" % what)
 
     # ---------------------------------------------------------------- the step
-    def _masked_loss(self, ids, call, ratio=None):
+    def _masked_loss(self, ids, call, ratio=None, forward=None):
         """-> the mean cross-entropy over the masked positions under ops.mask_tokens(ids, V, mask_seed, call, ratio).  The masked
-        count is at least B: the division is never by zero."""
+        count is at least B: the division is never by zero.  forward: inp -> logits (None: the model itself)."""
         inp, masked, n = ops.mask_tokens(ids, self.mask_token, self.mask_seed, call, ratio)
-        nll = ops.cross_entropy(self.gpt(inp), ids, reduction="none")
+        nll = ops.cross_entropy((self.gpt if forward is None else forward)(inp), ids, reduction="none")
         return (nll * masked.to(nll.dtype)).sum() / n.sum().to(nll.dtype)
+
+    # the two hooks of a conditional masked prior (trainers/masked_cond_prior.py); here: the model itself
+    def _forward_of(self, batch):
+        """inp -> logits for this batch, or None for gpt(inp)."""
+        return None
+
+    def _train_forward(self, batch):
+        """The same for training step step_count (the conditional trainer may drop the condition of some samples)."""
+        return self._forward_of(batch)
 
     def training_step(self, batch, mark=None):
         self.throttle.begin()
@@ -62,7 +72,7 @@ class MaskedPriorTrainer(PriorTrainer):
         self.gpt.train()
         if self.dropout_seed is not None:
             self.gpt.set_dropout_call(self.step_count)
-        loss = self._masked_loss(ids, self.step_count)          # the mask of a step: a function of (mask_seed, step) alone
+        loss = self._masked_loss(ids, self.step_count, forward=self._train_forward(batch))      # the mask: a function of (mask_seed, step) alone
         lr = self.current_lr()
         for group in self.optim.param_groups:
             group["lr"] = lr
@@ -79,7 +89,7 @@ class MaskedPriorTrainer(PriorTrainer):
         was_training = self.gpt.training
         self.gpt.eval()
         try:
-            loss = self._masked_loss(ids, 0, self.VAL_RATIO)
+            loss = self._masked_loss(ids, 0, self.VAL_RATIO, forward=self._forward_of(batch))
         finally:
             self.gpt.train(was_training)
         return {"loss": loss, "ppl": torch.exp(loss), "ids": ids}
@@ -121,9 +131,18 @@ class MaskedPriorTrainer(PriorTrainer):
         if nll_threshold is not None:
             self._no_likelihood("edit(nll_threshold=...)")
         if guidance_scale is not None and float(guidance_scale) != 1.0:
-            raise NotImplementedError("MaskedPriorTrainer.edit: guidance needs a conditional prior; conditioning the masked prior is not built")
+            raise NotImplementedError("MaskedPriorTrainer.edit: guidance needs a conditional prior: ConditionalMaskedPriorTrainer "
+                                      "(model.prior.masked.cond)")
         if (mask is not None) + (box is not None) != 1:
             raise ValueError("MaskedPriorTrainer.edit: exactly one of mask and box selects the region")
+        return self._edit_parallel(batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator)
+
+    def _edit_parallel(self, batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator, cells=None, image_size=None,
+                       cond=None, guidance=None):
+        """edit()'s work behind its selector checks.  cells: a host bool array (B, h, w) in place of mask and box; image_size: the
+        (H, W) a mask or box of a batch without a picture refers to.  cond: the conditional trainer's (tokens (B, T), table,
+        null_index) - generate_parallel's, repeated per candidate here; guidance: None or (scale, rank) - the dict gains
+        scores_uncond and rank 'gain' ranks by sum(fixed_logp - fixed_logp_u)."""
         n = int(n_candidates)
         if n < 1:
             raise ValueError("MaskedPriorTrainer.edit: n_candidates=%r must be at least 1" % (n_candidates,))
@@ -134,14 +153,25 @@ class MaskedPriorTrainer(PriorTrainer):
         B, T = ids.shape
         if T != self.h * self.w:
             raise ValueError("MaskedPriorTrainer.edit: sequences of h w = %d codes expected, got %d" % (self.h * self.w, T))
-        cells = self.cell_mask(B, mask, box, tuple(image.shape[-2:]) if has_image else None)
+        if cells is None:
+            cells = self.cell_mask(B, mask, box, tuple(image.shape[-2:]) if has_image else image_size)
         masked = torch.from_numpy(np.repeat(cells.reshape(B, T), n, axis=0).astype(np.uint8)).to(self.device)
         known = ids.repeat_interleave(n, dim=0)
         # one torch.rand call per candidate, candidate 0 first: its uniforms - and so its codes - do not depend on n_candidates
         uniforms = torch.stack([torch.rand(n_steps, 2, B, T, generator=generator, device=self.device) for _ in range(n)], dim=3)
         uniforms = uniforms.reshape(n_steps, 2, B * n, T)          # row b n + c: candidate c of slice b, as in `known`
-        tokens, fixed_logp = self.gpt.generate_parallel(
+        kw = {}
+        if cond is not None:
+            kw["cond"] = (cond[0].repeat_interleave(n, dim=0), cond[1], cond[2])
+        if guidance is not None:
+            kw["guidance_scale"] = guidance[0]
+        tokens, fixed_logp, *rest = self.gpt.generate_parallel(
             known, masked, n_steps, temperature=temperature, top_k=top_k, top_p=top_p,
-            choice_temperature=self.choice_temperature, uniforms=uniforms)
+            choice_temperature=self.choice_temperature, uniforms=uniforms, **kw)
         scores = fixed_logp.double().sum(1).reshape(B, n)
-        return self._edit_result(ids, tokens, scores, scores, cells, image)
+        if guidance is None:
+            return self._edit_result(ids, tokens, scores, scores, cells, image)
+        key = (fixed_logp.double() - rest[0].double()).sum(1).reshape(B, n) if guidance[1] == "gain" else scores
+        out = self._edit_result(ids, tokens, scores, key, cells, image)
+        out["scores_uncond"] = rest[0].double().sum(1).reshape(B, n)
+        return out
