@@ -1036,6 +1036,24 @@ int vqw_unmask_step(const long* tokens, const float* logp, const uint8_t* masked
                     uint8_t* masked_out, float* fixed_logp, float* conf, int B, int T, double gamma, float tau, long mask_token,
                     void* stream);
 
+/* ---- the pseudo-likelihood map of the masked code prior (csrc/pseudo_nll.hip; networks.MaskedGPT.pseudo_nll,
+ * trainers.MaskedPriorTrainer.pseudo_nll / detect_pseudo).  Added functions only; the ABI stays 9.  Forward only, no gradient, no
+ * atomics: the same bits every run.  Every refusal arrives with a message that names the constraint, before any launch.
+ * The lattice: a latent grid h x w (T = h w <= 65536, raster order) and a stride 1 <= sy <= h, 1 <= sx <= w; position t = y w + x
+ * belongs to group g(t) = (y mod sy) sx + (x mod sx) of S = sy sx groups, which partition the grid.  Pass s masks group s; the
+ * passes of a sample run side by side as batch rows, in chunks [s0, s0 + ns) with 0 <= s0, ns >= 1, s0 + ns <= S: chunk row
+ * r = b ns + (s - s0).  B ns T <= 2^31 - 4.
+ * vqw_lattice_inputs: ids [B][T], inp [B ns][T] (torch.long, 8-byte aligned, distinct).  inp[b ns + (s - s0)][t] = mask_token where
+ * g(t) = s, ids[b][t] elsewhere.  One streaming pass with 8-byte accesses, no mask tensor from the host.  mask_token >= 0.
+ * vqw_lattice_gather_ln: x [B ns][T][E], the trunk's output in front of ln_f; y [B][T][E].  For every (b, t) with s0 <= g(t) <
+ * s0 + ns: y[b][t][:] = LayerNorm(x[b ns + g(t) - s0][t][:]) under gamma, beta [E] and eps; every other row of y is left untouched,
+ * so successive chunks fill one y.  One wave per output row, the group computed once per row; the row's body is
+ * vqw_layernorm_fwd's (csrc/ln_row.h), so y has the bits of vqw_layernorm_fwd on the gathered row.  No statistics are written.  E a
+ * multiple of 4 with 4 <= E <= 4096; x, gamma, beta and y 16-byte aligned; y must not be x. */
+int vqw_lattice_inputs(const long* ids, long* inp, int B, int h, int w, int sy, int sx, int s0, int ns, long mask_token, void* stream);
+int vqw_lattice_gather_ln(const float* x, const float* gamma, const float* beta, float* y, int B, int h, int w, int E, int sy, int sx,
+                          int s0, int ns, float eps, void* stream);
+
 /* ---- scores of the prior's samples (csrc/sample_scores.hip; functions/sample_scores.py, PriorTrainer.score, Fit.score; the
  * reference has nothing like it).  Added functions only; the ABI stays 9.  Feature rows x [N][D], fp32, dense, 1 <= D <= 2048, any
  * N >= 1 up to 2^30; a row is used as y = fp32(x - shift), one fp32 subtraction per element while staging, shift [D] or null (0):

@@ -2,8 +2,8 @@
 // blocks' causal multi-head attention is in attention.hip.
 //
 // LayerNorm.  One wave owns a row of [rows][C]: lane l holds the float4 columns l, l + 64, ... in registers, the row is read
-// once.  mean = sum / C plus the mean of the residuals, then the variance from the centred values (never E[x^2] - mean^2,
-// mfma_util.h:65-67); every sum is one fixed butterfly.  The steps are gpt_math.h's, shared with the decode step's fused
+// once (ln_row.h: the row's body, shared with pseudo_nll.hip's gathering LayerNorm).  mean = sum / C plus the mean of the
+// residuals, then the variance from the centred values (never E[x^2] - mean^2, mfma_util.h:65-67); every sum is one fixed butterfly.  The steps are gpt_math.h's, shared with the decode step's fused
 // LayerNorm.  Backward: a workgroup owns LN_WG_ROWS consecutive rows, wave w the rows
 // w, w + 4, ... of them; dgamma / dbeta are summed per lane over the wave's rows, the four waves are folded in wave order in LDS,
 // the workgroup's partial goes to the workspace and a second kernel folds the partials in index order (in double).  No atomics.
@@ -11,6 +11,7 @@
 // GELU.  0.5 x (1 + erf(x / sqrt 2)) and its gradient Phi(x) + x phi(x) with the device erff / expf in fp32.
 #include "common.h"
 #include "gpt_math.h"
+#include "ln_row.h"
 #include "mfma_util.h"
 #include "../../include/vqwnet_hip.h"
 
@@ -25,10 +26,6 @@ extern "C" size_t vqw_layernorm_ws_bytes(long rows, int C) {
     return (size_t)ceil_div(rows, LN_WG_ROWS) * 2 * C * sizeof(float);
 }
 
-__device__ __forceinline__ float4 ln_ld(const float* p, int c4, int C4) {
-    return c4 < C4 ? *(const float4*)(p + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
 // grid ceil(rows / 4): wave w of workgroup g normalises row 4 g + w
 template <int NV>
 __global__ void __launch_bounds__(256) k_ln_fwd(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -36,31 +33,9 @@ __global__ void __launch_bounds__(256) k_ln_fwd(const float* __restrict__ x, con
                                                 float eps) {
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
-    const int lane = threadIdx.x & 63, C4 = C >> 2;
-    const float* xr = x + r * C;
-    float4 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) { v[i] = ln_ld(xr, lane + 64 * i, C4); s += sum4(v[i]); }
-    const float mu0 = wave_sum_f(s) / (float)C;
-    float s0 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (lane + 64 * i < C4) { ln_centre(v[i], mu0); s0 += sum4(v[i]); }
-    }
-    const float delta = wave_sum_f(s0) / (float)C, mu = mu0 + delta;
-    float m2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (lane + 64 * i < C4) { ln_centre(v[i], delta); m2 = ln_m2(v[i], m2); }
-    }
-    const float rs = 1.f / sqrtf(wave_sum_f(m2) / (float)C + eps);
-    float* yr = y + r * C;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c4 = lane + 64 * i;
-        if (c4 < C4) *(float4*)(yr + 4 * c4) = ln_affine(v[i], rs, *(const float4*)(gamma + 4 * c4), *(const float4*)(beta + 4 * c4));
-    }
+    const int lane = threadIdx.x & 63;
+    float mu, rs;
+    ln_row_fwd<NV>(x + r * C, gamma, beta, y + r * C, lane, C, eps, mu, rs);
     if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
 }
 

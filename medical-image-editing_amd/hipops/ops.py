@@ -2475,6 +2475,56 @@ def unmask_step(tokens, logp, masked, m0, gamma, tau, mask_token, u=None, fixed_
 
 
 # ----------------------------------------------------------------------------------------------
+# the pseudo-likelihood map of the masked code prior (csrc/pseudo_nll.hip; MaskedGPT.pseudo_nll): the lattice's inputs and the
+# gathering LayerNorm.  No gradient.
+# ----------------------------------------------------------------------------------------------
+def _lattice(name, grid, stride, s0, ns):
+    """(h, w, sy, sx, s0, ns) as integers; the kernels refuse what is out of range, with a message that names it."""
+    try:
+        (h, w), (sy, sx) = (int(v) for v in grid), (int(v) for v in stride)
+    except (TypeError, ValueError):
+        raise ValueError("%s: grid=%r and stride=%r must be pairs of integers" % (name, grid, stride)) from None
+    return h, w, sy, sx, int(s0), int(ns)
+
+
+def lattice_inputs(ids, grid, stride, s0, ns, mask_token):
+    """The inputs of the passes [s0, s0 + ns) of a pseudo-likelihood map: ids (B, T) torch.long, T = h w of grid = (h, w) ->
+    (B ns, T) torch.long, row b ns + (s - s0) = ids[b] with mask_token at every position of group s - position t = y w + x
+    belongs to group (y mod sy) sx + (x mod sx) of the S = sy sx groups of stride = (sy, sx).  One streaming launch; no mask
+    tensor, no host read.  1 <= sy <= h, 1 <= sx <= w, 0 <= s0, ns >= 1, s0 + ns <= S, mask_token >= 0."""
+    h, w, sy, sx, s0, ns = _lattice("lattice_inputs", grid, stride, s0, ns)
+    ids = _rows("lattice_inputs", ids, torch.long, None, "ids")
+    B, T = ids.shape
+    if T != h * w:
+        raise RuntimeError("lattice_inputs: ids of T = h w = %d codes expected for the grid %d x %d, got %d" % (h * w, h, w, T))
+    inp = torch.empty((B * max(ns, 0), T), dtype=torch.long, device=ids.device)
+    _L().vqw_lattice_inputs(ids, inp, B, h, w, sy, sx, s0, ns, int(mask_token))
+    return inp
+
+
+def lattice_gather_ln(x, weight, bias, y, grid, stride, s0, ns, eps=1e-5):
+    """The rows of a chunk of passes that a pseudo-likelihood map reads, normalised: x (B ns, T, E) fp32, the trunk's output of
+    lattice_inputs' rows in front of ln_f; y (B, T, E) fp32, contiguous, updated IN PLACE and returned: for every (b, t) whose
+    group g lies in [s0, s0 + ns), y[b, t] = layer_norm(x[b ns + g - s0, t]) - ops.layer_norm's bits on that row - and every other
+    row of y is left untouched, so successive chunks fill one y.  Forward only."""
+    _no_grad("lattice_gather_ln", x, weight, bias, y)
+    h, w, sy, sx, s0, ns = _lattice("lattice_gather_ln", grid, stride, s0, ns)
+    _dev(x, weight, bias, y)
+    x, weight, bias = _flat(x), _flat(weight), _flat(bias)
+    T = h * w
+    if y.dim() != 3 or y.dtype != torch.float32 or not y.is_contiguous() or y.shape[1] != T:
+        raise RuntimeError("lattice_gather_ln: y (B, T = %d, E) fp32, contiguous, expected (it is updated in place), got %s of %s" % (
+            T, tuple(y.shape), y.dtype))
+    B, _, E = y.shape
+    if x.dtype != torch.float32 or tuple(x.shape) != (B * ns, T, E):
+        raise RuntimeError("lattice_gather_ln: x (B ns, T, E) = %s fp32 expected, got %s of %s" % ((B * ns, T, E), tuple(x.shape), x.dtype))
+    if weight.numel() != E or bias.numel() != E:
+        raise RuntimeError("lattice_gather_ln: weight / bias of %d / %d elements for a trailing dimension of %d" % (weight.numel(), bias.numel(), E))
+    _L().vqw_lattice_gather_ln(x, weight, bias, y, B, h, w, E, sy, sx, s0, ns, float(eps))
+    return y
+
+
+# ----------------------------------------------------------------------------------------------
 # cached generation (networks/gpt.py GPT.decode_step / generate): the decode kernels.  Forward only.
 # ----------------------------------------------------------------------------------------------
 def _no_grad(name, *ts):

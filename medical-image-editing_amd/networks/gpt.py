@@ -46,6 +46,9 @@ codes and masks the others again (MaskGIT).  A bidirectional model has no past: 
 MaskedGPT.forward_conditioned adds one label token's embedding to every position (ops.embedding_cond: the latent grid and the
 label-token grid are the same grid, so the sequence stays h w long) and generate_parallel(cond=..., guidance_scale=...) decodes under
 it, with classifier-free guidance as one forward over 2B rows and one ops.sample_guided launch per pass.
+MaskedGPT.pseudo_nll is the model's opinion of a sequence code by code, -log p(code | the codes outside its lattice group): the
+passes of a sample side by side as batch rows (ops.lattice_inputs), ln_f on the rows the map reads only (ops.lattice_gather_ln), the
+head and the cross-entropy over B T rows whatever the number of passes (csrc/pseudo_nll.hip).
 """
 import math
 
@@ -484,6 +487,73 @@ class MaskedGPT(GPT):
         if call is not None:
             self.set_dropout_call(call + 1)
         return x
+
+    @torch.no_grad()
+    def pseudo_nll(self, ids, grid, stride=(2, 2), max_rows=64, cond=None):
+        """What the model thinks of a slice code by code, as a map (B, h, w) fp32: ids (B, T) torch.long with T = h w of grid =
+        (h, w).  The lattice of stride = (sy, sx), 1 <= sy <= h, 1 <= sx <= w, splits the grid into S = sy sx groups - position
+        t = y w + x belongs to group g(t) = (y mod sy) sx + (x mod sx) - and pass s sees the slice with the mask token at every
+        position of group s:
+            map[b, t] = -log p(ids[b, t] | ids[b, u] for g(u) != g(t); the mask token where g(u) = g(t)),
+        read off pass g(t).  stride (h, w): T passes of one masked position each, the exact pseudo-likelihood -log p(code | all
+        the others); (2, 2), the default: four passes, every masked code sees its eight neighbours; (1, 1): one all-masked pass,
+        the per-position marginal.  It is NOT a likelihood: the terms do not multiply to a probability of the slice, and their sum
+        ranks nothing but positions of one slice under one stride (the training objective of the model, evaluated where it is
+        asked).
+
+        Eval mode, no gradients, no host read, no random numbers; the training flag is restored.  The passes of a sample run side
+        by side as batch rows, ns = max(1, max_rows // B) passes per chunk: ops.lattice_inputs, the trunk in front of ln_f, and
+        ops.lattice_gather_ln, which normalises into ONE y (B, T, E) only the rows the map reads.  After the last chunk ln_f is
+        done, and the head and the cross-entropy run once over B T rows - the logits are (B, T, V) whatever S is.  cond = (tokens
+        (B, T) torch.long, table, null_index): generate_parallel's triple; the stem is ops.embedding_cond under the tokens repeated
+        per pass (null_index is not read: nothing is dropped).  Anything else raises ValueError naming the value."""
+        try:
+            h, w = (int(v) for v in grid)
+        except (TypeError, ValueError):
+            raise ValueError("MaskedGPT.pseudo_nll: grid=%r must be a pair (h, w)" % (grid,)) from None
+        if not torch.is_tensor(ids) or ids.dim() != 2 or ids.dtype != torch.long or h < 1 or w < 1 or ids.shape[1] != h * w \
+                or ids.shape[0] < 1 or h * w > self.block_size:
+            raise ValueError("MaskedGPT.pseudo_nll: ids (B, T) torch.long with T = h w = %d x %d <= block_size=%d expected, got %s of %s" % (
+                h, w, self.block_size, tuple(ids.shape) if torch.is_tensor(ids) else type(ids).__name__, getattr(ids, "dtype", None)))
+        try:
+            sy, sx = (int(v) for v in stride)
+            ok = all(float(v) == int(v) for v in stride)
+        except (TypeError, ValueError):
+            sy = sx = 0
+            ok = False
+        if not (ok and 1 <= sy <= h and 1 <= sx <= w):
+            raise ValueError("MaskedGPT.pseudo_nll: stride=%r must be a pair (sy, sx) of integers in [1, h = %d] x [1, w = %d]" % (stride, h, w))
+        if isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 1:
+            raise ValueError("MaskedGPT.pseudo_nll: max_rows=%r must be an integer >= 1" % (max_rows,))
+        B, T = ids.shape
+        dev, E = self.head.weight.device, self.config.n_embed
+        ctok = ctab = None
+        if cond is not None:
+            ctok, ctab, _ = cond
+            if not torch.is_tensor(ctok) or ctok.dtype != torch.long or tuple(ctok.shape) != (B, T):
+                raise ValueError("MaskedGPT.pseudo_nll: cond tokens (B, T) = (%d, %d) torch.long expected, got %s of %s" % (
+                    B, T, tuple(ctok.shape) if torch.is_tensor(ctok) else type(ctok).__name__, getattr(ctok, "dtype", None)))
+            ctok = ctok.to(dev).contiguous()
+        S, per = sy * sx, max(1, int(max_rows) // B)
+        ids = ids.to(dev).contiguous()
+        was_training = self.training
+        self.eval()
+        try:
+            y = torch.empty(B, T, E, dtype=torch.float32, device=dev)          # every row belongs to exactly one pass: all are written
+            for s0 in range(0, S, per):
+                ns = min(per, S - s0)
+                inp = ops.lattice_inputs(ids, (h, w), (sy, sx), s0, ns, self.mask_token)
+                if cond is None:
+                    x = self._trunk(inp, None)[0]
+                else:
+                    x = ops.embedding_cond(inp, self.tok_embed.weight, self.pos_embed, ctok.repeat_interleave(ns, dim=0), ctab)
+                    for block in self.blocks:
+                        x = block._forward(x, None, None)[0]
+                ops.lattice_gather_ln(x, self.ln_f.weight, self.ln_f.bias, y, (h, w), (sy, sx), s0, ns, self.ln_f.eps)
+            nll = ops.cross_entropy(ops.linear(y, self.head.weight), ids, reduction="none")
+        finally:
+            self.train(was_training)
+        return nll.reshape(B, h, w)
 
     @torch.no_grad()
     def generate_parallel(self, ids, masked, n_steps, temperature=1.0, top_k=None, top_p=None, choice_temperature=4.5, generator=None,

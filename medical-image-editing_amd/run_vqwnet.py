@@ -31,13 +31,18 @@ p_uncond, drop_seed} train the prior with the condition dropped onto a null embe
 synth.{guidance_scale, rank} (edit.{guidance_scale, rank}) draw from z_u + scale (z_c - z_u); absent keys mean off.
 With model.prior.masked = {n_steps, choice_temperature, mask_seed} -p trains the bidirectional masked prior instead
 (trainers/masked_prior.py: networks.MaskedGPT learns to fill in masked codes) and -p -m edit fills the region in again in
-edit.n_steps (default: masked.n_steps) parallel passes that see the kept codes on both sides; edit.nll_threshold, -m detect and
-model.prior.cond are refused with it.  Absent or `false`, every mode is what it was.
+edit.n_steps (default: masked.n_steps) parallel passes that see the kept codes on both sides; edit.nll_threshold and
+model.prior.cond are refused with it, and so is -m detect without detect.pseudo.  Absent or `false`, every mode is what it was.
+The masked prior's own opinion of a slice is its pseudo-likelihood map (MaskedPriorTrainer.pseudo_nll: -log p(code | the codes
+outside its lattice group), from both sides): edit.pnll_threshold, with the optional edit.stride = [sy, sx], is one more selector
+of -p -m edit - the codes whose map exceeds it - and detect.pseudo = {threshold, stride} with detect.nll_threshold false runs
+-p -m detect on the masked prior (MaskedPriorTrainer.detect_pseudo); detect.csv's mean_nll column then holds the mean pseudo-NLL.
 With model.prior.masked.cond (model.prior.cond's keys) the masked prior is conditioned on the label maps
 (trainers/masked_cond_prior.py: the label token of a latent cell is added to the embedding of its position, the sequence stays h w
 long): -p trains p(codes | label map), -p -m synth decodes slices from label maps alone in synth.n_steps (default: masked.n_steps)
 parallel passes and edits them through synth.discs, -p -m edit and -p -m score run under the slices' own label maps, and the guidance
-keys work as for model.prior.cond; -m detect stays refused.
+keys work as for model.prior.cond; edit.pnll_threshold reads the map under the slice's own label; -m detect stays refused, with
+detect.pseudo too.
 -p -m score scores the samples of the prior of run.resume_checkpoint against the first score.n_slices test slices (Fit.score): the
 Frechet distance, precision / recall and density / coverage in the frozen first stage's own feature space and the divergence of the
 code histograms, each beside its floor - the same score between two halves of the real slices - in <run dir>/score/score.csv and
@@ -115,8 +120,8 @@ def check_arguments(config, args):
         if prior_condition(config) is not None:
             raise NotImplementedError("-m detect with model.prior.cond: a prior conditioned on the lesion labels is told where the lesion "
                                       "is; detection needs the unconditional prior")
-        from trainers.config import prior_masked
-        if prior_masked(config) is not None:
+        from trainers.config import detect_pseudo, prior_masked
+        if prior_masked(config) is not None and detect_pseudo(config) is None:          # with detect.pseudo: MaskedPriorTrainer.detect_pseudo
             raise NotImplementedError("-m detect with model.prior.masked: detection selects the codes to restore by a raster-order "
                                       "likelihood, which the masked prior does not define; it needs the autoregressive prior")
     elif args.mode == "synth":

@@ -36,6 +36,9 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
                  config.run.resume_checkpoint    (editing with the prior, -p -m edit: keys of this project; Fit.edit)
     config.detect.{n_slices, n_candidates, temperature, top_k, top_p, seed, nll_threshold, sigma, against, weight, labels},
                  config.run.resume_checkpoint    (anomaly detection with the prior, -p -m detect: keys of this project; Fit.detect)
+    config.detect.pseudo.{threshold, stride} (optional, with model.prior.masked and detect.nll_threshold false: detection by the
+                 masked prior's pseudo-likelihood map, MaskedPriorTrainer.detect_pseudo) and config.edit.pnll_threshold with the
+                 optional edit.stride (with model.prior.masked: one more selector of -p -m edit, the same map)
 
 The focal frequency loss (use_frequency_loss) is functions.FocalFrequencyLoss, built on HIP kernels in place of the
 third-party focal-frequency-loss package.  The perceptual loss (use_perceptual_loss with perceptual_loss_type 'vgg', the
@@ -195,11 +198,51 @@ def check_edit_config(config):
         raise NotImplementedError("editing with the prior (run_vqwnet.py -p -m edit) needs edit.{%s}; missing: %s"
                                   % (", ".join(EDIT_KEYS), ", ".join(missing)))
     given = [k for k in EDIT_SELECTORS if _get(section, k) is not None]
+    selectors = EDIT_SELECTORS
+    if prior_masked(config) is not None:          # the masked prior's own selector, edit.pnll_threshold, counts among them
+        selectors = EDIT_SELECTORS + ("pnll_threshold",)
+        given += ["pnll_threshold"] if edit_pnll(config) is not None else []
+    else:
+        edit_pnll(config)                         # refused without model.prior.masked
     if len(given) != 1:
         raise NotImplementedError("editing with the prior (run_vqwnet.py -p -m edit) needs exactly one of edit.{%s}; given: %s"
-                                  % (", ".join(EDIT_SELECTORS), ", ".join(given) or "none"))
+                                  % (", ".join(selectors), ", ".join(given) or "none"))
     guidance(config, "edit")          # the optional edit.{guidance_scale, rank}
     edit_n_steps(config)              # the optional edit.n_steps of the masked prior
+
+
+def _stride(stride, where):
+    """A lattice stride [sy, sx] of a config -> (sy, sx): two integers >= 1 (the latent grid bounds them from above: the trainer)."""
+    ok = isinstance(stride, (list, tuple)) and len(stride) == 2 and all(
+        isinstance(v, int) and not isinstance(v, bool) and v >= 1 for v in stride)
+    if not ok:
+        raise ValueError("%s=%r must be [sy, sx], two integers >= 1" % (where, stride))
+    return int(stride[0]), int(stride[1])
+
+
+def _threshold(value, where):
+    """A pseudo-likelihood threshold of a config -> float: a number, not a boolean."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or value != value:
+        raise ValueError("%s=%r must be a number" % (where, value))
+    return float(value)
+
+
+def edit_pnll(config):
+    """The optional edit.pnll_threshold with the optional edit.stride -> None (absent or `false`) or (threshold, (sy, sx) or None:
+    the trainer's default (2, 2)): the masked prior picks the region itself, the codes whose pseudo-likelihood map
+    (MaskedPriorTrainer.pseudo_nll) exceeds the threshold.  Both keys need model.prior.masked; edit.stride needs
+    edit.pnll_threshold."""
+    section = _get(config, "edit")
+    thr, stride = _get(section, "pnll_threshold"), _get(section, "stride")
+    has_thr, has_stride = thr is not None and thr is not False, stride is not None and stride is not False
+    if (has_thr or has_stride) and prior_masked(config) is None:
+        raise ValueError("edit.%s selects by the pseudo-likelihood map of the masked prior and needs model.prior.masked"
+                         % ("pnll_threshold" if has_thr else "stride"))
+    if has_stride and not has_thr:
+        raise ValueError("edit.stride=%r is the lattice of edit.pnll_threshold and needs it" % (stride,))
+    if not has_thr:
+        return None
+    return _threshold(thr, "edit.pnll_threshold"), (_stride(stride, "edit.stride") if has_stride else None)
 
 
 def edit_n_steps(config):
@@ -375,11 +418,36 @@ def synth_n_steps(config):
     return n_steps
 
 
+DETECT_PSEUDO_KEYS = ("threshold", "stride")
+
+
+def detect_pseudo(config):
+    """The optional detect.pseudo = {"threshold": number, "stride": [sy, sx]} -> None (absent or `false`: detection by token_nll, the
+    autoregressive prior's) or {"threshold": float, "stride": (sy, sx)}: detection with the masked prior
+    (MaskedPriorTrainer.detect_pseudo restores the codes whose pseudo-likelihood map under the lattice `stride` exceeds `threshold`).
+    It needs model.prior.masked and refuses model.prior.masked.cond: a prior that is told where the lesion is cannot detect it."""
+    pseudo = _get(_get(config, "detect"), "pseudo")
+    if pseudo is None or pseudo is False:
+        return None
+    what = "detecting with the masked prior (run_vqwnet.py -p -m detect with detect.pseudo)"
+    if prior_masked(config) is None:
+        raise ValueError("%s: detect.pseudo is the masked prior's pseudo-likelihood selector and needs model.prior.masked; the "
+                         "autoregressive prior detects by detect.nll_threshold" % what)
+    if prior_condition(config) is not None:
+        raise NotImplementedError("%s: detect.pseudo with model.prior.masked.cond - a prior conditioned on the lesion labels is told "
+                                  "where the lesion is; detection needs the unconditional masked prior" % what)
+    missing = [k for k in DETECT_PSEUDO_KEYS if not hasattr(pseudo, k)]
+    if missing:
+        raise NotImplementedError("%s needs detect.pseudo.{%s}; missing: %s" % (what, ", ".join(DETECT_PSEUDO_KEYS), ", ".join(missing)))
+    return {"threshold": _threshold(pseudo.threshold, "detect.pseudo.threshold"), "stride": _stride(pseudo.stride, "detect.pseudo.stride")}
+
+
 def check_detect_config(config):
     """NotImplementedError unless the config describes a detection run (run_vqwnet.py -p -m detect): check_prior_config's keys,
     run.resume_checkpoint (the -p checkpoint whose prior restores), and the eleven keys of the `detect` section - n_slices (0: the
     whole test split), n_candidates, temperature, top_k, top_p, seed, nll_threshold (a number), sigma, against ('image' or
-    'reconstruction'), weight ('mask' or 'none'), labels (detect_labels).  No device work."""
+    'reconstruction'), weight ('mask' or 'none'), labels (detect_labels).  With the optional detect.pseudo (detect_pseudo: the masked
+    prior's detection) detect.nll_threshold must be `false` instead.  No device work."""
     check_prior_config(config)
     if not _get(config.run, "resume_checkpoint"):
         raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect) needs run.resume_checkpoint, the -p checkpoint "
@@ -389,7 +457,12 @@ def check_detect_config(config):
     if missing:
         raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect) needs detect.{%s}; missing: %s"
                                   % (", ".join(DETECT_KEYS), ", ".join(missing)))
-    if section.nll_threshold is None or isinstance(section.nll_threshold, bool):
+    pseudo = detect_pseudo(config)            # the masked prior's detection: detect.pseudo in place of detect.nll_threshold
+    if pseudo is not None:
+        if section.nll_threshold is not None and section.nll_threshold is not False:
+            raise ValueError("detect.nll_threshold=%r beside detect.pseudo: the masked prior restores by its pseudo-likelihood map "
+                             "(detect.pseudo.threshold) and defines no token_nll; set detect.nll_threshold to false" % (section.nll_threshold,))
+    elif section.nll_threshold is None or isinstance(section.nll_threshold, bool):
         raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect) needs a number for detect.nll_threshold, the "
                                   "token_nll above which a code is restored; missing: detect.nll_threshold")
     for key, allowed in (("against", DETECT_AGAINST), ("weight", DETECT_WEIGHT)):

@@ -545,7 +545,8 @@ class Fit:
     def edit(self):
         """`-p -m edit`: PriorTrainer.edit over the first edit.n_slices slices of the test split with the prior of
         run.resume_checkpoint; the region is edit.box (y0, y1, x0, x1 in pixels), edit.mask_path (a .npy mask at pixel or code
-        resolution) or edit.nll_threshold.  Under <run dir>/edit/: slice_<i>.png - four grey tiles side by side: the slice, its
+        resolution), edit.nll_threshold or, with the masked prior, edit.pnll_threshold (its pseudo-likelihood map under the optional
+        edit.stride).  Under <run dir>/edit/: slice_<i>.png - four grey tiles side by side: the slice, its
         reconstruction from its own codes, the best edit, the composite; codes_<i>.npy - (3, h, w) int64: the codes before,
         after, and the cell mask; edit.csv - slice, candidate, score, rank (0: the best), n_resampled.  All draws come from one
         generator seeded with edit.seed: a seed reproduces every file byte for byte."""
@@ -556,11 +557,16 @@ class Fit:
             return []
         e, tr = self.config.edit, self.trainer
         n_slices = int(e.n_slices)
+        from .config import edit_pnll
         selector = {}
         if _get(e, "box") is not None:
             selector["box"] = tuple(int(v) for v in e.box)
         elif _get(e, "mask_path") is not None:
             selector["mask"] = np.load(e.mask_path)
+        elif edit_pnll(self.config) is not None:          # the masked prior's own pick: its pseudo-likelihood map above a threshold
+            selector["pnll_threshold"], stride = edit_pnll(self.config)
+            if stride is not None:
+                selector["stride"] = stride
         else:
             selector["nll_threshold"] = float(e.nll_threshold)
         from .config import guidance, edit_n_steps
@@ -666,10 +672,13 @@ class Fit:
         token_nll, the largest value of the map, the winner's score and, with labels, the slice's positive pixels;
         with labels detect_result.csv - the eight values of ops.detection_scores over all scored pixels: the maps go into ONE
         histogram on the device (ops.score_histogram per batch), read once at the end.  All draws come from one generator seeded
-        with detect.seed: a seed reproduces every file byte for byte."""
-        from .config import detect_labels
+        with detect.seed: a seed reproduces every file byte for byte.  With model.prior.masked and detect.pseudo = {threshold, stride} it is
+        MaskedPriorTrainer.detect_pseudo instead: the codes whose pseudo-likelihood map exceeds the threshold are restored in parallel
+        passes, and detect.csv's mean_nll column holds the mean pseudo-NLL."""
+        from .config import detect_labels, detect_pseudo
         if not self.prior:
             raise ValueError("detecting needs the prior trainer (-p)")
+        pseudo = detect_pseudo(self.config)
         self._load_weights_for_test()
         if self.rank != 0:
             return None
@@ -689,9 +698,12 @@ class Fit:
                 break
             take = n_slices - done if n_slices else None
             image = self._to_device(batch)[:take]
-            out = tr.detect({"image": image}, nll_threshold=float(e.nll_threshold), n_candidates=int(e.n_candidates),
-                            temperature=float(e.temperature or 1.0), top_k=e.top_k or None, top_p=e.top_p or None,
-                            sigma=float(e.sigma or 0.0), against=e.against, weight=e.weight, generator=gen)
+            kw = dict(n_candidates=int(e.n_candidates), temperature=float(e.temperature or 1.0), top_k=e.top_k or None, top_p=e.top_p or None,
+                      sigma=float(e.sigma or 0.0), against=e.against, weight=e.weight, generator=gen)
+            if pseudo is not None:          # the masked prior: its pseudo-likelihood map selects, out["nll"] holds it
+                out = tr.detect_pseudo({"image": image}, pseudo["threshold"], stride=pseudo["stride"], **kw)
+            else:
+                out = tr.detect({"image": image}, nll_threshold=float(e.nll_threshold), **kw)
             B = image.shape[0]
             stats = [out["n_resampled"].double(), out["nll"].double().mean((1, 2)), out["map"].reshape(B, -1).max(1).values.double(),
                      out["score"].double()]

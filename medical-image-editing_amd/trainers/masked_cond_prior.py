@@ -22,7 +22,9 @@ cells ops.cells_changed reports, redrawn under the new map's tokens - and keeps 
 MaskedGPT.generate_parallel call over the B n_candidates rows; under guidance a pass runs the label's rows and the null rows side by
 side (2 B n rows) and ops.sample_guided mixes them inside the sampler.  A candidate's score is fixed_logp.double().sum(1), the
 conditional log-probabilities of its codes under the passes that fixed them; rank='gain' ranks by sum(fixed_logp - fixed_logp_u).
-nll_threshold, token_nll and detect raise as in the parent, sample_ids as in ConditionalPriorTrainer.
+nll_threshold, token_nll and detect raise as in the parent, sample_ids as in ConditionalPriorTrainer.  pseudo_nll is the parent's map
+under the batch's own label tokens and edit(pnll_threshold=) a fourth selector on it; detect_pseudo raises: a prior that is told
+where the lesion is cannot detect it.
 """
 import torch
 
@@ -155,21 +157,35 @@ class ConditionalMaskedPriorTrainer(LabelConditionMixin, MaskedPriorTrainer):
                                   top_p=top_p, generator=generator, guidance_scale=guidance_scale)["ids"]
 
     # ---------------------------------------------------------------- editing
+    def _pseudo_cond(self, batch):
+        """pseudo_nll under the batch's own label tokens: -log p(code | the other codes, the label map)."""
+        return self._cond_arg(self.cond_tokens(batch))
+
+    def detect_pseudo(self, *args, **kwargs):
+        raise NotImplementedError("ConditionalMaskedPriorTrainer.detect_pseudo: a prior that is told where the lesion is (the label map "
+                                  "it is conditioned on) cannot detect it; use the unconditional MaskedPriorTrainer (model.prior.masked "
+                                  "without cond)")
+
     @torch.no_grad()
     def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, n_steps=None, temperature=1.0, top_k=None, top_p=None,
-             generator=None, new_label=None, guidance_scale=None, rank="cond"):
+             generator=None, new_label=None, guidance_scale=None, rank="cond", pnll_threshold=None, stride=None):
         """MaskedPriorTrainer.edit under a condition, with ConditionalPriorTrainer.edit's third selector: exactly one of mask, box
         and new_label.  With mask or box the condition is the batch's own.  new_label (the batch's 'label' with the user's changes
         drawn in; same dtype and shape): the condition comes from new_label, the redrawn cells are those in which any pixel of the
         label changed (ops.cells_changed; one device-to-host read) and every other code is kept; a label unchanged everywhere
         returns the slice unchanged with the score 0.  Returns the parent's dict plus cond (B, T), the tokens of the condition, and
         label_cells (B, h, w), the same as a map over the latent.  guidance_scale and rank as in synthesize: under guidance the
-        dict gains scores_uncond.  nll_threshold raises NotImplementedError."""
+        dict gains scores_uncond.  pnll_threshold (with `stride`, default (2, 2)) is the fourth selector: the codes whose pseudo_nll
+        under the batch's own label exceeds it, redrawn under that label (one device-to-host read of the map).  nll_threshold raises
+        NotImplementedError, stride without pnll_threshold ValueError."""
         if nll_threshold is not None:
             self._no_likelihood("edit(nll_threshold=...)")
         guided, scale = self._guidance("edit", guidance_scale, rank)
-        if (mask is not None) + (box is not None) + (new_label is not None) != 1:
-            raise ValueError("ConditionalMaskedPriorTrainer.edit: exactly one of mask, box and new_label selects the region")
+        if (mask is not None) + (box is not None) + (new_label is not None) + (pnll_threshold is not None) != 1:
+            raise ValueError("ConditionalMaskedPriorTrainer.edit: exactly one of mask, box and new_label selects the region, or "
+                             "pnll_threshold in their place")
+        if stride is not None and pnll_threshold is None:
+            raise ValueError("ConditionalMaskedPriorTrainer.edit: stride=%r is the lattice of pnll_threshold and needs it" % (stride,))
         cells = None
         has_label = isinstance(batch, dict) and batch.get("label") is not None
         label_size = tuple(batch["label"].shape[-2:]) if has_label else None          # what a mask or box of an {'ids'} batch refers to
@@ -181,6 +197,8 @@ class ConditionalMaskedPriorTrainer(LabelConditionMixin, MaskedPriorTrainer):
             tokens = self.cond.tokens(self._label(new_label))
         else:
             tokens = self.cond_tokens(batch)
+            if pnll_threshold is not None:
+                cells = self._pseudo_cells(batch, pnll_threshold, stride)[0]
         out = self._edit_parallel(batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator, cells=cells,
                                   image_size=label_size, cond=self._cond_arg(tokens), guidance=(scale, rank) if guided else None)
         out["cond"], out["label_cells"] = tokens, tokens.reshape(-1, self.h, self.w)

@@ -18,7 +18,15 @@ contract and dict; a candidate's score is the sum of fixed_logp over the redrawn
 pass that fixed it, given both sides of the region.  It is a ranking among candidates of one region, not a likelihood: a
 raster-order likelihood is not defined for this model, so token_nll, the nll_threshold selector, detect and guidance raise
 NotImplementedError.  Conditioning on label maps, with guidance, is trainers/masked_cond_prior.py, through the hooks _forward_of /
-_train_forward and _edit_parallel.
+_train_forward, _pseudo_cond and _edit_parallel.
+
+What the model thinks of a slice code by code has a name of its own: pseudo_nll(batch, stride) is MaskedGPT.pseudo_nll of the
+slice's codes, -log p(code | the codes outside its lattice group) as an (h, w) map, S = sy sx passes side by side (stride (h, w): the
+exact pseudo-likelihood; (2, 2), the default: four passes; (1, 1): the all-masked marginal).  It is not a likelihood either - the
+terms do not multiply to a probability of the slice - but it is the training objective evaluated where it is asked, from both sides
+of every code.  edit(pnll_threshold=, stride=) lets it select the region (one device-to-host read), and detect_pseudo(batch,
+pnll_threshold, ...) is PriorTrainer.detect's contract and dict on it: the codes above the threshold are restored in n_steps
+parallel passes and ops.anomaly_map smooths the residual (the launcher's -p -m detect with detect.pseudo).
 """
 import numpy as np
 import torch
@@ -118,24 +126,74 @@ class MaskedPriorTrainer(PriorTrainer):
     def detect(self, *args, **kwargs):
         self._no_likelihood("detect")
 
+    # ---------------------------------------------------------------- the pseudo-likelihood map
+    def _pseudo_cond(self, batch):
+        """MaskedGPT.pseudo_nll's cond for this batch (the conditional trainer: its label tokens); here: None."""
+        return None
+
+    @torch.no_grad()
+    def pseudo_nll(self, batch, stride=(2, 2), max_rows=64):
+        """What the prior thinks of a slice code by code, from both sides: MaskedGPT.pseudo_nll of codes(batch) on the latent grid
+        -> (B, h, w) fp32, -log p(code | the codes outside its lattice group), S = sy sx passes.  stride (h, w) is the exact
+        pseudo-likelihood, (1, 1) the all-masked marginal.  Not a likelihood (its terms do not multiply to a probability of the
+        slice): a high value marks a code the prior did not expect where it stands.  token_nll stays undefined for this model."""
+        ids = self.codes(batch)
+        if ids.shape[1] != self.h * self.w:
+            raise ValueError("MaskedPriorTrainer.pseudo_nll: sequences of h w = %d codes expected, got %d" % (self.h * self.w, ids.shape[1]))
+        return self.gpt.pseudo_nll(ids, (self.h, self.w), stride=stride, max_rows=max_rows, cond=self._pseudo_cond(batch))
+
+    def _pseudo_cells(self, batch, pnll_threshold, stride):
+        """The pnll_threshold selector -> (the host bool array (B, h, w) of the codes whose pseudo_nll exceeds it, the map): one
+        device-to-host read, as PriorTrainer._edit's nll_threshold."""
+        try:
+            thr = float(pnll_threshold)
+        except (TypeError, ValueError):
+            thr = float("nan")
+        if thr != thr:
+            raise ValueError("MaskedPriorTrainer: pnll_threshold=%r must be a number (it may be infinite)" % (pnll_threshold,))
+        pnll = self.pseudo_nll(batch, stride=(2, 2) if stride is None else stride)
+        return (pnll > thr).cpu().numpy(), pnll          # the one read of the selector
+
     # ---------------------------------------------------------------- editing
     @torch.no_grad()
     def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, n_steps=None, temperature=1.0, top_k=None, top_p=None,
-             generator=None, guidance_scale=None, rank=None):
+             generator=None, guidance_scale=None, rank=None, pnll_threshold=None, stride=None):
         """PriorTrainer.edit's contract and dict on the bidirectional prior: the codes of the region (`mask` or `box`, cell_mask) are
         masked and filled in again n_candidates times by ONE MaskedGPT.generate_parallel call over the B n_candidates rows -
         n_steps (default: the trainer's) forwards, whatever the size of the region, each seeing the kept codes on both sides.  Each
         candidate's uniforms (n_steps, 2, B, T) are one torch.rand call, candidate 0 first: its codes do not depend on
         n_candidates.  A candidate's score is fixed_logp.double().sum(1), over the redrawn positions (0 elsewhere).  A slice with
-        no code selected comes back unchanged with the score 0.  nll_threshold and guidance raise NotImplementedError."""
+        no code selected comes back unchanged with the score 0.  The third selector, pnll_threshold, lets the prior pick the region:
+        the codes whose pseudo_nll (under `stride`, default (2, 2)) exceeds it, at the cost of one device-to-host read of the map.
+        nll_threshold and guidance raise NotImplementedError; stride without pnll_threshold raises ValueError."""
         if nll_threshold is not None:
             self._no_likelihood("edit(nll_threshold=...)")
         if guidance_scale is not None and float(guidance_scale) != 1.0:
             raise NotImplementedError("MaskedPriorTrainer.edit: guidance needs a conditional prior: ConditionalMaskedPriorTrainer "
                                       "(model.prior.masked.cond)")
-        if (mask is not None) + (box is not None) != 1:
-            raise ValueError("MaskedPriorTrainer.edit: exactly one of mask and box selects the region")
-        return self._edit_parallel(batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator)
+        if (mask is not None) + (box is not None) + (pnll_threshold is not None) != 1:
+            raise ValueError("MaskedPriorTrainer.edit: exactly one of mask and box selects the region, or pnll_threshold in their place")
+        if stride is not None and pnll_threshold is None:
+            raise ValueError("MaskedPriorTrainer.edit: stride=%r is the lattice of pnll_threshold and needs it" % (stride,))
+        cells = None if pnll_threshold is None else self._pseudo_cells(batch, pnll_threshold, stride)[0]
+        return self._edit_parallel(batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator, cells=cells)
+
+    # ---------------------------------------------------------------- anomaly detection
+    @torch.no_grad()
+    def detect_pseudo(self, batch, pnll_threshold, stride=(2, 2), n_candidates=4, n_steps=None, temperature=1.0, top_k=None, top_p=None,
+                      sigma=2.0, against="image", weight="mask", generator=None):
+        """PriorTrainer.detect's contract and dict on the bidirectional prior: restore the codes whose pseudo_nll (under `stride`)
+        exceeds pnll_threshold - ONE edit(pnll_threshold=...), the same draws under the same generator: n_steps parallel passes
+        whatever the region - and smooth the pixel residual between what was there and what the prior put there,
+        ops.anomaly_map(a, b, cellmask, sigma).  against and weight as in PriorTrainer.detect.  Returns its dict: map (B, H, W);
+        restored; nll (B, h, w), here the pseudo-likelihood map; cellmask (B, h, w) uint8; score (B,) float64, the winner's
+        fixed_logp sum (0 where nothing was restored); n_resampled (B,) long."""
+        if pnll_threshold is None:
+            raise ValueError("MaskedPriorTrainer.detect_pseudo: pnll_threshold selects the codes to restore and is required")
+        self._detect_checks("MaskedPriorTrainer.detect_pseudo", batch, sigma, against, weight)
+        cells, pnll = self._pseudo_cells(batch, pnll_threshold, stride)
+        out = self._edit_parallel(batch, None, None, n_candidates, n_steps, temperature, top_k, top_p, generator, cells=cells)
+        return self._detect_result(batch, out, pnll, sigma, against, weight)
 
     def _edit_parallel(self, batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator, cells=None, image_size=None,
                        cond=None, guidance=None):

@@ -493,14 +493,22 @@ class PriorTrainer(TrainerBase):
         uint8; score (B,) float64, the winner's log-probability; n_resampled (B,) long, the restored codes per slice."""
         if nll_threshold is None:
             raise ValueError("PriorTrainer.detect: nll_threshold selects the codes to restore and is required")
+        self._detect_checks("PriorTrainer.detect", batch, sigma, against, weight)
+        out, nll = self._edit(batch, None, None, nll_threshold, n_candidates, temperature, top_k, top_p, generator)
+        return self._detect_result(batch, out, nll, sigma, against, weight)
+
+    def _detect_checks(self, name, batch, sigma, against, weight):
+        """What a detection refuses before any device work (detect here, MaskedPriorTrainer.detect_pseudo)."""
         if against not in ("image", "reconstruction"):
-            raise ValueError("PriorTrainer.detect: against=%r must be 'image' or 'reconstruction'" % (against,))
+            raise ValueError("%s: against=%r must be 'image' or 'reconstruction'" % (name, against))
         if weight not in ("mask", "none"):
-            raise ValueError("PriorTrainer.detect: weight=%r must be 'mask' or 'none'" % (weight,))
+            raise ValueError("%s: weight=%r must be 'mask' or 'none'" % (name, weight))
         ops.gauss_taps(sigma)                # a bad sigma is refused before any device work
         if against == "image" and isinstance(batch, dict) and batch.get("ids") is not None:
-            raise ValueError("PriorTrainer.detect: against='image' needs a batch with an image ({'ids'} has none)")
-        out, nll = self._edit(batch, None, None, nll_threshold, n_candidates, temperature, top_k, top_p, generator)
+            raise ValueError("%s: against='image' needs a batch with an image ({'ids'} has none)" % name)
+
+    def _detect_result(self, batch, out, nll, sigma, against, weight):
+        """detect()'s dict from an edit's dict `out` and the map `nll` that selected its cells: everything behind the edit."""
         if against == "image":
             image = batch["image"] if isinstance(batch, dict) else batch
             a, b = image.to(self.device), out["composite"]
