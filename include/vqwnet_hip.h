@@ -1082,6 +1082,31 @@ size_t vqw_ball_counts_ws_bytes(long M, long N);
 int vqw_ball_counts(const float* q, const float* a, const float* r2, const float* shift, int32_t* cnt_q, int32_t* hit_a, void* ws,
                     size_t ws_bytes, long M, long N, int D, void* stream);
 
+/* ---- the seamless composite of an edit (csrc/blend.hip; ops.blend_cells, PriorTrainer.edit with blend="pyramid"; the reference has
+ * nothing like it).  Added functions only; the ABI stays 9.  Burt-Adelson multi-band blending on NHWC fp32 pictures [N][H][W][C]
+ * under the cell mask [N][h][w] bytes (non-zero: the edit; H = fy h, W = fx w).  Per image and channel, separable, clamped
+ * (replicated) borders, w = [1, 4, 6, 4, 1] / 16:
+ *   REDUCE(x)[i][j] = sum_m sum_n w[m] w[n] x[clamp(2i+m)][clamp(2j+n)], m, n = -2..2: (H, W) -> (H/2, W/2)
+ *   EXPAND(x) to (2H, 2W), along each axis in turn: [2k] = (x[k-1] + 6 x[k] + x[k+1]) / 8, [2k+1] = (x[k] + x[k+1]) / 2, clamped
+ *   M_0 = the mask at pixels (0 / 1), M_{l+1} = REDUCE(M_l); G_0 = d, G_{l+1} = REDUCE(G_l), d = edit - image, or edit - recon
+ *   when recon is not null (the difference of two decodes: the first stage's own error cancels where the codes did not change)
+ *   R_L = M_L G_L; R_l = M_l (G_l - EXPAND(G_{l+1})) + EXPAND(R_{l+1}) for l = L-1 .. 0; out = image + R_0,  L = levels.
+ * Order: every filter runs its row pass (along x) first, then its column pass, taps ascending, accumulated from the left -
+ * ((w0 x0 + w1 x1) + w2 x2) ... with the fp32 taps 0.0625, 0.25, 0.375; EXPAND is ((a + 6 b) + c) 0.125 and (b + c) 0.5; the band is
+ * m (g - eg) + er; one fp32 rounding per operation, no fused multiply-add, no float atomics: the same bits every run.  Where the
+ * mask pyramid is 0 under every tap, R_0 is exactly 0 and out has the bits of image.
+ * Plan: `levels` reduce launches (the C planes of G and the plane of M of a level through one LDS tile with a 2-pixel halo) and
+ * `levels` collapse launches (EXPAND of G and of R, the product with M and the sum fused over one LDS tile; R_L is formed while the
+ * top collapse stages).  Level 0 is never stored: image and edit (or edit and recon) are read by the first reduce and again by the
+ * last collapse, out is written once.  workspace: vqw_blend_cells_workspace(N, H, W, C, levels) floats - the planes of G_l, M_l for
+ * l = 1..L and of R_l for l = 1..L-1; the query returns 0 for arguments out of range.
+ * Refused, with a message before any launch: a null pointer (recon alone may be null); N, H, W or C < 1; levels outside [1, 12];
+ * 2^levels not dividing H or W; H % h or W % w non-zero; a workspace that is too small; N > 65535 or C > 65534;
+ * N H W (C + 1) >= 2^31; image, edit, recon, out or workspace not 16-byte aligned.  out must not be an input. */
+long vqw_blend_cells_workspace(int N, int H, int W, int C, int levels);
+int vqw_blend_cells(const float* image, const float* edit, const float* recon, const uint8_t* cellmask, float* out, float* workspace,
+                    long workspace_floats, int N, int H, int W, int C, int h, int w, int levels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1984,6 +1984,36 @@ def paste_cells(image, edit, cellmask):
     return out
 
 
+def blend_cells(image, edit, cellmask, levels, recon=None):
+    """The seamless composite of an edit: Burt-Adelson multi-band blending over `levels` pyramid levels (csrc/blend.hip; the
+    definition is in include/vqwnet_hip.h).  out = image + R_0, where R collapses the Laplacian pyramid of d under the Gaussian
+    pyramid of the cell mask; d = edit - image, or edit - recon when recon (the decode of the slice's own codes) is given.
+    image, edit, recon (B, C, H, W) fp32 in either memory format, cellmask (B, h, w) torch.uint8, H and W multiples of h, w and
+    of 2^levels, 1 <= levels <= 12 (the kernel's argument check refuses the rest).  2 levels launches.  Returns a channels_last
+    tensor.  No gradient."""
+    _dev(image, edit, cellmask, recon)
+    if isinstance(levels, bool) or not isinstance(levels, int):
+        raise RuntimeError("blend_cells: levels=%r must be an integer" % (levels,))
+    image, edit = nhwc(image.detach()), nhwc(edit.detach())
+    if image.shape != edit.shape:
+        raise RuntimeError("blend_cells: shape mismatch %s vs %s" % (tuple(image.shape), tuple(edit.shape)))
+    if recon is not None:
+        recon = nhwc(recon.detach())
+        if recon.shape != image.shape:
+            raise RuntimeError("blend_cells: shape mismatch %s vs recon %s" % (tuple(image.shape), tuple(recon.shape)))
+    N, C, H, W = image.shape
+    if cellmask.dtype != torch.uint8 or cellmask.dim() != 3 or cellmask.shape[0] != N:
+        raise RuntimeError("blend_cells: cellmask (B, h, w) torch.uint8 with B = %d expected, got %s of %s" % (N, tuple(cellmask.shape), cellmask.dtype))
+    h, w = cellmask.shape[1:]
+    if h < 1 or w < 1 or H % h or W % w:
+        raise RuntimeError("blend_cells: H = %d and W = %d must be multiples of the cell grid %d x %d" % (H, W, h, w))
+    floats = int(_L().vqw_blend_cells_workspace(N, H, W, C, levels))       # 0: out of range, and the kernel's check says which
+    ws = torch.empty(max(floats, 4), dtype=torch.float32, device=image.device)
+    out = torch.empty_like(image, memory_format=CL)
+    _L().vqw_blend_cells(image, edit, recon, cellmask.contiguous(), out, ws, ws.numel(), N, H, W, C, h, w, levels)
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # anomaly detection with the code prior (csrc/detect.hip): forward only, no gradient
 # ----------------------------------------------------------------------------------------------

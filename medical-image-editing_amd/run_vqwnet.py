@@ -18,7 +18,9 @@ epoch and resumes from run.resume_checkpoint.  -p is refused with -v, with -m te
 run.num_gpus > 1 (data-parallel prior training is not built).  -p -m edit edits slices with a trained prior (Fit.edit): the
 prior of run.resume_checkpoint redraws the codes of the region the `edit` section selects (box, mask_path or nll_threshold) in the
 first edit.n_slices test slices, edit.n_candidates times each, and keeps the likeliest; pictures, codes and scores go to
-<run dir>/edit/.  -m edit without -p is refused.  -p -m detect localises anomalies with a trained prior (Fit.detect): the prior
+<run dir>/edit/.  The optional edit.{blend, blend_levels, blend_source} blend the composite tile over a pyramid in place of the hard
+per-cell paste (ops.blend_cells; the same three keys under `synth` for its edit through the label map); absent, every file is what it
+was.  -m edit without -p is refused.  -p -m detect localises anomalies with a trained prior (Fit.detect): the prior
 of run.resume_checkpoint restores the codes whose token_nll exceeds detect.nll_threshold, the smoothed pixel residual is the
 anomaly map of a slice (ops.anomaly_map), and with detect.labels the maps are scored against the lesion labels - AUROC, average
 precision and the best Dice over all pixels (detect_result.csv beside detect.csv and the pictures in the run directory).  -m detect

@@ -160,14 +160,16 @@ class ConditionalPriorTrainer(LabelConditionMixin, PriorTrainer):
     # ---------------------------------------------------------------- editing
     @torch.no_grad()
     def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None,
-             generator=None, new_label=None, guidance_scale=None, rank="cond"):
+             generator=None, new_label=None, guidance_scale=None, rank="cond", blend=None, blend_levels=None, blend_source="edit"):
         """PriorTrainer.edit under a condition, with a fourth selector: exactly one of mask, box, nll_threshold and new_label.
         With mask, box or nll_threshold the prefix is the batch's own condition.  new_label (the batch's 'label' with the user's
         changes drawn in; same dtype and shape): the prefix comes from new_label, the redrawn cells are those in which any pixel of
         the label changed (ops.cells_changed; one device-to-host read) and every other code is kept.  Returns the parent's dict plus
         cond (B, Tc), the tokens of the prefix, and label_cells (B, h, w), the same tokens as a map over the latent.
-        guidance_scale and rank as in synthesize: under guidance the dict gains scores_uncond."""
+        guidance_scale and rank as in synthesize: under guidance the dict gains scores_uncond.  blend, blend_levels and blend_source
+        as in PriorTrainer.edit, on every selector."""
         guided, scale = self._guidance("edit", guidance_scale, rank)
+        blending = self._blending(batch, blend, blend_levels, blend_source)
         if (mask is not None) + (box is not None) + (nll_threshold is not None) + (new_label is not None) != 1:
             raise ValueError("ConditionalPriorTrainer.edit: exactly one of mask, box, nll_threshold and new_label selects the region")
         cells = None
@@ -182,7 +184,7 @@ class ConditionalPriorTrainer(LabelConditionMixin, PriorTrainer):
         else:
             tokens = self.cond_tokens(batch)
         out = self._edit(dict(batch, cond=tokens), mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator, cells=cells,
-                         image_size=label_size, guidance=(scale, rank) if guided else None)[0]
+                         image_size=label_size, guidance=(scale, rank) if guided else None, blending=blending)[0]
         out["cond"], out["label_cells"] = tokens, tokens.reshape(-1, self.h, self.w)
         return out
 

@@ -209,6 +209,52 @@ def check_edit_config(config):
                                   % (", ".join(selectors), ", ".join(given) or "none"))
     guidance(config, "edit")          # the optional edit.{guidance_scale, rank}
     edit_n_steps(config)              # the optional edit.n_steps of the masked prior
+    blend(config, "edit")             # the optional edit.{blend, blend_levels, blend_source}
+
+
+BLEND_MODES, BLEND_SOURCES, BLEND_MAX_LEVELS, BLEND_DEFAULT_LEVELS = ("paste", "pyramid"), ("edit", "delta"), 12, 3
+
+
+def default_blend_levels(fy, fx):
+    """The pyramid depth of a blended composite when none is given: min(3, the largest L with 2^L dividing both sides fy = H / h and
+    fx = W / w of a latent cell in pixels) - the mixing zone of the lowest band stays within a cell or so.  0 (a cell of odd size
+    has no pyramid) raises ValueError."""
+    fy, fx = int(fy), int(fx)
+    if fy < 1 or fx < 1:
+        raise ValueError("blend: a latent cell of %d x %d pixels" % (fy, fx))
+    levels = 0
+    while levels < BLEND_DEFAULT_LEVELS and fy % (2 << levels) == 0 and fx % (2 << levels) == 0:
+        levels += 1
+    if levels == 0:
+        raise ValueError("blend='pyramid': a latent cell of %d x %d pixels has an odd side and no pyramid; there is no default "
+                         "blend_levels for it" % (fy, fx))
+    return levels
+
+
+def check_blend(blend, blend_levels, blend_source, where=""):
+    """The three blending values of an edit -> (blend, blend_levels, blend_source) normalised, ValueError otherwise.  blend: None
+    (or `false`) and 'paste' - the hard per-cell paste, ops.paste_cells - or 'pyramid', ops.blend_cells; blend_levels: None (or
+    `false`: default_blend_levels) or an integer in [1, 12]; blend_source: 'edit' (d = edit - image) or 'delta' (d = edit - recon,
+    the difference of two decodes).  `where`: the prefix of the names in the messages.  No device work."""
+    names = tuple(where + k for k in ("blend", "blend_levels", "blend_source"))
+    blend = None if blend is None or blend is False else blend
+    if blend is not None and (not isinstance(blend, str) or blend not in BLEND_MODES):
+        raise ValueError("%s=%r is None, 'paste' or 'pyramid'" % (names[0], blend))
+    levels = None if blend_levels is None or blend_levels is False else blend_levels
+    if levels is not None and (isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= BLEND_MAX_LEVELS):
+        raise ValueError("%s=%r must be an integer in [1, %d]" % (names[1], blend_levels, BLEND_MAX_LEVELS))
+    source = "edit" if blend_source is None or blend_source is False else blend_source
+    if not isinstance(source, str) or source not in BLEND_SOURCES:
+        raise ValueError("%s=%r is 'edit' or 'delta'" % (names[2], blend_source))
+    return blend, levels, source
+
+
+def blend(config, name):
+    """The three optional blending keys of the `edit` or `synth` section `name` -> {blend, blend_levels, blend_source}, the keywords
+    of the trainers' edit(); absent (or `false`) means off: the hard paste, default levels, source 'edit'.  No device work."""
+    section = _get(config, name)
+    mode, levels, source = check_blend(_get(section, "blend"), _get(section, "blend_levels"), _get(section, "blend_source"), where=name + ".")
+    return {"blend": mode, "blend_levels": levels, "blend_source": source}
 
 
 def _stride(stride, where):
@@ -403,6 +449,7 @@ def check_synth_config(config):
             raise ValueError("synth.discs is false or a list of [cy, cx, radius, value] (got %r)" % (discs,))
     guidance(config, "synth")          # the optional synth.{guidance_scale, rank}
     synth_n_steps(config)              # the optional synth.n_steps of the masked prior
+    blend(config, "synth")             # the optional synth.{blend, blend_levels, blend_source} of the edit through the label map
 
 
 def synth_n_steps(config):

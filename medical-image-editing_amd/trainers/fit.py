@@ -547,7 +547,8 @@ class Fit:
         run.resume_checkpoint; the region is edit.box (y0, y1, x0, x1 in pixels), edit.mask_path (a .npy mask at pixel or code
         resolution), edit.nll_threshold or, with the masked prior, edit.pnll_threshold (its pseudo-likelihood map under the optional
         edit.stride).  Under <run dir>/edit/: slice_<i>.png - four grey tiles side by side: the slice, its
-        reconstruction from its own codes, the best edit, the composite; codes_<i>.npy - (3, h, w) int64: the codes before,
+        reconstruction from its own codes, the best edit, the composite (blended when edit.blend is 'pyramid', with the optional
+        edit.blend_levels and edit.blend_source: ops.blend_cells in place of the hard paste); codes_<i>.npy - (3, h, w) int64: the codes before,
         after, and the cell mask; edit.csv - slice, candidate, score, rank (0: the best), n_resampled.  All draws come from one
         generator seeded with edit.seed: a seed reproduces every file byte for byte."""
         if not self.prior:
@@ -576,6 +577,10 @@ class Fit:
         n_steps = edit_n_steps(self.config)
         if n_steps is not None:   # the masked prior's keyword: the number of parallel decoding passes
             selector.update(n_steps=n_steps)
+        from .config import blend
+        blending = blend(self.config, "edit")
+        if blending["blend"] is not None:     # edit.{blend, blend_levels, blend_source}: how the composite tile is put together
+            selector.update(blending)
         gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
         out_dir = os.path.join(self.logger.log_dir, "edit")
         os.makedirs(out_dir, exist_ok=True)
@@ -629,6 +634,9 @@ class Fit:
         n_steps = synth_n_steps(self.config)
         if n_steps is not None:   # the conditional masked prior's keyword: the number of parallel decoding passes
             kw.update(n_steps=n_steps)
+        from .config import blend
+        blending = blend(self.config, "synth")          # synth.{blend, blend_levels, blend_source}: the composite of the edit below
+        blending = blending if blending["blend"] is not None else {}
         gen = torch.Generator(device=self.device).manual_seed(int(e.seed or 0))
         out_dir = os.path.join(self.logger.log_dir, "synth")
         os.makedirs(out_dir, exist_ok=True)
@@ -649,7 +657,7 @@ class Fit:
                 yy, xx = torch.meshgrid(torch.arange(new.shape[-2], device=self.device), torch.arange(new.shape[-1], device=self.device), indexing="ij")
                 for cy, cx, radius, value in discs:
                     new.reshape(B, *new.shape[-2:])[:, (yy - int(cy)) ** 2 + (xx - int(cx)) ** 2 <= int(radius) ** 2] = int(value)
-                edited = tr.edit(step, new_label=new, generator=gen, **kw)
+                edited = tr.edit(step, new_label=new, generator=gen, **kw, **blending)
                 tiles += [grey_of(new), ops.export_grey(edited["composite"])[0].cpu().numpy()]
                 redrawn = edited["cellmask"].reshape(B, -1).sum(1).cpu().numpy()
             best, scores = out["best"].cpu().numpy(), out["scores"].cpu().numpy()

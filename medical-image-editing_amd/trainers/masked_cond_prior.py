@@ -168,7 +168,8 @@ class ConditionalMaskedPriorTrainer(LabelConditionMixin, MaskedPriorTrainer):
 
     @torch.no_grad()
     def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, n_steps=None, temperature=1.0, top_k=None, top_p=None,
-             generator=None, new_label=None, guidance_scale=None, rank="cond", pnll_threshold=None, stride=None):
+             generator=None, new_label=None, guidance_scale=None, rank="cond", pnll_threshold=None, stride=None, blend=None,
+             blend_levels=None, blend_source="edit"):
         """MaskedPriorTrainer.edit under a condition, with ConditionalPriorTrainer.edit's third selector: exactly one of mask, box
         and new_label.  With mask or box the condition is the batch's own.  new_label (the batch's 'label' with the user's changes
         drawn in; same dtype and shape): the condition comes from new_label, the redrawn cells are those in which any pixel of the
@@ -177,7 +178,9 @@ class ConditionalMaskedPriorTrainer(LabelConditionMixin, MaskedPriorTrainer):
         label_cells (B, h, w), the same as a map over the latent.  guidance_scale and rank as in synthesize: under guidance the
         dict gains scores_uncond.  pnll_threshold (with `stride`, default (2, 2)) is the fourth selector: the codes whose pseudo_nll
         under the batch's own label exceeds it, redrawn under that label (one device-to-host read of the map).  nll_threshold raises
-        NotImplementedError, stride without pnll_threshold ValueError."""
+        NotImplementedError, stride without pnll_threshold ValueError.  blend, blend_levels and blend_source as in
+        PriorTrainer.edit, on every selector."""
+        blending = self._blending(batch, blend, blend_levels, blend_source)
         if nll_threshold is not None:
             self._no_likelihood("edit(nll_threshold=...)")
         guided, scale = self._guidance("edit", guidance_scale, rank)
@@ -200,6 +203,7 @@ class ConditionalMaskedPriorTrainer(LabelConditionMixin, MaskedPriorTrainer):
             if pnll_threshold is not None:
                 cells = self._pseudo_cells(batch, pnll_threshold, stride)[0]
         out = self._edit_parallel(batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator, cells=cells,
-                                  image_size=label_size, cond=self._cond_arg(tokens), guidance=(scale, rank) if guided else None)
+                                  image_size=label_size, cond=self._cond_arg(tokens), guidance=(scale, rank) if guided else None,
+                                  blending=blending)
         out["cond"], out["label_cells"] = tokens, tokens.reshape(-1, self.h, self.w)
         return out

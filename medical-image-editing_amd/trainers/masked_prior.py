@@ -157,7 +157,8 @@ class MaskedPriorTrainer(PriorTrainer):
     # ---------------------------------------------------------------- editing
     @torch.no_grad()
     def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, n_steps=None, temperature=1.0, top_k=None, top_p=None,
-             generator=None, guidance_scale=None, rank=None, pnll_threshold=None, stride=None):
+             generator=None, guidance_scale=None, rank=None, pnll_threshold=None, stride=None, blend=None, blend_levels=None,
+             blend_source="edit"):
         """PriorTrainer.edit's contract and dict on the bidirectional prior: the codes of the region (`mask` or `box`, cell_mask) are
         masked and filled in again n_candidates times by ONE MaskedGPT.generate_parallel call over the B n_candidates rows -
         n_steps (default: the trainer's) forwards, whatever the size of the region, each seeing the kept codes on both sides.  Each
@@ -165,7 +166,9 @@ class MaskedPriorTrainer(PriorTrainer):
         n_candidates.  A candidate's score is fixed_logp.double().sum(1), over the redrawn positions (0 elsewhere).  A slice with
         no code selected comes back unchanged with the score 0.  The third selector, pnll_threshold, lets the prior pick the region:
         the codes whose pseudo_nll (under `stride`, default (2, 2)) exceeds it, at the cost of one device-to-host read of the map.
-        nll_threshold and guidance raise NotImplementedError; stride without pnll_threshold raises ValueError."""
+        nll_threshold and guidance raise NotImplementedError; stride without pnll_threshold raises ValueError.  blend, blend_levels
+        and blend_source as in PriorTrainer.edit, on every selector."""
+        blending = self._blending(batch, blend, blend_levels, blend_source)
         if nll_threshold is not None:
             self._no_likelihood("edit(nll_threshold=...)")
         if guidance_scale is not None and float(guidance_scale) != 1.0:
@@ -176,7 +179,8 @@ class MaskedPriorTrainer(PriorTrainer):
         if stride is not None and pnll_threshold is None:
             raise ValueError("MaskedPriorTrainer.edit: stride=%r is the lattice of pnll_threshold and needs it" % (stride,))
         cells = None if pnll_threshold is None else self._pseudo_cells(batch, pnll_threshold, stride)[0]
-        return self._edit_parallel(batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator, cells=cells)
+        return self._edit_parallel(batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator, cells=cells,
+                                   blending=blending)
 
     # ---------------------------------------------------------------- anomaly detection
     @torch.no_grad()
@@ -196,11 +200,11 @@ class MaskedPriorTrainer(PriorTrainer):
         return self._detect_result(batch, out, pnll, sigma, against, weight)
 
     def _edit_parallel(self, batch, mask, box, n_candidates, n_steps, temperature, top_k, top_p, generator, cells=None, image_size=None,
-                       cond=None, guidance=None):
+                       cond=None, guidance=None, blending=None):
         """edit()'s work behind its selector checks.  cells: a host bool array (B, h, w) in place of mask and box; image_size: the
         (H, W) a mask or box of a batch without a picture refers to.  cond: the conditional trainer's (tokens (B, T), table,
         null_index) - generate_parallel's, repeated per candidate here; guidance: None or (scale, rank) - the dict gains
-        scores_uncond and rank 'gain' ranks by sum(fixed_logp - fixed_logp_u)."""
+        scores_uncond and rank 'gain' ranks by sum(fixed_logp - fixed_logp_u).  blending: PriorTrainer._blending's value."""
         n = int(n_candidates)
         if n < 1:
             raise ValueError("MaskedPriorTrainer.edit: n_candidates=%r must be at least 1" % (n_candidates,))
@@ -228,8 +232,8 @@ class MaskedPriorTrainer(PriorTrainer):
             choice_temperature=self.choice_temperature, uniforms=uniforms, **kw)
         scores = fixed_logp.double().sum(1).reshape(B, n)
         if guidance is None:
-            return self._edit_result(ids, tokens, scores, scores, cells, image)
+            return self._edit_result(ids, tokens, scores, scores, cells, image, blending)
         key = (fixed_logp.double() - rest[0].double()).sum(1).reshape(B, n) if guidance[1] == "gain" else scores
-        out = self._edit_result(ids, tokens, scores, key, cells, image)
+        out = self._edit_result(ids, tokens, scores, key, cells, image, blending)
         out["scores_uncond"] = rest[0].double().sum(1).reshape(B, n)
         return out

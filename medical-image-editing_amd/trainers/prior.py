@@ -26,7 +26,8 @@ and _edit go through them.
 Editing (the launcher's -p -m edit).  token_nll(batch) is the prior's opinion of a slice code by code, -log p(code | the codes
 before it) as an (h, w) map.  edit(batch, mask | box | nll_threshold) redraws the selected codes n_candidates times with
 GPT.generate_masked, keeps every other code, scores each candidate by the log-probability of its whole sequence and pastes the best
-one back into the slice cell by cell (ops.paste_cells).
+one back into the slice cell by cell (ops.paste_cells), or, with blend='pyramid', blends it in over a pyramid (ops.blend_cells: no
+step along the boundaries of the edited cells; blend_source='delta' blends the difference of the two decodes onto the slice).
 
 Detecting (the launcher's -p -m detect).  detect(batch, nll_threshold) is one edit(nll_threshold=...) - the prior restores the codes
 it finds unlikely - and ops.anomaly_map of what was there against what the prior put there: the smoothed pixel residual, the
@@ -48,6 +49,7 @@ from networks.gpt import GPT
 from networks.vqgan_model import VQGAN
 
 from .base import TrainerBase
+from .config import check_blend, default_blend_levels
 
 
 def learning_rate(step, lr, warmup_steps=0, decay_steps=0, final_ratio=0.1):
@@ -393,7 +395,7 @@ class PriorTrainer(TrainerBase):
 
     @torch.no_grad()
     def edit(self, batch, mask=None, box=None, nll_threshold=None, n_candidates=4, temperature=1.0, top_k=None, top_p=None,
-             generator=None):
+             generator=None, blend=None, blend_levels=None, blend_source="edit"):
         """Redraw the codes of a region of every slice with the prior and keep the rest.  Exactly one selector: `mask` (a host
         array at pixel or code resolution, cell_mask), `box` = (y0, y1, x0, x1) in pixels, or `nll_threshold`, which selects the
         codes whose token_nll exceeds it - the prior picks the region itself; this costs one device-to-host read of the map.
@@ -406,16 +408,40 @@ class PriorTrainer(TrainerBase):
 
         Returns a dict: ids (B, T) the best candidate (source_ids: the slice's own codes); candidates (B, n, T) and scores (B, n) float64 in draw order; best (B,);
         cellmask (B, h, w) uint8; recon and edit, the slice's own codes and the best candidate's through decode_from_ids; and
-        composite = ops.paste_cells(image, edit, cellmask).  A {'ids'} batch has no image and no composite."""
-        return self._edit(batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator)[0]
+        composite = ops.paste_cells(image, edit, cellmask).  A {'ids'} batch has no image and no composite.
+
+        blend: None or 'paste' - that hard per-cell paste - or 'pyramid': composite = ops.blend_cells(image, edit, cellmask,
+        blend_levels, recon if blend_source == 'delta' else None), multi-band blending that leaves no step along the cells'
+        boundaries; nothing else in the dict changes.  blend_levels: the depth of the pyramid, default min(3, the largest L with 2^L
+        dividing both sides of a cell in pixels).  blend_source 'edit' blends edit - image, 'delta' the difference of the two
+        decodes edit - recon: the first stage's own error cancels where the codes did not change.  A bad value raises ValueError
+        before any device work."""
+        blending = self._blending(batch, blend, blend_levels, blend_source)
+        return self._edit(batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator, blending=blending)[0]
+
+    def _blending(self, batch, blend, blend_levels, blend_source):
+        """edit()'s three blending keywords -> None (the hard paste) or (levels, source) of ops.blend_cells; ValueError for a bad
+        value, a depth whose 2^levels does not divide the picture, or a cell of odd size without blend_levels.  Shapes only: no
+        device work.  A {'ids'} batch has no composite: its values are checked and otherwise unused."""
+        blend, levels, source = check_blend(blend, blend_levels, blend_source)
+        if blend != "pyramid" or (isinstance(batch, dict) and batch.get("ids") is not None):
+            return None
+        H, W = (batch["image"] if isinstance(batch, dict) else batch).shape[-2:]
+        if H % self.h or W % self.w:
+            raise ValueError("PriorTrainer.edit: the picture's %d x %d is no multiple of the latent's %d x %d" % (H, W, self.h, self.w))
+        if levels is None:
+            levels = default_blend_levels(H // self.h, W // self.w)
+        elif H % (1 << levels) or W % (1 << levels):
+            raise ValueError("PriorTrainer.edit: blend_levels=%d: 2^%d does not divide the picture's %d x %d" % (levels, levels, H, W))
+        return levels, source
 
     def _edit(self, batch, mask, box, nll_threshold, n_candidates, temperature, top_k, top_p, generator, cells=None, image_size=None,
-              guidance=None):
+              guidance=None, blending=None):
         """edit()'s work -> (edit()'s dict, the token_nll map (B, h, w) the nll_threshold selector computed, else None): what edit
         and detect share.  cells: a host bool array (B, h, w) in place of the three selectors (the conditional trainer's fourth);
         image_size: the (H, W) a mask or box of a batch without a picture refers to (cell_mask's default otherwise).  guidance:
         None or (scale, rank) of the conditional trainer - the null prefix runs beside the batch's, the dict gains scores_uncond
-        and rank 'gain' ranks by sum(logp - logp_u)."""
+        and rank 'gain' ranks by sum(logp - logp_u).  blending: _blending's value for the composite."""
         if cells is None and (mask is not None) + (box is not None) + (nll_threshold is not None) != 1:
             raise ValueError("PriorTrainer.edit: exactly one of mask, box and nll_threshold selects the region")
         n = int(n_candidates)
@@ -456,14 +482,15 @@ class PriorTrainer(TrainerBase):
         key = scores
         if guidance is not None and guidance[1] == "gain":
             key = (logp.double() - rest[0].double()).sum(1).reshape(B, n)
-        out = self._edit_result(ids, tokens, scores, key, cells, image)
+        out = self._edit_result(ids, tokens, scores, key, cells, image, blending)
         if guidance is not None:
             out["scores_uncond"] = rest[0].double().sum(1).reshape(B, n)
         return out, nll
 
-    def _edit_result(self, ids, tokens, scores, key, cells, image):
+    def _edit_result(self, ids, tokens, scores, key, cells, image, blending=None):
         """edit()'s dict from the drawn candidates: tokens (B n, T) in draw order, scores and the ranking key (B, n) float64, cells
-        the host bool array (B, h, w), image the slices or None ({'ids'} batch: no composite).  One device-to-host read ranks."""
+        the host bool array (B, h, w), image the slices or None ({'ids'} batch: no composite).  One device-to-host read ranks.
+        blending: None - the composite is ops.paste_cells - or _blending's (levels, source) for ops.blend_cells."""
         (B, T), n = ids.shape, scores.shape[1]
         best = torch.from_numpy(np.argmax(key.cpu().numpy(), axis=1)).to(self.device)      # the read of the ranking; first maximum
         candidates = tokens.reshape(B, n, T)
@@ -471,8 +498,11 @@ class PriorTrainer(TrainerBase):
         cellmask = torch.from_numpy(cells.astype(np.uint8)).to(self.device)
         out = {"ids": best_ids, "source_ids": ids, "candidates": candidates, "scores": scores, "best": best, "cellmask": cellmask,
                "recon": self.vqgan.decode_from_ids(ids, self.h, self.w), "edit": self.vqgan.decode_from_ids(best_ids, self.h, self.w)}
-        if image is not None:
+        if image is not None and blending is None:
             out["composite"] = ops.paste_cells(image, out["edit"], cellmask)
+        elif image is not None:
+            levels, source = blending
+            out["composite"] = ops.blend_cells(image, out["edit"], cellmask, levels, out["recon"] if source == "delta" else None)
         return out
 
     # ---------------------------------------------------------------- anomaly detection
