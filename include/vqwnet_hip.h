@@ -1003,6 +1003,51 @@ int vqw_score_histogram(const float* scores, const uint8_t* labels, long* hist, 
  * out[0..3] are NaN: that is the definition, not an error.  Refused: hist or out null, a pointer not 8-byte aligned. */
 int vqw_detection_scores(const long* hist, const long* err, double* out, void* stream);
 
+/* ---- lesion-wise detection scores: connected components of score maps (csrc/components.hip; ops.label_components,
+ * ops.component_areas, ops.lesion_match, functions/lesion_scores.py LesionScores, trainers/fit.py Fit.detect; the reference has
+ * nothing like it).  Added functions only; the ABI stays 9.  Integer atomics only (minima, counts, same-value stores), the same bits
+ * every run; no allocation and no host read inside a call; every refusal below arrives with a message before any launch.
+ * Labelling: images [N][H][W], foreground = mask byte != 0 (mask given, scores null) or score >= threshold (scores fp32 given,
+ * mask null; a NaN score is background, a NaN threshold is refused).  Two foreground pixels of ONE image are joined when they are
+ * neighbours - connectivity 4: W, E, N, S; 8: the diagonals too - never across images.  labels [N][H][W] int32: background 0, the
+ * components of image n numbered 1..counts[n] in raster order of each component's first pixel, the one with the smallest y W + x
+ * (scipy.ndimage.label's numbering: the result is canonical).  counts [N] int32.
+ * Plan, six launches, no workgroup ever waits for another (no flag, no spin, no cooperative launch: kernel boundaries order the
+ * passes): (1) a workgroup labels a 32 x 64 tile in LDS - row runs by pointer jumping, then a union-find with atomicMin links to
+ * the row above - and writes each pixel's provisional label, the GLOBAL index n H W + y W + x of its tile-local root, into the
+ * workspace; (2) the foreground pixels of a tile's top row and left column union with their neighbours in the adjacent tiles (N,
+ * else NW and NE; W, else NW and SW) in that array by the lock-free minimum rule: find both roots, atomicMin the larger root's slot
+ * with the smaller, go on from the value the atomic returned if the slot was no longer a root - parents are read with relaxed
+ * agent-scope atomic loads and the decision to stop is taken only on the atomic's return value; the root of a finished component is
+ * its smallest pixel index whatever the order of the merges; (3) every pixel walks to its root, roots are counted per chunk of
+ * 1024 pixels; (4) one workgroup per image scans the chunk counts; (5) roots take their numbers; (6) every pixel takes its
+ * root's number.  Every walk descends through strictly decreasing indices, so it ends; each also counts its steps against a bound
+ * (twice the pixel count of the launch: two walkers; four tile sizes inside a tile) and past it stops and ORs a bit into err [1] int32 (accumulated, the
+ * caller clears it once): 1 tile pass, 2 seam pass, 4 flatten pass, 8 vqw_component_areas met a label outside [0, cap].  err != 0
+ * means the result is not to be used.  ws: vqw_label_components_ws_ints(N, H, W) int32 (0 for arguments out of range).
+ * Refused: N, H or W < 1 (an empty tensor); N H W >= 2^31 (32-bit indices); connectivity not 4 or 8; both or neither of mask and
+ * scores; a null labels, counts, err or ws; scores, labels, counts, err or ws not 4-byte aligned; a workspace that is too small.
+ * Areas: areas [N][cap] int32, cleared by the call; areas[n][l - 1] = the pixels of image n with label l >= 1.  cap is the most
+ * components an H x W image can hold - ceil(H / 2) ceil(W / 2) under connectivity 8, ceil(H W / 2) under 4 - a function of the
+ * shape alone, so nothing is read back to size it; a label outside [0, cap] is not counted and sets err bit 8.  One streaming
+ * pass; the lanes of a wave that share the label of its first active lane are merged into one add by a ballot.
+ * Matching: acc [8] (torch.long), ADDED to: [0] slices = N; [1] gt_lesions = sum gt_counts; [2] gt_detected: ground-truth
+ * components that share at least one pixel with a KEPT predicted component - one whose area is >= min_size (equal is kept);
+ * [3] pred_components: the kept ones; [4] pred_false: kept components that share no pixel with any ground-truth pixel; [5] inter:
+ * pixels both kept-predicted and ground truth; [6] pred_pixels: pixels of kept components; [7] gt_pixels.  pred_areas [N][pcap] as
+ * above; a label above its image's count (or cap) is background.  One streaming pass sets the hit flags (same-value byte stores
+ * into ws, cleared by the call) and adds the three pixel counts once per wave, then one workgroup per image folds flags, the kept
+ * test and the counts into acc.  ws: vqw_lesion_match_ws_bytes(N, pcap, gcap) bytes.  Refused: an empty tensor; N H W >= 2^31;
+ * min_size < 1; pcap or gcap < 1; a null pointer; int32 tensors not 4-byte or acc not 8-byte aligned; a workspace that is too
+ * small.  (Label maps of different shapes are refused by ops.lesion_match: the C call takes one shape.) */
+long vqw_label_components_ws_ints(int N, int H, int W);
+int vqw_label_components(const uint8_t* mask, const float* scores, float threshold, int* labels, int* counts, int* err, int* ws,
+                         long ws_ints, int N, int H, int W, int connectivity, void* stream);
+int vqw_component_areas(const int* labels, int* areas, int* err, int N, int H, int W, int cap, void* stream);
+long vqw_lesion_match_ws_bytes(int N, int pcap, int gcap);
+int vqw_lesion_match(const int* pred_labels, const int* pred_counts, const int* pred_areas, const int* gt_labels, const int* gt_counts,
+                     long* acc, uint8_t* ws, long ws_bytes, int N, int H, int W, int pcap, int gcap, int min_size, void* stream);
+
 /* ---- the bidirectional masked code prior (csrc/masked_prior.hip; networks.MaskedGPT, trainers.MaskedPriorTrainer; MaskGIT's
  * recipe: fill in masked codes, decode in a few parallel passes).  Added functions only; the ABI stays 9.  Integer LDS atomics only,
  * no float atomics: the same bits every run.  One workgroup per sample; 1 <= B <= 65535, 1 <= T <= 65536, T a multiple of nothing.

@@ -8,3 +8,4 @@ from .perceptual_loss import VGGLoss  # noqa: F401
 from .lpips_loss import LPIPSLoss  # noqa: F401
 from .metrics import MeanSquaredError, StructuralSimilarityIndexMeasure, PeakSignalNoiseRatio, label_entropy  # noqa: F401
 from .sample_scores import FeatureStats, Moments, frechet_distance, manifold_scores, code_scores, sample_scores  # noqa: F401
+from .lesion_scores import LesionScores, derived_scores, lesion_csv_row, LESION_SCORES, LESION_CSV  # noqa: F401

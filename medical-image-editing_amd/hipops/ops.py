@@ -2107,6 +2107,126 @@ def detection_scores(hist, err=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# lesion-wise detection scores (csrc/components.hip): connected components, their areas, the matching
+# ----------------------------------------------------------------------------------------------
+LESION_ACC = ("slices", "gt_lesions", "gt_detected", "pred_components", "pred_false", "inter", "pred_pixels", "gt_pixels")
+
+
+def component_cap(H, W, connectivity=8):
+    """The most components an H x W image can hold: ceil(H / 2) ceil(W / 2) under connectivity 8, ceil(H W / 2) under 4."""
+    if connectivity not in (4, 8):
+        raise RuntimeError("component_cap: connectivity=%r must be 4 or 8" % (connectivity,))
+    return ((H + 1) // 2) * ((W + 1) // 2) if connectivity == 8 else (H * W + 1) // 2
+
+
+def _component_map(name, what, t):
+    if t.dtype != torch.int32 or t.dim() != 3:
+        raise RuntimeError("%s: %s (N, H, W) torch.int32 expected, got %s of %s" % (name, what, tuple(t.shape), t.dtype))
+    return t.contiguous()
+
+
+def _component_counts(name, what, t, N):
+    if t.dtype != torch.int32 or tuple(t.shape) != (N,):
+        raise RuntimeError("%s: %s (%d,) torch.int32 expected, got %s of %s" % (name, what, N, tuple(t.shape), t.dtype))
+    return t.contiguous()
+
+
+def label_components(x, threshold=None, connectivity=8, err=None):
+    """Connected components of the images x (N, H, W) -> (labels (N, H, W) torch.int32, counts (N,) torch.int32, err (1,)
+    torch.int32).  x torch.uint8 (or torch.bool): foreground = non-zero; with `threshold` x is fp32 and foreground = x >= threshold
+    (a NaN score is background).  connectivity 4 or 8, per image, never across images.  Background is 0; the components of image
+    n are numbered 1..counts[n] in raster order of each component's first pixel (scipy.ndimage.label's numbering).  err is the
+    kernels' error word (vqw_label_components in include/vqwnet_hip.h): 0 unless a walk passed its step bound, which no input
+    can cause - a result with err != 0 is not to be used; it is left on the device so that the call makes no host read.  With
+    `err` given (a (1,) torch.int32 tensor) the bits are ORed into it and it is the one returned: an accumulator keeps one word."""
+    _dev(x, err)
+    if x.dim() != 3:
+        raise RuntimeError("label_components: x (N, H, W) expected, got shape %s" % (tuple(x.shape),))
+    if x.numel() == 0:
+        raise RuntimeError("label_components: an empty tensor %s is refused" % (tuple(x.shape),))
+    if connectivity not in (4, 8):
+        raise RuntimeError("label_components: connectivity=%r must be 4 or 8" % (connectivity,))
+    mask = scores = None
+    if threshold is None:
+        if x.dtype == torch.bool:
+            x = x.contiguous().view(torch.uint8)
+        if x.dtype != torch.uint8:
+            raise RuntimeError("label_components: without a threshold x is torch.uint8 (foreground = non-zero), got %s" % x.dtype)
+        mask = x.contiguous()
+    else:
+        if x.dtype != torch.float32:
+            raise RuntimeError("label_components: with a threshold x is torch.float32 (foreground = x >= threshold), got %s" % x.dtype)
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise RuntimeError("label_components: the threshold is NaN")
+        scores = x.detach().contiguous()
+    N, H, W = x.shape
+    if N * H * W >= 2 ** 31:
+        raise RuntimeError("label_components: N H W = %d must stay below 2^31 (32-bit pixel indices)" % (N * H * W))
+    L = _L()
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=x.device)
+    counts = torch.empty(N, dtype=torch.int32, device=x.device)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=x.device)
+    elif err.dtype != torch.int32 or err.numel() != 1:
+        raise RuntimeError("label_components: err (1,) torch.int32 expected, got %s of %s" % (tuple(err.shape), err.dtype))
+    ws = torch.empty(max(int(L.vqw_label_components_ws_ints(N, H, W)), 4), dtype=torch.int32, device=x.device)
+    L.vqw_label_components(mask, scores, 0.0 if threshold is None else threshold, labels, counts, err, ws, ws.numel(), N, H, W, connectivity)
+    return labels, counts, err
+
+
+def component_areas(labels, counts, connectivity=8, err=None):
+    """(N, cap) torch.int32: entry [n][l - 1] is the pixel count of component l of image n, entries past counts[n] are 0.  cap =
+    component_cap(H, W, connectivity), a function of the shape alone: pass the connectivity the labels were made with (4 gives
+    the larger cap, which holds either).  A label outside [0, cap] is not counted and sets bit 8 of err (1,) torch.int32 when
+    given (label_components' error word).  `counts` is checked for its shape only: the areas follow from the labels."""
+    _dev(labels, counts, err)
+    labels = _component_map("component_areas", "labels", labels)
+    N, H, W = labels.shape
+    if labels.numel() == 0:
+        raise RuntimeError("component_areas: an empty tensor %s is refused" % (tuple(labels.shape),))
+    _component_counts("component_areas", "counts", counts, N)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=labels.device)
+    elif err.dtype != torch.int32 or err.numel() != 1:
+        raise RuntimeError("component_areas: err (1,) torch.int32 expected, got %s of %s" % (tuple(err.shape), err.dtype))
+    cap = component_cap(H, W, connectivity)
+    areas = torch.empty((N, cap), dtype=torch.int32, device=labels.device)
+    _L().vqw_component_areas(labels, areas, err, N, H, W, cap)
+    return areas
+
+
+def new_lesion_acc(device, k=1):
+    """(k, 8) torch.long, zeroed: one row of lesion_match's counters (LESION_ACC names them) per threshold."""
+    return torch.zeros((int(k), len(LESION_ACC)), dtype=torch.long, device=device)
+
+
+def lesion_match(pred_labels, pred_counts, pred_areas, gt_labels, gt_counts, min_size, acc):
+    """Adds the matching of predicted against ground-truth components to acc (8,) torch.long IN PLACE (LESION_ACC; the definitions
+    are vqw_lesion_match's in include/vqwnet_hip.h): a predicted component is kept when its area is >= min_size; a ground-truth
+    component is detected when it shares a pixel with a kept one; a kept one that shares no pixel with the ground truth is false.
+    pred_areas: component_areas(pred_labels, pred_counts, ...).  No host read.  Returns None."""
+    _dev(pred_labels, pred_counts, pred_areas, gt_labels, gt_counts, acc)
+    pred_labels, gt_labels = _component_map("lesion_match", "pred_labels", pred_labels), _component_map("lesion_match", "gt_labels", gt_labels)
+    if pred_labels.shape != gt_labels.shape:
+        raise RuntimeError("lesion_match: label maps of different shapes: pred_labels %s, gt_labels %s" % (tuple(pred_labels.shape), tuple(gt_labels.shape)))
+    N, H, W = pred_labels.shape
+    if pred_labels.numel() == 0:
+        raise RuntimeError("lesion_match: an empty tensor %s is refused" % (tuple(pred_labels.shape),))
+    pred_counts, gt_counts = _component_counts("lesion_match", "pred_counts", pred_counts, N), _component_counts("lesion_match", "gt_counts", gt_counts, N)
+    if pred_areas.dtype != torch.int32 or pred_areas.dim() != 2 or pred_areas.shape[0] != N or pred_areas.shape[1] < 1 or not pred_areas.is_contiguous():
+        raise RuntimeError("lesion_match: pred_areas (%d, cap) torch.int32, contiguous, expected, got %s of %s" % (N, tuple(pred_areas.shape), pred_areas.dtype))
+    if isinstance(min_size, bool) or not isinstance(min_size, int) or min_size < 1:
+        raise RuntimeError("lesion_match: min_size=%r must be an integer >= 1" % (min_size,))
+    if acc.dtype != torch.long or tuple(acc.shape) != (len(LESION_ACC),) or not acc.is_contiguous():
+        raise RuntimeError("lesion_match: acc (%d,) torch.long, contiguous, expected, got %s of %s" % (len(LESION_ACC), tuple(acc.shape), acc.dtype))
+    L = _L()
+    pcap, gcap = pred_areas.shape[1], component_cap(H, W, 4)          # the ground truth's connectivity is not known here: 4's cap holds either
+    ws = torch.empty(max(int(L.vqw_lesion_match_ws_bytes(N, pcap, gcap)), 16), dtype=torch.uint8, device=acc.device)
+    L.vqw_lesion_match(pred_labels, pred_counts, pred_areas, gt_labels, gt_counts, acc, ws, ws.numel(), N, H, W, pcap, gcap, int(min_size))
+
+
+# ----------------------------------------------------------------------------------------------
 # scores of the prior's samples (csrc/sample_scores.hip): feature rows (N, D) fp32, used as fp32(x - shift)
 # ----------------------------------------------------------------------------------------------
 FEATURE_MAX_D = 2048

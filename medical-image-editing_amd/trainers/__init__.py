@@ -15,6 +15,7 @@ from .masked_prior import MaskedPriorTrainer  # noqa: F401
 from .masked_cond_prior import ConditionalMaskedPriorTrainer  # noqa: F401
 from .config import prior_masked, edit_n_steps, synth_n_steps  # noqa: F401
 from .config import detect_pseudo, edit_pnll  # noqa: F401
+from .config import detect_lesionwise  # noqa: F401
 from .config import blend, check_blend, default_blend_levels  # noqa: F401
 from .evaluation import Evaluator, write_result_csv  # noqa: F401
 from .fit import Fit, InferenceModels, build_loader  # noqa: F401

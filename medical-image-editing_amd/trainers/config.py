@@ -39,6 +39,8 @@ set_transform (trainers/base.py:189-237, 164-183, 261-282) with the reference's 
     config.detect.pseudo.{threshold, stride} (optional, with model.prior.masked and detect.nll_threshold false: detection by the
                  masked prior's pseudo-likelihood map, MaskedPriorTrainer.detect_pseudo) and config.edit.pnll_threshold with the
                  optional edit.stride (with model.prior.masked: one more selector of -p -m edit, the same map)
+    config.detect.lesionwise.{thresholds, min_size, connectivity} (optional, with detect.labels: lesion-wise scores of the maps,
+                 functions.LesionScores; detect_lesionwise)
 
 The focal frequency loss (use_frequency_loss) is functions.FocalFrequencyLoss, built on HIP kernels in place of the
 third-party focal-frequency-loss package.  The perceptual loss (use_perceptual_loss with perceptual_loss_type 'vgg', the
@@ -489,12 +491,44 @@ def detect_pseudo(config):
     return {"threshold": _threshold(pseudo.threshold, "detect.pseudo.threshold"), "stride": _stride(pseudo.stride, "detect.pseudo.stride")}
 
 
+DETECT_LESIONWISE_KEYS = ("thresholds", "min_size", "connectivity")
+
+
+def detect_lesionwise(config):
+    """The optional detect.lesionwise = {"thresholds": [...], "min_size": int, "connectivity": 4 | 8} -> None (absent or `false`: pixel-wise
+    scores only) or {"thresholds": [float, ...], "min_size": int, "connectivity": int}: lesion-wise scores of the maps at every
+    threshold (functions.LesionScores: connected components of the thresholded map against those of the labels; Fit.detect writes
+    detect_lesions.csv).  Thresholds are finite numbers >= 0, at least one; predicted components smaller than min_size >= 1 pixels
+    are dropped.  It needs detect.labels: there is nothing to match without a ground truth."""
+    section = _get(_get(config, "detect"), "lesionwise")
+    if section is None or section is False:
+        return None
+    what = "lesion-wise detection scores (run_vqwnet.py -p -m detect with detect.lesionwise)"
+    missing = [k for k in DETECT_LESIONWISE_KEYS if not hasattr(section, k)]
+    if missing:
+        raise NotImplementedError("%s needs detect.lesionwise.{%s}; missing: %s" % (what, ", ".join(DETECT_LESIONWISE_KEYS), ", ".join(missing)))
+    thresholds = section.thresholds
+    ok = isinstance(thresholds, (list, tuple)) and len(thresholds) >= 1 and all(
+        isinstance(t, (int, float)) and not isinstance(t, bool) and t == t and 0 <= t < float("inf") for t in thresholds)
+    if not ok:
+        raise ValueError("detect.lesionwise.thresholds=%r must be a list of at least one finite number >= 0" % (thresholds,))
+    if isinstance(section.min_size, bool) or not isinstance(section.min_size, int) or section.min_size < 1:
+        raise ValueError("detect.lesionwise.min_size=%r must be an integer >= 1" % (section.min_size,))
+    if isinstance(section.connectivity, bool) or section.connectivity not in (4, 8):
+        raise ValueError("detect.lesionwise.connectivity=%r must be 4 or 8" % (section.connectivity,))
+    if detect_labels(config) == (None, None):
+        raise ValueError("%s matches components against the ground truth and needs detect.labels (a modality name or "
+                         "{\"synthetic\": {...}}); detect.labels is false" % what)
+    return {"thresholds": [float(t) for t in thresholds], "min_size": int(section.min_size), "connectivity": int(section.connectivity)}
+
+
 def check_detect_config(config):
     """NotImplementedError unless the config describes a detection run (run_vqwnet.py -p -m detect): check_prior_config's keys,
     run.resume_checkpoint (the -p checkpoint whose prior restores), and the eleven keys of the `detect` section - n_slices (0: the
     whole test split), n_candidates, temperature, top_k, top_p, seed, nll_threshold (a number), sigma, against ('image' or
     'reconstruction'), weight ('mask' or 'none'), labels (detect_labels).  With the optional detect.pseudo (detect_pseudo: the masked
-    prior's detection) detect.nll_threshold must be `false` instead.  No device work."""
+    prior's detection) detect.nll_threshold must be `false` instead.  The optional detect.lesionwise is read by detect_lesionwise.
+    No device work."""
     check_prior_config(config)
     if not _get(config.run, "resume_checkpoint"):
         raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect) needs run.resume_checkpoint, the -p checkpoint "
@@ -517,6 +551,7 @@ def check_detect_config(config):
             raise NotImplementedError("detecting with the prior (run_vqwnet.py -p -m detect): detect.%s is one of %s (got %r)"
                                       % (key, ", ".join(repr(a) for a in allowed), getattr(section, key)))
     detect_labels(config)
+    detect_lesionwise(config)          # the optional lesion-wise scores
 
 
 SCORE_KEYS = ("n_slices", "n_samples", "batch_size", "k", "temperature", "top_k", "top_p", "against", "seed", "guidance_scale")

@@ -682,11 +682,15 @@ class Fit:
         histogram on the device (ops.score_histogram per batch), read once at the end.  All draws come from one generator seeded
         with detect.seed: a seed reproduces every file byte for byte.  With model.prior.masked and detect.pseudo = {threshold, stride} it is
         MaskedPriorTrainer.detect_pseudo instead: the codes whose pseudo-likelihood map exceeds the threshold are restored in parallel
-        passes, and detect.csv's mean_nll column holds the mean pseudo-NLL."""
-        from .config import detect_labels, detect_pseudo
+        passes, and detect.csv's mean_nll column holds the mean pseudo-NLL.  With detect.lesionwise = {thresholds, min_size,
+        connectivity} (and labels) every batch's map also goes to functions.LesionScores, and detect_lesions.csv holds one row per
+        threshold - threshold, slices, gt_lesions, gt_detected, sensitivity, pred_components, pred_false, fp_per_slice, precision, f1,
+        dice_filtered - read once at the end and returned under "lesionwise"; without the section no file is added or changed."""
+        from .config import detect_labels, detect_lesionwise, detect_pseudo
         if not self.prior:
             raise ValueError("detecting needs the prior trainer (-p)")
         pseudo = detect_pseudo(self.config)
+        lesionwise = detect_lesionwise(self.config)
         self._load_weights_for_test()
         if self.rank != 0:
             return None
@@ -700,6 +704,10 @@ class Fit:
         out_dir = self.logger.log_dir
         os.makedirs(out_dir, exist_ok=True)
         hist, err = ops.new_score_histogram(self.device)
+        lesions_acc = None
+        if lesionwise is not None:
+            from functions import LesionScores
+            lesions_acc = LesionScores(lesionwise["thresholds"], lesionwise["min_size"], lesionwise["connectivity"])
         per_slice, done = [], 0                          # device tensors per batch: read once, after the loop
         for batch in loader:
             if n_slices and done >= n_slices:
@@ -721,6 +729,8 @@ class Fit:
                     raise ValueError("detect: a label of %d pixels per slice for a map of %d" % (label.shape[1], out["map"][0].numel()))
                 label = (label != 0).to(torch.uint8)
                 ops.score_histogram(out["map"], label, hist, err)
+                if lesions_acc is not None:
+                    lesions_acc.update(out["map"], label.reshape(out["map"].shape))
                 stats.append(label.sum(1, dtype=torch.long).double())
             per_slice.append(torch.stack(stats, dim=1))
             if done < n_save:
@@ -743,6 +753,15 @@ class Fit:
                 f.write("auroc,ap,best_dice,best_threshold,P,N,err_free,err\n")
                 f.write("%.17g,%.17g,%.17g,%.9g,%d,%d,%d,%d\n" % (result["auroc"], result["ap"], result["best_dice"], result["best_threshold"],
                                                                int(result["P"]), int(result["N"]), int(result["err_free"]), result["err"]))
+            if lesions_acc is not None:
+                from functions import LESION_CSV, lesion_csv_row
+                result["lesionwise"] = lesions_acc.result()          # the one read of the lesion-wise counts
+                if any(r["err"] for r in result["lesionwise"]):
+                    raise RuntimeError("detect: the component kernels reported error word %d" % result["lesionwise"][0]["err"])
+                with open(os.path.join(out_dir, "detect_lesions.csv"), "w") as f:
+                    f.write(",".join(LESION_CSV) + "\n")
+                    for r in result["lesionwise"]:
+                        f.write(lesion_csv_row(r) + "\n")
         self.print("Detection results are saved: {}".format(out_dir))
         return result
 
